@@ -94,12 +94,72 @@ def build_inputs(args, total_steps, ctx=None):
         scans = synth.raycast_scans_gpu(truth, m["origin"], float(m["mpc"]), poses, 1_000_000, 100_000, ctx, max_range=max_range,
                                         noise_sigma=0.005, rng=rng)
     else:
-        scans = []
-        for k in range(1, len(poses)):
-            scans.append(synth.raycast_scan(truth, m["origin"], float(m["mpc"]), poses[k - 1], poses[k], 1_000_000 + k * 100_000,
-                                            max_range=max_range, noise_sigma=0.005, rng=rng))
+        scans = raycast_scans_host(truth, m["origin"], float(m["mpc"]), poses, 1_000_000, 100_000, max_range=max_range,
+                                   noise_sigma=0.005, rng=rng)
     rands = np.random.default_rng(99).integers(0, 2**31 - 1, size=total_steps + 4)
     return m, truth, poses, odo, scans, rands
+
+
+def raycast_scans_host(truth, origin, mpc, poses, t0_us, dt_us, rays=None, max_range=None, noise_sigma=0.0, rng=None, block=64, chunk=32):
+    """The scans synth.raycast_scan casts along `poses` (scan k - 1 from poses[k - 1] to poses[k], ending at t0_us + k dt_us), bit
+    for bit, at a fraction of its cost, so that input synthesis stays a small part of a long run.  The same per-scan expressions
+    give every ray's origin and direction (the same numpy calls on the same arrays); the march then runs over the rays of `block`
+    scans at once, `chunk` samples at a time, and a ray leaves it at its first stop -- every sample it looks at is the same
+    elementwise arithmetic on the same operands.  Blocks are marched on up to 16 host threads (numpy releases the interpreter
+    lock in its loops); the noise is drawn from `rng` afterwards, scan after scan, as the loop over raycast_scan draws it."""
+    from concurrent.futures import ThreadPoolExecutor
+    from botlab_amd import synth
+    rays = synth.RAYS if rays is None else rays
+    max_range = synth.MAX_RANGE if max_range is None else max_range
+    h, w = truth.shape
+    i = np.arange(rays)
+    frac = (i + 1) / rays
+    thetas = (2.0 * np.pi * i / rays).astype(np.float32)
+    step = mpc / 2.0
+    nsteps = int(max_range / step)
+    ks = np.arange(1, nsteps + 1) * step
+    n = len(poses) - 1
+
+    def march(b0):
+        nb = min(block, n - b0)
+        px, py, c, s = (np.empty((nb, rays)) for _ in range(4))
+        for j in range(nb):
+            pb, pe = poses[b0 + j], poses[b0 + j + 1]
+            px[j] = pb[0] + (pe[0] - pb[0]) * frac
+            py[j] = pb[1] + (pe[1] - pb[1]) * frac
+            dth = np.arctan2(np.sin(pe[2] - pb[2]), np.cos(pe[2] - pb[2]))
+            ang = (pb[2] + dth * frac) - thetas
+            c[j], s[j] = np.cos(ang), np.sin(ang)
+        px, py, c, s = px.ravel(), py.ravel(), c.ravel(), s.ravel()
+        ranges = np.full(nb * rays, max_range)
+        live = np.arange(nb * rays)
+        for j0 in range(0, nsteps, chunk):
+            k = ks[j0:j0 + chunk]
+            cx = np.floor(((px[live, None] + c[live, None] * k[None, :]) - origin[0]) / mpc).astype(np.int64)
+            cy = np.floor(((py[live, None] + s[live, None] * k[None, :]) - origin[1]) / mpc).astype(np.int64)
+            inside = (cx >= 0) & (cx < w) & (cy >= 0) & (cy < h)
+            occ = np.zeros_like(inside)
+            occ[inside] = truth[cy[inside], cx[inside]] > 0
+            stop = occ | ~inside
+            stopped = stop.any(axis=1)
+            first = stop.argmax(axis=1)
+            hit = stopped & occ[np.arange(len(live)), first]            # a ray that leaves the grid keeps max_range
+            ranges[live[hit]] = k[first[hit]]
+            live = live[~stopped]
+            if not len(live):
+                break
+        return ranges.reshape(nb, rays)
+
+    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
+        blocks = list(ex.map(march, range(0, n, block)))
+    times_back = (rays - 1 - i) * synth.RAY_DT_US
+    scans = []
+    for r in (row for ranges in blocks for row in ranges):
+        if noise_sigma > 0.0:
+            r = r + rng.normal(0.0, noise_sigma, size=rays)
+        t_end = t0_us + (len(scans) + 1) * dt_us
+        scans.append(synth.LidarScan(r.astype(np.float32), thetas.copy(), (t_end - times_back).astype(np.int64), utime=int(t_end)))
+    return scans
 
 
 def record_exploration(args, total_steps, ctx, m, truth, start, rands):
@@ -185,6 +245,39 @@ def pick_goal(dist_cells, origin, start_xy, radius, max_l1_cells):
         return None
     k = np.argmax(np.where(ok, l1, -1))
     return (float(origin[0]) + (xs[k] + 0.5) * 0.05, float(origin[1]) + (ys[k] + 0.5) * 0.05)
+
+
+DUMP_MAP_CELLS = 2_000_000          # --dump-outputs: a larger map is stored as a fixed, seeded sample of this many cells (24 MB with
+DUMP_PARTICLES = 300_000            # the indices), a larger particle set as one of this many particles (24 MB): < 64 MB in all
+
+
+def dump_outputs(dirpath, pose, path, cells, particles):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy --
+    pose.npy       (4,) float64      the pose estimate: utime, x, y, theta
+    path.npy       (L, 4) float64    the replanned path, one row per pose (runs with a replan only)
+    map.npy        (H, W) float32    the log-odds map after the step's update (map_sample.npy + map_sample_index.npy, flat
+                                     cell indices, for maps of more than DUMP_MAP_CELLS cells)
+    particles.npy  (n, 9) float64    utime, x, y, theta, parent utime, x, y, theta, weight -- the particles this process holds
+                                     (particles_index.npy for sets of more than DUMP_PARTICLES)."""
+    os.makedirs(dirpath, exist_ok=True)
+    out = {"pose": np.array([pose.utime, pose.x, pose.y, pose.theta], np.float64)}
+    if path is not None:
+        out["path"] = np.array([(p.utime, p.x, p.y, p.theta) for p in path], np.float64).reshape(-1, 4)
+    flat = cells.astype(np.float32).ravel()
+    if flat.size > DUMP_MAP_CELLS:
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, DUMP_MAP_CELLS, replace=False))
+        out["map_sample"], out["map_sample_index"] = flat[idx], idx.astype(np.float64)
+    else:
+        out["map"] = flat.reshape(cells.shape)
+    cols = ("utime", "x", "y", "theta", "p_utime", "p_x", "p_y", "p_theta", "weight")
+    parts = np.stack([particles[c].astype(np.float64) for c in cols], axis=1)
+    if len(parts) > DUMP_PARTICLES:
+        idx = np.sort(np.random.default_rng(1).choice(len(parts), DUMP_PARTICLES, replace=False))
+        parts, out["particles_index"] = parts[idx], idx.astype(np.float64)
+    out["particles"] = parts
+    assert sum(a.nbytes for a in out.values()) < 64 << 20
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def cpu_baseline(args, m, odo, scans, rands, goal, n_steps):
@@ -674,12 +767,13 @@ def summary_of(out):
     return s or None
 
 
-def emit(out, json_fd, full):
-    """Detail record first (stderr + gpurun_out/bench_detail.json), then ONE compact line on stdout (the full record instead for
-    --full-line: the child runs of other_configs and the profile collector read it)."""
+def emit(out, json_fd, full_record, detail):
+    """With `detail` (a --full run), the detail record first (stderr, and a bench_detail.json under the repository's root); then
+    ONE compact line on stdout (the full record instead for --full-line: the child runs of other_configs and the profile
+    collector read it)."""
     out["summary"] = summary_of(out)
     detail_path = None
-    if not full:
+    if detail and not full_record:
         try:
             d = os.path.join(ROOT, "gpurun_out")
             os.makedirs(d, exist_ok=True)
@@ -693,7 +787,7 @@ def emit(out, json_fd, full):
         sys.stderr.flush()
         out["detail"] = ("gpurun_out/bench_detail.json and the [bench-detail] line on stderr: other_configs, astar_fixtures, same_search, latency, "
                          "explore, streaming_kernels, host times") if detail_path else "the [bench-detail] line on stderr"
-    line = json.dumps(out if full else compact_line(out))
+    line = json.dumps(out if full_record else compact_line(out))
     sys.stdout.flush()
     os.write(json_fd, (line + "\n").encode())
 
@@ -742,9 +836,17 @@ def main():
     ap.add_argument("--astar-fixtures", action="store_true", help="only the reference's own A* table (astar_test's six maps): one JSON line")
     ap.add_argument("--sub", action="store_true", help="a child run of the default invocation (other_configs): no children of its own; prints the full record")
     ap.add_argument("--full-line", action="store_true", help="print the full record on stdout instead of the compact line (tools; --sub implies it)")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run: skip the short runs of configs 4 and 5")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full run: skip the short runs of the other configurations")
     ap.add_argument("--other-steps", type=int, default=1000, help="timed steps of each other_configs run")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the other_configs child runs (default "
+                    "preset), the per-stage kernel pass, the streaming kernels, the CPU baseline, same_search, the reference's A* table "
+                    "and the detail record.  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them computed "
+                    "as DIR/<name>.npy (float32 / float64, < 64 MB in all): pose, path (with a replan), map, particles")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full or args.sub                   # a child run of --full is part of it
     presets = {3: dict(particles=1_000_000, no_astar=True, map="convex_10mx10m_5cm"),     # slam.cpp:36-45: --localization-only <map>
                4: dict(grid=2000, lanes=3, batch=64, depth=256),
                5: dict(grid=4096, particles=256_000, lanes=3, batch=16, depth=64)}
@@ -769,7 +871,8 @@ def main():
         os.close(json_fd)
         raise SystemExit(self_launch(args.gpus))
     other = None
-    if args.config == 0 and args.gpus == 1 and args.grid == 200 and not args.sub and not args.no_other_configs and "WORLD_SIZE" not in os.environ:
+    if (args.full and args.config == 0 and args.gpus == 1 and args.grid == 200 and not args.sub and not args.no_other_configs
+            and "WORLD_SIZE" not in os.environ):
         other = run_other_configs(args.other_steps, 150)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -960,6 +1063,7 @@ def main():
         in_flight.append(k)
 
     last_pose = [None]
+    last_path = [None]
 
     def fetch():
         # hands back the pose and the path of the oldest enqueued step (waits for that step only)
@@ -968,6 +1072,7 @@ def main():
             path, st = aplanner.fetch(return_stats=True)
             pops_total[0] += st[0]
             last_pose[0] = path[0]               # the start pose of the path is that step's pose estimate
+            last_path[0] = path
             return path[0]
         return None
 
@@ -1090,37 +1195,41 @@ def main():
         drain()                      # the explorer's last steps (and their plans), outside the timed region
         torch.cuda.synchronize()
         tail_s = time.perf_counter() - t_tail
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, before anything else runs on the filter or the map
+        dump_outputs(args.dump_outputs, pose, last_path[0] if goal_pose is not None else None, grid.cells(), engine.pf.particles())
     main_ms_total, main_n = ctx.timing_get(_capi.BL_K_MCL_MAIN)
     host_ms = (1e3 * host_t[0] / args.steps, 1e3 * host_t[1] / args.steps)
     slowest = sorted(step_wall, reverse=True)[:4]
     pops_timed = pops_total[0]
     final_pose, final_k = pose, k
-    # per-stage kernel times: a short untimed pass with every timer on (events between launches cost a few us each, so
-    # they stay out of the timed region)
-    ctx.timing_reset()
-    ctx.timing_enable(True)
-    aplanner.timing(1)
-    for _ in range(min(args.steps, 30, total - k - 1)):
-        step(k)
-        k += 1
-    drain()
-    torch.cuda.synchronize()
-    ctx.timing_enable(False)
-    stage_ms = {}
-    for name, kid in (("mcl_main", _capi.BL_K_MCL_MAIN), ("mcl_scan", _capi.BL_K_MCL_SCAN), ("map", _capi.BL_K_MAP)):
-        ms, n = ctx.timing_get(kid)
-        stage_ms[name] = (ms / n if n else 0.0, n)
-    d_ms, a_ms, pn = aplanner.timing(-1)
-    aplanner.timing(0)
-    stage_ms["dist"] = (d_ms / pn if pn else 0.0, pn)
-    stage_ms["astar"] = (a_ms / pn if pn else 0.0, pn)
-    if main_n:
-        stage_ms["mcl_main"] = (main_ms_total / main_n, main_n)                      # the timed-region figure
-    # (a run too short for the event stride to catch a launch keeps the post-pass figure)
+    stage_ms = {"mcl_main": (main_ms_total / main_n if main_n else 0.0, main_n)}       # the timed-region figure
+    if full:
+        # per-stage kernel times: a short untimed pass with every timer on (events between launches cost a few us each, so
+        # they stay out of the timed region)
+        ctx.timing_reset()
+        ctx.timing_enable(True)
+        aplanner.timing(1)
+        for _ in range(min(args.steps, 30, total - k - 1)):
+            step(k)
+            k += 1
+        drain()
+        torch.cuda.synchronize()
+        ctx.timing_enable(False)
+        for name, kid in (("mcl_main", _capi.BL_K_MCL_MAIN), ("mcl_scan", _capi.BL_K_MCL_SCAN), ("map", _capi.BL_K_MAP)):
+            ms, n = ctx.timing_get(kid)
+            stage_ms[name] = (ms / n if n else 0.0, n)
+        d_ms, a_ms, pn = aplanner.timing(-1)
+        aplanner.timing(0)
+        stage_ms["dist"] = (d_ms / pn if pn else 0.0, pn)
+        stage_ms["astar"] = (a_ms / pn if pn else 0.0, pn)
+        if main_n:
+            stage_ms["mcl_main"] = (main_ms_total / main_n, main_n)                      # the timed-region figure
+        # (a run too short for the event stride to catch a launch keeps the post-pass figure)
     pose, k = final_pose, final_k
     pops_total[0] = pops_timed
     stream_k = None
-    if world == 1 and (args.sub or args.grid != 200):
+    if world == 1 and full and (args.sub or args.grid != 200):
         stream_k = streaming_kernels(ctx, grid, planner, aplanner, pose_dev, goal_pose, m["cells"].shape[1], m["cells"].shape[0])
 
     if os.environ.get("BOTLAB_FINISH_LOOKAHEAD") and world == 1:
@@ -1156,7 +1265,7 @@ def main():
         others = {}
         map_bytes = 16.0 * R + 2.0 * traced + (24.0 * N if ride_finish else 0.0)     # riding finish: 16 N read + 8 N prefix written
         for name, b in (("map", map_bytes), ("dist", 5.0 * W * H * per_launch), ("astar", 52.0 * pops_step * per_launch)):
-            ms = stage_ms[name][0]
+            ms = stage_ms[name][0] if name in stage_ms else 0.0          # (the per-stage pass runs with --full)
             if ms > 0 and (goal is not None or name == "map"):
                 gbs = b / (ms * 1e-3) / 1e9
                 others[name] = {"algorithmic_bytes_per_launch": round(b, 1), "avg_launch_ms": round(ms, 5), "achieved": round(gbs, 3),
@@ -1295,7 +1404,7 @@ def main():
                                                  if "error" not in r and r["config"] in (0, 3) and not r["flags"][:1] == ["--no-astar"]
                                                  and (not r.get("planner") or r["planner"][2] != 0)}
             out["particle_sweep_steps_per_s"][str(args.particles)] = round(args.steps / elapsed, 1)
-        if args.cpu_steps > 0 and world == 1:
+        if full and args.cpu_steps > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, m, odo, scans, rands, goal, args.cpu_steps)
             if goal is not None:
                 ss = same_search(ctx, grid, planner, pose, goal_pose, m)
@@ -1308,7 +1417,7 @@ def main():
         if other is not None and world == 1:
             # the reference's own published table (astar_test's six maps), HIP path beside the CPU oracle
             out["astar_fixtures"] = astar_fixtures(ctx, reps=3)
-        emit(out, json_fd, full=bool(args.sub or args.full_line))
+        emit(out, json_fd, full_record=bool(args.sub or args.full_line), detail=full)
     phase(json_fd, "teardown")
     if dist.is_initialized():
         dist.barrier()

@@ -199,7 +199,7 @@ if "distfused" in which:
 if "stream" in which:
     collect_streaming()
 if "default" in which:
-    collect("bench_default", ["--cpu-steps", "0", "--no-other-configs"], config={"particles": 100000, "grid": [200, 200], "rays": 290}, sq=True)
+    collect("bench_default", ["--full", "--cpu-steps", "0", "--no-other-configs"], config={"particles": 100000, "grid": [200, 200], "rays": 290}, sq=True)
 if "config4" in which:
     collect("config4", ["--config", "4", "--goal-l1", "400", "--cpu-steps", "0", "--sub", "--steps", "600", "--warmup", "150"])
 if "config5" in which:
