@@ -26,7 +26,6 @@
 
 #include "bl_astar2_turbo.h"
 #include "bl_astar2_deep.h"
-#include "bl_astar2_duo.h"
 #include "bl_astar2_ahead.h"
 
 #define A2_COSTN 256
@@ -109,13 +108,6 @@ __device__ __forceinline__ void a2_wait_vm4(unsigned& x, unsigned& y, unsigned& 
 #define A2_ULE 37
 #define A2_UGT 34
 #define A2_EQ 32
-
-// BOTLAB_ASTAR_NO_TURBO=1 (read by the host, astar_launch_kernel): the C++ loop everywhere (tests, A/B runs)
-__device__ bool a2_turbo_enabled = true;
-__device__ bool a2_deep_ahead_enabled = true;     // the same three waves beyond LDS (bl_astar2_ahead.h, "the deep regime": 0.88 - 0.90 us per pop where
-                                                  // bl_astar2_deep.h's one wave takes 1.12 - 1.14); BOTLAB_ASTAR_DEEP_AHEAD=0: that one-wave loop
-__device__ bool a2_walk_ahead_enabled = true;     // LDS-regime loop of single searches: the next pop's walk beside the pushes (bl_astar2_ahead.h: pops / pushes / expansions
-                                                  // on three waves, 0.634 us per pop where bl_astar2_duo.h's two take 0.71 - 0.72); BOTLAB_ASTAR_AHEAD=0: the duo loop, =1: two waves
 
 // per-lane constants of the wave-parallel heap operations
 struct a2_lanes {
@@ -581,8 +573,8 @@ __global__ __launch_bounds__(64) void k_heap2_probe(const int* __restrict__ keys
 
 // One wavefront runs the reference's search loop; lanes 0..3 evaluate the four neighbours of the popped node, lane 4 re-derives
 // its gCost (as k_astar does).  Closed cells: closed[] holds (generation << 3) | move, written once per cell.
-// Launched with 64 threads, or with 128: the second wavefront then runs the expansions of the LDS-regime loop beside the first
-// (bl_astar2_duo.h) and waits at a barrier whenever the first is anywhere else.
+// Launched with 64 threads, or with 192: the second and third wavefronts then run the pushes and the expansions of the straight-line
+// loops beside the first (bl_astar2_ahead.h) and wait at a barrier whenever the first is anywhere else.
 template <class C>
 __global__ __launch_bounds__(192) void k_astar2(astar_args a)
 {
@@ -638,7 +630,7 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
     // the straight-line loop's constants (bl_astar2_turbo.h): a row per lane, then the scalars
     const unsigned tbl = kbase + C::TBL_OFF;
     static_assert((C::TBL_OFF & 15) == 0, "table alignment");
-    const bool turbo = fast && cost_in_lds && a2_turbo_enabled;
+    const bool turbo = fast && cost_in_lds && a.turbo;
     const bool ahead = (long long)a.W * a.H * 6 > (3ll << 20);
     // (two rounds in global memory reach level LEV + 10 >= 22; the scratch bounds the list at 2^25 entries)
     const unsigned deep_max = (unsigned)min((long long)a.heap_cap, 1ll << min(C::LEV + 11, 25)) - 4u;
@@ -669,64 +661,31 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
         }
         __syncthreads();
     }
-    // ---- two wavefronts: the second runs the expansions of the LDS-regime loop until the first says QUIT (bl_astar2_duo.h)
-    const bool duo = turbo && blockDim.x >= 128u;
-    const bool walk_ahead = duo && a2_walk_ahead_enabled;
-    const bool ahead3 = walk_ahead && blockDim.x == 192u;      // ... with the expansions on a third wave (BOTLAB_ASTAR_AHEAD=2)
-    // (deep_max etc. are wave-uniform; the three waves agree on the forms they run)
-    const bool deep3 = ahead3 && a2_deep_ahead_enabled && turbo && C::PLEV == C::LEV - 1;
+    // ---- three wavefronts (bl_astar2_ahead.h): wave 0 pops, wave 1 pushes, wave 2 expands -- in both regimes -- until wave 0 says QUIT
+    const bool three = turbo && blockDim.x == 192u;
     if (wave == 2) {
-        if (ahead3) {
+        if (three) {
             if (ahead) asm volatile(A2A_BODY_EXPAND3(A2T_PREFETCH, "4", "3")
                          :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
                             [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
                             [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2A_EXPUSH_CLOBBERS);
+                         : A2A_EXPAND3_CLOBBERS);
             else asm volatile(A2A_BODY_EXPAND3("", "2", "1")
                          :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
                             [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
                             [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2A_EXPUSH_CLOBBERS);
+                         : A2A_EXPAND3_CLOBBERS);
         }
         return;
     }
     if (wave == 1) {
-        if (deep3) {
+        if (three)
             asm volatile(A2A_BODY_PUSH3D
                          :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [kmax2] "n"(C::KEY_BYTES - 2), [pln] "n"(C::PLN),
                             [kslots] "n"(C::KSLOTS), [kslotsm1] "n"(C::KSLOTS - 1),
                             [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
                             [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
                          : A2A_PUSH3D_CLOBBERS);
-        } else if (ahead3) {
-            asm volatile(A2A_BODY_PUSH3
-                         :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
-                            [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
-                            [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2A_PUSH3_CLOBBERS);
-        } else if (walk_ahead) {
-            if (ahead) asm volatile(A2A_BODY_EXPUSH(A2T_PREFETCH, "4", "3")
-                         :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
-                            [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
-                            [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2A_EXPUSH_CLOBBERS);
-            else asm volatile(A2A_BODY_EXPUSH("", "2", "1")
-                         :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
-                            [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
-                            [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2A_EXPUSH_CLOBBERS);
-        } else if (duo) {
-            if (ahead) asm volatile(A2W_BODY_EXPAND(A2T_PREFETCH, "4")
-                         :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
-                            [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
-                            [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2W_EXPAND_CLOBBERS);
-            else asm volatile(A2W_BODY_EXPAND("", "2")
-                         :: [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
-                            [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
-                            [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2W_EXPAND_CLOBBERS);
-        }
         return;
     }
     // neighbour offsets: xDeltas {1,-1,0,0}, yDeltas {0,0,1,-1} (astar.cpp:215-216); lane 4: the cell itself
@@ -753,18 +712,12 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
             unsigned s_len = (unsigned)__builtin_amdgcn_readfirstlane((int)len), s_pops = (unsigned)__builtin_amdgcn_readfirstlane((int)pops);
             unsigned s_pushes = (unsigned)__builtin_amdgcn_readfirstlane((int)pushes);
             // (grids whose distance + closed arrays fit the L2 gain nothing from asking for lines ahead)
-            if (walk_ahead) asm volatile(A2A_BODY_POP
+            if (three) asm volatile(A2A_BODY_POP
                          : [len] "+s"(s_len), [pops] "+s"(s_pops), [pushes] "+s"(s_pushes), [code] "=&s"(code), [gm] "=&s"(gm), [pt] "=&s"(ptop)
                          : [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
                            [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
                            [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
                          : A2A_POP_CLOBBERS);
-            else if (duo) asm volatile(A2W_BODY_HEAP
-                         : [len] "+s"(s_len), [pops] "+s"(s_pops), [pushes] "+s"(s_pushes), [code] "=&s"(code), [gm] "=&s"(gm), [pt] "=&s"(ptop)
-                         : [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
-                           [ok0lo] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) & 0xffffffffull)),
-                           [ok0hi] "n"((unsigned)(((2ull << ((1 << (C::FD + 1)) - 2)) - 1ull) >> 32))
-                         : A2T_CLOBBERS);
             else if (ahead) asm volatile(A2T_BODY(A2T_PREFETCH, "2")
                          : [len] "+s"(s_len), [pops] "+s"(s_pops), [pushes] "+s"(s_pushes), [code] "=&s"(code), [gm] "=&s"(gm), [pt] "=&s"(ptop)
                          : [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [pln] "n"(C::PLN),
@@ -780,7 +733,7 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
             len = s_len; pops = s_pops; pushes = s_pushes;
             if (code == 2u) { goal_m = gm; cx = (int)((ptop >> 2) & 0x7fffu); cy = (int)(ptop >> 17); res.status = ASTAR_ST_FOUND; break; }
             if (code == 3u) { res.status = ASTAR_ST_LIMIT; break; }
-            if (code == 4u) { res.status = ASTAR_ST_BROKEN; break; }          // (two-wave loop: the other wave's flag never came)
+            if (code == 4u) { res.status = ASTAR_ST_BROKEN; break; }          // (three-wave loop: wave 2's flag never came)
             if (len == 0) break;
         }
         if (deep && len >= (unsigned)C::PLN + 2u && len <= deep_max) {
@@ -788,7 +741,7 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
             unsigned code, gm, ptop;
             unsigned s_len = (unsigned)__builtin_amdgcn_readfirstlane((int)len), s_pops = (unsigned)__builtin_amdgcn_readfirstlane((int)pops);
             unsigned s_pushes = (unsigned)__builtin_amdgcn_readfirstlane((int)pushes);
-            if (deep3) asm volatile(A2A_BODY_POPD
+            if (three) asm volatile(A2A_BODY_POPD
                          : [len] "+s"(s_len), [pops] "+s"(s_pops), [pushes] "+s"(s_pushes), [code] "=&s"(code), [gm] "=&s"(gm), [pt] "=&s"(ptop)
                          : [tbl] "s"(__builtin_amdgcn_readfirstlane((int)tbl)), [kmax] "n"(C::KEY_BYTES - 4), [kmax2] "n"(C::KEY_BYTES - 2), [pln] "n"(C::PLN),
                            [kslots] "n"(C::KSLOTS), [kslotsm1] "n"(C::KSLOTS - 1), [dlo] "n"(C::PLN + 2),
@@ -877,11 +830,11 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
         if (full) { res.status = ASTAR_ST_CAPACITY; break; }
         if (goal_m) { res.status = ASTAR_ST_FOUND; break; }
     }
-    if (duo) {                                                                  // the second wave waits at X: let it go home
+    if (three) {                                                                // waves 1 and 2 wait at B1: let them go home
         if (lane == 0) *(a2_lds_u32*)(size_t)(tbl + 4096u + 4u * A2W_RUN_WORD) = A2W_QUIT;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #ifdef BL_ASTAR_STAMPS
-        for (int q = 0; q < 8; ++q) __builtin_amdgcn_s_sleep(100);           // (the second wave adds its sums on its way out)
+        for (int q = 0; q < 8; ++q) __builtin_amdgcn_s_sleep(100);           // (waves 1 and 2 add their sums on their way out)
 #endif
     }
     res.pops = pops; res.pushes = pushes;
@@ -910,21 +863,12 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
     tr1 = __builtin_amdgcn_s_memrealtime();
     res.stamps[0] = (long long)acc_all; res.stamps[1] = (long long)acc_adj; res.stamps[2] = (long long)acc_nb;
     res.stamps[3] = (long long)(tr1 - tr0); res.stamps[4] = (long long)acc_wait; res.stamps[5] = (long long)acc_push;
-    if (walk_ahead) {
-        // walk-ahead loop (bl_astar2_ahead.h): cycles inside the barriers -- wave 0 in B1 / B2 -> [0] / [1], wave 1 in B1 / B2 -> [2] / [4];
-        // walks taken again -> [5]; tops whose expansion had been made ahead | not -> path_off
+    if (three) {
+        // three-wave loop (bl_astar2_ahead.h): cycles inside B1 -- wave 0 -> [0], wave 2 -> [2], wave 1 -> [4] --, wave 0's inside B2 -> [1];
+        // walks taken again -> [5]; tops whose expansion had been made ahead | pushes whose ancestor line was read again -> path_off
         const a2_lds_u32* sc = (const a2_lds_u32*)(size_t)(tbl + 4096u);
-        res.stamps[0] = sc[24]; res.stamps[1] = sc[26]; res.stamps[2] = sc[27]; res.stamps[4] = sc[28]; res.stamps[5] = sc[29];
-        res.path_off = (long long)sc[30] | ((long long)sc[31] << 32);
-        // (deep regime on three waves: the wave that pushes inside B1 in place of wave 2's B2; first pushes whose ancestors were read
-        // again in place of the expansions not made ahead)
-        if (deep3) { res.stamps[4] = sc[21]; res.path_off = (long long)sc[30] | ((long long)sc[22] << 32); }
-    } else if (duo) {
-        // two-wave loop: wave 0's cycles inside Y, X, Z; wave 1's inside X, Y (bl_astar2_duo.h).  Wave 1 adds its sums on its way out:
-        // it has left by the time the barrier below is through... the sums it has added so far, then
-        const a2_lds_u32* sc = (const a2_lds_u32*)(size_t)(tbl + 4096u);
-        res.stamps[0] = sc[21]; res.stamps[1] = sc[22]; res.stamps[2] = sc[23]; res.stamps[4] = sc[25]; res.stamps[5] = sc[24];
-        res.path_off = (long long)sc[30] | ((long long)sc[31] << 32);      // (diagnostic only) expansions out of registers | asked for
+        res.stamps[0] = sc[24]; res.stamps[1] = sc[26]; res.stamps[2] = sc[27]; res.stamps[4] = sc[21]; res.stamps[5] = sc[29];
+        res.path_off = (long long)sc[30] | ((long long)sc[22] << 32);
     } else if (turbo) {
         // the straight-line loop's own sums (table words 16 .. 21) on top: checks + top -> [0] (with the rest), pop -> [1], expansion -> [2], load wait -> [4], pushes -> [5]
         const a2_lds_u32* sc = (const a2_lds_u32*)(size_t)(tbl + 4096u);

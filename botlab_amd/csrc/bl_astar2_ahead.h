@@ -1,53 +1,128 @@
-// bl_astar2_ahead.h -- the search loop of k_astar2 on three (or two) wavefronts, with the NEXT pop's walk taken beside the pushes: the
-// LDS regime first, its form for open lists that reach into global memory at the end of the file ("the deep regime").
-// The default for searches that have their compute unit to themselves (round 6).
+// bl_astar2_ahead.h -- the search loop of k_astar2 on THREE wavefronts, with the NEXT pop's walk taken beside the pushes: the LDS
+// regime first, its form for open lists that reach into global memory at the end of the file ("the deep regime").
+// What searches that have their compute unit to themselves run (round 6); the replanner's units, which share CUs, run the one-wave
+// loops (bl_astar2_turbo.h, bl_astar2_deep.h).
+//
+// A lone wavefront issues one instruction per ~4.2 cycles (the CU's arbiter visits a SIMD every fourth cycle), and the one-wave loop
+// is ~460 instructions per pop: it waits for its own instruction stream, not for memory.  The waves of a workgroup sit on different
+// SIMDs and each issues at that rate (tests/tools/two_wave_probe.hip: 4.4 cycles per instruction each; an s_barrier all reach ~10
+// cycles; LDS write -> barrier -> read ~150).  So an iteration is split over three waves:
+//
+//     wave 0 (POP)     B1 | test, the entry at the back, climb, Z, stores         | B2 | walk of the NEXT pop (reads only)
+//     wave 1 (PUSH)    B1 | (deep regime: the pushes' ancestor lines)             | B2 | pushes, where they landed
+//     wave 2 (EXPAND)  B1 | top, Z, "is it the top I expanded?", record           | B2 | expansion of the top FORESEEN next
 //
 // std::pop_heap moves the hole from the root to a leaf along the smaller children (stl_heap.h __adjust_heap) BEFORE it looks at the
 // value it re-inserts: the walk depends on the heap alone, not on the entry from the back of the array.  So pop k + 1's walk can be
-// taken on the heap as pop k left it, while the other wavefront is still pushing expansion k's candidates -- as long as no decision
-// of the walk read a position those pushes wrote.  A push writes an ancestor line: its slot and the ancestors that drop a level, up
-// to the position t where the entry lands; the walk reads the two children of every node on its path; so a written position was read
+// taken on the heap as pop k left it, while wave 1 is still pushing expansion k's candidates -- as long as no decision of the walk
+// read a position those pushes wrote.  A push writes an ancestor line: its slot and the ancestors that drop a level, up to the
+// position t where the entry lands; the walk reads the two children of every node on its path; so a written position was read
 // exactly when parent(t) lies on the walk's path (if a deeper written position's parent were on the path, so would parent(t) be: the
 // path is closed under ancestors).  tests/tools/walk_ahead_model.py replays the reference's search on the astar fixtures with
 // libstdc++'s index operations: the early walk reads a written position in 0.1 % (5e5 pops) .. 2.8 % (1e4 - 4e4 pops) of the
 // iterations (a quarter of them in searches of ~1 000 pops: launch-bound anyway).  Such an iteration takes its walk again.
 //
-//   two waves:
-//     wave 0 (POP)     B1 | test, the entry at the back, climb, stores       | B2 | walk of the NEXT pop (reads only) ....................... | B1
-//     wave 1 (EXPUSH)  B1 | top, Z, "is it the top I expanded?", record      | B2 | pushes, where they landed, expansion of the top FORESEEN next | B1
-//   three waves (the default): wave 1 keeps the pushes, wave 2 takes everything else of it; the candidates go from wave 2 to wave 1
-//   through the record (words 48..55) before B2.
+// B1 / B2 are workgroup barriers.  Z is a flag word, not a barrier (wave 2 would stand in it for the whole of wave 0's climb): wave
+// 2 raises it when it HAS read the top and the root's children, wave 0 looks at it in front of its stores into the heap -- hundreds
+// of cycles behind B1, so it never waits, but the order is the flag's, not the clock's -- and lowers it again.  The expansion a pop
+// needs is made an iteration AHEAD, for the top wave 2 foresees (the smaller child of the root, of equal keys the right one, as
+// __adjust_heap walks: 95 - 99.5 % of the tops on the reference's maze searches), with the popped cell's closedList entry held back
+// until the top is seen to be that entry.  Same macros, same index operations in the same order as the one-wave loop: the open
+// list goes through the same states (the fixtures run through all of them).
 //
-// B1 / B2 are workgroup barriers; Z is bl_astar2_duo.h's flag (wave 1 has read the top: wave 0 may store).  The expansion a pop needs
-// is made an iteration AHEAD as well, for the top wave 1 foresees (the smaller child of the root, as bl_astar2_duo.h asks its loads
-// ahead: 99.5 % of the tops here), with the popped cell's closedList entry held back until the top is seen to be that entry.  Same
-// macros, same index operations in the same order as the one-wave loop (bl_astar2_turbo.h) and the two-wave loop without the early
-// walk (bl_astar2_duo.h): the open list goes through the same states (the fixtures run through all of them).
-//
-// MEASURED (profiles/r06_astar_walk_ahead_stamps.txt, r06_astar_pop.csv; maze 2: 13 693 pops, 1.86 pushes per pop, bl_astar2_duo.h
-// 0.71 - 0.72 us per pop):
-//   two waves (BOTLAB_ASTAR_AHEAD=1, the forms above)                          0.705 - 0.720: both waves busy (~1 580 of ~1 750 cycles)
-//   THREE waves (the default): wave 0 pops, wave 1 pushes, wave 2 expansions     0.69 as first built, 0.63 - 0.64 with wave 0 trimmed
-// With three waves the pops alone are the chain (wave 0 waits ~55 cycles in either barrier -- the barrier's own cost --, the expansion
-// wave ~400 + ~90), so every cycle off wave 0 counts: the four path tests as ONE vector test (lane j = push j, lane 3 = the entry
-// at the back), no wait in front of B1 (the walk taken ahead only reads), the loop's checks made once per iteration, the next
-// walk's first pairs asked for while the record is on its way; on wave 1 the first push's ancestor reads go out with the record
-// reads (they need the length only).  What is left on wave 0, ~1 400 cycles: two LDS round trips in front of the climb (the entry
-// at the back, the flag), the stores and the wait for them, the record's round trip, a walk of 2 - 3 rounds (~470).
+// MEASURED (profiles/r06_astar_walk_ahead_stamps.txt, r06_astar_pop.csv; maze 2: 13 693 pops, 1.86 pushes per pop): 0.69 us per pop
+// as first built, 0.63 - 0.64 with wave 0 trimmed.  The pops alone are the chain (wave 0 waits ~55 cycles in either barrier -- the
+// barrier's own cost --, the expansion wave ~400 + ~90), so every cycle off wave 0 counts: the four path tests as ONE vector test
+// (lane j = push j, lane 3 = the entry at the back), no wait in front of B1 (the walk taken ahead only reads), the loop's checks
+// made once per iteration, the next walk's first pairs asked for while the record is on its way; on wave 1 the first push's
+// ancestor reads go out with the record reads (they need the length only).  What is left on wave 0, ~1 400 cycles: two LDS round
+// trips in front of the climb (the entry at the back, the flag), the stores and the wait for them, the record's round trip, a walk
+// of 2 - 3 rounds (~470).
 //
 // Hand-over (table words, record at tbl + 4096 + 128):
-//     32..35  wave 1 -> wave 0 before B2: push mask, goal mask, popped payload, -;  word 35 on (re-)entry wave 0 -> wave 1: the length
+//     32..34  wave 2 -> waves 0, 1 before B2: push mask, goal mask, popped payload
+//     35      wave 0 -> waves 1, 2 on (re-)entry: the length
 //     36..38  wave 1 -> wave 0 before B1: per push max(landing node >> 1, 1) (1-based node index of the landing's parent; the root
 //             when the entry rose to the top: every walk has it), 0x7fffffff for "no push"
-//     48..55  (three waves) wave 2 -> wave 1 before B2: (key, payload) of the expansion's four candidates
+//     48..55  wave 2 -> wave 1 before B2: (key, payload) of the expansion's four candidates
 //     44      run word: 1 go, 2 quit, 3 go and forget what you foresaw (wave 0 has been elsewhere; the length is in word 35), 4 park
 //     45      Z
 // Wave 0 leaves the loop at an iteration boundary only, behind a B1 it enters with the run word on "park": wave 1's pushes are in,
-// and wave 1 goes back to B1 and waits there (as it does at the kernel's start) until wave 0 comes back or says quit.
+// and waves 1 and 2 go back to B1 and wait there (as they do at the kernel's start) until wave 0 comes back or says quit.
 #ifndef BL_ASTAR2_AHEAD_H
 #define BL_ASTAR2_AHEAD_H
 
 #define A2A_PARK 4u
+
+#define A2W_RUN_WORD 44
+#define A2W_GO 1u
+#define A2W_QUIT 2u
+
+// Diagnostic build (-DBL_ASTAR_STAMPS): cycles inside barriers (ACC an SGPR the loops leave alone) and counts, added into table
+// words at the loop's exit.  Wave 0: words 24 / 26 = inside B1 / B2, 29 = walks taken again; wave 1: 21 = inside B1, 22 = pushes
+// whose ancestor line was read again (deep regime); wave 2: 27 / 28 = inside B1 / B2, 30 / 31 = tops whose expansion had been
+// made ahead / not.
+#ifdef BL_ASTAR_STAMPS
+#define A2W_TIMED_BARRIER(ACC) "s_memtime s[100:101]\n\ts_waitcnt lgkmcnt(0)\n\ts_mov_b32 s43, s100\n\ts_barrier\n\ts_memtime s[100:101]\n\ts_waitcnt lgkmcnt(0)\n\ts_sub_u32 s43, s100, s43\n\ts_add_u32 " ACC ", " ACC ", s43\n\t"
+#define A2W_ACC_OUT(ACC, OFF) "v_mov_b32 v245, %[tbl]\n\tv_mov_b32 v250, " ACC "\n\ts_mov_b64 exec, 1\n\tds_add_u32 v245, v250 offset:" OFF "\n\ts_mov_b64 exec, -1\n\ts_waitcnt lgkmcnt(0)\n\t"
+#define A2W_ACC_ZERO(ACC) "s_mov_b32 " ACC ", 0\n\t"
+#define A2W_ACC_COUNT(ACC) "s_add_u32 " ACC ", " ACC ", 1\n\t"
+#else
+#define A2W_TIMED_BARRIER(ACC) "s_barrier\n\t"
+#define A2W_ACC_OUT(ACC, OFF) ""
+#define A2W_ACC_ZERO(ACC) ""
+#define A2W_ACC_COUNT(ACC) ""
+#endif
+
+// constants of every wave (the one-wave loop's entry)
+#define A2W_ENTRY                                                                                             \
+    "v_mbcnt_lo_u32_b32 v188, -1, 0\n\t"                                                                      \
+    "v_mbcnt_hi_u32_b32 v188, -1, v188\n\t"                                                                   \
+    "v_lshlrev_b32 v190, 6, v188\n\t"                                                                         \
+    "v_add_u32 v190, %[tbl], v190\n\t"                                                                        \
+    "v_mov_b32 v191, %[tbl]\n\t"                                                                              \
+    "ds_read_b128 v[180:183], v190\n\t"                                                                       \
+    "ds_read_b128 v[184:187], v190 offset:16\n\t"                                                             \
+    "ds_read_b64 v[178:179], v190 offset:32\n\t"                                                              \
+    "ds_read_b128 v[192:195], v191 offset:4096\n\t"                                                           \
+    "ds_read_b128 v[196:199], v191 offset:4112\n\t"                                                           \
+    "ds_read_b128 v[200:203], v191 offset:4128\n\t"                                                           \
+    "ds_read_b128 v[204:207], v191 offset:4144\n\t"                                                           \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
+    A2T_RSF("s44", "v192") A2T_RSF("s45", "v193") A2T_RSF("s46", "v194") A2T_RSF("s47", "v195")               \
+    A2T_RSF("s48", "v196") A2T_RSF("s49", "v197") A2T_RSF("s50", "v198") A2T_RSF("s58", "v199")               \
+    A2T_RSF("s52", "v200") A2T_RSF("s53", "v201") A2T_RSF("s54", "v202") A2T_RSF("s55", "v203")               \
+    A2T_RSF("s56", "v204") A2T_RSF("s57", "v205") A2T_RSF("s59", "v206") A2T_RSF("s60", "v207")               \
+    "s_mov_b32 s62, %[ok0lo]\n\t"                                                                             \
+    "s_mov_b32 s63, %[ok0hi]\n\t"                                                                             \
+    "s_mov_b32 s64, -1\n\t"                                                                                   \
+    "s_mov_b32 s65, 0x7fffffff\n\t"                                                                           \
+    "s_mov_b64 s[66:67], 31\n\t"                                                                              \
+    "s_mov_b64 s[96:97], 16\n\t"                                                                              \
+    "s_mov_b64 s[98:99], 0xff\n\t"                                                                            \
+    "s_lshl_b32 s51, s48, 3\n\t"                                                                              \
+    "v_mov_b32 v177, s56\n\t"                                                                                 \
+    "v_mov_b32 v176, 0xffff\n\t"
+
+// ---- wave 0's gate in front of its stores into the heap: Z (see above); the run word turns to "go" at the same place
+#define A2W_GATE_ASK "ds_read_b32 v218, v214 offset:52\n\t"
+#define A2W_STORES_GATE(TAG)                                                                                  \
+    "s_mov_b32 s39, 0\n\t"                                                                                    \
+    TAG ":\n\t"                                                                                               \
+    "v_readfirstlane_b32 s70, v218\n\t"                                                                       \
+    "s_cmp_lg_u32 s70, 0\n\t"                                                                                 \
+    "s_cbranch_scc1 " TAG "1f\n\t"                                                                            \
+    "s_add_u32 s39, s39, 1\n\t"                      /* (never seen: the flag goes up a few instructions behind B1.  A wave that */ \
+    "s_cmp_gt_u32 s39, 0x400000\n\t"                 /* does not come back from a loop would hang the device: give up instead, */ \
+    "s_cbranch_scc1 94f\n\t"                         /* ~1 s, the search ends as BROKEN) */                   \
+    "ds_read_b32 v218, v214 offset:52\n\t"                                                                    \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
+    "s_branch " TAG "b\n\t"                                                                                   \
+    TAG "1:\n\t"                                                                                              \
+    "s_mov_b64 exec, 1\n\t"                                                                                   \
+    "ds_write_b32 v214, v219 offset:52\n\t"                                                                   \
+    "ds_write_b32 v214, v217 offset:48\n\t"                                                                   \
+    "s_mov_b64 exec, -1\n\t"
 
 // the rounds of a pop's walk on a heap of s40 entries (the entry at the back already taken off): round data in v200-v203 / v205-v208 /
 // v240-v243, masks s[72:73] / s[74:75] / s[76:77]; s78 = 1 + the leaf the hole ends in.  Which rounds ran is a function of s40.
@@ -127,7 +202,7 @@
     "v_mov_b32 v224, s40\n\t"                                                                                 \
     "s_mov_b64 exec, 1\n\t"                                                                                   \
     "ds_write_b32 v214, v216 offset:48\n\t"                                                                   \
-    "ds_write_b32 v214, v224 offset:12\n\t"          /* the length, for the other wave */                     \
+    "ds_write_b32 v214, v224 offset:12\n\t"          /* the length, for the other waves */                    \
     "s_mov_b64 exec, -1\n\t"                                                                                  \
     "v_min_u32 v215, 3, v188\n\t"                                                                             \
     "v_lshl_add_u32 v215, v215, 2, v214\n\t"                                                                  \
@@ -144,7 +219,7 @@
     "s_cbranch_scc1 91f\n\t"                                                                                  \
     /* (nothing this wave has WRITTEN is under way here: the walk taken ahead only reads) */                  \
     "2:\n\t"                                                                                                  \
-    A2W_TIMED_BARRIER("s36")                     /* B1: the pushes are in; the other wave takes the top from here */ \
+    A2W_TIMED_BARRIER("s36")                     /* B1: the pushes are in; wave 2 takes the top from here */         \
     "ds_read_b32 v210, v215\n\t"                     /* where they landed: lane j the j-th push */            \
     /* ---- the entry at the back of the array (key v193, payload v197): the value the pop's sift-down places */ \
     "s_lshl_b32 s70, s40, 1\n\t"                                                                              \
@@ -193,7 +268,7 @@
     A2W_STORES_GATE("70")                                                                                     \
     A2T_STORE("v200", "v204", "v202", "v203", "s[72:73]") A2T_STORE("v205", "v209", "v207", "v208", "s[74:75]") \
     A2T_LAND_STORE                                                                                            \
-    /* ---- the pop is in: the other wave pushes, this one takes the next pop's walk */                       \
+    /* ---- the pop is in: wave 1 pushes, this one takes the next pop's walk */                               \
     "40:\n\t"                                                                                                 \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
     A2W_TIMED_BARRIER("s38")                     /* B2 */                                                     \
@@ -261,7 +336,7 @@
     "25:\n\t"                                                                                                 \
     A2T_RARE_UP("s[74:75]", "v201", "v202", "s[72:73]", "26b", "27")                                          \
     A2T_RARE_ROOT("s[72:73]", "26b")                                                                          \
-    /* ---- exits: the other wave is parked behind the barrier (its pushes are in by then) */                 \
+    /* ---- exits: the other waves are parked behind the barrier (the pushes are in by then) */               \
     "91:\n\t"                                                                                                 \
     "s_mov_b32 %[code], 1\n\t"                                                                                \
     "s_branch 98f\n\t"                                                                                        \
@@ -277,7 +352,7 @@
     "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
     "s_barrier\n\t"                                                                                           \
     "s_branch 99f\n\t"                                                                                        \
-    "94:\n\t"                                        /* the other wave's flag never came: no barrier would either */ \
+    "94:\n\t"                                        /* wave 2's flag never came: no barrier would either */         \
     "s_mov_b32 %[code], 4\n\t"                                                                                \
     "99:\n\t"                                                                                                 \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
@@ -290,38 +365,37 @@
 
 #define A2A_POP_CLOBBERS A2T_CLOBBERS
 
-// ---------------------------------------------------------------------------------------------------------- wave 1: expansions and pushes
-// A2T_PUSH_REST, and where the entry landed: max(landing node >> 1, 1) into lane J of v167
-#define A2A_PUSH_REST(J)                                                                                      \
-    "s_ff1_i32_b32 s91, s87\n\t"                                                                              \
-    "s_add_i32 s70, s87, -1\n\t"                                                                              \
-    "s_and_b32 s87, s87, s70\n\t"                                                                             \
-    "v_readlane_b32 s89, v226, s91\n\t"                                                                       \
-    "s_waitcnt lgkmcnt(1)\n\t"                                                                                \
-    "s_nop 1\n\t"                                                                                             \
-    "v_cmp_lt_u32 vcc, s89, v234\n\t"                                                                         \
-    "s_not_b64 s[92:93], vcc\n\t"                                                                             \
-    "s_ff1_i32_b64 s70, s[92:93]\n\t"                                                                         \
-    "s_bfm_b64 s[92:93], s70, 0\n\t"                                                                          \
-    "s_lshr_b32 s70, s78, s70\n\t"                                                                            \
-    "s_lshr_b32 s39, s70, 1\n\t"                                                                              \
-    "s_max_u32 s39, s39, 1\n\t"                                                                               \
-    "v_writelane_b32 v167, s39, " J "\n\t"                                                                    \
-    "s_lshl_b32 s71, s70, 1\n\t"                                                                              \
-    "s_lshl_b32 s70, s70, 2\n\t"                                                                              \
-    "s_add_i32 s70, s70, s56\n\t"                                                                             \
-    "s_add_i32 s70, s70, -4\n\t"                                                                              \
-    "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
-    "v_mov_b32 v232, s71\n\t"                                                                                 \
-    "v_mov_b32 v238, s70\n\t"                                                                                 \
-    "s_mov_b64 exec, s[92:93]\n\t"                                                                            \
-    "ds_write_b16 v236, v234\n\t"                                                                             \
-    "ds_write_b32 v237, v235\n\t"                                                                             \
-    "s_lshl_b64 exec, 1, s91\n\t"                    /* the entry itself: straight from the lane that holds it */ \
-    "ds_write_b16 v232, v226\n\t"                                                                             \
-    "ds_write_b32 v238, v227\n\t"                                                                             \
-    "s_mov_b64 exec, -1\n\t"                                                                                  \
-    "s_add_i32 s40, s40, 1\n\t"
+// ---------------------------------------------------------------------------------------------------------- wave 2: the expansions
+// A2T_NBR in two halves: coordinates, in-grid mask and addresses of the five cells; their two loads
+#define A2W_NBR_ADDR                                                                                          \
+    "v_bfe_u32 v228, v196, 2, 15\n\t"                                                                         \
+    "v_lshrrev_b32 v229, 17, v196\n\t"                                                                        \
+    "v_add_u32 v210, v228, v186\n\t"                                                                          \
+    "v_add_u32 v211, v229, v187\n\t"                                                                          \
+    "v_cmp_gt_u32 vcc, s44, v210\n\t"                                                                         \
+    "v_cmp_gt_u32_e64 s[94:95], s45, v211\n\t"                                                                \
+    "s_and_b64 s[94:95], s[94:95], vcc\n\t"                                                                   \
+    "s_and_b64 s[94:95], s[94:95], s[66:67]\n\t"                                                              \
+    "v_mad_u32_u24 v212, v211, s44, v210\n\t"                                                                 \
+    "v_cndmask_b32_e64 v212, 0, v212, s[94:95]\n\t"                                                           \
+    "v_lshlrev_b32 v213, 1, v212\n\t"                                                                         \
+    "v_lshlrev_b32 v214, 2, v212\n\t"
+// ... of the FORESEEN top (payload v150): coordinates, mask and addresses in a second set (v151-v157, s[82:83]), loads into (D0, D1)
+#define A2W_NBR2_TO(D0, D1)                                                                                   \
+    "v_bfe_u32 v151, v150, 2, 15\n\t"                                                                         \
+    "v_lshrrev_b32 v152, 17, v150\n\t"                                                                        \
+    "v_add_u32 v153, v151, v186\n\t"                                                                          \
+    "v_add_u32 v154, v152, v187\n\t"                                                                          \
+    "v_cmp_gt_u32 vcc, s44, v153\n\t"                                                                         \
+    "v_cmp_gt_u32_e64 s[82:83], s45, v154\n\t"                                                                \
+    "s_and_b64 s[82:83], s[82:83], vcc\n\t"                                                                   \
+    "s_and_b64 s[82:83], s[82:83], s[66:67]\n\t"                                                              \
+    "v_mad_u32_u24 v155, v154, s44, v153\n\t"                                                                 \
+    "v_cndmask_b32_e64 v155, 0, v155, s[82:83]\n\t"                                                           \
+    "v_lshlrev_b32 v156, 1, v155\n\t"                                                                         \
+    "v_lshlrev_b32 v157, 2, v155\n\t"                                                                         \
+    "global_load_ushort " D0 ", v156, s[52:53]\n\t"                                                           \
+    "global_load_dword " D1 ", v157, s[54:55] sc1\n\t"
 
 // A2T_EXPAND without its store: the closedList entry of the popped cell (address v214, value v218, lane mask -> s[72:73]) is left to
 // A2A_COMMIT -- the expansion below is made for a top that is only FORESEEN.
@@ -363,23 +437,6 @@
     TAG ":\n\t"                                                                                               \
     "v_readlane_b32 s75, v212, 4\n\t"                /* the cell this expansion closes */
 
-// the pushes of an expansion (mask s87, keys v226, payloads v227 in lanes 0..3) into a heap of s40 entries behind the pop, and where
-// each landed (A2A_PUSH_REST) into the record's words 36..38 (v168 = the lane's word)
-#define A2A_PUSHES                                                                                            \
-    "s_add_i32 s40, s40, -1\n\t"                                                                              \
-    "v_mov_b32 v167, 0x7fffffff\n\t"                                                                          \
-    A2T_PUSH_CHECK("17f") A2T_PUSH_READ A2A_PUSH_REST("0")                                                    \
-    A2T_PUSH_CHECK("17f") A2T_PUSH_READ A2A_PUSH_REST("1")                                                    \
-    A2T_PUSH_CHECK("17f") A2T_PUSH_READ A2A_PUSH_REST("2")                                                    \
-    "17:\n\t"                                                                                                 \
-    "s_mov_b64 exec, 15\n\t"                                                                                  \
-    "ds_write_b32 v168, v167\n\t"                                                                             \
-    "s_mov_b64 exec, -1\n\t"
-// (three waves) the candidates for the wave that pushes: (key, payload) of lanes 0..3 into the record's words 48..55
-#define A2A_REC_CANDIDATES                                                                                    \
-    "s_mov_b64 exec, 15\n\t"                                                                                  \
-    "ds_write_b64 v171, v[226:227]\n\t"
-
 // the foreseen top of the NEXT iteration (the smaller child of the root as read at B1, of equal keys the right one: payload v150,
 // key v164) and the loads of its expansion, into (v160, v161)
 #define A2A_FORESEE                                                                                           \
@@ -389,13 +446,27 @@
     "v_cndmask_b32 v150, v162, v163, vcc\n\t"                                                                 \
     A2W_NBR2_TO("v160", "v161")
 
-// One iteration.  The expansion a pop needs is made one iteration AHEAD, for the top the wave foresees (bl_astar2_duo.h: right for
-// 95 - 99.5 % of the tops), behind the pushes and beside the other wave's walk: key v192 / payload v196 of the entry it is for, the
-// candidates' keys v226 / payloads v227, push mask s87, goal mask s88, and its closedList entry not stored yet (s[72:73], v214, v218,
-// cell s75); s74 = "there is one".  At B1 the top really there is compared with it: the same entry (payload and key) -> the entry is
-// stored and the record goes out at once; another (or none foreseen: wave 0 has been elsewhere) -> the expansion is made now, from
-// loads asked for now (v158, v159).  v169 = the record's address, v168 = the lane's word of "where the pushes landed" (lanes 0..3).
-#define A2A_XBODY(PREFETCH, VMWAIT, SPECWAIT, RECX, MID)                                                                           \
+// Wave 2, one iteration per pass through 10.  The expansion a pop needs is made one iteration AHEAD, for the top the wave foresees,
+// behind B2 and beside wave 0's walk and wave 1's pushes: key v192 / payload v196 of the entry it is for, the candidates' keys v226 /
+// payloads v227, push mask s87, goal mask s88, and its closedList entry not stored yet (s[72:73], v214, v218, cell s75); s74 = "there
+// is one".  At B1 the top really there is compared with it: the same entry (payload and key) -> the entry is stored and the record
+// goes out at once; another (or none foreseen: wave 0 has been elsewhere) -> the expansion is made now, from loads asked for now
+// (v158, v159).  v169 = the record's address, v171 = the lane's candidate (lanes 0..3: words 48..55, for wave 1).
+#define A2A_BODY_EXPAND3(PREFETCH, VMWAIT, SPECWAIT)                                                          \
+    A2W_ENTRY                                                                                                 \
+    "s_mov_b32 s40, 0\n\t"                                                                                    \
+    "s_mov_b32 s74, 0\n\t"                           /* no expansion made ahead */                            \
+    A2W_ACC_ZERO("s41") A2W_ACC_ZERO("s42") A2W_ACC_ZERO("s79") A2W_ACC_ZERO("s81")                           \
+    "v_mov_b32 v190, 2\n\t"                                                                                   \
+    "v_mov_b32 v165, 4\n\t"                                                                                   \
+    "v_add_u32 v169, 4224, v191\n\t"                 /* the record */                                         \
+    "v_min_u32 v171, 3, v188\n\t"                                                                             \
+    "v_lshl_add_u32 v171, v171, 3, v169\n\t"                                                                  \
+    "v_add_u32 v171, 64, v171\n\t"                   /* the lane's candidate (lanes 0..3): words 48..55 */    \
+    "v_mov_b32 v166, s51\n\t"                        /* a closed entry of this search */                      \
+    "v_mov_b32 v150, -1\n\t"                         /* no top foreseen */                                    \
+    "v_mov_b32 v170, 1\n\t"                                                                                   \
+    "s_mov_b32 s84, -1\n\t"                          /* no cell closed */                                     \
     "10:\n\t"                                                                                                 \
     A2W_TIMED_BARRIER("s41")                     /* B1: the heap is final */                                  \
     "ds_read_b32 v240, v169 offset:48\n\t"           /* the run word */                                       \
@@ -408,7 +479,7 @@
     "v_readfirstlane_b32 s70, v240\n\t"                                                                       \
     "s_cmp_eq_u32 s70, 2\n\t"                                                                                 \
     "s_cbranch_scc1 99f\n\t"                                                                                  \
-    "s_cmp_eq_u32 s70, 4\n\t"                        /* parked: the other wave is elsewhere */                \
+    "s_cmp_eq_u32 s70, 4\n\t"                        /* parked: wave 0 is elsewhere */                        \
     "s_cbranch_scc1 10b\n\t"                                                                                  \
     "s_mov_b64 exec, 1\n\t"                      /* Z: the top and the children have been read -- wave 0 may store */ \
     "ds_write_b32 v169, v170 offset:52\n\t"                                                                   \
@@ -460,11 +531,11 @@
     "v_mov_b32 v232, v196\n\t"                                                                                \
     "s_mov_b64 exec, 1\n\t"                                                                                   \
     "ds_write_b96 v169, v[230:232]\n\t"              /* (word 35 -- the length for a re-entry -- is wave 0's) */ \
-    RECX                                                                                                      \
+    "s_mov_b64 exec, 15\n\t"                                                                                  \
+    "ds_write_b64 v171, v[226:227]\n\t"                                                                       \
     "s_mov_b64 exec, -1\n\t"                                                                                  \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
     A2W_TIMED_BARRIER("s42")                     /* B2: the pop is in */                                      \
-    MID                                                                                                       \
     /* ---- the expansion of the top foreseen for the next iteration, from the loads asked for at B1 */       \
     "v_mov_b32 v196, v150\n\t"                                                                                \
     "v_mov_b32 v192, v164\n\t"                                                                                \
@@ -486,92 +557,10 @@
     A2A_EXPAND_NOSTORE("16")                                                                                  \
     "s_mov_b32 s74, 1\n\t"                                                                                    \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
-    "s_branch 10b\n\t"
-
-#define A2A_BODY_EXPUSH(PREFETCH, VMWAIT, SPECWAIT)                                                                    \
-    A2W_ENTRY                                                                                                 \
-    "s_mov_b32 s40, 0\n\t"                                                                                    \
-    "s_mov_b32 s74, 0\n\t"                           /* no expansion made ahead */                            \
-    A2W_ACC_ZERO("s41") A2W_ACC_ZERO("s42") A2W_ACC_ZERO("s79") A2W_ACC_ZERO("s81")                           \
-    "v_mov_b32 v190, 2\n\t"                                                                                   \
-    "v_mov_b32 v165, 4\n\t"                                                                                   \
-    "v_add_u32 v169, 4224, v191\n\t"                 /* the record */                                         \
-    "v_min_u32 v168, 3, v188\n\t"                                                                             \
-    "v_lshl_add_u32 v168, v168, 2, v169\n\t"                                                                  \
-    "v_add_u32 v168, 16, v168\n\t"                   /* the lane's word of where the pushes landed (lanes 0..3) */ \
-    "v_mov_b32 v166, s51\n\t"                        /* a closed entry of this search */                      \
-    "v_mov_b32 v170, 1\n\t"                                                                                   \
-    "s_mov_b32 s84, -1\n\t"                          /* no cell closed */                                     \
-    A2A_XBODY(PREFETCH, VMWAIT, SPECWAIT, "", A2A_PUSHES)                                                     \
-    "99:\n\t"                                                                                                 \
-    A2W_ACC_OUT("s41", "4204") A2W_ACC_OUT("s42", "4208") A2W_ACC_OUT("s79", "4216") A2W_ACC_OUT("s81", "4220") \
-    "s_waitcnt vmcnt(0)\n\t"
-
-// ---------------------------------------------------------------------------------------------------------- three waves
-// The same loop with the expansions on a wave of their own: wave 0 the pops (A2A_BODY_POP, unchanged), wave 1 the pushes, wave 2 the
-// expansions (what wave 1 does above, without the pushes; the candidates go to wave 1 through the record's words 48..55).  All three
-// meet at B1 and B2; wave 1 and wave 2 park at B1 together.
-#define A2A_BODY_EXPAND3(PREFETCH, VMWAIT, SPECWAIT)                                                          \
-    A2W_ENTRY                                                                                                 \
-    "s_mov_b32 s40, 0\n\t"                                                                                    \
-    "s_mov_b32 s74, 0\n\t"                           /* no expansion made ahead */                            \
-    A2W_ACC_ZERO("s41") A2W_ACC_ZERO("s42") A2W_ACC_ZERO("s79") A2W_ACC_ZERO("s81")                           \
-    "v_mov_b32 v190, 2\n\t"                                                                                   \
-    "v_mov_b32 v165, 4\n\t"                                                                                   \
-    "v_add_u32 v169, 4224, v191\n\t"                 /* the record */                                         \
-    "v_min_u32 v171, 3, v188\n\t"                                                                             \
-    "v_lshl_add_u32 v171, v171, 3, v169\n\t"                                                                  \
-    "v_add_u32 v171, 64, v171\n\t"                   /* the lane's candidate (lanes 0..3): words 48..55 */    \
-    "v_mov_b32 v166, s51\n\t"                        /* a closed entry of this search */                      \
-    "v_mov_b32 v150, -1\n\t"                         /* no top foreseen */                                    \
-    "v_mov_b32 v170, 1\n\t"                                                                                   \
-    "s_mov_b32 s84, -1\n\t"                          /* no cell closed */                                     \
-    A2A_XBODY(PREFETCH, VMWAIT, SPECWAIT, A2A_REC_CANDIDATES, "")                                             \
-    "99:\n\t"                                                                                                 \
-    A2W_ACC_OUT("s41", "4204") A2W_ACC_OUT("s42", "4208") A2W_ACC_OUT("s79", "4216") A2W_ACC_OUT("s81", "4220") \
-    "s_waitcnt vmcnt(0)\n\t"
-
-#define A2A_BODY_PUSH3                                                                                        \
-    A2W_ENTRY                                                                                                 \
-    "s_mov_b32 s40, 0\n\t"                                                                                    \
-    "v_add_u32 v169, 4224, v191\n\t"                 /* the record */                                         \
-    "v_min_u32 v168, 3, v188\n\t"                                                                             \
-    "v_lshl_add_u32 v171, v168, 3, v169\n\t"                                                                  \
-    "v_add_u32 v171, 64, v171\n\t"                   /* the lane's candidate (lanes 0..3): words 48..55 */    \
-    "v_lshl_add_u32 v168, v168, 2, v169\n\t"                                                                  \
-    "v_add_u32 v168, 16, v168\n\t"                   /* the lane's word of where the pushes landed */         \
-    "10:\n\t"                                                                                                 \
-    "s_barrier\n\t"                                  /* B1 */                                                 \
-    "ds_read_b32 v240, v169 offset:48\n\t"           /* the run word */                                       \
-    "ds_read_b32 v242, v169 offset:12\n\t"           /* the length (of use behind run word 3 only) */         \
-    "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
-    "v_readfirstlane_b32 s70, v240\n\t"                                                                       \
-    "s_cmp_eq_u32 s70, 2\n\t"                                                                                 \
-    "s_cbranch_scc1 99f\n\t"                                                                                  \
-    "s_cmp_eq_u32 s70, 4\n\t"                        /* parked: wave 0 is elsewhere */                        \
-    "s_cbranch_scc1 10b\n\t"                                                                                  \
-    "s_cmp_eq_u32 s70, 3\n\t"                                                                                 \
-    "s_cbranch_scc0 11f\n\t"                                                                                  \
-    "v_readfirstlane_b32 s40, v242\n\t"                                                                       \
-    "11:\n\t"                                                                                                 \
-    "s_barrier\n\t"                                  /* B2: the pop is in, the expansion's record is there */ \
-    "ds_read_b32 v210, v169\n\t"                     /* the push mask */                                      \
-    "ds_read_b64 v[226:227], v171\n\t"               /* the lane's candidate */                               \
-    "s_add_i32 s40, s40, -1\n\t"                                                                              \
-    "v_mov_b32 v167, 0x7fffffff\n\t"                                                                          \
-    A2T_PUSH_READ                                  /* the first push's ancestors: they need the length only */ \
-    "s_waitcnt lgkmcnt(2)\n\t"                                                                                \
-    "v_readfirstlane_b32 s87, v210\n\t"                                                                       \
-    A2T_PUSH_CHECK("17f") A2A_PUSH_REST("0")                                                                  \
-    A2T_PUSH_CHECK("17f") A2T_PUSH_READ A2A_PUSH_REST("1")                                                    \
-    A2T_PUSH_CHECK("17f") A2T_PUSH_READ A2A_PUSH_REST("2")                                                    \
-    "17:\n\t"                                                                                                 \
-    "s_mov_b64 exec, 15\n\t"                                                                                  \
-    "ds_write_b32 v168, v167\n\t"                                                                             \
-    "s_mov_b64 exec, -1\n\t"                                                                                  \
-    "s_waitcnt lgkmcnt(0)\n\t"                                                                                \
     "s_branch 10b\n\t"                                                                                        \
-    "99:\n\t"
+    "99:\n\t"                                                                                                 \
+    A2W_ACC_OUT("s41", "4204") A2W_ACC_OUT("s42", "4208") A2W_ACC_OUT("s79", "4216") A2W_ACC_OUT("s81", "4220") \
+    "s_waitcnt vmcnt(0)\n\t"
 
 // ---------------------------------------------------------------------------------------------------------- the deep regime
 // The same three waves for open lists that reach into global memory (bl_astar2_deep.h: PLN + 2 <= length <= deep_max): wave 0's
@@ -1009,9 +998,10 @@
     "s_cmp_eq_u32 s82, s84\n\t"                                                                               \
     "s_cbranch_scc1 " STALE "\n\t"
 
-// wave 1 for both regimes: the LDS pushes of A2A_BODY_PUSH3, or (regime word 1) the deep regime's (A2P_* above) with where they landed, and then
-// the entry at the back of the array for wave 0's next pop.  s61 = the regime; v172 landings, v173 record, v174 / v175 the lane's
+// wave 1 for both regimes: the LDS pushes, or (regime word 1) the deep regime's (A2P_* above) with where they landed, and then the
+// entry at the back of the array for wave 0's next pop.  s61 = the regime; v172 landings, v173 record, v174 / v175 the lane's
 // landing word / candidate.
+// A2T_PUSH_REST, and where the entry landed: max(landing node >> 1, 1) into lane J of v172
 #define A2A_PUSH_REST_L(J)                                                                                    \
     "s_ff1_i32_b32 s91, s87\n\t"                                                                              \
     "s_add_i32 s70, s87, -1\n\t"                                                                              \
@@ -1180,8 +1170,8 @@
 
 #define A2A_PUSH3D_CLOBBERS A2D_CLOBBERS
 
-#define A2A_PUSH3_CLOBBERS A2T_CLOBBERS, "v167", "v168", "v169", "v171"
-
-#define A2A_EXPUSH_CLOBBERS A2W_EXPAND_CLOBBERS, "v164", "v167", "v168", "v169", "v170", "v171", "v246"
+#define A2W_EXPAND_CLOBBERS A2T_CLOBBERS, "s82", "s83", "s84", "s85", "v150", "v151", "v152", "v153", "v154", "v155", "v156", "v157", "v158", "v159", \
+    "v160", "v161", "v162", "v163", "v165", "v166"
+#define A2A_EXPAND3_CLOBBERS A2W_EXPAND_CLOBBERS, "v164", "v167", "v168", "v169", "v170", "v171", "v246"
 
 #endif

@@ -1913,7 +1913,7 @@ extern "C" void* bl_dist_device_ptr(bl_dist* d)
 #define ASTAR_ST_NOPATH 1        // early exit or open list exhausted: 1-pose path
 #define ASTAR_ST_CAPACITY 2
 #define ASTAR_ST_LIMIT 3
-#define ASTAR_ST_BROKEN 4          // the two wavefronts of a search lost each other (bl_astar2_duo.h: never observed; ends the search instead of hanging)
+#define ASTAR_ST_BROKEN 4          // the wavefronts of a search lost each other (bl_astar2_ahead.h's flag never came: never observed; ends the search instead of hanging)
 
 struct astar_result { int status; int path_len; long long pops; long long pushes; bl_pose_xyt_t start; long long stamps[6];
                       long long path_off; };           // batch form: where the path went in the shared pool
@@ -2019,6 +2019,7 @@ struct astar_args {
     // (an array in pinned host memory, read once per workgroup: indexing a by-value kernel argument with blockIdx moves the
     // whole argument block out of scalar registers and slowed every search by a third)
     const astar_unit* units;
+    bool turbo;                        // k_astar2's straight-line loops where they apply (false: the C++ loop everywhere, BOTLAB_ASTAR_NO_TURBO)
 };
 
 // The LDS part of the heap is addressed through an address_space(3) pointer: a two-way select between an LDS and a
@@ -2474,15 +2475,30 @@ extern "C" int bl_astar_set_open_capacity(bl_ctx* ctx, int64_t nodes)
 static int astar_cells_to_path(const bl_frame& frame, const bl_pose_xyt_t& start, const int32_t* cells, int n,
                                bl_pose_xyt_t* out_path, int cap);
 
+// The switches that force another form of the search (A/B runs, probes, tests), read once per process:
+//   BOTLAB_ASTAR_NO_TURBO    k_astar2's C++ loop everywhere
+//   BOTLAB_ASTAR_V1          k_astar's 8-byte entries
+//   BOTLAB_ASTAR_DUO=0       k_astar2 on one wave everywhere
+//   BOTLAB_ASTAR_SMALL_LDS   the replanner's 40 KB footprint on a lone search (on one wave, as the replanner's units run it);
+//                            =3: on three waves -- short searches then reach the deep regime's three-wave loop
+struct astar_forms { bool no_turbo, v1, one_wave, small_lds, small_lds3; };
+static const astar_forms& astar_switches()
+{
+    static const astar_forms f = [] {
+        const char* duo = getenv("BOTLAB_ASTAR_DUO");
+        const char* small = getenv("BOTLAB_ASTAR_SMALL_LDS");
+        return astar_forms{getenv("BOTLAB_ASTAR_NO_TURBO") != nullptr, getenv("BOTLAB_ASTAR_V1") != nullptr,
+                           duo != nullptr && atoi(duo) == 0, small != nullptr, small != nullptr && atoi(small) == 3};
+    }();
+    return f;
+}
+
 static int astar_prepare(bl_ctx* ctx, const bl_dist* d)
 {
     if (!ctx->astar) {
         ctx->astar = new bl_astar_state();
         memset((void*)ctx->astar, 0, sizeof(bl_astar_state));
         ctx->astar->path_head = ASTAR_PATH_HEAD;
-        if (getenv("BOTLAB_ASTAR_NO_TURBO")) { const bool off = false; BL_HIP(hipMemcpyToSymbol(HIP_SYMBOL(a2_turbo_enabled), &off, sizeof(off))); }
-        if (getenv("BOTLAB_ASTAR_DEEP_AHEAD") && atoi(getenv("BOTLAB_ASTAR_DEEP_AHEAD")) == 0) { const bool off = false; BL_HIP(hipMemcpyToSymbol(HIP_SYMBOL(a2_deep_ahead_enabled), &off, sizeof(off))); }
-        if (getenv("BOTLAB_ASTAR_AHEAD") && atoi(getenv("BOTLAB_ASTAR_AHEAD")) == 0) { const bool off = false; BL_HIP(hipMemcpyToSymbol(HIP_SYMBOL(a2_walk_ahead_enabled), &off, sizeof(off))); }
         if (const char* e = getenv("BOTLAB_ASTAR_PATH_HEAD")) { const int v = atoi(e); if (v >= 1 && v <= ASTAR_PATH_HEAD) ctx->astar->path_head = v; }
         for (int i = 0; i < ASTAR_SLOTS; ++i) {
             BL_HIP(hipHostMalloc((void**)&ctx->astar->h_out[i], ASTAR_HDR + ASTAR_PATH_HEAD * 4, hipHostMallocDefault));
@@ -2616,6 +2632,7 @@ static int astar_fill(bl_ctx* ctx, const bl_dist* d, const bl_pose_xyt_t* start,
         memset(&a.start_host, 0, sizeof(a.start_host));
     }
     a.max_pops = 1ll << 31;
+    a.turbo = !astar_switches().no_turbo;
     if (const char* e = getenv("BOTLAB_ASTAR_MAX_POPS")) { const long long v = atoll(e); if (v > 0) a.max_pops = v; }      // probes: stop after v pops
     bl_dist* dm = const_cast<bl_dist*>(d);           // closed[] is search scratch that travels with the grid
     if (++dm->closed_gen >= (1u << 28)) {            // (a wrap every 2.7e8 searches: start over from a zeroed array)
@@ -2645,22 +2662,17 @@ static int astar_after(bl_ctx* ctx, const bl_dist* d)
 // (the reference's own parameters give -3998 at the least).  BOTLAB_ASTAR_V1=1: k_astar's 8-byte entries (probes, A/B runs).
 static bool astar_split_ok(const bl_astar_state* s)
 {
-    static const bool force_v1 = getenv("BOTLAB_ASTAR_V1") != nullptr;
-    return !force_v1 && s->lut_valid && s->lut_min > -32768;
+    return !astar_switches().v1 && s->lut_valid && s->lut_min > -32768;
 }
 
 extern "C" int bl_astar_debug_last_kernel(bl_ctx* ctx) { return ctx && ctx->astar ? ctx->astar->last_kernel : 0; }
 
-// Threads of a k_astar2 workgroup.  128: a second wavefront runs the expansions of the LDS-regime loop beside the first
-// (bl_astar2_duo.h: -4 .. -9 % per pop there).  Only for searches that have their compute unit to themselves (the 147 KB heap):
-// the replanner's units share CUs four at a time, where a second wave per search would take issue slots from the others.
-// BOTLAB_ASTAR_DUO=0: one wave everywhere (A/B runs, tests).
+// Threads of a k_astar2 workgroup.  192: pops, pushes and expansions on three wavefronts (bl_astar2_ahead.h).  Only for searches that
+// have their compute unit to themselves (the 147 KB heap): the replanner's units share CUs four at a time, where more waves per
+// search would take issue slots from the others.  BOTLAB_ASTAR_DUO=0: one wave everywhere (A/B runs, tests).
 static int astar2_threads(bool shares_cu = false)
 {
-    static const bool duo = !(getenv("BOTLAB_ASTAR_DUO") && atoi(getenv("BOTLAB_ASTAR_DUO")) == 0);
-    // (bl_astar2_ahead.h: pops / pushes / expansions on three waves unless BOTLAB_ASTAR_AHEAD says 0 -- the duo loop -- or 1 -- its two-wave form)
-    static const bool three = !(getenv("BOTLAB_ASTAR_AHEAD") && atoi(getenv("BOTLAB_ASTAR_AHEAD")) != 2);
-    return duo && !shares_cu ? (three ? 192 : 128) : 64;
+    return astar_switches().one_wave || shares_cu ? 64 : 192;
 }
 
 static void astar_launch_kernel(bl_ctx* ctx, const astar_args& a, int workgroups, bool split)
@@ -2670,12 +2682,10 @@ static void astar_launch_kernel(bl_ctx* ctx, const astar_args& a, int workgroups
     // flight then take a dozen CUs out of the filter's single round (4096 x 4096 / 256k particles: k_mcl_main 0.43 -> 0.37 ms
     // with the small footprint, the searches themselves no slower).  A search that runs alone takes the 147 KB heap: an open
     // list spilling past the LDS levels pays an HBM round trip per heap level.
-    static const bool force_small = getenv("BOTLAB_ASTAR_SMALL_LDS") != nullptr;     // probes: the replanner's footprint on a lone search
-    const bool small = ctx->astar_small_lds || force_small;
+    const astar_forms& f = astar_switches();
+    const bool small = ctx->astar_small_lds || f.small_lds;
     if (ctx->astar) ctx->astar->last_kernel = split ? 2 : 1;
-    // (BOTLAB_ASTAR_SMALL_LDS=3: the small footprint on three waves -- tests reach the deep regime's three-wave loop with short searches)
-    static const bool small3 = force_small && atoi(getenv("BOTLAB_ASTAR_SMALL_LDS")) == 3;
-    if (split && small) hipLaunchKernelGGL((k_astar2<a2_small>), dim3(workgroups), dim3(astar2_threads(!(small3 && !ctx->astar_small_lds))), a2_small::BYTES, ctx->stream, a);
+    if (split && small) hipLaunchKernelGGL((k_astar2<a2_small>), dim3(workgroups), dim3(astar2_threads(!(f.small_lds3 && !ctx->astar_small_lds))), a2_small::BYTES, ctx->stream, a);
     else if (split) hipLaunchKernelGGL((k_astar2<a2_big>), dim3(workgroups), dim3(astar2_threads()), a2_big::BYTES, ctx->stream, a);
     else if (small) hipLaunchKernelGGL((k_astar<AH_LDS_SMALL, AH_COST_LDS_SMALL>), dim3(workgroups), dim3(64), AH_LDS_SMALL_BYTES, ctx->stream, a);
     else hipLaunchKernelGGL((k_astar<AH_LDS, AH_COST_LDS>), dim3(workgroups), dim3(64), AH_LDS_BYTES, ctx->stream, a);
@@ -2766,12 +2776,8 @@ extern "C" int bl_astar_search_result(bl_ctx* ctx, bl_pose_xyt_t* out_path, int 
 #ifdef BL_ASTAR_STAMPS
     {
         const double pp = (double)(r.pops ? r.pops : 1);
-        if (astar2_threads() >= 128 && !(ctx->astar_small_lds || getenv("BOTLAB_ASTAR_SMALL_LDS")) && !(getenv("BOTLAB_ASTAR_AHEAD") && atoi(getenv("BOTLAB_ASTAR_AHEAD")) == 0))
-            fprintf(stderr, "[astar ahead stamps] pops %lld: cycles/pop inside barriers -- wave 0: B1 %.0f, B2 %.0f; wave 1: B1 %.0f, B2 %.0f | walks taken again %.4f per pop | search %.0f cycles/pop | expansions made ahead %lld, not %lld\n", r.pops,
-                    (double)r.stamps[0] / pp, (double)r.stamps[1] / pp, (double)r.stamps[2] / pp, (double)r.stamps[4] / pp, (double)r.stamps[5] / pp,
-                    (double)r.stamps[3] * 1e-8 * 2.4e9 / pp, (long long)(r.path_off & 0xffffffffll), (long long)(r.path_off >> 32));
-        else if (astar2_threads() >= 128 && !(ctx->astar_small_lds || getenv("BOTLAB_ASTAR_SMALL_LDS")))
-            fprintf(stderr, "[astar duo stamps] pops %lld: cycles/pop -- wave 1: Z to the wait %.0f, the wait %.0f, expansion %.0f, record %.0f; wave 0 inside Y %.0f | search %.0f cycles/pop | tops foreseen %lld, not %lld\n", r.pops,
+        if (astar2_threads() == 192 && !(ctx->astar_small_lds || astar_switches().small_lds))
+            fprintf(stderr, "[astar ahead stamps] pops %lld: cycles/pop inside barriers -- wave 0: B1 %.0f, B2 %.0f; wave 2: B1 %.0f; wave 1: B1 %.0f | walks taken again %.4f per pop | search %.0f cycles/pop | expansions made ahead %lld, pushes whose ancestor line was read again %lld\n", r.pops,
                     (double)r.stamps[0] / pp, (double)r.stamps[1] / pp, (double)r.stamps[2] / pp, (double)r.stamps[4] / pp, (double)r.stamps[5] / pp,
                     (double)r.stamps[3] * 1e-8 * 2.4e9 / pp, (long long)(r.path_off & 0xffffffffll), (long long)(r.path_off >> 32));
         else
@@ -2922,6 +2928,7 @@ static int astar_batch_cells(bl_ctx* ctx, const bl_dist* d, const bl_pose_xyt_t*
         a.start_host = *start;
         bl_global_to_cell((double)start->x, (double)start->y, d->frame, &a.sx, &a.sy);
         a.max_pops = 1ll << 31;
+        a.turbo = !astar_switches().no_turbo;
         a.units = nullptr;
         a.batch_goals = s->b_goals;
         a.heap_stride = s->b_heap_each; a.closed_stride = (long long)cells; a.path_stride = (long long)s->b_path_each;

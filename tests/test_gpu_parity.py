@@ -951,16 +951,15 @@ def _fixtures_in_child(queue_path):
     json.dump(out, open(queue_path, "w"))
 
 
-@pytest.mark.parametrize("env", ["BOTLAB_ASTAR_NO_TURBO", "BOTLAB_ASTAR_V1", "BOTLAB_ASTAR_DUO=0", "BOTLAB_ASTAR_AHEAD=1", "BOTLAB_ASTAR_AHEAD=0",
-                                 "BOTLAB_ASTAR_DEEP_AHEAD=0", "BOTLAB_ASTAR_SMALL_LDS=3", "BOTLAB_ASTAR_SMALL_LDS=3,BOTLAB_ASTAR_DEEP_AHEAD=0"])
+@pytest.mark.parametrize("env", ["BOTLAB_ASTAR_NO_TURBO", "BOTLAB_ASTAR_V1", "BOTLAB_ASTAR_DUO=0", "BOTLAB_ASTAR_SMALL_LDS=1",
+                                 "BOTLAB_ASTAR_SMALL_LDS=3"])
 def test_astar_fixtures_with_the_other_forms_of_the_search(tmp_path, env):
     """the same fixtures through k_astar2's C++ forms (no straight-line loop), through round 4's k_astar (8-byte entries) -- the
     forms a search falls back to for lists of 0-1 entries, cost tables beyond LDS or below the 16-bit key range -- and through the
-    one-wave straight-line loop (what the replanner's units run), through round 5's two-wave loop (bl_astar2_duo.h, BOTLAB_ASTAR_AHEAD=0)
-    and through the two-wave form of the loop single searches take by default (bl_astar2_ahead.h: the next pop's walk beside the
-    pushes, expansions made ahead; three waves by default); with the one-wave loop beyond LDS in place of the three-wave one
-    (BOTLAB_ASTAR_DEEP_AHEAD=0), and with the 40 KB footprint on three waves (BOTLAB_ASTAR_SMALL_LDS=3: every maze search of more than
-    ~5 000 pops then crosses into the deep regime and back, and the three-wave loops run with the small footprint's tree shape)"""
+    one-wave straight-line loops in place of the three-wave ones single searches take by default (bl_astar2_ahead.h); with the
+    40 KB footprint on one wave (BOTLAB_ASTAR_SMALL_LDS=1: exactly what the replanner's units run -- every maze search of more than
+    ~5 000 pops then crosses into the one-wave deep loop, bl_astar2_deep.h, and back) and on three waves (BOTLAB_ASTAR_SMALL_LDS=3:
+    the same crossings through the deep regime's three-wave loop, and the three-wave loops with the small footprint's tree shape)"""
     import json
     import subprocess
     out = str(tmp_path / "res.json")
