@@ -33,7 +33,14 @@ class SearchParams(C.Structure):
                 ("distanceCostExponent", C.c_double)]
 
 
-assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56
+class PfSpread(C.Structure):
+    """bl_pf_spread_t: spread of the posterior (80 bytes)."""
+    _fields_ = [("n_eff", C.c_double), ("mean_x", C.c_double), ("mean_y", C.c_double), ("var_x", C.c_double), ("var_y", C.c_double),
+                ("cov_xy", C.c_double), ("theta_resultant", C.c_double), ("units_sum", C.c_uint64), ("units_sq_lo", C.c_uint64),
+                ("units_sq_hi", C.c_uint64)]
+
+
+assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56 and C.sizeof(PfSpread) == 80
 
 class MotionPlannerState(C.Structure):
     """bl_motion_planner_t: the MotionPlanner members plan_path_to_frontier reads (motion_planner.hpp:153-165)."""
@@ -84,6 +91,8 @@ SIGNATURES = {
     "bl_pf_set_exchange_buffers": (C.c_int, [_vp, _vp, _vp]),
     "bl_pf_exchange_rec_ptr": (_vp, [_vp]),
     "bl_pf_init_at_pose": (C.c_int, [_vp, _P(Pose), C.c_uint64]),
+    "bl_pf_init_uniform": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_int64, C.c_uint64]),
+    "bl_pf_spread": (C.c_int, [_vp, _P(PfSpread)]),
     "bl_pf_set_particles": (C.c_int, [_vp, _vp, _vp]),
     "bl_pf_get_particles": (C.c_int, [_vp, _vp]),
     "bl_pf_set_noise_seed": (C.c_int, [_vp, C.c_uint64]),

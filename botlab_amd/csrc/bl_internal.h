@@ -145,6 +145,9 @@ int bl_planner_reserve(bl_planner* p, const bl_grid* map, bl_planner_snap* out);
 int bl_planner_commit(bl_planner* p, const bl_pose_xyt_t* goal, const bl_search_params_t* params);
 void bl_planner_cancel(bl_planner* p);
 
+// bl_planning.hip: the device arrays of a transformed distance grid (BL_ERR_ARG before its first transform)
+int bl_dist_view(const bl_dist* d, const uint16_t** l1, const float** lut, int* width, int* height);
+
 // RAII-less helpers
 int bl_timer_begin(bl_ctx* ctx, int id, hipEvent_t* a, hipEvent_t* b);
 int bl_timer_end(bl_ctx* ctx, int id, hipEvent_t a, hipEvent_t b);

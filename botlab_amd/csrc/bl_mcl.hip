@@ -113,6 +113,12 @@ struct bl_pf {
     unsigned long long sh_gen;                 // moved updates exchanged so far
     int sh_tiles_all;                          // tiles of the padded particle set (one parity of the tile-sum buffer)
     int64_t sh_bytes_pulled_bound;             // (diagnostic) upper bound of the bytes the last k_mcl_main may have read from other ranks
+    // global localization (bl_pf_init_uniform, bl_pf_spread): per-tile counts / offsets of the eligible cells, their ordered list,
+    // the spread's block partials and result -- allocated on first use
+    uint32_t* gl_tiles; size_t gl_tiles_cap;   // [2][tiles]: counts, then exclusive offsets; + 1 word: the total
+    uint32_t* gl_list; size_t gl_list_cap;     // eligible cell indices, row-major order
+    void* sp_parts;                            // [SPREAD_MAX_BLOCKS] spread_part
+    void* sp_out;                              // spread_dev
 };
 
 // ---------------------------------------------------------------- device helpers
@@ -1614,7 +1620,8 @@ extern "C" void bl_pf_destroy(bl_pf* pf)
     (void)hipStreamSynchronize(pf->ctx->stream);
     if (!pf->rec_external) { if (pf->rec[0]) (void)hipFree(pf->rec[0]); if (pf->rec[1]) (void)hipFree(pf->rec[1]); }
     void* ptrs[] = {pf->fin_wild, pf->tile_partials, pf->fin_recs, pf->fin_tabs, pf->fin_sync, pf->prefix, pf->parent, pf->state, pf->partials, pf->block_sums, pf->dbg_idx, pf->dbg_like,
-                    pf->d_noise, pf->d_export, pf->sh_xchg, pf->sh_tab, pf->sh_fin, pf->sh_flags, pf->sh_peers_dev, pf->strict_recs, pf->strict_starts};
+                    pf->d_noise, pf->d_export, pf->sh_xchg, pf->sh_tab, pf->sh_fin, pf->sh_flags, pf->sh_peers_dev, pf->strict_recs, pf->strict_starts,
+                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete pf;
 }
@@ -2955,5 +2962,314 @@ extern "C" int bl_pf_debug_last(bl_pf* pf, int32_t* resample_idx, int32_t* likel
     if (likelihood_half_units)
         BL_HIP(hipMemcpyAsync(likelihood_half_units, pf->dbg_like, (size_t)pf->n_local * 4, hipMemcpyDeviceToHost, pf->ctx->stream));
     BL_HIP(hipStreamSynchronize(pf->ctx->stream));
+    return BL_OK;
+}
+
+// ---------------------------------------------------------------- global localization
+// bl_pf_init_uniform: Monte-Carlo localization started from a cloud spread uniformly over the free space of a known map.
+// A cell is ELIGIBLE when its log-odds is < 0 (the reference's "free", frontiers.hpp:23-24) and, with a distance grid, when the
+// float that grid shows for it (-1 where no obstacle exists) is > min_dist.  Four launches:
+//   k_gl_count    one workgroup per tile of GL_TILE cells, 16 cells per lane (one 16-byte load of the log-odds): eligible cells per tile
+//   k_gl_scan     one workgroup: exclusive offsets of the tile counts and the total F (read back: F == 0 is an argument error)
+//   k_gl_compact  the same tiles again: the index of every eligible cell, in row-major order, so that list[r] is the r-th one (staged
+//                 in LDS per tile, then stored contiguously)
+//   k_pf_init_uniform  one thread per particle, all N records
+// The cloud depends on (seed, map, dist, min_dist, N) alone -- not on the tile size, the launch shape or the number of ranks.
+#define GL_THREADS 256
+#define GL_TILE (GL_THREADS * 16)
+#define GL_SCAN_THREADS 1024
+#define GL_CTR1 0xfffffffeu                   // Philox counter words of the uniform initialisation: (m, GL_CTR1, GL_CTR2, 0 / 1).  The
+#define GL_CTR2 0x676c6f62u                   // action noise uses (m, step, 0x6d636c31, 0), initializeFilterAtPose (m, 0xffffffff, 0x6d636c31, 0)
+
+struct gl_src { const int8_t* cells; const uint16_t* l1; const float* lut; float min_dist; uint32_t n; };
+
+// bit k: cell base + k is eligible (cells at or past n are not)
+__device__ __forceinline__ uint32_t gl_mask16(const gl_src& s, uint32_t base)
+{
+    uint32_t m = 0;
+    if (base + 16 <= s.n) {
+        const uint4 v = *(const uint4*)(s.cells + base);          // base is a multiple of 16
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t t = w[q] & 0x80808080u;                // sign bits of four cells: log-odds < 0
+            m |= (((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u)) << (4 * q);
+        }
+    } else {
+        for (uint32_t k = 0; k < 16 && base + k < s.n; ++k)
+            if (s.cells[base + k] < 0) m |= 1u << k;
+    }
+    if (s.l1) {
+        for (uint32_t r = m; r; r &= r - 1) {
+            const int k = __builtin_ctz(r);
+            const int v = s.l1[base + k];
+            const float d = v == 0xFFFF ? -1.0f : s.lut[v];
+            if (!(d > s.min_dist)) m &= ~(1u << k);
+        }
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(GL_THREADS) void k_gl_count(gl_src s, uint32_t* tile_count)
+{
+    const uint32_t base = blockIdx.x * GL_TILE + threadIdx.x * 16;
+    uint32_t c = base < s.n ? (uint32_t)__popc(gl_mask16(s, base)) : 0u;
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    __shared__ uint32_t ws[GL_THREADS / 64];
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// offs[t] = sum of count[0..t), offs[tiles] = F
+__global__ __launch_bounds__(GL_SCAN_THREADS) void k_gl_scan(const uint32_t* count, uint32_t* offs, int tiles)
+{
+    const int per = (tiles + GL_SCAN_THREADS - 1) / GL_SCAN_THREADS;
+    const int b = threadIdx.x * per, e = min(b + per, tiles);
+    uint32_t sum = 0;
+    for (int i = b; i < e; ++i) sum += count[i];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t inc = sum;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += t;
+    }
+    __shared__ uint32_t ws[GL_SCAN_THREADS / 64];
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    uint32_t wbase = 0;
+    for (int w = 0; w < wv; ++w) wbase += ws[w];
+    uint32_t run = wbase + inc - sum;
+    for (int i = b; i < e; ++i) { offs[i] = run; run += count[i]; }
+    if (threadIdx.x == GL_SCAN_THREADS - 1) offs[tiles] = wbase + inc;
+}
+
+__global__ __launch_bounds__(GL_THREADS) void k_gl_compact(gl_src s, const uint32_t* offs, uint32_t* list)
+{
+    const uint32_t base = blockIdx.x * GL_TILE + threadIdx.x * 16;
+    uint32_t m = base < s.n ? gl_mask16(s, base) : 0u;
+    const uint32_t c = (uint32_t)__popc(m);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t inc = c;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += t;
+    }
+    __shared__ uint32_t ws[GL_THREADS / 64];
+    __shared__ uint32_t stage[GL_TILE];                          // the tile's part of the list, in order (16 KB)
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    uint32_t at = inc - c;
+    for (int w = 0; w < wv; ++w) at += ws[w];
+    for (; m; m &= m - 1) stage[at++] = base + (uint32_t)__builtin_ctz(m);
+    __syncthreads();
+    // then out to HBM contiguously: consecutive lanes, consecutive words
+    const uint32_t total = ws[0] + ws[1] + ws[2] + ws[3];
+    uint32_t* dst = list + offs[blockIdx.x];
+    for (uint32_t i = threadIdx.x; i < total; i += GL_THREADS) dst[i] = stage[i];
+}
+
+// Particle m (global index; every rank fills the whole record, its own slice of the parents):
+//   (a0..a3) = Philox4x32-10(counter (m, GL_CTR1, GL_CTR2, 0), key (seed lo, seed hi)),  b0 = word 0 of counter (m, GL_CTR1, GL_CTR2, 1)
+//   r     = hi64((a0 << 32 | a1) * F)                    rank of the eligible cell, in [0, F); bias below F / 2^64
+//   (cx, cy) = (list[r] % W, list[r] / W)
+//   fx = (a2 >> 8) * 2^-24, fy = (a3 >> 8) * 2^-24, ft = (b0 >> 8) * 2^-24      exact doubles in [0, 1)
+//   x  = (float)((double)origin_x + ((double)cx + fx) * (double)metersPerCell)   (cx + fx is exact; two double roundings, then one to float:
+//   y  = (float)((double)origin_y + ((double)cy + fy) * (double)metersPerCell)    grid_position_to_global_position, grid_utils.hpp:15-19)
+//   theta = bl_wrap_to_pi((float)((2 ft - 1) * M_PI))      (2 ft - 1 exact; the wrap only moves -(float)M_PI, which the narrowing can reach)
+// Plain IEEE double and float operations (-ffp-contract=off): a numpy model reproduces every bit.  Parent pose = pose, weight unit 1.
+__global__ void k_pf_init_uniform(float4* rec, float4* parent, int N, int lo, int n_local, const uint32_t* list, uint32_t F, uint32_t W,
+                                  double ox, double oy, double mpc, uint32_t k0, uint32_t k1)
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= N) return;
+    uint32_t a[4], b[4];
+    bl_philox4x32((uint32_t)m, GL_CTR1, GL_CTR2, 0u, k0, k1, a);
+    bl_philox4x32((uint32_t)m, GL_CTR1, GL_CTR2, 1u, k0, k1, b);
+    const uint32_t r = (uint32_t)__umul64hi(((unsigned long long)a[0] << 32) | a[1], (unsigned long long)F);
+    const uint32_t cell = list[r];
+    const uint32_t cx = cell % W, cy = cell / W;
+    const double fx = (double)(a[2] >> 8) * 0x1p-24, fy = (double)(a[3] >> 8) * 0x1p-24, ft = (double)(b[0] >> 8) * 0x1p-24;
+    const float x = (float)(ox + ((double)cx + fx) * mpc);
+    const float y = (float)(oy + ((double)cy + fy) * mpc);
+    const float th = bl_wrap_to_pi((float)((2.0 * ft - 1.0) * BL_PI));
+    rec[m] = make_float4(x, y, th, __uint_as_float(1u));
+    const int j = m - lo;
+    if (j >= 0 && j < n_local) parent[j] = make_float4(x, y, th, 0.0f);
+}
+
+// a composed shard cannot run the record-based finish alone: the last particle's pose stands in (as after bl_pf_set_particles)
+__global__ void k_pf_pose_from_rec(pf_state* state, const float4* rec, int m, int64_t utime)
+{
+    const float4 r = rec[m];
+    state->pose.utime = utime; state->pose.x = r.x; state->pose.y = r.y; state->pose.theta = r.z;
+}
+
+extern "C" int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* dist, float min_dist, int64_t utime, uint64_t seed)
+{
+    BL_CHECK_ARG(pf != nullptr && map != nullptr);
+    const int W = map->frame.width, H = map->frame.height;
+    BL_CHECK_ARG(W > 0 && H > 0 && (int64_t)W * H < ((int64_t)1 << 31));
+    if (pf->pending_end) { bl_set_error("update pending"); return BL_ERR_STATE; }
+    gl_src s;
+    s.cells = map->cells; s.l1 = nullptr; s.lut = nullptr; s.min_dist = min_dist; s.n = (uint32_t)((int64_t)W * H);
+    if (dist) {
+        int dw = 0, dh = 0;
+        int rc = bl_dist_view(dist, &s.l1, &s.lut, &dw, &dh);
+        if (rc) return rc;
+        if (dw != W || dh != H) { bl_set_error("distance grid %dx%d does not match the map %dx%d", dw, dh, W, H); return BL_ERR_ARG; }
+    }
+    BL_HIP(hipSetDevice(pf->ctx->device));
+    if (!pf->prefix) { int rc = pf_alloc(pf); if (rc) return rc; }
+    hipStream_t st = pf->ctx->stream;
+    const int tiles = (int)((s.n + GL_TILE - 1) / GL_TILE);
+    if (pf->gl_tiles_cap < (size_t)2 * tiles + 1) {
+        if (pf->gl_tiles) { BL_HIP(hipStreamSynchronize(st)); BL_HIP(hipFree(pf->gl_tiles)); pf->gl_tiles = nullptr; pf->gl_tiles_cap = 0; }
+        BL_HIP(hipMalloc((void**)&pf->gl_tiles, ((size_t)2 * tiles + 1) * sizeof(uint32_t)));
+        pf->gl_tiles_cap = (size_t)2 * tiles + 1;
+    }
+    uint32_t* counts = pf->gl_tiles;
+    uint32_t* offs = pf->gl_tiles + tiles;
+    hipLaunchKernelGGL(k_gl_count, dim3(tiles), dim3(GL_THREADS), 0, st, s, counts);
+    hipLaunchKernelGGL(k_gl_scan, dim3(1), dim3(GL_SCAN_THREADS), 0, st, (const uint32_t*)counts, offs, tiles);
+    BL_HIP(hipGetLastError());
+    uint32_t F = 0;
+    BL_HIP(hipMemcpyAsync(&F, offs + tiles, sizeof(F), hipMemcpyDeviceToHost, st));
+    BL_HIP(hipStreamSynchronize(st));
+    if (F == 0) { bl_set_error("no eligible cell: the map has no cell with log-odds < 0%s", dist ? " and distance > min_dist" : ""); return BL_ERR_ARG; }
+    if (pf->gl_list_cap < F) {
+        if (pf->gl_list) { BL_HIP(hipFree(pf->gl_list)); pf->gl_list = nullptr; pf->gl_list_cap = 0; }
+        BL_HIP(hipMalloc((void**)&pf->gl_list, (size_t)F * sizeof(uint32_t)));
+        pf->gl_list_cap = F;
+    }
+    hipLaunchKernelGGL(k_gl_compact, dim3(tiles), dim3(GL_THREADS), 0, st, s, (const uint32_t*)offs, pf->gl_list);
+    pf->cur = 0;
+    if (pf->sh_broken) { pf->sh_broken = false; BL_HIP(hipMemsetAsync(&pf->state->shard_broken, 0, sizeof(unsigned int), st)); }
+    hipLaunchKernelGGL(k_pf_init_uniform, dim3((pf->N + 255) / 256), dim3(256), 0, st, pf->rec[0], pf->parent, pf->N, pf->lo, pf->n_local,
+                       (const uint32_t*)pf->gl_list, F, (uint32_t)W, (double)map->frame.ox, (double)map->frame.oy, (double)map->frame.mpc,
+                       (uint32_t)seed, (uint32_t)(seed >> 32));
+    BL_HIP(hipGetLastError());
+    pf->pose_utime = utime; pf->parent_utime = utime;
+    pf->initialized = true;
+    pf->uniform_now = true;                      // weights 1 / N
+    // poseEstimate() = estimatePosteriorPose of the new cloud (it also centres the next update's LDS map window); then the plain
+    // prefix scan bl_pf_init_at_pose ends with, which knows the weights are equal
+    if (pf->sh_world > 1) hipLaunchKernelGGL(k_pf_pose_from_rec, dim3(1), dim3(1), 0, st, pf->state, (const float4*)pf->rec[0], pf->N - 1, utime);
+    else { int rc = pf_scan(pf, 0, 1, utime); if (rc) return rc; }
+    return pf_scan(pf, 0, 0, 0);
+}
+
+// Spread of the posterior over the current record: two passes of a fixed shape (the block count depends on N alone; every sum is
+// formed in the same order on every run) -- units, their squares (128 bits), units * (x, y, sin theta, cos theta); then
+// units * (dx^2, dy^2, dx dy) about the weighted mean.  Each pass: one launch over the record, one workgroup over its block partials.
+#define SPREAD_THREADS 256
+#define SPREAD_MAX_BLOCKS 1024
+struct spread_part { unsigned long long s, q_lo, q_hi; double v[4]; };
+struct spread_dev { double mean_x, mean_y; bl_pf_spread_t out; };
+
+static int spread_blocks(int N) { const int b = (N + SPREAD_THREADS * 4 - 1) / (SPREAD_THREADS * 4); return b < 1 ? 1 : b > SPREAD_MAX_BLOCKS ? SPREAD_MAX_BLOCKS : b; }
+
+// tree over the workgroup (fixed order); the total lands in thread 0's p
+__device__ void spread_block_reduce(spread_part& p)
+{
+    __shared__ unsigned long long ss[SPREAD_THREADS], sl[SPREAD_THREADS], sh[SPREAD_THREADS];
+    __shared__ double sv[4][SPREAD_THREADS];
+    const int t = threadIdx.x;
+    ss[t] = p.s; sl[t] = p.q_lo; sh[t] = p.q_hi;
+    for (int k = 0; k < 4; ++k) sv[k][t] = p.v[k];
+    __syncthreads();
+    for (int h = SPREAD_THREADS / 2; h > 0; h >>= 1) {
+        if (t < h) {
+            ss[t] += ss[t + h];
+            const unsigned long long lo = sl[t] + sl[t + h];
+            sh[t] += sh[t + h] + (lo < sl[t] ? 1ull : 0ull);
+            sl[t] = lo;
+            for (int k = 0; k < 4; ++k) sv[k][t] += sv[k][t + h];
+        }
+        __syncthreads();
+    }
+    p.s = ss[0]; p.q_lo = sl[0]; p.q_hi = sh[0];
+    for (int k = 0; k < 4; ++k) p.v[k] = sv[k][0];
+}
+
+__global__ __launch_bounds__(SPREAD_THREADS) void k_pf_spread(const float4* rec, int N, int pass, spread_part* parts, const spread_dev* dev)
+{
+    spread_part p;
+    p.s = 0; p.q_lo = 0; p.q_hi = 0;
+    for (int k = 0; k < 4; ++k) p.v[k] = 0.0;
+    const double mx = pass ? dev->mean_x : 0.0, my = pass ? dev->mean_y : 0.0;
+    const int stride = gridDim.x * SPREAD_THREADS;
+    for (int m = blockIdx.x * SPREAD_THREADS + threadIdx.x; m < N; m += stride) {
+        const float4 r = rec[m];
+        const uint32_t u = __float_as_uint(r.w);
+        const double du = (double)u;
+        if (pass == 0) {
+            p.s += u;
+            const unsigned long long u2 = (unsigned long long)u * u;
+            p.q_lo += u2;
+            p.q_hi += p.q_lo < u2 ? 1ull : 0ull;
+            double sn, cs;
+            sincos((double)r.z, &sn, &cs);
+            p.v[0] += du * (double)r.x; p.v[1] += du * (double)r.y; p.v[2] += du * sn; p.v[3] += du * cs;
+        } else {
+            const double dx = (double)r.x - mx, dy = (double)r.y - my;
+            p.v[0] += du * dx * dx; p.v[1] += du * dy * dy; p.v[2] += du * dx * dy;
+        }
+    }
+    spread_block_reduce(p);
+    if (threadIdx.x == 0) parts[blockIdx.x] = p;
+}
+
+__global__ __launch_bounds__(SPREAD_THREADS) void k_pf_spread_fin(const spread_part* parts, int nparts, int pass, spread_dev* dev)
+{
+    spread_part p;
+    p.s = 0; p.q_lo = 0; p.q_hi = 0;
+    for (int k = 0; k < 4; ++k) p.v[k] = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += SPREAD_THREADS) {
+        const spread_part& q = parts[i];
+        p.s += q.s;
+        const unsigned long long lo = p.q_lo + q.q_lo;
+        p.q_hi += q.q_hi + (lo < p.q_lo ? 1ull : 0ull);
+        p.q_lo = lo;
+        for (int k = 0; k < 4; ++k) p.v[k] += q.v[k];
+    }
+    spread_block_reduce(p);
+    if (threadIdx.x != 0) return;
+    const double S = (double)(pass == 0 ? p.s : dev->out.units_sum);       // (the second pass sums no units)
+    if (pass == 0) {
+        dev->out.units_sum = p.s; dev->out.units_sq_lo = p.q_lo; dev->out.units_sq_hi = p.q_hi;
+        dev->mean_x = dev->out.mean_x = p.v[0] / S;
+        dev->mean_y = dev->out.mean_y = p.v[1] / S;
+        dev->out.theta_resultant = sqrt(p.v[2] * p.v[2] + p.v[3] * p.v[3]) / S;
+    } else {
+        dev->out.var_x = p.v[0] / S; dev->out.var_y = p.v[1] / S; dev->out.cov_xy = p.v[2] / S;
+    }
+}
+
+extern "C" int bl_pf_spread(bl_pf* pf, bl_pf_spread_t* out)
+{
+    BL_CHECK_ARG(pf != nullptr && out != nullptr);
+    if (!pf->initialized || pf->pending_end) { bl_set_error("filter not initialised or update pending"); return BL_ERR_STATE; }
+    if (pf->sh_world > 1) { bl_set_error("bl_pf_spread needs the whole record on this device (composed shard)"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(pf->ctx->device));
+    hipStream_t st = pf->ctx->stream;
+    if (!pf->sp_parts) BL_HIP(hipMalloc(&pf->sp_parts, SPREAD_MAX_BLOCKS * sizeof(spread_part)));
+    if (!pf->sp_out) BL_HIP(hipMalloc(&pf->sp_out, sizeof(spread_dev)));
+    const int nb = spread_blocks(pf->N);
+    spread_part* parts = (spread_part*)pf->sp_parts;
+    spread_dev* dev = (spread_dev*)pf->sp_out;
+    const float4* rec = pf->rec[pf->cur];
+    for (int pass = 0; pass < 2; ++pass) {
+        hipLaunchKernelGGL(k_pf_spread, dim3(nb), dim3(SPREAD_THREADS), 0, st, rec, pf->N, pass, parts, (const spread_dev*)dev);
+        hipLaunchKernelGGL(k_pf_spread_fin, dim3(1), dim3(SPREAD_THREADS), 0, st, (const spread_part*)parts, nb, pass, dev);
+    }
+    BL_HIP(hipGetLastError());
+    spread_dev h;
+    BL_HIP(hipMemcpyAsync(&h, dev, sizeof(h), hipMemcpyDeviceToHost, st));
+    BL_HIP(hipStreamSynchronize(st));
+    *out = h.out;
+    // S^2 / sum(u^2), each operand rounded once to double (the 128-bit square sum by the host's correctly rounded conversion)
+    const unsigned __int128 q = ((unsigned __int128)h.out.units_sq_hi << 64) | h.out.units_sq_lo;
+    out->n_eff = ((double)h.out.units_sum * (double)h.out.units_sum) / (double)q;
     return BL_OK;
 }

@@ -1880,6 +1880,16 @@ extern "C" int bl_dist_download(bl_dist* d, float* cells)
     return dist_check_broken(d);
 }
 
+// the transform as the global initialisation of a particle filter reads it (bl_mcl.hip): the float a caller sees at cell i is
+// l1[i] == 0xFFFF ? -1 : lut[l1[i]], exactly as k_dist_floats forms it
+int bl_dist_view(const bl_dist* d, const uint16_t** l1, const float** lut, int* width, int* height)
+{
+    if (!d || !d->valid) { bl_set_error("distance grid not set (bl_dist_set_distances first)"); return BL_ERR_ARG; }
+    *l1 = d->l1; *lut = d->lut;
+    *width = d->frame.width; *height = d->frame.height;
+    return BL_OK;
+}
+
 extern "C" int bl_dist_shape(const bl_dist* d, int* width, int* height)
 {
     BL_CHECK_ARG(d != nullptr);

@@ -224,6 +224,17 @@ class Mapping:
             self.h = None
 
 
+def spread_stds(s):
+    """(position std, heading std) of a spread: sqrt of the larger eigenvalue of [[var_x, cov_xy], [cov_xy, var_y]] and
+    sqrt(-2 ln R), as OccupancyGridSLAMT's convergence test (include/botlab/slam_driver.hpp) forms them."""
+    a, b, c = s["var_x"], s["cov_xy"], s["var_y"]
+    h = 0.5 * (a + c)
+    lam = h + math.sqrt(max(0.0, 0.25 * (a - c) * (a - c) + b * b))
+    r = s["theta_resultant"]
+    th = math.sqrt(-2.0 * math.log(r)) if r > 0.0 else math.inf
+    return math.sqrt(max(0.0, lam)), th
+
+
 class ParticleFilter:
     """ParticleFilter(numParticles) (particle_filter.hpp:38-77).  shard=(lo, hi) keeps only those particles' private
     state on this device (botlab_amd.sharded drives the exchange)."""
@@ -241,6 +252,25 @@ class ParticleFilter:
         if seed is None:                                                # reference: std::random_device
             seed = int.from_bytes(np.random.bytes(8), "little")
         check(self.ctx.lib.bl_pf_init_at_pose(self.h, C.byref(pose), C.c_uint64(seed)))
+
+    def initializeFilterUniformly(self, grid, distances=None, minDistance=0.0, utime=0, seed=None):
+        """Global localization: particles spread uniformly over the free cells of `grid` (log-odds < 0) and, with an
+        ObstacleDistanceGrid of the same shape, only where its distance is > minDistance (bl_pf_init_uniform)."""
+        if seed is None:
+            seed = int.from_bytes(np.random.bytes(8), "little")
+        check(self.ctx.lib.bl_pf_init_uniform(self.h, grid.h, distances.h if distances is not None else None,
+                                              np.float32(minDistance), int(utime), C.c_uint64(seed)))
+
+    def spread(self):
+        """Spread of the posterior (bl_pf_spread): dict of n_eff, mean_x, mean_y, var_x, var_y, cov_xy, theta_resultant,
+        units_sum and units_sq (exact integers), and the derived position_std (square root of the covariance's larger
+        eigenvalue, metres) and theta_std (circular standard deviation sqrt(-2 ln R), radians)."""
+        out = _capi.PfSpread()
+        check(self.ctx.lib.bl_pf_spread(self.h, C.byref(out)))
+        d = {f: getattr(out, f) for f, _ in _capi.PfSpread._fields_ if not f.startswith("units_sq")}
+        d["units_sq"] = (int(out.units_sq_hi) << 64) | int(out.units_sq_lo)
+        d["position_std"], d["theta_std"] = spread_stds(d)
+        return d
 
     def setParticles(self, particles, units=None):
         """particles: structured array (PARTICLE_DTYPE) of all N particles."""

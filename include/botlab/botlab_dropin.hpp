@@ -262,6 +262,31 @@ public:
         if (rnd) rnd.read(reinterpret_cast<char*>(&seed), sizeof(seed));
         check(bl_pf_init_at_pose(h_, &p, seed), "bl_pf_init_at_pose");
     }
+    // (extension) global localization: the particles spread uniformly over the free cells of `map` (log-odds < 0) and, when
+    // minDistToObstacle > 0, only where the obstacle distance exceeds it (botlab_hip.h, bl_pf_init_uniform); the particles' pose and
+    // parent utimes are `utime` (initializeFilterAtPose takes them from its pose)
+    void initializeFilterUniformly(const OccupancyGrid& map, float minDistToObstacle = 0.0f, int64_t utime = 0)
+    {
+        uint64_t seed = 0;                                                      // as initializeFilterAtPose: /dev/urandom
+        std::ifstream rnd("/dev/urandom", std::ios::binary);
+        if (rnd) rnd.read(reinterpret_cast<char*>(&seed), sizeof(seed));
+        bl_dist* dist = nullptr;
+        if (minDistToObstacle > 0.0f) {
+            check(bl_dist_create(default_ctx(), &dist), "bl_dist_create");
+            const int rc = bl_dist_set_distances(dist, map.device());
+            if (rc != BL_OK) { bl_dist_destroy(dist); check(rc, "bl_dist_set_distances"); }
+        }
+        const int rc = bl_pf_init_uniform(h_, map.device(), dist, minDistToObstacle, utime, seed);
+        if (dist) bl_dist_destroy(dist);
+        check(rc, "bl_pf_init_uniform");
+    }
+    // (extension) spread of the posterior: has a globally initialised filter converged? (botlab_hip.h, bl_pf_spread)
+    bl_pf_spread_t spread() const
+    {
+        bl_pf_spread_t s;
+        check(bl_pf_spread(h_, &s), "bl_pf_spread");
+        return s;
+    }
     Pose updateFilter(const Pose& odometry, const Lidar& laser, const OccupancyGrid& map)   // particle_filter.cpp:37-52
     {
         bl_lidar_t v = lidar_view(laser);

@@ -251,6 +251,7 @@ public:
         how_.awaitingFrame = waitForOptitrack;
         if (!mappingOnlyMode && !localizationOnlyMap.empty()) {
             how_.mapKnown = grid_.loadFromFile(localizationOnlyMap);
+            how_.mapFromFile = how_.mapKnown;
             how_.odometryOnly = actionOnlyMode;
         }
         const Pose origin = slam_detail::pose_of<Pose>(0, 0.0f, 0.0f, 0.0f);
@@ -293,6 +294,21 @@ public:
     // iteration are published after its map update has been enqueued instead of before.
     void setFusedStep(bool on) { fused_ = on; }
 
+    // (extension) Global localization: in localization-only mode (map from a file, not action-only) the filter is seeded uniformly
+    // over the map's free cells instead of around the start pose (the robot's place in the map is not known).  Until the cloud has
+    // converged every iteration takes the call-by-call updateFilter path, publishes SLAM_POSE / SLAM_PARTICLES as usual and leaves
+    // the map alone (a map extended from an unconverged pose would corrupt the known map).  Converged: the square root of the larger
+    // eigenvalue of the particles' weighted x / y covariance <= positionTolerance metres and the heading's circular standard
+    // deviation sqrt(-2 ln R) <= headingTolerance radians (ParticleFilterT::spread).  From the first converged iteration on the
+    // driver is the plain localization-only driver (fused step, map extended).  Off by default; set before the first iteration.
+    void setGlobalLocalization(bool on) { global_ = on; }
+    void setGlobalLocalizationThresholds(double positionTolerance, double headingTolerance)
+    {
+        globalPosTol_ = positionTolerance;
+        globalHeadingTol_ = headingTolerance;
+    }
+    bool globalLocalizationConverged() const { return globalConverged_; }
+
     // The oldest queued scan can be processed once the pose source covers the time of its first ray (slam.cpp:163-188).
     bool isReadyToUpdate() const
     {
@@ -312,6 +328,14 @@ public:
             std::cerr << "OccupancyGridSLAM: scan with only " << scan_.num_ranges << " ranges skipped\n";
             return;
         }
+        if (globalSearching()) {                        // global localization, not converged yet: filter only, the map is left alone
+            before_ = now_;
+            now_ = pf_.updateFilter(odomAtScan_, scan_, grid_);
+            announce();
+            globalConverged_ = spreadConverged();
+            if (globalConverged_) extendMap(false);    // the first converged iteration extends the map, as every later one does
+            return;
+        }
         const bool riding = localize();
         extendMap(riding);
     }
@@ -329,8 +353,8 @@ private:
     // What the four modes of slam.hpp:72-78 differ in:  mapping-only = posesGiven;  localization-only = mapKnown from a file;
     // action-only = that + odometryOnly;  full SLAM = none of them (mapKnown turns true with the first map update).
     struct How {
-        bool posesGiven, odometryOnly, mapKnown, awaitingFrame, started;
-        How() : posesGiven(false), odometryOnly(false), mapKnown(false), awaitingFrame(false), started(false) {}
+        bool posesGiven, odometryOnly, mapKnown, awaitingFrame, started, mapFromFile;
+        How() : posesGiven(false), odometryOnly(false), mapKnown(false), awaitingFrame(false), started(false), mapFromFile(false) {}
     };
 
     How how_;
@@ -345,6 +369,22 @@ private:
     Publisher out_;
     int dropped_ = 0, mapsMade_ = 0;
     bool fused_ = true;
+    // global localization: switch, convergence thresholds (defaults: 0.2 m, 0.3 rad -- more than twice the steady spread of a
+    // filter started at the true pose, 0.025 m / 0.10 rad, measured in tests/test_global_init_model_cpu.py), state
+    bool global_ = false, globalConverged_ = false;
+    double globalPosTol_ = 0.2, globalHeadingTol_ = 0.3;
+
+    bool globalSearching() const { return global_ && how_.mapFromFile && !how_.odometryOnly && !how_.posesGiven && !globalConverged_; }
+
+    // position std (largest principal axis) and heading circular std of the filter's cloud
+    bool spreadConverged() const
+    {
+        const bl_pf_spread_t s = pf_.spread();
+        const double h = 0.5 * (s.var_x + s.var_y);
+        const double pos = std::sqrt(h + std::sqrt(0.25 * (s.var_x - s.var_y) * (s.var_x - s.var_y) + s.cov_xy * s.cov_xy));
+        const double heading = s.theta_resultant > 0.0 ? std::sqrt(-2.0 * std::log(s.theta_resultant)) : HUGE_VAL;
+        return pos <= globalPosTol_ && heading <= globalHeadingTol_;
+    }
 
     const PoseTraceT<Pose>& poseSource() const { return how_.posesGiven ? truth_ : odom_; }
 
@@ -355,7 +395,8 @@ private:
         before_ = now_ = start_;
         before_.utime = scan_.times.front();
         now_.utime = scan_.times.back();
-        pf_.initializeFilterAtPose(before_);
+        if (globalSearching()) pf_.initializeFilterUniformly(grid_, 0.0f, before_.utime);
+        else pf_.initializeFilterAtPose(before_);
         how_.started = true;
     }
 

@@ -119,6 +119,7 @@ int bl_mapping_update_dev_pose(bl_mapping* m, const bl_lidar_t* scan, const void
  * Particles [shard_lo, shard_hi) of num_particles live on this device; the exchange record of all num_particles
  * (x, y, theta, weight-units: 16 bytes each) is replicated.  Single GPU: shard = [0, N). */
 typedef struct bl_pf bl_pf;
+typedef struct bl_dist bl_dist;           /* ObstacleDistanceGrid (below); bl_pf_init_uniform takes one */
 int bl_pf_create(bl_ctx* ctx, int num_particles, int shard_lo, int shard_hi, bl_pf** out);
 void bl_pf_destroy(bl_pf* pf);
 /* Optional, before init: use caller-allocated device buffers for the two exchange records (each at least
@@ -128,6 +129,27 @@ void* bl_pf_exchange_rec_ptr(bl_pf* pf);     /* the record written by the last u
 /* initializeFilterAtPose (particle_filter.cpp:16-34): N(pose, 0.01) per coordinate from a counter-based Philox stream
  * keyed by seed (reference: std::random_device), last particle = pose, weights 1/N. */
 int bl_pf_init_at_pose(bl_pf* pf, const bl_pose_xyt_t* pose, uint64_t seed);
+/* Global localization: the filter seeded uniformly over the free space of a known map (Monte-Carlo localization from no known
+ * start).  A cell is eligible when its log-odds is < 0 (frontiers.hpp:23-24) and, if `dist` is given (same shape as the map, already
+ * transformed), when the distance that grid shows for it is > min_dist (keeps the robot's centre off the walls).  Each particle takes
+ * an eligible cell uniformly, a uniform offset inside it and a uniform heading; parent pose = pose, equal weights, pose utimes = utime.
+ * The cloud depends on (seed, map, dist, min_dist, num_particles) only: Philox keyed by seed and the global particle index, with
+ * counter words of its own (exact formulas: bl_mcl.hip, k_pf_init_uniform).  poseEstimate() becomes estimatePosteriorPose of the
+ * new cloud (a composed shard: the last particle's pose).  No eligible cell, or a `dist` of another shape: BL_ERR_ARG and the filter
+ * is left as it was. */
+int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* dist /* NULL: log-odds only */, float min_dist, int64_t utime,
+                       uint64_t seed);
+/* Spread of the posterior (is a filter started by bl_pf_init_uniform converged?), one reduction of fixed order over the current record
+ * (u = a particle's weight units, S = sum of u, weights u / S):
+ *   units_sum = S; units_sq_hi:units_sq_lo = sum of u^2 as a 128-bit integer; n_eff = (double)S * (double)S / (double)(sum of u^2)
+ *   mean_x, mean_y: weighted means;  var_x, var_y, cov_xy: weighted (population) second moments about them;
+ *   theta_resultant: mean resultant length R of the heading, |sum of u (cos theta, sin theta)| / S in double (circular std sqrt(-2 ln R)).
+ * BL_ERR_STATE while an update is pending and on a composed shard (bl_pf_estimate_posterior_pose's rule).  Synchronises. */
+typedef struct bl_pf_spread_t {
+    double n_eff, mean_x, mean_y, var_x, var_y, cov_xy, theta_resultant;
+    uint64_t units_sum, units_sq_lo, units_sq_hi;
+} bl_pf_spread_t;                         /* 80 bytes */
+int bl_pf_spread(bl_pf* pf, bl_pf_spread_t* out);
 /* Replace the whole posterior from a host AoS array of num_particles records (weights must be uniform or the
  * weight-unit integers in `units` given; units == NULL -> uniform). */
 int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, const uint32_t* units);
@@ -198,7 +220,6 @@ int bl_debug_trig_addition_probe(bl_ctx* ctx, uint64_t pairs, uint32_t seed, flo
 int bl_pf_debug_last(bl_pf* pf, int32_t* resample_idx, int32_t* likelihood_half_units);
 
 /* ------------------------------------------------------------------ ObstacleDistanceGrid  (src/planning/obstacle_distance_grid.hpp:28-96) */
-typedef struct bl_dist bl_dist;
 int bl_dist_create(bl_ctx* ctx, bl_dist** out);
 void bl_dist_destroy(bl_dist* d);
 /* setDistances(map), obstacle_distance_grid.cpp:73-91.  When `map` is a later state of the very map `d` last transformed --
