@@ -40,7 +40,21 @@ class PfSpread(C.Structure):
                 ("units_sq_hi", C.c_uint64)]
 
 
+class PfRecoveryParams(C.Structure):
+    """bl_pf_recovery_params_t: kidnapped-robot recovery (48 bytes)."""
+    _fields_ = [("alpha_slow", C.c_double), ("alpha_fast", C.c_double), ("ratio", C.c_double), ("max_fraction", C.c_double),
+                ("min_dist", C.c_float), ("seed", C.c_uint64)]
+
+
+class PfRecoveryState(C.Structure):
+    """bl_pf_recovery_state_t: the recovery tracker (56 bytes)."""
+    _fields_ = [("w_slow", C.c_double), ("w_fast", C.c_double), ("w_avg", C.c_double), ("p_inject", C.c_double),
+                ("updates", C.c_uint32), ("primed", C.c_uint32), ("injected_last", C.c_uint32), ("pad", C.c_uint32),
+                ("injected_total", C.c_uint64)]
+
+
 assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56 and C.sizeof(PfSpread) == 80
+assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
 
 class MotionPlannerState(C.Structure):
     """bl_motion_planner_t: the MotionPlanner members plan_path_to_frontier reads (motion_planner.hpp:153-165)."""
@@ -93,6 +107,8 @@ SIGNATURES = {
     "bl_pf_init_at_pose": (C.c_int, [_vp, _P(Pose), C.c_uint64]),
     "bl_pf_init_uniform": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_int64, C.c_uint64]),
     "bl_pf_spread": (C.c_int, [_vp, _P(PfSpread)]),
+    "bl_pf_set_recovery": (C.c_int, [_vp, _vp, _vp, _P(PfRecoveryParams)]),
+    "bl_pf_recovery_state": (C.c_int, [_vp, _P(PfRecoveryState)]),
     "bl_pf_set_particles": (C.c_int, [_vp, _vp, _vp]),
     "bl_pf_get_particles": (C.c_int, [_vp, _vp]),
     "bl_pf_set_noise_seed": (C.c_int, [_vp, C.c_uint64]),

@@ -119,6 +119,13 @@ struct bl_pf {
     uint32_t* gl_list; size_t gl_list_cap;     // eligible cell indices, row-major order
     void* sp_parts;                            // [SPREAD_MAX_BLOCKS] spread_part
     void* sp_out;                              // spread_dev
+    // kidnapped-robot recovery (bl_pf_set_recovery): parameters, the eligible list of its own, the update counter u, the device
+    // side; sensed: rec[cur] carries sensor-model weights (the fold's condition)
+    bool rc_on, sensed;
+    bl_pf_recovery_params_t rc_p;
+    uint32_t* rc_list; size_t rc_list_cap;
+    uint32_t rc_u;
+    struct pf_recovery_dev* rc_dev;            // list, frame and key, and the tracker
 };
 
 // ---------------------------------------------------------------- device helpers
@@ -546,8 +553,39 @@ struct mcl_args {
     // this process sees that rank's arrays (its own, or another rank's through an IPC mapping), indexed by the global i.  A table
     // in device memory: indexing a table inside this by-value argument per lane would move the argument into scratch.
     const struct mcl_shard_tab* sh;
+    struct pf_recovery_dev* rc;   // kidnapped-robot recovery (read by the REC instantiations only)
 };
 struct mcl_shard_tab { int world, block; const float4* src[BL_MAX_SHARDS]; const unsigned long long* prefix[BL_MAX_SHARDS]; };
+
+// Recovery on the device.  bl_pf_set_recovery writes the list, its frame and the key and zeroes the tracker; k_pf_recovery_fold writes
+// the tracker at the start of every moved update in recovery mode (updates = that update's u); k_mcl_main reads u, t, the list and
+// the key and counts its injections.  injected_last = injected_total - total_at_fold.
+struct pf_recovery_dev {
+    double w_slow, w_fast, w_avg, p;
+    uint32_t updates, primed;
+    unsigned long long t;                     // injection threshold on the decision word: floor(p * 2^32), 2^32 for p >= 1
+    unsigned long long total_at_fold;
+    unsigned long long injected_total;
+    const uint32_t* list;                     // the eligible cells, row-major; F of them in a grid W cells wide
+    uint32_t F, W, k0, k1;                    // k0, k1: the recovery seed
+    double ox, oy, mpc;                       // the grid's frame
+};
+#define RC_CTR 0x72637679u                    // Philox counter word of the recovery: (m, u, RC_CTR, 0 / 1) sample, (m, u, RC_CTR, 2) decision
+
+// The pose of bl_pf_init_uniform's sample from Philox words a[0..3], b0 over an eligible list of F cells of a grid W cells wide
+// (formulas: k_pf_init_uniform); weight units 1
+__device__ __forceinline__ float4 gl_pose(const uint32_t a[4], uint32_t b0, const uint32_t* list, uint32_t F, uint32_t W,
+                                          double ox, double oy, double mpc)
+{
+    const uint32_t r = (uint32_t)__umul64hi(((unsigned long long)a[0] << 32) | a[1], (unsigned long long)F);
+    const uint32_t cell = list[r];
+    const uint32_t cx = cell % W, cy = cell / W;
+    const double fx = (double)(a[2] >> 8) * 0x1p-24, fy = (double)(a[3] >> 8) * 0x1p-24, ft = (double)(b0 >> 8) * 0x1p-24;
+    const float x = (float)(ox + ((double)cx + fx) * mpc);
+    const float y = (float)(oy + ((double)cy + fy) * mpc);
+    const float th = bl_wrap_to_pi((float)((2.0 * ft - 1.0) * BL_PI));
+    return make_float4(x, y, th, __uint_as_float(1u));
+}
 
 __device__ __forceinline__ float4 mcl_src_at(const mcl_args& a, int i)
 {
@@ -785,7 +823,9 @@ extern "C" int bl_debug_mcl_stamps(unsigned long long* out, int n)
 #define MCL_STAMP_HW() do { } while (0)
 #endif
 
-template <int INTERP, int BLOCK, int MAP_MODE>
+// REC: kidnapped-robot recovery -- some resampled particles are replaced by uniform samples over the recovery list (bl_pf_set_recovery).
+// A template parameter so that the default instantiations compile exactly as without it.
+template <int INTERP, int BLOCK, int MAP_MODE, bool REC = false>
 __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
 {
     extern __shared__ __align__(16) signed char s_dyn[];
@@ -940,6 +980,7 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
     float2 pcs_own = make_float2(2.0f, 0.0f);               // (2, -): "take the hardware sine / cosine" (a.fast_trig == 2)
     float pth_sin = 0.0f, pth_cos = 1.0f;
     int i = mp;
+    bool injected = false;                                  // (REC) this particle's prior is a uniform sample
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     float px = 0.f, py = 0.f, pth = 0.f, sx0 = 0.f, sy0 = 0.f;
     // ---- resamplePosteriorDistribution (particle_filter.cpp:84-103): first index with T <= prefix[i], clamped to N-1
@@ -963,6 +1004,22 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
         if (a.resample && uni_n > 0) i = uni_search(a.state, uni_n, rs_T, a.N);
         else if (a.resample) i = a.sh ? resample_bisect(pview, rs_T, rs_lo, rs_hi, a.strict != 0) : resample_bisect(a.prefix, rs_T, rs_lo, rs_hi, a.strict != 0);
         MCL_STAMP(6);
+        if (REC) {
+            // augmented MCL: particle mp is injected iff word 0 of Philox((mp, u, RC_CTR, 2), seed) < t; its prior is the uniform sample
+            // of counters (mp, u, RC_CTR, 0 / 1) over the recovery list (bl_pf_init_uniform's formula)
+            const pf_recovery_dev& rc = *a.rc;
+            uint32_t d[4];
+            bl_philox4x32((uint32_t)mp, rc.updates, RC_CTR, 2u, rc.k0, rc.k1, d);
+            injected = (unsigned long long)d[0] < rc.t;
+            if (injected) {
+                uint32_t w0[4], w1[4];
+                bl_philox4x32((uint32_t)mp, rc.updates, RC_CTR, 0u, rc.k0, rc.k1, w0);
+                bl_philox4x32((uint32_t)mp, rc.updates, RC_CTR, 1u, rc.k0, rc.k1, w1);
+                s = gl_pose(w0, w1[0], rc.list, rc.F, rc.W, rc.ox, rc.oy, rc.mpc);
+                i = -1;
+            }
+        }
+        if (!injected)
         s = mcl_src_at(a, i);
         // ---- ActionModel::applyAction (action_model.cpp:78-103)
         float n1, n2, n3;
@@ -984,6 +1041,11 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
         if (a.cells) bl_global_to_grid(px, py, a.frame, &sx0, &sy0);
         bl_sincosf(pth, &pth_sin, &pth_cos);                 // (the estimate's partial sums need them anyway: particle_filter.cpp:151-152)
         if (a.cells && a.fast_trig == 1) pcs_own = make_float2(a.frame.cpm * pth_cos, a.frame.cpm * pth_sin);    // ("pcs scaled", ray_cells_fast)
+    }
+    if (REC) {
+        // the injections of this wave, one atomic: each particle once (without the shared prologue every lane of its group ran it)
+        const unsigned long long b = __builtin_amdgcn_ballot_w64(injected && (shared_pro || sub == 0));
+        if (b != 0 && lane == 0) atomicAdd(&a.rc->injected_total, (unsigned long long)__popcll(b));
     }
     // guard-band offset of the fast trig path for this particle: 2.04 u times a bound on its cell coordinates (ray_cells_fast)
     // (the part of the band that does not grow with the range: 2.04 u times the particle's own cell coordinates; what a ray adds to
@@ -1621,7 +1683,7 @@ extern "C" void bl_pf_destroy(bl_pf* pf)
     if (!pf->rec_external) { if (pf->rec[0]) (void)hipFree(pf->rec[0]); if (pf->rec[1]) (void)hipFree(pf->rec[1]); }
     void* ptrs[] = {pf->fin_wild, pf->tile_partials, pf->fin_recs, pf->fin_tabs, pf->fin_sync, pf->prefix, pf->parent, pf->state, pf->partials, pf->block_sums, pf->dbg_idx, pf->dbg_like,
                     pf->d_noise, pf->d_export, pf->sh_xchg, pf->sh_tab, pf->sh_fin, pf->sh_flags, pf->sh_peers_dev, pf->strict_recs, pf->strict_starts,
-                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out};
+                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out, pf->rc_list, pf->rc_dev};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete pf;
 }
@@ -1760,6 +1822,7 @@ extern "C" int bl_pf_init_at_pose(bl_pf* pf, const bl_pose_xyt_t* pose, uint64_t
     pf->pose_utime = pose->utime; pf->parent_utime = pose->utime;
     pf->initialized = true;
     pf->uniform_now = true;                      // weights 1 / N (particle_filter.cpp:25)
+    pf->sensed = false;                          // (placeholder units: the recovery tracker does not fold them)
     // the reference does not reset its ActionModel here; a filter is initialised once (slam.cpp:232-250)
     return pf_scan(pf, 0, 0, 0);
 }
@@ -1771,6 +1834,7 @@ extern "C" int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, co
     if (!pf->prefix) { int rc = pf_alloc(pf); if (rc) return rc; }
     std::vector<float4> rec(pf->N), par(pf->n_local);
     pf->uniform_now = true;
+    pf->sensed = false;
     for (int m = 0; m < pf->N; ++m) {
         uint32_t u = units ? units[m] : 1u;
         if (units && units[m] != units[0]) pf->uniform_now = false;
@@ -1874,6 +1938,36 @@ static int pf_upload_noise(bl_pf* pf, const float* noise)
                           hipMemcpyHostToDevice, pf->ctx->stream));
     BL_HIP(hipStreamSynchronize(pf->ctx->stream));          // caller-owned pageable buffer
     return BL_OK;
+}
+
+// The recovery tracker's step at the start of moved update u (bl_pf_set_recovery, botlab_hip.h): fold the posterior about to be
+// resampled (fold != 0: a sensor update produced it), then the injected fraction p and the threshold t.  One lane, plain IEEE double
+// without contraction (a numpy model reproduces every bit); the stores are ordinary global stores of that lane.
+__global__ __launch_bounds__(64) void k_pf_recovery_fold(const pf_state* __restrict__ state, pf_recovery_dev* __restrict__ d, int fold, uint32_t u,
+                                                         int N, double alpha_slow, double alpha_fast, double ratio, double max_fraction)
+{
+#pragma clang fp contract(off)
+    if (threadIdx.x != 0) return;
+    pf_recovery_dev v = *d;
+    if (fold) {
+        const double w_avg = (state->S * 0.0005) / (double)N;       // the mean of the reference's raw weights max(likelihood, 0.001)
+        v.w_avg = w_avg;
+        if (!v.primed) { v.w_slow = w_avg; v.w_fast = w_avg; v.primed = 1; }
+        else {
+            v.w_slow = v.w_slow + alpha_slow * (w_avg - v.w_slow);
+            v.w_fast = v.w_fast + alpha_fast * (w_avg - v.w_fast);
+        }
+    }
+    double p = 0.0;
+    if (v.primed && v.w_fast < ratio * v.w_slow) {
+        p = 1.0 - v.w_fast / (ratio * v.w_slow);
+        if (max_fraction < p) p = max_fraction;
+    }
+    v.p = p;
+    v.t = p >= 1.0 ? (1ull << 32) : (unsigned long long)floor(p * 4294967296.0);
+    v.updates = u;
+    v.total_at_fold = v.injected_total;
+    *d = v;
 }
 
 static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, const float* noise, int resample)
@@ -2029,14 +2123,26 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     pf->sh_stage_sums = pf->sh_stage_groups = false;
     int blocks = (int)(main_blocks + tail_blocks);
     if (blocks > pf->partials_cap) { bl_set_error("internal: partials buffer too small"); return BL_ERR_STATE; }
+    // kidnapped-robot recovery: a moved, sensor-weighted update of a whole set -- the tracker folds the posterior about to be resampled
+    // (one wave, in front of k_mcl_main), then the REC instantiation injects
+    const bool rec_mode = pf->rc_on && map != nullptr && resample != 0 && pf->sh_world <= 1 && pf->n_local == pf->N;
+    a.rc = nullptr;
+    if (rec_mode) {
+        const bl_pf_recovery_params_t& q = pf->rc_p;
+        pf->rc_u += 1;
+        hipLaunchKernelGGL(k_pf_recovery_fold, dim3(1), dim3(64), 0, ctx->stream, (const pf_state*)pf->state, pf->rc_dev, pf->sensed ? 1 : 0,
+                           pf->rc_u, pf->N, q.alpha_slow, q.alpha_fast, q.ratio, q.max_fraction);
+        a.rc = pf->rc_dev;
+    }
     hipEvent_t e0, e1;
     int rc = bl_timer_pair(ctx, BL_K_MCL_MAIN, &e0, &e1);     // a timed launch carries its own start/stop events
     if (rc) return rc;
-#define MCL_LAUNCH(B, M)                                                                                          \
+#define MCL_LAUNCH_REC(B, M, REC)                                                                                 \
     do {                                                                                                          \
-        if (a.interp) hipExtLaunchKernelGGL((k_mcl_main<1, B, (M) == 2 ? 0 : (M)>), dim3(blocks), dim3(B), lds_bytes, ctx->stream, e0, e1, 0, a); \
-        else hipExtLaunchKernelGGL((k_mcl_main<0, B, M>), dim3(blocks), dim3(B), lds_bytes, ctx->stream, e0, e1, 0, a);          \
+        if (a.interp) hipExtLaunchKernelGGL((k_mcl_main<1, B, (M) == 2 ? 0 : (M), REC>), dim3(blocks), dim3(B), lds_bytes, ctx->stream, e0, e1, 0, a); \
+        else hipExtLaunchKernelGGL((k_mcl_main<0, B, M, REC>), dim3(blocks), dim3(B), lds_bytes, ctx->stream, e0, e1, 0, a);          \
     } while (0)
+#define MCL_LAUNCH(B, M) do { if (rec_mode) MCL_LAUNCH_REC(B, M, true); else MCL_LAUNCH_REC(B, M, false); } while (0)
 #define MCL_LAUNCH_MODE(B)                                    \
     do {                                                      \
         if (mode == 0) MCL_LAUNCH(B, 0);                      \
@@ -2048,6 +2154,7 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     else MCL_LAUNCH_MODE(1024);
 #undef MCL_LAUNCH_MODE
 #undef MCL_LAUNCH
+#undef MCL_LAUNCH_REC
     BL_HIP(hipGetLastError());
     rc = bl_timer_commit(ctx, BL_K_MCL_MAIN, e0, e1);
     if (rc) return rc;
@@ -2112,6 +2219,10 @@ extern "C" int bl_pf_update_begin(bl_pf* pf, const bl_pose_xyt_t* odometry, cons
     rc = pf_launch_main(pf, map, R, rand_value, noise, 1);
     if (rc) return rc;
     pf->uniform_now = false;                     // the record this update writes carries the sensor model's weights
+    // ... which the recovery tracker folds -- unless this update interpolated its scan (particles with a nonzero pose utime: the first
+    // update after an initialisation or upload with utime != 0; pf_launch_main's a.interp): its scan is interpolated towards utime 0
+    // (D3) and its weights are an order of magnitude below the steady ones
+    pf->sensed = pf->pose_utime == 0;
     pf->pending_end = true;
     return BL_OK;
 }
@@ -3086,16 +3197,10 @@ __global__ void k_pf_init_uniform(float4* rec, float4* parent, int N, int lo, in
     uint32_t a[4], b[4];
     bl_philox4x32((uint32_t)m, GL_CTR1, GL_CTR2, 0u, k0, k1, a);
     bl_philox4x32((uint32_t)m, GL_CTR1, GL_CTR2, 1u, k0, k1, b);
-    const uint32_t r = (uint32_t)__umul64hi(((unsigned long long)a[0] << 32) | a[1], (unsigned long long)F);
-    const uint32_t cell = list[r];
-    const uint32_t cx = cell % W, cy = cell / W;
-    const double fx = (double)(a[2] >> 8) * 0x1p-24, fy = (double)(a[3] >> 8) * 0x1p-24, ft = (double)(b[0] >> 8) * 0x1p-24;
-    const float x = (float)(ox + ((double)cx + fx) * mpc);
-    const float y = (float)(oy + ((double)cy + fy) * mpc);
-    const float th = bl_wrap_to_pi((float)((2.0 * ft - 1.0) * BL_PI));
-    rec[m] = make_float4(x, y, th, __uint_as_float(1u));
+    const float4 v = gl_pose(a, b[0], list, F, W, ox, oy, mpc);
+    rec[m] = v;
     const int j = m - lo;
-    if (j >= 0 && j < n_local) parent[j] = make_float4(x, y, th, 0.0f);
+    if (j >= 0 && j < n_local) parent[j] = make_float4(v.x, v.y, v.z, 0.0f);
 }
 
 // a composed shard cannot run the record-based finish alone: the last particle's pose stands in (as after bl_pf_set_particles)
@@ -3105,12 +3210,11 @@ __global__ void k_pf_pose_from_rec(pf_state* state, const float4* rec, int m, in
     state->pose.utime = utime; state->pose.x = r.x; state->pose.y = r.y; state->pose.theta = r.z;
 }
 
-extern "C" int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* dist, float min_dist, int64_t utime, uint64_t seed)
+// The eligible cells of `map` (row-major) into *list, grown to fit; *F_out = their count.  BL_ERR_ARG for a `dist` of another shape
+// or no eligible cell -- *list is then untouched.  Leaves the list's launches enqueued on the ctx's stream.
+static int gl_build_list(bl_pf* pf, const bl_grid* map, const bl_dist* dist, float min_dist, uint32_t** list, size_t* cap, uint32_t* F_out)
 {
-    BL_CHECK_ARG(pf != nullptr && map != nullptr);
     const int W = map->frame.width, H = map->frame.height;
-    BL_CHECK_ARG(W > 0 && H > 0 && (int64_t)W * H < ((int64_t)1 << 31));
-    if (pf->pending_end) { bl_set_error("update pending"); return BL_ERR_STATE; }
     gl_src s;
     s.cells = map->cells; s.l1 = nullptr; s.lut = nullptr; s.min_dist = min_dist; s.n = (uint32_t)((int64_t)W * H);
     if (dist) {
@@ -3137,12 +3241,27 @@ extern "C" int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* 
     BL_HIP(hipMemcpyAsync(&F, offs + tiles, sizeof(F), hipMemcpyDeviceToHost, st));
     BL_HIP(hipStreamSynchronize(st));
     if (F == 0) { bl_set_error("no eligible cell: the map has no cell with log-odds < 0%s", dist ? " and distance > min_dist" : ""); return BL_ERR_ARG; }
-    if (pf->gl_list_cap < F) {
-        if (pf->gl_list) { BL_HIP(hipFree(pf->gl_list)); pf->gl_list = nullptr; pf->gl_list_cap = 0; }
-        BL_HIP(hipMalloc((void**)&pf->gl_list, (size_t)F * sizeof(uint32_t)));
-        pf->gl_list_cap = F;
+    if (*cap < F) {
+        if (*list) { BL_HIP(hipFree(*list)); *list = nullptr; *cap = 0; }
+        BL_HIP(hipMalloc((void**)list, (size_t)F * sizeof(uint32_t)));
+        *cap = F;
     }
-    hipLaunchKernelGGL(k_gl_compact, dim3(tiles), dim3(GL_THREADS), 0, st, s, (const uint32_t*)offs, pf->gl_list);
+    hipLaunchKernelGGL(k_gl_compact, dim3(tiles), dim3(GL_THREADS), 0, st, s, (const uint32_t*)offs, *list);
+    BL_HIP(hipGetLastError());
+    *F_out = F;
+    return BL_OK;
+}
+
+extern "C" int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* dist, float min_dist, int64_t utime, uint64_t seed)
+{
+    BL_CHECK_ARG(pf != nullptr && map != nullptr);
+    const int W = map->frame.width, H = map->frame.height;
+    BL_CHECK_ARG(W > 0 && H > 0 && (int64_t)W * H < ((int64_t)1 << 31));
+    if (pf->pending_end) { bl_set_error("update pending"); return BL_ERR_STATE; }
+    uint32_t F = 0;
+    int rc0 = gl_build_list(pf, map, dist, min_dist, &pf->gl_list, &pf->gl_list_cap, &F);
+    if (rc0) return rc0;
+    hipStream_t st = pf->ctx->stream;
     pf->cur = 0;
     if (pf->sh_broken) { pf->sh_broken = false; BL_HIP(hipMemsetAsync(&pf->state->shard_broken, 0, sizeof(unsigned int), st)); }
     hipLaunchKernelGGL(k_pf_init_uniform, dim3((pf->N + 255) / 256), dim3(256), 0, st, pf->rec[0], pf->parent, pf->N, pf->lo, pf->n_local,
@@ -3152,6 +3271,7 @@ extern "C" int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* 
     pf->pose_utime = utime; pf->parent_utime = utime;
     pf->initialized = true;
     pf->uniform_now = true;                      // weights 1 / N
+    pf->sensed = false;
     // poseEstimate() = estimatePosteriorPose of the new cloud (it also centres the next update's LDS map window); then the plain
     // prefix scan bl_pf_init_at_pose ends with, which knows the weights are equal
     if (pf->sh_world > 1) hipLaunchKernelGGL(k_pf_pose_from_rec, dim3(1), dim3(1), 0, st, pf->state, (const float4*)pf->rec[0], pf->N - 1, utime);
@@ -3271,5 +3391,67 @@ extern "C" int bl_pf_spread(bl_pf* pf, bl_pf_spread_t* out)
     // S^2 / sum(u^2), each operand rounded once to double (the 128-bit square sum by the host's correctly rounded conversion)
     const unsigned __int128 q = ((unsigned __int128)h.out.units_sq_hi << 64) | h.out.units_sq_lo;
     out->n_eff = ((double)h.out.units_sum * (double)h.out.units_sum) / (double)q;
+    return BL_OK;
+}
+
+// ---------------------------------------------------------------- kidnapped-robot recovery (augmented MCL)
+// bl_pf_set_recovery: the eligible list (bl_pf_init_uniform's three list kernels, into the recovery's own buffer) and a zeroed tracker.
+// From then on every moved, sensor-weighted update launches k_pf_recovery_fold (one wave) in front of k_mcl_main's REC instantiation
+// (pf_launch_main); the formulas are in botlab_hip.h.
+extern "C" int bl_pf_set_recovery(bl_pf* pf, const bl_grid* map, const bl_dist* dist, const bl_pf_recovery_params_t* params)
+{
+    BL_CHECK_ARG(pf != nullptr);
+    if (params) {
+        const bl_pf_recovery_params_t& q = *params;
+        BL_CHECK_ARG(map != nullptr);
+        const int W = map->frame.width, H = map->frame.height;
+        BL_CHECK_ARG(W > 0 && H > 0 && (int64_t)W * H < ((int64_t)1 << 31));
+        if (!(q.alpha_slow > 0.0 && q.alpha_slow < q.alpha_fast && q.alpha_fast <= 1.0) || !(q.ratio > 0.0 && q.ratio < HUGE_VAL) ||
+            !(q.max_fraction >= 0.0 && q.max_fraction <= 1.0)) {
+            bl_set_error("recovery parameters: need 0 < alpha_slow < alpha_fast <= 1, 0 < ratio < inf, 0 <= max_fraction <= 1");
+            return BL_ERR_ARG;
+        }
+    }
+    if (pf->pending_end) { bl_set_error("update pending"); return BL_ERR_STATE; }
+    if (pf->sh_world > 1 || pf->n_local < pf->N) { bl_set_error("recovery needs the whole particle set on this device (composed shard or partial slice)"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(pf->ctx->device));
+    hipStream_t st = pf->ctx->stream;
+    if (!params) {
+        pf->rc_on = false;
+        if (pf->rc_list) { BL_HIP(hipStreamSynchronize(st)); BL_HIP(hipFree(pf->rc_list)); pf->rc_list = nullptr; pf->rc_list_cap = 0; }
+        return BL_OK;
+    }
+    if (!pf->rc_dev) BL_HIP(hipMalloc((void**)&pf->rc_dev, sizeof(pf_recovery_dev)));
+    if (pf->rc_list) BL_HIP(hipStreamSynchronize(st));           // the last update may still read the old list
+    uint32_t F = 0;
+    int rc = gl_build_list(pf, map, dist, params->min_dist, &pf->rc_list, &pf->rc_list_cap, &F);
+    if (rc) return rc;
+    pf_recovery_dev h;
+    memset(&h, 0, sizeof(h));
+    h.list = pf->rc_list; h.F = F; h.W = (uint32_t)map->frame.width;
+    h.k0 = (uint32_t)params->seed; h.k1 = (uint32_t)(params->seed >> 32);
+    h.ox = (double)map->frame.ox; h.oy = (double)map->frame.oy; h.mpc = (double)map->frame.mpc;
+    BL_HIP(hipMemcpyAsync(pf->rc_dev, &h, sizeof(h), hipMemcpyHostToDevice, st));
+    BL_HIP(hipStreamSynchronize(st));            // (h is a stack copy)
+    pf->rc_p = *params;
+    pf->rc_u = 0;
+    pf->rc_on = true;
+    return BL_OK;
+}
+
+extern "C" int bl_pf_recovery_state(bl_pf* pf, bl_pf_recovery_state_t* out)
+{
+    BL_CHECK_ARG(pf != nullptr && out != nullptr);
+    if (pf->pending_end) { bl_set_error("update pending"); return BL_ERR_STATE; }
+    memset(out, 0, sizeof(*out));
+    if (!pf->rc_on) return BL_OK;
+    BL_HIP(hipSetDevice(pf->ctx->device));
+    pf_recovery_dev h;
+    BL_HIP(hipMemcpyAsync(&h, pf->rc_dev, sizeof(h), hipMemcpyDeviceToHost, pf->ctx->stream));
+    BL_HIP(hipStreamSynchronize(pf->ctx->stream));
+    out->w_slow = h.w_slow; out->w_fast = h.w_fast; out->w_avg = h.w_avg; out->p_inject = h.p;
+    out->updates = h.updates; out->primed = h.primed;
+    out->injected_last = (uint32_t)(h.injected_total - h.total_at_fold);
+    out->injected_total = h.injected_total;
     return BL_OK;
 }

@@ -235,6 +235,12 @@ def spread_stds(s):
     return math.sqrt(max(0.0, lam)), th
 
 
+# kidnapped-robot recovery defaults (ParticleFilter.setRecovery): AMCL's averaging rates; ratio and max_fraction calibrated on the
+# CPU reference filter (tests/test_recovery_model_cpu.py)
+RECOVERY_ALPHA_SLOW, RECOVERY_ALPHA_FAST = 0.001, 0.1
+RECOVERY_RATIO, RECOVERY_MAX_FRACTION = 0.9, 0.1
+
+
 class ParticleFilter:
     """ParticleFilter(numParticles) (particle_filter.hpp:38-77).  shard=(lo, hi) keeps only those particles' private
     state on this device (botlab_amd.sharded drives the exchange)."""
@@ -271,6 +277,28 @@ class ParticleFilter:
         d["units_sq"] = (int(out.units_sq_hi) << 64) | int(out.units_sq_lo)
         d["position_std"], d["theta_std"] = spread_stds(d)
         return d
+
+    def setRecovery(self, grid, distances=None, minDistance=0.0, alphaSlow=RECOVERY_ALPHA_SLOW, alphaFast=RECOVERY_ALPHA_FAST,
+                    ratio=RECOVERY_RATIO, maxFraction=RECOVERY_MAX_FRACTION, seed=None):
+        """Kidnapped-robot recovery (augmented MCL, bl_pf_set_recovery): while the fast average of the mean particle weight falls below
+        ratio times the slow one, up to maxFraction of the resampled particles are replaced by poses drawn uniformly over the free
+        cells of `grid` as it stands now (log-odds < 0 and, with an ObstacleDistanceGrid, distance > minDistance).  grid=None turns
+        recovery off."""
+        if grid is None:
+            check(self.ctx.lib.bl_pf_set_recovery(self.h, None, None, None))
+            return
+        if seed is None:
+            seed = int.from_bytes(np.random.bytes(8), "little")
+        p = _capi.PfRecoveryParams(float(alphaSlow), float(alphaFast), float(ratio), float(maxFraction), float(np.float32(minDistance)),
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF)
+        check(self.ctx.lib.bl_pf_set_recovery(self.h, grid.h, distances.h if distances is not None else None, C.byref(p)))
+
+    def recoveryState(self):
+        """The recovery tracker (bl_pf_recovery_state): dict of w_slow, w_fast, w_avg, p_inject, updates, primed, injected_last,
+        injected_total (all zero while recovery is off)."""
+        out = _capi.PfRecoveryState()
+        check(self.ctx.lib.bl_pf_recovery_state(self.h, C.byref(out)))
+        return {f: getattr(out, f) for f, _ in _capi.PfRecoveryState._fields_ if f != "pad"}
 
     def setParticles(self, particles, units=None):
         """particles: structured array (PARTICLE_DTYPE) of all N particles."""

@@ -280,6 +280,40 @@ public:
         if (dist) bl_dist_destroy(dist);
         check(rc, "bl_pf_init_uniform");
     }
+    // (extension) kidnapped-robot recovery, augmented MCL (botlab_hip.h, bl_pf_set_recovery): while the fast average of the mean
+    // particle weight falls below params.ratio times the slow one, a fraction of the resampled particles is replaced by poses drawn
+    // uniformly over the free cells of `map` as it stands now (distance > params.min_dist when that is > 0)
+    static bl_pf_recovery_params_t defaultRecoveryParams()
+    {
+        bl_pf_recovery_params_t q;
+        q.alpha_slow = 0.001; q.alpha_fast = 0.1;                               // AMCL's
+        q.ratio = 0.9; q.max_fraction = 0.1;                                    // calibrated
+        q.min_dist = 0.0f;
+        q.seed = 0;
+        std::ifstream rnd("/dev/urandom", std::ios::binary);
+        if (rnd) rnd.read(reinterpret_cast<char*>(&q.seed), sizeof(q.seed));
+        return q;
+    }
+    void enableRecovery(const OccupancyGrid& map, const bl_pf_recovery_params_t& params)
+    {
+        bl_dist* dist = nullptr;
+        if (params.min_dist > 0.0f) {
+            check(bl_dist_create(default_ctx(), &dist), "bl_dist_create");
+            const int rc = bl_dist_set_distances(dist, map.device());
+            if (rc != BL_OK) { bl_dist_destroy(dist); check(rc, "bl_dist_set_distances"); }
+        }
+        const int rc = bl_pf_set_recovery(h_, map.device(), dist, &params);
+        if (dist) bl_dist_destroy(dist);
+        check(rc, "bl_pf_set_recovery");
+    }
+    void enableRecovery(const OccupancyGrid& map) { enableRecovery(map, defaultRecoveryParams()); }
+    void disableRecovery() { check(bl_pf_set_recovery(h_, nullptr, nullptr, nullptr), "bl_pf_set_recovery"); }
+    bl_pf_recovery_state_t recoveryState() const
+    {
+        bl_pf_recovery_state_t s;
+        check(bl_pf_recovery_state(h_, &s), "bl_pf_recovery_state");
+        return s;
+    }
     // (extension) spread of the posterior: has a globally initialised filter converged? (botlab_hip.h, bl_pf_spread)
     bl_pf_spread_t spread() const
     {

@@ -308,6 +308,16 @@ public:
         globalHeadingTol_ = headingTolerance;
     }
     bool globalLocalizationConverged() const { return globalConverged_; }
+    // (extension) Kidnapped-robot recovery (ParticleFilterT::enableRecovery, default parameters): in localization-only mode (map from a
+    // file, not action-only) recovery is turned on over the map as it stands once the filter is localised -- when it starts from a
+    // pose, at the start; with global localization, at the first converged iteration.  From then on every iteration is the
+    // call-by-call updateFilter (no fused step: the map update depends on the update's outcome), and an iteration whose update
+    // injected particles (the filter no longer fits the measurements) leaves the map alone: a map extended from a wrong pose would
+    // hold the filter where it is.  Off by default; set before the first iteration.
+    void setKidnapRecovery(bool on) { kidnap_ = on; }
+    bool kidnapRecoveryActive() const { return kidnapOn_; }
+    int heldMapUpdates() const { return heldMaps_; }          // iterations whose map update recovery held back
+    bl_pf_recovery_state_t kidnapRecoveryState() const { return pf_.recoveryState(); }
 
     // The oldest queued scan can be processed once the pose source covers the time of its first ray (slam.cpp:163-188).
     bool isReadyToUpdate() const
@@ -333,7 +343,18 @@ public:
             now_ = pf_.updateFilter(odomAtScan_, scan_, grid_);
             announce();
             globalConverged_ = spreadConverged();
-            if (globalConverged_) extendMap(false);    // the first converged iteration extends the map, as every later one does
+            if (globalConverged_) {
+                startRecovery();
+                extendMap(false);                       // the first converged iteration extends the map, as every later one does
+            }
+            return;
+        }
+        if (kidnapOn_) {                                // recovery on: the map only from an update that did not inject
+            before_ = now_;
+            now_ = pf_.updateFilter(odomAtScan_, scan_, grid_);
+            announce();
+            if (pf_.recoveryState().p_inject > 0.0) ++heldMaps_;
+            else extendMap(false);
             return;
         }
         const bool riding = localize();
@@ -373,6 +394,15 @@ private:
     // filter started at the true pose, 0.025 m / 0.10 rad, measured in tests/test_global_init_model_cpu.py), state
     bool global_ = false, globalConverged_ = false;
     double globalPosTol_ = 0.2, globalHeadingTol_ = 0.3;
+    bool kidnap_ = false, kidnapOn_ = false;     // kidnapped-robot recovery: switch, turned on
+    int heldMaps_ = 0;
+
+    void startRecovery()
+    {
+        if (!kidnap_ || kidnapOn_ || !how_.mapFromFile || how_.odometryOnly || how_.posesGiven) return;
+        pf_.enableRecovery(grid_);
+        kidnapOn_ = true;
+    }
 
     bool globalSearching() const { return global_ && how_.mapFromFile && !how_.odometryOnly && !how_.posesGiven && !globalConverged_; }
 
@@ -396,7 +426,7 @@ private:
         before_.utime = scan_.times.front();
         now_.utime = scan_.times.back();
         if (globalSearching()) pf_.initializeFilterUniformly(grid_, 0.0f, before_.utime);
-        else pf_.initializeFilterAtPose(before_);
+        else { pf_.initializeFilterAtPose(before_); startRecovery(); }
         how_.started = true;
     }
 

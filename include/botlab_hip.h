@@ -150,6 +150,44 @@ typedef struct bl_pf_spread_t {
     uint64_t units_sum, units_sq_lo, units_sq_hi;
 } bl_pf_spread_t;                         /* 80 bytes */
 int bl_pf_spread(bl_pf* pf, bl_pf_spread_t* out);
+/* Kidnapped-robot recovery (augmented MCL, Probabilistic Robotics 8.3.5): while the measurements stop fitting the cloud, a fraction
+ * of the resampled particles is replaced by poses drawn uniformly over the free space of a known map.
+ *   Eligible list: a snapshot of the eligible cells of `map` at call time (bl_pf_init_uniform's rule: log-odds < 0 and, with `dist`,
+ *     distance > min_dist), in a buffer of the recovery's own.  The tracker starts unprimed, updates = 0.  Calling again rebuilds the
+ *     list and resets the tracker; params == NULL turns recovery off and frees the list.
+ *   Errors: BL_ERR_ARG for bad parameters, a `dist` of another shape or no eligible cell; BL_ERR_STATE while an update is pending and
+ *     on a composed shard or a partial slice (n_local < N).  Either way the filter is left exactly as it was.
+ *   Tracking: u counts the moved, sensor-weighted updates since recovery was enabled (1, 2, ...).  At the start of update u the
+ *     posterior about to be resampled is folded in, if a sensor update produced it from a scan it did not interpolate: not a
+ *     cloud of bl_pf_init_at_pose, bl_pf_init_uniform or bl_pf_set_particles, and not the posterior of an update whose particles
+ *     carried a nonzero pose utime -- the first update after an initialisation or upload with utime != 0, which interpolates its
+ *     scan towards utime 0 (the reference's MovingLaserScan with ActionModel::utime_ == 0) and scores an order of magnitude low.
+ *     An action-only update keeps the weights it moved and so the flag:
+ *       w_avg = ((double)S * 0.0005) / (double)N           (S = the posterior's weight units: the mean of max(likelihood, 0.001))
+ *       unprimed: w_slow = w_fast = w_avg, primed = 1;  else w_slow = w_slow + alpha_slow * (w_avg - w_slow), w_fast likewise
+ *     (plain IEEE double, no contraction).
+ *   Injected fraction: p = (primed && w_fast < ratio * w_slow) ? min(max_fraction, 1.0 - w_fast / (ratio * w_slow)) : 0;
+ *     t = p >= 1 ? 2^32 : floor(p * 2^32) (a uint64).
+ *   Injection: output particle m (global index) is injected iff word 0 of Philox4x32-10((m, u, 0x72637679, 2), seed) < t.  Its prior
+ *     (the pose the action model moves and the sensor model weights) is bl_pf_init_uniform's sample over the recovery list, with
+ *     counter words (m, u, 0x72637679, 0 / 1) and the recovery seed.  Every other particle takes its resampled source.  All three
+ *     resampling rules (integer prefix, strict, equal weights) compose with it.  bl_pf_debug_last reports index -1 for an injected
+ *     particle.  Injected particles enter estimatePosteriorPose like any other. */
+typedef struct bl_pf_recovery_params_t {
+    double alpha_slow, alpha_fast;        /* 0 < alpha_slow < alpha_fast <= 1 (defaults 0.001, 0.1) */
+    double ratio;                         /* inject only while w_fast < ratio * w_slow; > 0 and finite */
+    double max_fraction;                  /* cap on the injected fraction, in [0, 1] */
+    float min_dist;                       /* eligibility as bl_pf_init_uniform: log-odds < 0 and, with dist, distance > min_dist */
+    uint64_t seed;
+} bl_pf_recovery_params_t;                /* 48 bytes */
+int bl_pf_set_recovery(bl_pf* pf, const bl_grid* map, const bl_dist* dist /* NULL: log-odds only */,
+                       const bl_pf_recovery_params_t* params /* NULL: off */);
+typedef struct bl_pf_recovery_state_t {
+    double w_slow, w_fast, w_avg, p_inject;
+    uint32_t updates, primed, injected_last, pad;   /* injected_last: particles injected by the last moved update */
+    uint64_t injected_total;
+} bl_pf_recovery_state_t;                 /* 56 bytes; all zero while recovery is off */
+int bl_pf_recovery_state(bl_pf* pf, bl_pf_recovery_state_t* out);   /* synchronises; BL_ERR_STATE while an update is pending */
 /* Replace the whole posterior from a host AoS array of num_particles records (weights must be uniform or the
  * weight-unit integers in `units` given; units == NULL -> uniform). */
 int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, const uint32_t* units);
