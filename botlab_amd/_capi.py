@@ -53,8 +53,20 @@ class PfRecoveryState(C.Structure):
                 ("injected_total", C.c_uint64)]
 
 
+class PfAdaptiveParams(C.Structure):
+    """bl_pf_adaptive_params_t: adaptive particle count, KLD-sampling (40 bytes)."""
+    _fields_ = [("min_particles", C.c_int32), ("pad", C.c_int32), ("epsilon", C.c_double), ("z", C.c_double),
+                ("bin_xy", C.c_double), ("bin_theta", C.c_double)]
+
+
+class PfAdaptiveState(C.Structure):
+    """bl_pf_adaptive_state_t: active / next particle counts and the last count of bins (24 bytes)."""
+    _fields_ = [("active", C.c_int32), ("next", C.c_int32), ("bins", C.c_uint32), ("k_sat", C.c_uint32), ("counts", C.c_uint64)]
+
+
 assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56 and C.sizeof(PfSpread) == 80
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
+assert C.sizeof(PfAdaptiveParams) == 40 and C.sizeof(PfAdaptiveState) == 24
 
 class MotionPlannerState(C.Structure):
     """bl_motion_planner_t: the MotionPlanner members plan_path_to_frontier reads (motion_planner.hpp:153-165)."""
@@ -109,6 +121,8 @@ SIGNATURES = {
     "bl_pf_spread": (C.c_int, [_vp, _P(PfSpread)]),
     "bl_pf_set_recovery": (C.c_int, [_vp, _vp, _vp, _P(PfRecoveryParams)]),
     "bl_pf_recovery_state": (C.c_int, [_vp, _P(PfRecoveryState)]),
+    "bl_pf_set_adaptive": (C.c_int, [_vp, _P(PfAdaptiveParams)]),
+    "bl_pf_adaptive_state": (C.c_int, [_vp, _P(PfAdaptiveState)]),
     "bl_pf_set_particles": (C.c_int, [_vp, _vp, _vp]),
     "bl_pf_get_particles": (C.c_int, [_vp, _vp]),
     "bl_pf_set_noise_seed": (C.c_int, [_vp, C.c_uint64]),

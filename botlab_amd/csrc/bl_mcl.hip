@@ -126,6 +126,21 @@ struct bl_pf {
     uint32_t* rc_list; size_t rc_list_cap;
     uint32_t rc_u;
     struct pf_recovery_dev* rc_dev;            // list, frame and key, and the tracker
+    // adaptive particle count (bl_pf_set_adaptive, KLD-sampling).  cap: bl_pf_create's num_particles, what every buffer is sized for;
+    // cap_local: the slice given to bl_pf_create.  In adaptive mode N = n_local = hi = active (lo = 0); ad_next: what the next
+    // resampling update draws (cap while adaptive mode is off).  The count of a resampling update is read back into ad_hcount
+    // (pinned) behind ad_ev; ad_pending until pf_adaptive_resolve has turned it into ad_bins / ad_next.
+    int cap, cap_local;
+    bool ad_on, ad_pending;
+    bl_pf_adaptive_params_t ad_p;
+    uint32_t ad_ksat, ad_bins;
+    int ad_next;
+    uint64_t ad_counts;
+    unsigned long long* ad_table;              // [1 + ad_table_cap]: the count, then the open-addressing table of bin keys (0: empty)
+    size_t ad_table_cap;
+    unsigned long long* ad_hcount;
+    hipEvent_t ad_ev;
+    std::vector<double>* ad_wfloor;            // [cap + 1]: w_floor of n floor weights (the reference's serial sum), built once
 };
 
 // ---------------------------------------------------------------- device helpers
@@ -1304,6 +1319,21 @@ __global__ __launch_bounds__(256) void k_pf_resample_only(const unsigned long lo
     if (on) out[m] = resample_bisect(prefix, T, lo, hi, strict != 0);
 }
 
+// ... with M output particles drawn from N records (adaptive particle count: M = next, N = active)
+__global__ __launch_bounds__(256) void k_pf_resample_next(const unsigned long long* __restrict__ prefix, const pf_state* __restrict__ state,
+                                                          int N, int M, double r, double M_inv, int strict, int32_t* __restrict__ out)
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+    const bool on = m < M;
+    double T = on ? r + m * M_inv : 0.0;
+    const int uni_n = state->uni_n;
+    if (uni_n > 0) { if (on) out[m] = uni_search(state, uni_n, T, N); return; }
+    if (!strict) T *= state->S;
+    int lo, hi;
+    resample_bracket(prefix, N, T, on, lane, &lo, &hi, strict != 0);
+    if (on) out[m] = resample_bisect(prefix, T, lo, hi, strict != 0);
+}
+
 // ---- strict resampling: the reference's cumulative weight, bit for bit.
 // resamplePosteriorDistribution (particle_filter.cpp:84-103) compares U with c, c = w_0, then c += w_i: a SEQUENTIALLY ROUNDED
 // double sum of the normalised weights w_i = fl64(units_i / S).  One wave reproduces every c_i: inside a binade the sum is an
@@ -1603,7 +1633,7 @@ __global__ void k_pf_set_pose(pf_state* state, bl_pose_xyt_t pose, int only_utim
 // ---------------------------------------------------------------- host side
 static int pf_alloc(bl_pf* pf)
 {
-    size_t N = pf->N, n = pf->n_local;
+    size_t N = pf->cap, n = pf->cap_local;
     if (!pf->rec[0]) {
         BL_HIP(hipMalloc((void**)&pf->rec[0], N * sizeof(float4)));
         BL_HIP(hipMalloc((void**)&pf->rec[1], N * sizeof(float4)));
@@ -1650,6 +1680,7 @@ extern "C" int bl_pf_create(bl_ctx* ctx, int num_particles, int shard_lo, int sh
     memset((void*)pf, 0, sizeof(*pf));
     pf->ctx = ctx;
     pf->N = num_particles; pf->lo = shard_lo; pf->hi = shard_hi; pf->n_local = shard_hi - shard_lo;
+    pf->cap = num_particles; pf->cap_local = pf->n_local; pf->ad_next = num_particles;
     {   // computeNormalizedPosterior on N floor weights: wSum += 0.001 N times, then 0.001 / wSum (volatile: no vectorised reassociation)
         volatile double wsum = 0.0;
         for (int i = 0; i < num_particles; ++i) wsum = wsum + 0.001;
@@ -1683,8 +1714,10 @@ extern "C" void bl_pf_destroy(bl_pf* pf)
     if (!pf->rec_external) { if (pf->rec[0]) (void)hipFree(pf->rec[0]); if (pf->rec[1]) (void)hipFree(pf->rec[1]); }
     void* ptrs[] = {pf->fin_wild, pf->tile_partials, pf->fin_recs, pf->fin_tabs, pf->fin_sync, pf->prefix, pf->parent, pf->state, pf->partials, pf->block_sums, pf->dbg_idx, pf->dbg_like,
                     pf->d_noise, pf->d_export, pf->sh_xchg, pf->sh_tab, pf->sh_fin, pf->sh_flags, pf->sh_peers_dev, pf->strict_recs, pf->strict_starts,
-                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out, pf->rc_list, pf->rc_dev};
+                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out, pf->rc_list, pf->rc_dev, pf->ad_table};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    if (pf->ad_hcount) { (void)hipHostFree(pf->ad_hcount); (void)hipEventDestroy(pf->ad_ev); }
+    delete pf->ad_wfloor;
     delete pf;
 }
 
@@ -1698,6 +1731,22 @@ extern "C" int bl_pf_set_exchange_buffers(bl_pf* pf, void* d_rec0, void* d_rec1)
 
 extern "C" void* bl_pf_exchange_rec_ptr(bl_pf* pf) { return pf && pf->prefix ? (void*)pf->rec[pf->pending_end ? pf->cur ^ 1 : pf->cur] : nullptr; }
 extern "C" const void* bl_pf_pose_device_ptr(bl_pf* pf) { return pf && pf->state ? (const void*)&pf->state->pose : nullptr; }
+
+// w_floor of the current count: N floor weights (an adaptive set's N differs from the capacity: its table, built once)
+static double pf_w_floor(const bl_pf* pf)
+{
+    return (pf->N == pf->cap || !pf->ad_wfloor) ? pf->w_floor : (*pf->ad_wfloor)[pf->N];
+}
+
+// an initialisation or upload fills the whole capacity: active = next = capacity; a pending count is dropped
+static void pf_adaptive_fill(bl_pf* pf)
+{
+    if (pf->ad_pending) { (void)hipEventSynchronize(pf->ad_ev); pf->ad_pending = false; }
+    pf->ad_next = pf->cap;
+    if (pf->N == pf->cap) return;
+    pf->N = pf->n_local = pf->hi = pf->cap;
+    pf->scan_blocks = (pf->cap + SCAN_TILE - 1) / SCAN_TILE;
+}
 
 // what the launch that writes the weight total is told about equal weights (uni_update): 1 = the host knows the record's weights are
 // all equal (only a launch over rec[cur] as uploaded / initialised may be told so), 0 = recognise the all-floor set, -1 = off
@@ -1720,8 +1769,9 @@ static void pf_strict_cumulative(bl_pf* pf, int which)
     const int nchunks = (pf->N + 127) / 128;
     if (pf->N >= STRICT_PAR_MIN && !one_wave) {
         if (!pf->strict_recs) {
-            if (hipMalloc((void**)&pf->strict_recs, (size_t)nchunks * sizeof(strict_rec)) != hipSuccess) pf->strict_recs = nullptr;
-            if (pf->strict_recs && hipMalloc((void**)&pf->strict_starts, ((size_t)nchunks + 128) * sizeof(double)) != hipSuccess) { (void)hipFree(pf->strict_recs); pf->strict_recs = nullptr; }
+            const int cap_chunks = (pf->cap + 127) / 128;         // (sized for the capacity: an adaptive set changes N)
+            if (hipMalloc((void**)&pf->strict_recs, (size_t)cap_chunks * sizeof(strict_rec)) != hipSuccess) pf->strict_recs = nullptr;
+            if (pf->strict_recs && hipMalloc((void**)&pf->strict_starts, ((size_t)cap_chunks + 128) * sizeof(double)) != hipSuccess) { (void)hipFree(pf->strict_recs); pf->strict_recs = nullptr; }
         }
         if (pf->strict_recs) {
             hipStream_t st = pf->ctx->stream;
@@ -1761,7 +1811,7 @@ static int pf_finish_fill(bl_pf* pf, mcl_finish_args* f)
     }
     f->sh = nullptr;
     f->uni_mode = pf_uni_mode(pf, false);
-    f->w_floor = pf->w_floor;
+    f->w_floor = pf_w_floor(pf);
     f->wild = pf->sh_world > 1 ? nullptr : pf->fin_wild;      // (a composed finish keeps to records, tables and replays)
     f->no_trees = getenv("BOTLAB_MCL_NO_TREES") != nullptr ? 1 : 0;
     f->recs = pf->fin_recs;
@@ -1793,7 +1843,7 @@ static int pf_scan(bl_pf* pf, int which, int write_pose, int64_t utime)
         hipLaunchKernelGGL(k_mcl_finish, dim3(MCLF_EXTRA_WGS + f.groups_wait), dim3(MCLF_WG), MCLF_LDS_BYTES, ctx->stream, f);
     } else {
         hipLaunchKernelGGL(k_scan_write_prefix, dim3(pf->scan_blocks), dim3(SCAN_THREADS), 0, ctx->stream, pf->rec[which], pf->N,
-                           pf->block_sums, pf->scan_blocks, pf->prefix, pf->state, pf_uni_mode(pf, true), pf->w_floor);
+                           pf->block_sums, pf->scan_blocks, pf->prefix, pf->state, pf_uni_mode(pf, true), pf_w_floor(pf));
     }
     BL_HIP(hipGetLastError());
     pf_strict_cumulative(pf, which);
@@ -1813,6 +1863,7 @@ extern "C" int bl_pf_init_at_pose(bl_pf* pf, const bl_pose_xyt_t* pose, uint64_t
     BL_CHECK_ARG(pf != nullptr && pose != nullptr);
     BL_HIP(hipSetDevice(pf->ctx->device));
     if (!pf->prefix) { int rc = pf_alloc(pf); if (rc) return rc; }
+    pf_adaptive_fill(pf);
     pf->cur = 0;
     if (pf->sh_broken) { pf->sh_broken = false; BL_HIP(hipMemsetAsync(&pf->state->shard_broken, 0, sizeof(unsigned int), pf->ctx->stream)); }
     hipLaunchKernelGGL(k_pf_init, dim3((pf->N + 255) / 256), dim3(256), 0, pf->ctx->stream, pf->rec[0], pf->parent, pf->N,
@@ -1832,6 +1883,7 @@ extern "C" int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, co
     BL_CHECK_ARG(pf != nullptr && particles != nullptr);
     BL_HIP(hipSetDevice(pf->ctx->device));
     if (!pf->prefix) { int rc = pf_alloc(pf); if (rc) return rc; }
+    pf_adaptive_fill(pf);
     std::vector<float4> rec(pf->N), par(pf->n_local);
     pf->uniform_now = true;
     pf->sensed = false;
@@ -1865,7 +1917,7 @@ extern "C" int bl_pf_get_particles(bl_pf* pf, bl_particle_t* out_local)
     BL_CHECK_ARG(pf != nullptr && out_local != nullptr);
     if (!pf->initialized || pf->pending_end) { bl_set_error("filter not initialised or update pending"); return BL_ERR_STATE; }
     BL_HIP(hipSetDevice(pf->ctx->device));
-    if (!pf->d_export) BL_HIP(hipMalloc((void**)&pf->d_export, (size_t)pf->n_local * sizeof(bl_particle_t)));
+    if (!pf->d_export) BL_HIP(hipMalloc((void**)&pf->d_export, (size_t)pf->cap_local * sizeof(bl_particle_t)));
     hipLaunchKernelGGL(k_pf_export, dim3((pf->n_local + 255) / 256), dim3(256), 0, pf->ctx->stream, pf->rec[pf->cur],
                        pf->parent, pf->state, pf->lo, pf->n_local, pf->pose_utime, pf->parent_utime, pf->d_export);
     BL_HIP(hipGetLastError());
@@ -1889,7 +1941,7 @@ extern "C" int64_t bl_pf_encode_particles_lcm(bl_pf* pf, int64_t utime, uint8_t*
     const int64_t body = (int64_t)pf->n_local * 48, total = 20 + body;
     if (total > cap) { bl_set_error("LCM encode: %lld bytes do not fit the %lld-byte buffer", (long long)total, (long long)cap); return -(int64_t)BL_ERR_CAPACITY; }
     if (hipSetDevice(pf->ctx->device) != hipSuccess) return -(int64_t)BL_ERR_HIP;
-    if (!pf->d_export) { if (hipMalloc((void**)&pf->d_export, (size_t)pf->n_local * sizeof(bl_particle_t)) != hipSuccess) { bl_set_error("hipMalloc failed"); return -(int64_t)BL_ERR_HIP; } }
+    if (!pf->d_export) { if (hipMalloc((void**)&pf->d_export, (size_t)pf->cap_local * sizeof(bl_particle_t)) != hipSuccess) { bl_set_error("hipMalloc failed"); return -(int64_t)BL_ERR_HIP; } }
     const long long dwords = (long long)pf->n_local * 12;
     hipLaunchKernelGGL(k_pf_encode_lcm, dim3((unsigned)((dwords + 255) / 256)), dim3(256), 0, pf->ctx->stream, pf->rec[pf->cur], pf->parent,
                        pf->state, pf->lo, pf->n_local, pf->pose_utime, pf->parent_utime, (uint32_t*)pf->d_export);
@@ -1931,10 +1983,11 @@ static bool action_update(bl_pf* pf, const bl_pose_xyt_t& odometry)
     return pf->moved;
 }
 
-static int pf_upload_noise(bl_pf* pf, const float* noise)
+// parity mode: 3 * n floats for the n output particles of the update (n_local, or next in adaptive mode)
+static int pf_upload_noise(bl_pf* pf, const float* noise, int n)
 {
-    if (!pf->d_noise) BL_HIP(hipMalloc((void**)&pf->d_noise, (size_t)pf->n_local * 3 * sizeof(float)));
-    BL_HIP(hipMemcpyAsync(pf->d_noise, noise + (size_t)pf->lo * 3, (size_t)pf->n_local * 3 * sizeof(float),
+    if (!pf->d_noise) BL_HIP(hipMalloc((void**)&pf->d_noise, (size_t)pf->cap_local * 3 * sizeof(float)));
+    BL_HIP(hipMemcpyAsync(pf->d_noise, noise + (size_t)pf->lo * 3, (size_t)n * 3 * sizeof(float),
                           hipMemcpyHostToDevice, pf->ctx->stream));
     BL_HIP(hipStreamSynchronize(pf->ctx->stream));          // caller-owned pageable buffer
     return BL_OK;
@@ -1970,9 +2023,150 @@ __global__ __launch_bounds__(64) void k_pf_recovery_fold(const pf_state* __restr
     *d = v;
 }
 
+// ---------------------------------------------------------------- adaptive particle count (KLD-sampling)
+// The count of a resampling update: k = distinct bins of the parent poses [0, n) (botlab_hip.h, bl_pf_set_adaptive).  A bin is
+// packed into 63 bits -- three indices clamped to [-2^20, 2^20 - 1], offset by 2^20, 21 bits each -- and stored plus one (0: an
+// empty slot).  k_kld_count: every workgroup takes KLD_PER_WG particles and removes their duplicates in an LDS table first (a
+// converged cloud has a handful of bins among thousands of particles); only its distinct keys go to the global open-addressing
+// table, and each wave adds the keys it was first to insert with one atomic.  Once the count has reached k_sat a workgroup
+// inserts nothing more (AMCL's early stop): the count is exact below k_sat, and at least k_sat otherwise.  The global table has
+// at least twice as many slots as particles, so it cannot fill; every probe loop is bounded by its table size all the same.
+#define KLD_WG 256
+#define KLD_PER_THREAD 4
+#define KLD_PER_WG (KLD_WG * KLD_PER_THREAD)
+#define KLD_LDS_SLOTS (2 * KLD_PER_WG)
+#define KLD_IDX_LIM 1048576.0                     // 2^20
+
+__host__ __device__ __forceinline__ unsigned long long kld_mix(unsigned long long k)     // splitmix64's finaliser
+{
+    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
+    k ^= k >> 27; k *= 0x94d049bb133111ebull;
+    return k ^ (k >> 31);
+}
+
+__device__ __forceinline__ unsigned long long kld_index(double v, double bin)
+{
+    const double q = floor(v / bin);
+    if (!(q >= -KLD_IDX_LIM)) return 0ull;                                // (NaN too)
+    if (q > KLD_IDX_LIM - 1.0) return (unsigned long long)(2.0 * KLD_IDX_LIM - 1.0);
+    return (unsigned long long)(long long)(q + KLD_IDX_LIM);
+}
+
+__global__ __launch_bounds__(KLD_WG) void k_kld_count(const float4* __restrict__ parent, int n, double bin_xy, double bin_theta,
+                                                      unsigned long long* __restrict__ count_table, unsigned int mask, unsigned int k_sat)
+{
+    __shared__ unsigned long long s_tab[KLD_LDS_SLOTS];
+    __shared__ int s_stop;
+    unsigned long long* count = count_table;
+    unsigned long long* table = count_table + 1;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid == 0) s_stop = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= k_sat;
+    for (int i = tid; i < KLD_LDS_SLOTS; i += KLD_WG) s_tab[i] = 0ull;
+    __syncthreads();
+    if (s_stop) return;                                                     // (uniform over the workgroup)
+    const int base = blockIdx.x * KLD_PER_WG;
+    for (int r = 0; r < KLD_PER_THREAD; ++r) {
+        const int j = base + r * KLD_WG + tid;
+        if (j >= n) break;
+        const float4 p = parent[j];
+        const unsigned long long key = ((kld_index((double)p.x, bin_xy) << 42) | (kld_index((double)p.y, bin_xy) << 21) |
+                                        kld_index((double)p.z, bin_theta)) + 1ull;
+        unsigned int h = (unsigned int)kld_mix(key) & (KLD_LDS_SLOTS - 1);
+        for (int probe = 0; probe < KLD_LDS_SLOTS; ++probe) {             // (at most KLD_PER_WG keys in twice as many slots)
+            const unsigned long long prev = atomicCAS(&s_tab[h], 0ull, key);
+            if (prev == 0ull || prev == key) break;
+            h = (h + 1) & (KLD_LDS_SLOTS - 1);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) s_stop = __hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= k_sat;
+    __syncthreads();
+    if (s_stop) return;
+    unsigned int added = 0;                                                 // (wave-uniform: a sum of ballots)
+    for (int i = tid; i < KLD_LDS_SLOTS; i += KLD_WG) {
+        const unsigned long long key = s_tab[i];
+        bool fresh = false;
+        if (key != 0ull) {
+            unsigned int h = (unsigned int)kld_mix(key) & mask;
+            for (unsigned int probe = 0; probe <= mask; ++probe) {
+                const unsigned long long prev = atomicCAS(&table[h], 0ull, key);
+                if (prev == 0ull) { fresh = true; break; }
+                if (prev == key) break;
+                h = (h + 1) & mask;
+            }
+        }
+        added += (unsigned int)__popcll(__builtin_amdgcn_ballot_w64(fresh));
+    }
+    if (lane == 0 && added != 0) atomicAdd(count, (unsigned long long)added);
+}
+
+// n(k) of the bound (botlab_hip.h): plain double (the library builds with -ffp-contract=off)
+static double kld_bound(uint64_t k, double epsilon, double z)
+{
+    const double km1 = (double)(k - 1);
+    const double b = 2.0 / (9.0 * km1);
+    const double c = 1.0 - b + sqrt(b) * z;
+    return ceil(km1 / (2.0 * epsilon) * c * c * c);
+}
+
+static int kld_next(const bl_pf_adaptive_params_t& q, int cap, uint64_t k)
+{
+    const double n = k <= 1 ? (double)q.min_particles : kld_bound(k, q.epsilon, q.z);
+    if (!(n < (double)cap)) return cap;                                     // (NaN: the capacity)
+    return n > (double)q.min_particles ? (int)n : q.min_particles;
+}
+
+// the smallest k in [2, cap + 1] with n(k) >= cap; cap + 1 when there is none (a count of at most cap particles never stops early)
+static uint32_t kld_ksat(const bl_pf_adaptive_params_t& q, int cap)
+{
+    for (uint64_t k = 2; k <= (uint64_t)cap; ++k)
+        if (kld_bound(k, q.epsilon, q.z) >= (double)cap) return (uint32_t)k;
+    return (uint32_t)cap + 1u;
+}
+
+// turn the last count into bins and next (waits for its read-back)
+static int pf_adaptive_resolve(bl_pf* pf)
+{
+    if (!pf->ad_pending) return BL_OK;
+    BL_HIP(hipEventSynchronize(pf->ad_ev));
+    pf->ad_pending = false;
+    const unsigned long long k = *pf->ad_hcount;
+    pf->ad_bins = k < pf->ad_ksat ? (uint32_t)k : pf->ad_ksat;
+    pf->ad_next = kld_next(pf->ad_p, pf->cap, pf->ad_bins);
+    return BL_OK;
+}
+
+// the count of the update just launched (its parent poses, N of them), read back behind ad_ev
+static int pf_adaptive_count(bl_pf* pf)
+{
+    hipStream_t st = pf->ctx->stream;
+    unsigned int slots = 1024;
+    while (slots < 2u * (unsigned int)pf->N) slots <<= 1;                  // (ad_table_cap: the same rule for the capacity)
+    BL_HIP(hipMemsetAsync(pf->ad_table, 0, ((size_t)slots + 1) * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_kld_count, dim3((pf->N + KLD_PER_WG - 1) / KLD_PER_WG), dim3(KLD_WG), 0, st, (const float4*)pf->parent, pf->N,
+                       pf->ad_p.bin_xy, pf->ad_p.bin_theta, pf->ad_table, slots - 1u, pf->ad_ksat);
+    BL_HIP(hipGetLastError());
+    BL_HIP(hipMemcpyAsync(pf->ad_hcount, pf->ad_table, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    BL_HIP(hipEventRecord(pf->ad_ev, st));
+    pf->ad_pending = true;
+    pf->ad_counts += 1;
+    return BL_OK;
+}
+
 static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, const float* noise, int resample)
 {
     bl_ctx* ctx = pf->ctx;
+    // The output count.  A resampling update of an adaptive set (or the first one after adaptive mode was turned off) draws next
+    // particles from the N = active records; everything else keeps n_local.  next comes from the count of the last resampling
+    // update: when it has not been read yet, this is where the host waits for it (the one wait adaptive mode adds).
+    int n_out = pf->n_local;
+    const bool resize = resample != 0 && (pf->ad_on || pf->N != pf->cap);
+    if (resize) {
+        int rc_a = pf_adaptive_resolve(pf);
+        if (rc_a) return rc_a;
+        n_out = pf->ad_next;
+    }
+    if (noise) { int rc_n = pf_upload_noise(pf, noise, n_out); if (rc_n) return rc_n; }
     mcl_args a;
     a.src = pf->rec[pf->cur];
     a.dst = pf->rec[pf->cur ^ 1];
@@ -1987,8 +2181,8 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     // MovingLaserScan(scan, parent_pose, pose) (sensor_model.cpp:18): begin = parent utime, end = ActionModel::utime_ = 0 (D3)
     a.t_begin = pf->pose_utime; a.t_den = (pf->pose_utime != 0) ? (double)(0 - pf->pose_utime) : 1.0;
     a.R = R;
-    a.N = pf->N; a.lo = pf->lo; a.n_local = pf->n_local;
-    a.M_inv = 1.0 / pf->N;                                           // particle_filter.cpp:89
+    a.N = pf->N; a.lo = pf->lo; a.n_local = n_out;                  // (adaptive: N active records searched, n_out = next drawn)
+    a.M_inv = 1.0 / (resize ? n_out : pf->N);                        // particle_filter.cpp:89
     a.r = (((double)rand_value) / (double)RAND_MAX) * a.M_inv;       // particle_filter.cpp:92
     a.rot1 = pf->rot1; a.trans = pf->trans; a.rot2 = pf->rot2;
     a.rot1Std = pf->rot1Std; a.transStd = pf->transStd; a.rot2Std = pf->rot2Std;
@@ -2081,10 +2275,10 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     a.split_log2 = 0;
     if (map && pf->split_log2_override >= 0) a.split_log2 = pf->split_log2_override;
     else if (map) {
-        while (a.split_log2 < 6 && ((int64_t)pf->n_local << a.split_log2) < (int64_t)MCL_MIN_BLOCKS * block) a.split_log2++;
+        while (a.split_log2 < 6 && ((int64_t)n_out << a.split_log2) < (int64_t)MCL_MIN_BLOCKS * block) a.split_log2++;
         // ... and, up to four lanes per particle, until the launch is about two rounds of the machine: 256 000 particles at two
         // lanes are 1000 workgroups -- one round and a third -- and took 0.309 ms where four lanes (2000 workgroups) take 0.252
-        while (a.split_log2 < 2 && ((int64_t)pf->n_local << a.split_log2) < (int64_t)1400 * block) a.split_log2++;
+        while (a.split_log2 < 2 && ((int64_t)n_out << a.split_log2) < (int64_t)1400 * block) a.split_log2++;
     }
     while (a.split_log2 > 0 && (1 << a.split_log2) > R) a.split_log2--;
     // Whole rounds.  All workgroups of this VALU-bound kernel take about the same time T, so 782 workgroups on a machine
@@ -2095,8 +2289,8 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     // 73): those workgroups last ~T/10.  One round is counted a little short of what the device holds (below), because the
     // replanner's kernels on the other streams occupy a few workgroup slots.
     const int gpb = block >> a.split_log2;                  // particles per region-1 workgroup
-    int64_t main_blocks = ((int64_t)pf->n_local + gpb - 1) / gpb, tail_blocks = 0;
-    int64_t main_particles = pf->n_local;
+    int64_t main_blocks = ((int64_t)n_out + gpb - 1) / gpb, tail_blocks = 0;
+    int64_t main_particles = n_out;
     const int tail_tile = block >> 6;                       // particles per region-2 workgroup
     if (map && !pf->no_balance && gpb >= 1) {
         const int cus = pf->cus > 0 ? pf->cus : 256;
@@ -2115,7 +2309,7 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
         if (full >= 1 && excess > 0 && excess * 8 < round * 5 && excess * gpb <= 24576) {
             main_blocks = full * round;
             main_particles = main_blocks * gpb;
-            tail_blocks = ((int64_t)pf->n_local - main_particles + tail_tile - 1) / tail_tile;
+            tail_blocks = ((int64_t)n_out - main_particles + tail_tile - 1) / tail_tile;
         }
     }
     a.main_blocks = (int)main_blocks; a.main_particles = (int)main_particles;
@@ -2158,6 +2352,12 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     BL_HIP(hipGetLastError());
     rc = bl_timer_commit(ctx, BL_K_MCL_MAIN, e0, e1);
     if (rc) return rc;
+    if (resize && n_out != pf->N) {
+        // the new record holds n_out particles: from here on (finish, estimate, exports) N is that count
+        pf->N = pf->n_local = pf->hi = n_out;
+        pf->scan_blocks = (n_out + SCAN_TILE - 1) / SCAN_TILE;
+    }
+    if (resize && pf->ad_on) { rc = pf_adaptive_count(pf); if (rc) return rc; }
     pf->last_blocks = blocks;
     pf->last_tile = gpb;                                  // particles per region-1 workgroup of k_mcl_main
     pf->last_main_blocks = a.main_blocks; pf->last_main_particles = a.main_particles; pf->last_tail_tile = tail_tile;
@@ -2215,7 +2415,6 @@ extern "C" int bl_pf_update_begin(bl_pf* pf, const bl_pose_xyt_t* odometry, cons
     int R = 0;
     int rc = bl_scan_upload(pf->ctx, scan, &R);
     if (rc) return rc;
-    if (noise) { rc = pf_upload_noise(pf, noise); if (rc) return rc; }
     rc = pf_launch_main(pf, map, R, rand_value, noise, 1);
     if (rc) return rc;
     pf->uniform_now = false;                     // the record this update writes carries the sensor model's weights
@@ -2343,6 +2542,7 @@ extern "C" int bl_pf_shard_setup(bl_pf* pf, int rank, int world, int block)
     BL_CHECK_ARG(pf->lo == rank * block && pf->hi == (pf->N < (rank + 1) * block ? pf->N : (rank + 1) * block));
     BL_CHECK_ARG((int64_t)(world - 1) * block < pf->N);            // every rank owns particles
     if (pf->rec_external) { bl_set_error("a composed finish keeps its exchange records in the library's own allocations"); return BL_ERR_STATE; }
+    if (pf->ad_on || pf->N != pf->cap) { bl_set_error("a sharded set keeps a fixed particle count: turn adaptive mode off and re-initialise"); return BL_ERR_STATE; }
     if (pf->strict) { bl_set_error("strict resampling needs the whole particle set on one device"); return BL_ERR_STATE; }
     BL_HIP(hipSetDevice(pf->ctx->device));
     if (!pf->prefix) { int rc = pf_alloc(pf); if (rc) return rc; }
@@ -2787,7 +2987,6 @@ extern "C" int bl_pf_update_action_only(bl_pf* pf, const bl_pose_xyt_t* odometry
     BL_HIP(hipSetDevice(pf->ctx->device));
     bool mv = action_update(pf, *odometry);
     if (mv) {
-        if (noise) { int rc = pf_upload_noise(pf, noise); if (rc) return rc; }
         int rc = pf_launch_main(pf, nullptr, 0, 0, noise, 0);     // proposal = applyAction(posterior_) (particle_filter.cpp:60-61)
         if (rc) return rc;
         pf->fused_finish = false;                                 // weights are carried over: plain scan, no estimate
@@ -2916,12 +3115,19 @@ extern "C" int bl_pf_debug_resample(bl_pf* pf, int rand_value, int32_t* out_idx)
     if (!pf->initialized || pf->pending_end) { bl_set_error("filter not initialised or update pending"); return BL_ERR_STATE; }
     if (pf->n_local != pf->N) { bl_set_error("bl_pf_debug_resample needs the whole particle set on one device"); return BL_ERR_ARG; }
     BL_HIP(hipSetDevice(pf->ctx->device));
-    const double M_inv = 1.0 / pf->N;                                              // particle_filter.cpp:89
+    // (adaptive: the next indices the next resampling update would take from the N active records)
+    int M = pf->N;
+    if (pf->ad_on || pf->N != pf->cap) { int rc = pf_adaptive_resolve(pf); if (rc) return rc; M = pf->ad_next; }
+    const double M_inv = 1.0 / M;                                                  // particle_filter.cpp:89
     const double r = (((double)rand_value) / (double)RAND_MAX) * M_inv;            // particle_filter.cpp:92
-    hipLaunchKernelGGL(k_pf_resample_only, dim3((pf->N + 255) / 256), dim3(256), 0, pf->ctx->stream, pf->prefix, pf->state, pf->N, r, M_inv,
-                       pf->prefix_is_strict ? 1 : 0, pf->dbg_idx);
+    if (M == pf->N)
+        hipLaunchKernelGGL(k_pf_resample_only, dim3((pf->N + 255) / 256), dim3(256), 0, pf->ctx->stream, pf->prefix, pf->state, pf->N, r, M_inv,
+                           pf->prefix_is_strict ? 1 : 0, pf->dbg_idx);
+    else
+        hipLaunchKernelGGL(k_pf_resample_next, dim3((M + 255) / 256), dim3(256), 0, pf->ctx->stream, pf->prefix, pf->state, pf->N, M, r, M_inv,
+                           pf->prefix_is_strict ? 1 : 0, pf->dbg_idx);
     BL_HIP(hipGetLastError());
-    BL_HIP(hipMemcpyAsync(out_idx, pf->dbg_idx, (size_t)pf->N * 4, hipMemcpyDeviceToHost, pf->ctx->stream));
+    BL_HIP(hipMemcpyAsync(out_idx, pf->dbg_idx, (size_t)M * 4, hipMemcpyDeviceToHost, pf->ctx->stream));
     BL_HIP(hipStreamSynchronize(pf->ctx->stream));
     return BL_OK;
 }
@@ -3262,6 +3468,7 @@ extern "C" int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* 
     int rc0 = gl_build_list(pf, map, dist, min_dist, &pf->gl_list, &pf->gl_list_cap, &F);
     if (rc0) return rc0;
     hipStream_t st = pf->ctx->stream;
+    pf_adaptive_fill(pf);
     pf->cur = 0;
     if (pf->sh_broken) { pf->sh_broken = false; BL_HIP(hipMemsetAsync(&pf->state->shard_broken, 0, sizeof(unsigned int), st)); }
     hipLaunchKernelGGL(k_pf_init_uniform, dim3((pf->N + 255) / 256), dim3(256), 0, st, pf->rec[0], pf->parent, pf->N, pf->lo, pf->n_local,
@@ -3453,5 +3660,77 @@ extern "C" int bl_pf_recovery_state(bl_pf* pf, bl_pf_recovery_state_t* out)
     out->updates = h.updates; out->primed = h.primed;
     out->injected_last = (uint32_t)(h.injected_total - h.total_at_fold);
     out->injected_total = h.injected_total;
+    return BL_OK;
+}
+
+// ---------------------------------------------------------------- adaptive particle count (KLD-sampling)
+// bl_pf_set_adaptive: checks, the table of the count (sized for the capacity), the w_floor table (once per filter), k_sat.  From
+// then on every resampling update draws next particles and counts its parents (pf_launch_main); the formulas are in botlab_hip.h.
+extern "C" int bl_pf_set_adaptive(bl_pf* pf, const bl_pf_adaptive_params_t* params)
+{
+    BL_CHECK_ARG(pf != nullptr);
+    if (params) {
+        const bl_pf_adaptive_params_t& q = *params;
+        if (!(q.min_particles >= 2 && q.min_particles <= pf->cap) || !(q.epsilon > 0.0 && q.epsilon < HUGE_VAL) || !(q.z > 0.0 && q.z < HUGE_VAL) ||
+            !(q.bin_xy > 0.0 && q.bin_xy < HUGE_VAL) || !(q.bin_theta > 0.0 && q.bin_theta < HUGE_VAL)) {
+            bl_set_error("adaptive parameters: need 2 <= min_particles <= capacity (%d) and epsilon, z, bin_xy, bin_theta > 0 and finite", pf->cap);
+            return BL_ERR_ARG;
+        }
+    }
+    if (pf->pending_end) { bl_set_error("update pending"); return BL_ERR_STATE; }
+    if (pf->sh_world > 1 || pf->cap_local < pf->cap || pf->rec_external) {
+        bl_set_error("adaptive particle count needs the whole particle set in the library's own buffers (not a sharded set)");
+        return BL_ERR_STATE;
+    }
+    BL_HIP(hipSetDevice(pf->ctx->device));
+    if (pf->ad_pending) { BL_HIP(hipEventSynchronize(pf->ad_ev)); pf->ad_pending = false; }
+    if (!params) {
+        pf->ad_on = false;
+        pf->ad_next = pf->cap;                   // the next resampling update draws the whole capacity
+        pf->ad_ksat = 0;
+        return BL_OK;
+    }
+    size_t slots = 1024;
+    while (slots < 2 * (size_t)pf->cap) slots <<= 1;
+    if (pf->ad_table_cap < slots) {
+        unsigned long long* t = nullptr;
+        BL_HIP(hipMalloc((void**)&t, (slots + 1) * sizeof(unsigned long long)));
+        if (pf->ad_table) { BL_HIP(hipStreamSynchronize(pf->ctx->stream)); BL_HIP(hipFree(pf->ad_table)); }
+        pf->ad_table = t; pf->ad_table_cap = slots;
+    }
+    if (!pf->ad_hcount) {
+        BL_HIP(hipHostMalloc((void**)&pf->ad_hcount, sizeof(unsigned long long), hipHostMallocDefault));
+        if (hipEventCreateWithFlags(&pf->ad_ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipHostFree(pf->ad_hcount); pf->ad_hcount = nullptr;
+            bl_set_error("hipEventCreate failed"); return BL_ERR_HIP;
+        }
+    }
+    if (!pf->ad_wfloor) {
+        // computeNormalizedPosterior on n floor weights for every n (bl_pf_create's loop, one pass)
+        std::vector<double>* t = new std::vector<double>((size_t)pf->cap + 1, 0.0);
+        volatile double wsum = 0.0;
+        for (int n = 1; n <= pf->cap; ++n) { wsum = wsum + 0.001; (*t)[n] = 0.001 / wsum; }
+        pf->ad_wfloor = t;
+    }
+    pf->ad_p = *params;
+    pf->ad_ksat = kld_ksat(*params, pf->cap);
+    pf->ad_on = true;
+    pf->ad_next = pf->N;                         // next = active until a count says otherwise
+    pf->ad_bins = 0;
+    pf->ad_counts = 0;
+    return BL_OK;
+}
+
+extern "C" int bl_pf_adaptive_state(bl_pf* pf, bl_pf_adaptive_state_t* out)
+{
+    BL_CHECK_ARG(pf != nullptr && out != nullptr);
+    if (pf->pending_end) { bl_set_error("update pending"); return BL_ERR_STATE; }
+    if (pf->ad_pending) { BL_HIP(hipSetDevice(pf->ctx->device)); int rc = pf_adaptive_resolve(pf); if (rc) return rc; }
+    memset(out, 0, sizeof(*out));
+    out->active = pf->N;
+    out->next = pf->ad_next;
+    out->bins = pf->ad_bins;
+    out->k_sat = pf->ad_on ? pf->ad_ksat : 0u;
+    out->counts = pf->ad_counts;
     return BL_OK;
 }

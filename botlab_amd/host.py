@@ -240,6 +240,11 @@ def spread_stds(s):
 RECOVERY_ALPHA_SLOW, RECOVERY_ALPHA_FAST = 0.001, 0.1
 RECOVERY_RATIO, RECOVERY_MAX_FRACTION = 0.9, 0.1
 
+# adaptive particle count defaults (ParticleFilter.setAdaptive): AMCL's epsilon, the 0.99 quantile, the reference's 200 particles as
+# the floor; bins calibrated on the CPU reference filter (tests/test_adaptive_model_cpu.py)
+ADAPTIVE_MIN_PARTICLES, ADAPTIVE_EPSILON, ADAPTIVE_Z = 200, 0.01, 2.326
+ADAPTIVE_BIN_XY, ADAPTIVE_BIN_THETA = 0.1, math.radians(10.0)
+
 
 class ParticleFilter:
     """ParticleFilter(numParticles) (particle_filter.hpp:38-77).  shard=(lo, hi) keeps only those particles' private
@@ -253,6 +258,14 @@ class ParticleFilter:
         h = C.c_void_p()
         check(self.ctx.lib.bl_pf_create(self.ctx.h, self.N, self.lo, self.hi, C.byref(h)))
         self.h = h
+        self._adaptive_used = False       # the particle count may differ from N once adaptive mode has been on
+
+    def _counts(self):
+        """(active, next): particles in the current record, particles the next resampling update draws."""
+        if not self._adaptive_used:
+            return self.hi - self.lo, self.hi - self.lo
+        s = self.adaptiveState()
+        return s["active"], s["next"]
 
     def initializeFilterAtPose(self, pose, seed=None):
         if seed is None:                                                # reference: std::random_device
@@ -300,6 +313,28 @@ class ParticleFilter:
         check(self.ctx.lib.bl_pf_recovery_state(self.h, C.byref(out)))
         return {f: getattr(out, f) for f, _ in _capi.PfRecoveryState._fields_ if f != "pad"}
 
+    def setAdaptive(self, minParticles=ADAPTIVE_MIN_PARTICLES, epsilon=ADAPTIVE_EPSILON, z=ADAPTIVE_Z, binXY=ADAPTIVE_BIN_XY,
+                    binTheta=ADAPTIVE_BIN_THETA):
+        """Adaptive particle count (KLD-sampling, bl_pf_set_adaptive): every resampling update draws between minParticles and N
+        particles, as many as the number of occupied (binXY, binXY, binTheta) bins of the resampled set needs for a KLD error
+        below epsilon with quantile z.  minParticles=None turns it off (the next resampling update draws N again)."""
+        if minParticles is None:
+            check(self.ctx.lib.bl_pf_set_adaptive(self.h, None))
+            return
+        p = _capi.PfAdaptiveParams(int(minParticles), 0, float(epsilon), float(z), float(binXY), float(binTheta))
+        check(self.ctx.lib.bl_pf_set_adaptive(self.h, C.byref(p)))
+        self._adaptive_used = True
+
+    def adaptiveState(self):
+        """bl_pf_adaptive_state: dict of active, next, bins, k_sat, counts."""
+        out = _capi.PfAdaptiveState()
+        check(self.ctx.lib.bl_pf_adaptive_state(self.h, C.byref(out)))
+        return {f: getattr(out, f) for f, _ in _capi.PfAdaptiveState._fields_}
+
+    def numParticles(self):
+        """Particles in the current record (N, or the adaptive count)."""
+        return self._counts()[0]
+
     def setParticles(self, particles, units=None):
         """particles: structured array (PARTICLE_DTYPE) of all N particles."""
         p = np.ascontiguousarray(particles)
@@ -322,7 +357,7 @@ class ParticleFilter:
         nz = None
         if noise is not None:
             nz = np.ascontiguousarray(noise, dtype=np.float32)
-            assert nz.size == 3 * self.N
+            assert nz.size == 3 * (self._counts()[1] if self._adaptive_used else self.N)
         out = Pose()
         check(self.ctx.lib.bl_pf_update(self.h, C.byref(odometry), C.byref(ls), grid.h, int(rand_value),
                                         nz.ctypes.data if nz is not None else None, C.byref(out) if want_pose else None))
@@ -372,7 +407,7 @@ class ParticleFilter:
 
     def debugResample(self, rand_value):
         """Source index of every output particle of resamplePosteriorDistribution for this rand() value (particle_filter.cpp:84-103)."""
-        idx = np.empty(self.N, np.int32)
+        idx = np.empty(self._counts()[1] if self._adaptive_used else self.N, np.int32)
         check(self.ctx.lib.bl_pf_debug_resample(self.h, int(rand_value), idx.ctypes.data))
         return idx
 
@@ -390,7 +425,7 @@ class ParticleFilter:
 
     def particles(self):
         """particles_t.particles of the local shard as a structured array."""
-        out = np.zeros(self.hi - self.lo, dtype=PARTICLE_DTYPE)
+        out = np.zeros(self._counts()[0], dtype=PARTICLE_DTYPE)
         check(self.ctx.lib.bl_pf_get_particles(self.h, out.ctypes.data))
         return out
 
@@ -398,7 +433,7 @@ class ParticleFilter:
         check(self.ctx.lib.bl_pf_debug_enable(self.h, 1 if on else 0))
 
     def debugLast(self):
-        n = self.hi - self.lo
+        n = self._counts()[0]
         idx = np.empty(n, np.int32)
         like = np.empty(n, np.int32)
         check(self.ctx.lib.bl_pf_debug_last(self.h, idx.ctypes.data, like.ctypes.data))

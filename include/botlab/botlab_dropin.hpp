@@ -314,6 +314,27 @@ public:
         check(bl_pf_recovery_state(h_, &s), "bl_pf_recovery_state");
         return s;
     }
+    // (extension) adaptive particle count, KLD-sampling (botlab_hip.h, bl_pf_set_adaptive): every resampling update draws between
+    // params.min_particles and the capacity (the constructor's numParticles), as many as the spread of the posterior needs
+    static bl_pf_adaptive_params_t defaultAdaptiveParams()
+    {
+        bl_pf_adaptive_params_t q;
+        q.min_particles = 200;                                                  // the reference's particle count (slam_main.cpp)
+        q.pad = 0;
+        q.epsilon = 0.01; q.z = 2.326;                                          // AMCL's kld_err; the 0.99 quantile
+        q.bin_xy = 0.1; q.bin_theta = 0.17453292519943295;                      // calibrated
+        return q;
+    }
+    void enableAdaptive(const bl_pf_adaptive_params_t& params) { check(bl_pf_set_adaptive(h_, &params), "bl_pf_set_adaptive"); }
+    void enableAdaptive() { enableAdaptive(defaultAdaptiveParams()); }
+    void disableAdaptive() { check(bl_pf_set_adaptive(h_, nullptr), "bl_pf_set_adaptive"); }
+    bl_pf_adaptive_state_t adaptiveState() const
+    {
+        bl_pf_adaptive_state_t s;
+        check(bl_pf_adaptive_state(h_, &s), "bl_pf_adaptive_state");
+        return s;
+    }
+    int numParticles() const { return adaptiveState().active; }                 // particles in the current record
     // (extension) spread of the posterior: has a globally initialised filter converged? (botlab_hip.h, bl_pf_spread)
     bl_pf_spread_t spread() const
     {
@@ -360,12 +381,13 @@ public:
     }
     Particles particles() const                                                 // particle_filter.cpp:75-81
     {
-        std::vector<bl_particle_t> raw(n_);
+        const int n = numParticles();                                           // (the adaptive count: at most n_)
+        std::vector<bl_particle_t> raw(n);
         check(bl_pf_get_particles(h_, raw.data()), "bl_pf_get_particles");
         Particles out;
-        out.num_particles = n_;
-        out.particles.resize(n_);
-        for (int i = 0; i < n_; ++i) {
+        out.num_particles = n;
+        out.particles.resize(n);
+        for (int i = 0; i < n; ++i) {
             out.particles[i].pose = pose_out<Pose>(raw[i].pose);
             out.particles[i].parent_pose = pose_out<Pose>(raw[i].parent_pose);
             out.particles[i].weight = raw[i].weight;

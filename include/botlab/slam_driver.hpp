@@ -318,6 +318,14 @@ public:
     bool kidnapRecoveryActive() const { return kidnapOn_; }
     int heldMapUpdates() const { return heldMaps_; }          // iterations whose map update recovery held back
     bl_pf_recovery_state_t kidnapRecoveryState() const { return pf_.recoveryState(); }
+    // (extension) Adaptive particle count (ParticleFilterT::enableAdaptive, default parameters): the filter is created with the
+    // capacity, seeded with all of it (at the start pose, or uniformly with global localization), and from then on every resampling
+    // update draws only as many particles as the spread of the posterior needs, down to 200.  Every iteration is then the
+    // call-by-call updateFilter.  Composes with global localization and kidnapped-robot recovery.  Off by default; set before the
+    // first iteration.
+    void setAdaptiveParticles(bool on) { adaptive_ = on; }
+    bool adaptiveParticlesActive() const { return adaptiveOn_; }
+    bl_pf_adaptive_state_t adaptiveState() const { return pf_.adaptiveState(); }
 
     // The oldest queued scan can be processed once the pose source covers the time of its first ray (slam.cpp:163-188).
     bool isReadyToUpdate() const
@@ -396,6 +404,7 @@ private:
     double globalPosTol_ = 0.2, globalHeadingTol_ = 0.3;
     bool kidnap_ = false, kidnapOn_ = false;     // kidnapped-robot recovery: switch, turned on
     int heldMaps_ = 0;
+    bool adaptive_ = false, adaptiveOn_ = false; // adaptive particle count: switch, turned on
 
     void startRecovery()
     {
@@ -427,6 +436,7 @@ private:
         now_.utime = scan_.times.back();
         if (globalSearching()) pf_.initializeFilterUniformly(grid_, 0.0f, before_.utime);
         else { pf_.initializeFilterAtPose(before_); startRecovery(); }
+        if (adaptive_ && !how_.posesGiven) { pf_.enableAdaptive(); adaptiveOn_ = true; }
         how_.started = true;
     }
 
@@ -442,7 +452,7 @@ private:
     {
         if (how_.posesGiven || !how_.mapKnown) return false;
         before_ = now_;
-        if (!how_.odometryOnly && fused_) {
+        if (!how_.odometryOnly && fused_ && !adaptiveOn_) {
             pf_.updateFilterBegin(odomAtScan_, scan_, grid_);
             if (!waiting_.empty()) prefetch_scan(waiting_.front());      // the next scan is already queued: it rides along
             return true;

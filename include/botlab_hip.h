@@ -188,6 +188,37 @@ typedef struct bl_pf_recovery_state_t {
     uint64_t injected_total;
 } bl_pf_recovery_state_t;                 /* 56 bytes; all zero while recovery is off */
 int bl_pf_recovery_state(bl_pf* pf, bl_pf_recovery_state_t* out);   /* synchronises; BL_ERR_STATE while an update is pending */
+/* Adaptive particle count (KLD-sampling, Fox 2003; Probabilistic Robotics Table 8.4), off by default.
+ *   Capacity = bl_pf_create's num_particles; every buffer stays sized for it.  Inits and uploads fill it: active = next = capacity.
+ *   active: particles of the current record (exports, spread, debug_last, the estimate and recovery's w_avg use it).  next: what
+ *     the next resampling update draws from the active records, by the usual rule with M = next (U_m = r + m / next); in parity
+ *     mode it takes 3 * next noise floats, and bl_pf_debug_resample reports next indices.
+ *   The count: after every resampling update, k = distinct bins of its parent poses (injected particles included), a bin being
+ *     (floor(x / bin_xy), floor(y / bin_xy), floor(theta / bin_theta)) in double from the float pose, each index clamped to
+ *     [-2^20, 2^20 - 1] (NaN: -2^20).  Exact for |x|, |y| < 2^20 bin_xy and |theta| < 2^20 bin_theta.
+ *   The bound: for k >= 2, b = 2 / (9 (k - 1)), c = 1 - b + sqrt(b) * z, n = ceil((k - 1) / (2 epsilon) * c * c * c) (plain double);
+ *     n = min_particles for k <= 1;  next = min(capacity, max(min_particles, n)).  k_sat = the smallest k in [2, capacity] with
+ *     n(k) >= capacity (capacity + 1 if none): the count stops there and reports min(k, k_sat).
+ *   Action-only and unmoved updates keep active, next and the count.  Enabling sets next = active; params == NULL turns it off and
+ *     the next resampling update draws the capacity.  The first resampling update after a count waits for its 8-byte read-back.
+ *   Errors: BL_ERR_ARG for bad parameters; BL_ERR_STATE while an update is pending and on a sharded filter (partial slice, composed
+ *     finish, external exchange buffers; bl_pf_shard_setup is refused while it is on).  Either way the filter is left as it was. */
+typedef struct bl_pf_adaptive_params_t {
+    int32_t min_particles;                /* 2 <= min_particles <= capacity */
+    int32_t pad;
+    double epsilon;                       /* KLD bound on the error, > 0 */
+    double z;                             /* upper standard-normal quantile, > 0 (2.326: the 0.99 quantile) */
+    double bin_xy, bin_theta;             /* histogram bin, metres / radians, > 0 */
+} bl_pf_adaptive_params_t;                /* 40 bytes */
+int bl_pf_set_adaptive(bl_pf* pf, const bl_pf_adaptive_params_t* params /* NULL: off */);
+typedef struct bl_pf_adaptive_state_t {
+    int32_t active;                       /* particles in the current record */
+    int32_t next;                         /* particles the next resampling update will draw */
+    uint32_t bins;                        /* k of the last count, saturated at k_sat; 0 if none yet */
+    uint32_t k_sat;                       /* 0 while adaptive mode is off */
+    uint64_t counts;                      /* resampling updates counted since enabling */
+} bl_pf_adaptive_state_t;                 /* 24 bytes */
+int bl_pf_adaptive_state(bl_pf* pf, bl_pf_adaptive_state_t* out);   /* synchronises; BL_ERR_STATE while an update is pending */
 /* Replace the whole posterior from a host AoS array of num_particles records (weights must be uniform or the
  * weight-unit integers in `units` given; units == NULL -> uniform). */
 int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, const uint32_t* units);
