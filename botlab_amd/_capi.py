@@ -64,7 +64,24 @@ class PfAdaptiveState(C.Structure):
     _fields_ = [("active", C.c_int32), ("next", C.c_int32), ("bins", C.c_uint32), ("k_sat", C.c_uint32), ("counts", C.c_uint64)]
 
 
+class ScanMatchParams(C.Structure):
+    """bl_scan_match_params_t: the window of a correlative scan match (28 bytes)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("ntheta", C.c_int32), ("dtheta", C.c_float), ("max_range", C.c_float),
+                ("min_score", C.c_int32), ("keep_volume", C.c_int32)]
+
+
+class ScanMatchResult(C.Structure):
+    """bl_scan_match_result_t: the best candidate of a correlative scan match (56 bytes)."""
+    _fields_ = [("pose", Pose), ("di", C.c_int32), ("dj", C.c_int32), ("dk", C.c_int32), ("score", C.c_int32),
+                ("score_centre", C.c_int32), ("ties", C.c_int32), ("rays_used", C.c_int32), ("accepted", C.c_int32)]
+
+    def __repr__(self):
+        return (f"ScanMatchResult(pose={self.pose!r}, di={self.di}, dj={self.dj}, dk={self.dk}, score={self.score}, "
+                f"score_centre={self.score_centre}, ties={self.ties}, rays_used={self.rays_used}, accepted={self.accepted})")
+
+
 assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56 and C.sizeof(PfSpread) == 80
+assert C.sizeof(ScanMatchParams) == 28 and C.sizeof(ScanMatchResult) == 56
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
 assert C.sizeof(PfAdaptiveParams) == 40 and C.sizeof(PfAdaptiveState) == 24
 
@@ -210,6 +227,11 @@ SIGNATURES = {
     "bl_frontiers_stats": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
     "bl_frontiers_debug_sweep_kernel": (C.c_int, [_vp]),
     "bl_frontiers_destroy": (None, [_vp]),
+    "bl_scanmatch_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_scanmatch_destroy": (None, [_vp]),
+    "bl_scanmatch_match": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _P(ScanMatchParams), _P(ScanMatchResult)]),
+    "bl_scanmatch_volume": (C.c_int, [_vp, _vp]),
+    "bl_scanmatch_debug_path": (C.c_int, [_vp]),
     "bl_lcm_fingerprint": (C.c_uint64, [C.c_int]),
     "bl_lcm_encode_pose": (C.c_int64, [C.c_int, _P(Pose), _vp, C.c_int64]),
     "bl_lcm_encode_lidar": (C.c_int64, [_P(Lidar), _vp, _vp, C.c_int64]),

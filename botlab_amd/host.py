@@ -445,6 +445,49 @@ class ParticleFilter:
             self.h = None
 
 
+class ScanMatcher:
+    """Correlative scan matcher (bl_scanmatch_*, include/botlab_hip.h): the pose of a scan against the map from a bounded window of
+    whole-cell shifts and heading steps around a centre pose, without odometry.  Off the filter's path: it reads the map only."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_scanmatch_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        self._shape = None
+
+    def match(self, scan, centre, grid, nx=4, ny=4, ntheta=12, dtheta=math.radians(0.5), max_range=8.0, min_score=0,
+              keep_volume=False):
+        """The best (di, dj, dk) of the window as a _capi.ScanMatchResult (pose, di, dj, dk, score, score_centre, ties, rays_used,
+        accepted)."""
+        ls = scan.as_c()
+        params = _capi.ScanMatchParams(int(nx), int(ny), int(ntheta), float(np.float32(dtheta)), float(np.float32(max_range)),
+                                       int(min_score), 1 if keep_volume else 0)
+        res = _capi.ScanMatchResult()
+        self._shape = None                 # a refused match keeps no volume either (the library forgets it as well)
+        check(self.ctx.lib.bl_scanmatch_match(self.h, grid.h, C.byref(ls), C.byref(centre), C.byref(params), C.byref(res)))
+        if keep_volume:
+            self._shape = (2 * int(ntheta) + 1, 2 * int(ny) + 1, 2 * int(nx) + 1)
+        return res
+
+    def volume(self):
+        """Scores [dk + ntheta][dj + ny][di + nx] of the last match (int32); it must have been run with keep_volume=True."""
+        if self._shape is None:
+            raise _capi.BotlabHipError("ScanMatcher.volume: the last match did not keep its score volume (status 4)")
+        out = np.empty(self._shape, dtype=np.int32)
+        check(self.ctx.lib.bl_scanmatch_volume(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def debugPath(self):
+        """0: the last match staged its map window in LDS; 1: it read the grid directly; -1: no match yet."""
+        return int(self.ctx.lib.bl_scanmatch_debug_path(self.h))
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_scanmatch_destroy(self.h)
+            self.h = None
+
+
 class ObstacleDistanceGrid:
     """ObstacleDistanceGrid().setDistances(map); operator()(x, y) (obstacle_distance_grid.hpp:28-96)."""
 

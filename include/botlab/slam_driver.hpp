@@ -20,11 +20,13 @@
 #include <cstdint>
 #include <functional>
 #include <iostream>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "botlab_dropin.hpp"
+#include "scan_matcher.hpp"
 
 namespace botlab_hip {
 
@@ -327,6 +329,18 @@ public:
     bool adaptiveParticlesActive() const { return adaptiveOn_; }
     bl_pf_adaptive_state_t adaptiveState() const { return pf_.adaptiveState(); }
 
+    // (extension) Correlative scan matching (ScanMatcherT, scan_matcher.hpp): the pose the filter is given as its odometry comes from
+    // the scan and the map instead of from the encoders alone.  Every iteration of a mode that runs the filter (not mapping-only)
+    // forms a centre -- the last corrected pose composed with the odometry's motion since the last scan (none, if no new odometry
+    // arrived) --, matches the scan against the map as it stands around it, and hands the corrected pose to updateFilter /
+    // updateFilterActionOnly where the odometry pose went.  A match that is not accepted passes the centre on: dead reckoning from
+    // the last corrected pose, which is what an empty map at start-up gives.  The first centre is the start pose.  Every iteration
+    // is then the call-by-call updateFilter.  Not combined with global localization (no start pose to chain from: matching stays
+    // off there).  Off by default, and with it off nothing the driver does changes; set before the first iteration.
+    void setScanMatching(bool on, const bl_scan_match_params_t& p) { matching_ = on; matchParams_ = p; }
+    const bl_scan_match_result_t& lastScanMatch() const { return lastMatch_; }
+    int scanMatchCount() const { return matches_; }
+
     // The oldest queued scan can be processed once the pose source covers the time of its first ray (slam.cpp:163-188).
     bool isReadyToUpdate() const
     {
@@ -346,6 +360,7 @@ public:
             std::cerr << "OccupancyGridSLAM: scan with only " << scan_.num_ranges << " ranges skipped\n";
             return;
         }
+        if (scanMatching()) correctOdometry();
         if (globalSearching()) {                        // global localization, not converged yet: filter only, the map is left alone
             before_ = now_;
             now_ = pf_.updateFilter(odomAtScan_, scan_, grid_);
@@ -359,7 +374,7 @@ public:
         }
         if (kidnapOn_) {                                // recovery on: the map only from an update that did not inject
             before_ = now_;
-            now_ = pf_.updateFilter(odomAtScan_, scan_, grid_);
+            now_ = pf_.updateFilter(filterOdometry(), scan_, grid_);
             announce();
             if (pf_.recoveryState().p_inject > 0.0) ++heldMaps_;
             else extendMap(false);
@@ -405,6 +420,40 @@ private:
     bool kidnap_ = false, kidnapOn_ = false;     // kidnapped-robot recovery: switch, turned on
     int heldMaps_ = 0;
     bool adaptive_ = false, adaptiveOn_ = false; // adaptive particle count: switch, turned on
+
+    // correlative scan matching: switch and window; the matcher (made on first use); the pose last handed to the filter and the
+    // odometry it was formed at; the last match
+    bool matching_ = false;
+    bl_scan_match_params_t matchParams_ = default_scan_match_params();
+    std::unique_ptr<ScanMatcherT<Pose, Lidar> > matcher_;
+    bool matchStarted_ = false;
+    Pose corrected_, odomAtMatch_;
+    bl_scan_match_result_t lastMatch_ = bl_scan_match_result_t();
+    int matches_ = 0;
+
+    bool scanMatching() const { return matching_ && !global_ && !how_.posesGiven; }
+    const Pose& filterOdometry() const { return scanMatching() ? corrected_ : odomAtScan_; }
+
+    // The centre of this iteration's match and the match itself.  The odometry's motion since the last match, taken in the odometry
+    // frame, is replayed from the last corrected pose: rotated by the difference of the two headings (double arithmetic on the float
+    // members, narrowed once).  Odometry that did not move gives the last corrected pose itself.
+    void correctOdometry()
+    {
+        if (!matcher_) matcher_.reset(new ScanMatcherT<Pose, Lidar>());
+        if (!matchStarted_) { corrected_ = before_; odomAtMatch_ = odomAtScan_; matchStarted_ = true; }
+        const double dx = static_cast<double>(odomAtScan_.x) - static_cast<double>(odomAtMatch_.x);
+        const double dy = static_cast<double>(odomAtScan_.y) - static_cast<double>(odomAtMatch_.y);
+        const double dth = static_cast<double>(odomAtScan_.theta) - static_cast<double>(odomAtMatch_.theta);
+        const double rot = static_cast<double>(corrected_.theta) - static_cast<double>(odomAtMatch_.theta);
+        const double c = std::cos(rot), s = std::sin(rot);
+        Pose centre = slam_detail::pose_of<Pose>(odomAtScan_.utime, static_cast<float>(corrected_.x + (c * dx - s * dy)),
+                                                 static_cast<float>(corrected_.y + (s * dx + c * dy)),
+                                                 slam_detail::wrap_pi(static_cast<float>(corrected_.theta + dth)));
+        lastMatch_ = matcher_->match(scan_, centre, grid_, matchParams_);
+        ++matches_;
+        corrected_ = slam_detail::pose_of<Pose>(odomAtScan_.utime, lastMatch_.pose.x, lastMatch_.pose.y, lastMatch_.pose.theta);
+        odomAtMatch_ = odomAtScan_;
+    }
 
     void startRecovery()
     {
@@ -452,12 +501,12 @@ private:
     {
         if (how_.posesGiven || !how_.mapKnown) return false;
         before_ = now_;
-        if (!how_.odometryOnly && fused_ && !adaptiveOn_) {
+        if (!how_.odometryOnly && fused_ && !adaptiveOn_ && !scanMatching()) {
             pf_.updateFilterBegin(odomAtScan_, scan_, grid_);
             if (!waiting_.empty()) prefetch_scan(waiting_.front());      // the next scan is already queued: it rides along
             return true;
         }
-        now_ = how_.odometryOnly ? pf_.updateFilterActionOnly(odomAtScan_) : pf_.updateFilter(odomAtScan_, scan_, grid_);
+        now_ = how_.odometryOnly ? pf_.updateFilterActionOnly(filterOdometry()) : pf_.updateFilter(filterOdometry(), scan_, grid_);
         announce();
         return false;
     }

@@ -288,6 +288,55 @@ int bl_debug_trig_addition_probe(bl_ctx* ctx, uint64_t pairs, uint32_t seed, flo
                                  uint64_t* pairs_checked);
 int bl_pf_debug_last(bl_pf* pf, int32_t* resample_idx, int32_t* likelihood_half_units);
 
+/* ------------------------------------------------------------------ correlative scan matching (no reference counterpart)
+ * The pose of a scan against the map from the scan alone (Olson, "Real-time correlative scan matching", ICRA 2009, in its
+ * exhaustive single-resolution form): the scan is rasterised at every candidate heading, slid over the map in whole cells, and
+ * the best-scoring (di, dj, dk) of a bounded window around a centre pose c wins.  Every score is an exact integer.
+ *   Valid rays: range > 0.15f (moving_laser_scan.cpp:24) and range < max_range; at most 4096 of them.
+ *   Heading dk: theta_k = c.theta + (float)dk * dtheta in float; ray angle a = wrap_to_pi(theta_k - thetas[r])
+ *     (moving_laser_scan.cpp:33); cosf / sinf the C library's.
+ *   Endpoint cell of ray r at heading dk, SensorModel::scoreRay's float arithmetic and truncating conversion
+ *     (sensor_model.cpp:28-40) with s = global_position_to_grid_position(c):
+ *       ex = (int)(range * cosf(a) * cellsPerMeter + s.x),  ey = (int)(range * sinf(a) * cellsPerMeter + s.y);
+ *     a float sum that is NaN or at least 2^30 in magnitude has no cell (the ray counts nothing).
+ *   Score: score(di, dj, dk) = sum over the valid rays of max(0, L[ey + dj][ex + di]), L the int8 log-odds, a cell outside the
+ *     grid counting 0: translation is a whole-cell shift of the rasterised scan, not a re-rounding per shift.
+ *   Best candidate: the highest score; ties go to the smallest di*di + dj*dj, then the smallest |dk|, then the smallest dk, dj,
+ *     di -- one 64-bit key per candidate, so the maximum does not depend on the order of reduction.  An empty or all-free map
+ *     returns the centre.
+ *   Not in it: multi-resolution pruning, sub-cell refinement, a covariance estimate, a motion prior. */
+typedef struct bl_scan_match_params_t {
+    int32_t nx, ny;          /* half window in cells: shifts di in [-nx, nx], dj in [-ny, ny];   0 <= nx, ny <= 64   */
+    int32_t ntheta;          /* half window in heading steps: dk in [-ntheta, ntheta];           0 <= ntheta <= 180  */
+    float   dtheta;          /* heading step in radians, > 0                                                          */
+    float   max_range;       /* rays with range >= max_range are skipped (no return)                                  */
+    int32_t min_score;       /* a best score below this is "no match": the pose is the centre, accepted = 0           */
+    int32_t keep_volume;     /* != 0: keep the whole score volume on the device for bl_scanmatch_volume (tests, tools)*/
+} bl_scan_match_params_t;    /* 28 bytes */
+typedef struct bl_scan_match_result_t {
+    bl_pose_xyt_t pose;      /* accepted: x = (float)((double)c.x + di * (double)meters_per_cell), y likewise with dj,
+                                theta = wrap_to_pi(theta_dk); otherwise the centre's x, y, theta as given; utime = the scan's */
+    int32_t di, dj, dk;      /* the best candidate (also when it is not accepted) */
+    int32_t score;           /* of the best candidate */
+    int32_t score_centre;    /* of (0, 0, 0): what the match gained */
+    int32_t ties;            /* candidates sharing the best score (1 = unique) */
+    int32_t rays_used;
+    int32_t accepted;        /* score >= min_score */
+} bl_scan_match_result_t;    /* 56 bytes */
+typedef struct bl_scanmatch bl_scanmatch;
+int bl_scanmatch_create(bl_ctx* ctx, bl_scanmatch** out);           /* buffers grow on demand up to the limits above */
+void bl_scanmatch_destroy(bl_scanmatch* sm);
+/* One stream-ordered sequence on the ctx stream (the map must belong to the same ctx); synchronises to hand the result back.
+ * BL_ERR_ARG: a limit above exceeded, dtheta <= 0 (or NaN), a null pointer, more than 4096 valid rays. */
+int bl_scanmatch_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* centre,
+                       const bl_scan_match_params_t* params, bl_scan_match_result_t* result);
+/* scores[2 ntheta + 1][2 ny + 1][2 nx + 1] of the last match; BL_ERR_STATE if it was not kept -- a call of bl_scanmatch_match that
+ * was refused counts as the last match and keeps nothing (synchronises) */
+int bl_scanmatch_volume(bl_scanmatch* sm, int32_t* scores);
+/* diagnostic: which scoring path the last match took -- 0 the map window staged in LDS, 1 the grid read directly (the window
+ * the scan's endpoints and the shifts span does not fit in LDS); -1 before the first match */
+int bl_scanmatch_debug_path(const bl_scanmatch* sm);
+
 /* ------------------------------------------------------------------ ObstacleDistanceGrid  (src/planning/obstacle_distance_grid.hpp:28-96) */
 int bl_dist_create(bl_ctx* ctx, bl_dist** out);
 void bl_dist_destroy(bl_dist* d);
