@@ -17,6 +17,12 @@
 // weight c_i satisfies U_m <= c_i, U_m = r + m/N.  Here: first i with U_m * S <= prefix[i] (double product against an
 // exact integer), i clamped to N-1.  The reference accumulates c_i sequentially in double; the two rules can differ
 // only when U_m lies within rounding distance of a partial sum (DESIGN.md "Resampling").
+//
+// Removed, so that nobody looks for them: the 256- and 1024-thread instantiations of k_mcl_main (nothing launched them: one size,
+// MCL_BLOCK); the v_sin_f32 / v_cos_f32 form of the fast ray loop with its probe (measured slower than the addition theorems, never
+// selected); the switches for LDS-less, unpacked and unbalanced launches, a fixed split, the round divisor, a skipped search, the
+// one-wave strict chain and the one-wave walk of an overflowed list (never set by a test, a tool or the bench -- the code each
+// forced is still reached by its natural condition).  The switches that remain: mcl_switches below.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,7 +34,9 @@
 #include "bl_mcl_finish.h"
 
 #define MCL_LDS_RAYS 384                      // rays whose (range, theta, cos theta, sin theta) table is staged in LDS at a time (longer scans: several passes)
+#define MCL_BLOCK 512                         // threads of a k_mcl_main workgroup: within 3 % of the best of 256 / 512 / 1024 at 100k and 1M particles, 200x200
 #define MCL_MIN_BLOCKS 512                    // split rays over lanes until the launch has at least this many workgroups (2 per CU)
+#define MCL_ROUND_SHORT_DIV 128               // a round of the machine is counted 1/128 short of what the device holds: other streams' kernels occupy a few slots (pf_launch_main)
 #define MCL_WIN_SMALL_BYTES (64 * 1024)       // whole-grid staging budget (200x200 int8 framed = 41 KB -> three workgroups per CU)
 #define MCL_WIN_MAX 208                       // window side: 208^2 = 42 KB, three workgroups per CU like the whole-grid image of a 200x200 map
 #define MCL_WIN_MARGIN 24                     // cells added to the scan's reach on every side of the window for the spread of the cloud
@@ -37,6 +45,42 @@
 #define SCAN_TILE (SCAN_THREADS * SCAN_ITEMS)
 
 // pf_state: bl_mcl_finish.h
+
+// The switches that force another form of an update (tests, probes, A/B runs).  Read when a filter is created, so two filters of one
+// process may differ (the tests set them between two filters):
+//   BOTLAB_MCL_NO_FUSED_FINISH   the record-based finish (k_scan_tile_sums + k_mcl_finish) instead of the one fed by k_mcl_main's block
+//                                sums -- the finish every shard count shares (test_gpu_sharded_two_ranks.py, test_gpu_shard_host_cpp.py,
+//                                tests/tools/stream_kernels_probe.py)
+//   BOTLAB_MCL_NO_FRAMED         no zero-framed copy of a large grid: mode 0, unpacked scoring from the grid itself
+//                                (test_mcl_parity_large_grid_lds_window, test_large_grid_mirror_kept_current_by_map_updates)
+//   BOTLAB_MCL_NO_MIRROR_REUSE   the framed copy is made again in front of every update (test_large_grid_mirror_kept_current_by_map_updates)
+//   BOTLAB_MCL_NO_STAGE_DMA      whole-grid and window staging through registers instead of LDS-DMA (test_whole_grid_staging_forms_agree)
+//   BOTLAB_MCL_NO_STAGE_X4       whole-grid staging row by row from the grid instead of 16-byte pieces of the framed copy (the same test)
+//   BOTLAB_MCL_NO_WINDOW         large grids: every gather through L2 from the framed copy, mode 0 (test_mcl_parity_large_grid_lds_window)
+//   BOTLAB_MCL_WINDOW=cells      large grids: the window's side, up to 384 (the same test: a window most rays miss, one over the grid's edge)
+//   BOTLAB_MCL_NO_FAST_TRIG      exact sinf / cosf for every ray (test_fast_trig_on_and_off_give_identical_likelihoods)
+// Read elsewhere: BOTLAB_MCL_NO_WILD when a filter's buffers are allocated (no wild maps: the finish keeps to records, tables and replays;
+// tests/tools/est_small_probe.py), BOTLAB_NO_AUTO_STRICT once per process (pf_uni_mode), BOTLAB_SHARD_WAIT_MS, BOTLAB_FINISH_LOOKAHEAD
+// and BOTLAB_FINISH_STAMPS where they are used.
+struct mcl_switches {
+    bool no_fused_finish, no_framed, no_mirror_reuse, no_stage_dma, no_stage_x4, no_window, no_fast_trig;
+    int window;                   // window side in cells (0: from the scan's reach)
+};
+static mcl_switches mcl_switches_read()
+{
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    mcl_switches w;
+    w.no_fused_finish = set("BOTLAB_MCL_NO_FUSED_FINISH");
+    w.no_framed = set("BOTLAB_MCL_NO_FRAMED");
+    w.no_mirror_reuse = set("BOTLAB_MCL_NO_MIRROR_REUSE");
+    w.no_stage_dma = set("BOTLAB_MCL_NO_STAGE_DMA");
+    w.no_stage_x4 = set("BOTLAB_MCL_NO_STAGE_X4");
+    w.no_window = set("BOTLAB_MCL_NO_WINDOW");
+    w.no_fast_trig = set("BOTLAB_MCL_NO_FAST_TRIG");
+    const char* win = getenv("BOTLAB_MCL_WINDOW");
+    w.window = win ? atoi(win) : 0;
+    return w;
+}
 
 struct bl_pf {
     bl_ctx* ctx;
@@ -57,14 +101,11 @@ struct bl_pf {
     pf_state* state;
     double* partials;         // [blocks][5]
     int partials_cap;
-    bool use_lds;
     int last_blocks, last_tile;   // launch shape of the last k_mcl_main
     int last_main_blocks, last_main_particles, last_tail_tile;
-    bool fused_finish, no_fused_finish, no_packed, no_balance, no_framed, no_window, no_fast_trig, no_mirror_reuse, no_stage_dma, no_stage_x4;
-    int window_override;          // window side in cells (0: from the scan's reach)
+    bool fused_finish;
+    mcl_switches sw;              // the forms the environment forced when the filter was created
     int cus;                      // compute units of the device
-    int split_log2_override;  // -1: automatic
-    int block_override;       // 0: automatic
     bool debug;               // record resample index / likelihood per particle (parity tests)
     bool strict;              // strict resampling: prefix[] is overwritten with the reference's rounded double cumulative after every finish
     void* strict_recs; double* strict_starts;     // ... by chunks side by side: a record and the true start per chunk of 128 particles
@@ -367,8 +408,6 @@ __device__ __forceinline__ void ray_cells_pk(float2_t start, float cpm, float ra
 // range * that is t in one multiplication where the reference has two.  The scaling's rounding is half an ulp of each of cp, sp:
 // <= 6e-8 (|cp cr| + |sp sr|) <= 6e-8 into the direction, together <= 8.8e-7 < MCL_TRIG_EPS; t' = fl(range * (cpm dir')) has ONE
 // rounding where t = fl(fl(range * dir) * cpm) has two, inside the 4u the second line below allows.  The probe measures this form.
-// The guard band below is the one the hardware-sine form was proven with (tests/tools/sincos_hw_probe.hip measured 8.81e-7 for it);
-// it is kept, so the exact path behind it is taken as often as before.
 // With dir' = dir + eta, |eta| <= eps, and u = 2^-24 the relative error of one float operation:
 //     |fl(range * dir') - fl(range * dir)|      <= range * (eps + 2u)
 //     |t' - t|, t = fl(fl(range * dir) * cpm)   <= range * cpm * (eps + 4u) (1 + 2u)
@@ -387,16 +426,11 @@ __device__ __forceinline__ void ray_cells_pk(float2_t start, float cpm, float ra
 // cells; everything downstream is integer.  The test itself (round 6): the distance of c to the nearest integer is 0.5 - |fract(c) - 0.5|,
 // exactly, so "both coordinates farther than B" is max(|fract - 0.5|) < 0.5 - B -- two v_fract, one packed add, one max per point;
 // the threshold 0.5 - B is formed with 1.2e-7 taken off (its two roundings are half an ulp of 0.5 each), which only widens the band.
-// MCL_TRIG_EPS: 5.5 % above the larger maximum measured for the hardware form (bl_debug_trig_probe, kept: BOTLAB_MCL_HW_TRIG=1 takes
-// that form), 13 % above the addition form's analytic bound and 45 % above its measured maximum; tests/test_gpu_trig_guard.py
-// asserts the measured maxima of both forms stay below it.
+// MCL_TRIG_EPS: 5.7 % above the analytic bound of the scaled addition form (8.8e-7, above) and 45 % above its measured maximum
+// (bl_debug_trig_addition_probe); tests/test_gpu_trig_guard.py asserts the bound and the measured maximum against this constant.
+// The value predates the addition form -- it was sized for a v_sin_f32 / v_cos_f32 form of the direction that measured slower and has
+// been removed -- and is kept as it is: the band, and with it how often the exact path is taken, follows from it.
 #define MCL_TRIG_EPS 9.3e-7f
-__device__ __forceinline__ void hw_sincos_unwrapped(float d, float* sn, float* cs)
-{
-    const float rev = d * 0.15915494309189535f;
-    asm("v_sin_f32 %0, %1" : "=v"(*sn) : "v"(rev));
-    asm("v_cos_f32 %0, %1" : "=v"(*cs) : "v"(rev));
-}
 // (range, theta, cos theta, sin theta): cosf / sinf as libm rounds them (bl_sincosf_cells: a double polynomial rounded once,
 // within 0.56 ulp -- a double sincos here cost the staging waves more than the transcendentals it replaces saved the ray loop)
 __device__ __forceinline__ float4 ray_table_entry(float range, float theta)
@@ -412,20 +446,12 @@ __device__ __forceinline__ float2_t trig_by_addition(float2_t pcs, float cr, flo
     const float2_t t = a * float2_t{sr, sr};
     return __builtin_elementwise_fma(pcs, float2_t{cr, cr}, t);           // (cp cr + sp sr, sp cr - cp sr)
 }
-// (p, r: the particle's and the ray's angle -- their difference is formed only where it is used, the hardware form and the exact path;
-// hw: wave-uniform, a kernel argument)
-template <bool HW>
+// (p, r: the particle's and the ray's angle -- their difference is formed only where it is used, the exact path)
 __device__ __forceinline__ void ray_cells_fast(float2_t start, float cpm, float range, float p, float r, float2_t pcs, float cr, float sr,
                                                float k1, float kh2, short2_t& E, short2_t& X)
 {
-    float2_t dc;                                             // cpm * (cos, sin)(p - r)
-    if (HW) {                                                // (BOTLAB_MCL_HW_TRIG: a loop of its own, chosen outside it; the marker
-        float sn, cs;                                        // keeps the optimiser from folding the two loops back into one with this
-        asm volatile("; hardware sine / cosine");            // branch inside)
-        hw_sincos_unwrapped(p - r, &sn, &cs);
-        dc = float2_t{cs, sn} * cpm;
-    } else
-        dc = trig_by_addition(pcs, cr, sr);                  // pcs = cpm (cos p, sin p): the direction comes out in cells per metre ("pcs scaled" above)
+    // cpm * (cos, sin)(p - r); pcs = cpm (cos p, sin p): the direction comes out in cells per metre ("pcs scaled" above)
+    const float2_t dc = trig_by_addition(pcs, cr, sr);
     // the two points by two packed multiply-adds (e = range dc + start, x = range dc + e) where the reference has a product, its
     // double and two additions: see "x'' = " above -- one rounding per point instead of two or three, inside the same bounds
     const float2_t rr = {range, range};
@@ -559,8 +585,8 @@ struct mcl_args {
     int split_log2;               // each particle's rays are spread over 2^split_log2 adjacent lanes
     int pk_ok;                    // grid and scan admit the packed 16-bit scoring path (see score_ray_pk)
     int theta_simple;             // every theta of the scan lies in [0, 6.2831] (see wrap_to_pi_cells)
-    int fast_trig;                // ray directions without the exact sinf / cosf, a guard band and the exact path behind it (ray_cells_fast):
-                                  // 1 by the addition theorems, 2 by the hardware sine / cosine, 0 off
+    int fast_trig;                // ray directions by the addition theorems instead of the exact sinf / cosf, a guard band and the exact path
+                                  // behind it (ray_cells_fast)
     int stage_dma;                // whole-grid staging by LDS-DMA (rows of whole dwords, at most 64 of them)
     float max_range_cells;        // longest kept ray in cells
     int main_blocks, main_particles;   // region 1: main_blocks workgroups cover particles [0, main_particles) of the shard
@@ -651,24 +677,24 @@ __device__ __forceinline__ void philox_normals3(uint32_t m, uint32_t step, uint3
 
 // The same loops with the two cells from ray_cells_fast (theta_simple scans only): the direction by the addition theorems from
 // the particle's (cos, sin) pair pcs_ and the table's.  Rays [LO, HI) of the chunk (LO a multiple of the split).
-#define MCL_RAY_LOOP_FAST_RANGE(PM, LO, HI, HW)                                         \
+#define MCL_RAY_LOOP_FAST_RANGE(PM, LO, HI)                                             \
     do {                                                                                \
         const int rounds_ = ((HI) - (LO)) >> sl2;                                       \
         int off_ = ((LO) + sub) * 16;                                                   \
         for (int k_ = 0; k_ < rounds_; ++k_, off_ += split * 16) {                      \
             const float4 rt = *(const float4*)((const char*)s_ray + off_);              \
             short2_t E_, X_;                                                            \
-            ray_cells_fast<HW>(start, a.frame.cpm, rt.x, pth_r, rt.y, pcs_, rt.z, rt.w, trig_k1, trig_kh2, E_, X_);   \
+            ray_cells_fast(start, a.frame.cpm, rt.x, pth_r, rt.y, pcs_, rt.z, rt.w, trig_k1, trig_kh2, E_, X_);   \
             acc += score_cells_pk(PM, S, E_, X_);                                       \
         }                                                                               \
         if ((off_ >> 4) < (HI)) {                                                       \
             const float4 rt = *(const float4*)((const char*)s_ray + off_);              \
             short2_t E_, X_;                                                            \
-            ray_cells_fast<HW>(start, a.frame.cpm, rt.x, pth_r, rt.y, pcs_, rt.z, rt.w, trig_k1, trig_kh2, E_, X_);   \
+            ray_cells_fast(start, a.frame.cpm, rt.x, pth_r, rt.y, pcs_, rt.z, rt.w, trig_k1, trig_kh2, E_, X_);   \
             acc += score_cells_pk(PM, S, E_, X_);                                       \
         }                                                                               \
     } while (0)
-#define MCL_RAY_LOOP_FAST(PM) do { if (hw_trig_) MCL_RAY_LOOP_FAST_RANGE(PM, 0, cnt, true); else MCL_RAY_LOOP_FAST_RANGE(PM, 0, cnt, false); } while (0)
+#define MCL_RAY_LOOP_FAST(PM) MCL_RAY_LOOP_FAST_RANGE(PM, 0, cnt)
 
 // ---- resampling search, first part: a wave narrows the range its lanes have to bisect -----------------------------------
 // The lanes of a wave resample consecutive particles, so their targets T ascend and every lane's source index lies
@@ -804,12 +830,12 @@ __device__ __forceinline__ void stage_rows(int* s_map32, int rows, int wq, int q
 
 // One lane group per output particle m of the shard: low-variance resample (gather), ActionModel::applyAction,
 // SensorModel::likelihood, weight units, and the block's partial sums for normalisation + pose estimate.
-// Launch shape: BLOCK threads; a particle occupies `split` = 2^split_log2 adjacent lanes of one wave (a whole wave in the
+// Launch shape: MCL_BLOCK threads; a particle occupies `split` = 2^split_log2 adjacent lanes of one wave (a whole wave in the
 // second region of the launch), lane `sub` of them taking rays sub, sub + split, ...  (the host picks split so that the
 // launch has >= ~512 workgroups: at 100k particles a one-thread-per-particle launch is 6 waves per CU and latency-bound on
 // its serial 290-ray loop).
 // Shared prologue (split >= 4, no pose interpolation): the per-particle work -- resampling bisection, gather, Philox noise,
-// action model -- is done ONCE per particle by the first P = BLOCK / split threads of the workgroup (one particle per lane)
+// action model -- is done ONCE per particle by the first P = MCL_BLOCK / split threads of the workgroup (one particle per lane)
 // while the other waves stage the ray table and the map; the result reaches the particle's lanes through a small LDS table,
 // and the same P threads write the particle and feed the partial sums after the ray loop.  (With every lane of a group
 // repeating the prologue, as the first form of this kernel did, a wave spent a quarter of its instructions outside the ray
@@ -840,20 +866,20 @@ extern "C" int bl_debug_mcl_stamps(unsigned long long* out, int n)
 
 // REC: kidnapped-robot recovery -- some resampled particles are replaced by uniform samples over the recovery list (bl_pf_set_recovery).
 // A template parameter so that the default instantiations compile exactly as without it.
-template <int INTERP, int BLOCK, int MAP_MODE, bool REC = false>
-__global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
+template <int INTERP, int MAP_MODE, bool REC = false>
+__global__ __launch_bounds__(MCL_BLOCK) void k_mcl_main(mcl_args a)
 {
     extern __shared__ __align__(16) signed char s_dyn[];
-    __shared__ double s_part[BLOCK / 64][5];
+    __shared__ double s_part[MCL_BLOCK / 64][5];
     __shared__ map_window s_win;
     // (range, theta, cos theta, sin theta) of the kept rays, MCL_LDS_RAYS at a time: one ds_read_b128 per ray.  (A table that is
     // read from LDS or, past its size, from global memory makes every access a FLAT load behind two scalar branches.)  The cosine
     // and sine are those of the ray's own angle, formed in double and rounded once (ray_table_entry): the fast ray loop gets the
     // direction of pose.theta - theta from them by the addition theorems instead of two transcendentals per particle-ray.
     __shared__ float4 s_ray[MCL_LDS_RAYS];
-    __shared__ float4 s_pp[BLOCK / 4];                      // shared prologue: (theta, start x, start y, -) per particle
-    __shared__ float2 s_pcs[BLOCK / 4];                     // ... and (cos theta, sin theta), formed in double and rounded once
-    __shared__ int s_acc[BLOCK / 4];                        // shared prologue: half-unit score per particle
+    __shared__ float4 s_pp[MCL_BLOCK / 4];                      // shared prologue: (theta, start x, start y, -) per particle
+    __shared__ float2 s_pcs[MCL_BLOCK / 4];                     // ... and (cos theta, sin theta), formed in double and rounded once
+    __shared__ int s_acc[MCL_BLOCK / 4];                        // shared prologue: half-unit score per particle
     const lds_i8_t* s_map = (const lds_i8_t*)s_dyn;
     int* s_map32 = (int*)s_dyn;
     map_window win = {0, 0, 0, 0, 0};
@@ -861,7 +887,7 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     MCL_STAMP(0);
 
-    // Two regions in one launch (see "Whole rounds" in pf_launch_main): workgroups [0, main_blocks) take BLOCK >> split_log2
+    // Two regions in one launch (see "Whole rounds" in pf_launch_main): workgroups [0, main_blocks) take MCL_BLOCK >> split_log2
     // particles each, 2^split_log2 lanes per particle; the workgroups after them take the remaining particles one per
     // wave (64 lanes over the rays), so that the last partial round of the machine lasts a tenth of a full one.
     // composed shard whose exchange gave up (k_shard_wait): the other ranks' records and prefix are not what this update needs
@@ -869,15 +895,15 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
     const bool tail = (int)blockIdx.x >= a.main_blocks;
     const int sl2 = tail ? 6 : a.split_log2;
     const int split = 1 << sl2;
-    const int P = BLOCK >> sl2;                                                     // particles of this workgroup
-    const int jbase = tail ? a.main_particles + ((int)blockIdx.x - a.main_blocks) * (BLOCK >> 6) : (int)blockIdx.x * P;
+    const int P = MCL_BLOCK >> sl2;                                                 // particles of this workgroup
+    const int jbase = tail ? a.main_particles + ((int)blockIdx.x - a.main_blocks) * (MCL_BLOCK >> 6) : (int)blockIdx.x * P;
     const int jl = tid >> sl2;
     const int j = jbase + jl;
     const int sub = tid & (split - 1);
     const bool active = j < a.n_local && (tail || j < a.main_particles);
     const bool shared_pro = !INTERP && sl2 >= 2;                                    // workgroup-uniform
     const int pw = shared_pro ? (P + 63) >> 6 : 0;                                  // waves that run the prologue only
-    const int n_sw = BLOCK / 64 - pw;                                               // waves that stage
+    const int n_sw = MCL_BLOCK / 64 - pw;                                           // waves that stage
     // the particle whose prologue and epilogue this thread runs
     const int jp = shared_pro ? jbase + tid : j;
     const bool pro_active = shared_pro ? (tid < P && jp < a.n_local && (tail || jp < a.main_particles)) : active;
@@ -992,7 +1018,7 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
 #endif
     // ---- phase 1b: per-particle prologue
     double t_units = 0, t_x = 0, t_y = 0, t_s = 0, t_c = 0;
-    float2 pcs_own = make_float2(2.0f, 0.0f);               // (2, -): "take the hardware sine / cosine" (a.fast_trig == 2)
+    float2 pcs_own = make_float2(0.0f, 0.0f);               // cpm (cos, sin) of the heading: read by the fast ray loop only
     float pth_sin = 0.0f, pth_cos = 1.0f;
     int i = mp;
     bool injected = false;                                  // (REC) this particle's prior is a uniform sample
@@ -1055,7 +1081,7 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
         pth = bl_wrap_to_pi(s.z + n1 + n3);
         if (a.cells) bl_global_to_grid(px, py, a.frame, &sx0, &sy0);
         bl_sincosf(pth, &pth_sin, &pth_cos);                 // (the estimate's partial sums need them anyway: particle_filter.cpp:151-152)
-        if (a.cells && a.fast_trig == 1) pcs_own = make_float2(a.frame.cpm * pth_cos, a.frame.cpm * pth_sin);    // ("pcs scaled", ray_cells_fast)
+        if (a.cells && a.fast_trig) pcs_own = make_float2(a.frame.cpm * pth_cos, a.frame.cpm * pth_sin);    // ("pcs scaled", ray_cells_fast)
     }
     if (REC) {
         // the injections of this wave, one atomic: each particle once (without the shared prologue every lane of its group ran it)
@@ -1077,12 +1103,11 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
     if (shared_pro) { const float4 e = s_pp[jl]; r_pth = e.x; r_sx0 = e.y; r_sy0 = e.z; trig_k2 = e.w; r_pcs = s_pcs[jl]; }
     const float2_t pcs_ = {r_pcs.x, r_pcs.y};
     // the far point's band per metre of range, in cells: 2 x 1.02 cpm (eps + 4u) for the direction and the products (4u = 2^-22; the
-    // fused form needs 2u, the hardware-trig form 3u), + 3.06 u x 2 cpm for the roundings at coordinates that a ray moves by up to 2 cpm
+    // fused form needs 2u), + 3.06 u x 2 cpm for the roundings at coordinates that a ray moves by up to 2 cpm
     // cells per metre (6.12 u = 3.648e-7)
     const float trig_k1 = a.frame.cpm * (2.04f * (MCL_TRIG_EPS + 2.3842e-7f) + 3.648e-7f);
     const float trig_kh2 = 0.5f - 1.5f * trig_k2 - 1.2e-7f;                        // (ray_cells_fast: the band as a threshold on |fract - 0.5|; the far point's, formed as e + t)
     const bool fast_trig = a.fast_trig != 0;                                       // wave-uniform
-    const bool hw_trig_ = a.fast_trig == 2;
     const int isx0 = (int)r_sx0, isy0 = (int)r_sy0;
 
     // ---- SensorModel::likelihood (sensor_model.cpp:14-25) over MovingLaserScan(scan, parent_pose, pose)
@@ -1097,7 +1122,7 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
             const int cnt = a.R - base < MCL_LDS_RAYS ? a.R - base : MCL_LDS_RAYS;
             if (base > 0) {
                 __syncthreads();                                    // every lane is done with the previous chunk
-                for (int n = tid; n < cnt; n += BLOCK) s_ray[n] = ray_table_entry(a.ranges[base + n], a.thetas[base + n]);
+                for (int n = tid; n < cnt; n += MCL_BLOCK) s_ray[n] = ray_table_entry(a.ranges[base + n], a.thetas[base + n]);
                 __syncthreads();
             }
             if (!active) continue;
@@ -1172,7 +1197,7 @@ __global__ __launch_bounds__(BLOCK) void k_mcl_main(mcl_args a)
         t_c = t_units * (double)cth;
     }
     // the workgroup's five sums: lanes in a wave by shuffles, then the waves that hold particles in order
-    const int nred = shared_pro ? pw : BLOCK / 64;
+    const int nred = shared_pro ? pw : MCL_BLOCK / 64;
     if (wave < nred) {
         t_units = wave_sum(t_units); t_x = wave_sum(t_x); t_y = wave_sum(t_y); t_s = wave_sum(t_s); t_c = wave_sum(t_c);
         if (lane == 0) { s_part[wave][0] = t_units; s_part[wave][1] = t_x; s_part[wave][2] = t_y; s_part[wave][3] = t_s; s_part[wave][4] = t_c; }
@@ -1641,15 +1666,14 @@ static int pf_alloc(bl_pf* pf)
     BL_HIP(hipMalloc((void**)&pf->prefix, N * sizeof(unsigned long long)));
     BL_HIP(hipMalloc((void**)&pf->parent, n * sizeof(float4)));
     BL_HIP(hipMalloc((void**)&pf->state, sizeof(pf_state)));
-    int blocks = (int)((n * 64 + 255) / 256) + 1;          // worst case: every particle spread over a whole wave, 256-thread blocks
+    // worst case: every particle spread over a whole wave (MCL_BLOCK / 64 per workgroup in either region; the tail region rounds up once more)
+    int blocks = (int)((n * 64 + MCL_BLOCK - 1) / MCL_BLOCK) + 1;
     BL_HIP(hipMalloc((void**)&pf->partials, (size_t)blocks * 5 * sizeof(double)));
     pf->partials_cap = blocks;
     static bool attr_set = false;
     if (!attr_set) {
         const int big = 384 * 384;                     // BOTLAB_MCL_WINDOW may ask for up to 384 cells a side
-        BL_HIP(hipFuncSetAttribute((const void*)k_mcl_main<0, 256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        BL_HIP(hipFuncSetAttribute((const void*)k_mcl_main<0, 512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        BL_HIP(hipFuncSetAttribute((const void*)k_mcl_main<0, 1024, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+        BL_HIP(hipFuncSetAttribute((const void*)k_mcl_main<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
         BL_HIP(hipFuncSetAttribute((const void*)k_mcl_finish, hipFuncAttributeMaxDynamicSharedMemorySize, MCLF_LDS_BYTES));
         attr_set = true;
     }
@@ -1687,22 +1711,8 @@ extern "C" int bl_pf_create(bl_ctx* ctx, int num_particles, int shard_lo, int sh
         pf->w_floor = 0.001 / wsum;
     }
     pf->noise_seed = 0x243F6A8885A308D3ull;
-    pf->use_lds = getenv("BOTLAB_MCL_NO_LDS") == nullptr;
-    pf->no_fused_finish = getenv("BOTLAB_MCL_NO_FUSED_FINISH") != nullptr;
-    pf->no_packed = getenv("BOTLAB_MCL_NO_PACKED") != nullptr;
-    pf->no_balance = getenv("BOTLAB_MCL_NO_BALANCE") != nullptr;
-    pf->no_framed = getenv("BOTLAB_MCL_NO_FRAMED") != nullptr;
-    pf->no_mirror_reuse = getenv("BOTLAB_MCL_NO_MIRROR_REUSE") != nullptr;
-    pf->no_stage_dma = getenv("BOTLAB_MCL_NO_STAGE_DMA") != nullptr;
-    pf->no_stage_x4 = getenv("BOTLAB_MCL_NO_STAGE_X4") != nullptr;
-    pf->no_window = getenv("BOTLAB_MCL_NO_WINDOW") != nullptr;
-    pf->no_fast_trig = getenv("BOTLAB_MCL_NO_FAST_TRIG") != nullptr;
-    pf->window_override = getenv("BOTLAB_MCL_WINDOW") ? atoi(getenv("BOTLAB_MCL_WINDOW")) : 0;
+    pf->sw = mcl_switches_read();
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess) pf->cus = cus; }
-    pf->split_log2_override = getenv("BOTLAB_MCL_SPLIT_LOG2") ? atoi(getenv("BOTLAB_MCL_SPLIT_LOG2")) : -1;
-    if (pf->split_log2_override > 6) pf->split_log2_override = 6;
-    pf->block_override = getenv("BOTLAB_MCL_BLOCK") ? atoi(getenv("BOTLAB_MCL_BLOCK")) : 0;
-    if (pf->block_override != 0 && pf->block_override != 256 && pf->block_override != 512 && pf->block_override != 1024) pf->block_override = 0;
     *out = pf;
     return BL_OK;
 }
@@ -1765,9 +1775,8 @@ static void pf_strict_cumulative(bl_pf* pf, int which)
     // the runs of the reference's cumulative and k_mcl_main searches those, uni_seg in bl_mcl_finish.h)
     pf->prefix_is_strict = pf->strict;
     if (!pf->prefix_is_strict) return;
-    static const bool one_wave = getenv("BOTLAB_STRICT_ONE_WAVE") != nullptr;        // tests, A/B runs
     const int nchunks = (pf->N + 127) / 128;
-    if (pf->N >= STRICT_PAR_MIN && !one_wave) {
+    if (pf->N >= STRICT_PAR_MIN) {
         if (!pf->strict_recs) {
             const int cap_chunks = (pf->cap + 127) / 128;         // (sized for the capacity: an adaptive set changes N)
             if (hipMalloc((void**)&pf->strict_recs, (size_t)cap_chunks * sizeof(strict_rec)) != hipSuccess) pf->strict_recs = nullptr;
@@ -1813,7 +1822,6 @@ static int pf_finish_fill(bl_pf* pf, mcl_finish_args* f)
     f->uni_mode = pf_uni_mode(pf, false);
     f->w_floor = pf_w_floor(pf);
     f->wild = pf->sh_world > 1 ? nullptr : pf->fin_wild;      // (a composed finish keeps to records, tables and replays)
-    f->no_trees = getenv("BOTLAB_MCL_NO_TREES") != nullptr ? 1 : 0;
     f->recs = pf->fin_recs;
     f->tabs = pf->fin_tabs;
     f->sync = pf->fin_sync;
@@ -2191,18 +2199,15 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     a.step = pf->step;
     a.resample = resample;
     a.strict = pf->prefix_is_strict ? 1 : 0;
-    if (getenv("BOTLAB_MCL_DIAG_NOSEARCH")) a.resample = 0;
     // MovingLaserScan(scan, parent_pose, pose): parent_pose.utime is the particle's previous pose utime, pose.utime is
     // ActionModel::utime_ == 0 (D3); they differ only on the first moved update after initialisation.
     a.interp = (map && pf->pose_utime != 0) ? 1 : 0;
     // packed 16-bit scoring: grid up to 8192 a side, the longest kept ray spans at most 4000 cells (see score_ray_pk)
     a.theta_simple = ctx->scan.thetas_simple ? 1 : 0;
     a.max_range_cells = map ? ctx->scan.max_range * a.frame.cpm : 0.0f;
-    static const bool hw_trig = getenv("BOTLAB_MCL_HW_TRIG") != nullptr;        // the round-3 form of the fast path (A/B runs, tests)
-    a.fast_trig = (a.theta_simple && !pf->no_fast_trig) ? (hw_trig ? 2 : 1) : 0;
-    a.stage_dma = pf->no_stage_dma ? 0 : 1;
-    a.pk_ok = (map && a.frame.width <= 8192 && a.frame.height <= 8192 && ctx->scan.max_range * a.frame.cpm <= 4000.0f &&
-               !pf->no_packed) ? 1 : 0;
+    a.fast_trig = (a.theta_simple && !pf->sw.no_fast_trig) ? 1 : 0;
+    a.stage_dma = pf->sw.no_stage_dma ? 0 : 1;
+    a.pk_ok = (map && a.frame.width <= 8192 && a.frame.height <= 8192 && ctx->scan.max_range * a.frame.cpm <= 4000.0f) ? 1 : 0;
     // Where the gathers go.  Mode 1: the whole grid, zero-framed, staged in LDS by every workgroup (grids up to 64 KB).
     // Larger grids: a zero-framed copy in device memory, made by k_mcl_frame in front of this launch, and
     //   mode 2: an LDS window of it around the predicted pose, the scan's reach plus MCL_WIN_MARGIN cells for the spread of
@@ -2224,7 +2229,7 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
                 map->mirror_cap = whole;
                 map->mirror_valid = false;
             }
-            if (!map->mirror_valid || map->mirror_stride != stride || map->mirror_external || pf->no_mirror_reuse) {
+            if (!map->mirror_valid || map->mirror_stride != stride || map->mirror_external || pf->sw.no_mirror_reuse) {
                 const int dwords = (stride >> 2) * (H + 2 * MCL_FRAME);
                 hipLaunchKernelGGL(k_mcl_frame, dim3((dwords + 255) / 256), dim3(256), 0, ctx->stream, map->cells, W, H, stride, (int*)map->mirror);
                 map->mirror_stride = stride;
@@ -2234,7 +2239,7 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
             a.framed_stride = stride;
             return BL_OK;
         };
-        if (pf->use_lds && whole <= MCL_WIN_SMALL_BYTES) {
+        if (whole <= MCL_WIN_SMALL_BYTES) {
             a.win_w = W; a.win_h = H;
             lds_bytes = (int)whole;
             mode = 1;
@@ -2243,11 +2248,11 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
             // grid in dwords (206 instructions of 200 bytes): the staging waves' loads were issue-bound, 35 per wave in 6 us
             // (profiles/r06_mcl_timeline.txt).  Needs the image to be whole 16-byte pieces and the map to live on this ctx's
             // stream (the copy is kept current by k_map_update there); BOTLAB_MCL_NO_STAGE_X4=1: the row form.
-            if (!pf->no_stage_x4 && a.stage_dma && (whole & 15) == 0 && map->ctx == ctx && !map->mirror_external && !pf->no_framed && !pf->no_mirror_reuse) {
+            if (!pf->sw.no_stage_x4 && a.stage_dma && (whole & 15) == 0 && map->ctx == ctx && !map->mirror_external && !pf->sw.no_framed && !pf->sw.no_mirror_reuse) {
                 int rc_m = ensure_mirror();
                 if (rc_m) return rc_m;
             }
-        } else if (a.pk_ok && !a.interp && !pf->no_framed) {
+        } else if (a.pk_ok && !a.interp && !pf->sw.no_framed) {
             { int rc_m = ensure_mirror(); if (rc_m) return rc_m; }
             // Measured at 100k-1M particles on 2000^2 / 4096^2 grids: with the rays inside it a 208-cell window is 8-22 %
             // faster than gathering everything through L2, with nearly every ray leaving it (8 m rays) it is within
@@ -2255,9 +2260,9 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
             const int reach = (int)ceilf(ctx->scan.max_range * a.frame.cpm) + MCL_WIN_MARGIN;
             int side = (2 * reach + 3) & ~3;
             if (side > MCL_WIN_MAX) side = MCL_WIN_MAX;
-            if (pf->window_override > 0) side = (pf->window_override + 3) & ~3;
+            if (pf->sw.window > 0) side = (pf->sw.window + 3) & ~3;
             if (side > 384) side = 384;
-            if (pf->use_lds && !pf->no_window) {
+            if (!pf->sw.no_window) {
                 a.win_w = side < stride ? side : stride;
                 a.win_h = side < H + 2 * MCL_FRAME ? side : H + 2 * MCL_FRAME;
                 lds_bytes = a.win_w * a.win_h;
@@ -2269,12 +2274,10 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
         }
     }
     // Launch shape.  Rays of one particle go over 2^split_log2 adjacent lanes: the smallest split that gives
-    // >= MCL_MIN_BLOCKS workgroups (at most a wave).  512-thread workgroups (whole grid staged: 40 KB, up to 3 per CU).
-    int block = 512;                             // measured at 100k and 1M particles, 200x200: 512 is within 3 % of the best
-    if (pf->block_override > 0) block = pf->block_override;
+    // >= MCL_MIN_BLOCKS workgroups (at most a wave).  MCL_BLOCK-thread workgroups (whole grid staged: 40 KB, up to 3 per CU).
+    const int block = MCL_BLOCK;
     a.split_log2 = 0;
-    if (map && pf->split_log2_override >= 0) a.split_log2 = pf->split_log2_override;
-    else if (map) {
+    if (map) {
         while (a.split_log2 < 6 && ((int64_t)n_out << a.split_log2) < (int64_t)MCL_MIN_BLOCKS * block) a.split_log2++;
         // ... and, up to four lanes per particle, until the launch is about two rounds of the machine: 256 000 particles at two
         // lanes are 1000 workgroups -- one round and a third -- and took 0.309 ms where four lanes (2000 workgroups) take 0.252
@@ -2292,16 +2295,15 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     int64_t main_blocks = ((int64_t)n_out + gpb - 1) / gpb, tail_blocks = 0;
     int64_t main_particles = n_out;
     const int tail_tile = block >> 6;                       // particles per region-2 workgroup
-    if (map && !pf->no_balance && gpb >= 1) {
+    if (map) {
         const int cus = pf->cus > 0 ? pf->cus : 256;
         int per_cu = 32 / (block >> 6);
         const int lds_per_wg = lds_bytes + 9 * 1024;        // + static LDS (ray table, partial sums)
         if ((160 * 1024) / lds_per_wg < per_cu) per_cu = (160 * 1024) / lds_per_wg;
         if (per_cu < 1) per_cu = 1;
         // (round 6: 1/128 short -- six slots -- where it was 1/32 until the ray loop lost a quarter of its instructions: 11 930 -> 12 250
-        // steps/s on the headline, profiles/r06_mcl_round_split.txt; BOTLAB_MCL_ROUND_SHORT = the divisor, 0 = a full round)
-        static const int short_div = getenv("BOTLAB_MCL_ROUND_SHORT") ? atoi(getenv("BOTLAB_MCL_ROUND_SHORT")) : 128;
-        const int64_t round = (int64_t)cus * per_cu - (short_div > 0 ? (int64_t)cus * per_cu / short_div : 0);
+        // steps/s on the headline, profiles/r06_mcl_round_split.txt)
+        const int64_t round = (int64_t)cus * per_cu - (int64_t)cus * per_cu / MCL_ROUND_SHORT_DIV;
         const int64_t full = main_blocks / round, excess = main_blocks - full * round;
         // (a particle of the second region costs a wave about a tenth of a region-1 workgroup's time, and the device runs ~6000
         // such waves at once: past ~25 000 excess particles the second region outlasts the straggling round it replaces --
@@ -2331,22 +2333,15 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     hipEvent_t e0, e1;
     int rc = bl_timer_pair(ctx, BL_K_MCL_MAIN, &e0, &e1);     // a timed launch carries its own start/stop events
     if (rc) return rc;
-#define MCL_LAUNCH_REC(B, M, REC)                                                                                 \
+#define MCL_LAUNCH_REC(M, REC)                                                                                    \
     do {                                                                                                          \
-        if (a.interp) hipExtLaunchKernelGGL((k_mcl_main<1, B, (M) == 2 ? 0 : (M), REC>), dim3(blocks), dim3(B), lds_bytes, ctx->stream, e0, e1, 0, a); \
-        else hipExtLaunchKernelGGL((k_mcl_main<0, B, M, REC>), dim3(blocks), dim3(B), lds_bytes, ctx->stream, e0, e1, 0, a);          \
+        if (a.interp) hipExtLaunchKernelGGL((k_mcl_main<1, (M) == 2 ? 0 : (M), REC>), dim3(blocks), dim3(block), lds_bytes, ctx->stream, e0, e1, 0, a); \
+        else hipExtLaunchKernelGGL((k_mcl_main<0, M, REC>), dim3(blocks), dim3(block), lds_bytes, ctx->stream, e0, e1, 0, a);          \
     } while (0)
-#define MCL_LAUNCH(B, M) do { if (rec_mode) MCL_LAUNCH_REC(B, M, true); else MCL_LAUNCH_REC(B, M, false); } while (0)
-#define MCL_LAUNCH_MODE(B)                                    \
-    do {                                                      \
-        if (mode == 0) MCL_LAUNCH(B, 0);                      \
-        else if (mode == 1) MCL_LAUNCH(B, 1);                 \
-        else MCL_LAUNCH(B, 2);                                \
-    } while (0)
-    if (block == 256) MCL_LAUNCH_MODE(256);
-    else if (block == 512) MCL_LAUNCH_MODE(512);
-    else MCL_LAUNCH_MODE(1024);
-#undef MCL_LAUNCH_MODE
+#define MCL_LAUNCH(M) do { if (rec_mode) MCL_LAUNCH_REC(M, true); else MCL_LAUNCH_REC(M, false); } while (0)
+    if (mode == 0) MCL_LAUNCH(0);
+    else if (mode == 1) MCL_LAUNCH(1);
+    else MCL_LAUNCH(2);
 #undef MCL_LAUNCH
 #undef MCL_LAUNCH_REC
     BL_HIP(hipGetLastError());
@@ -2361,7 +2356,7 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     pf->last_blocks = blocks;
     pf->last_tile = gpb;                                  // particles per region-1 workgroup of k_mcl_main
     pf->last_main_blocks = a.main_blocks; pf->last_main_particles = a.main_particles; pf->last_tail_tile = tail_tile;
-    pf->fused_finish = (pf->n_local == pf->N) && pf->last_tile >= 1 && pf->last_tile <= mclf_chunk(MCLF_GT_LARGE) && !pf->no_fused_finish;
+    pf->fused_finish = (pf->n_local == pf->N) && pf->last_tile >= 1 && pf->last_tile <= mclf_chunk(MCLF_GT_LARGE) && !pf->sw.no_fused_finish;
     return BL_OK;
 }
 
@@ -2476,7 +2471,7 @@ int bl_pf_take_finish(bl_pf* pf, mcl_finish_args* out)
         // a shard (the record has just been gathered from every rank) or a launch shape the groups do not tile: the tile sums
         // come from the record itself, in an order that depends on N alone (k_scan_tile_sums, launched here), and the rest of
         // the finish -- groups, pre-chain, finisher -- rides in the caller's kernel exactly as in the fused form
-        if (pf->no_fused_finish) return -1;
+        if (pf->sw.no_fused_finish) return -1;
         const int which = pf->cur ^ 1;
         mcl_finish_args& f = *out;
         f.partials = pf->tile_partials; f.nblocks = pf->scan_blocks;
@@ -3142,52 +3137,7 @@ extern "C" int bl_pf_debug_uniform_runs(bl_pf* pf, int* out_runs)
     return BL_OK;
 }
 
-// ---- the measurement MCL_TRIG_EPS rests on, as a call (tests/test_gpu_trig_guard.py runs it on every driver run): the largest
-// |hw_sincos_unwrapped(d) - (sinf, cosf)(wrap_to_pi(d))| over EVERY float d in [-3 pi - 0.01, pi + 0.01], the range of a wrapped
-// pose angle less a scan angle in [0, 6.2831] (sensor_model.cpp:34-37 through moving_laser_scan.cpp:33).  ~0.7 s on the device.
-__global__ __launch_bounds__(256) void k_trig_probe(uint32_t lo_bits, uint32_t count, unsigned int* out_max)
-{
-    float ms = 0.f, mc = 0.f;
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
-        const float d = __uint_as_float(lo_bits + (uint32_t)i);
-        float sn, cs, hs, hc;
-        bl_sincosf_cells(bl_wrap_to_pi(d), &sn, &cs);
-        hw_sincos_unwrapped(d, &hs, &hc);
-        ms = fmaxf(ms, fabsf(hs - sn)); mc = fmaxf(mc, fabsf(hc - cs));
-        if (!(fabsf(hs - sn) <= 1.0f)) ms = 2.0f;               // a nan difference must not hide in fmaxf
-        if (!(fabsf(hc - cs) <= 1.0f)) mc = 2.0f;
-    }
-    for (int off = 32; off > 0; off >>= 1) { ms = fmaxf(ms, __shfl_xor(ms, off, 64)); mc = fmaxf(mc, __shfl_xor(mc, off, 64)); }
-    if ((threadIdx.x & 63) == 0) {                              // non-negative floats order like their bit patterns
-        atomicMax(&out_max[0], __float_as_uint(ms));
-        atomicMax(&out_max[1], __float_as_uint(mc));
-    }
-}
-
-extern "C" int bl_debug_trig_probe(bl_ctx* ctx, float* max_sin_err, float* max_cos_err, float* eps_used, uint64_t* floats_checked)
-{
-    BL_CHECK_ARG(ctx != nullptr && max_sin_err != nullptr && max_cos_err != nullptr);
-    BL_HIP(hipSetDevice(ctx->device));
-    unsigned int* d_max = nullptr;
-    BL_HIP(hipMalloc((void**)&d_max, 8));
-    BL_HIP(hipMemsetAsync(d_max, 0, 8, ctx->stream));
-    const float hi_pos = 3.1515927f, hi_neg = 9.4347780f;       // pi + 0.01, 3 pi + 0.01
-    uint32_t bp, bn;
-    memcpy(&bp, &hi_pos, 4); memcpy(&bn, &hi_neg, 4);
-    // positive floats 0 .. hi_pos: bit patterns 0 .. bp; negative floats -0 .. -hi_neg: 0x80000000 .. 0x80000000 + bn
-    hipLaunchKernelGGL(k_trig_probe, dim3(4096), dim3(256), 0, ctx->stream, 0u, bp + 1u, d_max);
-    hipLaunchKernelGGL(k_trig_probe, dim3(4096), dim3(256), 0, ctx->stream, 0x80000000u, bn + 1u, d_max);
-    BL_HIP(hipGetLastError());
-    float h[2];
-    BL_HIP(hipMemcpyAsync(h, d_max, 8, hipMemcpyDeviceToHost, ctx->stream));
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    BL_HIP(hipFree(d_max));
-    *max_sin_err = h[0]; *max_cos_err = h[1];
-    if (eps_used) *eps_used = MCL_TRIG_EPS;
-    if (floats_checked) *floats_checked = (uint64_t)bp + 1ull + (uint64_t)bn + 1ull;
-    return BL_OK;
-}
-
+// ---- the measurement MCL_TRIG_EPS rests on, as a call (tests/test_gpu_trig_guard.py runs it on every driver run):
 // |direction by the addition theorems - the reference's sinf / cosf of wrap_to_pi(fl(p - r))| over random pairs: p a float of
 // [-pi, pi] (a particle's wrapped heading), r a float of [0, 6.2831] (a theta_simple scan's ray angle), with the very functions the
 // ray loop calls (ray_table_entry, trig_by_addition; bl_sincosf_cells / wrap_to_pi_cells on the exact side).

@@ -106,7 +106,6 @@ struct mcl_finish_args {
                                            // tag) until its group has stored this launch's (mclf_store_rec, mclf_decode_rec)
     const mclf_shards* sh;                 // device memory; null: one rank (a table in the argument block itself would be indexed
                                            // per lane, which moves a by-value argument into scratch for every thread of the kernel)
-    int no_trees;                          // BOTLAB_MCL_NO_TREES: an overflowed list is walked by the chain's wave alone (tests, A/B)
 };
 
 #define MCLF_POSE_THREADS 256                 // the theta sums' addition order is that of a 256-thread workgroup, whoever runs it
@@ -1773,7 +1772,7 @@ __device__ __forceinline__ void mclf_pose(const mcl_finish_args& f, mclf_smem& s
     // an axis whose list overflowed (the sum hovers around zero) is walked with composition trees: its table area holds them, the
     // waves that would idle through the chains build them (mclf_tree_helper)
     bool trees[2] = {false, false};
-    if (staged && f.wild != nullptr && f.sh == nullptr && f.no_trees == 0) {
+    if (staged && f.wild != nullptr && f.sh == nullptr) {
         for (int ax = 0; ax < 2; ++ax) trees[ax] = *MCLF_STAGE(ax).nent > MCLF_MAXENT && nrec > MCLF_PRE_SUBS;
         if (tid < 2 && trees[tid]) {
             const mclf_trees tr = mclf_trees_at(MCLF_STAGE(tid));
