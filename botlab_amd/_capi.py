@@ -80,8 +80,25 @@ class ScanMatchResult(C.Structure):
                 f"score_centre={self.score_centre}, ties={self.ties}, rays_used={self.rays_used}, accepted={self.accepted})")
 
 
+class ScanMatchWideParams(C.Structure):
+    """bl_scan_match_wide_params_t: the window of a wide (pruned) correlative scan match (32 bytes)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("ntheta", C.c_int32), ("dtheta", C.c_float), ("max_range", C.c_float),
+                ("min_score", C.c_int32), ("block_log2", C.c_int32), ("exhaustive", C.c_int32)]
+
+
+class ScanMatchWideStats(C.Structure):
+    """bl_scan_match_wide_stats_t: what the last wide match pruned (40 bytes)."""
+    _fields_ = [("candidates", C.c_int64), ("blocks", C.c_int64), ("blocks_kept", C.c_int64), ("candidates_scored", C.c_int64),
+                ("block_log2", C.c_int32), ("path", C.c_int32)]
+
+    def __repr__(self):
+        return (f"ScanMatchWideStats(candidates={self.candidates}, blocks={self.blocks}, blocks_kept={self.blocks_kept}, "
+                f"candidates_scored={self.candidates_scored}, block_log2={self.block_log2}, path={self.path})")
+
+
 assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56 and C.sizeof(PfSpread) == 80
 assert C.sizeof(ScanMatchParams) == 28 and C.sizeof(ScanMatchResult) == 56
+assert C.sizeof(ScanMatchWideParams) == 32 and C.sizeof(ScanMatchWideStats) == 40
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
 assert C.sizeof(PfAdaptiveParams) == 40 and C.sizeof(PfAdaptiveState) == 24
 
@@ -231,6 +248,8 @@ SIGNATURES = {
     "bl_scanmatch_match": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _P(ScanMatchParams), _P(ScanMatchResult)]),
     "bl_scanmatch_volume": (C.c_int, [_vp, _vp]),
     "bl_scanmatch_debug_path": (C.c_int, [_vp]),
+    "bl_scanmatch_match_wide": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _P(ScanMatchWideParams), _P(ScanMatchResult)]),
+    "bl_scanmatch_wide_stats": (C.c_int, [_vp, _P(ScanMatchWideStats)]),
     "bl_lcm_fingerprint": (C.c_uint64, [C.c_int]),
     "bl_lcm_encode_pose": (C.c_int64, [C.c_int, _P(Pose), _vp, C.c_int64]),
     "bl_lcm_encode_lidar": (C.c_int64, [_P(Lidar), _vp, _vp, C.c_int64]),

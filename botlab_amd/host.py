@@ -478,6 +478,24 @@ class ScanMatcher:
         check(self.ctx.lib.bl_scanmatch_volume(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def match_wide(self, scan, centre, grid, nx, ny, ntheta, dtheta=math.radians(1.0), max_range=8.0, min_score=0, block_log2=0,
+                   exhaustive=False):
+        """bl_scanmatch_match_wide: the same definition over windows up to the whole map (nx, ny <= 4096, ntheta <= 720), exact,
+        by scoring coarse blocks of 2^block_log2 cells a side first (0: the library chooses) and only the surviving blocks
+        exactly; exhaustive=True scores every candidate.  Returns a _capi.ScanMatchResult."""
+        ls = scan.as_c()
+        params = _capi.ScanMatchWideParams(int(nx), int(ny), int(ntheta), float(np.float32(dtheta)), float(np.float32(max_range)),
+                                           int(min_score), int(block_log2), 1 if exhaustive else 0)
+        res = _capi.ScanMatchResult()
+        check(self.ctx.lib.bl_scanmatch_match_wide(self.h, grid.h, C.byref(ls), C.byref(centre), C.byref(params), C.byref(res)))
+        return res
+
+    def wide_stats(self):
+        """_capi.ScanMatchWideStats of the last wide match: candidates, blocks, blocks_kept, candidates_scored, block_log2, path."""
+        st = _capi.ScanMatchWideStats()
+        check(self.ctx.lib.bl_scanmatch_wide_stats(self.h, C.byref(st)))
+        return st
+
     def debugPath(self):
         """0: the last match staged its map window in LDS; 1: it read the grid directly; -1: no match yet."""
         return int(self.ctx.lib.bl_scanmatch_debug_path(self.h))

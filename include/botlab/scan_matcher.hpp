@@ -24,6 +24,21 @@ inline bl_scan_match_params_t default_scan_match_params()
     return p;
 }
 
+// the whole map around its middle and the whole circle in steps of a degree, the simulator's 8 m lidar, the library's block size
+inline bl_scan_match_wide_params_t whole_map_scan_match_params(const OccupancyGrid& map)
+{
+    bl_scan_match_wide_params_t p;
+    p.nx = (map.widthInCells() + 1) / 2 > 4096 ? 4096 : (map.widthInCells() + 1) / 2;
+    p.ny = (map.heightInCells() + 1) / 2 > 4096 ? 4096 : (map.heightInCells() + 1) / 2;
+    p.ntheta = 180;
+    p.dtheta = static_cast<float>(M_PI / 180.0);
+    p.max_range = 8.0f;
+    p.min_score = 0;
+    p.block_log2 = 0;
+    p.exhaustive = 0;
+    return p;
+}
+
 template <class Pose, class Lidar>
 class ScanMatcherT {
 public:
@@ -43,6 +58,23 @@ public:
         kept_ = params.keep_volume != 0;
         keptParams_ = params;
         return r;
+    }
+    // The same over windows up to the whole map (bl_scanmatch_match_wide): exact, by scoring coarse blocks first.  It leaves a kept
+    // volume of match() as it is.
+    bl_scan_match_result_t matchWide(const Lidar& scan, const Pose& centre, const OccupancyGrid& map, const bl_scan_match_wide_params_t& params)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        bl_pose_xyt_t c = pose_in(centre);
+        bl_scan_match_result_t r;
+        check(bl_scanmatch_match_wide(h_, map.device(), &v, &c, &params, &r), "bl_scanmatch_match_wide");
+        return r;
+    }
+    // what the last matchWide pruned
+    bl_scan_match_wide_stats_t wideStats() const
+    {
+        bl_scan_match_wide_stats_t s;
+        check(bl_scanmatch_wide_stats(h_, &s), "bl_scanmatch_wide_stats");
+        return s;
     }
     // scores [2 ntheta + 1][2 ny + 1][2 nx + 1] of the last match, sized by the window of that match; empty if it did not keep them
     std::vector<int32_t> volume()

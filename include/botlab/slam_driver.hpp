@@ -310,6 +310,15 @@ public:
         globalHeadingTol_ = headingTolerance;
     }
     bool globalLocalizationConverged() const { return globalConverged_; }
+    // (extension) Global localization by one scan match (ScanMatcherT::matchWide, scan_matcher.hpp): with global localization on, the
+    // first scan is matched against the known map over the window given, around the map's middle at heading 0
+    // (whole_map_scan_match_params(map) spans the whole map and the whole circle).  An accepted and unique match (ties == 1)
+    // starts the filter at that pose (initializeFilterAtPose), and the driver is the plain localization-only driver from the first
+    // iteration on (globalLocalizationConverged() is true at once).  Any other outcome seeds uniformly, exactly as without the
+    // switch.  Off by default; set before the first iteration.
+    void setGlobalLocalizationByScanMatch(const bl_scan_match_wide_params_t& p) { globalMatch_ = true; globalMatchParams_ = p; }
+    bool globalLocalizedByScanMatch() const { return globalMatched_; }
+    const bl_scan_match_result_t& globalScanMatch() const { return globalMatchResult_; }     // of the first scan (zeros before it)
     // (extension) Kidnapped-robot recovery (ParticleFilterT::enableRecovery, default parameters): in localization-only mode (map from a
     // file, not action-only) recovery is turned on over the map as it stands once the filter is localised -- when it starts from a
     // pose, at the start; with global localization, at the first converged iteration.  From then on every iteration is the
@@ -417,6 +426,10 @@ private:
     // filter started at the true pose, 0.025 m / 0.10 rad, measured in tests/test_global_init_model_cpu.py), state
     bool global_ = false, globalConverged_ = false;
     double globalPosTol_ = 0.2, globalHeadingTol_ = 0.3;
+    // global localization by one scan match: switch and window, whether it placed the filter, the match itself
+    bool globalMatch_ = false, globalMatched_ = false;
+    bl_scan_match_wide_params_t globalMatchParams_ = bl_scan_match_wide_params_t();
+    bl_scan_match_result_t globalMatchResult_ = bl_scan_match_result_t();
     bool kidnap_ = false, kidnapOn_ = false;     // kidnapped-robot recovery: switch, turned on
     int heldMaps_ = 0;
     bool adaptive_ = false, adaptiveOn_ = false; // adaptive particle count: switch, turned on
@@ -455,6 +468,21 @@ private:
         odomAtMatch_ = odomAtScan_;
     }
 
+    // The first scan against the whole window around the map's middle.  A unique accepted match is the start pose and ends the
+    // search before it began; anything else leaves everything as it was.
+    void matchOverTheMap()
+    {
+        if (!matcher_) matcher_.reset(new ScanMatcherT<Pose, Lidar>());
+        const PointT<float> o = grid_.originInGlobalFrame();
+        const Pose centre = slam_detail::pose_of<Pose>(before_.utime, o.x + 0.5f * grid_.widthInMeters(), o.y + 0.5f * grid_.heightInMeters(), 0.0f);
+        globalMatchResult_ = matcher_->matchWide(scan_, centre, grid_, globalMatchParams_);
+        if (!globalMatchResult_.accepted || globalMatchResult_.ties != 1) return;
+        before_.x = now_.x = globalMatchResult_.pose.x;
+        before_.y = now_.y = globalMatchResult_.pose.y;
+        before_.theta = now_.theta = globalMatchResult_.pose.theta;
+        globalMatched_ = globalConverged_ = true;
+    }
+
     void startRecovery()
     {
         if (!kidnap_ || kidnapOn_ || !how_.mapFromFile || how_.odometryOnly || how_.posesGiven) return;
@@ -483,6 +511,7 @@ private:
         before_ = now_ = start_;
         before_.utime = scan_.times.front();
         now_.utime = scan_.times.back();
+        if (globalSearching() && globalMatch_) matchOverTheMap();
         if (globalSearching()) pf_.initializeFilterUniformly(grid_, 0.0f, before_.utime);
         else { pf_.initializeFilterAtPose(before_); startRecovery(); }
         if (adaptive_ && !how_.posesGiven) { pf_.enableAdaptive(); adaptiveOn_ = true; }

@@ -301,7 +301,8 @@ int bl_pf_debug_last(bl_pf* pf, int32_t* resample_idx, int32_t* likelihood_half_
  *   Best candidate: the highest score; ties go to the smallest di*di + dj*dj, then the smallest |dk|, then the smallest dk, dj,
  *     di -- one 64-bit key per candidate, so the maximum does not depend on the order of reduction.  An empty or all-free map
  *     returns the centre.
- *   Not in it: multi-resolution pruning, sub-cell refinement, a covariance estimate, a motion prior. */
+ *   Not in it: sub-cell refinement, a covariance estimate, a motion prior.  Windows beyond the limits below, up to the whole
+ *   map, are bl_scanmatch_match_wide's (further down), which prunes. */
 typedef struct bl_scan_match_params_t {
     int32_t nx, ny;          /* half window in cells: shifts di in [-nx, nx], dj in [-ny, ny];   0 <= nx, ny <= 64   */
     int32_t ntheta;          /* half window in heading steps: dk in [-ntheta, ntheta];           0 <= ntheta <= 180  */
@@ -333,6 +334,47 @@ int bl_scanmatch_volume(bl_scanmatch* sm, int32_t* scores);
 /* diagnostic: which scoring path the last match took -- 0 the map window staged in LDS, 1 the grid read directly (the window
  * the scan's endpoints and the shifts span does not fit in LDS); -1 before the first match */
 int bl_scanmatch_debug_path(const bl_scanmatch* sm);
+
+/* The wide match: the definition above word for word -- valid rays, headings, endpoint cells, score(di, dj, dk), score_centre,
+ * rays_used, accepted, the pose -- over windows up to the whole map: 0 <= nx, ny <= 4096, 0 <= ntheta <= 720, at most 4096 valid
+ * rays, dtheta > 0.  It returns exactly what scoring every candidate returns, and gets there by pruning (Olson's multi-resolution
+ * speed-up, one pooled level).  With P the positive part of the map (0 outside the grid), B = 2^block_log2 and
+ * M[y][x] = max P[y .. y+B-1][x .. x+B-1], the block of shifts di in [i0, i0+B), dj in [j0, j0+B) at heading dk has
+ * bound = sum over the valid rays of M[ey + j0][ex + i0] >= every score of the block.  With L the exact score of any candidate
+ * (here: the best of the centre and of each heading's best-bounded block), every candidate scoring >= L lies in a block with
+ * bound >= L; those blocks are scored exactly, so the winner, its tie-break and `ties` are those of the exhaustive form.
+ *   Best candidate: the same total order -- highest score; then smallest di*di + dj*dj, |dk|, dk, dj, di -- as a two-word key (a
+ *     score is below 2^20), so the maximum does not depend on the order of reduction.
+ *   ties: candidates of the whole window sharing the best score, saturating at INT32_MAX.  When no block's bound is above 0 the
+ *     answer is known without scoring: the centre, score 0, ties = the window's candidate count (saturated).
+ *   block_log2: 0 = the library chooses (8 x 8, grown until the bounds, one int32 per heading and block, stay within 2^26 blocks =
+ *     256 MiB); otherwise 1 .. 6, refused with BL_ERR_ARG if its bounds exceed that budget.
+ *   exhaustive != 0: every candidate is scored with the same key and no pruning (a yardstick for tests and tools); refused with
+ *     BL_ERR_ARG above 2^31 candidates.
+ * A flat landscape (L = 0 under positive bounds) prunes nothing and costs what the exhaustive form costs; it is never wrong.
+ * One stream-ordered sequence on the ctx stream; synchronises to hand the result back.  BL_ERR_ARG (a limit exceeded, a null
+ * pointer, a map of another ctx) changes nothing, the statistics of the last wide match included. */
+typedef struct bl_scan_match_wide_params_t {
+    int32_t nx, ny;          /* half window in cells, 0 <= nx, ny <= 4096 */
+    int32_t ntheta;          /* half window in heading steps, 0 <= ntheta <= 720 */
+    float   dtheta;          /* heading step in radians, > 0 */
+    float   max_range;       /* rays with range >= max_range are skipped */
+    int32_t min_score;       /* a best score below this is "no match" */
+    int32_t block_log2;      /* 0, or 1 .. 6 */
+    int32_t exhaustive;      /* != 0: no pruning */
+} bl_scan_match_wide_params_t;   /* 32 bytes */
+typedef struct bl_scan_match_wide_stats_t {
+    int64_t candidates;          /* of the window */
+    int64_t blocks;              /* per heading ceil((2 nx + 1) / B) * ceil((2 ny + 1) / B) */
+    int64_t blocks_kept;         /* blocks with bound >= L (exhaustive: all) */
+    int64_t candidates_scored;   /* exact scores computed: the kept blocks' candidates, the seed blocks' and the centre */
+    int32_t block_log2;          /* used */
+    int32_t path;                /* exact scoring read the map from 0: LDS (the whole grid fits), 1: the grid */
+} bl_scan_match_wide_stats_t;    /* 40 bytes */
+int bl_scanmatch_match_wide(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* centre,
+                            const bl_scan_match_wide_params_t* params, bl_scan_match_result_t* result);
+/* of the last wide match that was not refused; BL_ERR_STATE before the first */
+int bl_scanmatch_wide_stats(const bl_scanmatch* sm, bl_scan_match_wide_stats_t* out);
 
 /* ------------------------------------------------------------------ ObstacleDistanceGrid  (src/planning/obstacle_distance_grid.hpp:28-96) */
 int bl_dist_create(bl_ctx* ctx, bl_dist** out);
