@@ -8,9 +8,11 @@ from ._capi import BotlabHipError, Lidar, Particle, Pose, SearchParams, load  # 
 from .host import (AsyncExplorer, AsyncPlanner, Context, LidarScan, Mapping, MotionPlanner, MotionPlannerParams, ObstacleDistanceGrid,  # noqa: F401
                    OccupancyGrid, ParticleFilter, PARTICLE_DTYPE, POSE_DTYPE, default_context, make_pose,
                    search_for_path, search_for_path_begin, search_for_path_end, search_for_path_batch, Frontiers,
-                   find_map_frontiers, plan_path_to_frontier, ExploringMap, ScanMatcher)
+                   find_map_frontiers, plan_path_to_frontier, ExploringMap, ScanMatcher, NavigationField, nav_params,
+                   plan_path_to_frontier_by_cost, NAV_UNREACHED)
 
 __all__ = ["AsyncExplorer", "AsyncPlanner", "BotlabHipError", "Lidar", "Particle", "Pose", "SearchParams", "load", "Context", "LidarScan", "Mapping",
            "MotionPlanner", "MotionPlannerParams", "ObstacleDistanceGrid", "OccupancyGrid", "ParticleFilter",
            "PARTICLE_DTYPE", "POSE_DTYPE", "default_context", "make_pose", "search_for_path", "search_for_path_begin",
-           "search_for_path_end", "search_for_path_batch", "Frontiers", "find_map_frontiers", "plan_path_to_frontier", "ExploringMap", "ScanMatcher"]
+           "search_for_path_end", "search_for_path_batch", "Frontiers", "find_map_frontiers", "plan_path_to_frontier", "ExploringMap", "ScanMatcher",
+           "NavigationField", "nav_params", "plan_path_to_frontier_by_cost", "NAV_UNREACHED"]

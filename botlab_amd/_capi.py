@@ -96,7 +96,14 @@ class ScanMatchWideStats(C.Structure):
                 f"candidates_scored={self.candidates_scored}, block_log2={self.block_log2}, path={self.path})")
 
 
+class NavFieldParams(C.Structure):
+    """bl_navfield_params_t: the metric and the goal reach of a navigation field (32 bytes)."""
+    _fields_ = [("minDistanceToObstacle", C.c_double), ("maxDistanceWithCost", C.c_double), ("distanceCostExponent", C.c_double),
+                ("obstacle_gain", C.c_int32), ("reach_cells", C.c_int32)]
+
+
 assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56 and C.sizeof(PfSpread) == 80
+assert C.sizeof(NavFieldParams) == 32
 assert C.sizeof(ScanMatchParams) == 28 and C.sizeof(ScanMatchResult) == 56
 assert C.sizeof(ScanMatchWideParams) == 32 and C.sizeof(ScanMatchWideStats) == 40
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
@@ -250,6 +257,17 @@ SIGNATURES = {
     "bl_scanmatch_debug_path": (C.c_int, [_vp]),
     "bl_scanmatch_match_wide": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _P(ScanMatchWideParams), _P(ScanMatchResult)]),
     "bl_scanmatch_wide_stats": (C.c_int, [_vp, _P(ScanMatchWideStats)]),
+    "bl_navfield_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_navfield_destroy": (None, [_vp]),
+    "bl_navfield_compute": (C.c_int, [_vp, _vp, _P(NavFieldParams), _vp, C.c_int]),
+    "bl_navfield_compute_to_pose": (C.c_int, [_vp, _vp, _P(NavFieldParams), _P(Pose)]),
+    "bl_navfield_paths": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "bl_navfield_gather": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "bl_navfield_download": (C.c_int, [_vp, _vp]),
+    "bl_navfield_shape": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "bl_navfield_device_ptr": (_vp, [_vp]),
+    "bl_navfield_tables": (C.c_int, [_vp, _vp, _vp, _P(C.c_int)]),
+    "bl_navfield_stats": (C.c_int, [_vp, _vp]),
     "bl_lcm_fingerprint": (C.c_uint64, [C.c_int]),
     "bl_lcm_encode_pose": (C.c_int64, [C.c_int, _P(Pose), _vp, C.c_int64]),
     "bl_lcm_encode_lidar": (C.c_int64, [_P(Lidar), _vp, _vp, C.c_int64]),

@@ -148,6 +148,14 @@ void bl_planner_cancel(bl_planner* p);
 // bl_planning.hip: the device arrays of a transformed distance grid (BL_ERR_ARG before its first transform)
 int bl_dist_view(const bl_dist* d, const uint16_t** l1, const float** lut, int* width, int* height);
 
+// isValid of the search (astar.cpp:140-149) for a cell whose distance-grid value is `dist`: the one predicate behind
+// the search's cost table and the navigation field's traversable(n)
+inline bool bl_search_traversable(float dist, double minDistanceToObstacle) { return dist > minDistanceToObstacle * 1.000001; }
+
+// bl_planning.hip: a transformed distance grid as bl_navfield.hip reads it (BL_ERR_ARG before its first transform)
+struct bl_dist_host_view { bl_ctx* ctx; bl_frame frame; const uint16_t* l1; const float* lut_host; int lut_n; };
+int bl_dist_view_host(const bl_dist* d, bl_dist_host_view* out);
+
 // RAII-less helpers
 int bl_timer_begin(bl_ctx* ctx, int id, hipEvent_t* a, hipEvent_t* b);
 int bl_timer_end(bl_ctx* ctx, int id, hipEvent_t a, hipEvent_t b);

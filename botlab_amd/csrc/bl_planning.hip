@@ -1890,6 +1890,19 @@ int bl_dist_view(const bl_dist* d, const uint16_t** l1, const float** lut, int* 
     return BL_OK;
 }
 
+// the same grid as the navigation field reads it (bl_navfield.hip): the integer distances on the device, the table f[n] on the
+// host, the frame and the ctx whose stream orders the transform.  After a caller has synchronised that stream it also tells a
+// whole-grid transform that gave up (dist_check_broken).
+int bl_dist_view_host(const bl_dist* d, bl_dist_host_view* out)
+{
+    if (!d || !d->valid) { bl_set_error("distance grid not set (bl_dist_set_distances first)"); return BL_ERR_ARG; }
+    int rc = dist_check_broken(const_cast<bl_dist*>(d));
+    if (rc) return rc;
+    out->ctx = d->ctx; out->frame = d->frame; out->l1 = d->l1;
+    out->lut_host = d->lut_host->data(); out->lut_n = d->lut_n;
+    return BL_OK;
+}
+
 extern "C" int bl_dist_shape(const bl_dist* d, int* width, int* height)
 {
     BL_CHECK_ARG(d != nullptr);
@@ -2578,7 +2591,7 @@ static int astar_prepare_lut(bl_ctx* ctx, const bl_dist* d, const bl_search_para
     for (int n = 0; n < ln; ++n) {
         float dist = f[n];
         int32_t c;
-        if (!(dist > params->minDistanceToObstacle * 1.000001)) c = ASTAR_INVALID_COST;
+        if (!bl_search_traversable(dist, params->minDistanceToObstacle)) c = ASTAR_INVALID_COST;
         else {
             c = 0;
             if (dist > params->minDistanceToObstacle && dist < params->maxDistanceWithCost) {

@@ -712,6 +712,136 @@ def plan_path_to_frontier(frontiers, robotPose, grid, planner, cap=1 << 16, retu
     return path
 
 
+NAV_UNREACHED = 0xFFFFFFFF
+NAV_OBSTACLE_GAIN = 50
+
+
+def nav_params(searchParams, obstacle_gain=NAV_OBSTACLE_GAIN, reach_cells=0):
+    """bl_navfield_params_t from a planner's SearchParams: the same three distances, the gain and the reach of a goal."""
+    return _capi.NavFieldParams(searchParams.minDistanceToObstacle, searchParams.maxDistanceWithCost, searchParams.distanceCostExponent,
+                                int(obstacle_gain), int(reach_cells))
+
+
+class NavigationField:
+    """The goal-rooted navigation field (bl_navfield_*, include/botlab_hip.h): the exact cost-to-go of every cell of a distance grid
+    to a set of goal cells over 8-connected moves, and the cheapest paths read off it.  One compute answers every query against
+    its goals."""
+
+    def __init__(self, ctx=None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_navfield_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        self._dist = None
+
+    def compute(self, distances, params, goal_cells):
+        """goal_cells: (n, 2) integer cells (x, y).  `distances` must stay alive (and untransformed, for paths) while the field is used."""
+        g = np.ascontiguousarray(np.asarray(goal_cells, dtype=np.int32).reshape(-1, 2))
+        self._dist = distances
+        check(self.ctx.lib.bl_navfield_compute(self.h, distances.h, C.byref(params), g.ctypes.data if len(g) else None, len(g)))
+
+    def computeToPose(self, distances, params, goal):
+        self._dist = distances
+        check(self.ctx.lib.bl_navfield_compute_to_pose(self.h, distances.h, C.byref(params), C.byref(goal)))
+
+    def paths(self, starts, cap_each=4097, raw=False):
+        """One descent per start pose.  Returns (paths, labels, costs): paths as lists of Pose (raw=True: a (n, cap_each) POSE_DTYPE
+        array and the lengths instead), the goal label each path reached (-1: none) and field(start)."""
+        n = len(starts)
+        s = (Pose * max(n, 1))(*starts)
+        buf = np.zeros((max(n, 1), cap_each), dtype=POSE_DTYPE)
+        lens = np.zeros(max(n, 1), np.int32)
+        labels = np.zeros(max(n, 1), np.int32)
+        costs = np.zeros(max(n, 1), np.uint32)
+        check(self.ctx.lib.bl_navfield_paths(self.h, s, n, buf.ctypes.data, cap_each, lens.ctypes.data, labels.ctypes.data, costs.ctypes.data))
+        if raw:                                          # lens[i] > cap_each: path i is cut off at cap_each poses
+            return (buf[:n], lens[:n]), labels[:n], costs[:n]
+        if n and int(lens[:n].max()) > cap_each:
+            raise _capi.BotlabHipError(f"a path of {int(lens[:n].max())} poses does not fit the {cap_each}-pose buffer")
+        out = [[Pose(int(p["utime"]), float(p["x"]), float(p["y"]), float(p["theta"])) for p in buf[i, :lens[i]]] for i in range(n)]
+        return out, labels[:n], costs[:n]
+
+    def gather(self, cells):
+        q = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 2))
+        out = np.zeros(len(q), np.uint32)
+        check(self.ctx.lib.bl_navfield_gather(self.h, q.ctypes.data if len(q) else None, len(q), out.ctypes.data if len(q) else None))
+        return out
+
+    def shape(self):
+        w, h = C.c_int(), C.c_int()
+        check(self.ctx.lib.bl_navfield_shape(self.h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def cells(self):
+        w, h = self.shape()
+        out = np.empty((h, w), dtype=np.uint32)
+        check(self.ctx.lib.bl_navfield_download(self.h, out.ctypes.data))
+        return out
+
+    def tables(self):
+        """(traversable, penalty) per L1 distance n = 0 .. width + height."""
+        n = C.c_int()
+        check(self.ctx.lib.bl_navfield_tables(self.h, None, None, C.byref(n)))
+        trav, pen = np.zeros(n.value, np.uint8), np.zeros(n.value, np.int32)
+        check(self.ctx.lib.bl_navfield_tables(self.h, trav.ctypes.data, pen.ctypes.data, C.byref(n)))
+        return trav, pen
+
+    def stats(self):
+        v = (C.c_int64 * 5)()
+        check(self.ctx.lib.bl_navfield_stats(self.h, v))
+        return dict(rounds=v[0], tile_sweeps=v[1], traversable=v[2], reached=v[3], goal_set=v[4])
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_navfield_destroy(self.h)
+            self.h = None
+
+
+def nav_min_traversable_cells(distances, searchParams):
+    """n_min: the smallest L1 distance (in cells) that is traversable under searchParams -- f[n] > minDistanceToObstacle * 1.000001
+    with the distance grid's own table f[n] = f[n - 1] + 0.1f; None if no distance of this grid is."""
+    w, h = distances.shape()
+    f = np.float32(0.0)
+    for n in range(w + h + 1):
+        if float(f) > searchParams.minDistanceToObstacle * 1.000001:
+            return n
+        f = np.float32(f + np.float32(0.1))
+    return None
+
+
+def plan_path_to_frontier_by_cost(frontiers, robotPose, grid, planner, reach_cells=None, obstacle_gain=NAV_OBSTACLE_GAIN, cap=1 << 16,
+                                  field=None):
+    """The frontier that is cheapest to reach, not the one closest in a straight line: ONE navigation field whose goals are every
+    cell of every frontier, and one descent from the robot.  A frontier cell borders unknown space and is never traversable itself,
+    so a goal counts as reached within reach_cells of it; the default is n_min, the smallest traversable L1 distance under the
+    planner's parameters.  Returns (path, index of the chosen frontier or -1, cost); an empty frontier list gives the empty path, as
+    plan_path_to_frontier does.  `grid` is unused, as there."""
+    dist = planner.distances_
+    ctx = dist.ctx
+    fr = frontiers.cells() if isinstance(frontiers, Frontiers) else [np.asarray(f, dtype=np.float32).reshape(-1, 2) for f in frontiers]
+    if len(fr) == 0:
+        return [], -1, NAV_UNREACHED
+    if reach_cells is None:
+        reach_cells = nav_min_traversable_cells(dist, planner.searchParams_)
+        if reach_cells is None:
+            reach_cells = 0
+    mpc, cpm, ox, oy = dist.frame()
+    owner, cells = [], []
+    for k, f in enumerate(fr):
+        for x, y in f:                                   # global_position_to_grid_cell (grid_utils.hpp:33-38)
+            cells.append((int((float(x) - float(ox)) * float(cpm)), int((float(y) - float(oy)) * float(cpm))))
+            owner.append(k)
+    nf = field or NavigationField(ctx)
+    try:
+        nf.compute(dist, nav_params(planner.searchParams_, obstacle_gain, reach_cells), np.array(cells, np.int32).reshape(-1, 2))
+        paths, labels, costs = nf.paths([robotPose], cap_each=cap)
+    finally:
+        if field is None:
+            nf.close()
+    label = int(labels[0])
+    return paths[0], (owner[label] if label >= 0 else -1), int(costs[0])
+
+
 # exploration_status_t (lcmtypes/exploration_status_t.lcm:3-11)
 STATE_INITIALIZING, STATE_EXPLORING_MAP, STATE_RETURNING_HOME, STATE_COMPLETED_EXPLORATION, STATE_FAILED_EXPLORATION = 0, 1, 2, 3, 4
 STATUS_IN_PROGRESS, STATUS_COMPLETE, STATUS_FAILED = 0, 1, 2
@@ -900,6 +1030,20 @@ class MotionPlanner:
             failed = [Pose(start.utime, start.x, start.y, start.theta)]   # failedPath (motion_planner.cpp:28-40)
             return (failed, (0, 0)) if return_stats else failed
         return search_for_path(start, goal, self.distances_, searchParams or self.searchParams_, return_stats=return_stats)
+
+    def planPathOptimal(self, start, goal, obstacle_gain=NAV_OBSTACLE_GAIN, return_cost=False, cap=1 << 16):
+        """The cheapest 8-connected path to the goal's cell by the navigation field (bl_navfield_*): the failed path when isValidGoal
+        fails, exactly as planPath; length 1 also when the goal cannot be reached."""
+        if not self.isValidGoal(goal):
+            failed = [Pose(start.utime, start.x, start.y, start.theta)]
+            return (failed, NAV_UNREACHED) if return_cost else failed
+        nf = NavigationField(self.distances_.ctx)
+        try:
+            nf.computeToPose(self.distances_, nav_params(self.searchParams_, obstacle_gain, 0), goal)
+            paths, _, costs = nf.paths([start], cap_each=cap)
+        finally:
+            nf.close()
+        return (paths[0], int(costs[0])) if return_cost else paths[0]
 
     def isPathSafe(self, path):
         # motion_planner.cpp:77-96 (one gather for all poses); a pose outside the grid is unsafe (DESIGN.md D9)

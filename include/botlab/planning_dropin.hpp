@@ -10,6 +10,7 @@
 #include <vector>
 
 #include <botlab/botlab_dropin.hpp>
+#include <botlab/nav_field.hpp>
 
 namespace botlab_hip {
 
@@ -53,6 +54,25 @@ public:
     }
     Path planPath(const Pose& start, const Pose& goal) const { return planPath(start, goal, searchParams_); }
 
+    // The cheapest 8-connected path to the goal's cell by the navigation field (nav_field.hpp; no reference counterpart): the
+    // failed path when isValidGoal fails, exactly as planPath; path_length 1 also when the goal cannot be reached.
+    Path planPathOptimal(const Pose& start, const Pose& goal, int32_t obstacle_gain = NAV_OBSTACLE_GAIN, uint32_t* cost = nullptr) const
+    {
+        if (cost) *cost = NAV_UNREACHED;
+        if (!isValidGoal(goal)) {
+            Path failedPath;
+            failedPath.utime = utime_now_us();
+            failedPath.path_length = 1;
+            failedPath.path.push_back(start);
+            return failedPath;
+        }
+        NavigationFieldT<Pose, Path> field;
+        field.computeToPose(distances_, nav_params(searchParams_, obstacle_gain, 0), goal);
+        typename NavigationFieldT<Pose, Path>::Result r = field.path(start);
+        if (cost) *cost = r.cost;
+        return r.path;
+    }
+
     bool isValidGoal(const Pose& goal) const                                // motion_planner.cpp:52-74
     {
         float dx = goal.x - prev_goal_.x, dy = goal.y - prev_goal_.y;
@@ -88,6 +108,7 @@ public:
     }
 
     void setMap(const OccupancyGrid& map) { distances_.setDistances(map); }   // motion_planner.cpp:99-102
+    const SearchParams& searchParams() const { return searchParams_; }
     void setParams(const MotionPlannerParams&)                              // motion_planner.cpp:105-110 reads params_, not the argument
     {
         searchParams_.minDistanceToObstacle = params_.robotRadius;
@@ -172,6 +193,42 @@ Path plan_path_to_frontier_t(const std::vector<frontier_t>& frontiers, const Pos
     path.path_length = static_cast<int32_t>(path.path.size());
     return path;
 }
+// The frontier that is cheapest to reach, not the one closest in a straight line (no reference counterpart): ONE navigation field
+// whose goals are every cell of every frontier, and one descent from the robot.  A frontier cell borders unknown space and is
+// never traversable itself, so a goal counts as reached within reach_cells of it; reach_cells < 0 takes n_min, the smallest
+// traversable L1 distance under the planner's parameters (nav_min_traversable_cells).  An empty frontier list gives the empty
+// path, as plan_path_to_frontier_t does.  *frontier: the index of the chosen frontier (-1: none); *cost: field(robot).
+template <class Path, class Pose, class Planner>
+Path plan_path_to_frontier_by_cost_t(const std::vector<frontier_t>& frontiers, const Pose& robotPose, const OccupancyGrid&, const Planner& planner,
+                                     int reach_cells = -1, int* frontier = nullptr, uint32_t* cost = nullptr,
+                                     int32_t obstacle_gain = NAV_OBSTACLE_GAIN)
+{
+    if (frontier) *frontier = -1;
+    if (cost) *cost = NAV_UNREACHED;
+    Path path;
+    if (frontiers.empty()) return path;
+    const ObstacleDistanceGrid& d = planner.distances();
+    if (reach_cells < 0) {
+        reach_cells = nav_min_traversable_cells(d, planner.searchParams());
+        if (reach_cells < 0) reach_cells = 0;
+    }
+    const PointT<float> o = d.originInGlobalFrame();
+    const float cpm = d.cellsPerMeter();
+    std::vector<int32_t> cells, owner;
+    for (size_t k = 0; k < frontiers.size(); ++k)
+        for (const PointT<float>& c : frontiers[k].cells) {                         // global_position_to_grid_cell (grid_utils.hpp:33-38)
+            cells.push_back(static_cast<int>((static_cast<double>(c.x) - o.x) * cpm));
+            cells.push_back(static_cast<int>((static_cast<double>(c.y) - o.y) * cpm));
+            owner.push_back(static_cast<int32_t>(k));
+        }
+    NavigationFieldT<Pose, Path> field;
+    field.compute(d, nav_params(planner.searchParams(), obstacle_gain, reach_cells), cells);
+    typename NavigationFieldT<Pose, Path>::Result r = field.path(robotPose, 65536);
+    if (frontier && r.goal >= 0) *frontier = owner[static_cast<size_t>(r.goal)];
+    if (cost) *cost = r.cost;
+    return r.path;
+}
+
 // Exploration::executeExploringMap (src/planning/exploration.cpp:277-369) without its LCM calls (the caller publishes the
 // status and the path): the per-map step of the exploration loop -- setMap, find_map_frontiers, plan_path_to_frontier when
 // the robot is within 0.5 m of the current target (or has none) -- and the status / next-state rule of :332-368.  The

@@ -635,6 +635,67 @@ int bl_plan_path_to_frontier(bl_ctx* ctx, const bl_frontiers* frontiers, const b
                              const bl_motion_planner_t* planner, bl_pose_xyt_t* out_path, int cap, int* out_len,
                              bl_pose_xyt_t* chosen_goal, int64_t* stats);
 
+/* ------------------------------------------------------------------ navigation field (no reference counterpart)
+ * The exact cost-to-go of every cell to a set of goal cells, and cheapest paths read off it: one field answers every query against
+ * its goals -- the path from any start, the cost at any cell, the nearest of many goals.  (bl_astar_search stays the reference's
+ * search, bit for bit; that search is not a shortest-path search and its paths are 4-connected.)
+ *   Inputs: a transformed bl_dist -- n(c), the integer L1 distance of cell c to the nearest non-free cell (0xFFFF: none), and the
+ *     float table f[n] the distance grid maps it through --, the parameters below, and a list of goal cells.
+ *   Per-distance tables, built once per compute on the host in double, d = (double)f[n], n = 0 .. width + height:
+ *     traversable(n): n != 0xFFFF and d > minDistanceToObstacle * 1.000001 -- isValid of bl_astar_search, formed by
+ *       the host code that fills the search's cost table: a cell the search calls invalid is not traversable here, every cell of a
+ *       map without any non-free cell included.
+ *     penalty(n): 0 when n is not traversable, d >= maxDistanceWithCost or maxDistanceWithCost <= minDistanceToObstacle; otherwise
+ *       (int32)floor(obstacle_gain * pow((maxD - d) / (maxD - minD), distanceCostExponent)), the host's pow.  With
+ *       distanceCostExponent >= 0 (required) it lies in [0, obstacle_gain].
+ *   Moves: 8-connected, inside the grid, between traversable cells; a straight move costs 10, a diagonal one 14.  The diagonal
+ *     (dx, dy) from c is allowed only if c + (dx, 0) and c + (0, dy) are traversable as well: no corner is cut.
+ *   Goal set: every traversable cell within Chebyshev distance reach_cells of a listed cell that lies inside the grid; its label is
+ *     the lowest index of such a listed cell.  Listed cells outside the grid contribute nothing.
+ *   Field (uint32 per cell, row-major): 0 on the goal set; elsewhere penalty(n(c)) + min over the allowed moves c -> c' of
+ *     (step + field(c')); 0xFFFFFFFF (UNREACHED) where c is not traversable or not connected to the goal set.  This is the minimum
+ *     over paths of the step costs plus the penalties of the path's cells outside the goal set; steps cost at least 10, so the
+ *     solution is unique and does not depend on the order it is computed in.  width * height * (14 + obstacle_gain) > 2^32 - 2 is
+ *     refused (BL_ERR_ARG): no cost can wrap.
+ *   Path from a start pose: the start cell is global_position_to_grid_cell of the pose, as the search finds it.  out[0] is the start
+ *     pose as given.  From cell c the path takes the allowed move minimising step + field(c'), ties by the order (+x), (-x), (+y),
+ *     (-y), (+x+y), (-x+y), (+x-y), (-x-y), until it stands on the goal set.  Pose k >= 1: x, y as bl_astar_search writes a path cell
+ *     ((float)((double)origin + (double)cell * (double)meters_per_cell)), theta = atan2f(dy, dx) of the move into it, utime the
+ *     start's.  Length 1 is "no path": the start is off the grid, not traversable, UNREACHED, or on the goal set already.  Per path
+ *     also: the label of the goal-set cell it ends on (-1 if it ends on none) and field(start) (UNREACHED off the grid or on a cell
+ *     that is not traversable).
+ * How it is computed (bl_navfield.hip): tiles of 32 x 32 cells relaxed to their fixed point in LDS, round after round of the tiles
+ * whose halo got lower; no workgroup waits for another, and the host ends the rounds when a round leaves no tile listed.  At most
+ * (traversable cells) + 1 rounds can list a tile; beyond that: BL_ERR_STATE.
+ * Calls are stream-ordered on the ctx stream and synchronous on return.  The bl_dist must belong to the same ctx and outlive the
+ * field; bl_navfield_paths reads its distances again, so it answers for the field only until that grid is transformed again. */
+typedef struct bl_navfield_params_t {
+    double minDistanceToObstacle;      /* bl_search_params_t's three, the same meaning of distance */
+    double maxDistanceWithCost;
+    double distanceCostExponent;       /* >= 0, finite */
+    int32_t obstacle_gain;             /* 0 .. 4095 (default 50): the penalty of a cell right at minDistanceToObstacle */
+    int32_t reach_cells;               /* 0 .. 1024; 0: a goal is exactly the listed cell */
+} bl_navfield_params_t;                /* 32 bytes */
+typedef struct bl_navfield bl_navfield;
+int bl_navfield_create(bl_ctx* ctx, bl_navfield** out);               /* buffers grow on demand */
+void bl_navfield_destroy(bl_navfield* nf);
+int bl_navfield_compute(bl_navfield* nf, const bl_dist* dist, const bl_navfield_params_t* params, const int32_t* goal_xy_cells /* x0,y0,x1,y1,... */,
+                        int n_goals);
+/* one goal: the cell of a pose (off the grid: nothing is reached) */
+int bl_navfield_compute_to_pose(bl_navfield* nf, const bl_dist* dist, const bl_navfield_params_t* params, const bl_pose_xyt_t* goal);
+/* n independent descents in one launch.  Path i goes to out_paths + i * cap_each (at most cap_each poses; out_lens[i] is the true
+ * length); out_goal / out_cost (optional): the label reached and field(start) per path. */
+int bl_navfield_paths(bl_navfield* nf, const bl_pose_xyt_t* starts, int n, bl_pose_xyt_t* out_paths, int cap_each, int* out_lens,
+                      int32_t* out_goal, uint32_t* out_cost);
+int bl_navfield_gather(bl_navfield* nf, const int32_t* xy_cells, int n, uint32_t* out);   /* field at n cells; off the grid: UNREACHED */
+int bl_navfield_download(bl_navfield* nf, uint32_t* cells);           /* width * height words */
+int bl_navfield_shape(const bl_navfield* nf, int* width, int* height);
+void* bl_navfield_device_ptr(bl_navfield* nf);                        /* uint32_t* in HBM (NULL before the first compute) */
+/* the tables of the last compute, *n = width + height + 1 entries each (either array may be NULL) */
+int bl_navfield_tables(bl_navfield* nf, uint8_t* traversable, int32_t* penalty, int* n);
+/* of the last compute, five counts: rounds that relaxed a tile, sweeps over a tile in LDS, traversable cells, reached cells,
+ * goal-set cells */
+int bl_navfield_stats(bl_navfield* nf, int64_t* out);
 
 /* ------------------------------------------------------------------ the exploration step, asynchronously  (src/planning/exploration.cpp:277-369)
  * Exploration::executeExploringMap on every published map: planner_.setMap, find_map_frontiers, and -- when the robot is within
