@@ -104,6 +104,15 @@ class NavFieldParams(C.Structure):
 
 assert C.sizeof(Pose) == 24 and C.sizeof(Particle) == 56 and C.sizeof(PfSpread) == 80
 assert C.sizeof(NavFieldParams) == 32
+
+
+class ViewGainParams(C.Structure):
+    """bl_viewgain_params_t: the ray fan and the cell classes of a view gain (20 bytes)."""
+    _fields_ = [("radius_cells", C.c_int32), ("n_rays", C.c_int32), ("occupied_above", C.c_int32), ("unknown_lo", C.c_int32),
+                ("unknown_hi", C.c_int32)]
+
+
+assert C.sizeof(ViewGainParams) == 20
 assert C.sizeof(ScanMatchParams) == 28 and C.sizeof(ScanMatchResult) == 56
 assert C.sizeof(ScanMatchWideParams) == 32 and C.sizeof(ScanMatchWideStats) == 40
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
@@ -268,6 +277,12 @@ SIGNATURES = {
     "bl_navfield_device_ptr": (_vp, [_vp]),
     "bl_navfield_tables": (C.c_int, [_vp, _vp, _vp, _P(C.c_int)]),
     "bl_navfield_stats": (C.c_int, [_vp, _vp]),
+    "bl_viewgain_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_viewgain_destroy": (None, [_vp]),
+    "bl_viewgain_set_params": (C.c_int, [_vp, _P(ViewGainParams)]),
+    "bl_viewgain_ray_ends": (C.c_int, [_vp, _vp, _P(C.c_int)]),
+    "bl_viewgain_compute": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "bl_viewgain_debug_seen": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
     "bl_lcm_fingerprint": (C.c_uint64, [C.c_int]),
     "bl_lcm_encode_pose": (C.c_int64, [C.c_int, _P(Pose), _vp, C.c_int64]),
     "bl_lcm_encode_lidar": (C.c_int64, [_P(Lidar), _vp, _vp, C.c_int64]),

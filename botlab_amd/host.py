@@ -842,6 +842,131 @@ def plan_path_to_frontier_by_cost(frontiers, robotPose, grid, planner, reach_cel
     return paths[0], (owner[label] if label >= 0 else -1), int(costs[0])
 
 
+class ViewGain:
+    """The view gain (bl_viewgain_*, include/botlab_hip.h): the number of distinct unknown cells a fan of n_rays rays of
+    radius_cells cells, cast from a candidate cell through the log-odds grid, reaches before a blocking cell or the edge of the
+    grid ends each ray."""
+
+    def __init__(self, radius_cells=60, n_rays=360, occupied_above=0, unknown_lo=0, unknown_hi=0, ctx=None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_viewgain_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        try:
+            self.setParams(radius_cells, n_rays, occupied_above, unknown_lo, unknown_hi)
+        except _capi.BotlabHipError:
+            self.close()
+            raise
+
+    def setParams(self, radius_cells, n_rays, occupied_above=0, unknown_lo=0, unknown_hi=0):
+        p = _capi.ViewGainParams(int(radius_cells), int(n_rays), int(occupied_above), int(unknown_lo), int(unknown_hi))
+        check(self.ctx.lib.bl_viewgain_set_params(self.h, C.byref(p)))
+        self.radius_cells = int(radius_cells)
+
+    def rayEnds(self):
+        """(n_rays, 2) int32: the end offset (x, y) of every ray, as the kernel uses it."""
+        n = C.c_int()
+        check(self.ctx.lib.bl_viewgain_ray_ends(self.h, None, C.byref(n)))
+        out = np.zeros((n.value, 2), np.int32)
+        check(self.ctx.lib.bl_viewgain_ray_ends(self.h, out.ctypes.data, C.byref(n)))
+        return out
+
+    def compute(self, grid, cells):
+        """uint32 gain of every candidate; cells: (n, 2) integer cells (x, y)."""
+        q = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 2))
+        out = np.zeros(len(q), np.uint32)
+        check(self.ctx.lib.bl_viewgain_compute(self.h, grid.h, q.ctypes.data if len(q) else None, len(q), out.ctypes.data if len(q) else None))
+        return out
+
+    def debugSeen(self, grid, x, y):
+        """(2R + 1, 2R + 1) uint8, 0 / 1: the seen set of one candidate in the window around it."""
+        side = 2 * self.radius_cells + 1
+        out = np.zeros((side, side), np.uint8)
+        check(self.ctx.lib.bl_viewgain_debug_seen(self.h, grid.h, int(x), int(y), out.ctypes.data))
+        return out
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_viewgain_destroy(self.h)
+            self.h = None
+
+
+def plan_path_to_frontier_by_gain(frontiers, robotPose, grid, planner, view=None, reach_cells=None, stride=1, min_gain=1, gain_weight=1,
+                                  obstacle_gain=NAV_OBSTACLE_GAIN, cap=1 << 16):
+    """The viewpoint near a frontier that weighs expected new map against travel cost.  Candidates are the cells within Chebyshev
+    reach_cells (default n_min, as plan_path_to_frontier_by_cost) of a frontier cell that the robot can reach, in row-major order,
+    thinned to x % stride == 0 and y % stride == 0; cost(c) is the navigation field rooted at the robot's cell, gain(c) the view
+    gain (`view`: a ViewGain, default ViewGain() on the grid's context).  Of the candidates with gain >= min_gain the one that
+    maximises gain_weight * gain - cost is chosen, ties by lower cost, then lower y, then lower x; the path is the cheapest one to
+    that cell (a second field, rooted there).  gain_weight = 1 is UNTUNED -- one newly seen cell is worth a tenth of a straight
+    step --: a knob for the caller, not a result.
+    Returns (path, frontier index, chosen cell (x, y) or None, gain, cost): the candidate's frontier is the owner of the
+    lowest-indexed frontier cell within reach of it.  An empty frontier list gives the empty path and -1; no surviving candidate
+    gives the robot's 1-pose path and -1."""
+    dist = planner.distances_
+    ctx = dist.ctx
+    fr = frontiers.cells() if isinstance(frontiers, Frontiers) else [np.asarray(f, dtype=np.float32).reshape(-1, 2) for f in frontiers]
+    if len(fr) == 0:
+        return [], -1, None, 0, NAV_UNREACHED
+    none = ([Pose(robotPose.utime, robotPose.x, robotPose.y, robotPose.theta)], -1, None, 0, NAV_UNREACHED)
+    if reach_cells is None:
+        reach_cells = nav_min_traversable_cells(dist, planner.searchParams_)
+        if reach_cells is None:
+            reach_cells = 0
+    reach_cells, stride = int(reach_cells), max(int(stride), 1)
+    mpc, cpm, ox, oy = dist.frame()
+    w, h = dist.shape()
+    rvx = (float(np.float32(robotPose.x)) - float(ox)) * float(cpm)      # the cell of a pose as the navigation field finds it
+    rvy = (float(np.float32(robotPose.y)) - float(oy)) * float(cpm)
+    if not (rvx > -1.0 and rvx < w and rvy > -1.0 and rvy < h):
+        return none
+    fcell, owner = [], []
+    for k, f in enumerate(fr):
+        for x, y in f:                                   # global_position_to_grid_cell (grid_utils.hpp:33-38)
+            fcell.append((int((float(x) - float(ox)) * float(cpm)), int((float(y) - float(oy)) * float(cpm))))
+            owner.append(k)
+    fcell = np.array(fcell, np.int64).reshape(-1, 2)
+    on = (fcell[:, 0] >= 0) & (fcell[:, 0] < w) & (fcell[:, 1] >= 0) & (fcell[:, 1] < h)
+    idx = np.flatnonzero(on)
+    if len(idx) == 0:
+        return none
+    # every cell within reach of a frontier cell inside the grid, with the lowest index of such a frontier cell
+    d = np.arange(-reach_cells, reach_cells + 1)         # arrays over (frontier cell, dy, dx); the 0 * terms only broadcast
+    cx =(fcell[idx, 0][:, None, None] + d[None, None, :]) + 0 * d[None, :, None]
+    cy = (fcell[idx, 1][:, None, None] + d[None, :, None]) + 0 * d[None, None, :]
+    who = np.broadcast_to(idx[:, None, None], cx.shape)
+    keep = (cx >= 0) & (cx < w) & (cy >= 0) & (cy < h) & (cx % stride == 0) & (cy % stride == 0)
+    flat, who = (cy * w + cx)[keep], who[keep]
+    if len(flat) == 0:
+        return none
+    order = np.lexsort((who, flat))                      # row-major, the lowest frontier cell first within a cell
+    flat, who = flat[order], who[order]
+    first = np.concatenate(([True], flat[1:] != flat[:-1]))
+    flat, who = flat[first], who[first]
+    cand = np.stack([flat % w, flat // w], axis=1).astype(np.int32)
+    nf = NavigationField(ctx)
+    vg = view or ViewGain(ctx=ctx)
+    try:
+        nf.compute(dist, nav_params(planner.searchParams_, obstacle_gain, 0), np.array([[int(rvx), int(rvy)]], np.int32))
+        cost = nf.gather(cand)
+        ok = cost != NAV_UNREACHED                       # UNREACHED also where the cell is not traversable
+        cand, who, cost = cand[ok], who[ok], cost[ok].astype(np.int64)
+        gain = vg.compute(grid, cand).astype(np.int64)
+        ok = gain >= int(min_gain)
+        cand, who, cost, gain = cand[ok], who[ok], cost[ok], gain[ok]
+        if len(cand) == 0:
+            return none
+        u = int(gain_weight) * gain - cost
+        best = np.lexsort((cand[:, 0], cand[:, 1], cost, -u))[0]
+        nf.compute(dist, nav_params(planner.searchParams_, obstacle_gain, 0), cand[best:best + 1])
+        paths, _, _ = nf.paths([robotPose], cap_each=cap)
+    finally:
+        nf.close()
+        if view is None:
+            vg.close()
+    return paths[0], owner[int(who[best])], (int(cand[best, 0]), int(cand[best, 1])), int(gain[best]), int(cost[best])
+
+
 # exploration_status_t (lcmtypes/exploration_status_t.lcm:3-11)
 STATE_INITIALIZING, STATE_EXPLORING_MAP, STATE_RETURNING_HOME, STATE_COMPLETED_EXPLORATION, STATE_FAILED_EXPLORATION = 0, 1, 2, 3, 4
 STATUS_IN_PROGRESS, STATUS_COMPLETE, STATUS_FAILED = 0, 1, 2

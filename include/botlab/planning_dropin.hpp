@@ -335,4 +335,6 @@ private:
 
 }  // namespace botlab_hip
 
+#include <botlab/view_gain.hpp>      // ViewGainT, plan_path_to_frontier_by_gain_t (built on frontier_t and the planner above)
+
 #endif  // BOTLAB_PLANNING_DROPIN_HPP

@@ -697,6 +697,44 @@ int bl_navfield_tables(bl_navfield* nf, uint8_t* traversable, int32_t* penalty, 
  * goal-set cells */
 int bl_navfield_stats(bl_navfield* nf, int64_t* out);
 
+/* ------------------------------------------------------------------ view gain (no reference counterpart)
+ * How much unknown map a sensor standing on a candidate cell could see: the number of distinct unknown cells that a fan of rays
+ * cast from the cell reaches.  All of it is integer arithmetic on the int8 log-odds cells of a bl_grid.
+ *   Cell classes of a log-odds value v: blocking when v > occupied_above (default 0); unknown when unknown_lo <= v <= unknown_hi
+ *     (defaults 0 and 0); anything else is seen through.  Blocking is tested first.
+ *   Ray table, built once per parameter set on the host in double: ray k of K = n_rays ends at the offset
+ *     (lround(R * cos(t)), lround(R * sin(t))), t = 2.0 * M_PI * k / K evaluated left to right, R = radius_cells; the host's cos, sin
+ *     and lround.  1 <= R <= 255, 1 <= K <= 4096.  A ray whose end is (0, 0) visits nothing.
+ *   Line: the all-integer Bresenham walk from (0, 0) to the end offset (ex, ey), start cell excluded, end cell included:
+ *     dx = |ex|, dy = |ey|, sx = sign(ex), sy = sign(ey), err = dx - dy, (x, y) = (0, 0); until (x, y) = (ex, ey):
+ *     e2 = 2 * err; if e2 >= -dy { err -= dy; x += sx; }  if e2 <= dx { err += dx; y += sy; }  then visit (x, y).
+ *     The walk is relative to the candidate: the same for every candidate.
+ *   Seen set of a candidate cell c, taking the cells c + (x, y) of each ray in order: the ray ends at the first cell outside the
+ *     grid, and at the first blocking cell, which is not seen; every unknown cell before that point is seen.  Unknown cells do not
+ *     stop a ray (the optimistic rule).  The candidate's own cell is never examined, whatever it holds.
+ *   Gain: gain(c) = the number of distinct cells in the seen set, uint32.  Rays overlap near the candidate, so this is not a sum
+ *     over rays; it does not depend on the order the rays are taken in.  A candidate outside the grid has gain 0.
+ * How it is computed (bl_viewgain.hip): one workgroup per candidate, a bitmap of the (2R + 1)^2 window in LDS, the rays dealt over
+ * the threads.  Calls are stream-ordered on the ctx stream and synchronous on return; the bl_grid must belong to the same ctx. */
+typedef struct bl_viewgain_params_t {
+    int32_t radius_cells;              /* R, 1 .. 255 */
+    int32_t n_rays;                    /* K, 1 .. 4096 */
+    int32_t occupied_above;            /* -128 .. 127 (default 0) */
+    int32_t unknown_lo;                /* -128 <= unknown_lo <= unknown_hi <= 127 (defaults 0, 0) */
+    int32_t unknown_hi;
+} bl_viewgain_params_t;                /* 20 bytes */
+typedef struct bl_viewgain bl_viewgain;
+int bl_viewgain_create(bl_ctx* ctx, bl_viewgain** out);               /* buffers grow on demand */
+void bl_viewgain_destroy(bl_viewgain* vg);
+/* builds and uploads the ray table; BL_ERR_ARG for parameters out of range (the handle then has none) */
+int bl_viewgain_set_params(bl_viewgain* vg, const bl_viewgain_params_t* params);
+/* the table the kernels use: *n = n_rays, xy (optional) = x0, y0, x1, y1, ...; BL_ERR_STATE before set_params */
+int bl_viewgain_ray_ends(bl_viewgain* vg, int32_t* xy, int* n);
+/* gain of n candidate cells (x0, y0, x1, y1, ...) in one launch; n == 0 is fine; BL_ERR_STATE before set_params */
+int bl_viewgain_compute(bl_viewgain* vg, const bl_grid* map, const int32_t* xy_cells, int n, uint32_t* out_gain);
+/* the seen set of one candidate: (2R + 1)^2 bytes, 0 / 1, row-major, the window around the cell (byte (dy + R) * (2R + 1) + dx + R) */
+int bl_viewgain_debug_seen(bl_viewgain* vg, const bl_grid* map, int x, int y, uint8_t* out);
+
 /* ------------------------------------------------------------------ the exploration step, asynchronously  (src/planning/exploration.cpp:277-369)
  * Exploration::executeExploringMap on every published map: planner_.setMap, find_map_frontiers, and -- when the robot is within
  * 0.5 m of currentTarget_ or has none -- plan_path_to_frontier; then the status / next-state rule (:332-368; D10).  A submission
