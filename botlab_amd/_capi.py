@@ -113,6 +113,15 @@ class ViewGainParams(C.Structure):
 
 
 assert C.sizeof(ViewGainParams) == 20
+
+
+class RBSlamResult(C.Structure):
+    """bl_rbslam_result_t: what one update of the Rao-Blackwellized SLAM hands back (64 bytes)."""
+    _fields_ = [("moved", C.c_int32), ("resampled", C.c_int32), ("best", C.c_int32), ("pad", C.c_int32), ("best_pose", Pose),
+                ("S", C.c_uint64), ("Q_lo", C.c_uint64), ("Q_hi", C.c_uint64)]
+
+
+assert C.sizeof(RBSlamResult) == 64
 assert C.sizeof(ScanMatchParams) == 28 and C.sizeof(ScanMatchResult) == 56
 assert C.sizeof(ScanMatchWideParams) == 32 and C.sizeof(ScanMatchWideStats) == 40
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
@@ -283,6 +292,19 @@ SIGNATURES = {
     "bl_viewgain_ray_ends": (C.c_int, [_vp, _vp, _P(C.c_int)]),
     "bl_viewgain_compute": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "bl_viewgain_debug_seen": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp]),
+    "bl_rbslam_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int8, C.c_int8,
+                                   _P(_vp)]),
+    "bl_rbslam_destroy": (None, [_vp]),
+    "bl_rbslam_set_resampling": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    "bl_rbslam_set_noise_seed": (C.c_int, [_vp, C.c_uint64]),
+    "bl_rbslam_init_at_pose": (C.c_int, [_vp, _P(Pose), C.c_uint64]),
+    "bl_rbslam_set_particles": (C.c_int, [_vp, _vp, _vp]),
+    "bl_rbslam_get_particles": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "bl_rbslam_update": (C.c_int, [_vp, _P(Pose), _P(Lidar), C.c_int, _vp, _P(RBSlamResult)]),
+    "bl_rbslam_map_download": (C.c_int, [_vp, C.c_int, _vp]),
+    "bl_rbslam_map_upload": (C.c_int, [_vp, C.c_int, _vp]),
+    "bl_rbslam_best_map": (C.c_int, [_vp, _vp]),
+    "bl_rbslam_debug_last": (C.c_int, [_vp, _vp, _vp]),
     "bl_lcm_fingerprint": (C.c_uint64, [C.c_int]),
     "bl_lcm_encode_pose": (C.c_int64, [C.c_int, _P(Pose), _vp, C.c_int64]),
     "bl_lcm_encode_lidar": (C.c_int64, [_P(Lidar), _vp, _vp, C.c_int64]),

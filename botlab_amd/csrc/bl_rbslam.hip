@@ -1,0 +1,951 @@
+// bl_rbslam.hip -- Rao-Blackwellized grid SLAM (FastSLAM on grids): P particles, each with a pose, a parent pose, a cumulative
+// score and its OWN W x H int8 map.  The definition is in include/botlab_hip.h ("bl_rbslam"); tests/rb_slam_model.py is the same
+// definition over the reference's per-particle entry points, and the two agree bit for bit.
+//
+// One moved update is five stream-ordered launches, no host loop over particles and no host round trip in between:
+//   k_rb_plan    one workgroup: S and Q of the units the last weighing left, the exact "resampling is due" test, and -- when due --
+//                the integer prefix, the low-variance search, the particle -> slot table and the list of map copies
+//   k_rb_copy    every map copy of the resampling in ONE launch, 16-byte vector loads and stores
+//   k_rb_weigh   ActionModel::applyAction and SensorModel::likelihood of every particle against its own map: a wave per particle,
+//                the rays across its lanes, the <= 3 cells of scoreRay gathered from the particle's map through L2
+//   k_rb_reduce  one workgroup: units, S, Q and the best particle
+//   k_rb_map     Mapping::updateMap of all P maps: a workgroup per (particle, window tile), hit and miss counts of the tile in an
+//                LDS window of uint16 counters, one owner thread per cell
+// The sensor model's and the mapper's arithmetic is restated here from bl_mcl.hip / bl_mapping.hip with bl_math.h's bit-exact pieces.
+#include <stdio.h>
+#include <string.h>
+
+#include "bl_internal.h"
+
+#define RB_MAX_PARTICLES 4096
+#define RB_PLAN_THREADS 1024
+#define RB_PLAN_ITEMS (RB_MAX_PARTICLES / RB_PLAN_THREADS)
+#define RB_WEIGH_THREADS 256
+#define RB_MAP_THREADS 512
+#define RB_MAP_COUNTERS (20 * 1024)          // uint16 counters of one window tile: 40 KB of LDS, so that three to four workgroups share a CU
+#define RB_MAP_TILE_W 256                    // widest tile; a window up to this wide is cut into horizontal strips only
+#define RB_MAP_SEG 16                        // cells per walk segment
+#define RB_MAP_SEG_RAYS 512                  // rays whose cells and segment table are kept in LDS (longer scans: a serial walk per ray)
+#define RB_MAP_MAX_RAYS 8192
+#define RB_CELL_LIMIT (1 << 24)              // |cell coordinate| bound for a ray to be traced (rejects NaN / inf geometry)
+#define RB_COPY_THREADS 256
+#define RB_COPY_VEC 4                        // int4 per thread and item: 16 KB per workgroup item
+#define RB_SCORE_SAT (1ll << 33)             // BL_RBSLAM_SCORE_MAX (botlab_hip.h)
+
+struct rb_state {
+    unsigned long long S, Q_lo, Q_hi;        // over the units of the last weighing
+    int weighed, resampled, ncopy, best;
+    bl_pose_xyt_t best_pose;
+};
+
+struct bl_rbslam {
+    bl_ctx* ctx;
+    int P;
+    bl_frame frame;
+    size_t stride;                           // bytes between two maps (W * H rounded up to 16)
+    float max_laser; int hit, miss;
+    uint32_t num, den;
+    int8_t* maps;                            // P slots
+    int8_t* staging;                         // one map: upload / download
+    float4* pose[2]; int cur;                // (x, y, theta, -)
+    float4* parent;
+    long long* cum;
+    unsigned long long* units;
+    int32_t* like; int32_t* idx; int32_t* slot; int2* copies;
+    float* d_noise;
+    rb_state* state;
+    rb_state* h_state;                       // pinned
+    bl_particle_t* d_export;
+    int64_t pose_utime, parent_utime;
+    bl_pose_xyt_t prev_odom;
+    bool action_initialized;
+    double rot1, trans, rot2;
+    uint64_t noise_seed; uint32_t step;
+    bool initialized, map_latched;
+};
+
+// ---------------------------------------------------------------- device helpers
+// ActionModel noise and initializeFilterAtPose draw exactly as bl_mcl.hip's filter does (same counters, same arithmetic)
+__device__ __forceinline__ void rb_philox_normals3(uint32_t m, uint32_t step, uint32_t k0, uint32_t k1, float z[3])
+{
+    uint32_t o[4];
+    bl_philox4x32(m, step, 0x6d636c31u, 0, k0, k1, o);
+    float u1 = ((float)(o[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
+    float u2 = ((float)(o[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    float u3 = ((float)(o[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
+    float u4 = ((float)(o[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
+    float s2, c2, c4;
+    sincosf(6.2831853071795864769f * u2, &s2, &c2);
+    c4 = cosf(6.2831853071795864769f * u4);
+    z[0] = ra * c2; z[1] = ra * s2; z[2] = rb * c4;
+}
+
+template <class T>
+__device__ __forceinline__ T rb_wave_incl_scan(T v, int lane)
+{
+    for (int off = 1; off < 64; off <<= 1) {
+        T t = __shfl_up(v, off, 64);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
+// exclusive scan over the workgroup's threads in thread order; *total: the sum.  s_w: one slot per wave.  Ends with a barrier.
+template <class T>
+__device__ __forceinline__ T rb_block_excl_scan(T v, T* s_w, T* total)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const T incl = rb_wave_incl_scan(v, lane);
+    __syncthreads();                                            // s_w may still be read from the previous use
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    T base = 0, tot = 0;
+    for (int w = 0; w < nw; ++w) { const T x = s_w[w]; if (w < wave) base += x; tot += x; }
+    *total = tot;
+    return base + incl - v;
+}
+
+// S and Q = sum u^2 of the workgroup's units.  u < 2^43 (RB_SCORE_SAT): with u = a 2^22 + b, a < 2^21, the three sums of a^2, a b and
+// b^2 over <= 4096 particles stay below 2^56 and are plain 64-bit reductions; one thread assembles the 128-bit Q.
+struct rb_sums { unsigned long long S, A2, AB, B2; };
+__device__ __forceinline__ void rb_sums_add(rb_sums& s, unsigned long long u)
+{
+    const unsigned long long a = u >> 22, b = u & ((1ull << 22) - 1ull);
+    s.S += u; s.A2 += a * a; s.AB += a * b; s.B2 += b * b;
+}
+__device__ __forceinline__ unsigned __int128 rb_q_of(const rb_sums& s)
+{
+    return ((unsigned __int128)s.A2 << 44) + ((unsigned __int128)s.AB << 23) + (unsigned __int128)s.B2;
+}
+__device__ __forceinline__ unsigned long long rb_wave_sum_u64(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// every thread gets the workgroup's sums.  s_r: 4 slots per wave.
+__device__ __forceinline__ rb_sums rb_block_sums(rb_sums s, unsigned long long* s_r)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    s.S = rb_wave_sum_u64(s.S); s.A2 = rb_wave_sum_u64(s.A2); s.AB = rb_wave_sum_u64(s.AB); s.B2 = rb_wave_sum_u64(s.B2);
+    __syncthreads();
+    if (lane == 0) { s_r[4 * wave] = s.S; s_r[4 * wave + 1] = s.A2; s_r[4 * wave + 2] = s.AB; s_r[4 * wave + 3] = s.B2; }
+    __syncthreads();
+    rb_sums t = {0, 0, 0, 0};
+    for (int w = 0; w < nw; ++w) { t.S += s_r[4 * w]; t.A2 += s_r[4 * w + 1]; t.AB += s_r[4 * w + 2]; t.B2 += s_r[4 * w + 3]; }
+    return t;
+}
+
+// ---------------------------------------------------------------- plan: due?, prefix, search, slot table, copy list
+struct rb_plan_args {
+    int P;
+    const unsigned long long* units;
+    rb_state* state;
+    int32_t* idx; int32_t* slot; int2* copies; long long* cum;
+    double r, M_inv;                         // particle_filter.cpp:89-92 with M = P
+    uint32_t num, den;
+};
+
+__global__ __launch_bounds__(RB_PLAN_THREADS) void k_rb_plan(rb_plan_args a)
+{
+    __shared__ unsigned long long s_pre[RB_MAX_PARTICLES];      // inclusive prefix; afterwards: has[] and dead[] (int each)
+    __shared__ unsigned short s_idx[RB_MAX_PARTICLES];
+    __shared__ unsigned long long s_w64[RB_PLAN_THREADS / 64 * 4];
+    __shared__ int s_w32[RB_PLAN_THREADS / 64];
+    __shared__ int s_due;
+    const int tid = threadIdx.x, P = a.P;
+    const int i0 = tid * RB_PLAN_ITEMS;                          // this thread's particles: i0 .. i0 + 3
+    unsigned long long u[RB_PLAN_ITEMS];
+    rb_sums sums = {0, 0, 0, 0};
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) {
+        u[k] = i0 + k < P ? a.units[i0 + k] : 0ull;
+        rb_sums_add(sums, u[k]);
+        mine += u[k];
+    }
+    unsigned long long S;
+    unsigned long long run = rb_block_excl_scan(mine, s_w64, &S);
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) { run += u[k]; if (i0 + k < P) s_pre[i0 + k] = run; }
+    const rb_sums tot = rb_block_sums(sums, s_w64);
+    if (tid == 0) {
+        // due iff den S^2 <= num P Q, exactly: S < 2^55 and Q < 2^98, num, den < 2^16 (botlab_hip.h)
+        const unsigned __int128 lhs = (unsigned __int128)S * S * a.den;
+        const unsigned __int128 rhs = rb_q_of(tot) * ((unsigned long long)a.num * (unsigned long long)P);
+        const int due = a.state->weighed && lhs <= rhs;
+        s_due = due;
+        a.state->resampled = due;
+        if (!due) a.state->ncopy = 0;
+    }
+    __syncthreads();
+    if (!s_due) {
+#pragma unroll
+        for (int k = 0; k < RB_PLAN_ITEMS; ++k) if (i0 + k < P) a.idx[i0 + k] = i0 + k;
+        return;
+    }
+    // ---- low-variance search by the integer-prefix rule: T_m = (r + m / M) S, first i with T_m <= prefix_i, clamped to P - 1
+    const double Sd = (double)S;
+    int src[RB_PLAN_ITEMS];
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) {
+        const int m = i0 + k;
+        src[k] = 0;
+        if (m < P) {
+            const double T = (a.r + m * a.M_inv) * Sd;
+            int lo = 0, hi = P - 1;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (T <= (double)s_pre[mid]) hi = mid; else lo = mid + 1; }
+            src[k] = lo;
+            s_idx[m] = (unsigned short)lo;
+        }
+    }
+    __syncthreads();                                            // the prefix is dead from here on
+    int* s_has = (int*)s_pre;
+    int* s_dead = s_has + RB_MAX_PARTICLES;
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) if (i0 + k < P) s_has[i0 + k] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) if (i0 + k < P) s_has[src[k]] = 1;
+    __syncthreads();
+    // the sources ascend with m: the first child of a source is the one whose predecessor has another source.  It keeps the slot;
+    // the k-th other child (in order of m) takes the slot of the k-th particle that died (in order of index).
+    bool extra[RB_PLAN_ITEMS];
+    int n_extra = 0, n_dead = 0;
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) {
+        const int m = i0 + k;
+        extra[k] = m < P && m > 0 && s_idx[m - 1] == src[k];
+        n_extra += extra[k] ? 1 : 0;
+        n_dead += (m < P && !s_has[m]) ? 1 : 0;
+    }
+    int total_extra, total_dead;
+    int rank_extra = rb_block_excl_scan(n_extra, s_w32, &total_extra);
+    int rank_dead = rb_block_excl_scan(n_dead, s_w32, &total_dead);
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) if (i0 + k < P && !s_has[i0 + k]) s_dead[rank_dead++] = i0 + k;
+    __syncthreads();
+    int new_slot[RB_PLAN_ITEMS];
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) {
+        const int m = i0 + k;
+        new_slot[k] = 0;
+        if (m < P) {
+            const int from = a.slot[src[k]];
+            new_slot[k] = from;
+            if (extra[k] && rank_extra < total_dead) {           // (total_extra == total_dead: P children, one first child per live source)
+                const int to = a.slot[s_dead[rank_extra]];
+                a.copies[rank_extra] = make_int2(from, to);
+                new_slot[k] = to;
+                ++rank_extra;
+            }
+        }
+    }
+    __syncthreads();                                            // every read of the old slot table is done
+#pragma unroll
+    for (int k = 0; k < RB_PLAN_ITEMS; ++k) {
+        const int m = i0 + k;
+        if (m < P) { a.slot[m] = new_slot[k]; a.idx[m] = src[k]; a.cum[m] = 0; }
+    }
+    if (tid == 0) a.state->ncopy = total_extra < total_dead ? total_extra : total_dead;
+}
+
+// ---------------------------------------------------------------- the map copies of a resampling, one launch
+__global__ __launch_bounds__(RB_COPY_THREADS) void k_rb_copy(int8_t* maps, size_t stride, const int2* __restrict__ copies,
+                                                             const rb_state* __restrict__ state, int chunks)
+{
+    const int ncopy = state->ncopy;
+    const size_t n16 = stride / 16;
+    const long long items = (long long)ncopy * chunks;
+    for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int c = (int)(it / chunks), ch = (int)(it - (long long)c * chunks);
+        const int2 sd = copies[c];
+        const int4* s4 = (const int4*)(maps + (size_t)sd.x * stride);
+        int4* d4 = (int4*)(maps + (size_t)sd.y * stride);
+        const size_t base = (size_t)ch * RB_COPY_THREADS * RB_COPY_VEC + threadIdx.x;
+        int4 v[RB_COPY_VEC];
+#pragma unroll
+        for (int q = 0; q < RB_COPY_VEC; ++q) { const size_t i = base + (size_t)q * RB_COPY_THREADS; if (i < n16) v[q] = s4[i]; }
+#pragma unroll
+        for (int q = 0; q < RB_COPY_VEC; ++q) { const size_t i = base + (size_t)q * RB_COPY_THREADS; if (i < n16) d4[i] = v[q]; }
+    }
+}
+
+// one map <-> a flat buffer, by slot; which < 0: the best particle's
+__global__ __launch_bounds__(RB_COPY_THREADS) void k_rb_map_io(int8_t* maps, size_t stride, const int32_t* __restrict__ slot,
+                                                               const rb_state* __restrict__ state, int which, int8_t* flat, size_t n, int to_maps)
+{
+    const int p = which < 0 ? state->best : which;
+    int8_t* m = maps + (size_t)slot[p] * stride;
+    const size_t n16 = ((((size_t)flat) & 15) == 0) ? n / 16 : 0;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (size_t)gridDim.x * blockDim.x;
+    if (to_maps) {
+        for (size_t i = t; i < n16; i += nt) ((int4*)m)[i] = ((const int4*)flat)[i];
+        for (size_t i = n16 * 16 + t; i < n; i += nt) m[i] = flat[i];
+    } else {
+        for (size_t i = t; i < n16; i += nt) ((int4*)flat)[i] = ((const int4*)m)[i];
+        for (size_t i = n16 * 16 + t; i < n; i += nt) flat[i] = m[i];
+    }
+}
+
+// ---------------------------------------------------------------- action + weigh
+struct rb_weigh_args {
+    int P, R;
+    const float4* src; float4* dst; float4* parent;
+    const int32_t* idx; const int32_t* slot;
+    const int8_t* maps; size_t stride; bl_frame frame;
+    const float* ranges; const float* thetas; const int64_t* times;
+    int64_t t_begin; double t_den; int interp;
+    const float* noise;
+    double rot1, trans, rot2, rot1Std, transStd, rot2Std;
+    uint32_t seed_lo, seed_hi, step;
+    long long* cum; unsigned long long* units; int32_t* like;
+};
+
+__device__ __forceinline__ int rb_grid_odds(const int8_t* __restrict__ cells, const bl_frame& f, int x, int y)
+{
+    const bool in = (unsigned int)x < (unsigned int)f.width && (unsigned int)y < (unsigned int)f.height;
+    const int v = cells[in ? (size_t)y * f.width + x : (size_t)0];
+    return in ? v : 0;                                          // OccupancyGrid::logOdds (occupancy_grid.cpp:63-71)
+}
+
+// SensorModel::scoreRay (sensor_model.cpp:28-59) in half-units: 2 * odds, o1 or o2
+__device__ __forceinline__ int rb_score_ray(const int8_t* __restrict__ cells, const bl_frame& f, float sx, float sy, float range, float cs, float sn)
+{
+    const float tx = range * cs * f.cpm, ty = range * sn * f.cpm;
+    const int ex = (int)(tx + sx), ey = (int)(ty + sy);
+    const int xx = (int)((2.0f * tx) + sx), xy = (int)((2.0f * ty) + sy);      // (2 range cos) cpm == 2 ((range cos) cpm) bit for bit
+    int ax, ay, bx, by;
+    bl_bresenham_first_step(ex, ey, (int)sx, (int)sy, &ax, &ay);
+    bl_bresenham_first_step(ex, ey, xx, xy, &bx, &by);
+    const int odds = rb_grid_odds(cells, f, ex, ey);
+    const int o1 = rb_grid_odds(cells, f, ax, ay);
+    const int o2 = rb_grid_odds(cells, f, bx, by);
+    return odds > 0 ? 2 * odds : (o1 > 0 ? o1 : (o2 > 0 ? o2 : 0));
+}
+
+__global__ __launch_bounds__(RB_WEIGH_THREADS) void k_rb_weigh(rb_weigh_args a)
+{
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * (RB_WEIGH_THREADS / 64) + (threadIdx.x >> 6);
+    if (m >= a.P) return;                                       // whole waves; no barrier below
+    const float4 s = a.src[a.idx[m]];
+    // ---- ActionModel::applyAction (action_model.cpp:78-103), the same in every lane of the wave
+    float n1, n2, n3;
+    if (a.noise) { n1 = a.noise[3 * m]; n2 = a.noise[3 * m + 1]; n3 = a.noise[3 * m + 2]; }
+    else {
+        float z[3];
+        rb_philox_normals3((uint32_t)m, a.step, a.seed_lo, a.seed_hi, z);
+        n1 = (float)(a.rot1 + a.rot1Std * (double)z[0]);
+        n2 = (float)(a.trans + a.transStd * (double)z[1]);
+        n3 = (float)(a.rot2 + a.rot2Std * (double)z[2]);
+    }
+    const float head = s.z + n1;
+    double hs, hc;
+    sincos((double)head, &hs, &hc);
+    const float px = (float)((double)s.x + (double)n2 * hc);
+    const float py = (float)((double)s.y + (double)n2 * hs);
+    const float pth = bl_wrap_to_pi(s.z + n1 + n3);
+    if (lane == 0) { a.dst[m] = make_float4(px, py, pth, 0.0f); a.parent[m] = make_float4(s.x, s.y, s.z, 0.0f); }
+    // ---- SensorModel::likelihood (sensor_model.cpp:14-25) over MovingLaserScan(scan, parent_pose, pose), against the particle's own map
+    const int8_t* cells = a.maps + (size_t)a.slot[m] * a.stride;
+    const bl_pose3 pb = {s.x, s.y, s.z}, pe = {px, py, pth};
+    int acc = 0;
+    for (int n = lane; n < a.R; n += 64) {                      // the host keeps only rays with range > 0.15f (moving_laser_scan.cpp:24)
+        const bl_pose3 rp = a.interp ? bl_interpolate_pose(pb, pe, bl_interp_ratio(a.times[n], a.t_begin, a.t_den)) : pe;
+        const float theta = bl_wrap_to_pi(rp.theta - a.thetas[n]);
+        float sx, sy, sn, cs;
+        bl_global_to_grid(rp.x, rp.y, a.frame, &sx, &sy);
+        bl_sincosf(theta, &sn, &cs);
+        acc += rb_score_ray(cells, a.frame, sx, sy, a.ranges[n], cs, sn);
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (lane == 0) {
+        long long c = a.cum[m] + (long long)acc;                // k_rb_plan has zeroed it when it resampled
+        if (c > RB_SCORE_SAT) c = RB_SCORE_SAT;
+        a.cum[m] = c;
+        a.like[m] = acc;
+        a.units[m] = c > 0 ? (unsigned long long)c * 1000ull : 2ull;
+    }
+}
+
+// ---------------------------------------------------------------- units -> S, Q, best
+__global__ __launch_bounds__(RB_PLAN_THREADS) void k_rb_reduce(int P, const unsigned long long* __restrict__ units, const float4* __restrict__ pose,
+                                                               int64_t utime, int weighed, rb_state* state)
+{
+    __shared__ unsigned long long s_w64[RB_PLAN_THREADS / 64 * 4];
+    __shared__ unsigned long long s_key[RB_PLAN_THREADS / 64];
+    const int tid = threadIdx.x;
+    rb_sums sums = {0, 0, 0, 0};
+    unsigned long long key = 0;                                 // (u, 4095 - index): the largest u, ties to the lowest index; u < 2^43
+    for (int i = tid; i < P; i += RB_PLAN_THREADS) {
+        const unsigned long long u = units[i];
+        rb_sums_add(sums, u);
+        const unsigned long long k = (u << 12) | (unsigned long long)(RB_MAX_PARTICLES - 1 - i);
+        key = k > key ? k : key;
+    }
+    const rb_sums tot = rb_block_sums(sums, s_w64);
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(key, off, 64); key = o > key ? o : key; }
+    if ((tid & 63) == 0) s_key[tid >> 6] = key;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 0; w < RB_PLAN_THREADS / 64; ++w) key = s_key[w] > key ? s_key[w] : key;
+        const int best = RB_MAX_PARTICLES - 1 - (int)(key & (RB_MAX_PARTICLES - 1));
+        const unsigned __int128 Q = rb_q_of(tot);
+        state->S = tot.S; state->Q_lo = (unsigned long long)Q; state->Q_hi = (unsigned long long)(Q >> 64);
+        state->best = best;
+        state->weighed = weighed;
+        const float4 p = pose[best];
+        bl_pose_xyt_t bp; bp.utime = utime; bp.x = p.x; bp.y = p.y; bp.theta = p.z;
+        state->best_pose = bp;
+    }
+}
+
+// ---------------------------------------------------------------- map update of all P maps
+struct rb_map_args {
+    int P, R;
+    int8_t* maps; size_t stride; bl_frame frame;
+    const int32_t* slot;
+    const float4* begin; const float4* end;  // parent poses and poses (a moved update), or the poses twice
+    const float* ranges; const float* thetas; const int64_t* times;
+    int64_t t_begin; double t_den; int interp;
+    float max_laser; int hit, miss;
+};
+
+// start cell and end cell of one ray (moving_laser_scan.cpp:22-37, mapping.cpp:45-49); x == 0x7fffffff: the ray takes no part
+__device__ __forceinline__ int4 rb_ray_cells(const rb_map_args& a, const bl_pose3& pb, const bl_pose3& pe, int r)
+{
+    int4 ray = make_int4(0x7fffffff, 0, 0, 0);
+    const float range = a.ranges[r];
+    if (range <= a.max_laser) {
+        const bl_pose3 rp = a.interp ? bl_interpolate_pose(pb, pe, bl_interp_ratio(a.times[r], a.t_begin, a.t_den)) : pe;
+        const float theta = bl_wrap_to_pi(rp.theta - a.thetas[r]);
+        float sn, cs, sx, sy;
+        bl_sincosf(theta, &sn, &cs);
+        bl_global_to_grid(rp.x, rp.y, a.frame, &sx, &sy);
+        const float fx = (range * cs * a.frame.cpm) + sx;
+        const float fy = (range * sn * a.frame.cpm) + sy;
+        const float lim = (float)RB_CELL_LIMIT;
+        if (fx > -lim && fx < lim && fy > -lim && fy < lim && sx > -lim && sx < lim && sy > -lim && sy < lim)
+            ray = make_int4((int)sx, (int)sy, (int)fx, (int)fy);
+    }
+    return ray;
+}
+
+__device__ __forceinline__ void rb_count(unsigned int* s_cnt, int c) { atomicAdd(&s_cnt[c >> 1], (c & 1) ? 0x10000u : 1u); }
+__device__ __forceinline__ int rb_count_of(const unsigned int* s_cnt, int c) { const unsigned int w = s_cnt[c >> 1]; return (int)((c & 1) ? (w >> 16) : (w & 0xffffu)); }
+
+// cells k0 .. k1 - 1 of the reference's Bresenham walk of `ray` (start included, end excluded; the closed form of bl_mapping.hip:
+// the major axis advances k, the minor axis floor((2 k dmin + dmaj) / (2 dmaj))), counted where they fall into the tile
+__device__ __forceinline__ void rb_walk(unsigned int* s_cnt, const int4 ray, int k0, int k1, int tx0, int ty0, int tx1, int ty1, int tw)
+{
+    const int dx = abs(ray.z - ray.x), dy = abs(ray.w - ray.y);
+    const int sx = ray.x < ray.z ? 1 : -1, sy = ray.y < ray.w ? 1 : -1;
+    const bool xmajor = dx >= dy;
+    const int dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
+    if (dmaj == 0) return;
+    const long long num = 2ll * k0 * dmin + dmaj;
+    int n = (int)(num / (2ll * dmaj));
+    long long rem = num - (long long)n * 2ll * dmaj;
+    for (int k = k0; k < k1; ++k) {
+        const int x = xmajor ? ray.x + sx * k : ray.x + sx * n;
+        const int y = xmajor ? ray.y + sy * n : ray.y + sy * k;
+        if (x >= tx0 && x <= tx1 && y >= ty0 && y <= ty1) rb_count(s_cnt, (y - ty0) * tw + (x - tx0));
+        rem += 2ll * dmin;
+        if (rem >= 2ll * dmaj) { rem -= 2ll * dmaj; n += 1; }
+    }
+}
+
+// One owner thread per cell of the tile: v' = HIT ? min(127, v + k c) : max(-128, v - k c) where the count c is not zero.
+template <bool HIT>
+__device__ __forceinline__ void rb_apply(int8_t* cells, int W, const unsigned int* s_cnt, int tx0, int ty0, int tw, int th, int k, bool dwords)
+{
+    const int tid = threadIdx.x;
+    if (dwords) {                                               // grid rows and tile columns are whole dwords: four cells per access
+        const int wq = tw >> 2, nitems = th * wq;
+        for (int it = tid; it < nitems; it += RB_MAP_THREADS) {
+            const int ry = it / wq, dq = it - ry * wq;
+            const unsigned long long c = *(const unsigned long long*)&s_cnt[(ry * tw + 4 * dq) >> 1];
+            if (!c) continue;
+            int* g = (int*)(cells + (size_t)(ty0 + ry) * W + tx0 + 4 * dq);
+            const int v = *g;
+            unsigned int nv = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int cnt = (int)((c >> (16 * b)) & 0xffffull);
+                const int val = (int)(int8_t)(v >> (8 * b));
+                const int r = HIT ? min(127, val + k * cnt) : max(-128, val - k * cnt);
+                nv |= ((unsigned int)r & 0xffu) << (8 * b);
+            }
+            *g = (int)nv;
+        }
+    } else {
+        for (int it = tid; it < tw * th; it += RB_MAP_THREADS) {
+            const int cnt = rb_count_of(s_cnt, it);
+            if (!cnt) continue;
+            const int ry = it / tw, cx = it - ry * tw;
+            int8_t* g = cells + (size_t)(ty0 + ry) * W + tx0 + cx;
+            const int val = *g;
+            *g = (int8_t)(HIT ? min(127, val + k * cnt) : max(-128, val - k * cnt));
+        }
+    }
+}
+
+// Mapping::updateMap (mapping.cpp:17-127) of particle blockIdx.x's map.  All hits are applied before any miss, as the reference's two
+// passes do, so a cell ends at max(-128, min(127, v + hit H) - miss M).  The window -- the bounding box of all ray cells clipped to the
+// grid -- is cut into tiles of at most RB_MAP_COUNTERS cells; the workgroups of a particle (gridDim.y of them) take its tiles in turn,
+// each forming the ray geometry itself.  Tiles are disjoint, so the workgroups of a particle never store to the same cell.
+__global__ __launch_bounds__(RB_MAP_THREADS) void k_rb_map(rb_map_args a)
+{
+    __shared__ unsigned int s_cnt[RB_MAP_COUNTERS / 2];
+    __shared__ int4 s_rays[RB_MAP_SEG_RAYS];
+    __shared__ int s_segp[RB_MAP_SEG_RAYS + 1];
+    __shared__ int s_wsum[RB_MAP_THREADS / 64];
+    __shared__ int s_box[4];
+    const int tid = threadIdx.x, lane = tid & 63, p = blockIdx.x;
+    const bool seg_walk = a.R <= RB_MAP_SEG_RAYS;
+    int8_t* cells = a.maps + (size_t)a.slot[p] * a.stride;
+    const float4 b4 = a.begin[p], e4 = a.end[p];
+    const bl_pose3 pb = {b4.x, b4.y, b4.z}, pe = {e4.x, e4.y, e4.z};
+    if (tid == 0) { s_box[0] = 0x7fffffff; s_box[1] = 0x7fffffff; s_box[2] = -0x7fffffff; s_box[3] = -0x7fffffff; }
+    __syncthreads();
+    // ---- ray geometry, bounding box, segment table
+    int bx_lo = 0x7fffffff, by_lo = 0x7fffffff, bx_hi = -0x7fffffff, by_hi = -0x7fffffff;
+    int segs = 0;
+    for (int r = tid; r < a.R; r += RB_MAP_THREADS) {
+        const int4 ray = rb_ray_cells(a, pb, pe, r);
+        if (ray.x != 0x7fffffff) {
+            bx_lo = min(bx_lo, min(ray.x, ray.z)); by_lo = min(by_lo, min(ray.y, ray.w));
+            bx_hi = max(bx_hi, max(ray.x, ray.z)); by_hi = max(by_hi, max(ray.y, ray.w));
+        }
+        if (seg_walk) {
+            s_rays[r] = ray;
+            if (ray.x != 0x7fffffff) segs = (max(abs(ray.z - ray.x), abs(ray.w - ray.y)) + RB_MAP_SEG - 1) / RB_MAP_SEG;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        bx_lo = min(bx_lo, __shfl_xor(bx_lo, off, 64)); by_lo = min(by_lo, __shfl_xor(by_lo, off, 64));
+        bx_hi = max(bx_hi, __shfl_xor(bx_hi, off, 64)); by_hi = max(by_hi, __shfl_xor(by_hi, off, 64));
+    }
+    if (lane == 0 && bx_lo != 0x7fffffff) {
+        atomicMin(&s_box[0], bx_lo); atomicMin(&s_box[1], by_lo);
+        atomicMax(&s_box[2], bx_hi); atomicMax(&s_box[3], by_hi);
+    }
+    if (seg_walk) {                                             // thread r holds ray r's segment count (R <= 512 threads)
+        int total;
+        const int excl = rb_block_excl_scan(segs, s_wsum, &total);
+        if (tid < a.R) s_segp[tid] = excl;
+        if (tid == 0) s_segp[a.R] = total;
+    }
+    __syncthreads();
+    const int W = a.frame.width, H = a.frame.height;
+    int bx0 = max(s_box[0], 0), by0 = max(s_box[1], 0);
+    int bx1 = min(s_box[2], W - 1), by1 = min(s_box[3], H - 1);
+    if (bx1 < bx0 || by1 < by0) return;                         // nothing inside the grid (uniform over the workgroup)
+    const bool dwords = (W & 3) == 0;                           // rows of whole dwords (the slots are 16-byte aligned)
+    if (dwords) { bx0 &= ~3; bx1 |= 3; }
+    const int ww = bx1 - bx0 + 1, wh = by1 - by0 + 1;
+    const int tw_max = ww < RB_MAP_TILE_W ? ww : RB_MAP_TILE_W; // a multiple of 4 when dwords
+    const int th_max = min(wh, RB_MAP_COUNTERS / tw_max);       // >= 80 rows
+    const int ntx = (ww + tw_max - 1) / tw_max, nty = (wh + th_max - 1) / th_max;
+    for (int tile = blockIdx.y; tile < ntx * nty; tile += gridDim.y) {
+        const int tyi = tile / ntx, txi = tile - tyi * ntx;
+        const int tx0 = bx0 + txi * tw_max, ty0 = by0 + tyi * th_max;
+        const int tx1 = min(tx0 + tw_max - 1, bx1), ty1 = min(ty0 + th_max - 1, by1);
+        const int tw = tx1 - tx0 + 1, th = ty1 - ty0 + 1;
+        const int nwords = (tw * th + 1) / 2;
+        __syncthreads();
+        for (int i = tid; i < nwords; i += RB_MAP_THREADS) s_cnt[i] = 0;
+        __syncthreads();
+        // ---- endpoint pass (mapping.cpp:42-57): H = rays ending in a cell
+        for (int r = tid; r < a.R; r += RB_MAP_THREADS) {
+            const int4 ray = seg_walk ? s_rays[r] : rb_ray_cells(a, pb, pe, r);
+            if (ray.x != 0x7fffffff && ray.z >= tx0 && ray.z <= tx1 && ray.w >= ty0 && ray.w <= ty1) rb_count(s_cnt, (ray.w - ty0) * tw + (ray.z - tx0));
+        }
+        __syncthreads();
+        rb_apply<true>(cells, W, s_cnt, tx0, ty0, tw, th, a.hit, dwords);
+        __syncthreads();                                        // this workgroup's stores are visible to its own loads below
+        for (int i = tid; i < nwords; i += RB_MAP_THREADS) s_cnt[i] = 0;
+        __syncthreads();
+        // ---- free-space pass (mapping.cpp:59-71, 101-127): M = rays crossing a cell
+        if (seg_walk) {
+            const int nseg = s_segp[a.R];
+            for (int sg = tid; sg < nseg; sg += RB_MAP_THREADS) {
+                int lo = 0, hi = a.R - 1;                       // last ray whose prefix <= sg
+                while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_segp[mid] <= sg) lo = mid; else hi = mid - 1; }
+                const int4 ray = s_rays[lo];
+                const int K = max(abs(ray.z - ray.x), abs(ray.w - ray.y));
+                const int k0 = (sg - s_segp[lo]) * RB_MAP_SEG;
+                rb_walk(s_cnt, ray, k0, min(K, k0 + RB_MAP_SEG), tx0, ty0, tx1, ty1, tw);
+            }
+        } else {
+            for (int r = tid; r < a.R; r += RB_MAP_THREADS) {
+                const int4 ray = rb_ray_cells(a, pb, pe, r);
+                if (ray.x == 0x7fffffff) continue;
+                rb_walk(s_cnt, ray, 0, max(abs(ray.z - ray.x), abs(ray.w - ray.y)), tx0, ty0, tx1, ty1, tw);
+            }
+        }
+        __syncthreads();
+        rb_apply<false>(cells, W, s_cnt, tx0, ty0, tw, th, a.miss, dwords);
+    }
+}
+
+// ---------------------------------------------------------------- init / export
+__global__ void k_rb_init(int P, bl_pose_xyt_t pose, uint32_t k0, uint32_t k1, float4* rec, float4* parent, long long* cum,
+                          unsigned long long* units, int32_t* like, int32_t* idx, int32_t* slot)
+{
+    // initializeFilterAtPose (particle_filter.cpp:16-34), drawn as bl_pf_init_at_pose draws
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= P) return;
+    float z[3];
+    rb_philox_normals3((uint32_t)m, 0xffffffffu, k0, k1, z);
+    float x = (float)((double)pose.x + 0.01 * (double)z[0]);
+    float y = (float)((double)pose.y + 0.01 * (double)z[1]);
+    float th = bl_wrap_to_pi((float)((double)pose.theta + 0.01 * (double)z[2]));
+    if (m == P - 1) { x = pose.x; y = pose.y; th = pose.theta; }
+    rec[m] = make_float4(x, y, th, 0.0f);
+    parent[m] = make_float4(x, y, th, 0.0f);
+    cum[m] = 0; units[m] = 2ull; like[m] = 0; idx[m] = m; slot[m] = m;
+}
+
+__global__ void k_rb_export(int P, const float4* rec, const float4* parent, const unsigned long long* units, const rb_state* state,
+                            int64_t pose_utime, int64_t parent_utime, bl_particle_t* out)
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= P) return;
+    const float4 r = rec[m], q = parent[m];
+    bl_particle_t o;
+    memset(&o, 0, sizeof(o));
+    o.pose.utime = pose_utime; o.pose.x = r.x; o.pose.y = r.y; o.pose.theta = r.z;
+    o.parent_pose.utime = parent_utime; o.parent_pose.x = q.x; o.parent_pose.y = q.y; o.parent_pose.theta = q.z;
+    o.weight = (double)units[m] / (double)state->S;
+    out[m] = o;
+}
+
+// ---------------------------------------------------------------- host side
+static int rb_launch_reduce(bl_rbslam* rb, int weighed)
+{
+    hipLaunchKernelGGL(k_rb_reduce, dim3(1), dim3(RB_PLAN_THREADS), 0, rb->ctx->stream, rb->P, rb->units, rb->pose[rb->cur], rb->pose_utime,
+                       weighed, rb->state);
+    BL_HIP(hipGetLastError());
+    return BL_OK;
+}
+
+static void rb_free(bl_rbslam* rb)
+{
+    void* d[] = {rb->maps, rb->staging, rb->pose[0], rb->pose[1], rb->parent, rb->cum, rb->units, rb->like, rb->idx, rb->slot, rb->copies,
+                 rb->d_noise, rb->state, rb->d_export};
+    for (void* q : d) if (q) (void)hipFree(q);
+    if (rb->h_state) (void)hipHostFree(rb->h_state);
+    delete rb;
+}
+
+extern "C" int bl_rbslam_create(bl_ctx* ctx, int num_particles, int width, int height, float meters_per_cell, float cells_per_meter,
+                                float origin_x, float origin_y, float max_laser_distance, int8_t hit_odds, int8_t miss_odds, bl_rbslam** out)
+{
+    BL_CHECK_ARG(ctx != nullptr && out != nullptr);
+    BL_CHECK_ARG(num_particles >= 1 && num_particles <= BL_RBSLAM_MAX_PARTICLES);
+    BL_CHECK_ARG(width > 0 && height > 0 && width <= 65535 && height <= 65535);
+    BL_CHECK_ARG(hit_odds >= 0 && miss_odds >= 0);
+    static_assert(BL_RBSLAM_MAX_PARTICLES == RB_MAX_PARTICLES && BL_RBSLAM_SCORE_MAX == RB_SCORE_SAT, "botlab_hip.h and bl_rbslam.hip disagree");
+    const size_t stride = ((size_t)width * height + 15) & ~(size_t)15;
+    if ((unsigned long long)stride * (unsigned long long)num_particles > BL_RBSLAM_MAX_MAP_BYTES) {
+        bl_set_error("bl_rbslam_create: %d maps of %d x %d cells exceed the cap of %llu bytes", num_particles, width, height,
+                     (unsigned long long)BL_RBSLAM_MAX_MAP_BYTES);
+        return BL_ERR_ARG;
+    }
+    BL_HIP(hipSetDevice(ctx->device));
+    bl_rbslam* rb = new bl_rbslam();
+    memset(rb, 0, sizeof(*rb));
+    rb->ctx = ctx; rb->P = num_particles;
+    rb->frame.width = width; rb->frame.height = height; rb->frame.mpc = meters_per_cell; rb->frame.cpm = cells_per_meter;
+    rb->frame.ox = origin_x; rb->frame.oy = origin_y;
+    rb->stride = stride;
+    rb->max_laser = max_laser_distance; rb->hit = hit_odds; rb->miss = miss_odds;
+    rb->num = 1; rb->den = 2;
+    const size_t P = (size_t)num_particles;
+    hipError_t e = hipMalloc((void**)&rb->maps, stride * P);
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->staging, stride);
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->pose[0], P * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->pose[1], P * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->parent, P * sizeof(float4));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->cum, P * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->units, P * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->like, P * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->idx, P * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->slot, P * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->copies, P * sizeof(int2));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->d_noise, P * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->state, sizeof(rb_state));
+    if (e == hipSuccess) e = hipMalloc((void**)&rb->d_export, P * sizeof(bl_particle_t));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&rb->h_state, sizeof(rb_state), hipHostMallocDefault);
+    if (e != hipSuccess) { bl_set_error("bl_rbslam_create: allocation failed: %s", hipGetErrorString(e)); rb_free(rb); return BL_ERR_HIP; }
+    *out = rb;
+    return BL_OK;
+}
+
+extern "C" void bl_rbslam_destroy(bl_rbslam* rb)
+{
+    if (!rb) return;
+    (void)hipSetDevice(rb->ctx->device);
+    (void)hipStreamSynchronize(rb->ctx->stream);
+    rb_free(rb);
+}
+
+extern "C" int bl_rbslam_set_resampling(bl_rbslam* rb, uint32_t num, uint32_t den)
+{
+    BL_CHECK_ARG(rb != nullptr);
+    BL_CHECK_ARG(num >= 1 && num <= 65535 && den >= 1 && den <= 65535);
+    rb->num = num; rb->den = den;
+    return BL_OK;
+}
+
+extern "C" int bl_rbslam_set_noise_seed(bl_rbslam* rb, uint64_t seed)
+{
+    BL_CHECK_ARG(rb != nullptr);
+    rb->noise_seed = seed;
+    return BL_OK;
+}
+
+static void rb_reset_run(bl_rbslam* rb, int64_t pose_utime, int64_t parent_utime)
+{
+    rb->cur = 0;
+    rb->pose_utime = pose_utime; rb->parent_utime = parent_utime;
+    rb->action_initialized = false;
+    rb->rot1 = rb->trans = rb->rot2 = 0;
+    rb->step = 0;
+    rb->map_latched = false;
+    rb->initialized = true;
+}
+
+extern "C" int bl_rbslam_init_at_pose(bl_rbslam* rb, const bl_pose_xyt_t* pose, uint64_t seed)
+{
+    BL_CHECK_ARG(rb != nullptr && pose != nullptr);
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    hipStream_t st = rb->ctx->stream;
+    BL_HIP(hipMemsetAsync(rb->maps, 0, rb->stride * (size_t)rb->P, st));
+    BL_HIP(hipMemsetAsync(rb->state, 0, sizeof(rb_state), st));
+    hipLaunchKernelGGL(k_rb_init, dim3((rb->P + 255) / 256), dim3(256), 0, st, rb->P, *pose, (uint32_t)seed, (uint32_t)(seed >> 32), rb->pose[0],
+                       rb->parent, rb->cum, rb->units, rb->like, rb->idx, rb->slot);
+    BL_HIP(hipGetLastError());
+    rb_reset_run(rb, pose->utime, pose->utime);
+    return rb_launch_reduce(rb, 0);
+}
+
+extern "C" int bl_rbslam_set_particles(bl_rbslam* rb, const bl_particle_t* particles, const int64_t* cum_scores)
+{
+    BL_CHECK_ARG(rb != nullptr && particles != nullptr);
+    if (!rb->initialized) { bl_set_error("bl_rbslam_set_particles before bl_rbslam_init_at_pose"); return BL_ERR_STATE; }
+    const int P = rb->P;
+    if (cum_scores) for (int m = 0; m < P; ++m) BL_CHECK_ARG(cum_scores[m] >= 0 && cum_scores[m] <= BL_RBSLAM_SCORE_MAX);
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    hipStream_t st = rb->ctx->stream;
+    std::vector<float4> rec(P), par(P);
+    std::vector<long long> cum(P);
+    std::vector<unsigned long long> units(P);
+    for (int m = 0; m < P; ++m) {
+        rec[m] = make_float4(particles[m].pose.x, particles[m].pose.y, particles[m].pose.theta, 0.0f);
+        par[m] = make_float4(particles[m].parent_pose.x, particles[m].parent_pose.y, particles[m].parent_pose.theta, 0.0f);
+        cum[m] = cum_scores ? cum_scores[m] : 0;
+        units[m] = cum[m] > 0 ? (unsigned long long)cum[m] * 1000ull : 2ull;
+    }
+    rb->cur = 0;
+    rb->pose_utime = particles[0].pose.utime; rb->parent_utime = particles[0].parent_pose.utime;
+    BL_HIP(hipMemcpyAsync(rb->pose[0], rec.data(), P * sizeof(float4), hipMemcpyHostToDevice, st));
+    BL_HIP(hipMemcpyAsync(rb->parent, par.data(), P * sizeof(float4), hipMemcpyHostToDevice, st));
+    BL_HIP(hipMemcpyAsync(rb->cum, cum.data(), P * sizeof(long long), hipMemcpyHostToDevice, st));
+    BL_HIP(hipMemcpyAsync(rb->units, units.data(), P * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    int rc = rb_launch_reduce(rb, cum_scores ? 1 : 0);
+    if (rc) return rc;
+    BL_HIP(hipStreamSynchronize(st));                           // caller-owned pageable buffers
+    return BL_OK;
+}
+
+extern "C" int bl_rbslam_get_particles(bl_rbslam* rb, bl_particle_t* out, int64_t* cum_scores, uint64_t* units)
+{
+    BL_CHECK_ARG(rb != nullptr);
+    if (!rb->initialized) { bl_set_error("bl_rbslam_get_particles before bl_rbslam_init_at_pose"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    hipStream_t st = rb->ctx->stream;
+    const size_t P = (size_t)rb->P;
+    if (out) {
+        hipLaunchKernelGGL(k_rb_export, dim3((rb->P + 255) / 256), dim3(256), 0, st, rb->P, rb->pose[rb->cur], rb->parent, rb->units, rb->state,
+                           rb->pose_utime, rb->parent_utime, rb->d_export);
+        BL_HIP(hipGetLastError());
+        BL_HIP(hipMemcpyAsync(out, rb->d_export, P * sizeof(bl_particle_t), hipMemcpyDeviceToHost, st));
+    }
+    if (cum_scores) BL_HIP(hipMemcpyAsync(cum_scores, rb->cum, P * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (units) BL_HIP(hipMemcpyAsync(units, rb->units, P * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    BL_HIP(hipStreamSynchronize(st));
+    return BL_OK;
+}
+
+// ActionModel::updateAction (action_model.cpp:22-75) -- host scalars, as bl_pf_update's
+static bool rb_action_update(bl_rbslam* rb, const bl_pose_xyt_t& odometry)
+{
+    if (!rb->action_initialized) { rb->prev_odom = odometry; rb->action_initialized = true; }
+    float deltaX = odometry.x - rb->prev_odom.x;
+    float deltaY = odometry.y - rb->prev_odom.y;
+    float deltaTheta = (float)bl_angle_diff(odometry.theta, rb->prev_odom.theta);
+    float dir = 1.0;
+    rb->rot1 = bl_angle_diff(atan2f(deltaY, deltaX), rb->prev_odom.theta);
+    rb->trans = sqrtf(deltaX * deltaX + deltaY * deltaY);
+    if (fabs(rb->trans) < 0.0001) { rb->rot1 = 0.0f; }
+    else if (fabs(rb->rot1) > BL_PI / 2.0) { rb->rot1 = -bl_angle_diff(BL_PI, rb->rot1); dir = -1.0; }
+    rb->trans *= dir;
+    rb->rot2 = bl_angle_diff(deltaTheta, rb->rot1);
+    const bool moved = !((fabs(rb->trans) + fabs(rb->rot2)) < 0.00001f);
+    rb->prev_odom = odometry;
+    return moved;
+}
+
+extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, const bl_lidar_t* scan, int rand_value, const float* noise,
+                                bl_rbslam_result_t* result)
+{
+    BL_CHECK_ARG(rb != nullptr && odometry != nullptr && scan != nullptr);
+    if (!rb->initialized) { bl_set_error("bl_rbslam_update before bl_rbslam_init_at_pose"); return BL_ERR_STATE; }
+    BL_CHECK_ARG(scan->num_ranges >= 0 && scan->num_ranges <= RB_MAP_MAX_RAYS);
+    bl_ctx* ctx = rb->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int R = 0;
+    int rc = bl_scan_upload(ctx, scan, &R);
+    if (rc) return rc;
+    const bool moved = rb_action_update(rb, *odometry);
+    const int P = rb->P;
+    if (moved) {
+        if (noise) {
+            BL_HIP(hipMemcpyAsync(rb->d_noise, noise, (size_t)P * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+            BL_HIP(hipStreamSynchronize(st));                   // caller-owned pageable buffer
+        }
+        rb_plan_args pa;
+        pa.P = P; pa.units = rb->units; pa.state = rb->state; pa.idx = rb->idx; pa.slot = rb->slot; pa.copies = rb->copies; pa.cum = rb->cum;
+        pa.M_inv = 1.0 / P;
+        pa.r = (((double)rand_value) / (double)RAND_MAX) * pa.M_inv;
+        pa.num = rb->num; pa.den = rb->den;
+        hipLaunchKernelGGL(k_rb_plan, dim3(1), dim3(RB_PLAN_THREADS), 0, st, pa);
+        const int chunks = (int)((rb->stride / 16 + RB_COPY_THREADS * RB_COPY_VEC - 1) / (RB_COPY_THREADS * RB_COPY_VEC));
+        if (P > 1) {
+            long long blocks = (long long)(P - 1) * chunks;
+            if (blocks > 2048) blocks = 2048;
+            hipLaunchKernelGGL(k_rb_copy, dim3((unsigned)blocks), dim3(RB_COPY_THREADS), 0, st, rb->maps, rb->stride, rb->copies, rb->state, chunks);
+        }
+        rb_weigh_args wa;
+        wa.P = P; wa.R = R;
+        wa.src = rb->pose[rb->cur]; wa.dst = rb->pose[rb->cur ^ 1]; wa.parent = rb->parent;
+        wa.idx = rb->idx; wa.slot = rb->slot; wa.maps = rb->maps; wa.stride = rb->stride; wa.frame = rb->frame;
+        wa.ranges = ctx->scan.ranges; wa.thetas = ctx->scan.thetas; wa.times = ctx->scan.times;
+        // the parent pose carries the utime the pose had, the pose takes the odometry's
+        wa.t_begin = rb->pose_utime;
+        wa.interp = rb->pose_utime != odometry->utime ? 1 : 0;
+        wa.t_den = wa.interp ? (double)(odometry->utime - rb->pose_utime) : 1.0;
+        wa.noise = noise ? rb->d_noise : nullptr;
+        wa.rot1 = rb->rot1; wa.trans = rb->trans; wa.rot2 = rb->rot2; wa.rot1Std = 0.05; wa.transStd = 0.005; wa.rot2Std = 0.05;
+        wa.seed_lo = (uint32_t)rb->noise_seed; wa.seed_hi = (uint32_t)(rb->noise_seed >> 32); wa.step = rb->step;
+        wa.cum = rb->cum; wa.units = rb->units; wa.like = rb->like;
+        hipLaunchKernelGGL(k_rb_weigh, dim3((P + RB_WEIGH_THREADS / 64 - 1) / (RB_WEIGH_THREADS / 64)), dim3(RB_WEIGH_THREADS), 0, st, wa);
+        BL_HIP(hipGetLastError());
+        rb->cur ^= 1;
+        rb->parent_utime = rb->pose_utime;
+        rb->pose_utime = odometry->utime;
+        rb->step += 1;
+        rc = rb_launch_reduce(rb, 1);
+        if (rc) return rc;
+    }
+    if (rb->map_latched && R > 0) {
+        rb_map_args ma;
+        ma.P = P; ma.R = R; ma.maps = rb->maps; ma.stride = rb->stride; ma.frame = rb->frame; ma.slot = rb->slot;
+        ma.end = rb->pose[rb->cur];
+        ma.begin = moved ? rb->parent : rb->pose[rb->cur];
+        ma.ranges = ctx->scan.ranges; ma.thetas = ctx->scan.thetas; ma.times = ctx->scan.times;
+        ma.interp = (moved && rb->parent_utime != rb->pose_utime) ? 1 : 0;
+        ma.t_begin = rb->parent_utime;
+        ma.t_den = ma.interp ? (double)(rb->pose_utime - rb->parent_utime) : 1.0;
+        ma.max_laser = rb->max_laser; ma.hit = rb->hit; ma.miss = rb->miss;
+        // tiles of the largest window the kept rays can span when the pose does not move inside the scan; a wider window (a jump
+        // between parent pose and pose) only makes the workgroups of a particle take several tiles each
+        const float reach_m = ctx->scan.max_range < rb->max_laser ? ctx->scan.max_range : rb->max_laser;
+        long long side = 2ll * (long long)ceilf(reach_m * rb->frame.cpm) + 8;
+        const int ww = (int)(side < rb->frame.width ? side : rb->frame.width), wh = (int)(side < rb->frame.height ? side : rb->frame.height);
+        const int tw = ww < RB_MAP_TILE_W ? ww : RB_MAP_TILE_W;
+        int th = RB_MAP_COUNTERS / (tw < 1 ? 1 : tw); if (th > wh) th = wh; if (th < 1) th = 1;
+        long long tiles = (long long)((ww + tw - 1) / tw) * ((wh + th - 1) / th);
+        if (tiles < 1) tiles = 1;
+        if (tiles > 64) tiles = 64;
+        hipLaunchKernelGGL(k_rb_map, dim3(P, (unsigned)tiles), dim3(RB_MAP_THREADS), 0, st, ma);
+        BL_HIP(hipGetLastError());
+    }
+    rb->map_latched = true;                                     // the very first update latches (mapping.cpp:19-21, 74, 88)
+    BL_HIP(hipMemcpyAsync(rb->h_state, rb->state, sizeof(rb_state), hipMemcpyDeviceToHost, st));
+    BL_HIP(hipStreamSynchronize(st));
+    if (result) {
+        memset(result, 0, sizeof(*result));
+        result->moved = moved ? 1 : 0;
+        result->resampled = moved ? rb->h_state->resampled : 0;
+        result->best = rb->h_state->best;
+        result->best_pose = rb->h_state->best_pose;
+        result->S = rb->h_state->S; result->Q_lo = rb->h_state->Q_lo; result->Q_hi = rb->h_state->Q_hi;
+    }
+    return BL_OK;
+}
+
+static int rb_map_io(bl_rbslam* rb, int which, int8_t* flat, int to_maps)
+{
+    const size_t n = (size_t)rb->frame.width * rb->frame.height;
+    size_t blocks = (n / 16 + RB_COPY_THREADS - 1) / RB_COPY_THREADS;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_rb_map_io, dim3((unsigned)blocks), dim3(RB_COPY_THREADS), 0, rb->ctx->stream, rb->maps, rb->stride, rb->slot, rb->state,
+                       which, flat, n, to_maps);
+    BL_HIP(hipGetLastError());
+    return BL_OK;
+}
+
+extern "C" int bl_rbslam_map_download(bl_rbslam* rb, int p, int8_t* cells)
+{
+    BL_CHECK_ARG(rb != nullptr && cells != nullptr && p >= 0 && p < rb->P);
+    if (!rb->initialized) { bl_set_error("bl_rbslam_map_download before bl_rbslam_init_at_pose"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    int rc = rb_map_io(rb, p, rb->staging, 0);
+    if (rc) return rc;
+    BL_HIP(hipMemcpyAsync(cells, rb->staging, (size_t)rb->frame.width * rb->frame.height, hipMemcpyDeviceToHost, rb->ctx->stream));
+    BL_HIP(hipStreamSynchronize(rb->ctx->stream));
+    return BL_OK;
+}
+
+extern "C" int bl_rbslam_map_upload(bl_rbslam* rb, int p, const int8_t* cells)
+{
+    BL_CHECK_ARG(rb != nullptr && cells != nullptr && p >= 0 && p < rb->P);
+    if (!rb->initialized) { bl_set_error("bl_rbslam_map_upload before bl_rbslam_init_at_pose"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    BL_HIP(hipMemcpyAsync(rb->staging, cells, (size_t)rb->frame.width * rb->frame.height, hipMemcpyHostToDevice, rb->ctx->stream));
+    int rc = rb_map_io(rb, p, rb->staging, 1);
+    if (rc) return rc;
+    BL_HIP(hipStreamSynchronize(rb->ctx->stream));              // caller-owned buffer
+    return BL_OK;
+}
+
+extern "C" int bl_rbslam_best_map(bl_rbslam* rb, bl_grid* dst)
+{
+    BL_CHECK_ARG(rb != nullptr && dst != nullptr);
+    if (!rb->initialized) { bl_set_error("bl_rbslam_best_map before bl_rbslam_init_at_pose"); return BL_ERR_STATE; }
+    BL_CHECK_ARG(dst->frame.width == rb->frame.width && dst->frame.height == rb->frame.height);
+    BL_CHECK_ARG(dst->ctx == rb->ctx);                          // one stream orders the copy behind the updates
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    dst->frame = rb->frame;
+    dst->mirror_valid = false;
+    (void)bl_grid_new_lineage(dst);
+    return rb_map_io(rb, -1, dst->cells, 0);
+}
+
+extern "C" int bl_rbslam_debug_last(bl_rbslam* rb, int32_t* resample_idx, int32_t* likelihood_half_units)
+{
+    BL_CHECK_ARG(rb != nullptr);
+    if (!rb->initialized) { bl_set_error("bl_rbslam_debug_last before bl_rbslam_init_at_pose"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    const size_t P = (size_t)rb->P;
+    if (resample_idx) BL_HIP(hipMemcpyAsync(resample_idx, rb->idx, P * sizeof(int32_t), hipMemcpyDeviceToHost, rb->ctx->stream));
+    if (likelihood_half_units) BL_HIP(hipMemcpyAsync(likelihood_half_units, rb->like, P * sizeof(int32_t), hipMemcpyDeviceToHost, rb->ctx->stream));
+    BL_HIP(hipStreamSynchronize(rb->ctx->stream));
+    return BL_OK;
+}

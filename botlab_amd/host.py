@@ -891,6 +891,102 @@ class ViewGain:
             self.h = None
 
 
+class RBSlam:
+    """Rao-Blackwellized grid SLAM (bl_rbslam_*, include/botlab_hip.h): numParticles particles, each with a pose, a parent pose, a
+    cumulative score and its own map of `grid`'s shape and frame; weighed against its own map, resampled -- maps and all -- when
+    num * P * sum u^2 >= den * (sum u)^2."""
+
+    def __init__(self, numParticles, width, height, metersPerCell, cellsPerMeter, origin, maxLaserDistance, hitOdds, missOdds, ctx=None):
+        self.ctx = ctx or default_context()
+        self.P, self.width, self.height = int(numParticles), int(width), int(height)
+        self.mpc, self.cpm = np.float32(metersPerCell), np.float32(cellsPerMeter)
+        self.origin = (np.float32(origin[0]), np.float32(origin[1]))
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_rbslam_create(self.ctx.h, self.P, self.width, self.height, self.mpc, self.cpm, self.origin[0], self.origin[1],
+                                            np.float32(maxLaserDistance), int(hitOdds), int(missOdds), C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def like(cls, numParticles, grid, maxLaserDistance, hitOdds, missOdds):
+        """Maps of the shape and frame of an OccupancyGrid."""
+        return cls(numParticles, grid.width, grid.height, grid.mpc, grid.cpm, grid.origin, maxLaserDistance, hitOdds, missOdds, ctx=grid.ctx)
+
+    def setResampling(self, num, den):
+        check(self.ctx.lib.bl_rbslam_set_resampling(self.h, int(num), int(den)))
+
+    def setNoiseSeed(self, seed):
+        check(self.ctx.lib.bl_rbslam_set_noise_seed(self.h, C.c_uint64(seed)))
+
+    def initializeAtPose(self, pose, seed=None):
+        if seed is None:
+            seed = int.from_bytes(np.random.bytes(8), "little")
+        check(self.ctx.lib.bl_rbslam_init_at_pose(self.h, C.byref(pose), C.c_uint64(seed)))
+
+    def setParticles(self, particles, cum_scores=None):
+        p = np.ascontiguousarray(particles)
+        assert p.dtype.itemsize == 56 and p.size == self.P
+        c = None
+        if cum_scores is not None:
+            c = np.ascontiguousarray(cum_scores, dtype=np.int64)
+            assert c.size == self.P
+        check(self.ctx.lib.bl_rbslam_set_particles(self.h, p.ctypes.data, c.ctypes.data if c is not None else None))
+
+    def particles(self):
+        """(particles as PARTICLE_DTYPE, cumulative scores int64, weight units uint64)."""
+        out = np.zeros(self.P, dtype=PARTICLE_DTYPE)
+        cum = np.zeros(self.P, np.int64)
+        units = np.zeros(self.P, np.uint64)
+        check(self.ctx.lib.bl_rbslam_get_particles(self.h, out.ctypes.data, cum.ctypes.data, units.ctypes.data))
+        return out, cum, units
+
+    def update(self, odometry, laser, rand_value=None, noise=None):
+        """One update; returns dict(moved, resampled, best, pose, S, Q).  noise (3 * P float32) replaces the Philox action noise."""
+        if rand_value is None:
+            rand_value = _libc.rand()
+        ls = laser.as_c()
+        nz = None
+        if noise is not None:
+            nz = np.ascontiguousarray(noise, dtype=np.float32)
+            assert nz.size == 3 * self.P
+        r = _capi.RBSlamResult()
+        check(self.ctx.lib.bl_rbslam_update(self.h, C.byref(odometry), C.byref(ls), int(rand_value), nz.ctypes.data if nz is not None else None,
+                                            C.byref(r)))
+        bp = r.best_pose
+        return dict(moved=bool(r.moved), resampled=bool(r.resampled), best=int(r.best), pose=Pose(bp.utime, bp.x, bp.y, bp.theta), S=int(r.S),
+                    Q=(int(r.Q_hi) << 64) | int(r.Q_lo))
+
+    def mapCells(self, p):
+        out = np.empty((self.height, self.width), np.int8)
+        check(self.ctx.lib.bl_rbslam_map_download(self.h, int(p), out.ctypes.data))
+        return out
+
+    def uploadMap(self, p, cells):
+        c = np.ascontiguousarray(cells, dtype=np.int8)
+        assert c.shape == (self.height, self.width)
+        check(self.ctx.lib.bl_rbslam_map_upload(self.h, int(p), c.ctypes.data))
+
+    def best_map(self, grid=None):
+        """The best particle's map as an OccupancyGrid (device to device; `grid`: one of the same shape to fill)."""
+        if grid is None:
+            grid = OccupancyGrid(ctx=self.ctx, _raw=(self.width, self.height, self.mpc, self.cpm, self.origin[0], self.origin[1]))
+        check(self.ctx.lib.bl_rbslam_best_map(self.h, grid.h))
+        grid.mpc, grid.cpm, grid.origin = self.mpc, self.cpm, self.origin
+        return grid
+
+    bestMap = best_map
+
+    def debugLast(self):
+        idx = np.empty(self.P, np.int32)
+        like = np.empty(self.P, np.int32)
+        check(self.ctx.lib.bl_rbslam_debug_last(self.h, idx.ctypes.data, like.ctypes.data))
+        return idx, like
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_rbslam_destroy(self.h)
+            self.h = None
+
+
 def plan_path_to_frontier_by_gain(frontiers, robotPose, grid, planner, view=None, reach_cells=None, stride=1, min_gain=1, gain_weight=1,
                                   obstacle_gain=NAV_OBSTACLE_GAIN, cap=1 << 16):
     """The viewpoint near a frontier that weighs expected new map against travel cost.  Candidates are the cells within Chebyshev

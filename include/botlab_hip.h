@@ -735,6 +735,79 @@ int bl_viewgain_compute(bl_viewgain* vg, const bl_grid* map, const int32_t* xy_c
 /* the seen set of one candidate: (2R + 1)^2 bytes, 0 / 1, row-major, the window around the cell (byte (dy + R) * (2R + 1) + dx + R) */
 int bl_viewgain_debug_seen(bl_viewgain* vg, const bl_grid* map, int x, int y, uint8_t* out);
 
+/* ------------------------------------------------------------------ Rao-Blackwellized grid SLAM (FastSLAM on grids; no reference counterpart)
+ * P particles (1 .. BL_RBSLAM_MAX_PARTICLES), each with a pose, a parent pose, a cumulative score c_p (int64, half-units of the
+ * sensor model's log-odds score) and its OWN width x height int8 map; all maps share one frame.  Every piece below is one the
+ * library already defines for one map and one filter, so that tests/rb_slam_model.py -- the same definition over the reference's
+ * per-particle entry points -- agrees with the device bit for bit.
+ *
+ * One bl_rbslam_update(odometry, scan, rand_value, noise):
+ *   1. Moved?  ActionModel::updateAction's rule on the odometry (action_model.cpp:22-75), host scalars, as bl_pf_update.
+ *   2. If moved and a resampling is DUE (rule below): low-variance resampling of the P particles by the integer-prefix rule with
+ *      M = P on the weight units u_p: T_m = (r + m / P) * S in double, r = (rand_value / RAND_MAX) / P, S = sum u; the source of
+ *      child m is the first i with T_m <= (double)prefix_i (prefix = the running uint64 sum of u), clamped to P - 1.  A child takes
+ *      its source's pose, parent pose AND map.  All cumulative scores are reset to 0.
+ *   3. If moved, action: ActionModel::applyAction per particle (action_model.cpp:78-103).  noise: a HOST array of 3 P floats
+ *      (sampled rot1, trans, rot2 per particle; the parity mode), or NULL: Philox from bl_rbslam_set_noise_seed's seed, the
+ *      counters and arithmetic of bl_pf_update.  The parent pose becomes the old pose (with its utime); the pose's utime becomes the
+ *      odometry's.
+ *   4. If moved, weigh: h_p = SensorModel::likelihood (sensor_model.cpp:14-59) of the scan for particle p against ITS OWN map,
+ *      in half-units (an exact integer: a ray scores 2 * odds, o1 or o2), the moving scan interpolated between parent pose and pose
+ *      by the rays' time stamps (interpolate_pose_by_time; equal utimes: the pose itself).  c_p = min(c_p + h_p, BL_RBSLAM_SCORE_MAX).
+ *      Weight units: u_p = max(1000 * c_p, 2) -- the filter's unit of 0.0005 with its floor of 0.001.  Adding log-odds scores over the
+ *      updates since the last resampling is the log-domain product of the weights; with a resampling on every update u_p is exactly
+ *      the reference filter's weight.
+ *      Saturation: c_p <= 2^33, so u_p < 2^43, S <= 4096 u < 2^55 and Q = sum u^2 < 2^98; with num, den < 2^16 both sides of the test
+ *      below stay under 2^126: 128-bit integers cannot overflow.  (A scan of 8192 rays scores at most 2^21 half-units.)
+ *   5. Best particle: the largest u_p, ties to the lowest index.  The SLAM pose of the update is its pose; best_map is its map.
+ *   6. Map: every particle's map receives Mapping::updateMap(scan, pose_p, map_p) (mapping.cpp:17-127) with
+ *      previousPose_ = parent_pose_p: v' = max(-128, min(127, v + hit * H) - miss * M) for a cell that ends H rays and is crossed by M,
+ *      over the rays with range <= max_laser_distance; rays that leave the grid update the cells inside it.  The very FIRST update
+ *      after bl_rbslam_init_at_pose latches and changes no cell (the reference's initialized_).  Not moved: steps 2-5 are skipped and
+ *      the scan is integrated with previousPose_ = pose_p, i.e. Mapping::updateMap(scan, pose_p, map_p) on a mapper whose previous
+ *      update was at pose_p.
+ * Resampling is DUE before the action of a moved update iff den * S^2 <= num * P * Q, in exact integers, S and Q over the units the
+ * last weighing left.  num / den = 1 / 1 resamples on every moved update (Cauchy-Schwarz); the default 1 / 2 is N_eff <= P / 2.
+ * Nothing is due before the first weighing (bl_rbslam_set_particles with scores counts as one).
+ * Map copies of a resampling: a particle -> slot table; the first child of a source keeps its slot, the k-th other child (in order
+ * of index) is copied into the slot of the k-th particle that died, all copies in one launch.  Only the order of results is the
+ * contract.  Everything is stream-ordered on the ctx stream; bl_rbslam_update synchronises once, to hand `result` back.
+ * Limits: the maps take P * ((width * height + 15) & ~15) bytes; more than BL_RBSLAM_MAX_MAP_BYTES: BL_ERR_ARG.  4 GiB holds 4096
+ * maps of 1000 x 1000 cells, a small part of the device's memory, which other objects of the process share.  width, height <= 65535;
+ * at most 8192 rays per scan. */
+#define BL_RBSLAM_MAX_PARTICLES 4096
+#define BL_RBSLAM_MAX_MAP_BYTES (4ull << 30)
+#define BL_RBSLAM_SCORE_MAX (1ll << 33)
+typedef struct bl_rbslam_result_t {
+    int32_t moved, resampled;          /* of this update */
+    int32_t best, pad;                 /* the best particle as of the last weighing (0 before the first) */
+    bl_pose_xyt_t best_pose;           /* its pose, utime = the particles' pose utime */
+    uint64_t S, Q_lo, Q_hi;            /* sum u and sum u^2 (two words) as of the last weighing */
+} bl_rbslam_result_t;                  /* 64 bytes */
+typedef struct bl_rbslam bl_rbslam;
+int bl_rbslam_create(bl_ctx* ctx, int num_particles, int width, int height, float meters_per_cell, float cells_per_meter,
+                     float origin_x, float origin_y, float max_laser_distance, int8_t hit_odds, int8_t miss_odds, bl_rbslam** out);
+void bl_rbslam_destroy(bl_rbslam* rb);
+int bl_rbslam_set_resampling(bl_rbslam* rb, uint32_t num, uint32_t den);      /* 1 .. 65535 each; default 1 / 2 */
+int bl_rbslam_set_noise_seed(bl_rbslam* rb, uint64_t seed);
+/* poses drawn as bl_pf_init_at_pose draws them (the last particle is the pose itself), maps zero, scores zero, the ActionModel and the
+ * map latch reset */
+int bl_rbslam_init_at_pose(bl_rbslam* rb, const bl_pose_xyt_t* pose, uint64_t seed);
+/* poses and parent poses of all P particles (utimes: particle 0's); cum_scores (P values in 0 .. BL_RBSLAM_SCORE_MAX) or NULL: zeros,
+ * and then nothing is due until the next weighing.  Maps, ActionModel and latch are left as they are.  BL_ERR_STATE before init. */
+int bl_rbslam_set_particles(bl_rbslam* rb, const bl_particle_t* particles, const int64_t* cum_scores);
+/* any of the three may be NULL; weight = u_p / S */
+int bl_rbslam_get_particles(bl_rbslam* rb, bl_particle_t* out, int64_t* cum_scores, uint64_t* units);
+/* BL_ERR_STATE before bl_rbslam_init_at_pose; result may be NULL */
+int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, const bl_lidar_t* scan, int rand_value, const float* noise,
+                     bl_rbslam_result_t* result);
+int bl_rbslam_map_download(bl_rbslam* rb, int p, int8_t* cells);              /* particle p's map, width * height bytes */
+int bl_rbslam_map_upload(bl_rbslam* rb, int p, const int8_t* cells);
+/* the best particle's map, device to device, into an ordinary grid of the same shape and ctx (it takes the frame): BL_ERR_ARG otherwise */
+int bl_rbslam_best_map(bl_rbslam* rb, bl_grid* dst);
+/* of the last moved update: the source of every particle (m itself when it did not resample) and h_p; either may be NULL */
+int bl_rbslam_debug_last(bl_rbslam* rb, int32_t* resample_idx, int32_t* likelihood_half_units);
+
 /* ------------------------------------------------------------------ the exploration step, asynchronously  (src/planning/exploration.cpp:277-369)
  * Exploration::executeExploringMap on every published map: planner_.setMap, find_map_frontiers, and -- when the robot is within
  * 0.5 m of currentTarget_ or has none -- plan_path_to_frontier; then the status / next-state rule (:332-368; D10).  A submission
