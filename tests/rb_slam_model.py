@@ -17,8 +17,15 @@ One update(odometry, scan, rand_value, noise):
      skipped and the mapper is primed with pose_p itself -- literally OracleMapping.update(scan, pose_p) twice, the first on a
      scratch grid.
 Resampling is DUE iff den * S^2 <= num * P * Q in exact integers, S = sum u, Q = sum u^2 over the units of the last weighing; nothing
-is due before the first weighing."""
+is due before the first weighing.
+A moved update whose odometry utime equals the poses' utime needs no rule of the model's own: the oracle's interpolate_pose_by_time
+returns the end pose when both utimes are equal, which is the header's "equal utimes: the pose itself".
+
+Helpers for the tests of the edges (tests/test_rb_slam_edges_cpu.py): watermark() marks a map with its particle's index, ray_cells()
+and window_box() give the window of an update, window_tiles() cuts it by k_rb_map's rule and launch_tiles() restates the host's
+gridDim.y of bl_rbslam_update.  None of them takes part in update()."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -37,6 +44,90 @@ def due(units, num, den):
     u = [int(v) for v in units]
     S, Q = sum(u), sum(v * v for v in u)
     return den * S * S <= num * len(u) * Q
+
+
+def watermark(p, n):
+    """n int8 values that name particle p (p < 2^14): two cells hold its index, the others a pattern seeded by it."""
+    v = ((np.arange(n, dtype=np.int64) * (2 * int(p) + 1) + 37 * int(p)) % 251 - 125).astype(np.int8)
+    v[0], v[1] = int(p) & 127, int(p) >> 7
+    return v
+
+
+def set_watermarks(maps, block):
+    """Writes watermark(p) into maps[p][block] for every p; block: a pair of slices no ray may reach."""
+    for p in range(len(maps)):
+        shape = maps[p][block].shape
+        maps[p][block] = watermark(p, shape[0] * shape[1]).reshape(shape)
+
+
+def watermark_owner(cells, block):
+    b = cells[block].ravel()
+    p = int(b[0]) | (int(b[1]) << 7)
+    return p if np.array_equal(b, watermark(p, b.size)) else -1
+
+
+def ray_cells(orc, scan, begin, end, origin, cpm, max_laser):
+    """(x0, y0, x1, y1) int cells of the rays Mapping::updateMap traces (range <= max_laser), from the oracle's MovingLaserScan;
+    the cell arithmetic is mapping.cpp:45-49 in float32."""
+    rays = orc.moving_scan(scan, begin, end)
+    rays = rays[rays[:, 2] <= np.float32(max_laser)]
+    cpm = np.float32(cpm)
+    sx = ((rays[:, 0].astype(np.float64) - np.float64(np.float32(origin[0]))) * np.float64(cpm)).astype(np.float32)
+    sy = ((rays[:, 1].astype(np.float64) - np.float64(np.float32(origin[1]))) * np.float64(cpm)).astype(np.float32)
+    ex = (rays[:, 2] * np.cos(rays[:, 3]).astype(np.float32) * cpm + sx).astype(np.float32)
+    ey = (rays[:, 2] * np.sin(rays[:, 3]).astype(np.float32) * cpm + sy).astype(np.float32)
+    return np.stack([np.trunc(sx), np.trunc(sy), np.trunc(ex), np.trunc(ey)], axis=1).astype(np.int64)
+
+
+def window_box(cells, W, H):
+    """k_rb_map's window: the bounding box of all start and end cells, clipped to the grid, dword-aligned when W % 4 == 0.
+    (x0, y0, x1, y1) inclusive, or None when nothing falls into the grid."""
+    if len(cells) == 0:
+        return None
+    x0, x1 = max(int(min(cells[:, 0].min(), cells[:, 2].min())), 0), min(int(max(cells[:, 0].max(), cells[:, 2].max())), W - 1)
+    y0, y1 = max(int(min(cells[:, 1].min(), cells[:, 3].min())), 0), min(int(max(cells[:, 1].max(), cells[:, 3].max())), H - 1)
+    if x1 < x0 or y1 < y0:
+        return None
+    if W % 4 == 0:
+        x0, x1 = x0 & ~3, x1 | 3
+    return x0, y0, x1, y1
+
+
+MAP_COUNTERS, MAP_TILE_W = 20480, 256       # RB_MAP_COUNTERS, RB_MAP_TILE_W (bl_rbslam.hip)
+
+
+def window_tiles(box):
+    """(ntx, nty) of k_rb_map's cut: tiles of min(ww, 256) columns and min(wh, 20480 // tw) rows."""
+    ww, wh = box[2] - box[0] + 1, box[3] - box[1] + 1
+    tw = min(ww, MAP_TILE_W)
+    th = min(wh, MAP_COUNTERS // tw)
+    return -(-ww // tw), -(-wh // th)
+
+
+def launch_tiles(scan, max_laser, cpm, W, H):
+    """gridDim.y of k_rb_map as bl_rbslam_update sizes it: the tiles of a square window of 2 * ceil(reach * cpm) + 8 cells, reach =
+    min(largest kept range of the scan, max_laser), clipped to the grid; between 1 and 64."""
+    kept = scan.ranges[scan.ranges > np.float32(0.15)]
+    reach = min(np.float32(kept.max()) if len(kept) else np.float32(0.0), np.float32(max_laser))
+    side = 2 * int(math.ceil(np.float32(reach * np.float32(cpm)))) + 8
+    ww, wh = min(side, W), min(side, H)
+    tw = min(ww, MAP_TILE_W)
+    th = max(min(MAP_COUNTERS // max(tw, 1), wh), 1)
+    return max(1, min(64, -(-ww // tw) * -(-wh // th)))
+
+
+def started_model(orc, P, shape, mpc, cpm, origin, max_laser, hit, miss, num, den, start, spread=None):
+    """A model initialised at the pose `start` (utime 1000); spread: the seed of distinct start poses, 0.01 apart in x, y and theta."""
+    mdl = RBSlamModel(orc, P, shape, mpc, cpm, origin, max_laser, hit, miss, num, den)
+    mdl.init_at_pose(start[0], start[1], start[2], 1000)
+    if spread is not None:
+        rng = np.random.default_rng(spread)
+        p = mdl.parts.copy()
+        p["x"] += rng.normal(0, 0.01, P).astype(np.float32); p["y"] += rng.normal(0, 0.01, P).astype(np.float32)
+        p["theta"] += rng.normal(0, 0.01, P).astype(np.float32)
+        p["p_x"], p["p_y"], p["p_theta"] = p["x"], p["y"], p["theta"]
+        mdl.set_particles(p)
+    return mdl
 
 
 class RBSlamModel:

@@ -14,19 +14,12 @@ pytestmark = pytest.mark.gpu
 POSE_FIELDS = ["utime", "x", "y", "theta", "p_utime", "p_x", "p_y", "p_theta"]
 
 
-def _pair(oracle, gpu_ctx, m, P, num, den, start, shape=None, origin=None, spread=None):
+def _pair(oracle, gpu_ctx, m, P, num, den, start, shape=None, origin=None, spread=None, cpm=CPM, max_laser=MAX_LASER, hit=HIT, miss=MISS):
+    """The model and the device object of one run, both holding the same particles (tests/test_gpu_rb_slam_edges.py shares it)."""
     shape = shape or m["cells"].shape
     origin = origin or m["origin"]
-    mdl = rbm.RBSlamModel(oracle, P, shape, m["mpc"], CPM, origin, MAX_LASER, HIT, MISS, num, den)
-    mdl.init_at_pose(start[0], start[1], start[2], 1000)
-    if spread is not None:                      # distinct start poses
-        rng = np.random.default_rng(spread)
-        p = mdl.parts.copy()
-        p["x"] += rng.normal(0, 0.01, P).astype(np.float32); p["y"] += rng.normal(0, 0.01, P).astype(np.float32)
-        p["theta"] += rng.normal(0, 0.01, P).astype(np.float32)
-        p["p_x"], p["p_y"], p["p_theta"] = p["x"], p["y"], p["theta"]
-        mdl.set_particles(p)
-    rb = bl.RBSlam(P, shape[1], shape[0], m["mpc"], CPM, origin, MAX_LASER, HIT, MISS, ctx=gpu_ctx)
+    mdl = rbm.started_model(oracle, P, shape, m["mpc"], cpm, origin, max_laser, hit, miss, num, den, start, spread)
+    rb = bl.RBSlam(P, shape[1], shape[0], m["mpc"], cpm, origin, max_laser, hit, miss, ctx=gpu_ctx)
     rb.setResampling(num, den)
     rb.initializeAtPose(bl.make_pose(start[0], start[1], start[2], utime=1000), seed=1)
     rb.setParticles(mdl.parts)
@@ -51,14 +44,15 @@ def _compare(mdl, rb, r_m, r_g, k, maps_of=None):
         assert rb.mapCells(p).tobytes() == mdl.maps[p].tobytes(), (k, p)
 
 
-def _run(mdl, rb, odoms, scans, seed, maps_every=1, maps_of=None):
+def _run(mdl, rb, odoms, scans, seed, maps_every=1, maps_of=None, rand_value=None):
     rng = np.random.default_rng(seed)
     flags = []
     for k in range(len(odoms)):
         o = odoms[k]
         noise = mdl.draw_noise(o, rng)
-        r_m = mdl.update(o, scans[k], 4242 + k, noise)
-        r_g = rb.update(bl.make_pose(o[0], o[1], o[2], utime=o[3]), scans[k], rand_value=4242 + k, noise=noise)
+        rv = 4242 + k if rand_value is None else rand_value
+        r_m = mdl.update(o, scans[k], rv, noise)
+        r_g = rb.update(bl.make_pose(o[0], o[1], o[2], utime=o[3]), scans[k], rand_value=rv, noise=noise)
         last = k == len(odoms) - 1
         _compare(mdl, rb, r_m, r_g, k, maps_of=maps_of if maps_of is not None else (None if last or k % maps_every == 0 else []))
         flags.append((r_m["moved"], r_m["resampled"]))
