@@ -112,6 +112,8 @@ struct bl_pf {
     bool uniform_now;         // every particle of rec[cur] carries the same weight (a fresh filter, equal uploaded weights): the one kind of
                               // weights on which the integer rule and the reference's rounded cumulative part ways (rand() near 0 or
                               // RAND_MAX puts every U on a partial sum) -- the next resampling then takes the reference's cumulative
+    bool updated_now;         // the weights of the newest record were written by a sensor update (every unit >= 2 there): the one kind of record
+                              // whose total may be read as "every particle at the floor" (2 N units).  An upload totals 2 N in many ways
     bool prefix_is_strict;    // prefix[] holds that cumulative (doubles), not the integer prefix
     double w_floor;           // 0.001 / wSum of N floor weights as the reference's loop rounds it (particle_filter.cpp:116-141): the all-floor set's weight
     unsigned long long* block_sums;   // scan scratch
@@ -1758,14 +1760,19 @@ static void pf_adaptive_fill(bl_pf* pf)
     pf->scan_blocks = (pf->cap + SCAN_TILE - 1) / SCAN_TILE;
 }
 
-// what the launch that writes the weight total is told about equal weights (uni_update): 1 = the host knows the record's weights are
-// all equal (only a launch over rec[cur] as uploaded / initialised may be told so), 0 = recognise the all-floor set, -1 = off
-// (BOTLAB_NO_AUTO_STRICT=1: the integer rule everywhere -- tests, A/B runs)
-static int pf_uni_mode(const bl_pf* pf, bool plain_scan)
+// what the launch that writes the weight total is told about equal weights (uni_update, mclf_term_S).  It follows from where the
+// record's weights came from, never from their total alone:
+//    1  an initialisation or an upload in which the host saw equal units: weights units / S = 1 / N;
+//    0  a sensor update wrote them (every unit >= 2): a total of 2 N units is the all-floor set, weight w_floor;
+//   -1  off: an upload of unequal units (a total of 2 N means nothing there: [1,3,1,3..], [0,4,0,4..] and [2 N,0,0..] all have it),
+//       or BOTLAB_NO_AUTO_STRICT=1 (the integer rule everywhere -- tests, A/B runs).
+// An update sets the flags when it begins, before any launch that ends it; an action-only update carries weights and flags over.
+static int pf_uni_mode(const bl_pf* pf)
 {
     static const bool no_auto = getenv("BOTLAB_NO_AUTO_STRICT") != nullptr;
     if (no_auto) return -1;
-    return plain_scan && pf->uniform_now ? 1 : 0;
+    if (pf->uniform_now) return 1;
+    return pf->updated_now ? 0 : -1;
 }
 
 // strict resampling: the integer prefix just written gives way to the reference's own cumulative (same buffer, as doubles)
@@ -1819,7 +1826,7 @@ static int pf_finish_fill(bl_pf* pf, mcl_finish_args* f)
         pf->fin_last_nrec = nrec;
     }
     f->sh = nullptr;
-    f->uni_mode = pf_uni_mode(pf, false);
+    f->uni_mode = pf_uni_mode(pf);
     f->w_floor = pf_w_floor(pf);
     f->wild = pf->sh_world > 1 ? nullptr : pf->fin_wild;      // (a composed finish keeps to records, tables and replays)
     f->recs = pf->fin_recs;
@@ -1851,7 +1858,7 @@ static int pf_scan(bl_pf* pf, int which, int write_pose, int64_t utime)
         hipLaunchKernelGGL(k_mcl_finish, dim3(MCLF_EXTRA_WGS + f.groups_wait), dim3(MCLF_WG), MCLF_LDS_BYTES, ctx->stream, f);
     } else {
         hipLaunchKernelGGL(k_scan_write_prefix, dim3(pf->scan_blocks), dim3(SCAN_THREADS), 0, ctx->stream, pf->rec[which], pf->N,
-                           pf->block_sums, pf->scan_blocks, pf->prefix, pf->state, pf_uni_mode(pf, true), pf_w_floor(pf));
+                           pf->block_sums, pf->scan_blocks, pf->prefix, pf->state, pf_uni_mode(pf), pf_w_floor(pf));
     }
     BL_HIP(hipGetLastError());
     pf_strict_cumulative(pf, which);
@@ -1881,6 +1888,7 @@ extern "C" int bl_pf_init_at_pose(bl_pf* pf, const bl_pose_xyt_t* pose, uint64_t
     pf->pose_utime = pose->utime; pf->parent_utime = pose->utime;
     pf->initialized = true;
     pf->uniform_now = true;                      // weights 1 / N (particle_filter.cpp:25)
+    pf->updated_now = false;
     pf->sensed = false;                          // (placeholder units: the recovery tracker does not fold them)
     // the reference does not reset its ActionModel here; a filter is initialised once (slam.cpp:232-250)
     return pf_scan(pf, 0, 0, 0);
@@ -1889,11 +1897,18 @@ extern "C" int bl_pf_init_at_pose(bl_pf* pf, const bl_pose_xyt_t* pose, uint64_t
 extern "C" int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, const uint32_t* units)
 {
     BL_CHECK_ARG(pf != nullptr && particles != nullptr);
+    if (units) {
+        // (an upload fills the whole capacity.  Units of total 0 would make every weight 0 / 0: refused before anything changes)
+        bool any = false;
+        for (int m = 0; m < pf->cap && !any; ++m) any = units[m] != 0u;
+        if (!any) { bl_set_error("bl_pf_set_particles: every weight unit is 0; the filter keeps its particles"); return BL_ERR_ARG; }
+    }
     BL_HIP(hipSetDevice(pf->ctx->device));
     if (!pf->prefix) { int rc = pf_alloc(pf); if (rc) return rc; }
     pf_adaptive_fill(pf);
     std::vector<float4> rec(pf->N), par(pf->n_local);
     pf->uniform_now = true;
+    pf->updated_now = false;
     pf->sensed = false;
     for (int m = 0; m < pf->N; ++m) {
         uint32_t u = units ? units[m] : 1u;
@@ -2413,6 +2428,7 @@ extern "C" int bl_pf_update_begin(bl_pf* pf, const bl_pose_xyt_t* odometry, cons
     rc = pf_launch_main(pf, map, R, rand_value, noise, 1);
     if (rc) return rc;
     pf->uniform_now = false;                     // the record this update writes carries the sensor model's weights
+    pf->updated_now = true;
     // ... which the recovery tracker folds -- unless this update interpolated its scan (particles with a nonzero pose utime: the first
     // update after an initialisation or upload with utime != 0; pf_launch_main's a.interp): its scan is interpolated towards utime 0
     // (D3) and its weights are an order of magnitude below the steady ones
@@ -3428,6 +3444,7 @@ extern "C" int bl_pf_init_uniform(bl_pf* pf, const bl_grid* map, const bl_dist* 
     pf->pose_utime = utime; pf->parent_utime = utime;
     pf->initialized = true;
     pf->uniform_now = true;                      // weights 1 / N
+    pf->updated_now = false;
     pf->sensed = false;
     // poseEstimate() = estimatePosteriorPose of the new cloud (it also centres the next update's LDS map window); then the plain
     // prefix scan bl_pf_init_at_pose ends with, which knows the weights are equal

@@ -90,7 +90,8 @@ struct mcl_finish_args {
     unsigned long long* prefix;
     pf_state* state;
     int64_t utime;
-    int uni_mode;                          // equal weights (uni_seg): 0 = detect the all-floor set from the total, -1 = off (BOTLAB_NO_AUTO_STRICT)
+    int uni_mode;                          // equal weights (uni_seg), by where the record's weights came from (pf_uni_mode): 1 = equal units uploaded or
+                                           // initialised, 0 = a sensor update wrote them: detect the all-floor set from the total, -1 = off
     double w_floor;                        // the weight computeNormalizedPosterior leaves on N floor weights: 0.001 / (0.001 + ... + 0.001, N terms, rounded at every step); the host forms it once per filter
     ss_rec* recs;                          // [2][groups * subs]: x records, then y records
     mclf_tab_elem* tabs;                   // [2][MCLF_TSLOTS][MCLF_SUB]
@@ -211,8 +212,9 @@ __device__ inline int uni_search(const pf_state* st, int uni_n, double T, int N)
 }
 
 // the launch that has just written the total S of the weight units decides whether the set is one of equal weights.  mode 1: the host
-// knows it is (a fresh filter, an upload of equal weights: w = fl(units / S) = fl(1 / N)); 0: only the all-floor set is recognised
-// (S == 2 N: w = w_floor = 0.001 / wSum as computeNormalizedPosterior leaves it, formed by the host); -1: never.
+// knows it is (a fresh filter, an upload of equal weights: w = fl(units / S) = fl(1 / N)); 0: a sensor update wrote the record, so every
+// unit is at least 2 and only the all-floor set totals 2 N (S == 2 N: w = w_floor = 0.001 / wSum as computeNormalizedPosterior leaves
+// it, formed by the host); -1: never -- in particular for an upload of unequal units, whose total may be 2 N with any weights at all.
 __device__ inline void uni_update(pf_state* st, int N, double S, int mode, double w_floor)
 {
     int n = 0;
@@ -444,7 +446,9 @@ __device__ __forceinline__ void mclf_sub_range(const mcl_finish_args& f, int s, 
 // 0.001 (then wSum itself is a rounded sum; DESIGN.md "Pose estimate").
 // The all-floor set (uni_seg) is the one case in which that matters to every term: the reference's weight is w_floor = 0.001 / wSum
 // for all N particles (a few 1e-12 away from 2 / S = 1 / N: a last-bit difference in one term of a few thousand, and the float sum
-// rounds differently there).  A NEGATIVE S says "the weight is -S" (mclf_term_S).
+// rounds differently there).  A NEGATIVE S says "the weight is -S" (mclf_term_S).  Only a record a sensor update wrote (uni_mode 0) is
+// read that way: an uploaded record's weights are units / S whatever its total, the one of N units of 2 included (particles() hands
+// those out as 1 / N).
 __device__ __forceinline__ double mclf_term(const float4& r, double S, int axis)
 {
     const double w = S < 0.0 ? -S : (double)__float_as_uint(r.w) / S;
@@ -452,7 +456,7 @@ __device__ __forceinline__ double mclf_term(const float4& r, double S, int axis)
 }
 __device__ __forceinline__ double mclf_term_S(const mcl_finish_args& f, double S)
 {
-    return (f.uni_mode >= 0 && S == 2.0 * (double)f.N) ? -f.w_floor : S;
+    return (f.uni_mode == 0 && S == 2.0 * (double)f.N) ? -f.w_floor : S;
 }
 __device__ __forceinline__ void mclf_load_terms(const mcl_finish_args& f, int axis, double S, int lo, int hi, int lane, double (&t)[MCLF_ITEMS])
 {

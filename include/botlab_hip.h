@@ -219,8 +219,16 @@ typedef struct bl_pf_adaptive_state_t {
     uint64_t counts;                      /* resampling updates counted since enabling */
 } bl_pf_adaptive_state_t;                 /* 24 bytes */
 int bl_pf_adaptive_state(bl_pf* pf, bl_pf_adaptive_state_t* out);   /* synchronises; BL_ERR_STATE while an update is pending */
-/* Replace the whole posterior from a host AoS array of num_particles records (weights must be uniform or the
- * weight-unit integers in `units` given; units == NULL -> uniform). */
+/* Replace the whole posterior from a host AoS array of num_particles records.  The `weight` fields are not read: the weights are
+ * units[m] / sum(units), units == NULL -> uniform (every unit 1).
+ *   Legal units: any uint32 values, zeros included, whose total is not 0 (num_particles * (2^32 - 1) < 2^53: the total and every
+ *     prefix of it are exact in a double).  A total of 0 would make every weight 0 / 0: BL_ERR_ARG, and the filter keeps what it held.
+ *   Resampling: equal units (the host compares them) are resampled against the reference's own rounded cumulative of N weights 1 / N;
+ *     any other upload by the integer rule, first i with (r + m / N) * S <= prefix[i], clamped to N - 1 (strict resampling: the
+ *     reference's cumulative for every set).
+ *   A total of 2 * num_particles units means "every particle at the likelihood floor" (weight 0.001 / wSum in resampling and in the
+ *     pose estimate) ONLY for a record a sensor update wrote, where every unit is at least 2.  An upload with that total -- [1,3,1,3..],
+ *     [0,4,0,4..], one unit of 2 N, every unit 2 -- is resampled and estimated with units / S like any other upload. */
 int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, const uint32_t* units);
 /* particles(): the local shard as lcm particle_t records (synchronises). */
 int bl_pf_get_particles(bl_pf* pf, bl_particle_t* out_local);

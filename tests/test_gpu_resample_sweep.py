@@ -43,6 +43,9 @@ def _sweep(oracle, ctx, N, units, strict=False):
             got = pf.debugResample(rv)
             oracle.lib.orc_resample_indices(host.ctypes.data, N, rv, want.ctypes.data)
             d = np.nonzero(got != want)[0]
+            # (the default rule itself is stated in tests/resample_rule_model.py; unequal weights on which it and the reference's rule
+            # part by that one index are committed in tests/golden/resample_parting_cases.npz and held exactly, both sides, by
+            # tests/test_gpu_uploaded_weights.py)
             assert np.all(np.abs(got[d].astype(np.int64) - want[d]) <= 1), (N, rv)        # never farther than the neighbour
             out[rv] = int(d.size)
     finally:
