@@ -13,6 +13,12 @@
 //     queue visits the touches in key order and grows every component not grown yet from its seed.
 // The depth of the computation is the number of BFS levels (inherent to the FIFO order); each level is a few barriers
 // of one 1024-thread workgroup, with all per-cell state in L2-resident arrays.
+//
+// Removed, so that nobody looks for them: the switches BOTLAB_FRONTIER_ONE_WG_SWEEP (one workgroup for flood and sweep of a grid
+// beyond LDS), BOTLAB_FRONTIER_OLD_FLOOD (the flood without the LDS hash on any grid) and BOTLAB_EXPLORER_NORMAL_PRIORITY (an
+// explorer lane on a stream of the default priority) -- never set by a test, a tool or the bench.  The code each surviving path
+// needs is still reached by its natural condition: the one-workgroup sweep when counts[8] asks for it, the flood without the hash on
+// a grid with a side beyond FL_MAX_SIDE; what only the first switch reached (flood and sweep of a large grid in ONE launch) went.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -39,7 +45,6 @@ struct frontier_args {
     int32_t* counts;            // [0] frontiers, [1] frontier cells, [2] free cells reached (+1), [3] levels, [4] overflow flag,
                                 // [5], [6] time stamps, [8] "take the one-workgroup sweep" flag, [10] "k_frontier_grow2 declined: k_frontier_grow"
                                 // flag, [12] frontier-class cells found, [13] touches found (k_frontier_touches: one 64-bit counter)
-    int phase;                  // k_frontiers: 0 flood + sweep (small grids), 1 flood only, 2 sweep only (and only if counts[8] is set)
     uint2* touch;               // (key, cell) of every frontier cell the flood touched, in no order; FR_TOUCH_MAX entries
     int32_t* fcell;             // every frontier-class cell of the grid, in no order; FG_CELL_MAX entries (k_frontier_touches; counts[12])
     int grow_v1;                // 1, 2: take k_frontier_grow (visited set only, classes from global memory) whatever the map holds
@@ -94,9 +99,14 @@ __device__ __forceinline__ int fr_log_odds(const frontier_args& a, int x, int y)
     return (x >= 0 && y >= 0 && x < a.W && y < a.H) ? (int)a.cells[(size_t)y * a.W + x] : 0;
 }
 
-// CLS_LDS: the class bytes of the whole grid live in LDS (grids up to FR_CLS_LDS cells); otherwise in the global scratch.
+// k_frontiers<FORM>, one workgroup:
+//   FR_ALL_LDS     classification, flood and sweep in one launch, the class bytes of the whole grid in LDS (grids up to FR_CLS_LDS cells);
+//   FR_FLOOD_ONLY  the flood of the multi-launch form over the class bytes in the global scratch (k_frontier_classify has filled them):
+//                  launched for grids with a side beyond FL_MAX_SIDE, every other grid floods through k_frontier_flood;
+//   FR_SWEEP_ONLY  the sweep of the multi-launch form over a finished flood, and only if counts[8] asks for it.
 // All communication is inside ONE workgroup (one CU, one vector L1): __syncthreads() orders plain stores/loads and makes
 // the claim atomics (performed at L2) complete; claim words are read back with L2-scope loads only.
+enum { FR_ALL_LDS = 0, FR_FLOOD_ONLY = 1, FR_SWEEP_ONLY = 2 };
 #define FR_CLS_LDS (96 * 1024)
 #define FR_LQ 4096                // next-level queue entries mirrored in LDS (wider levels are re-read from the global queue)
 #define FR_B 4                    // queue positions per thread in a batched level
@@ -213,18 +223,19 @@ __device__ __forceinline__ int fr_level_lds(const frontier_args& a, uint8_t* cls
     return total;
 }
 
-template <bool CLS_LDS>
+template <int FORM>
 __global__ __launch_bounds__(FR_T) void k_frontiers(frontier_args a)
 {
+    constexpr bool CLS_LDS = FORM == FR_ALL_LDS;
     fr_robot_cell(a);
     const long long t_begin = wall_clock64();
     extern __shared__ uint8_t s_cls[];
     __shared__ int s_wave[FR_T / 64];
     __shared__ unsigned int s_umin[FR_T / 64];
     __shared__ int s_q[2][FR_LQ];
-    // claims of a narrow level (large grids only: the small-grid form spends its LDS on the class bytes)
-    __shared__ int s_hc[CLS_LDS ? 1 : FR_CH];
-    __shared__ unsigned int s_hk[CLS_LDS ? 1 : FR_CH];
+    // claims of a narrow level (the flood of a large grid only: the small-grid form spends its LDS on the class bytes)
+    __shared__ int s_hc[FORM == FR_FLOOD_ONLY ? FR_CH : 1];
+    __shared__ unsigned int s_hk[FORM == FR_FLOOD_ONLY ? FR_CH : 1];
     __shared__ int s_full;
     const int tid = threadIdx.x;
     const long long ncell = (long long)a.W * a.H;
@@ -236,17 +247,17 @@ __global__ __launch_bounds__(FR_T) void k_frontiers(frontier_args a)
     __syncthreads();
     // ---- free-space flood (:47-82), xDeltas {-1,1,0,0}, yDeltas {0,0,1,-1}
     int lo = 0, hi = 1, levels = 0, cur = 0;
-    if (!CLS_LDS) {
+    if (FORM == FR_FLOOD_ONLY) {
         for (int i = tid; i < FR_CH; i += FR_T) { s_hc[i] = -1; s_hk[i] = FR_INF; }
         if (tid == 0) s_full = 0;
         __syncthreads();
     }
-    if (a.phase == 2) {                                     // the flood has run (phase 1): only the sweep, and only when asked for
+    if (FORM == FR_SWEEP_ONLY) {                            // the flood has run: only the sweep, and only when asked for
         if (a.counts[8] == 0) return;
         lo = hi = a.counts[2]; levels = a.counts[3];
     }
-    while (lo < hi) {
-        if (!CLS_LDS && hi - lo <= FR_B * FR_T) {
+    while (FORM != FR_SWEEP_ONLY && lo < hi) {
+        if (FORM == FR_FLOOD_ONLY && hi - lo <= FR_B * FR_T) {
             // ---- large grids, levels of up to FR_B x 1024 cells: claims on free cells settled in LDS (fr_level_lds)
             const int total = hi - lo <= FR_T ? fr_level_lds<1>(a, cls, s_q[cur], s_q[cur ^ 1], s_hc, s_hk, s_wave, &s_full, lo, hi)
                                               : fr_level_lds<FR_B>(a, cls, s_q[cur], s_q[cur ^ 1], s_hc, s_hk, s_wave, &s_full, lo, hi);
@@ -367,7 +378,7 @@ __global__ __launch_bounds__(FR_T) void k_frontiers(frontier_args a)
     }
     const int qn = hi;
     const long long t_flood = wall_clock64();
-    if (a.phase == 1) {
+    if (FORM == FR_FLOOD_ONLY) {
         if (tid == 0) { a.counts[2] = qn; a.counts[3] = levels; a.counts[5] = (int)(t_flood - t_begin); a.counts[8] = 0; a.counts[10] = 0; a.counts[12] = 0; a.counts[13] = 0; }
         return;
     }
@@ -471,13 +482,13 @@ __global__ __launch_bounds__(FR_T) void k_frontiers(frontier_args a)
     if (tid == 0) {
         if (nf <= a.cap_frontiers) a.out_offsets[nf] = total_cells;
         a.counts[0] = nf; a.counts[1] = total_cells; a.counts[2] = qn; a.counts[3] = levels; a.counts[4] = overflow;
-        if (a.phase == 0) a.counts[5] = (int)(t_flood - t_begin);
+        if (FORM == FR_ALL_LDS) a.counts[5] = (int)(t_flood - t_begin);
         a.counts[6] = (int)(wall_clock64() - t_flood);     // 100 MHz ticks: flood, frontier sweep
     }
 }
 
 // ---- large grids: the flood with everything a level needs in LDS ---------------------------------------------------------------
-// The level loop of k_frontiers<false> pays a global round trip per level for the class bytes of the neighbours (39 ms for 3582
+// The level loop of k_frontiers<FR_FLOOD_ONLY> pays a global round trip per level for the class bytes of the neighbours (39 ms for 3582
 // levels at 4096^2, 11 us a level).  Here a level needs NO global load that was not issued a level earlier:
 //   * k_frontier_nb leaves, per cell, the STATIC classes of its four neighbours in one byte (free / frontier / other); a queue
 //     entry carries its cell's byte, loaded when the cell was claimed (the load flies while the level's scan runs);
@@ -846,7 +857,7 @@ __global__ __launch_bounds__(FL_T) void k_frontier_flood(frontier_args a)
 //                       part of a grown frontier); ONE WAVE then runs the reference's FIFO growth serially, eight lanes looking
 //                       at the eight neighbours of up to eight queued cells per global round trip, the visited set an LDS hash.
 // A map with more touches than FR_TOUCH_MAX or a frontier larger than the hash holds takes the one-workgroup sweep instead
-// (k_frontiers phase 2, launched behind this one: it returns at once unless counts[8] is set).
+// (k_frontiers<FR_SWEEP_ONLY>, launched behind this one: it returns at once unless counts[8] is set).
 #define FR_TOUCH_MAX 16384
 #define FR_TOUCH_PER_THREAD (FR_TOUCH_MAX / FR_T)
 #define FR_HASH 16384                       // slots of the visited set (a power of two); a frontier may fill half of them
@@ -1177,7 +1188,7 @@ struct bl_frontier_scratch {
     uint2* touch = nullptr;
     uint8_t* nb = nullptr;
     int32_t* fcell = nullptr;
-    int form = 0;                     // the last launch: 0 one workgroup with the classes in LDS, 1 one workgroup (large grid), 2 the multi-launch form
+    int form = 0;                     // the last launch: 0 one workgroup with the classes in LDS, 2 the multi-launch form
 };
 
 void bl_frontier_scratch_free(bl_ctx* ctx)
@@ -1226,59 +1237,34 @@ static int frontiers_launch(bl_ctx* ctx, const bl_grid* map, const bl_pose_xyt_t
     if (!d_pose) bl_global_to_cell((double)robot_pose->x, (double)robot_pose->y, map->frame, &a.rx, &a.ry);      // :39
     a.cls = s->cls; a.claim = s->claim; a.fclaim = s->fclaim; a.queue = s->queue;
     a.out_cells = s->out_cells; a.out_offsets = s->out_offsets; a.cap_frontiers = s->cap_frontiers; a.counts = s->counts;
-    a.phase = 0; a.touch = s->touch; a.nb = s->nb; a.fcell = s->fcell;
+    a.touch = s->touch; a.nb = s->nb; a.fcell = s->fcell;
     static const int grow_v1 = getenv("BOTLAB_FRONTIER_GROW_V1") ? atoi(getenv("BOTLAB_FRONTIER_GROW_V1")) : 0;     // A/B runs and tests of that form
     a.grow_v1 = grow_v1;                                   // 1: k_frontier_grow from the start; 2: k_frontier_grow2 gives up once its set is built
     hipEvent_t e0, e1;
     int rc = bl_timer_begin(ctx, BL_K_FRONTIERS, &e0, &e1);
     if (rc) return rc;
     if (n <= (size_t)FR_CLS_LDS) {
-        static unsigned long long attr_set_devices = 0ull;
-        const unsigned long long bit = 1ull << (ctx->device & 63);
-        if (!(attr_set_devices & bit)) {
-            BL_HIP(hipFuncSetAttribute((const void*)k_frontiers<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FR_CLS_LDS));
-            attr_set_devices |= bit;
-        }
-        hipLaunchKernelGGL(k_frontiers<true>, dim3(1), dim3(FR_T), (n + 15) & ~(size_t)15, ctx->stream, a);
+        BL_DYN_LDS_ONCE_PER_DEVICE(k_frontiers<FR_ALL_LDS>, FR_CLS_LDS, ctx);
+        hipLaunchKernelGGL(k_frontiers<FR_ALL_LDS>, dim3(1), dim3(FR_T), (n + 15) & ~(size_t)15, ctx->stream, a);
         s->form = 0;
     } else {
         long long cblocks = ((long long)n + 255) / 256;
         if (cblocks > 8192) cblocks = 8192;
         hipLaunchKernelGGL(k_frontier_classify, dim3((unsigned int)cblocks), dim3(256), 0, ctx->stream, a);
-        static const bool one_wg_sweep = getenv("BOTLAB_FRONTIER_ONE_WG_SWEEP") != nullptr;       // A/B runs and tests of the fallback
-        s->form = one_wg_sweep ? 1 : 2;
-        if (one_wg_sweep) {
-            hipLaunchKernelGGL(k_frontiers<false>, dim3(1), dim3(FR_T), 0, ctx->stream, a);
+        s->form = 2;
+        if (W <= FL_MAX_SIDE && H <= FL_MAX_SIDE) {
+            // the flood with its levels' state in LDS (k_frontier_flood): entries are 14-bit coordinates
+            BL_DYN_LDS_ONCE_PER_DEVICE(k_frontier_flood, FL_LDS_BYTES, ctx);
+            hipLaunchKernelGGL(k_frontier_nb, dim3((unsigned int)cblocks), dim3(256), 0, ctx->stream, a);
+            hipLaunchKernelGGL(k_frontier_flood, dim3(1), dim3(FL_T), FL_LDS_BYTES, ctx->stream, a);
         } else {
-            a.phase = 1;
-            static const bool old_flood = getenv("BOTLAB_FRONTIER_OLD_FLOOD") != nullptr;                 // A/B runs
-            if (!old_flood && W <= FL_MAX_SIDE && H <= FL_MAX_SIDE) {
-                // the flood with its levels' state in LDS (k_frontier_flood): entries are 14-bit coordinates
-                static unsigned long long attr_set_devices = 0ull;
-                const unsigned long long bit = 1ull << (ctx->device & 63);
-                if (!(attr_set_devices & bit)) {
-                    BL_HIP(hipFuncSetAttribute((const void*)k_frontier_flood, hipFuncAttributeMaxDynamicSharedMemorySize, FL_LDS_BYTES));
-                    attr_set_devices |= bit;
-                }
-                hipLaunchKernelGGL(k_frontier_nb, dim3((unsigned int)cblocks), dim3(256), 0, ctx->stream, a);
-                hipLaunchKernelGGL(k_frontier_flood, dim3(1), dim3(FL_T), FL_LDS_BYTES, ctx->stream, a);
-            } else {
-                hipLaunchKernelGGL(k_frontiers<false>, dim3(1), dim3(FR_T), 0, ctx->stream, a);
-            }
-            hipLaunchKernelGGL(k_frontier_touches, dim3((unsigned int)((cblocks + 3) / 4)), dim3(256), 0, ctx->stream, a);       // (four cells per thread)
-            {
-                static unsigned long long attr_set_devices = 0ull;
-                const unsigned long long bit = 1ull << (ctx->device & 63);
-                if (!(attr_set_devices & bit)) {
-                    BL_HIP(hipFuncSetAttribute((const void*)k_frontier_grow2, hipFuncAttributeMaxDynamicSharedMemorySize, FG_LDS_BYTES));
-                    attr_set_devices |= bit;
-                }
-            }
-            hipLaunchKernelGGL(k_frontier_grow2, dim3(1), dim3(FR_T), FG_LDS_BYTES, ctx->stream, a);
-            hipLaunchKernelGGL(k_frontier_grow, dim3(1), dim3(FR_T), 0, ctx->stream, a);         // (returns at once unless counts[10] is set)
-            a.phase = 2;
-            hipLaunchKernelGGL(k_frontiers<false>, dim3(1), dim3(FR_T), 0, ctx->stream, a);
+            hipLaunchKernelGGL(k_frontiers<FR_FLOOD_ONLY>, dim3(1), dim3(FR_T), 0, ctx->stream, a);
         }
+        hipLaunchKernelGGL(k_frontier_touches, dim3((unsigned int)((cblocks + 3) / 4)), dim3(256), 0, ctx->stream, a);       // (four cells per thread)
+        BL_DYN_LDS_ONCE_PER_DEVICE(k_frontier_grow2, FG_LDS_BYTES, ctx);
+        hipLaunchKernelGGL(k_frontier_grow2, dim3(1), dim3(FR_T), FG_LDS_BYTES, ctx->stream, a);
+        hipLaunchKernelGGL(k_frontier_grow, dim3(1), dim3(FR_T), 0, ctx->stream, a);         // (returns at once unless counts[10] is set)
+        hipLaunchKernelGGL(k_frontiers<FR_SWEEP_ONLY>, dim3(1), dim3(FR_T), 0, ctx->stream, a);  // (returns at once unless counts[8] is set)
     }
     BL_HIP(hipGetLastError());
     rc = bl_timer_end(ctx, BL_K_FRONTIERS, e0, e1);
@@ -1304,7 +1290,7 @@ static int frontiers_collect(bl_ctx* ctx, const bl_frame& frame, double min_fron
     if (total > 0) BL_HIP(hipMemcpy(cells.data(), s->out_cells, (size_t)total * 4, hipMemcpyDeviceToHost));
     bl_frontiers* f = new bl_frontiers();
     f->bfs_cells = s->h_counts[2]; f->bfs_levels = s->h_counts[3];
-    f->sweep_kernel = s->form < 2 ? s->form : (s->h_counts[8] ? 1 : (s->h_counts[10] ? 2 : 3));
+    f->sweep_kernel = s->form == 0 ? 0 : (s->h_counts[8] ? 1 : (s->h_counts[10] ? 2 : 3));
     f->offsets.push_back(0);
     for (int k = 0; k < nf; ++k) {
         const int cnt = offs[k + 1] - offs[k];
@@ -1421,10 +1407,10 @@ extern "C" int bl_explorer_create(bl_ctx* ctx, int lanes, double robot_radius, b
     e->planner.prev_goal.x = 1e9f; e->planner.prev_goal.y = 1e9f;   // never set by the reference's exploration loop (D5)
     // (a failure below hands the partly built explorer to bl_explorer_destroy, which tolerates missing members: nothing leaks)
     auto build_lane = [&](explorer_lane& L) -> int {
-        // a lane's stream has the lowest priority (BOTLAB_EXPLORER_NORMAL_PRIORITY=1: the default one): a plan to a frontier is one
+        // a lane's stream has the lowest priority: a plan to a frontier is one
         // kernel of up to seconds, and streams of one priority share the runtime's four hardware queues -- with its stream behind
         // a lane's on one queue the SLAM loop ran at 182 instead of 3 700 steps/s (4096 x 4096, the explorer on every newest map)
-        int rc = getenv("BOTLAB_EXPLORER_NORMAL_PRIORITY") ? bl_ctx_create(ctx->device, nullptr, &L.ctx) : bl_ctx_create_low_priority(ctx->device, &L.ctx);
+        int rc = bl_ctx_create_low_priority(ctx->device, &L.ctx);
         if (rc) return rc;
         L.ctx->astar_small_lds = true;                  // its searches co-run with the SLAM stream's kernels
         rc = bl_dist_create(L.ctx, &L.dist);
@@ -1493,7 +1479,7 @@ extern "C" int bl_explorer_submit(bl_explorer* e, const bl_grid* map, const void
     L.snap->frame = map->frame;
     L.snap->mirror_valid = false;
     // (the lane is idle: its last submission has been fetched, and a fetch leaves nothing behind on the lane's stream)
-    int rc = bl_snapshot_enqueue(e->main, map, L.snap, d_pose, L.d_pose, nullptr, nullptr, 0ull);
+    int rc = bl_snapshot_enqueue(e->main, map, L.snap, d_pose, L.d_pose);
     if (rc) return rc;
     BL_HIP(hipEventRecord(L.snap_ready, e->main->stream));
     BL_HIP(hipStreamWaitEvent(L.ctx->stream, L.snap_ready, 0));

@@ -31,6 +31,18 @@ int bl_ctx_create_low_priority(int device, bl_ctx** out);      // bl_ctx.hip: ow
         }                                                                             \
     } while (0)
 
+// `kernel` may ask for up to `bytes` of dynamic LDS.  The attribute belongs to the device that is current when it is set: once per
+// device this process drives (each place that says this keeps its own record of the devices done).
+#define BL_DYN_LDS_ONCE_PER_DEVICE(kernel, bytes, ctx)                                                                   \
+    do {                                                                                                                 \
+        static unsigned long long attr_set_devices_ = 0ull;                                                              \
+        const unsigned long long bit_ = 1ull << ((ctx)->device & 63);                                                    \
+        if (!(attr_set_devices_ & bit_)) {                                                                               \
+            BL_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)));  \
+            attr_set_devices_ |= bit_;                                                                                   \
+        }                                                                                                                \
+    } while (0)
+
 struct bl_timer {
     double total_ms = 0;
     int64_t launches = 0;
@@ -131,15 +143,12 @@ void bl_grid_adopt_lineage(bl_grid* snap, const bl_grid* src);   // snap's cells
 int4* bl_grid_log_next(bl_grid* g, uint64_t* version);
 
 // bl_planning.hip: map + device pose snapshot on main's stream (whole grid, or the dirty cells when snap holds an earlier version)
-int bl_snapshot_enqueue(struct bl_ctx* main, const bl_grid* map, bl_grid* snap, const void* d_pose, bl_pose_xyt_t* snap_pose,
-                        unsigned int* done_count, unsigned long long* flag, unsigned long long seq);
+int bl_snapshot_enqueue(struct bl_ctx* main, const bl_grid* map, bl_grid* snap, const void* d_pose, bl_pose_xyt_t* snap_pose);
 
-// where a replanner submission wants its map + pose snapshot, and the number to publish in *flag when it is complete
+// where a replanner submission wants its map + pose snapshot (the lane waits for it behind an event on the SLAM stream)
 struct bl_planner_snap {
     bl_grid* grid;                    // the snapshot grid itself (its lineage is set once the copy is enqueued)
     int8_t* cells; bl_pose_xyt_t* pose;
-    unsigned long long* flag; unsigned long long seq;
-    unsigned int* done_count;
 };
 int bl_planner_reserve(bl_planner* p, const bl_grid* map, bl_planner_snap* out);                    // bl_planning.hip
 int bl_planner_commit(bl_planner* p, const bl_pose_xyt_t* goal, const bl_search_params_t* params);

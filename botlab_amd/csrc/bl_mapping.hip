@@ -55,10 +55,9 @@ struct map_args {
     long long* stamps;              // diagnostic build only (-DBL_MAP_STAMPS)
     int8_t* mirror; int mirror_stride;   // cell (0, 0) of the grid's zero-framed mirror when it is current (bl_internal.h), or null
     int4* dirty_entry; unsigned long long dirty_version;   // the lineage's log entry of this update (bl_internal.h), or null
-    // optional tail: copy the updated grid and the pose to a replanner snapshot and publish its submission number
+    // optional tail: copy the updated grid and the pose to a replanner snapshot
     // (bl_planner_submit_with_map_update: saves a dependent launch on the SLAM stream)
     int8_t* snap_cells; bl_pose_xyt_t* snap_pose; const bl_pose_xyt_t* snap_pose_src;
-    unsigned long long* snap_flag; unsigned long long snap_seq;
     // optional: the end of the particle-filter update whose pose estimate this map update uses (bl_mcl_finish.h).
     // Workgroup 0 forms the estimate before it reads the pose; workgroups 1.. write the weight prefix meanwhile.
     int fin_on; mcl_finish_args fin;
@@ -182,11 +181,6 @@ __global__ __launch_bounds__(MAP_THREADS) void k_map_update(map_args a)
         }
         // (a riding finish: the estimate was written by another workgroup of this launch -- take it from this one's LDS copy)
         if (threadIdx.x == 0) *a.snap_pose = a.fin_on ? s_fin_pose : *a.snap_pose_src;
-        if (a.snap_flag) {                                              // flag hand-off only; an event hand-off needs nothing here
-            __threadfence();
-            __syncthreads();
-            if (threadIdx.x == 0) __hip_atomic_store(a.snap_flag, a.snap_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
     }
 }
 
@@ -634,10 +628,9 @@ static int mapping_update_impl(bl_mapping* m, const bl_lidar_t* scan, const bl_p
     } else map->mirror_valid = false;
     // the cells this update may change go to the lineage's log (grids up to 65535 a side: checked above)
     a.dirty_entry = bl_grid_log_next(map, (uint64_t*)&a.dirty_version);
-    a.snap_cells = nullptr; a.snap_pose = nullptr; a.snap_pose_src = nullptr; a.snap_flag = nullptr; a.snap_seq = 0;
+    a.snap_cells = nullptr; a.snap_pose = nullptr; a.snap_pose_src = nullptr;
     if (snap) {
         a.snap_cells = snap->cells; a.snap_pose = snap->pose; a.snap_pose_src = (const bl_pose_xyt_t*)d_pose;
-        a.snap_flag = snap->flag; a.snap_seq = snap->seq;
     }
 #ifdef BL_MAP_STAMPS
     static long long* d_st = nullptr;

@@ -13,11 +13,18 @@
 // (std::push_heap / std::pop_heap semantics, stl_heap.h) by one wavefront; the closed list is an int32 grid of parent moves
 // (first closing of a cell wins, which is all is_member/get_member ever observe).  Single-search latency is bound by
 // dependent memory accesses, not bandwidth (DESIGN.md "A*").
+//
+// Removed, so that nobody looks for them: the replanner's flag hand-off (BOTLAB_PLANNER_HANDOFF_FLAG: a word the snapshot kernels
+// published and a lane's stream waited on -- every hand-off is an event), the rings of plan_path_to_frontier evaluated ahead of the
+// rule (BOTLAB_FRONTIER_SPECULATE: measured not to pay), the whole-grid transform through the region kernels
+// (BOTLAB_DIST_REGION_COLS) and the switches BOTLAB_SNAPSHOT_NO_INCREMENTAL, BOTLAB_PLAN_TRACE and BOTLAB_PLANNER_OPEN_CAPACITY
+// (now the constant PLANNER_OPEN_ENTRIES) -- never set by a test, a tool or the bench.  The code each surviving path needs is
+// still reached by its natural condition: the region kernels by an incremental transform, the whole-grid snapshot by a first
+// snapshot or a new lineage.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <chrono>
 #include <cmath>
 #include <deque>
 #include <map>
@@ -1639,24 +1646,14 @@ static int dist_set_distances_batch(int n, bl_dist* const* ds, const bl_grid* co
         return BL_OK;
     }
     for (int u = 0; u < n; ++u) ds[u]->floats_valid = false;
-    const bool merged = H >= 4 * DC2_ROWS && W >= 4 * DC2_TX && (W & 1) == 0 && (H + DC2_ROWS - 1) / DC2_ROWS <= DST_MAX_GROUPS;
     const int strips = (H + DC2_ROWS - 1) / DC2_ROWS;
-    const size_t merged_lds = (size_t)2 * strips * 2 * DC2_TX * sizeof(int);
-    {   // the attribute belongs to the device that is current when it is set: once per device this process drives
-        static unsigned long long attr_set_devices = 0ull;
-        const unsigned long long bit = 1ull << (ctx->device & 63);
-        if (!(attr_set_devices & bit)) {
-            BL_HIP(hipFuncSetAttribute((const void*)k_dist_cols_region<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * DST_MAX_GROUPS * 2 * DC2_TX * (int)sizeof(int)));
-            attr_set_devices |= bit;
-        }
-    }
+    const bool two_pass_cols = H >= 4 * DC2_ROWS && W >= 4 * DC2_TX && (W & 1) == 0;     // the column pass in strips of DC2_ROWS rows
+    const bool merged = two_pass_cols && strips <= DST_MAX_GROUPS;
+    BL_DYN_LDS_ONCE_PER_DEVICE(k_dist_cols_region<1>, 2 * DST_MAX_GROUPS * 2 * DC2_TX * (int)sizeof(int), ctx);
     hipEvent_t e0, e1;
     int rc = bl_timer_begin(ctx, BL_K_DIST, &e0, &e1);
     if (rc) return rc;
     hipEvent_t f0, f1;
-    // BOTLAB_DIST_REGION_COLS=1: a transform of the whole grid goes through the region kernels too (their plan = the grid): tests
-    static const bool region_kernels = getenv("BOTLAB_DIST_REGION_COLS") != nullptr;
-    const bool bound_kept = all_inc || (merged && region_kernels);                       // the column pass leaves the bound D behind
     if (all_inc) {
         // The window is B dilated by D + 1, so D must bound l1 as it stands: the whole-grid kernels leave none behind
         // (dist_plan_full: zero) -- the first incremental transform after one of them forms it, one read of l1.
@@ -1675,6 +1672,7 @@ static int dist_set_distances_batch(int n, bl_dist* const* ds, const bl_grid* co
         rc = bl_timer_end(ctx, BL_K_DIST_ROWS, f0, f1);
         if (rc) return rc;
         const int win_items = (DINC_MAX / (2 * DC2_TX)) * (DINC_MAX / DC2_ROWS);       // the widest window's items
+        const size_t merged_lds = (size_t)2 * strips * 2 * DC2_TX * sizeof(int);
         rc = bl_timer_begin(ctx, BL_K_DIST_COLS_SUMMARY, &f0, &f1);
         if (rc) return rc;
         hipLaunchKernelGGL(k_dist_cols_region<0>, dim3(win_items, 1, n), dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
@@ -1690,7 +1688,7 @@ static int dist_set_distances_batch(int n, bl_dist* const* ds, const bl_grid* co
         // (BOTLAB_DIST_NO_FUSED=1: the four-launch form)
         const bool no_fused = getenv("BOTLAB_DIST_NO_FUSED") != nullptr;        // (read per call: tests switch forms inside one process)
         const int tiles = ((W + DF_T - 1) / DF_T) * ((H + DF_T - 1) / DF_T);
-        const bool fused = !no_fused && !region_kernels && (W & 15) == 0 && W >= 4 * DF_T && H >= 4 * DF_T && W <= DF_MAX_SIDE && H <= DF_MAX_SIDE &&
+        const bool fused = !no_fused && (W & 15) == 0 && W >= 4 * DF_T && H >= 4 * DF_T && W <= DF_MAX_SIDE && H <= DF_MAX_SIDE &&
                            tiles <= DF_MAXK * DF_MAX_WGS;
         if (fused) {
             const int per_wg = (tiles + DF_MAX_WGS - 1) / DF_MAX_WGS;           // tiles a workgroup keeps in registers
@@ -1729,50 +1727,38 @@ static int dist_set_distances_batch(int n, bl_dist* const* ds, const bl_grid* co
             rc = bl_timer_end(ctx, BL_K_DIST_FUSED, f0, f1);
             if (rc) return rc;
         } else {
-        if (!merged) for (int u = 0; u < n; ++u) b.state[u] = nullptr;      // (the small-grid column pass keeps no plan or bound)
-        rc = bl_timer_begin(ctx, BL_K_DIST_ROWS, &f0, &f1);
-        if (rc) return rc;
-        if (W >= 1024 && (W & 15) == 0) hipLaunchKernelGGL(k_dist_rows_wide, dim3(H, 1, n), dim3(256), 0, ctx->stream, b, W);
-        else if (W <= 256 && (W & 3) == 0) hipLaunchKernelGGL(k_dist_rows_narrow, dim3((H + 3) / 4, 1, n), dim3(256), 0, ctx->stream, b, W, H);
-        else hipLaunchKernelGGL(k_dist_rows, dim3(H, 1, n), dim3(256), 0, ctx->stream, b, W);
-        rc = bl_timer_end(ctx, BL_K_DIST_ROWS, f0, f1);
-        if (rc) return rc;
-        if (merged && region_kernels) {
-            const int groups = (W + 2 * DC2_TX - 1) / (2 * DC2_TX);
-            rc = bl_timer_begin(ctx, BL_K_DIST_COLS_SUMMARY, &f0, &f1);
+            if (!merged) for (int u = 0; u < n; ++u) b.state[u] = nullptr;      // (the small-grid column pass keeps no plan or bound)
+            rc = bl_timer_begin(ctx, BL_K_DIST_ROWS, &f0, &f1);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_dist_cols_region<0>, dim3(groups * strips, 1, n), dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
-            rc = bl_timer_end(ctx, BL_K_DIST_COLS_SUMMARY, f0, f1);
+            if (W >= 1024 && (W & 15) == 0) hipLaunchKernelGGL(k_dist_rows_wide, dim3(H, 1, n), dim3(256), 0, ctx->stream, b, W);
+            else if (W <= 256 && (W & 3) == 0) hipLaunchKernelGGL(k_dist_rows_narrow, dim3((H + 3) / 4, 1, n), dim3(256), 0, ctx->stream, b, W, H);
+            else hipLaunchKernelGGL(k_dist_rows, dim3(H, 1, n), dim3(256), 0, ctx->stream, b, W);
+            rc = bl_timer_end(ctx, BL_K_DIST_ROWS, f0, f1);
             if (rc) return rc;
-            rc = bl_timer_begin(ctx, BL_K_DIST_COLS_APPLY, &f0, &f1);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_dist_cols_region<1>, dim3(groups * strips, 1, n), dim3(DC2_TX, DC2_TY), merged_lds, ctx->stream, b, W, H);
-            rc = bl_timer_end(ctx, BL_K_DIST_COLS_APPLY, f0, f1);
-            if (rc) return rc;
-        } else if (H >= 4 * DC2_ROWS && W >= 4 * DC2_TX && (W & 1) == 0) {
-            const dim3 grid2((W + 2 * DC2_TX - 1) / (2 * DC2_TX), strips, n);
-            rc = bl_timer_begin(ctx, BL_K_DIST_COLS_SUMMARY, &f0, &f1);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_dist_cols_summary, grid2, dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
-            const bool carried = (H + DC2_ROWS - 1) / DC2_ROWS <= DC2_STAGE;
-            // (the small carry kernel is timed with the summaries it turns into carries)
-            if (carried) hipLaunchKernelGGL(k_dist_cols_carry, dim3((W + 255) / 256, 1, n), dim3(256), 0, ctx->stream, b, W, H);
-            rc = bl_timer_end(ctx, BL_K_DIST_COLS_SUMMARY, f0, f1);
-            if (rc) return rc;
-            rc = bl_timer_begin(ctx, BL_K_DIST_COLS_APPLY, &f0, &f1);
-            if (rc) return rc;
-            if (carried) hipLaunchKernelGGL(k_dist_cols_apply<true>, grid2, dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
-            else hipLaunchKernelGGL(k_dist_cols_apply<false>, grid2, dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
-            rc = bl_timer_end(ctx, BL_K_DIST_COLS_APPLY, f0, f1);
-            if (rc) return rc;
-        } else {
-            rc = bl_timer_begin(ctx, BL_K_DIST_COLS_APPLY, &f0, &f1);
-            if (rc) return rc;
-            if (H <= DCOL_TY * DCOLS_ROWS) hipLaunchKernelGGL(k_dist_cols_small, dim3((W + DCOL_TX - 1) / DCOL_TX, 1, n), dim3(DCOL_TX, DCOL_TY), 0, ctx->stream, b, W, H);
-            else hipLaunchKernelGGL(k_dist_cols, dim3((W + DCOL_TX - 1) / DCOL_TX, 1, n), dim3(DCOL_TX, DCOL_TY), 0, ctx->stream, b, W, H);
-            rc = bl_timer_end(ctx, BL_K_DIST_COLS_APPLY, f0, f1);
-            if (rc) return rc;
-        }
+            if (two_pass_cols) {
+                const dim3 grid2((W + 2 * DC2_TX - 1) / (2 * DC2_TX), strips, n);
+                rc = bl_timer_begin(ctx, BL_K_DIST_COLS_SUMMARY, &f0, &f1);
+                if (rc) return rc;
+                hipLaunchKernelGGL(k_dist_cols_summary, grid2, dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
+                const bool carried = strips <= DC2_STAGE;
+                // (the small carry kernel is timed with the summaries it turns into carries)
+                if (carried) hipLaunchKernelGGL(k_dist_cols_carry, dim3((W + 255) / 256, 1, n), dim3(256), 0, ctx->stream, b, W, H);
+                rc = bl_timer_end(ctx, BL_K_DIST_COLS_SUMMARY, f0, f1);
+                if (rc) return rc;
+                rc = bl_timer_begin(ctx, BL_K_DIST_COLS_APPLY, &f0, &f1);
+                if (rc) return rc;
+                if (carried) hipLaunchKernelGGL(k_dist_cols_apply<true>, grid2, dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
+                else hipLaunchKernelGGL(k_dist_cols_apply<false>, grid2, dim3(DC2_TX, DC2_TY), 0, ctx->stream, b, W, H);
+                rc = bl_timer_end(ctx, BL_K_DIST_COLS_APPLY, f0, f1);
+                if (rc) return rc;
+            } else {
+                rc = bl_timer_begin(ctx, BL_K_DIST_COLS_APPLY, &f0, &f1);
+                if (rc) return rc;
+                if (H <= DCOL_TY * DCOLS_ROWS) hipLaunchKernelGGL(k_dist_cols_small, dim3((W + DCOL_TX - 1) / DCOL_TX, 1, n), dim3(DCOL_TX, DCOL_TY), 0, ctx->stream, b, W, H);
+                else hipLaunchKernelGGL(k_dist_cols, dim3((W + DCOL_TX - 1) / DCOL_TX, 1, n), dim3(DCOL_TX, DCOL_TY), 0, ctx->stream, b, W, H);
+                rc = bl_timer_end(ctx, BL_K_DIST_COLS_APPLY, f0, f1);
+                if (rc) return rc;
+            }
         }
     }
     BL_HIP(hipGetLastError());
@@ -1787,7 +1773,7 @@ static int dist_set_distances_batch(int n, bl_dist* const* ds, const bl_grid* co
         // l1 is now the transform of this version of this lineage (the small-grid and two-pass column kernels keep no bound D: the
         // next transform is a full one as well)
         d->src_id = bl_grid_lineage_id(maps[u]); d->src_version = maps[u]->version;
-        d->bound_ok = bound_kept;
+        d->bound_ok = all_inc;
     }
     return BL_OK;
 }
@@ -3065,6 +3051,7 @@ extern "C" int bl_dist_gather(bl_dist* d, const int32_t* xy_cells, int n, float*
 #define PLANNER_SLOTS 2
 #define PLANNER_MAX_LANES 4
 #define PLANNER_MAX_BATCH ASTAR_MAX_UNITS
+#define PLANNER_OPEN_ENTRIES ((int64_t)1 << 22)        // open list of a unit: 4 M entries (32 MB) -- up to 4 x 32 units exist
 
 // A unit = what one replan needs: a ctx (A* scratch + result ring) on the lane's stream, a distance grid, snapshot slots.
 // A lane = one side stream with `batch` units.  Consecutive submissions fill the units of one lane; when the last one is
@@ -3101,10 +3088,7 @@ struct bl_planner {
     int cur_lane;                       // the lane collecting submissions
     int64_t submitted, fetched;
     std::deque<planner_ticket>* tickets;    // outstanding submissions, oldest first
-    unsigned long long* d_flag;         // number of the last submission whose snapshot is complete (written by the snapshot kernel)
-    unsigned int* d_done;               // workgroup counter of the multi-workgroup snapshot kernel
     bool reserved;
-    bool handoff_flag;                  // lane waits on the flag word (hipStreamWaitValue64) instead of an event
 };
 
 extern "C" int bl_planner_create_batched(bl_ctx* ctx, int lanes, int batch, bl_planner** out)
@@ -3118,12 +3102,6 @@ extern "C" int bl_planner_create_batched(bl_ctx* ctx, int lanes, int batch, bl_p
     p->lanes = lanes;
     p->batch = batch;
     p->tickets = new std::deque<planner_ticket>();
-    p->handoff_flag = getenv("BOTLAB_PLANNER_HANDOFF_FLAG") != nullptr;
-    BL_HIP(hipMalloc((void**)&p->d_flag, 8));
-    BL_HIP(hipMalloc((void**)&p->d_done, 4));
-    BL_HIP(hipMemsetAsync(p->d_flag, 0, 8, ctx->stream));        // on the SLAM stream: the null stream (and its hardware queue) stays untouched
-    BL_HIP(hipMemsetAsync(p->d_done, 0, 4, ctx->stream));
-    BL_HIP(hipStreamSynchronize(ctx->stream));
     for (int l = 0; l < lanes; ++l) {
         planner_lane& L = p->lane[l];
         for (int u = 0; u < batch; ++u) {
@@ -3134,8 +3112,7 @@ extern "C" int bl_planner_create_batched(bl_ctx* ctx, int lanes, int batch, bl_p
             // searches that co-run with the SLAM stream's kernels take the small LDS footprint; a planner with one search in flight
             // (the closed loop: every path fetched before the next step) gives it a CU's whole LDS
             U.ctx->astar_small_lds = lanes * batch > 1;
-            // open list of a unit: 4 M entries (32 MB) unless BOTLAB_PLANNER_OPEN_CAPACITY says otherwise -- up to 4 x 32 units exist
-            U.ctx->astar_capacity = getenv("BOTLAB_PLANNER_OPEN_CAPACITY") ? atoll(getenv("BOTLAB_PLANNER_OPEN_CAPACITY")) : ((int64_t)1 << 22);
+            U.ctx->astar_capacity = PLANNER_OPEN_ENTRIES;
             rc = bl_dist_create(U.ctx, &U.dist);
             if (rc) return rc;
             for (int i = 0; i < PLANNER_SLOTS; ++i) {
@@ -3172,18 +3149,13 @@ extern "C" void bl_planner_destroy(bl_planner* p)
         }
         for (int i = 0; i < PLANNER_SLOTS; ++i) if (L.slot_free[i]) (void)hipEventDestroy(L.slot_free[i]);
     }
-    if (p->d_flag) (void)hipFree(p->d_flag);
-    if (p->d_done) (void)hipFree(p->d_done);
     delete p->tickets;
     delete p;
 }
 
-// map + pose snapshot as ONE kernel on the SLAM stream (two hipMemcpyAsync D2D cost two copy-engine handshakes there).
-// The last workgroup to finish publishes the submission number to the planner's flag word; the lane stream waits for it
-// with hipStreamWaitValue64 -- nothing is recorded on the SLAM stream (an event record costs ~4-7 us of stream time).
+// map + pose snapshot as ONE kernel on the SLAM stream (two hipMemcpyAsync D2D cost two copy-engine handshakes there)
 __global__ __launch_bounds__(256) void k_planner_snapshot(const int8_t* __restrict__ src, int8_t* __restrict__ dst, size_t n,
-                                                          const bl_pose_xyt_t* __restrict__ src_pose, bl_pose_xyt_t* __restrict__ dst_pose,
-                                                          unsigned int* done_count, unsigned long long* flag, unsigned long long seq)
+                                                          const bl_pose_xyt_t* __restrict__ src_pose, bl_pose_xyt_t* __restrict__ dst_pose)
 {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t n16 = n / 16;
@@ -3192,20 +3164,6 @@ __global__ __launch_bounds__(256) void k_planner_snapshot(const int8_t* __restri
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) d4[i] = s4[i];
     for (size_t i = n16 * 16 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = src[i];
     if (blockIdx.x == 0 && threadIdx.x == 0) *dst_pose = *src_pose;
-    if (flag) {                                     // flag hand-off only; an event hand-off needs nothing here
-        // one fence per workgroup, after its barrier (a fence in every thread writes L2 back half a million times on a
-        // 16 MB grid: the copy then took 230 us instead of ~10)
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __threadfence();
-            const unsigned int old = atomicAdd(done_count, 1u);
-            if (old == gridDim.x - 1) {
-                *done_count = 0;
-                __threadfence();
-                __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
 }
 
 // The searches of the lane's collected submissions as one launch; the next lane collects from here on.
@@ -3214,7 +3172,7 @@ static int planner_launch_lane(bl_planner* p, int l)
     planner_lane& L = p->lane[l];
     if (L.filled == 0) return BL_OK;
     const int slot = (int)(L.batches % PLANNER_SLOTS);
-    if (p->batch > 1 && !p->handoff_flag) {
+    if (p->batch > 1) {
         // the deferred hand-over of bl_planner_commit: one event behind the newest snapshot covers every snapshot of the batch
         BL_HIP(hipEventRecord(L.unit[0].snap_ready[slot], p->main->stream));
         BL_HIP(hipStreamWaitEvent(L.side->stream, L.unit[0].snap_ready[slot], 0));
@@ -3243,7 +3201,7 @@ static int planner_launch_lane(bl_planner* p, int l)
 }
 
 // First half of a submission: pick the lane, unit and snapshot slot, make the SLAM stream safe to overwrite the slot, and
-// say where the snapshot goes and which number to publish when it is complete.
+// say where the snapshot goes.
 int bl_planner_reserve(bl_planner* p, const bl_grid* map, bl_planner_snap* out)
 {
     BL_CHECK_ARG(p != nullptr && map != nullptr && out != nullptr);
@@ -3283,16 +3241,13 @@ int bl_planner_reserve(bl_planner* p, const bl_grid* map, bl_planner_snap* out)
     out->cells = snap->cells;
     snap->mirror_valid = false;                              // (nobody localises on a snapshot, but its cells are about to change)
     out->pose = U.pose[slot];
-    out->flag = p->handoff_flag ? p->d_flag : nullptr;
-    out->seq = (unsigned long long)p->submitted + 1ull;
-    out->done_count = p->d_done;
     p->reserved = true;
     return BL_OK;
 }
 
 void bl_planner_cancel(bl_planner* p) { if (p) p->reserved = false; }
 
-// Second half: the lane stream waits for the published number and runs setDistances on the snapshot; search_for_path goes
+// Second half: the lane stream waits for the snapshot (an event) and runs setDistances on it; search_for_path goes
 // out with the lane's batch (at once when batch == 1).
 int bl_planner_commit(bl_planner* p, const bl_pose_xyt_t* goal, const bl_search_params_t* params)
 {
@@ -3305,16 +3260,11 @@ int bl_planner_commit(bl_planner* p, const bl_pose_xyt_t* goal, const bl_search_
     const int slot = (int)(L.batches % PLANNER_SLOTS);
     // A lane that collects a batch hands over ONCE, when the batch goes out (planner_launch_lane): an event record costs
     // the SLAM stream several microseconds, and the lane cannot start the batch's searches before its last snapshot anyway.
-    const bool deferred = p->batch > 1 && !p->handoff_flag;
-    int rc = BL_OK;
+    const bool deferred = p->batch > 1;
     if (!deferred) {
-        if (p->handoff_flag) {
-            BL_HIP(hipStreamWaitValue64(L.side->stream, p->d_flag, (uint64_t)p->submitted + 1ull, hipStreamWaitValueGte, 0xffffffffffffffffull));
-        } else {
-            BL_HIP(hipEventRecord(U.snap_ready[slot], p->main->stream));
-            BL_HIP(hipStreamWaitEvent(L.side->stream, U.snap_ready[slot], 0));
-        }
-        rc = bl_dist_set_distances(U.dist, U.snap[slot]);
+        BL_HIP(hipEventRecord(U.snap_ready[slot], p->main->stream));
+        BL_HIP(hipStreamWaitEvent(L.side->stream, U.snap_ready[slot], 0));
+        const int rc = bl_dist_set_distances(U.dist, U.snap[slot]);
         if (rc) return rc;
     }
     U.goal = *goal; U.params = *params;
@@ -3382,17 +3332,14 @@ __global__ __launch_bounds__(256) void k_planner_snapshot_inc(const int8_t* __re
 
 // Map + pose snapshot on main's stream into a grid of the same size (the whole grid, or -- when `snap` still holds an earlier
 // version of this very map -- the cells the updates in between may have changed); the snapshot then carries the map's lineage.
-// flag / done_count / seq: the replanner's flag hand-over (null / 0: none).
-int bl_snapshot_enqueue(bl_ctx* main, const bl_grid* map, bl_grid* snap, const void* d_pose, bl_pose_xyt_t* snap_pose,
-                        unsigned int* done_count, unsigned long long* flag, unsigned long long seq)
+int bl_snapshot_enqueue(bl_ctx* main, const bl_grid* map, bl_grid* snap, const void* d_pose, bl_pose_xyt_t* snap_pose)
 {
     const size_t n = (size_t)map->frame.width * map->frame.height;
     hipEvent_t f0, f1;
     int rc = bl_timer_begin(main, BL_K_SNAPSHOT, &f0, &f1);
     if (rc) return rc;
-    static const bool no_inc = getenv("BOTLAB_SNAPSHOT_NO_INCREMENTAL") != nullptr;
     const bl_grid* old = snap;
-    const bool inc = !no_inc && !flag && old->id != 0 && old->id == map->id && !map->mirror_external && map->log != nullptr &&
+    const bool inc = old->id != 0 && old->id == map->id && !map->mirror_external && map->log != nullptr &&
                      old->version <= map->version && map->version - old->version <= (uint64_t)(BL_DIRTY_LOG - 64) &&
                      (map->frame.width & 15) == 0 && n >= ((size_t)1 << 20);
     if (inc) {
@@ -3404,7 +3351,7 @@ int bl_snapshot_enqueue(bl_ctx* main, const bl_grid* map, bl_grid* snap, const v
         if (blocks < 1) blocks = 1;
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(k_planner_snapshot, dim3(blocks), dim3(256), 0, main->stream, map->cells, snap->cells, n,
-                           (const bl_pose_xyt_t*)d_pose, snap_pose, done_count, flag, seq);
+                           (const bl_pose_xyt_t*)d_pose, snap_pose);
     }
     BL_HIP(hipGetLastError());
     rc = bl_timer_end(main, BL_K_SNAPSHOT, f0, f1);
@@ -3420,7 +3367,7 @@ extern "C" int bl_planner_submit(bl_planner* p, const bl_grid* map, const void* 
     bl_planner_snap sn;
     int rc = bl_planner_reserve(p, map, &sn);
     if (rc) return rc;
-    rc = bl_snapshot_enqueue(p->main, map, sn.grid, d_start_pose, sn.pose, sn.done_count, sn.flag, sn.seq);
+    rc = bl_snapshot_enqueue(p->main, map, sn.grid, d_start_pose, sn.pose);
     if (rc) return rc;
     return bl_planner_commit(p, goal, params);
 }
@@ -3531,49 +3478,43 @@ extern "C" int bl_plan_path_to_frontier(bl_ctx* ctx, const bl_frontiers* frontie
     const float cpx = frontiers->xy[2 * (size_t)mid], cpy = frontiers->xy[2 * (size_t)mid + 1];
 
     std::map<long long, frontier_search> cache;                         // goal cell -> planPath result
-    struct cand { float x, y; int cx, cy; bool valid; int ring; };
+    struct cand { float x, y; int cx, cy; bool valid; };
     std::vector<cand> cands;
     std::vector<int32_t> q;
     std::vector<float> qv;
 
-    // check_valid (:87-102), first half, for the candidates cands[from..): isValidGoal by one gather of the goal cells' distances.
-    // Returns the number of goal cells among them that no search has been run for yet (they are entered into `todo`).
+    // check_valid (:87-102), first half, for the candidates of a ring: isValidGoal by one gather of the goal cells' distances.
+    // The goal cells among them that no search has been run for yet are entered into `todo`.
     std::vector<int2> todo;
     std::vector<long long> todo_key;
-    auto validity = [&](size_t from, int* fresh) -> int {
-        const int n = (int)(cands.size() - from);
-        *fresh = 0;
+    auto validity = [&]() -> int {
+        const int n = (int)cands.size();
         if (n == 0) return BL_OK;
         q.resize(2 * (size_t)n); qv.resize((size_t)n);
         for (int i = 0; i < n; ++i) {
-            cand& c = cands[from + (size_t)i];
+            cand& c = cands[(size_t)i];
             bl_global_to_cell((double)c.x, (double)c.y, frame, &c.cx, &c.cy);    // motion_planner.cpp:61
             q[2 * (size_t)i] = c.cx; q[2 * (size_t)i + 1] = c.cy;
         }
         int rc = bl_dist_gather(dist, q.data(), n, qv.data());
         if (rc) return rc;
         for (int i = 0; i < n; ++i) {
-            cand& c = cands[from + (size_t)i];
+            cand& c = cands[(size_t)i];
             c.valid = mp_is_valid_goal(pl, c.x, c.y, qv[i]);
             if (!c.valid) continue;
             const long long key = ((long long)c.cy << 32) | (unsigned int)c.cx;
-            if (cache.find(key) == cache.end()) { cache[key] = frontier_search(); todo.push_back(make_int2(c.cx, c.cy)); todo_key.push_back(key); *fresh += 1; }
+            if (cache.find(key) == cache.end()) { cache[key] = frontier_search(); todo.push_back(make_int2(c.cx, c.cy)); todo_key.push_back(key); }
         }
         return BL_OK;
     };
-    // ... second half, for every candidate gathered so far: planPath (one batch of searches, one per goal cell not searched yet)
+    // ... second half, for the same candidates: planPath (one batch of searches, one per goal cell not searched yet)
     // and isPathSafe (one gather over all path poses)
     auto evaluate = [&]() -> int {
         const int n = (int)cands.size();
         int rc = BL_OK;
         if (!todo.empty()) {
-            static const bool trace = getenv("BOTLAB_PLAN_TRACE") != nullptr;
-            const auto w0 = std::chrono::steady_clock::now();
-            long long max_pops = 0, sum_pops = 0; int n_found = 0;
             rc = astar_batch_cells(ctx, dist, &robotPose, todo.data(), (int)todo.size(), &pl.search,
-                                   [&](int i, bool found, const int32_t* pc, int len, long long po, long long pu) {
-                                       if (po > max_pops) max_pops = po;
-                                       sum_pops += po; n_found += found ? 1 : 0;
+                                   [&](int i, bool, const int32_t* pc, int len, long long po, long long pu) {
                                        frontier_search& fs = cache[todo_key[i]];
                                        fs.path.resize((size_t)1 + len);
                                        astar_cells_to_path(frame, robotPose, pc, len, fs.path.data(), 1 + len);
@@ -3581,9 +3522,6 @@ extern "C" int bl_plan_path_to_frontier(bl_ctx* ctx, const bl_frontiers* frontie
                                        pops += po; pushes += pu; searches += 1;
                                    });
             if (rc) return rc;
-            if (trace)
-                fprintf(stderr, "[plan] batch of %d searches: %d found, %lld pops in all, longest %lld, %.1f ms\n", (int)todo.size(), n_found, sum_pops,
-                        max_pops, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count());
             todo.clear(); todo_key.clear();
         }
         // isPathSafe (motion_planner.cpp:77-96) of every candidate path with >= 3 poses: one gather for all poses
@@ -3615,68 +3553,43 @@ extern "C" int bl_plan_path_to_frontier(bl_ctx* ctx, const bl_frontiers* frontie
     };
 
     // The sweep of :143-199 takes one ring of the expanding square after the other and stops at the first ring that holds a valid
-    // candidate.  The rings are independent of each other, so several CAN be evaluated ahead of the rule (BOTLAB_FRONTIER_SPECULATE=n:
-    // rings are gathered until they ask for n goal cells not searched yet, their searches run side by side as one batch, and the
-    // rule is then applied ring by ring, in the reference's order, to the same outcome).  Off by default (n = 1: one ring per
-    // batch, the reference's own sequence), because it does not pay: a plan's searches already arrive as ONE batch (the first ring
-    // with goals of enough clearance), whose length is its longest search (5.4e5 pops, 1.4 s on the cut arena), while the rings
-    // behind hold goals that are expensive or unreachable (68 searches, 1.0e7 pops, 8.7 s with n = 64 there).
+    // candidate: one ring per batch of searches, the reference's own sequence.
     bool foundPose = false;
     float square_radius = .025;
     float sq_len = .025;
     bl_pose_xyt_t goal_pose; memset(&goal_pose, 0, sizeof(goal_pose));    // D1
     int wraps = 0;
-    static const int speculate = getenv("BOTLAB_FRONTIER_SPECULATE") ? atoi(getenv("BOTLAB_FRONTIER_SPECULATE")) : 1;
     while (!foundPose) {
-        // ---- gather rings ahead (the radius sequence of :194-197, the D8 cut after the second wrap included)
         cands.clear();
-        struct ring_info { size_t begin, end; bool wraps_here; };
-        std::vector<ring_info> rings;
-        float r_spec = square_radius;
-        int wraps_spec = wraps, pending = (int)todo.size();
-        while (true) {
-            const float top_height = cpy + r_spec;
-            const float bot_height = cpy - r_spec;
-            const float left_bound = cpy + r_spec;          // sic: built from the y coordinate (:176-177)
-            const float right_bound = cpy - r_spec;
-            const size_t begin = cands.size();
-            const int ring = (int)rings.size();
-            for (float i = -r_spec; i <= r_spec; i += sq_len) {
-                cands.push_back(cand{cpx + i, top_height, 0, 0, false, ring});
-                cands.push_back(cand{cpx + i, bot_height, 0, 0, false, ring});
-            }
-            for (float i = -r_spec; i <= r_spec; i += sq_len) {
-                cands.push_back(cand{right_bound, cpy + i, 0, 0, false, ring});
-                cands.push_back(cand{left_bound, cpy + i, 0, 0, false, ring});
-            }
-            int fresh = 0;
-            int rc = validity(begin, &fresh);
-            if (rc) return rc;
-            pending += fresh;
-            bool wrap = false, last = false;
-            if (r_spec < 0.5) r_spec += sq_len;
-            else { r_spec = 0.05; wrap = true; if (++wraps_spec == 2) last = true; }     // (D8: the sweep ends there if nothing was found)
-            rings.push_back(ring_info{begin, cands.size(), wrap});
-            if (last || pending >= speculate || speculate <= 1) break;
+        const float top_height = cpy + square_radius;
+        const float bot_height = cpy - square_radius;
+        const float left_bound = cpy + square_radius;       // sic: built from the y coordinate (:176-177)
+        const float right_bound = cpy - square_radius;
+        for (float i = -square_radius; i <= square_radius; i += sq_len) {
+            cands.push_back(cand{cpx + i, top_height, 0, 0, false});
+            cands.push_back(cand{cpx + i, bot_height, 0, 0, false});
         }
-        int rc = evaluate();
+        for (float i = -square_radius; i <= square_radius; i += sq_len) {
+            cands.push_back(cand{right_bound, cpy + i, 0, 0, false});
+            cands.push_back(cand{left_bound, cpy + i, 0, 0, false});
+        }
+        int rc = validity();
         if (rc) return rc;
-        // ---- the rule, ring by ring: first of each pair if valid, else the second (:153-193); then the radius update (:194-197)
-        for (const ring_info& rg : rings) {
-            for (size_t i = rg.begin; i + 1 < rg.end; i += 2) {
-                if (cands[i].valid) { foundPose = true; goal_pose.x = cands[i].x; goal_pose.y = cands[i].y; }
-                else if (cands[i + 1].valid) { foundPose = true; goal_pose.x = cands[i + 1].x; goal_pose.y = cands[i + 1].y; }
+        rc = evaluate();
+        if (rc) return rc;
+        // ---- the rule: first of each pair if valid, else the second (:153-193); then the radius update (:194-197)
+        for (size_t i = 0; i + 1 < cands.size(); i += 2) {
+            if (cands[i].valid) { foundPose = true; goal_pose.x = cands[i].x; goal_pose.y = cands[i].y; }
+            else if (cands[i + 1].valid) { foundPose = true; goal_pose.x = cands[i + 1].x; goal_pose.y = cands[i + 1].y; }
+        }
+        if (square_radius < 0.5) square_radius += sq_len;
+        else {
+            square_radius = 0.05;
+            if (++wraps == 2 && !foundPose) {                                    // D8: the sweep ends there if nothing was found
+                if (stats) { stats[0] = pops; stats[1] = pushes; stats[2] = searches; }
+                *out_len = 1;
+                return BL_OK;
             }
-            if (square_radius < 0.5) square_radius += sq_len;
-            else {
-                square_radius = 0.05;
-                if (++wraps == 2 && !foundPose) {                                    // D8
-                    if (stats) { stats[0] = pops; stats[1] = pushes; stats[2] = searches; }
-                    *out_len = 1;
-                    return BL_OK;
-                }
-            }
-            if (foundPose) break;
         }
     }
     goal_pose.theta = robotPose.theta;                                           // :209

@@ -37,7 +37,7 @@ def _frame(shape):
 def _sweep_kernel_is(fr, k):
     """which kernels grew the frontiers (bl_frontiers_debug_sweep_kernel) -- checked only when no switch forces another form"""
     import os
-    if not any(v in os.environ for v in ("BOTLAB_FRONTIER_GROW_V1", "BOTLAB_FRONTIER_ONE_WG_SWEEP")):
+    if "BOTLAB_FRONTIER_GROW_V1" not in os.environ:
         assert fr.sweep_kernel() == k, (fr.sweep_kernel(), k)
 
 
@@ -201,6 +201,32 @@ def test_find_map_frontiers_a_grid_width_that_crowded_the_lds_set(oracle, gpu_ct
     fr = bl.find_map_frontiers(grid, bl.make_pose(rx, ry, 0.0), 0.1)
     assert len(exp) == 1 and len(exp[0]) == 1800
     _sweep_kernel_is(fr, 3)
+    _same_frontiers(fr.cells(), exp)
+
+
+@pytest.mark.parametrize("shape", [(8, 16384), (16384, 8)])
+def test_find_map_frontiers_a_side_beyond_the_lds_flood(oracle, gpu_ctx, shape):
+    """k_frontier_flood packs a cell's coordinates into 14 bits each: a grid with a side above 16 380 cells floods through
+    k_frontiers<false> instead, and only such a grid does.  131 072 cells (the multi-launch form), unknown but for a free corridor four
+    cells wide along the long side with an unknown rim all round; three occupied bars close three of its four lanes each, so the flood
+    bends.  The robot stands in the corridor at mid-length.  Same list as the oracle's."""
+    H, W = shape
+    long_side = max(H, W)
+    c = np.zeros((8, long_side), np.int8)                  # laid out along x; transposed below for the tall grid
+    c[2:6, 2:long_side - 2] = -50
+    c[2:5, long_side // 2 + 300] = 60
+    c[3:6, long_side // 2 - 700] = 60
+    c[2:5, 1000] = 60
+    cells = np.ascontiguousarray(c if W > H else c.T)
+    assert cells.shape == shape
+    origin, mpc = _frame(shape)
+    grid = bl.OccupancyGrid.from_cells(cells, origin, mpc, cellsPerMeter=helpers.CPM_DEFAULT, ctx=gpu_ctx)
+    cx, cy = (long_side // 2, 4) if W > H else (4, long_side // 2)
+    assert cells[cy, cx] == -50
+    rx, ry = float(origin[0]) + (cx + 0.5) * 0.05, float(origin[1]) + (cy + 0.5) * 0.05
+    exp = oracle.find_frontiers(cells, mpc, helpers.CPM_DEFAULT, origin, oracle.pose(rx, ry, 0.0), 0.1)
+    fr = bl.find_map_frontiers(grid, bl.make_pose(rx, ry, 0.0), 0.1)
+    assert len(exp) >= 1
     _same_frontiers(fr.cells(), exp)
 
 
