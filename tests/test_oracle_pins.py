@@ -242,3 +242,90 @@ def test_mapping_counts_then_clamp_closed_form(oracle, maps):
             assert np.array_equal(before, grid)          # first call changes nothing (mapping.cpp:74-76,88-90)
         pose_prev = pose
     assert (grid == 127).any() and (grid == -128).any()
+
+
+# ------------------------------------------------------------------ the map kernel's closed form of the Bresenham variant
+def _reference_walks(x1, y1):
+    """Mapping::bresenham (mapping.cpp:101-127) from (0, 0) to every (x1[i], y1[i]), all walks stepped together: (xs, ys, count), the
+    cells of walk i in xs[i, :count[i]], ys[i, :count[i]] (start included, end excluded)."""
+    n = len(x1)
+    dx, dy = np.abs(x1), np.abs(y1)
+    sx, sy = np.where(0 < x1, 1, -1), np.where(0 < y1, 1, -1)
+    err = dx - dy
+    x, y = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    cap = int((dx + dy).max()) + 2
+    xs, ys = np.zeros((n, cap), np.int64), np.zeros((n, cap), np.int64)
+    count = np.zeros(n, np.int64)
+    rows = np.arange(n)
+    for _ in range(cap):
+        act = (x != x1) | (y != y1)
+        if not act.any():
+            break
+        xs[rows[act], count[act]] = x[act]; ys[rows[act], count[act]] = y[act]
+        count += act
+        e2 = 2 * err
+        a, b = act & (e2 >= -dy), act & (e2 <= dx)
+        err = err - np.where(a, dy, 0) + np.where(b, dx, 0)
+        x, y = x + np.where(a, sx, 0), y + np.where(b, sy, 0)
+    assert not ((x != x1) | (y != y1)).any()
+    return xs, ys, count
+
+
+def _segment_walks(x1, y1, seg):
+    """k_map_update's walk of the same rays, every segment started on its own from the closed form (num, n, rem) and stepped cell by cell
+    as the kernel steps it: the arithmetic of bl_mapping.hip's phase C, for all rays and all segment starts at once."""
+    n = len(x1)
+    dx, dy = np.abs(x1), np.abs(y1)
+    sx, sy = np.where(0 < x1, 1, -1), np.where(0 < y1, 1, -1)
+    K = np.maximum(dx, dy)
+    xmajor = dx >= dy
+    dmaj, dmin = np.where(xmajor, dx, dy), np.where(xmajor, dy, dx)
+    nseg = (int(K.max()) + seg - 1) // seg
+    k0 = (np.arange(nseg, dtype=np.int64) * seg)[None, :].repeat(n, axis=0)
+    k1 = np.minimum(K[:, None], k0 + seg)
+    den = np.maximum(2 * dmaj, 1)[:, None]                       # (a ray with K = 0 has no segment)
+    num = 2 * k0 * dmin[:, None] + dmaj[:, None]
+    m = num // den
+    rem = num - m * den
+    xs, ys = np.zeros((n, nseg * seg), np.int64), np.zeros((n, nseg * seg), np.int64)
+    for j in range(seg):
+        k = k0 + j
+        x = np.where(xmajor[:, None], sx[:, None] * k, sx[:, None] * m)
+        y = np.where(xmajor[:, None], sy[:, None] * m, sy[:, None] * k)
+        live = k < k1
+        xs[:, j::seg] = np.where(live, x, 0); ys[:, j::seg] = np.where(live, y, 0)
+        rem = rem + 2 * dmin[:, None]
+        carry = rem >= den
+        rem, m = rem - np.where(carry, den, 0), m + carry
+    return xs, ys, K
+
+
+def _assert_segments_equal_reference(x1, y1, seg):
+    rx, ry, count = _reference_walks(x1, y1)
+    gx, gy, K = _segment_walks(x1, y1, seg)
+    assert np.array_equal(count, K)                              # the walk visits max(dx, dy) cells
+    w = min(rx.shape[1], gx.shape[1])
+    live = np.arange(w)[None, :] < K[:, None]
+    assert np.array_equal(np.where(live, rx[:, :w], 0), np.where(live, gx[:, :w], 0))
+    assert np.array_equal(np.where(live, ry[:, :w], 0), np.where(live, gy[:, :w], 0))
+
+
+def test_bresenham_segment_closed_form():
+    """The map kernel cuts a ray's walk into segments of MAP_SEG = 16 cells and starts each from a closed form.  Every segment of every
+    ray equals the reference's loop: exhaustively for dx, dy <= 64, and for 20000 seeded pairs up to 2000, in all sign combinations."""
+    import mapping_cases as mc
+    assert mc.SEG == 16
+    v = np.arange(-64, 65, dtype=np.int64)
+    x1, y1 = [a.ravel() for a in np.meshgrid(v, v)]
+    _assert_segments_equal_reference(x1, y1, mc.SEG)
+    # the scalar transcription the case builder uses is the same arithmetic
+    for x, y in [(0, 0), (1, 0), (0, -1), (16, 16), (-17, 16), (33, -1), (-48, -47), (5, 64), (-64, 31), (49, 24)]:
+        want = mc.walk(3, -2, 3 + x, -2 + y)
+        got = [c for k0 in range(0, max(abs(x), abs(y)), mc.SEG) for c in mc.segment_cells(3, -2, 3 + x, -2 + y, k0)]
+        assert got == want, (x, y)
+    rng = np.random.default_rng(20000)
+    big = rng.integers(0, 2001, (20000, 2)) * rng.choice([-1, 1], (20000, 2))
+    big[:40] = [(s * a, t * b) for a, b in [(2000, 0), (2000, 1), (2000, 1999), (2000, 2000), (1999, 1000), (1, 2000), (0, 2000), (1000, 2000),
+                                             (1601, 800), (2000, 1000)] for s in (1, -1) for t in (1, -1)]
+    for lo in range(0, len(big), 2000):
+        _assert_segments_equal_reference(big[lo:lo + 2000, 0].astype(np.int64), big[lo:lo + 2000, 1].astype(np.int64), mc.SEG)
