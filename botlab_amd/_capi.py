@@ -121,7 +121,13 @@ class RBSlamResult(C.Structure):
                 ("S", C.c_uint64), ("Q_lo", C.c_uint64), ("Q_hi", C.c_uint64)]
 
 
-assert C.sizeof(RBSlamResult) == 64
+class RBSlamMatchParams(C.Structure):
+    """bl_rbslam_match_params_t: the window of the per-particle scan match of the Rao-Blackwellized SLAM (24 bytes)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("ntheta", C.c_int32), ("dtheta", C.c_float), ("max_range", C.c_float),
+                ("min_score", C.c_int32)]
+
+
+assert C.sizeof(RBSlamResult) == 64 and C.sizeof(RBSlamMatchParams) == 24
 assert C.sizeof(ScanMatchParams) == 28 and C.sizeof(ScanMatchResult) == 56
 assert C.sizeof(ScanMatchWideParams) == 32 and C.sizeof(ScanMatchWideStats) == 40
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
@@ -305,6 +311,9 @@ SIGNATURES = {
     "bl_rbslam_map_upload": (C.c_int, [_vp, C.c_int, _vp]),
     "bl_rbslam_best_map": (C.c_int, [_vp, _vp]),
     "bl_rbslam_debug_last": (C.c_int, [_vp, _vp, _vp]),
+    "bl_rbslam_set_scan_matching": (C.c_int, [_vp, _P(RBSlamMatchParams)]),
+    "bl_rbslam_debug_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bl_rbslam_debug_match_path": (C.c_int, [_vp]),
     "bl_lcm_fingerprint": (C.c_uint64, [C.c_int]),
     "bl_lcm_encode_pose": (C.c_int64, [C.c_int, _P(Pose), _vp, C.c_int64]),
     "bl_lcm_encode_lidar": (C.c_int64, [_P(Lidar), _vp, _vp, C.c_int64]),

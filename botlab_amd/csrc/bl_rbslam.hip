@@ -9,6 +9,7 @@
 //   k_rb_weigh   ActionModel::applyAction and SensorModel::likelihood of every particle against its own map: a wave per particle,
 //                the rays across its lanes, the <= 3 cells of scoreRay gathered from the particle's map through L2
 //   k_rb_reduce  one workgroup: units, S, Q and the best particle
+//   (k_rb_match  only with scan matching on, and then k_rb_weigh in its form without the action: bl_rbslam_match.h)
 //   k_rb_map     Mapping::updateMap of all P maps: a workgroup per (particle, window tile), hit and miss counts of the tile in an
 //                LDS window of uint16 counters, one owner thread per cell
 // The sensor model's and the mapper's arithmetic is restated here from bl_mcl.hip / bl_mapping.hip with bl_math.h's bit-exact pieces.
@@ -62,6 +63,13 @@ struct bl_rbslam {
     double rot1, trans, rot2;
     uint64_t noise_seed; uint32_t step;
     bool initialized, map_latched;
+    // scan matching (step 3b, bl_rbslam_match.h); the buffers exist once it has been switched on
+    bool match_on, match_done;
+    bl_rbslam_match_params_t match;
+    float* match_rays;                       // ranges[RBM_MAX_RAYS] | thetas[RBM_MAX_RAYS]: the valid rays of the scan
+    float* h_match_rays;                     // pinned, the same layout
+    int32_t* match_out;                      // 7 x P
+    int match_path;
 };
 
 // ---------------------------------------------------------------- device helpers
@@ -324,13 +332,9 @@ __device__ __forceinline__ int rb_score_ray(const int8_t* __restrict__ cells, co
     return odds > 0 ? 2 * odds : (o1 > 0 ? o1 : (o2 > 0 ? o2 : 0));
 }
 
-__global__ __launch_bounds__(RB_WEIGH_THREADS) void k_rb_weigh(rb_weigh_args a)
+// ActionModel::applyAction (action_model.cpp:78-103) of particle m from its source pose s
+__device__ __forceinline__ void rb_action(const rb_weigh_args& a, int m, const float4 s, float* px, float* py, float* pth)
 {
-    const int lane = threadIdx.x & 63;
-    const int m = blockIdx.x * (RB_WEIGH_THREADS / 64) + (threadIdx.x >> 6);
-    if (m >= a.P) return;                                       // whole waves; no barrier below
-    const float4 s = a.src[a.idx[m]];
-    // ---- ActionModel::applyAction (action_model.cpp:78-103), the same in every lane of the wave
     float n1, n2, n3;
     if (a.noise) { n1 = a.noise[3 * m]; n2 = a.noise[3 * m + 1]; n3 = a.noise[3 * m + 2]; }
     else {
@@ -343,10 +347,30 @@ __global__ __launch_bounds__(RB_WEIGH_THREADS) void k_rb_weigh(rb_weigh_args a)
     const float head = s.z + n1;
     double hs, hc;
     sincos((double)head, &hs, &hc);
-    const float px = (float)((double)s.x + (double)n2 * hc);
-    const float py = (float)((double)s.y + (double)n2 * hs);
-    const float pth = bl_wrap_to_pi(s.z + n1 + n3);
-    if (lane == 0) { a.dst[m] = make_float4(px, py, pth, 0.0f); a.parent[m] = make_float4(s.x, s.y, s.z, 0.0f); }
+    *px = (float)((double)s.x + (double)n2 * hc);
+    *py = (float)((double)s.y + (double)n2 * hs);
+    *pth = bl_wrap_to_pi(s.z + n1 + n3);
+}
+
+// ACTION: step 3 and step 4 of particle m in one wave (the form every update without scan matching launches).  !ACTION: step 4
+// alone, on the pose and parent pose that k_rb_match (bl_rbslam_match.h) has left in dst and parent.
+template <bool ACTION>
+__device__ __forceinline__ void rb_weigh_wave(const rb_weigh_args& a)
+{
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * (RB_WEIGH_THREADS / 64) + (threadIdx.x >> 6);
+    if (m >= a.P) return;                                       // whole waves; no barrier below
+    float4 s;
+    float px, py, pth;
+    if (ACTION) {
+        s = a.src[a.idx[m]];
+        rb_action(a, m, s, &px, &py, &pth);                     // the same in every lane of the wave
+        if (lane == 0) { a.dst[m] = make_float4(px, py, pth, 0.0f); a.parent[m] = make_float4(s.x, s.y, s.z, 0.0f); }
+    } else {
+        s = a.parent[m];
+        const float4 d = a.dst[m];
+        px = d.x; py = d.y; pth = d.z;
+    }
     // ---- SensorModel::likelihood (sensor_model.cpp:14-25) over MovingLaserScan(scan, parent_pose, pose), against the particle's own map
     const int8_t* cells = a.maps + (size_t)a.slot[m] * a.stride;
     const bl_pose3 pb = {s.x, s.y, s.z}, pe = {px, py, pth};
@@ -368,6 +392,11 @@ __global__ __launch_bounds__(RB_WEIGH_THREADS) void k_rb_weigh(rb_weigh_args a)
         a.units[m] = c > 0 ? (unsigned long long)c * 1000ull : 2ull;
     }
 }
+
+__global__ __launch_bounds__(RB_WEIGH_THREADS) void k_rb_weigh(rb_weigh_args a) { rb_weigh_wave<true>(a); }
+__global__ __launch_bounds__(RB_WEIGH_THREADS) void k_rb_weigh_matched(rb_weigh_args a) { rb_weigh_wave<false>(a); }
+
+#include "bl_rbslam_match.h"
 
 // ---------------------------------------------------------------- units -> S, Q, best
 __global__ __launch_bounds__(RB_PLAN_THREADS) void k_rb_reduce(int P, const unsigned long long* __restrict__ units, const float4* __restrict__ pose,
@@ -634,9 +663,10 @@ static int rb_launch_reduce(bl_rbslam* rb, int weighed)
 static void rb_free(bl_rbslam* rb)
 {
     void* d[] = {rb->maps, rb->staging, rb->pose[0], rb->pose[1], rb->parent, rb->cum, rb->units, rb->like, rb->idx, rb->slot, rb->copies,
-                 rb->d_noise, rb->state, rb->d_export};
+                 rb->d_noise, rb->state, rb->d_export, rb->match_rays, rb->match_out};
     for (void* q : d) if (q) (void)hipFree(q);
     if (rb->h_state) (void)hipHostFree(rb->h_state);
+    if (rb->h_match_rays) (void)hipHostFree(rb->h_match_rays);
     delete rb;
 }
 
@@ -663,6 +693,7 @@ extern "C" int bl_rbslam_create(bl_ctx* ctx, int num_particles, int width, int h
     rb->stride = stride;
     rb->max_laser = max_laser_distance; rb->hit = hit_odds; rb->miss = miss_odds;
     rb->num = 1; rb->den = 2;
+    rb->match_path = -1;
     const size_t P = (size_t)num_particles;
     hipError_t e = hipMalloc((void**)&rb->maps, stride * P);
     if (e == hipSuccess) e = hipMalloc((void**)&rb->staging, stride);
@@ -707,6 +738,43 @@ extern "C" int bl_rbslam_set_noise_seed(bl_rbslam* rb, uint64_t seed)
     return BL_OK;
 }
 
+extern "C" int bl_rbslam_set_scan_matching(bl_rbslam* rb, const bl_rbslam_match_params_t* params)
+{
+    BL_CHECK_ARG(rb != nullptr);
+    if (!params) { rb->match_on = false; return BL_OK; }
+    BL_CHECK_ARG(params->nx >= 0 && params->nx <= BL_RBSLAM_MATCH_MAX_N && params->ny >= 0 && params->ny <= BL_RBSLAM_MATCH_MAX_N);
+    BL_CHECK_ARG(params->ntheta >= 0 && params->ntheta <= BL_RBSLAM_MATCH_MAX_NTHETA);
+    BL_CHECK_ARG(params->dtheta > 0.0f);                         // false for NaN
+    if (!rb->match_rays) {
+        BL_HIP(hipSetDevice(rb->ctx->device));
+        BL_HIP(hipMalloc((void**)&rb->match_rays, 2 * RBM_MAX_RAYS * sizeof(float)));
+        BL_HIP(hipHostMalloc((void**)&rb->h_match_rays, 2 * RBM_MAX_RAYS * sizeof(float), hipHostMallocDefault));
+        BL_HIP(hipMalloc((void**)&rb->match_out, 7 * (size_t)rb->P * sizeof(int32_t)));
+    }
+    rb->match = *params;
+    rb->match_on = true;
+    return BL_OK;
+}
+
+extern "C" int bl_rbslam_debug_match(bl_rbslam* rb, int32_t* di, int32_t* dj, int32_t* dk, int32_t* score, int32_t* score_centre,
+                                     int32_t* ties, int32_t* accepted)
+{
+    BL_CHECK_ARG(rb != nullptr);
+    if (!rb->match_done) { bl_set_error("bl_rbslam_debug_match: no moved update with scan matching on so far"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(rb->ctx->device));
+    int32_t* dst[7] = {di, dj, dk, score, score_centre, ties, accepted};
+    const size_t P = (size_t)rb->P;
+    for (int k = 0; k < 7; ++k)
+        if (dst[k]) BL_HIP(hipMemcpyAsync(dst[k], rb->match_out + k * P, P * sizeof(int32_t), hipMemcpyDeviceToHost, rb->ctx->stream));
+    BL_HIP(hipStreamSynchronize(rb->ctx->stream));
+    return BL_OK;
+}
+
+extern "C" int bl_rbslam_debug_match_path(const bl_rbslam* rb)
+{
+    return rb ? rb->match_path : -1;
+}
+
 static void rb_reset_run(bl_rbslam* rb, int64_t pose_utime, int64_t parent_utime)
 {
     rb->cur = 0;
@@ -715,6 +783,7 @@ static void rb_reset_run(bl_rbslam* rb, int64_t pose_utime, int64_t parent_utime
     rb->rot1 = rb->trans = rb->rot2 = 0;
     rb->step = 0;
     rb->map_latched = false;
+    rb->match_done = false; rb->match_path = -1;
     rb->initialized = true;
 }
 
@@ -799,6 +868,43 @@ static bool rb_action_update(bl_rbslam* rb, const bl_pose_xyt_t& odometry)
     return moved;
 }
 
+// step 3b: the action and the match of every particle against its own map, one launch (bl_rbslam_match.h)
+static int rb_launch_match(bl_rbslam* rb, const rb_weigh_args& wa, int rays, float reach_m)
+{
+    hipStream_t st = rb->ctx->stream;
+    const bl_rbslam_match_params_t& mp = rb->match;
+    if (rays > 0) {                                              // the pinned block is free: the previous update has synchronised
+        BL_HIP(hipMemcpyAsync(rb->match_rays, rb->h_match_rays, (size_t)rays * sizeof(float), hipMemcpyHostToDevice, st));
+        BL_HIP(hipMemcpyAsync(rb->match_rays + RBM_MAX_RAYS, rb->h_match_rays + RBM_MAX_RAYS, (size_t)rays * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    rb_match_args q;
+    q.rays = rays; q.ranges = rb->match_rays; q.thetas = rb->match_rays + RBM_MAX_RAYS;
+    q.nx = mp.nx; q.ny = mp.ny; q.ntheta = mp.ntheta; q.dtheta = mp.dtheta; q.min_score = mp.min_score;
+    // half window: reach + n + 1 cells (botlab_hip.h); the bound of the window decides the path for the whole launch
+    const float reach_c = ceilf(reach_m * rb->frame.cpm);
+    const bool whole = !(reach_c < (float)(RBM_WHOLE - 64));      // also NaN
+    q.hx = whole ? RBM_WHOLE : (int)reach_c + mp.nx + 1;
+    q.hy = whole ? RBM_WHOLE : (int)reach_c + mp.ny + 1;
+    long long bw = 2ll * q.hx + 1 + 3, bh = 2ll * q.hy + 1;       // + 3: the first column steps down to a multiple of four
+    if (bw > rb->frame.width) bw = rb->frame.width;
+    if (bh > rb->frame.height) bh = rb->frame.height;
+    const long long win_bytes = ((bw + 3) & ~3ll) * bh;
+    const bool staged = win_bytes <= (long long)RBM_WINDOW_BYTES;
+    q.ends_bytes = (int)(((size_t)(rays > 0 ? rays : 1) * sizeof(int2) + 15) & ~(size_t)15);
+    q.out = rb->match_out;
+    const size_t lds = (size_t)q.ends_bytes + (staged ? (size_t)(win_bytes > 16 ? win_bytes : 16) : (size_t)16);   // never empty: a masked-out lookup reads byte 0
+    if (staged) {
+        BL_DYN_LDS_ONCE_PER_DEVICE(k_rb_match<true>, RBM_WINDOW_BYTES + RBM_MAX_RAYS * sizeof(int2), rb->ctx);
+        hipLaunchKernelGGL(k_rb_match<true>, dim3(rb->P), dim3(RBM_THREADS), lds, st, wa, q);
+    } else {
+        hipLaunchKernelGGL(k_rb_match<false>, dim3(rb->P), dim3(RBM_THREADS), lds, st, wa, q);
+    }
+    BL_HIP(hipGetLastError());
+    rb->match_path = staged ? 0 : 1;
+    rb->match_done = true;
+    return BL_OK;
+}
+
 extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, const bl_lidar_t* scan, int rand_value, const float* noise,
                                 bl_rbslam_result_t* result)
 {
@@ -811,6 +917,21 @@ extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, co
     int R = 0;
     int rc = bl_scan_upload(ctx, scan, &R);
     if (rc) return rc;
+    // scan matching: the valid rays, packed for the copy; too many are refused before the ActionModel latches the odometry
+    int match_rays = 0; float match_reach = 0;
+    if (rb->match_on) {
+        int valid = 0;
+        for (int i = 0; i < scan->num_ranges; ++i) valid += (scan->ranges[i] > RBM_MIN_RANGE && scan->ranges[i] < rb->match.max_range) ? 1 : 0;
+        BL_CHECK_ARG(valid <= RBM_MAX_RAYS);
+        for (int i = 0; i < scan->num_ranges; ++i) {
+            const float r = scan->ranges[i];
+            if (r > RBM_MIN_RANGE && r < rb->match.max_range) {
+                rb->h_match_rays[match_rays] = r; rb->h_match_rays[RBM_MAX_RAYS + match_rays] = scan->thetas[i];
+                ++match_rays;
+                if (r > match_reach) match_reach = r;
+            }
+        }
+    }
     const bool moved = rb_action_update(rb, *odometry);
     const int P = rb->P;
     if (moved) {
@@ -843,7 +964,13 @@ extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, co
         wa.rot1 = rb->rot1; wa.trans = rb->trans; wa.rot2 = rb->rot2; wa.rot1Std = 0.05; wa.transStd = 0.005; wa.rot2Std = 0.05;
         wa.seed_lo = (uint32_t)rb->noise_seed; wa.seed_hi = (uint32_t)(rb->noise_seed >> 32); wa.step = rb->step;
         wa.cum = rb->cum; wa.units = rb->units; wa.like = rb->like;
-        hipLaunchKernelGGL(k_rb_weigh, dim3((P + RB_WEIGH_THREADS / 64 - 1) / (RB_WEIGH_THREADS / 64)), dim3(RB_WEIGH_THREADS), 0, st, wa);
+        if (!rb->match_on) {
+            hipLaunchKernelGGL(k_rb_weigh, dim3((P + RB_WEIGH_THREADS / 64 - 1) / (RB_WEIGH_THREADS / 64)), dim3(RB_WEIGH_THREADS), 0, st, wa);
+        } else {
+            rc = rb_launch_match(rb, wa, match_rays, match_reach);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_rb_weigh_matched, dim3((P + RB_WEIGH_THREADS / 64 - 1) / (RB_WEIGH_THREADS / 64)), dim3(RB_WEIGH_THREADS), 0, st, wa);
+        }
         BL_HIP(hipGetLastError());
         rb->cur ^= 1;
         rb->parent_utime = rb->pose_utime;

@@ -981,6 +981,26 @@ class RBSlam:
         check(self.ctx.lib.bl_rbslam_debug_last(self.h, idx.ctypes.data, like.ctypes.data))
         return idx, like
 
+    MATCH_FIELDS = ("di", "dj", "dk", "score", "score_centre", "ties", "accepted")
+
+    def setScanMatching(self, nx=2, ny=2, ntheta=4, dtheta=math.radians(0.5), max_range=8.0, min_score=0):
+        """Scan-matched proposals: after the action of a moved update every particle matches the scan against its own map in the
+        window +-nx, +-ny cells, +-ntheta steps of dtheta around its pose and moves to the best pose there.  setScanMatching(None): off."""
+        if nx is None:
+            check(self.ctx.lib.bl_rbslam_set_scan_matching(self.h, None))
+            return
+        p = _capi.RBSlamMatchParams(int(nx), int(ny), int(ntheta), float(dtheta), float(max_range), int(min_score))
+        check(self.ctx.lib.bl_rbslam_set_scan_matching(self.h, C.byref(p)))
+
+    def debugMatch(self):
+        """dict of int32 arrays (di, dj, dk, score, score_centre, ties, accepted) of the last moved update with matching on."""
+        out = [np.empty(self.P, np.int32) for _ in self.MATCH_FIELDS]
+        check(self.ctx.lib.bl_rbslam_debug_match(self.h, *[a.ctypes.data for a in out]))
+        return dict(zip(self.MATCH_FIELDS, out))
+
+    def debugMatchPath(self):
+        return int(self.ctx.lib.bl_rbslam_debug_match_path(self.h))
+
     def close(self):
         if self.h:
             self.ctx.lib.bl_rbslam_destroy(self.h)

@@ -32,6 +32,16 @@ public:
     // resampling is due when den * (sum u)^2 <= num * P * sum u^2: 1 / 1 on every moved update, the default 1 / 2 at N_eff <= P / 2
     void setResampling(uint32_t num, uint32_t den) { check(bl_rbslam_set_resampling(h_, num, den), "bl_rbslam_set_resampling"); }
     void setNoiseSeed(uint64_t seed) { check(bl_rbslam_set_noise_seed(h_, seed), "bl_rbslam_set_noise_seed"); }
+    // scan-matched proposals (GMapping's structure): after the action of a moved update every particle matches the scan against its own
+    // map in the window +-nx, +-ny cells, +-ntheta steps of dtheta around its pose and moves to the best pose there, if that scores at
+    // least minScore.  Off by default.
+    void setScanMatching(int nx = 2, int ny = 2, int ntheta = 4, float dtheta = 0.00872664626f, float maxRange = 8.0f, int minScore = 0)
+    {
+        bl_rbslam_match_params_t p;
+        p.nx = nx; p.ny = ny; p.ntheta = ntheta; p.dtheta = dtheta; p.max_range = maxRange; p.min_score = minScore;
+        check(bl_rbslam_set_scan_matching(h_, &p), "bl_rbslam_set_scan_matching");
+    }
+    void clearScanMatching() { check(bl_rbslam_set_scan_matching(h_, nullptr), "bl_rbslam_set_scan_matching"); }
     void initializeAtPose(const Pose& pose, uint64_t seed = 0)
     {
         const bl_pose_xyt_t p = pose_in(pose);

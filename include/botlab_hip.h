@@ -816,6 +816,46 @@ int bl_rbslam_best_map(bl_rbslam* rb, bl_grid* dst);
 /* of the last moved update: the source of every particle (m itself when it did not resample) and h_p; either may be NULL */
 int bl_rbslam_debug_last(bl_rbslam* rb, int32_t* resample_idx, int32_t* likelihood_half_units);
 
+/* ---- scan-matched proposals (GMapping's structure; off by default).  With matching on, a MOVED update gains a step between the
+ * action and the weighing:
+ *   3b. For every particle p, "correlative scan matching" above, word for word, with map = p's OWN map and centre c = p's pose as
+ *       step 3 left it: valid rays 0.15f < range < max_range (at most BL_RBSLAM_MATCH_MAX_RAYS of them: more is BL_ERR_ARG, refused
+ *       before the ActionModel latches the odometry, so the object is as before the call), theta_k = c.theta + (float)dk * dtheta,
+ *       scoreRay's endpoint cells, score(di, dj, dk) = sum of max(0, L_p[ey + dj][ex + di]) with 0 outside the grid, the best
+ *       candidate by the 64-bit key (score, then smallest di*di + dj*dj, |dk|, dk, dj, di).  The scan is taken as rigid at the pose:
+ *       the rays' time stamps play no part in the match.
+ *       If score >= min_score and (di, dj, dk) != (0, 0, 0), p's pose becomes x = (float)((double)c.x + di * (double)meters_per_cell),
+ *       y likewise with dj, theta = wrap_to_pi(theta_dk); otherwise it stays bit for bit as it was.  The centre wins every tie it is
+ *       part of, so an empty or all-free map moves nobody.  The utime and the parent pose are untouched.
+ *   Steps 4-6 run on the new pose: the weighing and the map update interpolate from the parent pose to the matched pose.
+ * A not-moved update matches nothing; a window of 0, 0, 0 leaves every output of the update equal to matching off.
+ * One launch for all particles, a workgroup each, stream-ordered like the rest.  The map cells a particle's candidates can reach lie in
+ * the window  centre cell +- (reach + n + 1)  per axis (n = nx or ny; centre cell = the truncated grid position of c), clipped to the
+ * grid, reach = ceilf(longest valid range * cells_per_meter) in float.  Path 0: the positive part of that window is staged in LDS;
+ * path 1: the map is read directly.  The path is one for the whole launch and decided on the host from the bound of the window:
+ *   bw = min(2 * (reach + nx + 1) + 1 + 3, width), bh = min(2 * (reach + ny + 1) + 1, height);
+ *   path 0 iff ((bw + 3) & ~3) * bh <= BL_RBSLAM_MATCH_WINDOW_BYTES.
+ * (+ 3: with width % 4 == 0 the window's first column steps down to a multiple of four.  8 m at 5 cm with n = 8: 344 * 339 bytes.) */
+#define BL_RBSLAM_MATCH_MAX_N 8
+#define BL_RBSLAM_MATCH_MAX_NTHETA 16
+#define BL_RBSLAM_MATCH_MAX_RAYS 4096
+#define BL_RBSLAM_MATCH_WINDOW_BYTES (120 * 1024)
+typedef struct bl_rbslam_match_params_t {
+    int32_t nx, ny;          /* half window in cells, 0 .. BL_RBSLAM_MATCH_MAX_N                                      */
+    int32_t ntheta;          /* half window in heading steps, 0 .. BL_RBSLAM_MATCH_MAX_NTHETA                         */
+    float   dtheta;          /* heading step in radians, > 0                                                          */
+    float   max_range;       /* rays with range >= max_range are skipped                                              */
+    int32_t min_score;       /* a best score below this leaves the pose where the action put it: accepted = 0         */
+} bl_rbslam_match_params_t;  /* 24 bytes */
+/* NULL: off (the default).  BL_ERR_ARG: a limit exceeded, dtheta <= 0 or NaN; the previous setting then stays in force. */
+int bl_rbslam_set_scan_matching(bl_rbslam* rb, const bl_rbslam_match_params_t* params);
+/* of the last moved update with matching on since bl_rbslam_init_at_pose, P entries each, any may be NULL: the best candidate, its
+ * score, the score of (0, 0, 0), the candidates sharing the best score, score >= min_score.  BL_ERR_STATE if there was none. */
+int bl_rbslam_debug_match(bl_rbslam* rb, int32_t* di, int32_t* dj, int32_t* dk, int32_t* score, int32_t* score_centre,
+                          int32_t* ties, int32_t* accepted);
+/* which path the last matched update took: 0 the map window staged in LDS, 1 the map read directly; -1 before the first */
+int bl_rbslam_debug_match_path(const bl_rbslam* rb);
+
 /* ------------------------------------------------------------------ the exploration step, asynchronously  (src/planning/exploration.cpp:277-369)
  * Exploration::executeExploringMap on every published map: planner_.setMap, find_map_frontiers, and -- when the robot is within
  * 0.5 m of currentTarget_ or has none -- plan_path_to_frontier; then the status / next-state rule (:332-368; D10).  A submission
