@@ -391,7 +391,9 @@ static int nav_params_ok(const bl_navfield_params_t* p)
 extern "C" int bl_navfield_compute(bl_navfield* nf, const bl_dist* dist, const bl_navfield_params_t* params, const int32_t* goal_xy_cells,
                                    int n_goals)
 {
-    BL_CHECK_ARG(nf != nullptr && dist != nullptr && n_goals >= 0 && (n_goals == 0 || goal_xy_cells != nullptr));
+    BL_CHECK_ARG(nf != nullptr);
+    nf->valid = false;                                               // a compute that is refused leaves no field: the last one answers for other arguments
+    BL_CHECK_ARG(dist != nullptr && n_goals >= 0 && (n_goals == 0 || goal_xy_cells != nullptr));
     int rc = nav_params_ok(params);
     if (rc) return rc;
     bl_ctx* ctx = nf->ctx;
@@ -406,7 +408,6 @@ extern "C" int bl_navfield_compute(bl_navfield* nf, const bl_dist* dist, const b
         return BL_ERR_ARG;
     }
     BL_HIP(hipSetDevice(ctx->device));
-    nf->valid = false;
     const nav_geom g = {W, H, (W + NAV_TILE - 1) / NAV_TILE, (H + NAV_TILE - 1) / NAV_TILE};
     const size_t ntiles = (size_t)g.TX * g.TY;
     if (n > nf->capacity) {

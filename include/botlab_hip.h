@@ -664,7 +664,8 @@ int bl_plan_path_to_frontier(bl_ctx* ctx, const bl_frontiers* frontiers, const b
  *     (step + field(c')); 0xFFFFFFFF (UNREACHED) where c is not traversable or not connected to the goal set.  This is the minimum
  *     over paths of the step costs plus the penalties of the path's cells outside the goal set; steps cost at least 10, so the
  *     solution is unique and does not depend on the order it is computed in.  width * height * (14 + obstacle_gain) > 2^32 - 2 is
- *     refused (BL_ERR_ARG): no cost can wrap.
+ *     refused (BL_ERR_ARG): no cost can wrap.  A compute that returns an error leaves the handle without a field (the readers
+ *     return BL_ERR_STATE), whatever it held before.
  *   Path from a start pose: the start cell is global_position_to_grid_cell of the pose, as the search finds it.  out[0] is the start
  *     pose as given.  From cell c the path takes the allowed move minimising step + field(c'), ties by the order (+x), (-x), (+y),
  *     (-y), (+x+y), (-x+y), (+x-y), (-x-y), until it stands on the goal set.  Pose k >= 1: x, y as bl_astar_search writes a path cell
