@@ -115,6 +115,31 @@ class ViewGainParams(C.Structure):
 assert C.sizeof(ViewGainParams) == 20
 
 
+class LocalPlanState(C.Structure):
+    """bl_localplan_state_t: a pose and the velocities the robot has now (32 bytes)."""
+    _fields_ = [("pose", Pose), ("v", C.c_float), ("w", C.c_float)]
+
+
+class LocalPlanParams(C.Structure):
+    """bl_localplan_params_t: limits, candidate counts, horizon and the four weights of the local planner (56 bytes)."""
+    _fields_ = [("v_min", C.c_float), ("v_max", C.c_float), ("w_max", C.c_float), ("acc_v", C.c_float), ("acc_w", C.c_float),
+                ("dt_control", C.c_float), ("dt_sim", C.c_float), ("n_v", C.c_int32), ("n_w", C.c_int32), ("n_steps", C.c_int32),
+                ("w_field", C.c_int32), ("w_heading", C.c_int32), ("w_clear", C.c_int32), ("w_speed", C.c_int32)]
+
+
+class LocalPlanResult(C.Structure):
+    """bl_localplan_result_t: the command of one state (32 bytes)."""
+    _fields_ = [("trans_v", C.c_float), ("angular_v", C.c_float), ("index", C.c_int32), ("n_admissible", C.c_int32), ("cost", C.c_int64),
+                ("flags", C.c_int32), ("pad", C.c_int32)]
+
+    def __repr__(self):
+        return (f"LocalPlanResult(trans_v={self.trans_v!r}, angular_v={self.angular_v!r}, index={self.index}, n_admissible={self.n_admissible}, "
+                f"cost={self.cost}, flags={self.flags})")
+
+
+assert C.sizeof(LocalPlanState) == 32 and C.sizeof(LocalPlanParams) == 56 and C.sizeof(LocalPlanResult) == 32
+
+
 class RBSlamResult(C.Structure):
     """bl_rbslam_result_t: what one update of the Rao-Blackwellized SLAM hands back (64 bytes)."""
     _fields_ = [("moved", C.c_int32), ("resampled", C.c_int32), ("best", C.c_int32), ("pad", C.c_int32), ("best_pose", Pose),
@@ -292,6 +317,15 @@ SIGNATURES = {
     "bl_navfield_device_ptr": (_vp, [_vp]),
     "bl_navfield_tables": (C.c_int, [_vp, _vp, _vp, _P(C.c_int)]),
     "bl_navfield_stats": (C.c_int, [_vp, _vp]),
+    "bl_localplan_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_localplan_destroy": (None, [_vp]),
+    "bl_localplan_set_params": (C.c_int, [_vp, _P(LocalPlanParams)]),
+    "bl_localplan_commands": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "bl_localplan_debug_costs": (C.c_int, [_vp, _vp, _P(LocalPlanState), _vp]),
+    "bl_localplan_debug_rollout": (C.c_int, [_vp, _vp, _P(LocalPlanState), C.c_int, _vp]),
+    "bl_localplan_tables": (C.c_int, [_vp, _P(LocalPlanState), _vp, _vp]),
+    "bl_localplan_debug_path": (C.c_int, [_vp]),
+    "bl_localplan_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
     "bl_viewgain_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_viewgain_destroy": (None, [_vp]),
     "bl_viewgain_set_params": (C.c_int, [_vp, _P(ViewGainParams)]),

@@ -21,8 +21,8 @@
 #include <string.h>
 
 #include "bl_internal.h"
+#include "bl_navfield_dev.h"                // the handle, nav_cost, nav_pose_cell, the moves and nav_descent_move
 
-#define NAV_UNREACHED 0xFFFFFFFFu
 #define NAV_TILE 32                    // cells a side: one thread per cell, 1024 threads
 #define NAV_HALO (NAV_TILE + 2)
 #define NAV_RELAX_GRID 1024            // workgroups of a round; each walks the list with this stride
@@ -42,39 +42,7 @@
 
 struct nav_geom { int W, H, TX, TY; };
 
-struct bl_navfield {
-    bl_ctx* ctx;
-    size_t capacity;                   // cells allocated
-    uint32_t* field;
-    unsigned int* tile_flag;           // per tile: the last round it was listed for
-    unsigned int* lists;               // 3 x tiles
-    size_t tiles_cap;
-    int32_t* table; int table_cap;     // device: per L1 distance, -1 not traversable, else the penalty
-    unsigned int* state;               // device NST_WORDS
-    unsigned int* h_state;             // pinned copy
-    int32_t* goals; int goals_cap;     // device x, y pairs
-    bl_frame frame; bool valid;
-    const uint16_t* l1;                // the distance grid the field was computed from (for the descent's corner rule)
-    const bl_dist* dist;
-    bl_navfield_params_t params;
-    int n_goals;
-    std::vector<uint8_t>* h_trav; std::vector<int32_t>* h_pen;
-    int64_t stats[5];
-    // paths / gather scratch
-    void* q_dev; size_t q_cap; void* q_host; size_t q_host_cap;
-    void* o_dev; size_t o_cap;
-};
-
 // ---------------------------------------------------------------------------------------------------------------- kernels
-__device__ __forceinline__ int nav_cost(const uint16_t* __restrict__ l1, const int32_t* __restrict__ table, int table_n, int W, int H,
-                                        int x, int y)
-{
-    if (x < 0 || y < 0 || x >= W || y >= H) return -1;
-    const int n = l1[(size_t)y * W + x];
-    if (n == 0xFFFF || n >= table_n) return -1;
-    return table[n];
-}
-
 __global__ __launch_bounds__(256) void k_nav_init(uint32_t* __restrict__ field, const uint16_t* __restrict__ l1,
                                                   const int32_t* __restrict__ table, int table_n, size_t n, unsigned int* state)
 {
@@ -129,10 +97,6 @@ __global__ __launch_bounds__(256) void k_nav_goals(uint32_t* __restrict__ field,
             }
     }
 }
-
-// the moves in the order of the definition: (+x), (-x), (+y), (-y), (+x+y), (-x+y), (+x-y), (-x-y)
-__device__ __constant__ int NAV_DX[8] = {1, -1, 0, 0, 1, -1, 1, -1};
-__device__ __constant__ int NAV_DY[8] = {0, 0, 1, -1, 1, 1, -1, -1};
 
 __global__ __launch_bounds__(NAV_TILE * NAV_TILE) void k_nav_relax(uint32_t* __restrict__ field, const uint16_t* __restrict__ l1,
                                                                    const int32_t* __restrict__ table, int table_n, nav_geom g,
@@ -252,15 +216,6 @@ struct nav_path_args {
     float theta[8];                    // atan2f(dy, dx) of the eight moves, from the host's libm
 };
 
-// the cell of a pose as the search finds it (global_position_to_grid_cell: a truncating cast), false when it is off the grid
-__device__ __forceinline__ bool nav_pose_cell(const bl_frame& f, float gx, float gy, int* cx, int* cy)
-{
-    const double vx = ((double)gx - (double)f.ox) * (double)f.cpm, vy = ((double)gy - (double)f.oy) * (double)f.cpm;
-    if (!(vx > -1.0 && vx < (double)f.width && vy > -1.0 && vy < (double)f.height)) return false;     // NaN: off the grid
-    *cx = (int)vx; *cy = (int)vy;
-    return true;
-}
-
 __global__ __launch_bounds__(64) void k_nav_paths(nav_path_args a)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -279,21 +234,8 @@ __global__ __launch_bounds__(64) void k_nav_paths(nav_path_args a)
     if (on && f != NAV_UNREACHED) {
         const long long max_steps = (long long)W * H;
         for (long long step = 0; f != 0 && step < max_steps; ++step) {
-            const bool px = nav_cost(a.l1, a.table, a.table_n, W, H, cx + 1, cy) >= 0, mx = nav_cost(a.l1, a.table, a.table_n, W, H, cx - 1, cy) >= 0;
-            const bool py = nav_cost(a.l1, a.table, a.table_n, W, H, cx, cy + 1) >= 0, my = nav_cost(a.l1, a.table, a.table_n, W, H, cx, cy - 1) >= 0;
-            uint32_t best = NAV_UNREACHED, best_f = 0;
-            int bm = -1;
-            for (int m = 0; m < 8; ++m) {
-                const int dx = NAV_DX[m], dy = NAV_DY[m];
-                bool ok;
-                if (m < 4) ok = m == 0 ? px : m == 1 ? mx : m == 2 ? py : my;
-                else ok = (dx > 0 ? px : mx) && (dy > 0 ? py : my) && nav_cost(a.l1, a.table, a.table_n, W, H, cx + dx, cy + dy) >= 0;
-                if (!ok) continue;
-                const uint32_t v = a.field[(size_t)(cy + dy) * W + cx + dx];
-                if (v == NAV_UNREACHED) continue;
-                const uint32_t w = v + (m < 4 ? 10u : 14u);
-                if (w < best) { best = w; best_f = v; bm = m; }       // ties: the first move in the fixed order
-            }
+            uint32_t best_f = 0;
+            const int bm = nav_descent_move(a.field, a.l1, a.table, a.table_n, W, H, cx, cy, &best_f);
             if (bm < 0 || best_f >= f) break;                         // cannot happen on a field at its fixed point
             cx += NAV_DX[bm]; cy += NAV_DY[bm]; f = best_f;
             if (len < a.cap) {

@@ -797,6 +797,91 @@ class NavigationField:
             self.h = None
 
 
+LOCALPLAN_REACHED, LOCALPLAN_OFF_FIELD, LOCALPLAN_BLOCKED = 1, 2, 4
+LOCALPLAN_RESULT_DTYPE = np.dtype([("trans_v", "<f4"), ("angular_v", "<f4"), ("index", "<i4"), ("n_admissible", "<i4"), ("cost", "<i8"),
+                                   ("flags", "<i4"), ("pad", "<i4")])
+assert LOCALPLAN_RESULT_DTYPE.itemsize == 32
+
+
+class LocalPlanner:
+    """The local planner (bl_localplan_*, include/botlab_hip.h): the velocity command of the next control period, by rollout of every
+    reachable (v, w) pair over a computed NavigationField.  A state is (pose, v, w): a Pose and the velocities the robot has now."""
+
+    def __init__(self, ctx=None, **params):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_localplan_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        self.params = None
+        if params:
+            self.set_params(**params)
+
+    def set_params(self, v_min, v_max, w_max, acc_v, acc_w, dt_control, dt_sim, n_v, n_w, n_steps, w_field=1, w_heading=0, w_clear=0,
+                   w_speed=0):
+        p = _capi.LocalPlanParams(v_min, v_max, w_max, acc_v, acc_w, dt_control, dt_sim, int(n_v), int(n_w), int(n_steps), int(w_field),
+                                  int(w_heading), int(w_clear), int(w_speed))
+        check(self.ctx.lib.bl_localplan_set_params(self.h, C.byref(p)))
+        self.params = p
+
+    @staticmethod
+    def _state(s):
+        pose, v, w = s
+        return _capi.LocalPlanState(pose, float(np.float32(v)), float(np.float32(w)))
+
+    def _counts(self):
+        if self.params is None:                              # the library's own refusal, with its message
+            check(self.ctx.lib.bl_localplan_tables(self.h, C.byref(_capi.LocalPlanState()), None, None))
+        return self.params.n_v, self.params.n_w, self.params.n_steps
+
+    def commands(self, field, states):
+        """One result per state, as a LOCALPLAN_RESULT_DTYPE array; all states in one launch sequence."""
+        n = len(states)
+        s = (_capi.LocalPlanState * max(n, 1))(*[self._state(q) for q in states])
+        out = np.zeros(max(n, 1), dtype=LOCALPLAN_RESULT_DTYPE)
+        check(self.ctx.lib.bl_localplan_commands(self.h, field.h, s, n, out.ctypes.data))
+        return out[:n]
+
+    def command(self, field, pose, v, w):
+        """(trans_v, angular_v, flags) for one state: what a motion controller publishes as mbot_motor_command_t."""
+        r = self.commands(field, [(pose, v, w)])[0]
+        return float(r["trans_v"]), float(r["angular_v"]), int(r["flags"])
+
+    def costs(self, field, state):
+        """int64 [n_w, n_v]: the cost of every candidate of one state, INT64_MAX where it is inadmissible."""
+        n_v, n_w, _ = self._counts()
+        out = np.zeros((n_w, n_v), dtype=np.int64)
+        check(self.ctx.lib.bl_localplan_debug_costs(self.h, field.h, C.byref(self._state(state)), out.ctypes.data))
+        return out
+
+    def rollout(self, field, state, c):
+        """The n_steps poses of candidate c of one state, as a POSE_DTYPE array."""
+        _, _, n_steps = self._counts()
+        out = np.zeros(n_steps, dtype=POSE_DTYPE)
+        check(self.ctx.lib.bl_localplan_debug_rollout(self.h, field.h, C.byref(self._state(state)), int(c), out.ctypes.data))
+        return out
+
+    def tables(self, state):
+        """(v_i, w_j): the candidate tables of one state."""
+        n_v, n_w, _ = self._counts()
+        v, w = np.zeros(n_v, np.float32), np.zeros(n_w, np.float32)
+        check(self.ctx.lib.bl_localplan_tables(self.h, C.byref(self._state(state)), v.ctypes.data, w.ctypes.data))
+        return v, w
+
+    def debugPath(self):
+        """0: the last launch staged the window in LDS; 1: it read the grids directly; -1 before the first."""
+        return self.ctx.lib.bl_localplan_debug_path(self.h)
+
+    def lastDeviceMs(self):
+        ms = C.c_float()
+        check(self.ctx.lib.bl_localplan_last_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_localplan_destroy(self.h)
+            self.h = None
+
+
 def nav_min_traversable_cells(distances, searchParams):
     """n_min: the smallest L1 distance (in cells) that is traversable under searchParams -- f[n] > minDistanceToObstacle * 1.000001
     with the distance grid's own table f[n] = f[n - 1] + 0.1f; None if no distance of this grid is."""

@@ -889,6 +889,89 @@ int bl_explorer_pending(const bl_explorer* e);
 int bl_explorer_fetch(bl_explorer* e, bl_explore_result_t* out, bl_pose_xyt_t* out_path, int cap);   /* out_path: currentPath_, up to cap poses */
 int bl_explorer_frontiers(const bl_explorer* e, bl_frontiers** out);                     /* frontiers_ of the last fetched step (caller destroys) */
 
+/* ------------------------------------------------------------------ local planner (no reference counterpart for the algorithm)
+ * The velocity command of the next control period, by rollout over a navigation field: of the (v, w) pairs a robot can reach within
+ * dt_control, the one whose simulated arc ends lowest on the field without touching a cell that is not traversable.  The reference
+ * ends in src/mbot/motion_controller.cpp, a rotate-translate-rotate waypoint follower that never looks at the map; the command has
+ * the shape of its lcmtypes/mbot_motor_command_t.lcm {utime, trans_v, angular_v}.
+ *   Inputs: a computed bl_navfield -- its uint32 field, traversable(n) and penalty(n) of its last compute, n(c) and the frame of its
+ *     bl_dist --, n states {pose, v, w} (the velocities the robot has now) and the parameters below.
+ *   Candidate tables, per state, on the host in double, narrowed to float once:
+ *     v_lo = max(v_min, v - acc_v * dt_control), v_hi = min(v_max, v + acc_v * dt_control); if v_lo > v_hi both become v clamped to
+ *     [v_min, v_max].  v_i = v_lo + (v_hi - v_lo) * i / (n_v - 1), evaluated left to right; n_v == 1: v_0 = v_hi.  The same for w_j
+ *     with the limits -w_max and w_max, acc_w and n_w.  Candidate c = j * n_v + i.
+ *   Rollout of candidate (i, j), float arithmetic, one rounding per operation: (x, y) of the pose, theta = wrap_to_pi(pose.theta),
+ *     s = v_i * dt_sim, dth = w_j * dt_sim.  For k = 1 .. n_steps: (cs, sn) = cosf, sinf of theta (glibc's, bit for bit: bl_math.h);
+ *     x = x + s * cs; y = y + s * sn; theta = wrap_to_pi(theta + dth); the visited cell is global_position_to_grid_cell of (x, y),
+ *     inside the grid by the test bl_navfield_paths applies to a start pose.
+ *   Admissible: every visited cell is inside the grid and traversable, and the last one, e, has field(e) != UNREACHED.  Then, in int64,
+ *     cost = w_field * field(e) + w_heading * h + w_clear * (sum over k of penalty(n(cell_k))) + w_speed * (n_v - 1 - i)
+ *     h = 0 when field(e) == 0; otherwise with d the move bl_navfield_paths would take from e (same allowed moves, same tie order) and
+ *     a_d its angle as a float constant ((float) of 0, pi, pi/2, -pi/2, pi/4, 3 pi/4, -pi/4, -3 pi/4 in double),
+ *     h = (int32)floorf(fabsf((float)angle_diff((double)theta_end, (double)a_d)) * (float)(1024 / pi)); 1024 when e has no allowed move
+ *     to a reached cell.
+ *   Result per state: the admissible candidate with the least key (cost, c) -- ties to the lowest c --: trans_v = v_i, angular_v = w_j,
+ *     index = c, cost, n_admissible.  Flags, each with the command (0, 0) and index -1:
+ *       REACHED    the pose's own cell has field 0; nothing is rolled out; cost 0, n_admissible 0
+ *       OFF_FIELD  the pose is off the grid, on a cell that is not traversable, or on an UNREACHED cell; cost INT64_MAX, n_admissible 0
+ *       BLOCKED    no candidate is admissible; cost INT64_MAX
+ *     The minimum is over exact integer keys: the result does not depend on the launch shape.
+ *   Refused with BL_ERR_ARG: by bl_localplan_set_params a non-finite value, v_min > v_max, w_max < 0, dt_control <= 0, dt_sim <= 0, a
+ *     count or a weight outside its range; by the calls that see the field (double)max(|v_min|, |v_max|) * (double)dt_sim >
+ *     (double)meters_per_cell -- a step may never skip a cell -- and a state with a non-finite member.
+ * How it is computed (bl_localplan.hip): a workgroup takes one state and a run of consecutive j.  The headings theta_k of a (state, j)
+ * do not depend on i: they are formed once, their (cos, sin) once per (j, k) into LDS, and the n_v speeds of that j read them back as
+ * broadcasts.  A rollout moves at most ceil(max|v| * dt_sim * n_steps * cells_per_meter) cells from the pose per axis; the costs
+ * (-1, or the penalty) of the window of that reach around the pose's cell are staged in LDS when it is small enough:
+ *   R = (int)ceil((double)max(|v_min|, |v_max|) * (double)dt_sim * n_steps * (double)cells_per_meter) + 2;
+ *   path 0 (staged) iff (2 R + 1) * (2 R + 1) * 2 <= BL_LOCALPLAN_WINDOW_BYTES, path 1 (the grids read through L2) otherwise.
+ * A cell outside the window is read from the grids on either path, so the rule decides speed only.  Per workgroup the least key,
+ * a second kernel takes the least of those per state.  bl_localplan_commands is one launch sequence for all states, stream-ordered
+ * on the ctx stream, with one synchronisation, at the return. */
+#define BL_LOCALPLAN_WINDOW_BYTES (48 * 1024)
+#define BL_LOCALPLAN_MAX_NV 64
+#define BL_LOCALPLAN_MAX_NW 1025
+#define BL_LOCALPLAN_MAX_STEPS 255
+#define BL_LOCALPLAN_MAX_WEIGHT 65535
+#define BL_LOCALPLAN_REACHED 1
+#define BL_LOCALPLAN_OFF_FIELD 2
+#define BL_LOCALPLAN_BLOCKED 4
+typedef struct bl_localplan_state_t {
+    bl_pose_xyt_t pose;
+    float v, w;                        /* the velocities the robot has now */
+} bl_localplan_state_t;                /* 32 bytes */
+typedef struct bl_localplan_params_t {
+    float v_min, v_max;                /* m/s; v_min < 0 allows reversing */
+    float w_max;                       /* rad/s, >= 0 */
+    float acc_v, acc_w;                /* m/s^2, rad/s^2 */
+    float dt_control, dt_sim;          /* s, > 0: the control period and the integration step */
+    int32_t n_v, n_w, n_steps;         /* 1 .. 64, 1 .. 1025, 1 .. 255 */
+    int32_t w_field, w_heading, w_clear, w_speed;   /* 0 .. 65535 each */
+} bl_localplan_params_t;               /* 56 bytes */
+typedef struct bl_localplan_result_t {
+    float trans_v, angular_v;          /* mbot_motor_command_t's two */
+    int32_t index;                     /* c of the winner, -1 with any flag */
+    int32_t n_admissible;
+    int64_t cost;
+    int32_t flags, pad;
+} bl_localplan_result_t;               /* 32 bytes */
+typedef struct bl_localplan bl_localplan;
+int bl_localplan_create(bl_ctx* ctx, bl_localplan** out);             /* buffers grow on demand */
+void bl_localplan_destroy(bl_localplan* lp);
+int bl_localplan_set_params(bl_localplan* lp, const bl_localplan_params_t* params);   /* refused: the handle keeps what it had */
+/* BL_ERR_STATE before set_params and for a field handle without a field; n == 0 is fine */
+int bl_localplan_commands(bl_localplan* lp, bl_navfield* nf, const bl_localplan_state_t* states, int n, bl_localplan_result_t* results);
+/* the n_v * n_w costs of one state's candidates, INT64_MAX for an inadmissible one, rolled out whatever the state's flags would be */
+int bl_localplan_debug_costs(bl_localplan* lp, bl_navfield* nf, const bl_localplan_state_t* state, int64_t* out);
+/* the n_steps poses (x, y, theta after step k; utime the state's) of candidate c, visited cells admissible or not */
+int bl_localplan_debug_rollout(bl_localplan* lp, bl_navfield* nf, const bl_localplan_state_t* state, int c, bl_pose_xyt_t* out);
+/* the candidate tables of one state: n_v and n_w floats (either may be NULL); host arithmetic only */
+int bl_localplan_tables(bl_localplan* lp, const bl_localplan_state_t* state, float* v, float* w);
+/* which path the last launch took: 0 the window staged in LDS, 1 the grids read directly; -1 before the first */
+int bl_localplan_debug_path(const bl_localplan* lp);
+/* device time of the last bl_localplan_commands' kernels (HIP events around the launches); BL_ERR_STATE before the first */
+int bl_localplan_last_device_ms(const bl_localplan* lp, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
