@@ -304,8 +304,10 @@ static void lp_tables_of(const bl_localplan_params_t& p, const bl_localplan_stat
 
 static int lp_state_ok(const bl_localplan_state_t* s, int n)
 {
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         BL_CHECK_ARG(isfinite(s[i].pose.x) && isfinite(s[i].pose.y) && isfinite(s[i].pose.theta) && isfinite(s[i].v) && isfinite(s[i].w));
+        BL_CHECK_ARG(!(fabsf(s[i].pose.theta) > BL_LOCALPLAN_MAX_THETA));             // every accepted heading wraps within bl_wrap_to_pi's guard
+    }
     return BL_OK;
 }
 

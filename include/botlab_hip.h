@@ -918,7 +918,9 @@ int bl_explorer_frontiers(const bl_explorer* e, bl_frontiers** out);            
  *     The minimum is over exact integer keys: the result does not depend on the launch shape.
  *   Refused with BL_ERR_ARG: by bl_localplan_set_params a non-finite value, v_min > v_max, w_max < 0, dt_control <= 0, dt_sim <= 0, a
  *     count or a weight outside its range; by the calls that see the field (double)max(|v_min|, |v_max|) * (double)dt_sim >
- *     (double)meters_per_cell -- a step may never skip a cell -- and a state with a non-finite member.
+ *     (double)meters_per_cell -- a step may never skip a cell --, a state with a non-finite member and a state whose
+ *     fabsf(pose.theta) > BL_LOCALPLAN_MAX_THETA: 65536 rad is 10 432 steps of wrap_to_pi (each rounded to float), below the 2^16 steps after which bl_math.h
+ *     cuts that loop, so every accepted heading wraps exactly as the reference's loop would.
  * How it is computed (bl_localplan.hip): a workgroup takes one state and a run of consecutive j.  The headings theta_k of a (state, j)
  * do not depend on i: they are formed once, their (cos, sin) once per (j, k) into LDS, and the n_v speeds of that j read them back as
  * broadcasts.  A rollout moves at most ceil(max|v| * dt_sim * n_steps * cells_per_meter) cells from the pose per axis; the costs
@@ -933,6 +935,7 @@ int bl_explorer_frontiers(const bl_explorer* e, bl_frontiers** out);            
 #define BL_LOCALPLAN_MAX_NW 1025
 #define BL_LOCALPLAN_MAX_STEPS 255
 #define BL_LOCALPLAN_MAX_WEIGHT 65535
+#define BL_LOCALPLAN_MAX_THETA 65536.0f
 #define BL_LOCALPLAN_REACHED 1
 #define BL_LOCALPLAN_OFF_FIELD 2
 #define BL_LOCALPLAN_BLOCKED 4

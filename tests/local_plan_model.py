@@ -22,6 +22,7 @@ F32 = np.float32
 REACHED, OFF_FIELD, BLOCKED = 1, 2, 4
 COST_NONE = 2 ** 63 - 1
 MAX_NV, MAX_NW, MAX_STEPS, MAX_WEIGHT = 64, 1025, 255, 65535
+MAX_THETA = F32(65536.0)                                     # BL_LOCALPLAN_MAX_THETA: 10 432 wrap steps, below bl_wrap_to_pi's cut at 2^16
 WINDOW_BYTES = 48 * 1024
 # the angle of each move of nm.MOVES, a double narrowed to float
 MOVE_ANGLE = [F32(a) for a in (0.0, math.pi, math.pi / 2, -math.pi / 2, math.pi / 4, 3 * math.pi / 4, -math.pi / 4, -3 * math.pi / 4)]
@@ -114,6 +115,13 @@ class World:
         return REACHED if int(self.field[c[1], c[0]]) == 0 else 0
 
 
+def state_ok(pose, v, w):
+    """lp_state_ok's rule: every member finite, and |theta| <= MAX_THETA (in float)."""
+    if not all(math.isfinite(float(F32(f))) for f in (pose[0], pose[1], pose[2], v, w)):
+        return False
+    return not abs(F32(pose[2])) > MAX_THETA
+
+
 def headings(theta, w_j, dt_sim, n_steps):
     """theta_0 .. theta_n: the heading each step integrates with, and the one the rollout ends on."""
     th = wrap_to_pi(F32(theta))
@@ -159,7 +167,10 @@ def heading_term(world, e, theta_end):
 def costs(world, p, pose, v, w, stats=None):
     """int64 [n_w * n_v] costs of a state's candidates, COST_NONE for an inadmissible one (whatever the state's flags would be).
     stats, a dict, counts what the rollouts met: 'left' / 'right' / 'bottom' / 'top' exits of the grid, 'blocked' cells, 'unreached'
-    ends, 'wrapped' candidates whose heading stepped through +-pi."""
+    ends, 'wrapped' candidates whose heading stepped through +-pi, 'strip' steps on the grid at x < origin x or y < origin y (the
+    (-1, 0) strip that the truncating cast gives to cell 0), 'strip_candidates' admissible candidates with such a step, and under
+    'terms' {c: (field(e), h, sum of penalties)} of every admissible candidate."""
+    assert state_ok(pose, v, w)
     vt, wt = tables(p, v, w)
     out = np.full(p.n_w * p.n_v, COST_NONE, dtype=np.int64)
     ox, oy, cpm = float(F32(world.origin[0])), float(F32(world.origin[1])), float(world.cpm)
@@ -171,7 +182,7 @@ def costs(world, p, pose, v, w, stats=None):
         for i in range(p.n_v):
             s = F32(vt[i] * p.dt_sim)
             x, y = F32(pose[0]), F32(pose[1])
-            pen, e, ok = 0, None, True
+            pen, e, ok, in_strip = 0, None, True, 0
             for k in range(p.n_steps):
                 x = F32(x + F32(s * cs_sn[k][0]))
                 y = F32(y + F32(s * cs_sn[k][1]))
@@ -189,6 +200,9 @@ def costs(world, p, pose, v, w, stats=None):
                         stats["blocked"] = stats.get("blocked", 0) + 1
                     break
                 pen += int(world.pcell[e[1], e[0]])
+                if stats is not None and (float(x) < ox or float(y) < oy):
+                    stats["strip"] = stats.get("strip", 0) + 1
+                    in_strip += 1
             if not ok:
                 continue
             fe = int(world.field[e[1], e[0]])
@@ -196,13 +210,18 @@ def costs(world, p, pose, v, w, stats=None):
                 if stats is not None:
                     stats["unreached"] = stats.get("unreached", 0) + 1
                 continue
+            if stats is not None and in_strip:
+                stats["strip_candidates"] = stats.get("strip_candidates", 0) + 1
             h = heading_term(world, e, ths[-1])
+            if stats is not None:
+                stats.setdefault("terms", {})[j * p.n_v + i] = (fe, h, pen)
             out[j * p.n_v + i] = p.w_field * fe + p.w_heading * h + p.w_clear * pen + p.w_speed * (p.n_v - 1 - i)
     return out
 
 
 def command(world, p, pose, v, w, stats=None):
     """The result of one state as a RESULT record, and the costs (None when nothing was rolled out)."""
+    assert state_ok(pose, v, w)
     r = np.zeros((), RESULT)
     r["index"], r["cost"] = -1, COST_NONE
     flags = world.start_flags(pose[0], pose[1])
