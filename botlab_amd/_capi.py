@@ -140,6 +140,14 @@ class LocalPlanResult(C.Structure):
 assert C.sizeof(LocalPlanState) == 32 and C.sizeof(LocalPlanParams) == 56 and C.sizeof(LocalPlanResult) == 32
 
 
+class ShortcutParams(C.Structure):
+    """bl_shortcut_params_t: clearance, longest span and the price of a waypoint of the path shortcutting (16 bytes)."""
+    _fields_ = [("clearance", C.c_double), ("max_span", C.c_int32), ("waypoint_cost", C.c_int32)]
+
+
+assert C.sizeof(ShortcutParams) == 16
+
+
 class RBSlamResult(C.Structure):
     """bl_rbslam_result_t: what one update of the Rao-Blackwellized SLAM hands back (64 bytes)."""
     _fields_ = [("moved", C.c_int32), ("resampled", C.c_int32), ("best", C.c_int32), ("pad", C.c_int32), ("best_pose", Pose),
@@ -326,6 +334,14 @@ SIGNATURES = {
     "bl_localplan_tables": (C.c_int, [_vp, _P(LocalPlanState), _vp, _vp]),
     "bl_localplan_debug_path": (C.c_int, [_vp]),
     "bl_localplan_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_shortcut_destroy": (None, [_vp]),
+    "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),
+    "bl_shortcut_cells": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "bl_shortcut_poses": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "bl_shortcut_debug_visible": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "bl_shortcut_debug_path": (C.c_int, [_vp]),
+    "bl_shortcut_last_device_ms": (C.c_int, [_vp, _P(C.c_float), _P(C.c_float)]),
     "bl_viewgain_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_viewgain_destroy": (None, [_vp]),
     "bl_viewgain_set_params": (C.c_int, [_vp, _P(ViewGainParams)]),

@@ -882,6 +882,87 @@ class LocalPlanner:
             self.h = None
 
 
+class PathShortcut:
+    """Path shortcutting (bl_shortcut_*, include/botlab_hip.h): any-angle waypoints from grid paths -- all-pairs line of sight over a
+    path's cells and the cheapest chain of segments over the visibility graph, in exact integers."""
+
+    MAX_POINTS, MAX_PATHS, WINDOW_BYTES = 8192, 4096, 64 * 1024
+
+    def __init__(self, ctx=None, **params):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_shortcut_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        self.params = None
+        if params:
+            self.set_params(**params)
+
+    def set_params(self, clearance, max_span=64, waypoint_cost=1024):
+        p = _capi.ShortcutParams(float(clearance), int(max_span), int(waypoint_cost))
+        check(self.ctx.lib.bl_shortcut_set_params(self.h, C.byref(p)))
+        self.params = p
+
+    def cells(self, distances, paths):
+        """paths: a list of (m, 2) integer arrays of cells (x, y).  Returns (keeps, costs): per path the kept indices (int32) and
+        costs as an (P, 2) int64 array: the shortened path's cost and the input path's."""
+        n = len(paths)
+        arrs = [np.asarray(q, dtype=np.int32).reshape(-1, 2) for q in paths]
+        offs = np.zeros(n + 1, np.int32)
+        offs[1:] = np.cumsum([len(q) for q in arrs], dtype=np.int64)
+        xy = np.ascontiguousarray(np.concatenate(arrs) if n else np.zeros((0, 2), np.int32), dtype=np.int32)
+        keep = np.zeros(max(len(xy), 1), np.int32)
+        counts = np.zeros(max(n, 1), np.int32)
+        cost = np.zeros((max(n, 1), 2), np.int64)
+        check(self.ctx.lib.bl_shortcut_cells(self.h, distances.h, xy.ctypes.data, offs.ctypes.data, n, keep.ctypes.data, counts.ctypes.data,
+                                             cost.ctypes.data))
+        return [keep[offs[k]:offs[k] + counts[k]].copy() for k in range(n)], cost[:n]
+
+    def shortcut(self, distances, path, return_cost=False):
+        """One path of Pose: the kept poses, headings along the segments."""
+        out, costs = self.poses(distances, [path])
+        return (out[0], costs[0]) if return_cost else out[0]
+
+    def poses(self, distances, paths):
+        """paths: a list of lists of Pose.  Returns (shortened paths as lists of Pose, (P, 2) int64 costs)."""
+        n = len(paths)
+        cap = max([len(q) for q in paths] + [1])
+        buf = np.zeros((max(n, 1), cap), dtype=POSE_DTYPE)
+        for k, q in enumerate(paths):
+            for i, p in enumerate(q):
+                buf[k, i] = (p.utime, p.x, p.y, p.theta, 0)
+        lens = np.array([len(q) for q in paths] + ([] if n else [0]), np.int32)
+        out = np.zeros_like(buf)
+        out_lens = np.zeros(max(n, 1), np.int32)
+        cost = np.zeros((max(n, 1), 2), np.int64)
+        check(self.ctx.lib.bl_shortcut_poses(self.h, distances.h, buf.ctypes.data, cap, lens.ctypes.data, n, out.ctypes.data, out_lens.ctypes.data,
+                                             cost.ctypes.data))
+        res = [[Pose(int(p["utime"]), float(p["x"]), float(p["y"]), float(p["theta"])) for p in out[k, :out_lens[k]]] for k in range(n)]
+        return res, cost[:n]
+
+    def visible(self, distances, cells):
+        """uint8 [m, m] of one path of m <= 512 cells: [j, i] = 1 iff (i, j) is an edge."""
+        xy = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 2))
+        m = len(xy)
+        out = np.zeros((m, m), np.uint8)
+        check(self.ctx.lib.bl_shortcut_debug_visible(self.h, distances.h, xy.ctypes.data, m, out.ctypes.data))
+        return out
+
+    def debugPath(self):
+        """0: the last launch staged the window in LDS; 1: it read the grids directly; -1 before the first."""
+        return self.ctx.lib.bl_shortcut_debug_path(self.h)
+
+    def lastDeviceMs(self):
+        """(all kernels, k_sc_visible alone) of the last cells / poses call, in ms."""
+        ms, mv = C.c_float(), C.c_float()
+        check(self.ctx.lib.bl_shortcut_last_device_ms(self.h, C.byref(ms), C.byref(mv)))
+        return ms.value, mv.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_shortcut_destroy(self.h)
+            self.h = None
+
+
 def nav_min_traversable_cells(distances, searchParams):
     """n_min: the smallest L1 distance (in cells) that is traversable under searchParams -- f[n] > minDistanceToObstacle * 1.000001
     with the distance grid's own table f[n] = f[n - 1] + 0.1f; None if no distance of this grid is."""
@@ -1370,6 +1451,19 @@ class MotionPlanner:
         finally:
             nf.close()
         return (paths[0], int(costs[0])) if return_cost else paths[0]
+
+    def shortcutPath(self, path, clearance=None, max_span=64, waypoint_cost=1024):
+        """Any-angle waypoints of a planPath / planPathOptimal result (PathShortcut); clearance None: minDistanceToObstacle."""
+        sc = PathShortcut(self.distances_.ctx, clearance=self.searchParams_.minDistanceToObstacle if clearance is None else clearance,
+                          max_span=max_span, waypoint_cost=waypoint_cost)
+        try:
+            return sc.shortcut(self.distances_, path)
+        finally:
+            sc.close()
+
+    def planPathShortcut(self, start, goal, clearance=None, max_span=64, waypoint_cost=1024):
+        """planPathOptimal followed by shortcutPath."""
+        return self.shortcutPath(self.planPathOptimal(start, goal), clearance, max_span, waypoint_cost)
 
     def isPathSafe(self, path):
         # motion_planner.cpp:77-96 (one gather for all poses); a pose outside the grid is unsafe (DESIGN.md D9)

@@ -11,6 +11,7 @@
 
 #include <botlab/botlab_dropin.hpp>
 #include <botlab/nav_field.hpp>
+#include <botlab/path_shortcut.hpp>
 
 namespace botlab_hip {
 
@@ -72,6 +73,22 @@ public:
         if (cost) *cost = r.cost;
         return r.path;
     }
+
+    // Any-angle waypoints of a planPath / planPathOptimal result (path_shortcut.hpp; no reference counterpart): the kept poses, so
+    // that a waypoint follower turns once per segment, not once per cell.  A path of fewer than 3 poses comes back as it is.
+    Path shortcutPath(const Path& path, double clearance, int max_span = 64, int waypoint_cost = 1024, int64_t* cost = nullptr) const
+    {
+        PathShortcutT<Path, Pose> sc(shortcut_params(clearance, max_span, waypoint_cost));
+        return sc.shortcut(path, distances_, cost);
+    }
+    Path shortcutPath(const Path& path) const { return shortcutPath(path, searchParams_.minDistanceToObstacle); }
+    // planPathOptimal followed by shortcutPath
+    Path planPathShortcut(const Pose& start, const Pose& goal, double clearance, int max_span = 64, int waypoint_cost = 1024,
+                          int32_t obstacle_gain = NAV_OBSTACLE_GAIN) const
+    {
+        return shortcutPath(planPathOptimal(start, goal, obstacle_gain), clearance, max_span, waypoint_cost);
+    }
+    Path planPathShortcut(const Pose& start, const Pose& goal) const { return planPathShortcut(start, goal, searchParams_.minDistanceToObstacle); }
 
     bool isValidGoal(const Pose& goal) const                                // motion_planner.cpp:52-74
     {

@@ -975,6 +975,78 @@ int bl_localplan_debug_path(const bl_localplan* lp);
 /* device time of the last bl_localplan_commands' kernels (HIP events around the launches); BL_ERR_STATE before the first */
 int bl_localplan_last_device_ms(const bl_localplan* lp, float* ms);
 
+/* ------------------------------------------------------------------ path shortcutting (no reference counterpart)
+ * Any-angle waypoints from a grid path: the cheapest chain of straight segments between cells of the path, each segment running
+ * over cells with enough clearance only.  bl_astar_search, bl_navfield_paths and bl_plan_path_to_frontier emit a pose per grid
+ * cell, as the reference's makePath does (src/planning/astar.cpp:235-274), and src/mbot/motion_controller.cpp turns, drives and
+ * stops once per pose.  Done exactly this is all-pairs line of sight over the path plus a shortest path over the visibility graph,
+ * not greedy string pulling.  Everything that is compared is an integer.
+ *   Inputs: a transformed bl_dist -- n(c) and the float table f[n], as the navigation field reads them --, the parameters below and
+ *     P paths of cells; path p has m_p cells (x_k, y_k), all inside the grid (a cell off the grid: BL_ERR_ARG).
+ *   ok(c): n(c) != 0xFFFF and (double)f[n(c)] > clearance * 1.000001 -- the field's traversable(n) with clearance in place of
+ *     minDistanceToObstacle, formed as a per-n table on the host by the same code.
+ *   Cover of a pair (a, b), DX = x_b - x_a, DY = y_b - y_a: every cell (x_a + u, y_a + v) of the bounding box of the two cells with
+ *     2 * |u * DY - v * DX| <= |DX| + |DY|.  This is exactly the set of cells whose closed square meets the segment between the two
+ *     cell centres (the supercover: both cells at a corner crossing); tests/test_path_shortcut_model_cpu.py checks it against
+ *     rational segment / square clipping.  It is the same set from either end.
+ *   Edges: (i, j) is an edge iff 0 < j - i <= max_span and either j == i + 1 or every cell of cover(i, j) is ok.  The input path's
+ *     own steps are always edges, whatever clearance is.
+ *   Length: L(i, j) = floor(sqrt(2^20 * (DX^2 + DY^2))), the exact integer square root (width + height < 65535, so the argument
+ *     is below 2^52).  A straight cell step is 1024, (3, 4) is exactly 5120.
+ *   Cost: cost[0] = 0; cost[j] = min over edges (i, j) of cost[i] + L(i, j) + waypoint_cost, in int64; pred[j] the minimising i, ties
+ *     to the SMALLEST i.
+ *   Result per path: the kept indices 0 = k_0 < ... < k_r = m - 1 read back from pred, their count, cost[m - 1], and the input
+ *     path's own cost: the sum over (i, i + 1) of L(i, i + 1) + waypoint_cost.  m == 0: count 0, both costs 0; m == 1: count 1, both
+ *     costs 0.  The minimum is over exact integers: the result does not depend on the launch shape.  max_span == 1 returns every path
+ *     unchanged, and so does a clearance that no cell satisfies.
+ *   Refused with BL_ERR_ARG: by bl_shortcut_set_params a clearance that is not finite, max_span outside 1 .. BL_SHORTCUT_MAX_POINTS,
+ *     waypoint_cost outside 0 .. BL_SHORTCUT_MAX_WAYPOINT_COST (the handle keeps what it had); by the calls more than
+ *     BL_SHORTCUT_MAX_PATHS paths, a path of more than BL_SHORTCUT_MAX_POINTS cells, offsets that do not start at 0 or decrease, a
+ *     cell or a pose off the grid, a bl_dist of another ctx.  BL_ERR_STATE before bl_shortcut_set_params.
+ *   Pose form (bl_shortcut_poses): cell k is global_position_to_grid_cell of pose k, inside the grid by the test bl_navfield_paths
+ *     applies to a start pose.  Kept poses keep x, y and utime bit for bit; pose 0 keeps its theta; a kept pose k_s, s >= 1, gets
+ *     theta = (float)atan2((double)DY, (double)DX) of the cell difference to the previous kept pose (the host's libm, on the host);
+ *     where both differences are 0 it keeps its own theta.  Pose 0 (a robot pose) may lie up to half a cell from its cell's
+ *     centre; the cover is taken from the centre, so the first segment is checked as if the robot stood there.
+ * How it is computed (bl_shortcut.hip): k_sc_visible, one launch for all paths, fills a bit matrix vis[path][j][bit j - i]; a wave
+ * takes one j and 64 consecutive spans j - i, walks from cell j along the major axis -- per major step the covered minor cells are at
+ * most 3, found from a carried cross product, no division -- and leaves at the first cell that is not ok.  The ok bits of a path's
+ * bounding box (bw x bh cells) are staged in LDS, rows padded to 32 bits:
+ *   path 0 (staged) iff ((bw + 31) / 32 * 4) * bh <= BL_SHORTCUT_WINDOW_BYTES for every path of the call, path 1 (n(c) and the table
+ *   read through L2) otherwise.  The rule decides speed only.
+ * k_sc_dp, a workgroup per path: cost[] in LDS, j serial, the lanes take the i of the window, L by a double sqrt corrected by
+ * integer compares, the least key (cost, i) by wave shuffles and one LDS hop; its last thread walks pred and writes the kept
+ * indices ascending.  No atomics.  Calls are stream-ordered on the ctx stream, with one synchronisation, at the return. */
+#define BL_SHORTCUT_WINDOW_BYTES (64 * 1024)
+#define BL_SHORTCUT_MAX_POINTS 8192
+#define BL_SHORTCUT_MAX_PATHS 4096
+#define BL_SHORTCUT_MAX_WAYPOINT_COST 1048576
+typedef struct bl_shortcut_params_t {
+    double clearance;                  /* metres, finite: a segment runs over cells farther than this from any obstacle */
+    int32_t max_span;                  /* 1 .. BL_SHORTCUT_MAX_POINTS: the longest j - i of an edge */
+    int32_t waypoint_cost;             /* 0 .. BL_SHORTCUT_MAX_WAYPOINT_COST, in 1/1024 cell: what one more waypoint is worth */
+} bl_shortcut_params_t;                /* 16 bytes */
+typedef struct bl_shortcut bl_shortcut;
+int bl_shortcut_create(bl_ctx* ctx, bl_shortcut** out);               /* buffers grow on demand */
+void bl_shortcut_destroy(bl_shortcut* sc);
+int bl_shortcut_set_params(bl_shortcut* sc, const bl_shortcut_params_t* params);   /* refused: the handle keeps what it had */
+/* P paths: path p is the cells xy[2 * k], xy[2 * k + 1] for k = offsets[p] .. offsets[p + 1] - 1 (offsets[0] == 0).  out_keep has
+ * room for offsets[P] indices: path p's kept indices (into its own cells) start at out_keep[offsets[p]], out_counts[p] of them.
+ * out_cost: 2 per path, the shortened path's cost and the input path's. */
+int bl_shortcut_cells(bl_shortcut* sc, const bl_dist* dist, const int32_t* xy, const int32_t* offsets, int P, int32_t* out_keep,
+                      int32_t* out_counts, int64_t* out_cost);
+/* P paths of poses: path p is paths[p * cap_each .. + lens[p]); the kept poses go to out_paths + p * cap_each, out_lens[p] of them.
+ * out_cost (optional) as above. */
+int bl_shortcut_poses(bl_shortcut* sc, const bl_dist* dist, const bl_pose_xyt_t* paths, int cap_each, const int* lens, int P,
+                      bl_pose_xyt_t* out_paths, int* out_lens, int64_t* out_cost);
+/* the edges of one path of m <= 512 cells: out[j * m + i] = 1 iff (i, j) is an edge, 0 elsewhere (m * m bytes) */
+int bl_shortcut_debug_visible(bl_shortcut* sc, const bl_dist* dist, const int32_t* xy, int m, uint8_t* out);
+/* which path the last k_sc_visible launch took: 0 the window staged in LDS, 1 the grids read directly; -1 before the first */
+int bl_shortcut_debug_path(const bl_shortcut* sc);
+/* device time of the last bl_shortcut_cells / bl_shortcut_poses, and of its k_sc_visible launches alone (ms_visible may be NULL):
+ * HIP events around the launches; BL_ERR_STATE before the first */
+int bl_shortcut_last_device_ms(const bl_shortcut* sc, float* ms, float* ms_visible);
+
 #ifdef __cplusplus
 }
 #endif
