@@ -96,6 +96,40 @@ class ScanMatchWideStats(C.Structure):
                 f"candidates_scored={self.candidates_scored}, block_log2={self.block_log2}, path={self.path})")
 
 
+class ScanMatchPrior(C.Structure):
+    """bl_scan_match_prior_t: the motion prior of a scan match and whether its moments are wanted (24 bytes)."""
+    _fields_ = [("a_xx", C.c_int32), ("a_xy", C.c_int32), ("a_yy", C.c_int32), ("a_tt", C.c_int32), ("half_life", C.c_int32),
+                ("want_moments", C.c_int32)]
+
+
+class ScanMatchMoments(C.Structure):
+    """bl_scan_match_moments_t: the weighted sums over a scan match's window, the best objective, the sub-cell fractions (112 bytes)."""
+    _fields_ = [(n, C.c_int64) for n in ("s0", "sx", "sy", "st", "sxx", "sxy", "syy", "sxt", "syt", "stt")] + \
+               [("best_obj", C.c_int32), ("pen_best", C.c_int32), ("sub_num", C.c_int32 * 3), ("sub_den", C.c_int32 * 3)]
+
+    def sums(self):
+        return tuple(int(getattr(self, n)) for n in ("s0", "sx", "sy", "st", "sxx", "sxy", "syy", "sxt", "syt", "stt"))
+
+    def fractions(self):
+        return tuple((int(self.sub_num[a]), int(self.sub_den[a])) for a in range(3))
+
+    def covariance(self, meters_per_cell, dtheta):
+        """(mean[3], cov[6] = xx, xy, yy, xt, yt, tt) in metres and radians: bl_scanmatch_covariance itself."""
+        mean, cov = (C.c_double * 3)(), (C.c_double * 6)()
+        load().bl_scanmatch_covariance(C.byref(self), float(meters_per_cell), float(dtheta), mean, cov)
+        return tuple(mean), tuple(cov)
+
+    def refined_pose(self, result, centre, meters_per_cell, dtheta):
+        """The matched pose moved by the sub-cell fractions (the centre when the match was not accepted): bl_scanmatch_refined_pose."""
+        out = Pose()
+        load().bl_scanmatch_refined_pose(C.byref(result), C.byref(self), C.byref(centre), float(meters_per_cell), float(dtheta),
+                                         C.byref(out))
+        return out
+
+    def __repr__(self):
+        return f"ScanMatchMoments(sums={self.sums()}, best_obj={self.best_obj}, pen_best={self.pen_best}, fractions={self.fractions()})"
+
+
 class NavFieldParams(C.Structure):
     """bl_navfield_params_t: the metric and the goal reach of a navigation field (32 bytes)."""
     _fields_ = [("minDistanceToObstacle", C.c_double), ("maxDistanceWithCost", C.c_double), ("distanceCostExponent", C.c_double),
@@ -163,6 +197,7 @@ class RBSlamMatchParams(C.Structure):
 assert C.sizeof(RBSlamResult) == 64 and C.sizeof(RBSlamMatchParams) == 24
 assert C.sizeof(ScanMatchParams) == 28 and C.sizeof(ScanMatchResult) == 56
 assert C.sizeof(ScanMatchWideParams) == 32 and C.sizeof(ScanMatchWideStats) == 40
+assert C.sizeof(ScanMatchPrior) == 24 and C.sizeof(ScanMatchMoments) == 112
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
 assert C.sizeof(PfAdaptiveParams) == 40 and C.sizeof(PfAdaptiveState) == 24
 
@@ -314,6 +349,10 @@ SIGNATURES = {
     "bl_scanmatch_debug_path": (C.c_int, [_vp]),
     "bl_scanmatch_match_wide": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _P(ScanMatchWideParams), _P(ScanMatchResult)]),
     "bl_scanmatch_wide_stats": (C.c_int, [_vp, _P(ScanMatchWideStats)]),
+    "bl_scanmatch_match_prior": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _P(ScanMatchParams), _P(ScanMatchPrior),
+                                           _P(ScanMatchResult), _P(ScanMatchMoments)]),
+    "bl_scanmatch_covariance": (None, [_P(ScanMatchMoments), C.c_double, C.c_double, _P(C.c_double), _P(C.c_double)]),
+    "bl_scanmatch_refined_pose": (None, [_P(ScanMatchResult), _P(ScanMatchMoments), _P(Pose), C.c_double, C.c_double, _P(Pose)]),
     "bl_navfield_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_navfield_destroy": (None, [_vp]),
     "bl_navfield_compute": (C.c_int, [_vp, _vp, _P(NavFieldParams), _vp, C.c_int]),

@@ -12,8 +12,15 @@
 //                clipped to the grid fits in the LDS, the positive part of those cells is staged there (path 0); otherwise the grid is read directly (path 1).
 //                Every workgroup leaves its best 64-bit key and how many of its candidates share that key's score.
 //   k_sm_final   one workgroup: maximum of the keys (order-independent), sum of the tie counts, the result struct.
+// bl_scanmatch_match_prior runs the same sequence with the prior forms of the last two (k_sm_score_prior,
+// k_sm_final_prior: the objective score - pen in the key, the volume and the tie count) and, when the moments are wanted, behind them
+//   k_sm_moments        a streaming pass over the stored objective volume: a wave owns whole rows of di, every lane a fixed di; the
+//                       weight of a candidate from one multiplication by a reciprocal of half_life and a 64-entry table in LDS;
+//                       64-bit integer sums, one record per workgroup, no atomics.
+//   k_sm_moments_final  one workgroup: the sum of the records, the sub-cell fractions from the winner's six neighbours.
 #include <string.h>
 
+#define BL_SM_HELPER                   // this translation unit defines the header's two helpers with external linkage (bindings call them)
 #include "bl_internal.h"
 
 #define SM_MAX_N 64
@@ -52,6 +59,11 @@ struct bl_scanmatch {
     bool volume_kept = false;
     int vol_nx = 0, vol_ny = 0, vol_nt = 0;
     int last_path = -1;
+    // the match with a prior: the moments record (best_obj and pen_best from k_sm_final_prior, the rest from k_sm_moments_final),
+    // its pinned copy, one partial record per workgroup of k_sm_moments
+    bl_scan_match_moments_t* d_mom = nullptr;
+    bl_scan_match_moments_t* h_mom = nullptr;
+    struct sm_partial* d_partial = nullptr;
     // the wide match (below): buffers of its own, so that bl_scanmatch_match's are as they were
     struct smw_head* d_whead = nullptr;
     void* wstaging = nullptr;          // pinned: smw_head | ranges | thetas
@@ -163,10 +175,22 @@ __device__ __forceinline__ uint32_t sm_positive_bytes(uint32_t v)       // max(0
     return v & ~(neg * 0xffu);
 }
 
-// grid: (slices, headings).  Dynamic LDS: uint8 window[lds_window_bytes].
-__global__ __launch_bounds__(1024) void k_sm_score(sm_head* __restrict__ head, const int8_t* __restrict__ cells, bl_frame f,
-                                                    const int2* __restrict__ ends, int lds_window_bytes,
-                                                    sm_block_best* __restrict__ best, int32_t* __restrict__ volume)
+// The prior of bl_scanmatch_match_prior as the kernels take it, and the objective's offset in the key's high word.
+struct sm_prior_k { int32_t a_xx, a_xy, a_yy, a_tt; };
+#define SM_OBJ_BIAS (1 << 23)
+__device__ __forceinline__ int sm_pen(const sm_prior_k& p, int di, int dj, int dk)
+{
+    const long long q = (long long)p.a_xx * (di * di) + 2ll * p.a_xy * (di * dj) + (long long)p.a_yy * (dj * dj) +
+                        (long long)p.a_tt * (dk * dk);               // 0 <= q < 2^31 within the limits
+    return (int)(q >> 8);
+}
+
+// The scoring loop of both forms.  PRIOR = false is bl_scanmatch_match's kernel, statement for statement; PRIOR = true takes the
+// penalty off once per candidate, behind the ray loop, and keys, stores and counts ties on the objective.
+template <bool PRIOR>
+__device__ __forceinline__ void sm_score_body(sm_head* __restrict__ head, const int8_t* __restrict__ cells, const bl_frame& f,
+                                              const int2* __restrict__ ends, int lds_window_bytes,
+                                              sm_block_best* __restrict__ best, int32_t* __restrict__ volume, const sm_prior_k& pr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ unsigned long long s_key[16];
@@ -204,7 +228,7 @@ __global__ __launch_bounds__(1024) void k_sm_score(sm_head* __restrict__ head, c
     const int per = (ncand + gridDim.x - 1) / gridDim.x;                // candidates of this slice
     const int c_begin = blockIdx.x * per, c_end = min(ncand, c_begin + per);
     unsigned long long key = 0;
-    int top = -1; uint32_t ties = 0;
+    int top = PRIOR ? INT32_MIN : -1; uint32_t ties = 0;                    // an objective is above -2^23
     for (int cb = c_begin + (tid & ~63); cb < c_end; cb += nthreads) {       // wave-uniform trip count: the broadcasts need every lane
         const int c = cb + lane;
         const int jrow = c / cw;
@@ -238,9 +262,10 @@ __global__ __launch_bounds__(1024) void k_sm_score(sm_head* __restrict__ head, c
             mine = next;
         }
         if (c >= c_end) continue;
+        if (PRIOR) acc -= sm_pen(pr, di, dj, dk);                            // from here on the objective; the centre's pen is 0
         if (volume) volume[(size_t)k * ncand + c] = acc;
         if (dk == 0 && di == 0 && dj == 0) head->score_centre = acc;
-        const unsigned long long kc = sm_key(acc, di, dj, dk);
+        const unsigned long long kc = sm_key(PRIOR ? acc + SM_OBJ_BIAS : acc, di, dj, dk);
         key = kc > key ? kc : key;
         if (acc > top) { top = acc; ties = 1; } else if (acc == top) ++ties;
     }
@@ -250,7 +275,8 @@ __global__ __launch_bounds__(1024) void k_sm_score(sm_head* __restrict__ head, c
     __syncthreads();
     unsigned long long bkey = 0;
     for (int w = 0; w < (nthreads >> 6); ++w) bkey = s_key[w] > bkey ? s_key[w] : bkey;
-    uint32_t n = (top >= 0 && (uint32_t)top == (uint32_t)(bkey >> 32)) ? ties : 0;
+    uint32_t n = PRIOR ? ((ties != 0 && (uint32_t)(top + SM_OBJ_BIAS) == (uint32_t)(bkey >> 32)) ? ties : 0)
+                       : ((top >= 0 && (uint32_t)top == (uint32_t)(bkey >> 32)) ? ties : 0);
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
     if (lane == 0) s_ties[wave] = n;
     __syncthreads();
@@ -263,9 +289,24 @@ __global__ __launch_bounds__(1024) void k_sm_score(sm_head* __restrict__ head, c
     }
 }
 
+// grid: (slices, headings).  Dynamic LDS: uint8 window[lds_window_bytes].
+__global__ __launch_bounds__(1024) void k_sm_score(sm_head* __restrict__ head, const int8_t* __restrict__ cells, bl_frame f,
+                                                    const int2* __restrict__ ends, int lds_window_bytes,
+                                                    sm_block_best* __restrict__ best, int32_t* __restrict__ volume)
+{
+    sm_score_body<false>(head, cells, f, ends, lds_window_bytes, best, volume, sm_prior_k());
+}
+__global__ __launch_bounds__(1024) void k_sm_score_prior(sm_head* __restrict__ head, const int8_t* __restrict__ cells, bl_frame f,
+                                                          const int2* __restrict__ ends, int lds_window_bytes,
+                                                          sm_block_best* __restrict__ best, int32_t* __restrict__ volume, sm_prior_k pr)
+{
+    sm_score_body<true>(head, cells, f, ends, lds_window_bytes, best, volume, pr);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- result
-__global__ __launch_bounds__(256) void k_sm_final(sm_head* __restrict__ head, const sm_block_best* __restrict__ best, int nblocks,
-                                                  bl_frame f)
+template <bool PRIOR>
+__device__ __forceinline__ void sm_final_body(sm_head* __restrict__ head, const sm_block_best* __restrict__ best, int nblocks,
+                                              const bl_frame& f, const sm_prior_k& pr, bl_scan_match_moments_t* __restrict__ mom)
 {
     __shared__ unsigned long long s_key[4];
     __shared__ uint32_t s_ties[4];
@@ -288,6 +329,11 @@ __global__ __launch_bounds__(256) void k_sm_final(sm_head* __restrict__ head, co
     if (tid == 0) {
         int score, di, dj, dk;
         sm_key_decode(key, &score, &di, &dj, &dk);
+        if (PRIOR) {                                                         // the high word held obj + 2^23; the score is the raw one
+            const int obj = score - SM_OBJ_BIAS, pen = sm_pen(pr, di, dj, dk);
+            mom->best_obj = obj; mom->pen_best = pen;
+            score = obj + pen;
+        }
         bl_scan_match_result_t r;
         r.di = di; r.dj = dj; r.dk = dk;
         r.score = score;
@@ -307,6 +353,153 @@ __global__ __launch_bounds__(256) void k_sm_final(sm_head* __restrict__ head, co
     }
 }
 
+__global__ __launch_bounds__(256) void k_sm_final(sm_head* __restrict__ head, const sm_block_best* __restrict__ best, int nblocks,
+                                                  bl_frame f)
+{
+    sm_final_body<false>(head, best, nblocks, f, sm_prior_k(), nullptr);
+}
+__global__ __launch_bounds__(256) void k_sm_final_prior(sm_head* __restrict__ head, const sm_block_best* __restrict__ best, int nblocks,
+                                                        bl_frame f, sm_prior_k pr, bl_scan_match_moments_t* __restrict__ mom)
+{
+    sm_final_body<true>(head, best, nblocks, f, pr, mom);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- moments
+#define SM_MOM_THREADS 256
+#define SM_MOM_MAX_GROUPS 1024
+#define SM_MOM_BATCH 4                  // rows a wave has in flight
+struct sm_partial { long long s[10]; };
+__constant__ int32_t c_sm_exp2[64] = { BL_SM_EXP2_VALUES };
+
+__device__ __forceinline__ long long sm_wave_sum(long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// The weight of a candidate d >= 0 below the best objective.  t = floor(64 d / half_life) = 64 e + i (d = e half_life + f and
+// 64 f / half_life < 64), taken as (64 d * magic) >> shift with shift = 30 + L, 2^L >= half_life, magic = ceil(2^shift / half_life)
+// <= 2^30: for n = 64 d < 2^30 (d < 2^23 + 2^19) the product is n / half_life + n r / (half_life 2^shift) with 0 <= r < half_life,
+// and the second term is below 2^-L <= 1 / half_life, so the floor is that of n / half_life.  The product is below 2^61.
+__device__ __forceinline__ int sm_weight(int d, uint32_t magic, int shift, const int32_t* tab)
+{
+    const unsigned long long t = ((unsigned long long)((uint32_t)d << 6) * magic) >> shift;
+    const uint32_t e = (uint32_t)(t >> 6), i = (uint32_t)t & 63u;
+    return e >= 21u ? 0 : (tab[i] >> e);
+}
+
+// grid: up to SM_MOM_MAX_GROUPS workgroups of four waves.  A row is the 2 nx + 1 objectives of one (dk, dj); wave g of G takes rows
+// g, g + G, ..., SM_MOM_BATCH of them at a time, its lanes along di in chunks of 64, so a lane's di is fixed for a whole chunk pass
+// and the row's dj, dk are wave-uniform: six running sums per lane (w, w dj, w dk, w dj dj, w dj dk, w dk dk) are folded into the
+// ten moments with di once per chunk.  (dk, dj) of the next row come from adding the stride's quotient and remainder: no division
+// per element or per row.
+__global__ __launch_bounds__(SM_MOM_THREADS) void k_sm_moments(const sm_head* __restrict__ head, const int32_t* __restrict__ volume,
+                                                               const bl_scan_match_moments_t* __restrict__ mom, uint32_t magic,
+                                                               int shift, sm_partial* __restrict__ partial)
+{
+    __shared__ int32_t s_tab[64];
+    __shared__ long long s_part[SM_MOM_THREADS / 64][10];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    if (tid < 64) s_tab[tid] = c_sm_exp2[tid];
+    __syncthreads();
+    const int nt = head->ntheta, nx = head->nx, ny = head->ny;
+    const int cw = 2 * nx + 1, ch = 2 * ny + 1, rows = (2 * nt + 1) * ch;
+    const int best = mom->best_obj;
+    const int nwaves = (int)gridDim.x * (SM_MOM_THREADS / 64);
+    const int g = __builtin_amdgcn_readfirstlane((int)blockIdx.x * (SM_MOM_THREADS / 64) + wave);
+    const int step_k = nwaves / ch, step_j = nwaves - step_k * ch;          // the stride from a row to the wave's next one
+    long long m[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) m[i] = 0;
+    for (int x0 = 0; x0 < cw; x0 += 64) {                                    // at most three chunks (cw <= 129)
+        const int xi = x0 + lane;
+        const bool on = xi < cw;
+        const int di = xi - nx;
+        long long a = 0, b = 0, c = 0, d2 = 0, e2 = 0, f2 = 0;
+        int k = g / ch, j = g - k * ch;                                      // of row r; once per chunk
+        for (int r = g; r < rows; r += SM_MOM_BATCH * nwaves) {              // wave-uniform
+            int v[SM_MOM_BATCH];
+#pragma unroll
+            for (int u = 0; u < SM_MOM_BATCH; ++u) {
+                const long long ru = (long long)r + (long long)u * nwaves;
+                v[u] = (on && ru < rows) ? volume[(size_t)ru * cw + xi] : best;           // ru < rows, xi < cw: below rows * cw
+            }
+#pragma unroll
+            for (int u = 0; u < SM_MOM_BATCH; ++u) {
+                const long long ru = (long long)r + (long long)u * nwaves;
+                const int dj = j - ny, dk = k - nt;
+                int w = sm_weight(best - v[u], magic, shift, s_tab);
+                w = (on && ru < rows) ? w : 0;
+                a += w;
+                b += (long long)w * dj;
+                c += (long long)w * dk;
+                d2 += (long long)w * (dj * dj);
+                e2 += (long long)w * (dj * dk);
+                f2 += (long long)w * (dk * dk);
+                k += step_k; j += step_j;
+                if (j >= ch) { j -= ch; ++k; }
+            }
+        }
+        m[0] += a; m[1] += a * di; m[2] += b; m[3] += c; m[4] += a * (di * di);
+        m[5] += b * di; m[6] += d2; m[7] += c * di; m[8] += e2; m[9] += f2;
+    }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const long long t = sm_wave_sum(m[i]);
+        if (lane == 0) s_part[wave][i] = t;
+    }
+    __syncthreads();
+    if (tid < 10) {
+        long long t = 0;
+        for (int w = 0; w < SM_MOM_THREADS / 64; ++w) t += s_part[w][tid];
+        partial[blockIdx.x].s[tid] = t;
+    }
+}
+
+// one workgroup: the sum of the records; the sub-cell fractions from the winner's neighbours along each axis, read only behind the
+// edge test (the neighbours of a candidate inside the window are inside the volume)
+__global__ __launch_bounds__(256) void k_sm_moments_final(const sm_head* __restrict__ head, const int32_t* __restrict__ volume,
+                                                          const sm_partial* __restrict__ partial, int nparts,
+                                                          bl_scan_match_moments_t* __restrict__ mom)
+{
+    __shared__ long long s_part[4][10];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    long long m[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) m[i] = 0;
+    for (int p = tid; p < nparts; p += 256) {
+#pragma unroll
+        for (int i = 0; i < 10; ++i) m[i] += partial[p].s[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const long long t = sm_wave_sum(m[i]);
+        if (lane == 0) s_part[wave][i] = t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        long long t[10];
+        for (int i = 0; i < 10; ++i) t[i] = s_part[0][i] + s_part[1][i] + s_part[2][i] + s_part[3][i];
+        mom->s0 = t[0]; mom->sx = t[1]; mom->sy = t[2]; mom->st = t[3]; mom->sxx = t[4];
+        mom->sxy = t[5]; mom->syy = t[6]; mom->sxt = t[7]; mom->syt = t[8]; mom->stt = t[9];
+        const int nt = head->ntheta, nx = head->nx, ny = head->ny, cw = 2 * nx + 1, ch = 2 * ny + 1;
+        const int di = head->result.di, dj = head->result.dj, dk = head->result.dk;
+        const size_t at = ((size_t)(dk + nt) * ch + (size_t)(dj + ny)) * cw + (size_t)(di + nx);
+        const int o0 = mom->best_obj;
+        const int half[3] = { nx, ny, nt }, pos[3] = { di, dj, dk };
+        const size_t stride[3] = { (size_t)1, (size_t)cw, (size_t)cw * ch };
+        for (int ax = 0; ax < 3; ++ax) {
+            int num = 0, den = 1;
+            if (half[ax] >= 1 && pos[ax] > -half[ax] && pos[ax] < half[ax]) {
+                const int om = volume[at - stride[ax]], op = volume[at + stride[ax]];
+                den = 2 * (2 * o0 - om - op); num = op - om;
+                if (den == 0) { num = 0; den = 1; }
+            }
+            mom->sub_num[ax] = num; mom->sub_den[ax] = den;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
 extern "C" int bl_scanmatch_create(bl_ctx* ctx, bl_scanmatch** out)
 {
@@ -314,6 +507,7 @@ extern "C" int bl_scanmatch_create(bl_ctx* ctx, bl_scanmatch** out)
     BL_HIP(hipSetDevice(ctx->device));
     // per create: the attribute belongs to the current device, and contexts of several devices and threads make matchers
     BL_HIP(hipFuncSetAttribute((const void*)k_sm_score, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_MAX));
+    BL_HIP(hipFuncSetAttribute((const void*)k_sm_score_prior, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_MAX));
     bl_scanmatch* sm = new bl_scanmatch();
     sm->ctx = ctx;
     hipError_t e = hipMalloc((void**)&sm->d_head, sizeof(sm_head));
@@ -327,6 +521,8 @@ extern "C" void bl_scanmatch_destroy(bl_scanmatch* sm)
     if (!sm) return;
     (void)hipStreamSynchronize(sm->ctx->stream);
     (void)hipFree(sm->d_head); (void)hipFree(sm->d_rays); (void)hipFree(sm->d_ends); (void)hipFree(sm->d_best); (void)hipFree(sm->d_volume);
+    (void)hipFree(sm->d_mom); (void)hipFree(sm->d_partial);
+    if (sm->h_mom) (void)hipHostFree(sm->h_mom);
     if (sm->staging) (void)hipHostFree(sm->staging);
     (void)hipFree(sm->d_whead); (void)hipFree(sm->d_wrays); (void)hipFree(sm->d_pool); (void)hipFree(sm->d_pool_rows);
     (void)hipFree(sm->d_bounds); (void)hipFree(sm->d_list); (void)hipFree(sm->d_seeds); (void)hipFree(sm->d_rec);
@@ -344,11 +540,21 @@ static int sm_grow(T** p, size_t* cap, size_t need)
     return BL_OK;
 }
 
-extern "C" int bl_scanmatch_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* centre,
-                                  const bl_scan_match_params_t* params, bl_scan_match_result_t* result)
+static bool sm_prior_ok(const bl_scan_match_prior_t* p)
+{
+    const int m = BL_SM_MAX_COEFF;
+    if (p->a_xx < 0 || p->a_xx > m || p->a_yy < 0 || p->a_yy > m || p->a_tt < 0 || p->a_tt > m || p->a_xy < -m || p->a_xy > m) return false;
+    return (long long)p->a_xy * p->a_xy <= (long long)p->a_xx * p->a_yy;
+}
+
+// bl_scanmatch_match (prior == nullptr) and bl_scanmatch_match_prior.  A refused plain match forgets a kept volume, as it always
+// has; a refused match with a prior changes nothing.
+static int sm_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* centre,
+                    const bl_scan_match_params_t* params, const bl_scan_match_prior_t* prior, bl_scan_match_result_t* result,
+                    bl_scan_match_moments_t* moments)
 {
     BL_CHECK_ARG(sm != nullptr);
-    sm->volume_kept = false;           // "the last match" includes a refused one: bl_scanmatch_volume then answers BL_ERR_STATE
+    if (!prior) sm->volume_kept = false;   // "the last match" includes a refused one: bl_scanmatch_volume then answers BL_ERR_STATE
     BL_CHECK_ARG(map != nullptr && scan != nullptr && centre != nullptr && params != nullptr && result != nullptr);
     BL_CHECK_ARG(map->ctx == sm->ctx);
     BL_CHECK_ARG(params->nx >= 0 && params->nx <= SM_MAX_N && params->ny >= 0 && params->ny <= SM_MAX_N);
@@ -358,6 +564,13 @@ extern "C" int bl_scanmatch_match(bl_scanmatch* sm, const bl_grid* map, const bl
     int rays = 0;
     for (int i = 0; i < scan->num_ranges; ++i) rays += (scan->ranges[i] > SM_MIN_RANGE && scan->ranges[i] < params->max_range) ? 1 : 0;
     BL_CHECK_ARG(rays <= SM_MAX_RAYS);
+    const bool want_moments = prior != nullptr && prior->want_moments != 0;
+    if (prior) {
+        BL_CHECK_ARG(sm_prior_ok(prior));
+        BL_CHECK_ARG(!want_moments || (prior->half_life >= 1 && prior->half_life <= BL_SM_MAX_HALF_LIFE && moments != nullptr));
+        sm->volume_kept = false;       // accepted: from here on this is the last match
+    }
+    const bool keep = params->keep_volume != 0 || want_moments;
     bl_ctx* ctx = sm->ctx;
     BL_HIP(hipSetDevice(ctx->device));
 
@@ -386,7 +599,16 @@ extern "C" int bl_scanmatch_match(bl_scanmatch* sm, const bl_grid* map, const bl
     if (slices < 1) slices = 1;
     const int nblocks = slices * nk;
     { size_t bc = (size_t)sm->best_cap; rc = sm_grow(&sm->d_best, &bc, (size_t)nblocks); sm->best_cap = (int)bc; if (rc) return rc; }
-    if (params->keep_volume) { rc = sm_grow(&sm->d_volume, &sm->volume_cap, (size_t)nk * ncand); if (rc) return rc; }
+    if (keep) { rc = sm_grow(&sm->d_volume, &sm->volume_cap, (size_t)nk * ncand); if (rc) return rc; }
+    // the moments pass: a wave per SM_MOM_BATCH rows of the volume, at most SM_MOM_MAX_GROUPS workgroups
+    const int mom_rows = nk * ch;
+    int mom_groups = (mom_rows + SM_MOM_BATCH * (SM_MOM_THREADS / 64) - 1) / (SM_MOM_BATCH * (SM_MOM_THREADS / 64));
+    if (mom_groups > SM_MOM_MAX_GROUPS) mom_groups = SM_MOM_MAX_GROUPS;
+    if (prior && !sm->d_mom) {
+        BL_HIP(hipMalloc((void**)&sm->d_mom, sizeof(bl_scan_match_moments_t)));
+        BL_HIP(hipMalloc((void**)&sm->d_partial, SM_MOM_MAX_GROUPS * sizeof(sm_partial)));
+        BL_HIP(hipHostMalloc((void**)&sm->h_mom, sizeof(bl_scan_match_moments_t), hipHostMallocDefault));
+    }
 
     // ---- header and the valid rays, one copy
     sm_head* h = (sm_head*)sm->staging;
@@ -424,16 +646,52 @@ extern "C" int bl_scanmatch_match(bl_scanmatch* sm, const bl_grid* map, const bl
     if (total > 0)
         hipLaunchKernelGGL(k_sm_raster, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, sm->d_head, sm->d_rays,
                            sm->d_rays + sm->ray_cap, f, sm->d_ends);
-    hipLaunchKernelGGL(k_sm_score, dim3(slices, nk), dim3(threads), lds_bytes, ctx->stream, sm->d_head, map->cells, f, sm->d_ends,
-                       lds_window, sm->d_best, params->keep_volume ? sm->d_volume : (int32_t*)nullptr);
-    hipLaunchKernelGGL(k_sm_final, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_best, nblocks, f);
+    if (!prior) {
+        hipLaunchKernelGGL(k_sm_score, dim3(slices, nk), dim3(threads), lds_bytes, ctx->stream, sm->d_head, map->cells, f, sm->d_ends,
+                           lds_window, sm->d_best, params->keep_volume ? sm->d_volume : (int32_t*)nullptr);
+        hipLaunchKernelGGL(k_sm_final, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_best, nblocks, f);
+    } else {
+        sm_prior_k pr; pr.a_xx = prior->a_xx; pr.a_xy = prior->a_xy; pr.a_yy = prior->a_yy; pr.a_tt = prior->a_tt;
+        hipLaunchKernelGGL(k_sm_score_prior, dim3(slices, nk), dim3(threads), lds_bytes, ctx->stream, sm->d_head, map->cells, f,
+                           sm->d_ends, lds_window, sm->d_best, keep ? sm->d_volume : (int32_t*)nullptr, pr);
+        hipLaunchKernelGGL(k_sm_final_prior, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_best, nblocks, f, pr, sm->d_mom);
+        if (want_moments) {
+            // floor(64 d / half_life) as a multiplication (sm_weight): shift = 30 + L with 2^L >= half_life, magic = ceil(2^shift / half_life)
+            int L = 0;
+            while ((1 << L) < prior->half_life) ++L;
+            const int shift = 30 + L;
+            const unsigned long long hl = (unsigned long long)prior->half_life;
+            const uint32_t magic = (uint32_t)(((1ull << shift) + hl - 1) / hl);
+            hipLaunchKernelGGL(k_sm_moments, dim3(mom_groups), dim3(SM_MOM_THREADS), 0, ctx->stream, sm->d_head, sm->d_volume, sm->d_mom,
+                               magic, shift, sm->d_partial);
+            hipLaunchKernelGGL(k_sm_moments_final, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_volume, sm->d_partial,
+                               mom_groups, sm->d_mom);
+        }
+    }
     BL_HIP(hipGetLastError());
     BL_HIP(hipMemcpyAsync(h, sm->d_head, sizeof(sm_head), hipMemcpyDeviceToHost, ctx->stream));
+    if (want_moments)
+        BL_HIP(hipMemcpyAsync(sm->h_mom, sm->d_mom, sizeof(bl_scan_match_moments_t), hipMemcpyDeviceToHost, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));
     *result = h->result;
+    if (want_moments) *moments = *sm->h_mom;
     sm->last_path = h->path;
-    if (params->keep_volume) { sm->volume_kept = true; sm->vol_nx = params->nx; sm->vol_ny = params->ny; sm->vol_nt = params->ntheta; }
+    if (keep) { sm->volume_kept = true; sm->vol_nx = params->nx; sm->vol_ny = params->ny; sm->vol_nt = params->ntheta; }
     return BL_OK;
+}
+
+extern "C" int bl_scanmatch_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* centre,
+                                  const bl_scan_match_params_t* params, bl_scan_match_result_t* result)
+{
+    return sm_match(sm, map, scan, centre, params, nullptr, result, nullptr);
+}
+
+extern "C" int bl_scanmatch_match_prior(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* centre,
+                                        const bl_scan_match_params_t* params, const bl_scan_match_prior_t* prior,
+                                        bl_scan_match_result_t* result, bl_scan_match_moments_t* moments)
+{
+    BL_CHECK_ARG(prior != nullptr);
+    return sm_match(sm, map, scan, centre, params, prior, result, moments);
 }
 
 extern "C" int bl_scanmatch_volume(bl_scanmatch* sm, int32_t* scores)

@@ -445,6 +445,34 @@ class ParticleFilter:
             self.h = None
 
 
+def prior_from_sigmas(sigma_x, sigma_y, rho, sigma_theta, score_per_nat, meters_per_cell, dtheta):
+    """The four coefficients of a scan match's motion prior (a_xx, a_xy, a_yy, a_tt) from a Gaussian on the motion: standard
+    deviations sigma_x, sigma_y (metres, correlation rho, |rho| < 1) and sigma_theta (radians), all > 0 (inf: no prior on that
+    axis); score_per_nat is the number of score units one nat of log-likelihood is worth.  The rule, in double arithmetic, the
+    same as botlab_hip::scan_match_prior_from_sigmas: the Gaussian's information matrix in cells and heading steps
+    (s_x = sigma_x / meters_per_cell, s_y likewise, s_t = sigma_theta / dtheta, q = 1 - rho^2: 1 / (q s_x^2), -rho / (q s_x s_y),
+    1 / (q s_y^2), 1 / s_t^2) times 256 score_per_nat / 2, each rounded to nearest as floor(v + 0.5) and clamped to
+    [0, 32767] (a_xy to [-32767, 32767]; NaN gives 0); then |a_xy| is lowered to floor(sqrt(a_xx a_yy)) if it exceeds it, so
+    that the clamped form is still never negative."""
+    sigma_x, sigma_y, rho, sigma_theta = float(sigma_x), float(sigma_y), float(rho), float(sigma_theta)
+    if not (sigma_x > 0 and sigma_y > 0 and sigma_theta > 0 and abs(rho) < 1 and float(score_per_nat) >= 0):
+        raise ValueError("prior_from_sigmas: sigmas must be > 0, |rho| < 1, score_per_nat >= 0")
+    k = 128.0 * float(score_per_nat)
+    sx, sy, st = sigma_x / float(meters_per_cell), sigma_y / float(meters_per_cell), sigma_theta / float(dtheta)
+    q = 1.0 - rho * rho
+
+    def coeff(v, lo):
+        if v != v:
+            return 0
+        return int(math.floor(min(max(v, lo), 32767.0) + 0.5))     # the bounds are integers: clamping first rounds the same
+    a_xx, a_yy = coeff(k * (1.0 / (q * sx * sx)), 0.0), coeff(k * (1.0 / (q * sy * sy)), 0.0)
+    a_xy = coeff(k * (-rho / (q * sx * sy)), -32767.0)
+    a_tt = coeff(k * (1.0 / (st * st)), 0.0)
+    if a_xy * a_xy > a_xx * a_yy:
+        a_xy = int(math.copysign(math.isqrt(a_xx * a_yy), a_xy))
+    return a_xx, a_xy, a_yy, a_tt
+
+
 class ScanMatcher:
     """Correlative scan matcher (bl_scanmatch_*, include/botlab_hip.h): the pose of a scan against the map from a bounded window of
     whole-cell shifts and heading steps around a centre pose, without odometry.  Off the filter's path: it reads the map only."""
@@ -469,6 +497,33 @@ class ScanMatcher:
         if keep_volume:
             self._shape = (2 * int(ntheta) + 1, 2 * int(ny) + 1, 2 * int(nx) + 1)
         return res
+
+    def match_prior(self, scan, centre, grid, prior=(0, 0, 0, 0), half_life=None, nx=4, ny=4, ntheta=12, dtheta=math.radians(0.5),
+                    max_range=8.0, min_score=0, keep_volume=False):
+        """bl_scanmatch_match_prior: the match under a motion prior (a_xx, a_xy, a_yy, a_tt), e.g. from prior_from_sigmas.
+        Returns (result, moments): a _capi.ScanMatchResult and, when half_life is given (1 .. 2^20), a _capi.ScanMatchMoments
+        (the ten weighted sums, best_obj, pen_best, the sub-cell fractions; .covariance(mpc, dtheta), .refined_pose(...)), else
+        None.  With half_life (or keep_volume) volume() then returns the objective volume."""
+        ls = scan.as_c()
+        params = _capi.ScanMatchParams(int(nx), int(ny), int(ntheta), float(np.float32(dtheta)), float(np.float32(max_range)),
+                                       int(min_score), 1 if keep_volume else 0)
+        want = half_life is not None
+        pr = _capi.ScanMatchPrior(int(prior[0]), int(prior[1]), int(prior[2]), int(prior[3]), int(half_life) if want else 0,
+                                  1 if want else 0)
+        res = _capi.ScanMatchResult()
+        mom = _capi.ScanMatchMoments() if want else None
+        shape = self._shape                # a refused match with a prior changes nothing
+        self._shape = None
+        try:
+            check(self.ctx.lib.bl_scanmatch_match_prior(self.h, grid.h, C.byref(ls), C.byref(centre), C.byref(params), C.byref(pr),
+                                                        C.byref(res), C.byref(mom) if want else None))
+        except _capi.BotlabHipError as e:
+            if "status 2" in str(e):
+                self._shape = shape
+            raise
+        if keep_volume or want:
+            self._shape = (2 * int(ntheta) + 1, 2 * int(ny) + 1, 2 * int(nx) + 1)
+        return res, mom
 
     def volume(self):
         """Scores [dk + ntheta][dj + ny][di + nx] of the last match (int32); it must have been run with keep_volume=True."""

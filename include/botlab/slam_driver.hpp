@@ -349,6 +349,18 @@ public:
     void setScanMatching(bool on, const bl_scan_match_params_t& p) { matching_ = on; matchParams_ = p; }
     const bl_scan_match_result_t& lastScanMatch() const { return lastMatch_; }
     int scanMatchCount() const { return matches_; }
+    // (extension) The match under a motion prior, and a sub-cell corrected pose (ScanMatcherT::matchWithPrior).
+    // setScanMatchingPrior: the driver's match becomes matchWithPrior around the same centre -- the prior is centred on the pose
+    // dead reckoning gives -- with the coefficients, half_life and want_moments as given (scan_match_prior_from_sigmas forms the
+    // coefficients).  setScanMatchingSubCell(true): the corrected pose handed to the filter and chained to the next centre is
+    // bl_scanmatch_refined_pose's instead of the whole-cell one; the driver then asks for the moments itself (with no prior set: a
+    // zero prior and a half_life of 64).  lastScanMatchMoments(): of the last match that asked for them (zeros before it).
+    // correctedPose(): the pose last handed to the filter.  All unset by default, and with them unset the driver's match is
+    // bl_scanmatch_match as before; set before the first iteration.
+    void setScanMatchingPrior(const bl_scan_match_prior_t& p) { matchPriorSet_ = true; matchPrior_ = p; }
+    void setScanMatchingSubCell(bool on) { matchSubCell_ = on; }
+    const bl_scan_match_moments_t& lastScanMatchMoments() const { return lastMoments_; }
+    const Pose& correctedPose() const { return corrected_; }
 
     // The oldest queued scan can be processed once the pose source covers the time of its first ray (slam.cpp:163-188).
     bool isReadyToUpdate() const
@@ -443,6 +455,10 @@ private:
     Pose corrected_, odomAtMatch_;
     bl_scan_match_result_t lastMatch_ = bl_scan_match_result_t();
     int matches_ = 0;
+    // the match under a prior: switch and prior; sub-cell switch; the moments of the last match that asked for them
+    bool matchPriorSet_ = false, matchSubCell_ = false;
+    bl_scan_match_prior_t matchPrior_ = bl_scan_match_prior_t();
+    bl_scan_match_moments_t lastMoments_ = bl_scan_match_moments_t();
 
     bool scanMatching() const { return matching_ && !global_ && !how_.posesGiven; }
     const Pose& filterOdometry() const { return scanMatching() ? corrected_ : odomAtScan_; }
@@ -462,9 +478,21 @@ private:
         Pose centre = slam_detail::pose_of<Pose>(odomAtScan_.utime, static_cast<float>(corrected_.x + (c * dx - s * dy)),
                                                  static_cast<float>(corrected_.y + (s * dx + c * dy)),
                                                  slam_detail::wrap_pi(static_cast<float>(corrected_.theta + dth)));
-        lastMatch_ = matcher_->match(scan_, centre, grid_, matchParams_);
+        if (matchPriorSet_ || matchSubCell_) {
+            bl_scan_match_prior_t prior = matchPrior_;
+            if (!matchPriorSet_) prior.half_life = 64;
+            if (matchSubCell_) prior.want_moments = 1;
+            lastMatch_ = matcher_->matchWithPrior(scan_, centre, grid_, matchParams_, prior, &lastMoments_);
+        } else {
+            lastMatch_ = matcher_->match(scan_, centre, grid_, matchParams_);
+        }
         ++matches_;
-        corrected_ = slam_detail::pose_of<Pose>(odomAtScan_.utime, lastMatch_.pose.x, lastMatch_.pose.y, lastMatch_.pose.theta);
+        bl_pose_xyt_t to = lastMatch_.pose;
+        if (matchSubCell_) {
+            const bl_pose_xyt_t c = pose_in(centre);
+            bl_scanmatch_refined_pose(&lastMatch_, &lastMoments_, &c, grid_.metersPerCell(), matchParams_.dtheta, &to);
+        }
+        corrected_ = slam_detail::pose_of<Pose>(odomAtScan_.utime, to.x, to.y, to.theta);
         odomAtMatch_ = odomAtScan_;
     }
 

@@ -309,8 +309,9 @@ int bl_pf_debug_last(bl_pf* pf, int32_t* resample_idx, int32_t* likelihood_half_
  *   Best candidate: the highest score; ties go to the smallest di*di + dj*dj, then the smallest |dk|, then the smallest dk, dj,
  *     di -- one 64-bit key per candidate, so the maximum does not depend on the order of reduction.  An empty or all-free map
  *     returns the centre.
- *   Not in it: sub-cell refinement, a covariance estimate, a motion prior.  Windows beyond the limits below, up to the whole
- *   map, are bl_scanmatch_match_wide's (further down), which prunes. */
+ *   A motion prior, a covariance estimate and a sub-cell pose are bl_scanmatch_match_prior's ("correlative scan matching with a
+ *   prior", below the wide match).  Windows beyond the limits below, up to the whole map, are
+ *   bl_scanmatch_match_wide's (further down), which prunes. */
 typedef struct bl_scan_match_params_t {
     int32_t nx, ny;          /* half window in cells: shifts di in [-nx, nx], dj in [-ny, ny];   0 <= nx, ny <= 64   */
     int32_t ntheta;          /* half window in heading steps: dk in [-ntheta, ntheta];           0 <= ntheta <= 180  */
@@ -383,6 +384,115 @@ int bl_scanmatch_match_wide(bl_scanmatch* sm, const bl_grid* map, const bl_lidar
                             const bl_scan_match_wide_params_t* params, bl_scan_match_result_t* result);
 /* of the last wide match that was not refused; BL_ERR_STATE before the first */
 int bl_scanmatch_wide_stats(const bl_scanmatch* sm, bl_scan_match_wide_stats_t* out);
+
+/* Correlative scan matching with a prior: bl_scanmatch_match's definition -- valid rays, headings, endpoint cells,
+ * score(di, dj, dk), the window limits (nx, ny <= 64, ntheta <= 180, at most 4096 valid rays; a score is at most
+ * 4096 * 127 < 2^19) -- word for word, and on top of it a motion prior on the candidate, a weighted second-moment summary of the
+ * whole window (a covariance) and a sub-cell offset of the winner.  Everything that is compared or summed is an integer, so the
+ * result does not depend on the launch shape or on the order of any reduction.  The numpy restatement is
+ * tests/scan_match_prior_model.py.
+ *   Prior, centred on the centre pose c, four integers in 1/256 of a score unit:
+ *       pen(di, dj, dk) = (a_xx di^2 + 2 a_xy di dj + a_yy dj^2 + a_tt dk^2) >> 8,  formed in int64.
+ *     Limits: 0 <= a_xx, a_yy, a_tt <= 32767, |a_xy| <= 32767, a_xy^2 <= a_xx a_yy (the form is then never negative; the sum
+ *     stays below 2^31 and pen below 2^23).  Anything else is BL_ERR_ARG.
+ *   Objective: obj = score - pen,  -2^23 < obj < 2^19.
+ *   Best candidate: the highest obj, then bl_scanmatch_match's order exactly (smallest di*di + dj*dj, |dk|, dk, dj, di): one
+ *     64-bit key with obj + 2^23 in the high word and that order's low word.  result.score is the RAW score of that candidate,
+ *     accepted = score >= min_score, ties counts the candidates sharing the best OBJECTIVE, score_centre is the centre's score
+ *     (its pen is 0).  With all four coefficients 0 the result equals bl_scanmatch_match's byte for byte.  On an empty or
+ *     all-free map obj = -pen and the centre wins by the key alone.
+ *   Weights.  half_life, 1 <= half_life <= 2^20, is the number of score units by which the objective must fall for a
+ *     candidate's weight to halve.  With d = best_obj - obj >= 0, all divisions integer divisions:
+ *       e = d / half_life,  f = d - e half_life,  i = (64 f) / half_life,  w = (e >= 21) ? 0 : (BL_SM_EXP2[i] >> e),
+ *     BL_SM_EXP2[i] = floor(2^20 2^(-i/64)), i = 0 .. 63 (below).  The best candidate has w = 2^20.
+ *   Moments: ten int64 sums over EVERY candidate of the window with di, dj, dk as the coordinates: s0 = sum w, sx = sum w di,
+ *     sy, st, sxx = sum w di di, sxy, syy, sxt, syt, stt.  At most 129 * 129 * 361 < 2^23 candidates * 2^20 * 180^2 < 2^58.
+ *   Sub-cell offset, one exact fraction (num, den) per axis (x: di, y: dj, t: dk).  If the axis' half window is at least 1 and
+ *     the best candidate is not on that axis' window edge, with o-, o0, o+ the objectives at best - 1, best, best + 1 along the
+ *     axis: den = 2 (2 o0 - o- - o+), num = o+ - o- (the vertex of the parabola through the three); if den == 0, or on the edge,
+ *     or with a half window of 0, the offset is (0, 1).  o0 is the maximum, so |num / den| <= 1/2. */
+#define BL_SM_EXP2_VALUES \
+    1048576, 1037280, 1026107, 1015053, 1004119, 993303, 982603, 972019, \
+    961548, 951190, 940944, 930808, 920781, 910863, 901051, 891345, \
+    881743, 872245, 862849, 853555, 844360, 835265, 826267, 817367, \
+    808562, 799852, 791236, 782713, 774282, 765941, 757690, 749529, \
+    741455, 733468, 725567, 717751, 710019, 702371, 694805, 687321, \
+    679917, 672593, 665348, 658181, 651091, 644077, 637139, 630276, \
+    623487, 616770, 610126, 603554, 597053, 590621, 584259, 577965, \
+    571740, 565581, 559488, 553462, 547500, 541602, 535768, 529997
+static const int32_t BL_SM_EXP2[64] = { BL_SM_EXP2_VALUES };
+#define BL_SM_MAX_COEFF 32767
+#define BL_SM_MAX_HALF_LIFE (1 << 20)
+typedef struct bl_scan_match_prior_t {
+    int32_t a_xx, a_xy, a_yy, a_tt;  /* the prior, 1/256 score unit per cell^2 (a_tt: per heading step^2); all 0: no prior */
+    int32_t half_life;               /* the weights' temperature; read only when want_moments != 0                          */
+    int32_t want_moments;            /* != 0: fill the moments (stores the objective volume and runs two more kernels)      */
+} bl_scan_match_prior_t;     /* 24 bytes */
+typedef struct bl_scan_match_moments_t {
+    int64_t s0, sx, sy, st, sxx, sxy, syy, sxt, syt, stt;
+    int32_t best_obj;        /* objective of the best candidate */
+    int32_t pen_best;        /* its penalty: result.score == best_obj + pen_best */
+    int32_t sub_num[3];      /* sub-cell offset of the best candidate along x, y, t: sub_num[a] / sub_den[a] of a cell / step */
+    int32_t sub_den[3];      /* never 0 */
+} bl_scan_match_moments_t;   /* 112 bytes */
+/* One stream-ordered sequence on the ctx stream (rasteriser, scoring, result; with want_moments the moments pass and its
+ * reduction behind them), one synchronisation to hand the results back.  want_moments == 0: half_life is not read, moments may
+ * be NULL (it is left alone), no volume is stored unless params->keep_volume asks.  After a call with keep_volume or
+ * want_moments bl_scanmatch_volume returns the OBJECTIVE volume (with a zero prior: the scores).  BL_ERR_ARG -- a limit of
+ * bl_scanmatch_match, a coefficient out of range, a_xy^2 > a_xx a_yy, want_moments with half_life outside 1 .. 2^20 or with
+ * moments == NULL, a null pointer -- changes nothing: a kept volume stays. */
+int bl_scanmatch_match_prior(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* centre,
+                             const bl_scan_match_params_t* params, const bl_scan_match_prior_t* prior,
+                             bl_scan_match_result_t* result, bl_scan_match_moments_t* moments);
+/* Two helpers for callers, in plain double: not part of the byte-equality contract (the library exports the same two functions
+ * for bindings).
+ * The weighted mean and covariance of the window.  mean[3]: the offset of the weighted mean from the centre pose, x and y in
+ * metres, theta in radians (sx / s0 * meters_per_cell, ..., st / s0 * dtheta).  cov[6] = xx, xy, yy, xt, yt, tt:
+ * cov_ab = (s_ab / s0 - (s_a / s0) (s_b / s0)) * scale_a scale_b with scale = meters_per_cell for x and y, dtheta for t.
+ * s0 >= 2^20 after any match; a record with s0 <= 0 (never filled) gives zeros. */
+#ifndef BL_SM_HELPER
+#define BL_SM_HELPER static inline
+#endif
+BL_SM_HELPER void bl_scanmatch_covariance(const bl_scan_match_moments_t* m, double meters_per_cell, double dtheta, double* mean,
+                                          double* cov)
+{
+    int i;
+    for (i = 0; i < 3; ++i) mean[i] = 0.0;
+    for (i = 0; i < 6; ++i) cov[i] = 0.0;
+    if (m->s0 <= 0) return;
+    {
+        const double s0 = (double)m->s0, mx = (double)m->sx / s0, my = (double)m->sy / s0, mt = (double)m->st / s0;
+        mean[0] = mx * meters_per_cell; mean[1] = my * meters_per_cell; mean[2] = mt * dtheta;
+        cov[0] = ((double)m->sxx / s0 - mx * mx) * (meters_per_cell * meters_per_cell);
+        cov[1] = ((double)m->sxy / s0 - mx * my) * (meters_per_cell * meters_per_cell);
+        cov[2] = ((double)m->syy / s0 - my * my) * (meters_per_cell * meters_per_cell);
+        cov[3] = ((double)m->sxt / s0 - mx * mt) * (meters_per_cell * dtheta);
+        cov[4] = ((double)m->syt / s0 - my * mt) * (meters_per_cell * dtheta);
+        cov[5] = ((double)m->stt / s0 - mt * mt) * (dtheta * dtheta);
+    }
+}
+/* The matched pose moved by the sub-cell offsets: x = (float)(c.x + (di + num_x / den_x) * meters_per_cell), y likewise,
+ * theta = the float (float)(c.theta + (dk + num_t / den_t) * dtheta) wrapped into [-pi, pi] as wrap_to_pi does (compared with
+ * the double pi, stepped by the double 2 pi, narrowed on every step); utime = result's.  A match that was not accepted gives
+ * result->pose, i.e. the centre. */
+BL_SM_HELPER void bl_scanmatch_refined_pose(const bl_scan_match_result_t* result, const bl_scan_match_moments_t* m,
+                                            const bl_pose_xyt_t* centre, double meters_per_cell, double dtheta, bl_pose_xyt_t* out)
+{
+    *out = result->pose;
+    if (!result->accepted) return;
+    {
+        const double pi = 3.14159265358979323846;
+        const double fx = (double)m->sub_num[0] / (double)m->sub_den[0], fy = (double)m->sub_num[1] / (double)m->sub_den[1];
+        const double ft = (double)m->sub_num[2] / (double)m->sub_den[2];
+        float th = (float)((double)centre->theta + ((double)result->dk + ft) * dtheta);
+        int guard = 0;
+        out->x = (float)((double)centre->x + ((double)result->di + fx) * meters_per_cell);
+        out->y = (float)((double)centre->y + ((double)result->dj + fy) * meters_per_cell);
+        while ((double)th < -pi && guard++ < 64) th = (float)((double)th + 2.0 * pi);
+        while ((double)th > pi && guard++ < 64) th = (float)((double)th - 2.0 * pi);
+        out->theta = th;
+    }
+}
 
 /* ------------------------------------------------------------------ ObstacleDistanceGrid  (src/planning/obstacle_distance_grid.hpp:28-96) */
 int bl_dist_create(bl_ctx* ctx, bl_dist** out);
