@@ -32,7 +32,8 @@
 #define A2_INF 0xFFFFu
 #define A2_MAXR 6
 
-template <int KLV, int PLV> struct a2cfg {
+template <int KLV, int PLV, bool CORUN = false> struct a2cfg {
+    static constexpr bool CO_RUNS = CORUN;                   // the form that runs beside the particle filter's workgroups (wave priority: k_astar2)
     static constexpr int KSLOTS = 1 << (KLV + 1);            // key slots in LDS
     static constexpr int PLN = (1 << (PLV + 1)) - 1;         // payload entries in LDS (entry PLN: dummy)
     static constexpr int KEY_BYTES = KSLOTS * 2;
@@ -48,7 +49,7 @@ template <int KLV, int PLV> struct a2cfg {
     static_assert(PLV >= FD + 5 && PLV <= FD + 9, "payload tier boundary must fall into the third round");
 };
 typedef a2cfg<14, 13> a2_big;       // 64 KB keys (32 767 entries) + 64 KB payloads (16 383): a search that has a CU to itself
-typedef a2cfg<12, 11> a2_small;     // 16 KB keys (8 191) + 16 KB payloads (4 095): beside the particle filter's workgroups
+typedef a2cfg<12, 11, true> a2_small;    // 16 KB keys (8 191) + 16 KB payloads (4 095): beside the particle filter's workgroups
 typedef a2cfg<11, 6> a2_test;       // tests: every storage tier within a few thousand entries
 
 typedef __attribute__((address_space(3))) unsigned short a2_lds_u16;
@@ -597,7 +598,9 @@ __global__ __launch_bounds__(192) void k_astar2(astar_args a)
     a2_g_u16* const gk = (a2_g_u16*)((char*)a.heap + 4ll * a.heap_cap);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    __builtin_amdgcn_s_setprio(3);
+    // a search is a latency-bound chain of lone waves: it wins issue arbitration (priority 3).  Not so the co-running form on a grid
+    // whose filter kernel stages the whole map in LDS: there k_mcl_main is what a SLAM step waits for and raises its own waves.
+    if (!(C::CO_RUNS && a2_yields(a.W, a.H))) __builtin_amdgcn_s_setprio(3);
     astar_result res; res.status = ASTAR_ST_NOPATH; res.path_len = 0; res.pops = 0; res.pushes = 0;
     for (int q = 0; q < 6; ++q) res.stamps[q] = 0;
     res.path_off = 0;

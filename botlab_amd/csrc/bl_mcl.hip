@@ -887,6 +887,13 @@ __global__ __launch_bounds__(MCL_BLOCK) void k_mcl_main(mcl_args a)
     map_window win = {0, 0, 0, 0, 0};
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // The replanner's searches run beside this kernel, three wavefronts on each of a few CUs.  At a higher priority than this
+    // kernel's waves they took a quarter of the issue slots of their SIMDs, and the workgroups there ended 10 us behind the rest of
+    // the launch (every fifth launch).  On the grids staged whole in LDS (200 x 200: short searches, lanes with time to spare) these
+    // waves go first and the co-running search forms stay at the default priority (a2_yields, bl_planning.hip).  On larger grids the
+    // searches are thousands of pops and the step waits for them as much as for this kernel: the same change cost 0.5 - 0.8 % there
+    // (profiles/replan_slots_other_configs.json), so nothing changes there.
+    if (MAP_MODE == 1) __builtin_amdgcn_s_setprio(3);
     MCL_STAMP(0);
 
     // Two regions in one launch (see "Whole rounds" in pf_launch_main): workgroups [0, main_blocks) take MCL_BLOCK >> split_log2

@@ -1946,6 +1946,8 @@ struct astar_result { int status; int path_len; long long pops; long long pushes
 #define AH_COST_LDS 8000
 #define AH_LDS_BYTES ((AH_LDS + 1) * 8 + AH_COST_LDS * 4)
 #define AH_LDS_SMALL 4095
+// a grid whose filter kernel stages the whole map in LDS (bl_mcl.hip, MCL_WIN_SMALL_BYTES: the framed image within 64 KB)
+__device__ __forceinline__ bool a2_yields(int W, int H) { return (long long)W * H <= 60 * 1024; }
 #define AH_COST_LDS_SMALL 2000
 #define AH_LDS_SMALL_BYTES ((AH_LDS_SMALL + 1) * 8 + AH_COST_LDS_SMALL * 4)
 #define AH_MAX_DIM 32767
@@ -2230,7 +2232,9 @@ __global__ __launch_bounds__(64) void k_astar(astar_args a)
     int2* g_heap = a.heap;
     __shared__ long long s_path[40];                    // heap_adjust_fused: the entries a walk passes, by heap level
     const int lane = threadIdx.x;
-    __builtin_amdgcn_s_setprio(3);          // a lone latency-bound wave: win issue arbitration against co-resident kernels
+    // a lone latency-bound wave: win issue arbitration against co-resident kernels -- but for the small form, which runs beside
+    // k_mcl_main (as k_astar2<a2_small>, bl_astar2.h)
+    if (!(LDSN == AH_LDS_SMALL && a2_yields(a.W, a.H))) __builtin_amdgcn_s_setprio(3);
     astar_result res; res.status = ASTAR_ST_NOPATH; res.path_len = 0; res.pops = 0; res.pushes = 0;
     for (int q = 0; q < 6; ++q) res.stamps[q] = 0;
     res.path_off = 0;
