@@ -64,6 +64,41 @@ class PfAdaptiveState(C.Structure):
     _fields_ = [("active", C.c_int32), ("next", C.c_int32), ("bins", C.c_uint32), ("k_sat", C.c_uint32), ("counts", C.c_uint64)]
 
 
+class PfClusterParams(C.Structure):
+    """bl_pf_cluster_params_t: bins and result size of bl_pf_clusters (16 bytes)."""
+    _fields_ = [("bin_xy", C.c_double), ("theta_bins", C.c_int32), ("max_clusters", C.c_int32)]
+
+
+class I128(C.Structure):
+    """bl_i128_t: a signed 128-bit integer, hi * 2^64 + lo."""
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64)]
+
+    def value(self):
+        return (int(self.hi) << 64) + int(self.lo)
+
+
+PF_MAX_CLUSTERS = 64
+PF_CLUSTER_SUMS = ("sx", "sy", "sxx", "syy", "sxy", "sc", "ss")
+
+
+class PfCluster(C.Structure):
+    """bl_pf_cluster_t: one cluster of the cloud, exact integer sums (144 bytes)."""
+    _fields_ = ([("count", C.c_uint64), ("units", C.c_uint64)] + [(n, I128) for n in PF_CLUSTER_SUMS] +
+                [("anchor_ix", C.c_int32), ("anchor_iy", C.c_int32), ("anchor_it", C.c_int32), ("pad", C.c_int32)])
+
+
+class PfClusters(C.Structure):
+    """bl_pf_clusters_t: what bl_pf_clusters reports (9240 bytes)."""
+    _fields_ = [("num_clusters", C.c_uint64), ("units_sum", C.c_uint64), ("active", C.c_int32), ("pad", C.c_int32),
+                ("clusters", PfCluster * PF_MAX_CLUSTERS)]
+
+
+class PfClusterPose(C.Structure):
+    """bl_pf_cluster_pose_t: a cluster's share, mean, covariance and heading in plain double (64 bytes)."""
+    _fields_ = [("share", C.c_double), ("mean_x", C.c_double), ("mean_y", C.c_double), ("var_x", C.c_double), ("var_y", C.c_double),
+                ("cov_xy", C.c_double), ("theta", C.c_double), ("theta_resultant", C.c_double)]
+
+
 class ScanMatchParams(C.Structure):
     """bl_scan_match_params_t: the window of a correlative scan match (28 bytes)."""
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("ntheta", C.c_int32), ("dtheta", C.c_float), ("max_range", C.c_float),
@@ -200,6 +235,7 @@ assert C.sizeof(ScanMatchWideParams) == 32 and C.sizeof(ScanMatchWideStats) == 4
 assert C.sizeof(ScanMatchPrior) == 24 and C.sizeof(ScanMatchMoments) == 112
 assert C.sizeof(PfRecoveryParams) == 48 and C.sizeof(PfRecoveryState) == 56
 assert C.sizeof(PfAdaptiveParams) == 40 and C.sizeof(PfAdaptiveState) == 24
+assert C.sizeof(PfClusterParams) == 16 and C.sizeof(PfCluster) == 144 and C.sizeof(PfClusters) == 9240 and C.sizeof(PfClusterPose) == 64
 
 class MotionPlannerState(C.Structure):
     """bl_motion_planner_t: the MotionPlanner members plan_path_to_frontier reads (motion_planner.hpp:153-165)."""
@@ -256,6 +292,8 @@ SIGNATURES = {
     "bl_pf_recovery_state": (C.c_int, [_vp, _P(PfRecoveryState)]),
     "bl_pf_set_adaptive": (C.c_int, [_vp, _P(PfAdaptiveParams)]),
     "bl_pf_adaptive_state": (C.c_int, [_vp, _P(PfAdaptiveState)]),
+    "bl_pf_clusters": (C.c_int, [_vp, _P(PfClusterParams), _P(PfClusters), _vp]),
+    "bl_pf_cluster_pose": (C.c_int, [_P(PfCluster), C.c_uint64, _P(PfClusterParams), _P(PfClusterPose)]),
     "bl_pf_set_particles": (C.c_int, [_vp, _vp, _vp]),
     "bl_pf_get_particles": (C.c_int, [_vp, _vp]),
     "bl_pf_set_noise_seed": (C.c_int, [_vp, C.c_uint64]),

@@ -30,6 +30,7 @@
 #include <new>
 
 #include <hip/hip_ext.h>
+#define BL_PF_HELPER                   // this translation unit defines the header's bl_pf_cluster_pose with external linkage (bindings call it)
 #include "bl_internal.h"
 #include "bl_mcl_finish.h"
 
@@ -162,6 +163,8 @@ struct bl_pf {
     uint32_t* gl_list; size_t gl_list_cap;     // eligible cell indices, row-major order
     void* sp_parts;                            // [SPREAD_MAX_BLOCKS] spread_part
     void* sp_out;                              // spread_dev
+    // pose hypotheses (bl_pf_clusters, bl_pf_cluster.h): one allocation sized for the capacity, made on first use
+    char* cl_mem;
     // kidnapped-robot recovery (bl_pf_set_recovery): parameters, the eligible list of its own, the update counter u, the device
     // side; sensed: rec[cur] carries sensor-model weights (the fold's condition)
     bool rc_on, sensed;
@@ -1733,7 +1736,7 @@ extern "C" void bl_pf_destroy(bl_pf* pf)
     if (!pf->rec_external) { if (pf->rec[0]) (void)hipFree(pf->rec[0]); if (pf->rec[1]) (void)hipFree(pf->rec[1]); }
     void* ptrs[] = {pf->fin_wild, pf->tile_partials, pf->fin_recs, pf->fin_tabs, pf->fin_sync, pf->prefix, pf->parent, pf->state, pf->partials, pf->block_sums, pf->dbg_idx, pf->dbg_like,
                     pf->d_noise, pf->d_export, pf->sh_xchg, pf->sh_tab, pf->sh_fin, pf->sh_flags, pf->sh_peers_dev, pf->strict_recs, pf->strict_starts,
-                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out, pf->rc_list, pf->rc_dev, pf->ad_table};
+                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out, pf->cl_mem, pf->rc_list, pf->rc_dev, pf->ad_table};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (pf->ad_hcount) { (void)hipHostFree(pf->ad_hcount); (void)hipEventDestroy(pf->ad_ev); }
     delete pf->ad_wfloor;
@@ -3572,6 +3575,71 @@ extern "C" int bl_pf_spread(bl_pf* pf, bl_pf_spread_t* out)
     // S^2 / sum(u^2), each operand rounded once to double (the 128-bit square sum by the host's correctly rounded conversion)
     const unsigned __int128 q = ((unsigned __int128)h.out.units_sq_hi << 64) | h.out.units_sq_lo;
     out->n_eff = ((double)h.out.units_sum * (double)h.out.units_sum) / (double)q;
+    return BL_OK;
+}
+
+// ---------------------------------------------------------------- pose hypotheses: the clusters of the cloud
+#include "bl_pf_cluster.h"
+
+static size_t pfc_slots(int n)
+{
+    size_t slots = 1024;
+    while (slots < 2 * (size_t)n) slots <<= 1;
+    return slots;
+}
+
+extern "C" int bl_pf_clusters(bl_pf* pf, const bl_pf_cluster_params_t* params, bl_pf_clusters_t* out, int32_t* labels)
+{
+    BL_CHECK_ARG(pf != nullptr && params != nullptr && out != nullptr);
+    if (!(params->bin_xy > 0.0 && params->bin_xy < HUGE_VAL) || params->theta_bins < 1 || params->theta_bins > 4096 ||
+        params->max_clusters < 1 || params->max_clusters > BL_PF_MAX_CLUSTERS) {
+        bl_set_error("cluster parameters: need bin_xy > 0 and finite, 1 <= theta_bins <= 4096, 1 <= max_clusters <= %d", BL_PF_MAX_CLUSTERS);
+        return BL_ERR_ARG;
+    }
+    if (!pf->initialized || pf->pending_end) { bl_set_error("filter not initialised or update pending"); return BL_ERR_STATE; }
+    if (pf->sh_world > 1) { bl_set_error("bl_pf_clusters needs the whole record on this device (composed shard)"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(pf->ctx->device));
+    hipStream_t st = pf->ctx->stream;
+    // one allocation for the capacity: [result][counters][table][bins][slot_id][parent][root][clid][clist][rank][labels]
+    const size_t cap = (size_t)pf->cap, cap_slots = pfc_slots(pf->cap);
+    const size_t off_counters = (sizeof(bl_pf_clusters_t) + 15) & ~(size_t)15, off_table = off_counters + 16;
+    const size_t off_bins = off_table + cap_slots * 8, off_slot_id = off_bins + cap * sizeof(pfc_bin);
+    const size_t off_words = off_slot_id + cap_slots * 4, total = off_words + 6 * cap * 4;
+    if (!pf->cl_mem) BL_HIP(hipMalloc((void**)&pf->cl_mem, total));
+    const int N = pf->N, T = params->theta_bins;
+    const size_t slots = pfc_slots(N);
+    pfc_dev d;
+    bl_pf_clusters_t* d_out = (bl_pf_clusters_t*)pf->cl_mem;
+    d.counters = (unsigned int*)(pf->cl_mem + off_counters);
+    d.table = (unsigned long long*)(pf->cl_mem + off_table);
+    d.bins = (pfc_bin*)(pf->cl_mem + off_bins);
+    d.slot_id = (unsigned int*)(pf->cl_mem + off_slot_id);
+    unsigned int* words = (unsigned int*)(pf->cl_mem + off_words);
+    d.parent = words; d.root = words + cap; d.clid = words + 2 * cap; d.clist = words + 3 * cap;
+    d.rank = (int*)(words + 4 * cap);
+    int32_t* d_labels = (int32_t*)(words + 5 * cap);
+    d.mask = (unsigned int)(slots - 1);
+    const double xy_scale = 1024.0 / params->bin_xy, th_scale = (double)T / 6.283185307179586;
+    const float4* rec = pf->rec[pf->cur];
+    const unsigned int wg_particles = (unsigned int)((N + PFC_PER_WG - 1) / PFC_PER_WG), wg_bins = (unsigned int)((N + PFC_WG - 1) / PFC_WG);
+    // the counters and the table lie side by side: a second call never sees the first call's keys
+    BL_HIP(hipMemsetAsync(d.counters, 0, 16 + slots * 8, st));
+    hipLaunchKernelGGL(k_pfc_bins<0>, dim3(wg_particles), dim3(PFC_WG), 0, st, rec, N, xy_scale, th_scale, T, d);
+    hipLaunchKernelGGL(k_pfc_bins<1>, dim3(wg_particles), dim3(PFC_WG), 0, st, rec, N, xy_scale, th_scale, T, d);
+    // (the bin count stays on the device: the three launches over the bins are sized for as many bins as particles)
+    hipLaunchKernelGGL(k_pfc_link, dim3(wg_bins), dim3(PFC_WG), 0, st, T, d);
+    hipLaunchKernelGGL(k_pfc_roots, dim3(wg_bins), dim3(PFC_WG), 0, st, d);
+    hipLaunchKernelGGL(k_pfc_fold, dim3(wg_bins), dim3(PFC_WG), 0, st, d);
+    hipLaunchKernelGGL(k_pfc_select, dim3(1), dim3(PFC_SEL_WG), 0, st, (int)params->max_clusters, N, d, d_out);
+    if (labels) hipLaunchKernelGGL(k_pfc_labels, dim3(wg_bins), dim3(PFC_WG), 0, st, rec, N, xy_scale, th_scale, T, d, d_labels);
+    BL_HIP(hipGetLastError());
+    // the result lands in a buffer of the library's: out and labels change only once everything has succeeded
+    std::vector<char> h(sizeof(bl_pf_clusters_t) + (labels ? (size_t)N * sizeof(int32_t) : 0));
+    BL_HIP(hipMemcpyAsync(h.data(), d_out, sizeof(bl_pf_clusters_t), hipMemcpyDeviceToHost, st));
+    if (labels) BL_HIP(hipMemcpyAsync(h.data() + sizeof(bl_pf_clusters_t), d_labels, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BL_HIP(hipStreamSynchronize(st));
+    memcpy(out, h.data(), sizeof(bl_pf_clusters_t));
+    if (labels) memcpy(labels, h.data() + sizeof(bl_pf_clusters_t), (size_t)N * sizeof(int32_t));
     return BL_OK;
 }
 

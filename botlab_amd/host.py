@@ -291,6 +291,44 @@ class ParticleFilter:
         d["position_std"], d["theta_std"] = spread_stds(d)
         return d
 
+    def clusters(self, bin_xy, theta_bins, max_clusters, labels=False):
+        """Pose hypotheses (bl_pf_clusters): the connected components of the occupied (bin_xy, bin_xy, 2 pi / theta_bins) bins,
+        heaviest first.  Returns a dict of num_clusters, units_sum, active, params and clusters: a list of min(num_clusters,
+        max_clusters) dicts of count, units, the exact sums sx, sy, sxx, syy, sxy, sc, ss (Python integers) and anchor (ix, iy, it);
+        with labels=True also labels, one int32 per particle: the rank of its cluster, -1 beyond max_clusters.  bin_xy,
+        theta_bins and any threshold on a cluster's share are untuned knobs."""
+        p = _capi.PfClusterParams(float(bin_xy), int(theta_bins), int(max_clusters))
+        out = _capi.PfClusters()
+        lab = np.empty(self._counts()[0], np.int32) if labels else None
+        check(self.ctx.lib.bl_pf_clusters(self.h, C.byref(p), C.byref(out), lab.ctypes.data if labels else None))
+        cl = []
+        for k in range(min(int(out.num_clusters), int(max_clusters))):
+            c = out.clusters[k]
+            e = {"count": int(c.count), "units": int(c.units), "anchor": (int(c.anchor_ix), int(c.anchor_iy), int(c.anchor_it))}
+            e.update({n: getattr(c, n).value() for n in _capi.PF_CLUSTER_SUMS})
+            cl.append(e)
+        d = {"num_clusters": int(out.num_clusters), "units_sum": int(out.units_sum), "active": int(out.active), "clusters": cl,
+             "params": (float(bin_xy), int(theta_bins), int(max_clusters)), "raw": out}
+        if labels:
+            d["labels"] = lab
+        return d
+
+    @staticmethod
+    def cluster_pose(result, k=0):
+        """bl_pf_cluster_pose of cluster k of a clusters() result: dict of share, mean_x, mean_y, var_x, var_y, cov_xy, theta,
+        theta_resultant and the derived position_std and theta_std (spread()'s two formulas on the cluster's own moments); None for
+        a cluster of 0 units or a rank the result does not hold."""
+        if not 0 <= k < len(result["clusters"]):
+            return None
+        p = _capi.PfClusterParams(*result["params"])
+        out = _capi.PfClusterPose()
+        if not _capi.load().bl_pf_cluster_pose(C.byref(result["raw"].clusters[k]), C.c_uint64(result["units_sum"]), C.byref(p), C.byref(out)):
+            return None
+        d = {f: getattr(out, f) for f, _ in _capi.PfClusterPose._fields_}
+        # (a resultant rounded above 1 -- every heading in one direction -- is a deviation of 0)
+        d["position_std"], d["theta_std"] = spread_stds(dict(d, theta_resultant=min(1.0, d["theta_resultant"])))
+        return d
+
     def setRecovery(self, grid, distances=None, minDistance=0.0, alphaSlow=RECOVERY_ALPHA_SLOW, alphaFast=RECOVERY_ALPHA_FAST,
                     ratio=RECOVERY_RATIO, maxFraction=RECOVERY_MAX_FRACTION, seed=None):
         """Kidnapped-robot recovery (augmented MCL, bl_pf_set_recovery): while the fast average of the mean particle weight falls below

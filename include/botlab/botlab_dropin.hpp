@@ -342,6 +342,30 @@ public:
         check(bl_pf_spread(h_, &s), "bl_pf_spread");
         return s;
     }
+    // (extension) pose hypotheses: the clusters of the cloud, heaviest first (botlab_hip.h, bl_pf_clusters).  labels, if given, takes
+    // one rank per particle of the current record (-1 beyond params.max_clusters).  The defaults are AMCL's histogram (0.5 m, 10
+    // degrees): like any share threshold put on the result they are untuned knobs.
+    static bl_pf_cluster_params_t defaultClusterParams()
+    {
+        bl_pf_cluster_params_t q;
+        q.bin_xy = 0.5; q.theta_bins = 36; q.max_clusters = 8;
+        return q;
+    }
+    bl_pf_clusters_t clusters(const bl_pf_cluster_params_t& params, std::vector<int32_t>* labels = nullptr) const
+    {
+        bl_pf_clusters_t c;
+        if (labels) labels->resize(static_cast<std::size_t>(numParticles()));
+        check(bl_pf_clusters(h_, &params, &c, labels ? labels->data() : nullptr), "bl_pf_clusters");
+        return c;
+    }
+    // the heaviest cluster's pose, covariance and share of the weight (bl_pf_cluster_pose); false when it carries no weight
+    bool heaviestCluster(const bl_pf_cluster_params_t& params, bl_pf_cluster_pose_t* pose) const
+    {
+        bl_pf_cluster_params_t one = params;
+        one.max_clusters = 1;
+        const bl_pf_clusters_t c = clusters(one);
+        return c.num_clusters > 0 && bl_pf_cluster_pose(&c.clusters[0], c.units_sum, &one, pose) != 0;
+    }
     Pose updateFilter(const Pose& odometry, const Lidar& laser, const OccupancyGrid& map)   // particle_filter.cpp:37-52
     {
         bl_lidar_t v = lidar_view(laser);

@@ -319,6 +319,21 @@ public:
     void setGlobalLocalizationByScanMatch(const bl_scan_match_wide_params_t& p) { globalMatch_ = true; globalMatchParams_ = p; }
     bool globalLocalizedByScanMatch() const { return globalMatched_; }
     const bl_scan_match_result_t& globalScanMatch() const { return globalMatchResult_; }     // of the first scan (zeros before it)
+    // (extension) Global localization judged by the heaviest pose hypothesis (ParticleFilterT::heaviestCluster, bl_pf_clusters)
+    // instead of by the whole cloud: while the driver is searching, an iteration counts as converged when the heaviest cluster
+    // holds at least minShare of the weight and that cluster's own position and heading deviations -- the two formulas above, on
+    // the cluster's moments -- are within the thresholds; a second mode that keeps some weight no longer holds the search up.  Until
+    // then SLAM_POSE carries the heaviest cluster's pose (the mean of a multi-modal cloud lies between its modes).  On convergence the
+    // filter is started again at the cluster's pose (initializeFilterAtPose, as after an accepted scan match), and from then on the
+    // driver is the plain driver.  minShare and the bins of `params` are untuned knobs.  Off by default, and with it off nothing
+    // the driver does changes; set before the first iteration.
+    void setGlobalLocalizationByCluster(const bl_pf_cluster_params_t& params, double minShare)
+    {
+        globalCluster_ = true;
+        globalClusterParams_ = params;
+        globalClusterMinShare_ = minShare;
+    }
+    const bl_pf_cluster_pose_t& globalCluster() const { return globalClusterPose_; }        // of the last searching iteration (zeros before it)
     // (extension) Kidnapped-robot recovery (ParticleFilterT::enableRecovery, default parameters): in localization-only mode (map from a
     // file, not action-only) recovery is turned on over the map as it stands once the filter is localised -- when it starts from a
     // pose, at the start; with global localization, at the first converged iteration.  From then on every iteration is the
@@ -385,6 +400,7 @@ public:
         if (globalSearching()) {                        // global localization, not converged yet: filter only, the map is left alone
             before_ = now_;
             now_ = pf_.updateFilter(odomAtScan_, scan_, grid_);
+            if (globalCluster_) { searchByCluster(); return; }
             announce();
             globalConverged_ = spreadConverged();
             if (globalConverged_) {
@@ -442,6 +458,11 @@ private:
     bool globalMatch_ = false, globalMatched_ = false;
     bl_scan_match_wide_params_t globalMatchParams_ = bl_scan_match_wide_params_t();
     bl_scan_match_result_t globalMatchResult_ = bl_scan_match_result_t();
+    // global localization by the heaviest cluster: switch, bins, the share it must hold, the last searching iteration's cluster
+    bool globalCluster_ = false;
+    bl_pf_cluster_params_t globalClusterParams_ = bl_pf_cluster_params_t();
+    double globalClusterMinShare_ = 0.0;
+    bl_pf_cluster_pose_t globalClusterPose_ = bl_pf_cluster_pose_t();
     bool kidnap_ = false, kidnapOn_ = false;     // kidnapped-robot recovery: switch, turned on
     int heldMaps_ = 0;
     bool adaptive_ = false, adaptiveOn_ = false; // adaptive particle count: switch, turned on
@@ -528,6 +549,30 @@ private:
         const double pos = std::sqrt(h + std::sqrt(0.25 * (s.var_x - s.var_y) * (s.var_x - s.var_y) + s.cov_xy * s.cov_xy));
         const double heading = s.theta_resultant > 0.0 ? std::sqrt(-2.0 * std::log(s.theta_resultant)) : HUGE_VAL;
         return pos <= globalPosTol_ && heading <= globalHeadingTol_;
+    }
+
+    // One searching iteration under setGlobalLocalizationByCluster, behind its updateFilter: the pose published is the heaviest
+    // cluster's; converged on its share and its own two deviations (a resultant of 1 or rounded above it: deviation 0).
+    void searchByCluster()
+    {
+        bl_pf_cluster_pose_t c;
+        const bool have = pf_.heaviestCluster(globalClusterParams_, &c);
+        if (have) {
+            globalClusterPose_ = c;
+            now_.x = static_cast<float>(c.mean_x);
+            now_.y = static_cast<float>(c.mean_y);
+            now_.theta = static_cast<float>(c.theta);
+        }
+        announce();
+        if (!have || !(c.share >= globalClusterMinShare_)) return;
+        const double h = 0.5 * (c.var_x + c.var_y);
+        const double pos = std::sqrt(h + std::sqrt(0.25 * (c.var_x - c.var_y) * (c.var_x - c.var_y) + c.cov_xy * c.cov_xy));
+        const double heading = c.theta_resultant >= 1.0 ? 0.0 : c.theta_resultant > 0.0 ? std::sqrt(-2.0 * std::log(c.theta_resultant)) : HUGE_VAL;
+        if (!(pos <= globalPosTol_ && heading <= globalHeadingTol_)) return;
+        globalConverged_ = true;
+        pf_.initializeFilterAtPose(now_);
+        startRecovery();
+        extendMap(false);
     }
 
     const PoseTraceT<Pose>& poseSource() const { return how_.posesGiven ? truth_ : odom_; }

@@ -13,6 +13,7 @@
 #ifndef BOTLAB_HIP_H
 #define BOTLAB_HIP_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -219,6 +220,87 @@ typedef struct bl_pf_adaptive_state_t {
     uint64_t counts;                      /* resampling updates counted since enabling */
 } bl_pf_adaptive_state_t;                 /* 24 bytes */
 int bl_pf_adaptive_state(bl_pf* pf, bl_pf_adaptive_state_t* out);   /* synchronises; BL_ERR_STATE while an update is pending */
+/* Pose hypotheses: the clusters of the cloud (AMCL's pf_cluster_stats).  The particles [0, active) of the current record are
+ * binned, the connected components of the occupied bins are the clusters, and the heaviest ones are reported with exact integer
+ * sums.  Everything summed or compared is an integer: the result does not depend on a launch shape or an order of arrival.
+ *   Constants, formed once in plain double:  xy_scale = 1024.0 / bin_xy,  th_scale = (double)T / 6.283185307179586  (T = theta_bins).
+ *   Per particle (x, y, theta floats, u its weight units):
+ *     fine position  px = clamp(floor((double)x * xy_scale), -2^30, 2^30 - 1) as int64 (NaN: -2^30), py likewise;
+ *     position bin   ix = px >> 10 (floor), iy likewise -- a bin is bin_xy wide, a fine unit bin_xy / 1024;
+ *     heading bin    q = clamp(floor((double)theta * th_scale), -2^40, 2^40 - 1) (NaN: -2^40), it = q mod T in [0, T);
+ *     heading terms  (sn, cs) = bl_sincosf(theta) -- glibc's sinf / cosf, bit for bit -- when theta is finite and |theta| < 100,
+ *                    else (0, 0);  si = (int64)rint((double)sn * 1048576.0), ci likewise.
+ *   Clusters: a bin (ix, iy, it) is occupied when at least one particle falls into it (a particle of 0 units counts).  Two different
+ *     occupied bins are adjacent iff |d ix| <= 1, |d iy| <= 1 and d it = -1, 0 or +1 (mod T).  A cluster is a connected component
+ *     of the occupied bins under this adjacency.
+ *   Per cluster, over its particles: count; units U = sum u; sx = sum u px, sy = sum u py, sxx = sum u px^2, syy = sum u py^2,
+ *     sxy = sum u px py, sc = sum u ci, ss = sum u si as signed 128-bit integers (|sxx| can reach 2^112); anchor = the
+ *     lexicographically smallest (ix, iy, it) of its bins.
+ *   Order: U descending, then anchor ascending (a total order).  The call reports the number of clusters C, the total units S, active,
+ *     and the first min(C, max_clusters) clusters; the rest of clusters[] is zero.  labels, if given, takes one int32 per particle:
+ *     the rank of its cluster when that rank is < max_clusters, else -1.
+ *   Runs on the ctx stream and synchronises.  BL_ERR_ARG for bad parameters; BL_ERR_STATE before an initialisation, while an update is
+ *     pending and on a composed shard (bl_pf_spread's rule).  Either way the filter, out and labels are left as they were.
+ *     bin_xy, theta_bins and any share threshold a caller puts on the result are untuned knobs. */
+#define BL_PF_MAX_CLUSTERS 64
+typedef struct bl_pf_cluster_params_t {
+    double bin_xy;                        /* position bin, metres: > 0 and finite */
+    int32_t theta_bins;                   /* T, heading bins of the full turn: 1 .. 4096 */
+    int32_t max_clusters;                 /* K, clusters reported: 1 .. BL_PF_MAX_CLUSTERS */
+} bl_pf_cluster_params_t;                 /* 16 bytes */
+typedef struct bl_i128_t { uint64_t lo; int64_t hi; } bl_i128_t;       /* value = hi * 2^64 + lo */
+typedef struct bl_pf_cluster_t {
+    uint64_t count, units;
+    bl_i128_t sx, sy, sxx, syy, sxy, sc, ss;
+    int32_t anchor_ix, anchor_iy, anchor_it, pad;
+} bl_pf_cluster_t;                        /* 144 bytes */
+typedef struct bl_pf_clusters_t {
+    uint64_t num_clusters;                /* C */
+    uint64_t units_sum;                   /* S */
+    int32_t active, pad;
+    bl_pf_cluster_t clusters[BL_PF_MAX_CLUSTERS];
+} bl_pf_clusters_t;                       /* 9240 bytes */
+int bl_pf_clusters(bl_pf* pf, const bl_pf_cluster_params_t* params, bl_pf_clusters_t* out, int32_t* labels /* NULL or active ints */);
+/* A cluster's pose, in plain double: not part of the byte-equality contract (the library exports the same function for bindings).
+ * The position sums are recentred on the anchor bin exactly, in 128-bit integers -- a = 1024 anchor_ix: sx' = sx - a U,
+ * sxx' = sxx - 2 a sx + a^2 U, likewise y and the cross term -- and every integer is converted to double once:
+ *   share = U / S;  mean_x = (a + sx' / U + 0.5) / xy_scale (the middle of the mean fine unit), mean_y likewise;
+ *   var_x = (sxx' / U - (sx' / U)^2) / xy_scale^2, var_y and cov_xy likewise (population moments);
+ *   theta = atan2(ss, sc);  theta_resultant = hypot(ss, sc) / (U * 2^20)  (circular std sqrt(-2 ln R)).
+ * Returns 1; a cluster of 0 units has no pose: returns 0 and writes nothing. */
+typedef struct bl_pf_cluster_pose_t {
+    double share, mean_x, mean_y, var_x, var_y, cov_xy, theta, theta_resultant;
+} bl_pf_cluster_pose_t;                   /* 64 bytes */
+#ifndef BL_PF_HELPER
+#define BL_PF_HELPER static inline
+#endif
+BL_PF_HELPER int bl_pf_cluster_pose(const bl_pf_cluster_t* c, uint64_t units_sum, const bl_pf_cluster_params_t* params,
+                                    bl_pf_cluster_pose_t* out)
+{
+    if (c->units == 0) return 0;
+    {
+        const double xy_scale = 1024.0 / params->bin_xy;
+        const __int128 U = (__int128)c->units, ax = (__int128)1024 * c->anchor_ix, ay = (__int128)1024 * c->anchor_iy;
+#define BL_PF_I128(v) ((__int128)(((unsigned __int128)(uint64_t)(v).hi << 64) | (v).lo))
+        const __int128 sx = BL_PF_I128(c->sx), sy = BL_PF_I128(c->sy);
+        const __int128 rx = sx - ax * U, ry = sy - ay * U;
+        const __int128 rxx = BL_PF_I128(c->sxx) - 2 * ax * sx + ax * ax * U;
+        const __int128 ryy = BL_PF_I128(c->syy) - 2 * ay * sy + ay * ay * U;
+        const __int128 rxy = BL_PF_I128(c->sxy) - ax * sy - ay * sx + ax * ay * U;
+        const double dU = (double)c->units, mx = (double)rx / dU, my = (double)ry / dU;
+        const double dss = (double)BL_PF_I128(c->ss), dsc = (double)BL_PF_I128(c->sc);
+#undef BL_PF_I128
+        out->share = dU / (double)units_sum;
+        out->mean_x = ((double)ax + mx + 0.5) / xy_scale;
+        out->mean_y = ((double)ay + my + 0.5) / xy_scale;
+        out->var_x = ((double)rxx / dU - mx * mx) / (xy_scale * xy_scale);
+        out->var_y = ((double)ryy / dU - my * my) / (xy_scale * xy_scale);
+        out->cov_xy = ((double)rxy / dU - mx * my) / (xy_scale * xy_scale);
+        out->theta = atan2(dss, dsc);
+        out->theta_resultant = hypot(dss, dsc) / (dU * 1048576.0);
+    }
+    return 1;
+}
 /* Replace the whole posterior from a host AoS array of num_particles records.  The `weight` fields are not read: the weights are
  * units[m] / sum(units), units == NULL -> uniform (every unit 1).
  *   Legal units: any uint32 values, zeros included, whose total is not 0 (num_particles * (2^32 - 1) < 2^53: the total and every
