@@ -253,6 +253,8 @@ class ExploreResult(C.Structure):
 BL_K_MCL_MAIN, BL_K_MCL_SCAN, BL_K_MAP, BL_K_DIST, BL_K_ASTAR, BL_K_FRONTIERS = range(6)
 BL_K_DIST_ROWS, BL_K_DIST_COLS_SUMMARY, BL_K_DIST_COLS_APPLY, BL_K_SNAPSHOT, BL_K_DIST_FUSED = range(6, 11)
 BL_OK, BL_ERR_HIP, BL_ERR_ARG, BL_ERR_CAPACITY, BL_ERR_STATE = range(5)
+BL_DIST_L1, BL_DIST_EUCLIDEAN = 0, 1
+BL_EDT_MAX_CELLS = 254
 
 _vp = C.c_void_p
 _P = C.POINTER
@@ -323,6 +325,10 @@ SIGNATURES = {
     "bl_dist_shape": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
     "bl_dist_frame": (C.c_int, [_vp, _P(C.c_float), _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "bl_dist_device_ptr": (_vp, [_vp]),
+    "bl_dist_create_euclidean": (C.c_int, [_vp, C.c_int, _P(_vp)]),
+    "bl_dist_metric": (C.c_int, [_vp, _P(C.c_int), _P(C.c_int)]),
+    "bl_dist_download_codes": (C.c_int, [_vp, _vp]),
+    "bl_dist_table": (C.c_int, [_vp, _vp, _P(C.c_int)]),
     "bl_astar_search": (C.c_int, [_vp, _vp, _P(Pose), _P(Pose), _P(SearchParams), _vp, C.c_int, _P(C.c_int),
                                   _P(C.c_int64)]),
     "bl_astar_set_open_capacity": (C.c_int, [_vp, C.c_int64]),

@@ -161,9 +161,16 @@ int bl_dist_view(const bl_dist* d, const uint16_t** l1, const float** lut, int* 
 // the search's cost table and the navigation field's traversable(n)
 inline bool bl_search_traversable(float dist, double minDistanceToObstacle) { return dist > minDistanceToObstacle * 1.000001; }
 
-// bl_planning.hip: a transformed distance grid as bl_navfield.hip reads it (BL_ERR_ARG before its first transform)
-struct bl_dist_host_view { bl_ctx* ctx; bl_frame frame; const uint16_t* l1; const float* lut_host; int lut_n; };
+// bl_planning.hip: a transformed distance grid as bl_navfield.hip reads it (BL_ERR_ARG before its first transform).  l1 holds the
+// grid's codes n(c) and lut_host the float table they index, table_n entries of it: width + height + 1 for an L1 grid, R^2 + 2 for a
+// Euclidean one.  (lut_n is what has been allocated for an L1 grid's table: it only ever grows.)
+struct bl_dist_host_view { bl_ctx* ctx; bl_frame frame; const uint16_t* l1; const float* lut_host; int lut_n; int table_n; int metric; int max_cells; };
 int bl_dist_view_host(const bl_dist* d, bl_dist_host_view* out);
+
+// bl_edt.hip: the capped exact Euclidean transform (botlab_hip.h, "Euclidean distance grid") of W x H cells into `codes`, enqueued on
+// ctx's stream; g (W * H bytes) and has_source (one word) are its scratch.  bl_edt_table: the float table f[0 .. R^2 + 1].
+int bl_edt_transform(bl_ctx* ctx, const int8_t* cells, int W, int H, int R, uint8_t* g, unsigned int* has_source, uint16_t* codes);
+void bl_edt_table(int R, float mpc, std::vector<float>* out);
 
 // RAII-less helpers
 int bl_timer_begin(bl_ctx* ctx, int id, hipEvent_t* a, hipEvent_t* b);

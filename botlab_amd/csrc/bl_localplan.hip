@@ -333,7 +333,7 @@ static int lp_prepare(bl_localplan* lp, bl_navfield* nf, const bl_localplan_stat
     bl_dist_host_view v;
     int rc = bl_dist_view_host(nf->dist, &v);
     if (rc) return rc;
-    if (v.l1 != nf->l1 || v.frame.width != nf->frame.width || v.frame.height != nf->frame.height) {
+    if (v.l1 != nf->l1 || v.frame.width != nf->frame.width || v.frame.height != nf->frame.height || v.table_n != nf->table_n) {
         bl_set_error("local planner: the distance grid was resized since the field was computed");
         return BL_ERR_STATE;
     }
@@ -345,7 +345,7 @@ static int lp_prepare(bl_localplan* lp, bl_navfield* nf, const bl_localplan_stat
     rc = lp_state_ok(states, n);
     if (rc) return rc;
     memset((void*)a, 0, sizeof(*a));
-    a->field = nf->field; a->l1 = nf->l1; a->table = nf->table; a->table_n = nf->frame.width + nf->frame.height + 1;
+    a->field = nf->field; a->l1 = nf->l1; a->table = nf->table; a->table_n = nf->table_n;
     a->frame = nf->frame;
     a->n_v = p.n_v; a->n_w = p.n_w; a->n_steps = p.n_steps;
     int nvp = 1;

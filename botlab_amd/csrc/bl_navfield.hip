@@ -368,7 +368,13 @@ extern "C" int bl_navfield_compute(bl_navfield* nf, const bl_dist* dist, const b
         BL_HIP(hipMalloc((void**)&nf->lists, 3 * ntiles * 4));
         nf->tiles_cap = ntiles;
     }
-    const int ln = W + H + 1;
+    const int ln = v.table_n;
+    if (v.metric == BL_DIST_EUCLIDEAN && params->maxDistanceWithCost > params->minDistanceToObstacle &&
+        params->maxDistanceWithCost > (double)v.lut_host[v.max_cells * v.max_cells]) {
+        bl_set_error("bl_navfield_compute: maxDistanceWithCost %g lies beyond the Euclidean grid's cap of %d cells (%g m): a far cell's penalty would be "
+                     "priced from a lower bound of its distance", params->maxDistanceWithCost, v.max_cells, (double)v.lut_host[v.max_cells * v.max_cells]);
+        return BL_ERR_ARG;
+    }
     if (ln > nf->table_cap) {
         BL_HIP(hipStreamSynchronize(ctx->stream));
         if (nf->table) BL_HIP(hipFree(nf->table));
@@ -436,7 +442,7 @@ extern "C" int bl_navfield_compute(bl_navfield* nf, const bl_dist* dist, const b
     nf->stats[2] = s[NST_TRAVERSABLE];
     nf->stats[3] = s[NST_REACHED];
     nf->stats[4] = s[NST_GOALSET];
-    nf->frame = v.frame; nf->l1 = v.l1; nf->dist = dist; nf->params = *params; nf->n_goals = n_goals;
+    nf->frame = v.frame; nf->l1 = v.l1; nf->dist = dist; nf->params = *params; nf->n_goals = n_goals; nf->table_n = ln;
     nf->valid = true;
     return BL_OK;
 }
@@ -471,7 +477,7 @@ extern "C" int bl_navfield_paths(bl_navfield* nf, const bl_pose_xyt_t* starts, i
     bl_dist_host_view v;
     rc = bl_dist_view_host(nf->dist, &v);
     if (rc) return rc;
-    if (v.l1 != nf->l1 || v.frame.width != nf->frame.width || v.frame.height != nf->frame.height) {
+    if (v.l1 != nf->l1 || v.frame.width != nf->frame.width || v.frame.height != nf->frame.height || v.table_n != nf->table_n) {
         bl_set_error("bl_navfield_paths: the distance grid was resized since the field was computed");
         return BL_ERR_STATE;
     }
@@ -483,7 +489,7 @@ extern "C" int bl_navfield_paths(bl_navfield* nf, const bl_pose_xyt_t* starts, i
     BL_HIP(hipMemcpyAsync(nf->q_dev, starts, (size_t)n * sizeof(bl_pose_xyt_t), hipMemcpyHostToDevice, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));
     nav_path_args a;
-    a.field = nf->field; a.l1 = nf->l1; a.table = nf->table; a.table_n = nf->frame.width + nf->frame.height + 1;
+    a.field = nf->field; a.l1 = nf->l1; a.table = nf->table; a.table_n = nf->table_n;
     a.frame = nf->frame;
     a.goals = nf->goals; a.n_goals = nf->n_goals; a.reach = nf->params.reach_cells;
     a.starts = (const bl_pose_xyt_t*)nf->q_dev; a.n = n;

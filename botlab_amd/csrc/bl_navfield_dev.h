@@ -15,7 +15,8 @@ struct bl_navfield {
     unsigned int* tile_flag;           // per tile: the last round it was listed for
     unsigned int* lists;               // 3 x tiles
     size_t tiles_cap;
-    int32_t* table; int table_cap;     // device: per L1 distance, -1 not traversable, else the penalty
+    int32_t* table; int table_cap;     // device: per distance code, -1 not traversable, else the penalty
+    int table_n;                       // its entries for the field computed last (the distance grid's table_n)
     unsigned int* state;               // device NST_WORDS
     unsigned int* h_state;             // pinned copy
     int32_t* goals; int goals_cap;     // device x, y pairs

@@ -59,7 +59,25 @@ struct bl_dist {
     // k_dist_fused: the tiles' summary and claim words, the grid they were laid out for, the last launch's tag
     unsigned int* fwords; size_t fwords_cap; int f_w, f_h; unsigned int f_tag;
     int64_t n_inc, n_full, n_same;   // transforms by kind (diagnostic)
+    // a Euclidean grid (bl_dist_create_euclidean; kernels in bl_edt.hip): l1 then holds the codes d^2 capped at max_cells^2 (+ 1: far),
+    // lut / lut_host the table f[k] = sqrt(k) * mpc of R^2 + 2 entries; row, closed, sum_*, state and fwords stay unallocated
+    int metric, max_cells;
+    uint8_t* edt_g;           // the row pass's result, a byte per cell
+    unsigned int* edt_src;    // device word: the map has a source
+    float edt_mpc;            // the cell size lut was formed for
 };
+
+static int dist_check_broken(bl_dist* d);
+
+// The reference's search and everything defined through it read L1 distances: what such an entry answers for a Euclidean grid
+static int dist_need_l1(const bl_dist* d, const char* who)
+{
+    if (d && d->metric != BL_DIST_L1) {
+        bl_set_error("%s is defined on the L1 distance grid (bl_dist_create): it does not take a Euclidean one", who);
+        return BL_ERR_ARG;
+    }
+    return BL_OK;
+}
 
 #define DIST_INF (1 << 28)
 
@@ -1492,10 +1510,33 @@ extern "C" int bl_dist_create(bl_ctx* ctx, bl_dist** out)
     return BL_OK;
 }
 
+extern "C" int bl_dist_create_euclidean(bl_ctx* ctx, int max_cells, bl_dist** out)
+{
+    BL_CHECK_ARG(ctx != nullptr && out != nullptr);
+    if (max_cells < 1 || max_cells > BL_EDT_MAX_CELLS) {
+        bl_set_error("bl_dist_create_euclidean: max_cells %d outside 1 .. %d (the row pass keeps a byte per cell)", max_cells, BL_EDT_MAX_CELLS);
+        return BL_ERR_ARG;
+    }
+    int rc = bl_dist_create(ctx, out);
+    if (rc) return rc;
+    (*out)->metric = BL_DIST_EUCLIDEAN; (*out)->max_cells = max_cells;
+    return BL_OK;
+}
+
+extern "C" int bl_dist_metric(const bl_dist* d, int* metric, int* max_cells)
+{
+    BL_CHECK_ARG(d != nullptr);
+    if (metric) *metric = d->metric;
+    if (max_cells) *max_cells = d->metric == BL_DIST_EUCLIDEAN ? d->max_cells : 0;
+    return BL_OK;
+}
+
 extern "C" void bl_dist_destroy(bl_dist* d)
 {
     if (!d) return;
     (void)hipStreamSynchronize(d->ctx->stream);
+    if (d->edt_g) (void)hipFree(d->edt_g);
+    if (d->edt_src) (void)hipFree(d->edt_src);
     if (d->row) (void)hipFree(d->row);
     if (d->l1) (void)hipFree(d->l1);
     if (d->cells) (void)hipFree(d->cells);
@@ -1778,10 +1819,73 @@ static int dist_set_distances_batch(int n, bl_dist* const* ds, const bl_grid* co
     return BL_OK;
 }
 
+// setDistances of a Euclidean grid: always the whole map, by the kernels of bl_edt.hip (no incremental form, no batch)
+static int dist_set_euclidean(bl_dist* d, const bl_grid* map)
+{
+    bl_ctx* ctx = d->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    const int W = map->frame.width, H = map->frame.height, R = d->max_cells;
+    BL_CHECK_ARG(W >= 1 && H >= 1 && W + H < 0xFFFF);
+    const size_t n = (size_t)W * H;
+    if (n > d->capacity) {
+        BL_HIP(hipStreamSynchronize(ctx->stream));
+        if (d->l1) BL_HIP(hipFree(d->l1));
+        if (d->cells) BL_HIP(hipFree(d->cells));
+        if (d->edt_g) BL_HIP(hipFree(d->edt_g));
+        d->l1 = nullptr; d->cells = nullptr; d->edt_g = nullptr; d->capacity = 0; d->valid = false;
+        BL_HIP(hipMalloc((void**)&d->l1, n * 2));
+        BL_HIP(hipMalloc((void**)&d->edt_g, n));
+        d->capacity = n;
+    }
+    if (!d->edt_src) BL_HIP(hipMalloc((void**)&d->edt_src, sizeof(unsigned int)));
+    const int ln = R * R + 2;
+    if (!d->lut || !(d->edt_mpc == map->frame.mpc)) {
+        BL_HIP(hipStreamSynchronize(ctx->stream));                     // k_dist_floats of the last transform may still read the table
+        bl_edt_table(R, map->frame.mpc, d->lut_host);
+        if (!d->lut) BL_HIP(hipMalloc((void**)&d->lut, (size_t)ln * 4));
+        BL_HIP(hipMemcpy(d->lut, d->lut_host->data(), (size_t)ln * 4, hipMemcpyHostToDevice));
+        d->lut_n = ln; d->edt_mpc = map->frame.mpc;
+    }
+    d->frame = map->frame;
+    d->floats_valid = false;
+    hipEvent_t e0, e1;
+    int rc = bl_timer_begin(ctx, BL_K_DIST, &e0, &e1);
+    if (rc) return rc;
+    rc = bl_edt_transform(ctx, map->cells, W, H, R, d->edt_g, d->edt_src, d->l1);
+    if (rc) return rc;
+    rc = bl_timer_end(ctx, BL_K_DIST, e0, e1);
+    if (rc) return rc;
+    d->valid = true;
+    if (d->floats_handed_out) { rc = dist_floats(d); if (rc) return rc; }
+    d->n_full += 1;
+    d->src_id = 0; d->bound_ok = false;
+    return BL_OK;
+}
+
 extern "C" int bl_dist_set_distances(bl_dist* d, const bl_grid* map)
 {
     BL_CHECK_ARG(d != nullptr && map != nullptr);
+    if (d->metric == BL_DIST_EUCLIDEAN) return dist_set_euclidean(d, map);
     return dist_set_distances_batch(1, &d, &map);
+}
+
+// the table the codes of `d` index, as it stands after the last transform: *n entries (f may be NULL to ask for *n alone)
+extern "C" int bl_dist_table(const bl_dist* d, float* f, int* n)
+{
+    BL_CHECK_ARG(d != nullptr && d->valid);
+    const int ln = d->metric == BL_DIST_EUCLIDEAN ? d->max_cells * d->max_cells + 2 : d->frame.width + d->frame.height + 1;
+    if (n) *n = ln;
+    if (f) memcpy(f, d->lut_host->data(), (size_t)ln * 4);
+    return BL_OK;
+}
+
+// n(c) of either metric: width * height words (synchronises)
+extern "C" int bl_dist_download_codes(bl_dist* d, uint16_t* out)
+{
+    BL_CHECK_ARG(d != nullptr && out != nullptr && d->valid);
+    BL_HIP(hipMemcpyAsync(out, d->l1, (size_t)d->frame.width * d->frame.height * 2, hipMemcpyDeviceToHost, d->ctx->stream));
+    BL_HIP(hipStreamSynchronize(d->ctx->stream));
+    return dist_check_broken(d);
 }
 
 // the next setDistances transforms the whole map, whatever `d` holds now (timing the whole-grid kernels; tests)
@@ -1871,6 +1975,7 @@ extern "C" int bl_dist_download(bl_dist* d, float* cells)
 int bl_dist_view(const bl_dist* d, const uint16_t** l1, const float** lut, int* width, int* height)
 {
     if (!d || !d->valid) { bl_set_error("distance grid not set (bl_dist_set_distances first)"); return BL_ERR_ARG; }
+    { const int rc = dist_need_l1(d, "the particle filter's seeding (bl_pf_init_uniform, bl_pf_set_recovery)"); if (rc) return rc; }
     *l1 = d->l1; *lut = d->lut;
     *width = d->frame.width; *height = d->frame.height;
     return BL_OK;
@@ -1886,6 +1991,8 @@ int bl_dist_view_host(const bl_dist* d, bl_dist_host_view* out)
     if (rc) return rc;
     out->ctx = d->ctx; out->frame = d->frame; out->l1 = d->l1;
     out->lut_host = d->lut_host->data(); out->lut_n = d->lut_n;
+    out->metric = d->metric; out->max_cells = d->metric == BL_DIST_EUCLIDEAN ? d->max_cells : 0;
+    out->table_n = d->metric == BL_DIST_EUCLIDEAN ? d->max_cells * d->max_cells + 2 : d->frame.width + d->frame.height + 1;
     return BL_OK;
 }
 
@@ -2611,6 +2718,7 @@ static int astar_fill(bl_ctx* ctx, const bl_dist* d, const bl_pose_xyt_t* start,
 {
     BL_CHECK_ARG(ctx != nullptr && d != nullptr && goal != nullptr && params != nullptr);
     BL_CHECK_ARG(start != nullptr || d_start != nullptr);
+    { const int rcm = dist_need_l1(d, "search_for_path (bl_astar_search*)"); if (rcm) return rcm; }
     BL_CHECK_ARG(d->valid && d->ctx == ctx);
     BL_CHECK_ARG(d->frame.width <= AH_MAX_DIM && d->frame.height <= AH_MAX_DIM);
     BL_HIP(hipSetDevice(ctx->device));
@@ -2908,6 +3016,7 @@ static int astar_batch_cells(bl_ctx* ctx, const bl_dist* d, const bl_pose_xyt_t*
                              const bl_search_params_t* params, Sink sink)
 {
     BL_CHECK_ARG(ctx != nullptr && d != nullptr && start != nullptr && params != nullptr && n >= 0);
+    { const int rcm = dist_need_l1(d, "search_for_path (bl_astar_search_batch)"); if (rcm) return rcm; }
     BL_CHECK_ARG(d->valid && d->ctx == ctx);
     BL_CHECK_ARG(d->frame.width <= AH_MAX_DIM && d->frame.height <= AH_MAX_DIM);
     if (n == 0) return BL_OK;
@@ -3456,6 +3565,7 @@ extern "C" int bl_plan_path_to_frontier(bl_ctx* ctx, const bl_frontiers* frontie
                                         bl_pose_xyt_t* chosen_goal, int64_t* stats)
 {
     BL_CHECK_ARG(ctx != nullptr && frontiers != nullptr && robot_pose != nullptr && dist != nullptr && planner != nullptr);
+    { const int rcm = dist_need_l1(dist, "plan_path_to_frontier"); if (rcm) return rcm; }
     BL_CHECK_ARG(out_path != nullptr && cap >= 1 && out_len != nullptr && dist->valid && dist->ctx == ctx);
     const bl_motion_planner_t& pl = *planner;
     const bl_pose_xyt_t robotPose = *robot_pose;

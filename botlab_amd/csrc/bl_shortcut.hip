@@ -300,8 +300,7 @@ static int sc_run(bl_shortcut* sc, const bl_dist* dist, const int32_t* xy, const
     int rc = bl_dist_view_host(dist, &v);
     if (rc) return rc;
     BL_CHECK_ARG(v.ctx == ctx);
-    const int W = v.frame.width, H = v.frame.height, ln = W + H + 1;
-    BL_CHECK_ARG(v.lut_n >= ln);
+    const int W = v.frame.width, H = v.frame.height, ln = v.table_n;
     for (int k = 0; k < N; ++k) BL_CHECK_ARG(xy[2 * k] >= 0 && xy[2 * k] < W && xy[2 * k + 1] >= 0 && xy[2 * k + 1] < H);
     BL_HIP(hipSetDevice(ctx->device));
 

@@ -602,16 +602,44 @@ class ScanMatcher:
 class ObstacleDistanceGrid:
     """ObstacleDistanceGrid().setDistances(map); operator()(x, y) (obstacle_distance_grid.hpp:28-96)."""
 
-    def __init__(self, ctx=None):
+    def __init__(self, ctx=None, metric="l1", max_cells=64):
+        """metric "l1": the reference's grid (0.1 per L1 cell), what the search reads.  metric "euclidean": the exact Euclidean
+        transform in metres, capped at max_cells cells (bl_dist_create_euclidean), for the field, the local planner and the shortcut."""
         self.ctx = ctx or default_context()
         h = C.c_void_p()
-        check(self.ctx.lib.bl_dist_create(self.ctx.h, C.byref(h)))
+        if metric == "l1":
+            check(self.ctx.lib.bl_dist_create(self.ctx.h, C.byref(h)))
+        elif metric == "euclidean":
+            check(self.ctx.lib.bl_dist_create_euclidean(self.ctx.h, int(max_cells), C.byref(h)))
+        else:
+            raise ValueError("metric must be 'l1' or 'euclidean'")
         self.h = h
         self._host = None
 
     def setDistances(self, grid):
         check(self.ctx.lib.bl_dist_set_distances(self.h, grid.h))
         self._host = None
+
+    def metric(self):
+        """("l1", 0) or ("euclidean", max_cells) (bl_dist_metric)."""
+        m, r = C.c_int(), C.c_int()
+        check(self.ctx.lib.bl_dist_metric(self.h, C.byref(m), C.byref(r)))
+        return ("euclidean" if m.value == _capi.BL_DIST_EUCLIDEAN else "l1"), r.value
+
+    def codes(self):
+        """n(c) as uint16 (h, w): the L1 distance in cells, or the capped squared Euclidean distance; 0xFFFF: the map has no source."""
+        w, h = self.shape()
+        out = np.empty((h, w), dtype=np.uint16)
+        check(self.ctx.lib.bl_dist_download_codes(self.h, out.ctypes.data))
+        return out
+
+    def table(self):
+        """The float table the codes index (bl_dist_table)."""
+        n = C.c_int()
+        check(self.ctx.lib.bl_dist_table(self.h, None, C.byref(n)))
+        out = np.empty(n.value, dtype=np.float32)
+        check(self.ctx.lib.bl_dist_table(self.h, out.ctypes.data, C.byref(n)))
+        return out
 
     def forget(self):
         """The next setDistances transforms the whole map (bl_dist_forget)."""
@@ -1497,6 +1525,8 @@ class MotionPlanner:
         self.searchParams_ = SearchParams()
         self.num_frontiers = 1           # uninitialised in the reference (motion_planner.hpp:164); callers set it
         self.prev_goal = make_pose(1e9, 1e9, 0.0)
+        self.map_ = None
+        self.metric_ = None              # setMetricClearance: a second, Euclidean grid for the field and the shortcut
         self.setParams(self.params_)
 
     def setParams(self, params):
@@ -1507,23 +1537,47 @@ class MotionPlanner:
 
     def setMap(self, grid):
         self.distances_.setDistances(grid)
+        self.map_ = grid
+        if self.metric_ is not None:
+            self.metric_.setDistances(grid)
 
-    def setPrevGoal(self, goal): self.prev_goal = goal
-    def setNumFrontiers(self, n): self.num_frontiers = int(n)
+    def setMetricClearance(self, max_cells=64):
+        """Metric clearance for planPathOptimal, shortcutPath and planPathShortcut: they read an exact Euclidean distance grid
+        (capped at max_cells cells) beside the L1 grid, so that robotRadius means metres.  None turns it off (the default).  planPath,
+        isValidGoal, isPathSafe and the frontier choosers stay on the L1 grid either way.  Takes effect with the next setMap (and at
+        once for a map already set)."""
+        if self.metric_ is not None:
+            self.metric_.close()
+            self.metric_ = None
+        if max_cells is None:
+            return
+        self.metric_ = ObstacleDistanceGrid(ctx=self.distances_.ctx, metric="euclidean", max_cells=max_cells)
+        if self.map_ is not None:
+            self.metric_.setDistances(self.map_)
 
-    def isValidGoal(self, goal):
+    def metricDistances(self):
+        """The Euclidean grid of setMetricClearance (None while it is off)."""
+        return self.metric_
+
+    def _isValidGoalOn(self, distances, goal):
         # motion_planner.cpp:52-74
         dx = np.float32(goal.x) - np.float32(self.prev_goal.x)
         dy = np.float32(goal.y) - np.float32(self.prev_goal.y)
         dist_prev = np.sqrt(np.float32(dx * dx + dy * dy), dtype=np.float32)
         if self.num_frontiers != 1 and float(dist_prev) < 2 * self.searchParams_.minDistanceToObstacle:
             return False
-        mpc, cpm, ox, oy = self.distances_.frame()
+        mpc, cpm, ox, oy = distances.frame()
         gx = int((float(np.float32(goal.x)) - float(ox)) * float(cpm))
         gy = int((float(np.float32(goal.y)) - float(oy)) * float(cpm))
-        if self.distances_.isCellInGrid(gx, gy):
-            return float(self.distances_(gx, gy)) > self.params_.robotRadius
+        if distances.isCellInGrid(gx, gy):
+            return float(distances(gx, gy)) > self.params_.robotRadius
         return False
+
+    def setPrevGoal(self, goal): self.prev_goal = goal
+    def setNumFrontiers(self, n): self.num_frontiers = int(n)
+
+    def isValidGoal(self, goal):
+        return self._isValidGoalOn(self.distances_, goal)
 
     def planPath(self, start, goal, searchParams=None, return_stats=False):
         if not self.isValidGoal(goal):
@@ -1534,12 +1588,13 @@ class MotionPlanner:
     def planPathOptimal(self, start, goal, obstacle_gain=NAV_OBSTACLE_GAIN, return_cost=False, cap=1 << 16):
         """The cheapest 8-connected path to the goal's cell by the navigation field (bl_navfield_*): the failed path when isValidGoal
         fails, exactly as planPath; length 1 also when the goal cannot be reached."""
-        if not self.isValidGoal(goal):
+        dist = self.metric_ if self.metric_ is not None else self.distances_
+        if not self._isValidGoalOn(dist, goal):
             failed = [Pose(start.utime, start.x, start.y, start.theta)]
             return (failed, NAV_UNREACHED) if return_cost else failed
-        nf = NavigationField(self.distances_.ctx)
+        nf = NavigationField(dist.ctx)
         try:
-            nf.computeToPose(self.distances_, nav_params(self.searchParams_, obstacle_gain, 0), goal)
+            nf.computeToPose(dist, nav_params(self.searchParams_, obstacle_gain, 0), goal)
             paths, _, costs = nf.paths([start], cap_each=cap)
         finally:
             nf.close()
@@ -1550,7 +1605,7 @@ class MotionPlanner:
         sc = PathShortcut(self.distances_.ctx, clearance=self.searchParams_.minDistanceToObstacle if clearance is None else clearance,
                           max_span=max_span, waypoint_cost=waypoint_cost)
         try:
-            return sc.shortcut(self.distances_, path)
+            return sc.shortcut(self.metric_ if self.metric_ is not None else self.distances_, path)
         finally:
             sc.close()
 

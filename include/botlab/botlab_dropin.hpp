@@ -430,19 +430,47 @@ private:
 // ------------------------------------------------------------------------------------------------ ObstacleDistanceGrid
 class ObstacleDistanceGrid {
 public:
-    ObstacleDistanceGrid() : h_(nullptr), hostValid_(false) { check(bl_dist_create(default_ctx(), &h_), "bl_dist_create"); }
-    ObstacleDistanceGrid(const ObstacleDistanceGrid& o) : h_(nullptr), hostValid_(false)
+    ObstacleDistanceGrid() : h_(nullptr), maxCells_(0), hostValid_(false) { create(); }
+    // (extension; botlab_hip.h, "Euclidean distance grid") the exact Euclidean transform in metres, capped at max_cells cells
+    // (1 .. BL_EDT_MAX_CELLS): what the navigation field, the local planner and the path shortcut may read in place of the reference's
+    // L1 grid.  The search does not take it.  Same value semantics as the L1 grid.
+    static ObstacleDistanceGrid euclidean(int max_cells = 64) { return ObstacleDistanceGrid(max_cells, EuclideanTag()); }
+    ObstacleDistanceGrid(const ObstacleDistanceGrid& o) : h_(nullptr), maxCells_(o.maxCells_), hostValid_(false)
     {
-        check(bl_dist_create(default_ctx(), &h_), "bl_dist_create");
+        create();
         src_ = o.src_;
         if (src_.widthInCells() > 0) setDistances(src_);       // deep copy = recompute from the remembered map (bit-identical)
     }
     ObstacleDistanceGrid& operator=(const ObstacleDistanceGrid& o)
     {
-        if (this != &o) { src_ = o.src_; hostValid_ = false; if (src_.widthInCells() > 0) setDistances(src_); }
+        if (this != &o) {
+            if (maxCells_ != o.maxCells_) { bl_dist_destroy(h_); h_ = nullptr; maxCells_ = o.maxCells_; create(); }
+            src_ = o.src_; hostValid_ = false;
+            if (src_.widthInCells() > 0) setDistances(src_);
+        }
         return *this;
     }
     ~ObstacleDistanceGrid() { bl_dist_destroy(h_); }
+
+    int metric() const { return maxCells_ > 0 ? BL_DIST_EUCLIDEAN : BL_DIST_L1; }
+    int maxCells() const { return maxCells_; }                                  // 0 for an L1 grid
+    // n(c) of either metric, row-major: the L1 distance in cells, or the capped squared Euclidean distance; 0xFFFF: no source
+    std::vector<uint16_t> codes() const
+    {
+        std::vector<uint16_t> out(static_cast<size_t>(widthInCells()) * heightInCells());
+        if (!out.empty()) check(bl_dist_download_codes(h_, out.data()), "bl_dist_download_codes");
+        return out;
+    }
+    // the float table the codes index
+    std::vector<float> table() const
+    {
+        int n = 0;
+        check(bl_dist_table(h_, nullptr, &n), "bl_dist_table");
+        std::vector<float> f(static_cast<size_t>(n));
+        check(bl_dist_table(h_, f.data(), &n), "bl_dist_table");
+        return f;
+    }
+    const OccupancyGrid& source() const { return src_; }                        // the map of the last setDistances (empty before it)
 
     int widthInCells() const { int w = 0, h = 0; bl_dist_shape(h_, &w, &h); return w; }
     int heightInCells() const { int w = 0, h = 0; bl_dist_shape(h_, &w, &h); return h; }
@@ -470,7 +498,18 @@ public:
     }
     bl_dist* device() const { return h_; }
 private:
+    struct EuclideanTag {};
+    ObstacleDistanceGrid(int max_cells, EuclideanTag) : h_(nullptr), maxCells_(max_cells), hostValid_(false)
+    {
+        check(bl_dist_create_euclidean(default_ctx(), max_cells, &h_), "bl_dist_create_euclidean");
+    }
+    void create()
+    {
+        if (maxCells_ > 0) check(bl_dist_create_euclidean(default_ctx(), maxCells_, &h_), "bl_dist_create_euclidean");
+        else check(bl_dist_create(default_ctx(), &h_), "bl_dist_create");
+    }
     bl_dist* h_;
+    int maxCells_;
     OccupancyGrid src_;
     mutable std::vector<float> host_;
     mutable bool hostValid_;

@@ -60,7 +60,8 @@ public:
     Path planPathOptimal(const Pose& start, const Pose& goal, int32_t obstacle_gain = NAV_OBSTACLE_GAIN, uint32_t* cost = nullptr) const
     {
         if (cost) *cost = NAV_UNREACHED;
-        if (!isValidGoal(goal)) {
+        const ObstacleDistanceGrid& dist = clearanceGrid();
+        if (!isValidGoalOn(dist, goal)) {
             Path failedPath;
             failedPath.utime = utime_now_us();
             failedPath.path_length = 1;
@@ -68,7 +69,7 @@ public:
             return failedPath;
         }
         NavigationFieldT<Pose, Path> field;
-        field.computeToPose(distances_, nav_params(searchParams_, obstacle_gain, 0), goal);
+        field.computeToPose(dist, nav_params(searchParams_, obstacle_gain, 0), goal);
         typename NavigationFieldT<Pose, Path>::Result r = field.path(start);
         if (cost) *cost = r.cost;
         return r.path;
@@ -79,7 +80,7 @@ public:
     Path shortcutPath(const Path& path, double clearance, int max_span = 64, int waypoint_cost = 1024, int64_t* cost = nullptr) const
     {
         PathShortcutT<Path, Pose> sc(shortcut_params(clearance, max_span, waypoint_cost));
-        return sc.shortcut(path, distances_, cost);
+        return sc.shortcut(path, clearanceGrid(), cost);
     }
     Path shortcutPath(const Path& path) const { return shortcutPath(path, searchParams_.minDistanceToObstacle); }
     // planPathOptimal followed by shortcutPath
@@ -90,18 +91,36 @@ public:
     }
     Path planPathShortcut(const Pose& start, const Pose& goal) const { return planPathShortcut(start, goal, searchParams_.minDistanceToObstacle); }
 
-    bool isValidGoal(const Pose& goal) const                                // motion_planner.cpp:52-74
+    bool isValidGoal(const Pose& goal) const { return isValidGoalOn(distances_, goal); }   // motion_planner.cpp:52-74
+
+    // (extension) Metric clearance: planPathOptimal, shortcutPath and planPathShortcut read an exact Euclidean distance grid, capped at
+    // max_cells cells, that setMap transforms beside the L1 grid -- robotRadius then means metres (on a 5 cm map the L1 grid calls a
+    // cell 0.112 m from an obstacle "farther than 0.2 m").  planPathOptimal's goal test is isValidGoal's expression on that grid.
+    // planPath, isValidGoal, isPathSafe and plan_path_to_frontier* stay on the L1 grid, unchanged.  Off by default; max_cells <= 0
+    // turns it off again.
+    void setMetricClearance(int max_cells = 64)
+    {
+        metricOn_ = max_cells > 0;
+        if (!metricOn_) { metric_ = ObstacleDistanceGrid(); return; }
+        metric_ = ObstacleDistanceGrid::euclidean(max_cells);
+        if (distances_.source().widthInCells() > 0) metric_.setDistances(distances_.source());
+    }
+    bool metricClearance() const { return metricOn_; }
+    const ObstacleDistanceGrid& metricDistances() const { return metric_; }  // the Euclidean grid (an untransformed L1 grid while off)
+
+    // isValidGoal against `dist`: the L1 grid (isValidGoal itself) or, for planPathOptimal under metric clearance, the Euclidean one
+    bool isValidGoalOn(const ObstacleDistanceGrid& dist, const Pose& goal) const
     {
         float dx = goal.x - prev_goal_.x, dy = goal.y - prev_goal_.y;
         float distanceFromPrev = std::sqrt(dx * dx + dy * dy);
         if (num_frontiers_ != 1 && distanceFromPrev < 2 * searchParams_.minDistanceToObstacle) return false;
-        PointT<float> o = distances_.originInGlobalFrame();
+        PointT<float> o = dist.originInGlobalFrame();
         int32_t cell[2];
-        cell[0] = static_cast<int>((static_cast<double>(goal.x) - o.x) * distances_.cellsPerMeter());   // grid_utils.hpp:33-38
-        cell[1] = static_cast<int>((static_cast<double>(goal.y) - o.y) * distances_.cellsPerMeter());
-        if (distances_.isCellInGrid(cell[0], cell[1])) {
+        cell[0] = static_cast<int>((static_cast<double>(goal.x) - o.x) * dist.cellsPerMeter());   // grid_utils.hpp:33-38
+        cell[1] = static_cast<int>((static_cast<double>(goal.y) - o.y) * dist.cellsPerMeter());
+        if (dist.isCellInGrid(cell[0], cell[1])) {
             float d = 0;
-            check(bl_dist_gather(distances_.device(), cell, 1, &d), "bl_dist_gather");
+            check(bl_dist_gather(dist.device(), cell, 1, &d), "bl_dist_gather");
             return d > params_.robotRadius;
         }
         return false;
@@ -124,7 +143,11 @@ public:
         return true;
     }
 
-    void setMap(const OccupancyGrid& map) { distances_.setDistances(map); }   // motion_planner.cpp:99-102
+    void setMap(const OccupancyGrid& map)                                   // motion_planner.cpp:99-102
+    {
+        distances_.setDistances(map);
+        if (metricOn_) metric_.setDistances(map);
+    }
     const SearchParams& searchParams() const { return searchParams_; }
     void setParams(const MotionPlannerParams&)                              // motion_planner.cpp:105-110 reads params_, not the argument
     {
@@ -153,9 +176,12 @@ public:
 private:
     // num_frontiers / prev_goal are uninitialised in the reference (motion_planner.hpp:164-165); defined here as "one
     // frontier, previous goal far away" so that isValidGoal's proximity test is off until the setters are called.
-    void init_state() { num_frontiers_ = 1; prev_goal_.utime = 0; prev_goal_.x = 1e9f; prev_goal_.y = 1e9f; prev_goal_.theta = 0; }
+    const ObstacleDistanceGrid& clearanceGrid() const { return metricOn_ ? metric_ : distances_; }
+    void init_state() { metricOn_ = false; num_frontiers_ = 1; prev_goal_.utime = 0; prev_goal_.x = 1e9f; prev_goal_.y = 1e9f; prev_goal_.theta = 0; }
 
     ObstacleDistanceGrid distances_;
+    ObstacleDistanceGrid metric_;
+    bool metricOn_;
     MotionPlannerParams params_;
     SearchParams searchParams_;
     size_t num_frontiers_;

@@ -606,6 +606,31 @@ int bl_dist_frame(const bl_dist* d, float* meters_per_cell, float* cells_per_met
  * current transform.  (NULL before the first request on a grid that has never been transformed.) */
 void* bl_dist_device_ptr(bl_dist* d);
 
+/* ------------------------------------------------------------------ Euclidean distance grid  (no counterpart in the reference)
+ * The grid above is the reference's: an L1 transform shown as 0.1 per cell whatever the cell size.  The search keeps it.  A grid
+ * made by bl_dist_create_euclidean is the exact Euclidean transform in metres, capped at max_cells = R cells (1 .. 254):
+ *   Sources are the cells with log-odds >= 0 (those of bl_dist_set_distances); off-grid cells are no sources.
+ *   d2(c)   = min over sources s of (x_c - x_s)^2 + (y_c - y_s)^2, exact integers
+ *   code(c) = d2(c) when d2(c) <= R^2, else FAR = R^2 + 1; 0xFFFF for every cell when the map has no source (uint16)
+ *   f[k]    = (float)(sqrt((double)k) * (double)meters_per_cell), k = 0 .. R^2 + 1: the table has R^2 + 2 entries
+ *   The float view (bl_dist_download, bl_dist_gather, bl_dist_device_ptr) is f[code], -1.0f for 0xFFFF.  f[FAR] is a LOWER BOUND of
+ *   a far cell's distance, not its distance.
+ * It is an ordinary bl_dist handle: bl_dist_set_distances transforms the whole map every time (no incremental form:
+ * bl_dist_debug_stats counts `full`, bl_dist_debug_bound reports "not formed", bl_dist_forget changes nothing), the grid limits are
+ * bl_dist's own.  The navigation field, the local planner over such a field and the path shortcut take it; bl_navfield_compute*
+ * returns BL_ERR_ARG when maxDistanceWithCost > minDistanceToObstacle and maxDistanceWithCost > f[R^2] (a penalty would be priced
+ * from the far bound).  Everything else that takes a bl_dist is defined on the L1 grid and returns BL_ERR_ARG for a Euclidean one:
+ * bl_astar_search*, bl_plan_path_to_frontier, bl_pf_init_uniform, bl_pf_set_recovery. */
+#define BL_DIST_L1 0
+#define BL_DIST_EUCLIDEAN 1
+#define BL_EDT_MAX_CELLS 254
+int bl_dist_create_euclidean(bl_ctx* ctx, int max_cells, bl_dist** out);   /* max_cells outside 1 .. 254: BL_ERR_ARG */
+int bl_dist_metric(const bl_dist* d, int* metric, int* max_cells);         /* L1 grids: BL_DIST_L1, 0 */
+int bl_dist_download_codes(bl_dist* d, uint16_t* out);                     /* n(c) of either metric, width * height words (synchronises) */
+/* the float table the codes index, after a transform: *n = width + height + 1 entries for an L1 grid, R^2 + 2 for a Euclidean one;
+ * f may be NULL */
+int bl_dist_table(const bl_dist* d, float* f, int* n);
+
 /* ------------------------------------------------------------------ search_for_path  (src/planning/astar.hpp:58-61, astar.cpp:9-274)
  * out_path[0] is always the start pose; *out_len == 1 means "no path" (lcmtypes/robot_path_t.lcm:7).  If the path is
  * longer than cap, *out_len is the full length and only cap poses are written.  stats (optional, 2 x int64): pops,
