@@ -217,6 +217,14 @@ class ShortcutParams(C.Structure):
 assert C.sizeof(ShortcutParams) == 16
 
 
+class LFieldParams(C.Structure):
+    """bl_lfield_params_t: sigma (metres), the cap in cells, the source threshold and the peak of the likelihood field (16 bytes)."""
+    _fields_ = [("sigma", C.c_float), ("max_cells", C.c_int32), ("occ_min", C.c_int32), ("peak", C.c_int32)]
+
+
+assert C.sizeof(LFieldParams) == 16
+
+
 class RBSlamResult(C.Structure):
     """bl_rbslam_result_t: what one update of the Rao-Blackwellized SLAM hands back (64 bytes)."""
     _fields_ = [("moved", C.c_int32), ("resampled", C.c_int32), ("best", C.c_int32), ("pad", C.c_int32), ("best_pose", Pose),
@@ -425,6 +433,13 @@ SIGNATURES = {
     "bl_shortcut_debug_visible": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "bl_shortcut_debug_path": (C.c_int, [_vp]),
     "bl_shortcut_last_device_ms": (C.c_int, [_vp, _P(C.c_float), _P(C.c_float)]),
+    "bl_lfield_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_lfield_destroy": (None, [_vp]),
+    "bl_lfield_set_params": (C.c_int, [_vp, _P(LFieldParams)]),
+    "bl_lfield_compute": (C.c_int, [_vp, _vp]),
+    "bl_lfield_grid": (_vp, [_vp]),
+    "bl_lfield_table": (C.c_int, [_vp, _vp, _P(C.c_int)]),
+    "bl_lfield_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
     "bl_viewgain_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_viewgain_destroy": (None, [_vp]),
     "bl_viewgain_set_params": (C.c_int, [_vp, _P(ViewGainParams)]),

@@ -16,59 +16,14 @@
 //               stopping at the first dy with dy^2 >= best: every later candidate is at least dy^2, so the stop is exact.
 //
 // Integers only; no workgroup waits for another; the result does not depend on the launch shape.
-#include "bl_internal.h"
-
-#define EDT_TX 64            // columns of a tile = lanes of a wave
-#define EDT_TY 64            // rows of a tile
-#define EDT_WAVES 4
-#define EDT_ROW_THREADS 256
-#define EDT_ROW_WORDS 1024   // 64-bit source words of a row: rows up to 65536 cells (bl_dist: W + H < 65535)
+#include "bl_edt_dev.h"
 
 __global__ __launch_bounds__(EDT_ROW_THREADS) void k_edt_rows(const int8_t* __restrict__ cells, uint8_t* __restrict__ g, unsigned int* __restrict__ has_source,
                                                              int W, int R)
 {
     __shared__ unsigned long long s_mask[EDT_ROW_WORDS];
     __shared__ int s_any;
-    const int y = blockIdx.x;
-    const int8_t* __restrict__ row = cells + (size_t)y * W;
-    const int words = (W + 63) >> 6;
-    if (threadIdx.x == 0) s_any = 0;
-    __syncthreads();
-    bool any = false;
-    for (int x = threadIdx.x; x < words * 64; x += EDT_ROW_THREADS) {             // whole waves: the ballot needs every lane of a word
-        const bool src = x < W && row[x] >= 0;
-        const unsigned long long m = __ballot(src);
-        if ((threadIdx.x & 63) == 0) { s_mask[x >> 6] = m; any = any || m != 0ull; }
-    }
-    if (any) s_any = 1;
-    __syncthreads();
-    if (threadIdx.x == 0 && s_any) atomicOr(has_source, 1u);
-    const int cap = R + 1;
-    for (int x = threadIdx.x; x < W; x += EDT_ROW_THREADS) {
-        const int wi = x >> 6, b = x & 63;
-        int best = cap;
-        // nearest source at or left of x
-        unsigned long long m = s_mask[wi] & (~0ull >> (63 - b));
-        if (m) best = min(best, b - (63 - __clzll((long long)m)));
-        else {
-            int base = b + 1;                                                      // distance from x to bit 63 of the word before
-            for (int k = wi - 1; k >= 0 && base < best; --k, base += 64) {
-                m = s_mask[k];
-                if (m) { best = min(best, base + __clzll((long long)m)); break; }
-            }
-        }
-        // nearest source at or right of x
-        m = s_mask[wi] & (~0ull << b);
-        if (m) best = min(best, (int)__ffsll((unsigned long long)m) - 1 - b);
-        else {
-            int base = 64 - b;                                                     // distance from x to bit 0 of the next word
-            for (int k = wi + 1; k < words && base < best; ++k, base += 64) {
-                m = s_mask[k];
-                if (m) { best = min(best, base + (int)__ffsll((unsigned long long)m) - 1); break; }
-            }
-        }
-        g[(size_t)y * W + x] = (uint8_t)best;
-    }
+    edt_rows_body(cells, g, has_source, W, R, 0, s_mask, &s_any);
 }
 
 __global__ __launch_bounds__(EDT_TX * EDT_WAVES) void k_edt_cols(const uint8_t* __restrict__ g, const unsigned int* __restrict__ has_source,
@@ -77,13 +32,7 @@ __global__ __launch_bounds__(EDT_TX * EDT_WAVES) void k_edt_cols(const uint8_t* 
     extern __shared__ uint8_t s_g[];                                               // [(EDT_TY + 2 R)][EDT_TX]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = blockIdx.x * EDT_TX + lane, y0 = blockIdx.y * EDT_TY;
-    const int rows = EDT_TY + 2 * R;
-    const int cap = R + 1;
-    for (int r = wave; r < rows; r += EDT_WAVES) {
-        const int y = y0 - R + r;
-        s_g[r * EDT_TX + lane] = (x < W && y >= 0 && y < H) ? g[(size_t)y * W + x] : (uint8_t)cap;
-    }
-    __syncthreads();
+    edt_cols_stage(g, s_g, W, H, R);
     if (x >= W) return;
     const bool none = *has_source == 0u;
     const int far = R * R + 1;
@@ -91,16 +40,7 @@ __global__ __launch_bounds__(EDT_TX * EDT_WAVES) void k_edt_cols(const uint8_t* 
         const int y = y0 + ly;
         if (y >= H) break;
         if (none) { codes[(size_t)y * W + x] = (uint16_t)0xFFFF; continue; }
-        const uint8_t* __restrict__ col = s_g + (R + ly) * EDT_TX + lane;
-        const int g0 = col[0];
-        int best = g0 * g0;
-        for (int dy = 1; dy <= R; ++dy) {
-            const int d2 = dy * dy;
-            if (d2 >= best) break;
-            const int a = col[-dy * EDT_TX], b = col[dy * EDT_TX];
-            const int m = min(a, b);
-            best = min(best, m * m + d2);
-        }
+        const int best = edt_col_d2(s_g + (R + ly) * EDT_TX + lane, R);
         codes[(size_t)y * W + x] = (uint16_t)(best < far ? best : far);
     }
 }

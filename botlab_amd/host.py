@@ -187,7 +187,8 @@ class OccupancyGrid:
 
     def close(self):
         if self.h:
-            self.ctx.lib.bl_grid_destroy(self.h)
+            if getattr(self, "owns_handle", True):                     # (a LikelihoodField's grid belongs to the field)
+                self.ctx.lib.bl_grid_destroy(self.h)
             self.h = None
 
 
@@ -1082,6 +1083,70 @@ class PathShortcut:
         if self.h:
             self.ctx.lib.bl_shortcut_destroy(self.h)
             self.h = None
+
+
+class LikelihoodField:
+    """Likelihood field (bl_lfield_*, include/botlab_hip.h): an int8 grid whose cells hold peak * exp(-d^2 / (2 sigma^2)) of their
+    distance d to the nearest cell with log-odds >= occ_min, cut off beyond max_cells cells.  compute(grid) returns an OccupancyGrid
+    that ParticleFilter.updateFilter / updateBegin and ScanMatcher.match* take where the map went.  It is not a map: it has no free /
+    unknown distinction, so seeding, recovery, mapping, frontiers and the distance grids keep taking the real grid."""
+
+    MAX_CELLS = 64
+
+    def __init__(self, sigma=0.1, max_cells=None, occ_min=1, peak=127, ctx=None):
+        self.ctx = ctx or default_context()
+        self.sigma, self.max_cells, self.occ_min, self.peak = float(sigma), max_cells, int(occ_min), int(peak)
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_lfield_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        self.grid_ = None
+        if max_cells is not None:
+            self._set_params()
+
+    def _set_params(self):
+        p = _capi.LFieldParams(self.sigma, int(self.max_cells), self.occ_min, self.peak)
+        check(self.ctx.lib.bl_lfield_set_params(self.h, C.byref(p)))
+
+    def compute(self, grid):
+        """The field of `grid` as it stands (enqueued; nothing waits).  The returned OccupancyGrid does not own its handle: it is the
+        same object from call to call while the shape stays the same, and it dies with this field."""
+        if self.max_cells is None:       # ceil(3 sigma cells_per_meter) in 1 .. 64, fixed here (1e-6 of slack: 3 * 0.1 * 20 is 6, not 7)
+            self.max_cells = int(min(max(math.ceil(3.0 * self.sigma * float(grid.cpm) - 1e-6), 1), self.MAX_CELLS))
+            self._set_params()
+        check(self.ctx.lib.bl_lfield_compute(self.h, grid.h))
+        raw = self.ctx.lib.bl_lfield_grid(self.h)
+        g = self.grid_
+        if g is None or g.h is None or g.h.value != raw or (g.width, g.height) != (grid.width, grid.height):
+            g = OccupancyGrid.__new__(OccupancyGrid)
+            g.ctx, g.h, g.owns_handle = self.ctx, C.c_void_p(raw), False
+            self.grid_ = g
+        g.width, g.height, g.mpc, g.cpm, g.origin = grid.width, grid.height, grid.mpc, grid.cpm, grid.origin
+        return g
+
+    def grid(self):
+        """The OccupancyGrid of the last compute (None before the first)."""
+        return self.grid_
+
+    def table(self):
+        """int8 [max_cells^2 + 2] of the last compute: the field's value by squared distance in cells; the last entry (FAR) is 0."""
+        n = C.c_int()
+        out = np.zeros(self.MAX_CELLS * self.MAX_CELLS + 2, np.int8)
+        check(self.ctx.lib.bl_lfield_table(self.h, out.ctypes.data, C.byref(n)))
+        return out[:n.value].copy()
+
+    def lastDeviceMs(self):
+        """Device time of the last compute in ms (waits for it)."""
+        ms = C.c_float()
+        check(self.ctx.lib.bl_lfield_last_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_lfield_destroy(self.h)
+            self.h = None
+            if self.grid_ is not None:
+                self.grid_.h = None
+                self.grid_ = None
 
 
 def nav_min_traversable_cells(distances, searchParams):

@@ -74,6 +74,14 @@ public:
         host_.assign(static_cast<size_t>(width_) * height_, 0);
         allocate();
     }
+    // A view of a grid the library owns (LikelihoodFieldT's field, likelihood_field.hpp), with the frame of `frameOf`: the same
+    // accessors; reads download from it (after markDeviceWritten()); the destructor leaves the grid alone.  Not to be written
+    // through.  Copying a view makes an ordinary grid with a buffer of its own.
+    struct View {};
+    OccupancyGrid(View, const bl_grid* grid, const OccupancyGrid& frameOf)
+        : h_(const_cast<bl_grid*>(grid)), width_(frameOf.width_), height_(frameOf.height_), metersPerCell_(frameOf.metersPerCell_),
+          cellsPerMeter_(frameOf.cellsPerMeter_), origin_(frameOf.origin_), host_(static_cast<size_t>(frameOf.width_) * frameOf.height_, 0),
+          hostValid_(false), deviceValid_(true), owned_(false) {}
     OccupancyGrid(const OccupancyGrid& o) : h_(nullptr) { copyFrom(o); }
     OccupancyGrid& operator=(const OccupancyGrid& o) { if (this != &o) { release(); copyFrom(o); } return *this; }
     ~OccupancyGrid() { release(); }
@@ -159,6 +167,7 @@ private:
     PointT<float> origin_;
     mutable std::vector<CellOdds> host_;      // host mirror, synchronised lazily
     mutable bool hostValid_, deviceValid_;
+    bool owned_ = true;                       // false: a View, the library's grid
 
     int cellIndex(int x, int y) const { return y * width_ + x; }
     void allocate()
@@ -168,7 +177,7 @@ private:
         deviceValid_ = false;
         syncToDevice();
     }
-    void release() { if (h_) { bl_grid_destroy(h_); h_ = nullptr; } }
+    void release() { if (h_ && owned_) bl_grid_destroy(h_); h_ = nullptr; owned_ = true; }
     void copyFrom(const OccupancyGrid& o)
     {
         o.syncToHost();
@@ -260,6 +269,12 @@ public:
         uint64_t seed = 0;                                                      // reference: std::random_device
         std::ifstream rnd("/dev/urandom", std::ios::binary);
         if (rnd) rnd.read(reinterpret_cast<char*>(&seed), sizeof(seed));
+        check(bl_pf_init_at_pose(h_, &p, seed), "bl_pf_init_at_pose");
+    }
+    // (extension) the same with the seed given: a run that can be repeated
+    void initializeFilterAtPose(const Pose& pose, uint64_t seed)
+    {
+        bl_pose_xyt_t p = pose_in(pose);
         check(bl_pf_init_at_pose(h_, &p, seed), "bl_pf_init_at_pose");
     }
     // (extension) global localization: the particles spread uniformly over the free cells of `map` (log-odds < 0) and, when

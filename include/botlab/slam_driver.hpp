@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "botlab_dropin.hpp"
+#include "likelihood_field.hpp"
 #include "scan_matcher.hpp"
 
 namespace botlab_hip {
@@ -377,6 +378,19 @@ public:
     const bl_scan_match_moments_t& lastScanMatchMoments() const { return lastMoments_; }
     const Pose& correctedPose() const { return corrected_; }
 
+    // (extension) Likelihood field (LikelihoodFieldT, likelihood_field.hpp): the filter's update -- and the scan
+    // matcher's match, when setScanMatching is on -- read a smoothed field of the map where the map went.  With a map from a file
+    // (localization-only) the field is computed once, from the map as loaded; otherwise after every map update, so that the field of
+    // iteration k exists before the update of iteration k + 1.  Mapping, seeding, recovery, the global match over the map and the
+    // published map keep the real grid.  Every iteration is then the call-by-call updateFilter.  Off by default, and with it off
+    // nothing the driver does changes; set before the first iteration.
+    void setLikelihoodField(bool on, const bl_lfield_params_t& p) { lfieldOn_ = on; lfieldParams_ = p; }
+    bool likelihoodFieldActive() const { return static_cast<bool>(lfield_); }
+    const OccupancyGrid& sensorMap() const { return lfield_ ? lfield_->grid() : grid_; }     // what the filter's update reads
+    // (extension) The seed of the filter's first cloud, for runs that can be repeated (the reference, and the default here, take
+    // it from the OS).  Set before the first iteration.
+    void setFilterSeed(uint64_t seed) { seeded_ = true; seed_ = seed; }
+
     // The oldest queued scan can be processed once the pose source covers the time of its first ray (slam.cpp:163-188).
     bool isReadyToUpdate() const
     {
@@ -399,7 +413,7 @@ public:
         if (scanMatching()) correctOdometry();
         if (globalSearching()) {                        // global localization, not converged yet: filter only, the map is left alone
             before_ = now_;
-            now_ = pf_.updateFilter(odomAtScan_, scan_, grid_);
+            now_ = pf_.updateFilter(odomAtScan_, scan_, sensorMap());
             if (globalCluster_) { searchByCluster(); return; }
             announce();
             globalConverged_ = spreadConverged();
@@ -411,7 +425,7 @@ public:
         }
         if (kidnapOn_) {                                // recovery on: the map only from an update that did not inject
             before_ = now_;
-            now_ = pf_.updateFilter(filterOdometry(), scan_, grid_);
+            now_ = pf_.updateFilter(filterOdometry(), scan_, sensorMap());
             announce();
             if (pf_.recoveryState().p_inject > 0.0) ++heldMaps_;
             else extendMap(false);
@@ -480,6 +494,12 @@ private:
     bool matchPriorSet_ = false, matchSubCell_ = false;
     bl_scan_match_prior_t matchPrior_ = bl_scan_match_prior_t();
     bl_scan_match_moments_t lastMoments_ = bl_scan_match_moments_t();
+    // likelihood field: switch and parameters; the field (made when the poses start); the seed of the first cloud, if given
+    bool lfieldOn_ = false;
+    bl_lfield_params_t lfieldParams_ = default_lfield_params();
+    std::unique_ptr<LikelihoodFieldT> lfield_;
+    bool seeded_ = false;
+    uint64_t seed_ = 0;
 
     bool scanMatching() const { return matching_ && !global_ && !how_.posesGiven; }
     const Pose& filterOdometry() const { return scanMatching() ? corrected_ : odomAtScan_; }
@@ -503,9 +523,9 @@ private:
             bl_scan_match_prior_t prior = matchPrior_;
             if (!matchPriorSet_) prior.half_life = 64;
             if (matchSubCell_) prior.want_moments = 1;
-            lastMatch_ = matcher_->matchWithPrior(scan_, centre, grid_, matchParams_, prior, &lastMoments_);
+            lastMatch_ = matcher_->matchWithPrior(scan_, centre, sensorMap(), matchParams_, prior, &lastMoments_);
         } else {
-            lastMatch_ = matcher_->match(scan_, centre, grid_, matchParams_);
+            lastMatch_ = matcher_->match(scan_, centre, sensorMap(), matchParams_);
         }
         ++matches_;
         bl_pose_xyt_t to = lastMatch_.pose;
@@ -586,7 +606,14 @@ private:
         now_.utime = scan_.times.back();
         if (globalSearching() && globalMatch_) matchOverTheMap();
         if (globalSearching()) pf_.initializeFilterUniformly(grid_, 0.0f, before_.utime);
-        else { pf_.initializeFilterAtPose(before_); startRecovery(); }
+        else {
+            if (seeded_) pf_.initializeFilterAtPose(before_, seed_); else pf_.initializeFilterAtPose(before_);
+            startRecovery();
+        }
+        if (lfieldOn_ && !how_.posesGiven) {
+            lfield_.reset(new LikelihoodFieldT(lfieldParams_));
+            lfield_->compute(grid_);
+        }
         if (adaptive_ && !how_.posesGiven) { pf_.enableAdaptive(); adaptiveOn_ = true; }
         how_.started = true;
     }
@@ -603,12 +630,12 @@ private:
     {
         if (how_.posesGiven || !how_.mapKnown) return false;
         before_ = now_;
-        if (!how_.odometryOnly && fused_ && !adaptiveOn_ && !scanMatching()) {
+        if (!how_.odometryOnly && fused_ && !adaptiveOn_ && !scanMatching() && !lfield_) {
             pf_.updateFilterBegin(odomAtScan_, scan_, grid_);
             if (!waiting_.empty()) prefetch_scan(waiting_.front());      // the next scan is already queued: it rides along
             return true;
         }
-        now_ = how_.odometryOnly ? pf_.updateFilterActionOnly(filterOdometry()) : pf_.updateFilter(filterOdometry(), scan_, grid_);
+        now_ = how_.odometryOnly ? pf_.updateFilterActionOnly(filterOdometry()) : pf_.updateFilter(filterOdometry(), scan_, sensorMap());
         announce();
         return false;
     }
@@ -623,6 +650,7 @@ private:
         } else {
             mapping_.updateMap(scan_, now_, grid_);
         }
+        if (lfield_ && !how_.mapFromFile) lfield_->compute(grid_);
         how_.mapKnown = true;
         if (mapsMade_++ % kMapEvery == 0 && out_.slamMap) out_.slamMap(grid_.template toLCM<GridMsg>());
     }

@@ -1264,6 +1264,54 @@ int bl_shortcut_debug_path(const bl_shortcut* sc);
  * HIP events around the launches; BL_ERR_STATE before the first */
 int bl_shortcut_last_device_ms(const bl_shortcut* sc, float* ms, float* ms_visible);
 
+/* ------------------------------------------------------------------ likelihood field (no reference counterpart)
+ * A smoothed map for whatever scores ray end points: every cell holds a Gaussian of its distance to the nearest occupied cell
+ * (Probabilistic Robotics 6.4; AMCL's likelihood-field model).  The sensor model of bl_pf_update* and the scan matcher score a
+ * ray by the one cell its end point falls into; on a map whose walls are a cell or two thick that score is a needle around the
+ * true pose and a noisy plateau everywhere else.  On the field it falls off smoothly over max_cells cells.
+ *   Sources: the cells of the map with log-odds >= occ_min.  (The Euclidean distance grid's sources are log-odds >= 0: here an
+ *     unknown cell at 0 must not attract rays.)  Cells off the grid are no sources.
+ *   Code: d2(c) = the minimum over the sources of dx^2 + dy^2, in exact integers; code(c) = d2 when d2 <= R^2, else
+ *     FAR = R^2 + 1 (R = max_cells).  A map without a source has code FAR everywhere.
+ *   Table: T[k] = (int8) floor(peak * exp(-(k * m^2) / (2 s^2)) + 0.5) for k = 0 .. R^2, with m = (double)meters_per_cell of the
+ *     map and s = (double)sigma, formed in double on the host with the C library's exp;  T[R^2 + 1] = 0.  R^2 + 2 entries;
+ *     T[0] = peak.
+ *   Field: field(c) = T[code(c)]: 0 .. peak, never negative.  A map without a source gives 0 everywhere.
+ *   Result: a bl_grid owned by the handle, with the map's shape and the map's frame (metres per cell, cells per metre, origin) as
+ *     of the call.  The grid object stays the same from call to call while the shape stays the same; a compute on a map of
+ *     another shape destroys it and makes a new one (pointers to the old one dangle).  Every compute starts a new lineage of that
+ *     grid and marks its zero-framed mirror stale, as an upload does: a filter update after a recompute scores the new field.
+ *   It is an int8 grid like any other, and everything that scores ray end points against a const bl_grid* takes it as it
+ *     stands: bl_pf_update / bl_pf_update_begin (a value v > 0 scores as the log-odds v does) and bl_scanmatch_match,
+ *     _match_prior and _match_wide (they score max(cell, 0)).
+ *   What the field is NOT: a map.  It has no free / unknown distinction -- every cell away from a wall is 0, which an occupancy
+ *     grid reads as "unknown" -- and no negative cell.  bl_pf_init_uniform, bl_pf_set_recovery, bl_mapping_update*, the
+ *     frontiers, the view gain and the distance grids keep taking the real map; nothing enforces this.
+ *   bl_lfield_compute is three launches on the ctx stream (the source word's reset, a row pass, a column pass that ends in the
+ *     table look-up) and waits for nothing on the host, except that a compute whose table differs from the last one's (other
+ *     parameters, another meters_per_cell) first waits for that earlier table's upload.  Integers only on the device.
+ *   Refused with BL_ERR_ARG: by bl_lfield_set_params a sigma that is not finite or not > 0, max_cells outside
+ *     1 .. BL_LFIELD_MAX_CELLS, occ_min or peak outside 1 .. 127 (the handle keeps what it had); by bl_lfield_compute a null
+ *     pointer, a map of another ctx, a map wider than 65536 cells.  BL_ERR_STATE: compute before bl_lfield_set_params, table and
+ *     last_device_ms before the first compute. */
+#define BL_LFIELD_MAX_CELLS 64
+typedef struct bl_lfield_params_t {
+    float sigma;                       /* metres, finite, > 0 */
+    int32_t max_cells;                 /* R: 1 .. BL_LFIELD_MAX_CELLS */
+    int32_t occ_min;                   /* 1 .. 127: a cell is a source when its log-odds is >= occ_min */
+    int32_t peak;                      /* 1 .. 127: the field's value on a source */
+} bl_lfield_params_t;                  /* 16 bytes */
+typedef struct bl_lfield bl_lfield;
+int bl_lfield_create(bl_ctx* ctx, bl_lfield** out);
+void bl_lfield_destroy(bl_lfield* lf);                                 /* destroys the field grid with it */
+int bl_lfield_set_params(bl_lfield* lf, const bl_lfield_params_t* params);   /* refused: the handle keeps what it had */
+int bl_lfield_compute(bl_lfield* lf, const bl_grid* map);
+const bl_grid* bl_lfield_grid(const bl_lfield* lf);                    /* NULL before the first compute */
+/* the table of the last compute: *n = R^2 + 2, and those n entries to T unless T is NULL (room for up to 4098) */
+int bl_lfield_table(const bl_lfield* lf, int8_t* T, int* n);
+/* device time of the last bl_lfield_compute: HIP events around its launches (waits for that compute to finish) */
+int bl_lfield_last_device_ms(const bl_lfield* lf, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
