@@ -225,6 +225,20 @@ class LFieldParams(C.Structure):
 assert C.sizeof(LFieldParams) == 16
 
 
+class ObsLayerParams(C.Structure):
+    """bl_obslayer_params_t: the range cut, the occupancy threshold, the tolerance box, the time to live and the hits needed (20 bytes)."""
+    _fields_ = [("max_range", C.c_float), ("occ_min", C.c_int32), ("tol_cells", C.c_int32), ("ttl_scans", C.c_int32), ("min_hits", C.c_int32)]
+
+
+class ObsLayerStats(C.Structure):
+    """bl_obslayer_stats_t: the counter, the last update's rays by class and its two sets, the live cells (40 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("valid_rays", C.c_int32), ("rays_by_class", C.c_int32 * 5), ("hit_cells", C.c_int32),
+                ("cleared_cells", C.c_int32), ("live_cells", C.c_int32)]
+
+
+assert C.sizeof(ObsLayerParams) == 20 and C.sizeof(ObsLayerStats) == 40
+
+
 class RBSlamResult(C.Structure):
     """bl_rbslam_result_t: what one update of the Rao-Blackwellized SLAM hands back (64 bytes)."""
     _fields_ = [("moved", C.c_int32), ("resampled", C.c_int32), ("best", C.c_int32), ("pad", C.c_int32), ("best_pose", Pose),
@@ -440,6 +454,18 @@ SIGNATURES = {
     "bl_lfield_grid": (_vp, [_vp]),
     "bl_lfield_table": (C.c_int, [_vp, _vp, _P(C.c_int)]),
     "bl_lfield_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_obslayer_create": (C.c_int, [_vp, C.c_int, C.c_int, _P(_vp)]),
+    "bl_obslayer_destroy": (None, [_vp]),
+    "bl_obslayer_set_params": (C.c_int, [_vp, _P(ObsLayerParams)]),
+    "bl_obslayer_reset": (C.c_int, [_vp]),
+    "bl_obslayer_update": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose)]),
+    "bl_obslayer_compose": (C.c_int, [_vp, _vp, _vp]),
+    "bl_obslayer_classes": (C.c_int, [_vp, _vp, _P(C.c_int)]),
+    "bl_obslayer_stats": (C.c_int, [_vp, _P(ObsLayerStats)]),
+    "bl_obslayer_live_cells": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int)]),
+    "bl_obslayer_download": (C.c_int, [_vp, _vp, _vp, _P(C.c_uint32)]),
+    "bl_obslayer_upload": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
+    "bl_obslayer_last_device_ms": (C.c_int, [_vp, _P(C.c_float), _P(C.c_float)]),
     "bl_viewgain_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_viewgain_destroy": (None, [_vp]),
     "bl_viewgain_set_params": (C.c_int, [_vp, _P(ViewGainParams)]),

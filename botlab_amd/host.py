@@ -1149,6 +1149,100 @@ class LikelihoodField:
                 self.grid_ = None
 
 
+class ObstacleLayer:
+    """Obstacle layer (bl_obslayer_*, include/botlab_hip.h): what the scan sees and the map does not.  update(grid, scan, pose) casts
+    the scan against the static map and keeps a per-cell hit / clear / expire state; compose(grid, out) writes the map with 127 where
+    the layer is live into another OccupancyGrid, which the distance grids (and so every planner) take where the map went.  Rays at
+    or beyond max_range neither hit nor clear; an obstacle that left with nothing behind it goes by expiry (ttl_scans)."""
+
+    OFF, EXPLAINED, NOVEL, THROUGH, OUTSIDE = 0, 1, 2, 3, 4
+
+    def __init__(self, width, height, max_range=5.0, occ_min=1, tol_cells=1, ttl_scans=50, min_hits=1, ctx=None):
+        self.ctx = ctx or default_context()
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_obslayer_create(self.ctx.h, self.width, self.height, C.byref(h)))
+        self.h = h
+        try:
+            self.setParams(max_range, occ_min, tol_cells, ttl_scans, min_hits)
+        except _capi.BotlabHipError:
+            self.close()
+            raise
+
+    def setParams(self, max_range, occ_min, tol_cells, ttl_scans, min_hits):
+        """Refused (BotlabHipError raised): the layer keeps the parameters it had."""
+        p = _capi.ObsLayerParams(float(np.float32(max_range)), int(occ_min), int(tol_cells), int(ttl_scans), int(min_hits))
+        check(self.ctx.lib.bl_obslayer_set_params(self.h, C.byref(p)))
+        self.params = p
+
+    def update(self, grid, scan, pose):
+        """One update from `scan` taken at `pose` against the static map `grid` (enqueued; nothing waits for the kernels)."""
+        ls = scan.as_c()
+        check(self.ctx.lib.bl_obslayer_update(self.h, grid.h, C.byref(ls), C.byref(pose)))
+
+    def compose(self, grid, out=None):
+        """`grid` with 127 where the layer is live, written into `out` (another OccupancyGrid of the same shape; made when None)."""
+        if out is None:
+            out = OccupancyGrid(ctx=self.ctx, _raw=(grid.width, grid.height, grid.mpc, grid.cpm, grid.origin[0], grid.origin[1]))
+        check(self.ctx.lib.bl_obslayer_compose(self.h, grid.h, out.h))
+        out.mpc, out.cpm, out.origin = grid.mpc, grid.cpm, grid.origin
+        return out
+
+    def classes(self):
+        """uint8 per ray of the last update's scan, in scan order (OFF, EXPLAINED, NOVEL, THROUGH, OUTSIDE)."""
+        n = C.c_int()
+        check(self.ctx.lib.bl_obslayer_classes(self.h, None, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint8)
+        check(self.ctx.lib.bl_obslayer_classes(self.h, out.ctypes.data, C.byref(n)))
+        return out[:n.value]
+
+    def stats(self):
+        """dict: n, valid (rays), classes [5], hs (|Hs|), clr (|C \\ Hs|), live (cells)."""
+        s = _capi.ObsLayerStats()
+        check(self.ctx.lib.bl_obslayer_stats(self.h, C.byref(s)))
+        return dict(n=int(s.n), valid=int(s.valid_rays), classes=[int(v) for v in s.rays_by_class], hs=int(s.hit_cells),
+                    clr=int(s.cleared_cells), live=int(s.live_cells))
+
+    def live_cells(self, cap=None):
+        """int32 [m][2] of the live cells (x, y) in row-major order; at most cap of them."""
+        n = C.c_int()
+        if cap is None:
+            check(self.ctx.lib.bl_obslayer_live_cells(self.h, None, 0, C.byref(n)))
+            cap = n.value
+        out = np.zeros((max(int(cap), 1), 2), np.int32)
+        check(self.ctx.lib.bl_obslayer_live_cells(self.h, out.ctypes.data, int(cap), C.byref(n)))
+        return out[:min(n.value, int(cap))]
+
+    def download(self):
+        """(count uint8 [H][W], last uint32 [H][W], n)."""
+        count = np.empty((self.height, self.width), np.uint8)
+        last = np.empty((self.height, self.width), np.uint32)
+        n = C.c_uint32()
+        check(self.ctx.lib.bl_obslayer_download(self.h, count.ctypes.data, last.ctypes.data, C.byref(n)))
+        return count, last, int(n.value)
+
+    def upload(self, count, last, n):
+        """Replaces the state (tests, a restored layer): saturation, expiry and the counter's end are reached this way."""
+        count = np.ascontiguousarray(count, dtype=np.uint8)
+        last = np.ascontiguousarray(last, dtype=np.uint32)
+        assert count.shape == (self.height, self.width) and last.shape == (self.height, self.width)
+        check(self.ctx.lib.bl_obslayer_upload(self.h, count.ctypes.data, last.ctypes.data, C.c_uint32(int(n))))
+
+    def reset(self):
+        check(self.ctx.lib.bl_obslayer_reset(self.h))
+
+    def lastDeviceMs(self):
+        """(update_ms, compose_ms): device time of the last update and the last compose (waits for them)."""
+        u, c = C.c_float(), C.c_float()
+        check(self.ctx.lib.bl_obslayer_last_device_ms(self.h, C.byref(u), C.byref(c)))
+        return u.value, c.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_obslayer_destroy(self.h)
+            self.h = None
+
+
 def nav_min_traversable_cells(distances, searchParams):
     """n_min: the smallest L1 distance (in cells) that is traversable under searchParams -- f[n] > minDistanceToObstacle * 1.000001
     with the distance grid's own table f[n] = f[n - 1] + 0.1f; None if no distance of this grid is."""
@@ -1592,6 +1686,7 @@ class MotionPlanner:
         self.prev_goal = make_pose(1e9, 1e9, 0.0)
         self.map_ = None
         self.metric_ = None              # setMetricClearance: a second, Euclidean grid for the field and the shortcut
+        self.composed_ = None            # setMapWithObstacles: the planner's own grid of map and layer
         self.setParams(self.params_)
 
     def setParams(self, params):
@@ -1605,6 +1700,17 @@ class MotionPlanner:
         self.map_ = grid
         if self.metric_ is not None:
             self.metric_.setDistances(grid)
+
+    def setMapWithObstacles(self, grid, layer):
+        """setMap of `grid` with the cells an ObstacleLayer holds live written over it as occupied (127): composed into a grid the
+        planner owns, then the ordinary setMap.  The caller's update comes first (layer.update(grid, scan, pose)); `grid` is untouched."""
+        c = self.composed_
+        if c is None or c.h is None or (c.width, c.height) != (grid.width, grid.height):
+            if c is not None:
+                c.close()
+            c = None
+        self.composed_ = layer.compose(grid, c)
+        self.setMap(self.composed_)
 
     def setMetricClearance(self, max_cells=64):
         """Metric clearance for planPathOptimal, shortcutPath and planPathShortcut: they read an exact Euclidean distance grid

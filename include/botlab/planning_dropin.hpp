@@ -148,6 +148,16 @@ public:
         distances_.setDistances(map);
         if (metricOn_) metric_.setDistances(map);
     }
+    // (extension) setMap of `map` with the cells an obstacle layer (ObstacleLayerT, obstacle_layer.hpp) holds live written over it as
+    // occupied: composed into a grid this planner owns, then the ordinary setMap.  The caller's layer.update(map, scan, pose) comes
+    // first; `map` is untouched.
+    template <class Layer>
+    void setMapWithObstacles(const OccupancyGrid& map, Layer& layer)
+    {
+        layer.compose(map, composed_);
+        setMap(composed_);
+    }
+    const OccupancyGrid& composedMap() const { return composed_; }          // of the last setMapWithObstacles
     const SearchParams& searchParams() const { return searchParams_; }
     void setParams(const MotionPlannerParams&)                              // motion_planner.cpp:105-110 reads params_, not the argument
     {
@@ -181,6 +191,7 @@ private:
 
     ObstacleDistanceGrid distances_;
     ObstacleDistanceGrid metric_;
+    OccupancyGrid composed_;
     bool metricOn_;
     MotionPlannerParams params_;
     SearchParams searchParams_;

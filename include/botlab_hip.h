@@ -1312,6 +1312,96 @@ int bl_lfield_table(const bl_lfield* lf, int8_t* T, int* n);
 /* device time of the last bl_lfield_compute: HIP events around its launches (waits for that compute to finish) */
 int bl_lfield_last_device_ms(const bl_lfield* lf, float* ms);
 
+/* ------------------------------------------------------------------ obstacle layer (no reference counterpart)
+ * What the scan sees and the map does not.  Every planner reads a bl_dist, which comes from a bl_grid: whatever stands in mapped
+ * free space -- a box, a person, a second robot -- does not exist for them when the map is a loaded one, and under SLAM appears only
+ * after enough scans and stays behind as a trail.  The layer is the fast, transient state beside the slow map: the beam model's
+ * "short reading" (a return that ends in mapped free space with nothing mapped in front of it) found by casting the scan against
+ * the static map, a per-cell hit / clear / expire state, and an int8 grid composed of map and layer that goes wherever the map
+ * went.
+ *   State, for a layer of width x height cells: count (uint8) and last (uint32, 0 = never hit) per cell, one update counter n
+ *     (uint32, 0 at creation).  A map of another shape is refused (BL_ERR_ARG).
+ *   bl_obslayer_update(layer, map, scan, pose) sets n = n + 1 and then:
+ *   a. Rays.  The valid rays are the scan matcher's: 0.15f < range < max_range.  Geometry is the scan matcher's at heading step 0,
+ *     one pose for the whole scan (no moving-scan interpolation), float32 with one rounding per operation:
+ *       (px, py) = ((float)(((double)x - origin_x) * cells_per_meter), likewise y)           the matcher's grid position
+ *       a = wrap_to_pi(theta - theta_r);  fx = (range * cosf(a)) * cells_per_meter + px;  fy likewise with sinf
+ *       has = |fx| < 2^30 and |fy| < 2^30;  start cell s = (trunc(px), trunc(py));  end cell e = (trunc(fx), trunc(fy)).
+ *   b. Walk.  Cells k = 0 .. K - 1, K = max(|dx|, |dy|), of the reference's Bresenham variant from s to e (mapping.cpp:101-127),
+ *     start included, end excluded: the major axis advances k, the minor floor((2 k dmin + dmaj) / (2 dmaj)).  A static cell is
+ *     occupied iff its log-odds is >= occ_min.  Cells outside the grid are skipped everywhere: neither occupied nor cleared.
+ *     first = the least k whose cell is inside the grid and occupied, else K.
+ *   c. Class, of every ray of the scan in scan order:
+ *       BL_OBS_OFF 0        not valid, or has false
+ *       BL_OBS_EXPLAINED 1  some occupied cell of the grid lies within Chebyshev distance tol_cells of e (e itself may lie outside)
+ *       BL_OBS_THROUGH 3    not explained and first < K: the return contradicts map and pose; it contributes nothing
+ *       BL_OBS_NOVEL 2      not explained, first == K, e inside the grid
+ *       BL_OBS_OUTSIDE 4    not explained, first == K, e outside the grid
+ *   d. Sets and transition.  C = the in-grid walk cells k < first of the rays of class 1, 2 and 4;  Hs = the end cells of the
+ *     class-2 rays.  Both are sets (a cell hit by five rays is hit once), so the transition depends neither on the order of the
+ *     rays nor on the launch shape:
+ *       c in Hs:      count = (last != 0 and n - last < ttl_scans) ? min(count + 1, 255) : 1;  last = n     (a hit beats a clear)
+ *       c in C \ Hs:  count = 0;  last = 0
+ *       otherwise unchanged.
+ *     live(c) = count >= min_hits and last != 0 and n - last < ttl_scans, with the current n (n - last in uint32 arithmetic).
+ *     Rays at or beyond max_range neither hit nor clear: expiry is what removes an obstacle that left with nothing behind it.
+ *   bl_obslayer_compose(layer, map, out): out(c) = 127 where live(c), else map(c).  `out` is another bl_grid of the same shape; it
+ *     takes the map's frame.  Every compose starts a new lineage of `out` and marks its zero-framed mirror stale, as an upload does,
+ *     so an incremental bl_dist_set_distances and the filter's mirror never see the previous composition.
+ *   Refused with BL_ERR_ARG: by bl_obslayer_set_params a max_range that is not finite or not > 0.15, occ_min outside 1 .. 127,
+ *     tol_cells outside 0 .. 16, ttl_scans outside 1 .. 65535, min_hits outside 1 .. 255 (the handle keeps what it had); by
+ *     bl_obslayer_update a map of another shape or ctx, ceil((double)max_range * cells_per_meter) > 4096, more than 4096 valid
+ *     rays, a pose member that is not finite (n and the state are untouched); by bl_obslayer_compose an `out` that is the map or
+ *     of another shape.  BL_ERR_STATE: update, compose, stats and live_cells before bl_obslayer_set_params; update when
+ *     n == 2^32 - 1 (n and the state are untouched; bl_obslayer_reset starts over); last_device_ms for a call not yet made.
+ *   Calls are stream-ordered on the ctx stream and wait for nothing on the host, except that an update first waits for the
+ *     previous update's scan to have left its pinned block; the readers (classes, stats, live_cells, download) synchronise.
+ *   What the layer is not: a tracker (no velocities), and nothing here touches the map update, the filter, the navigation field or
+ *     the local planner -- they take the composed grid as they take any bl_grid. */
+#define BL_OBSLAYER_MAX_RAYS 4096
+#define BL_OBSLAYER_MAX_REACH 4096     /* cells: ceil(max_range * cells_per_meter) */
+#define BL_OBSLAYER_MAX_TOL 16
+#define BL_OBS_OFF 0
+#define BL_OBS_EXPLAINED 1
+#define BL_OBS_NOVEL 2
+#define BL_OBS_THROUGH 3
+#define BL_OBS_OUTSIDE 4
+typedef struct bl_obslayer_params_t {
+    float max_range;                   /* metres, finite, > 0.15 */
+    int32_t occ_min;                   /* 1 .. 127: a static cell is occupied when its log-odds is >= occ_min */
+    int32_t tol_cells;                 /* 0 .. 16: a return this close (Chebyshev) to an occupied cell is the map's */
+    int32_t ttl_scans;                 /* 1 .. 65535: a cell not hit for this many updates is dead */
+    int32_t min_hits;                  /* 1 .. 255: hits in a row (none expired, none cleared) before a cell is live */
+} bl_obslayer_params_t;                /* 20 bytes: offsets 0, 4, 8, 12, 16 */
+typedef struct bl_obslayer_stats_t {
+    uint32_t n;                        /* the update counter */
+    int32_t valid_rays;                /* of the last update */
+    int32_t rays_by_class[5];          /* of the last update, indexed by BL_OBS_* */
+    int32_t hit_cells;                 /* |Hs| of the last update (0 after a reset or an upload) */
+    int32_t cleared_cells;             /* |C \ Hs| of the last update (0 after a reset or an upload) */
+    int32_t live_cells;                /* with the current n */
+} bl_obslayer_stats_t;                 /* 40 bytes: offsets 0, 4, 8, 28, 32, 36 */
+typedef struct bl_obslayer bl_obslayer;
+int bl_obslayer_create(bl_ctx* ctx, int width, int height, bl_obslayer** out);
+void bl_obslayer_destroy(bl_obslayer* layer);
+int bl_obslayer_set_params(bl_obslayer* layer, const bl_obslayer_params_t* params);   /* refused: the handle keeps what it had */
+int bl_obslayer_reset(bl_obslayer* layer);                             /* all cells never hit, n = 0 */
+int bl_obslayer_update(bl_obslayer* layer, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* pose);
+int bl_obslayer_compose(bl_obslayer* layer, const bl_grid* map, bl_grid* out_grid);
+/* the classes of the last update's rays, in scan order: *n_rays = the scan's num_ranges (0 before the first update and after a
+ * reset), and that many bytes to `out` unless it is NULL */
+int bl_obslayer_classes(bl_obslayer* layer, uint8_t* out, int* n_rays);
+int bl_obslayer_stats(bl_obslayer* layer, bl_obslayer_stats_t* out);
+/* the live cells in row-major order (y, then x) as x, y pairs: *count = how many there are, the first min(cap, *count) to xy */
+int bl_obslayer_live_cells(bl_obslayer* layer, int32_t* xy, int cap, int* count);
+/* the state: width * height entries each, row-major; any pointer may be NULL */
+int bl_obslayer_download(bl_obslayer* layer, uint8_t* count, uint32_t* last, uint32_t* n);
+/* Replaces the state.  For tests and for restoring a saved layer: saturation (count 255), expiry (n - last around ttl_scans) and the
+ * counter's end (n = 2^32 - 1) are reached through it, not by millions of updates.  The sets of the last update are forgotten. */
+int bl_obslayer_upload(bl_obslayer* layer, const uint8_t* count, const uint32_t* last, uint32_t n);
+/* device time of the last update and of the last compose: HIP events around their launches (waits for them); either may be NULL */
+int bl_obslayer_last_device_ms(const bl_obslayer* layer, float* update_ms, float* compose_ms);
+
 #ifdef __cplusplus
 }
 #endif
