@@ -239,6 +239,50 @@ class ObsLayerStats(C.Structure):
 assert C.sizeof(ObsLayerParams) == 20 and C.sizeof(ObsLayerStats) == 40
 
 
+class ObsTracksParams(C.Structure):
+    """bl_obstracks_params_t: blob area limits, the gate, the two filter gains, confirmation, coasting and the speed of "moving" (32 bytes)."""
+    _fields_ = [("min_cells", C.c_int32), ("max_cells", C.c_int32), ("gate_cells", C.c_int32), ("alpha", C.c_int32), ("beta", C.c_int32),
+                ("confirm_hits", C.c_int32), ("max_missed", C.c_int32), ("min_speed", C.c_int32)]
+
+
+class ObsTracksCompose(C.Structure):
+    """bl_obstracks_compose_t: how far ahead to stamp, and the box around the robot's cell that stays clear (16 bytes)."""
+    _fields_ = [("horizon", C.c_int32), ("robot_x", C.c_int32), ("robot_y", C.c_int32), ("keep_clear", C.c_int32)]
+
+
+class ObsTrack(C.Structure):
+    """bl_obstrack_t: one slot (56 bytes)."""
+    _fields_ = [("id", C.c_uint32), ("px", C.c_int32), ("py", C.c_int32), ("vx", C.c_int32), ("vy", C.c_int32), ("hits", C.c_int32),
+                ("missed", C.c_int32), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("flags", C.c_int32), ("slot", C.c_int32)]
+
+
+class ObsBlob(C.Structure):
+    """bl_obsblob_t: one blob of the last update (56 bytes)."""
+    _fields_ = [("sum_x", C.c_int64), ("sum_y", C.c_int64), ("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32),
+                ("y1", C.c_int32), ("cx", C.c_int32), ("cy", C.c_int32), ("eligible", C.c_int32), ("track", C.c_int32), ("rep", C.c_int32)]
+
+
+class ObsTracksStats(C.Structure):
+    """bl_obstracks_stats_t (56 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("next_id", C.c_uint32), ("live_cells", C.c_int32), ("blobs", C.c_int32), ("eligible", C.c_int32),
+                ("dropped", C.c_int32), ("matched", C.c_int32), ("born", C.c_int32), ("deleted", C.c_int32), ("unborn", C.c_int32),
+                ("tracks", C.c_int32), ("confirmed", C.c_int32), ("refused", C.c_int32), ("rounds", C.c_int32)]
+
+
+class ObsTracksState(C.Structure):
+    """bl_obstracks_state_t: the counters that go with the slots (16 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("next_id", C.c_uint32), ("fresh", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(ObsTracksParams) == 32 and C.sizeof(ObsTracksCompose) == 16 and C.sizeof(ObsTrack) == 56 and C.sizeof(ObsBlob) == 56
+assert C.sizeof(ObsTracksStats) == 56 and C.sizeof(ObsTracksState) == 16
+OBSTRACK_DTYPE = [("id", "<u4"), ("px", "<i4"), ("py", "<i4"), ("vx", "<i4"), ("vy", "<i4"), ("hits", "<i4"), ("missed", "<i4"), ("area", "<i4"),
+                  ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("flags", "<i4"), ("slot", "<i4")]
+OBSBLOB_DTYPE = [("sum_x", "<i8"), ("sum_y", "<i8"), ("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("cx", "<i4"),
+                 ("cy", "<i4"), ("eligible", "<i4"), ("track", "<i4"), ("rep", "<i4")]
+
+
 class RBSlamResult(C.Structure):
     """bl_rbslam_result_t: what one update of the Rao-Blackwellized SLAM hands back (64 bytes)."""
     _fields_ = [("moved", C.c_int32), ("resampled", C.c_int32), ("best", C.c_int32), ("pad", C.c_int32), ("best_pose", Pose),
@@ -466,6 +510,19 @@ SIGNATURES = {
     "bl_obslayer_download": (C.c_int, [_vp, _vp, _vp, _P(C.c_uint32)]),
     "bl_obslayer_upload": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
     "bl_obslayer_last_device_ms": (C.c_int, [_vp, _P(C.c_float), _P(C.c_float)]),
+    "bl_obstracks_create": (C.c_int, [_vp, C.c_int, C.c_int, _P(_vp)]),
+    "bl_obstracks_destroy": (None, [_vp]),
+    "bl_obstracks_set_params": (C.c_int, [_vp, _P(ObsTracksParams)]),
+    "bl_obstracks_reset": (C.c_int, [_vp]),
+    "bl_obstracks_update": (C.c_int, [_vp, _vp]),
+    "bl_obstracks_compose": (C.c_int, [_vp, _vp, _vp, _vp, _P(ObsTracksCompose)]),
+    "bl_obstracks_tracks": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int)]),
+    "bl_obstracks_blobs": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int)]),
+    "bl_obstracks_labels": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int)]),
+    "bl_obstracks_stats": (C.c_int, [_vp, _P(ObsTracksStats)]),
+    "bl_obstracks_download": (C.c_int, [_vp, _vp, _P(ObsTracksState)]),
+    "bl_obstracks_upload": (C.c_int, [_vp, _vp, _P(ObsTracksState)]),
+    "bl_obstracks_last_device_ms": (C.c_int, [_vp, _P(C.c_float), _P(C.c_float)]),
     "bl_viewgain_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_viewgain_destroy": (None, [_vp]),
     "bl_viewgain_set_params": (C.c_int, [_vp, _P(ViewGainParams)]),

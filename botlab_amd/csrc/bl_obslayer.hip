@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "bl_internal.h"
+#include "bl_obslayer_dev.h"
 
 #define OBS_MIN_RANGE 0.15f               // moving_laser_scan.cpp:24, as the scan matcher
 #define OBS_RAY_WAVES 4                   // rays (waves) per workgroup of k_obs_rays
@@ -29,12 +30,6 @@
 #define OBS_NOVEL 2
 #define OBS_THROUGH 3
 #define OBS_OUTSIDE 4
-
-struct obs_live_rule { uint32_t n, ttl, min_hits; };
-__device__ __forceinline__ bool obs_live(const obs_live_rule& q, uint32_t count, uint32_t last)
-{
-    return count >= q.min_hits && last != 0u && q.n - last < q.ttl;
-}
 
 // cell k of the walk from (sx, sy) towards (ex, ey): bl_mapping.hip's closed form
 struct obs_walk { int sx, sy, stepx, stepy, dx, dy; };
@@ -254,22 +249,6 @@ __global__ __launch_bounds__(256) void k_obs_livewrite(const uint8_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-struct bl_obslayer {
-    bl_ctx* ctx;
-    int W, H;
-    bl_obslayer_params_t params; bool have_params;
-    uint32_t n;
-    uint8_t* d_count; uint32_t* d_last; uint32_t* d_hit; uint32_t* d_clr;
-    float* d_rays; uint8_t* d_classes; int ray_cap;         // ranges | thetas, ray_cap each
-    float* h_rays;                                          // pinned, the same layout
-    int4* d_rows; int* d_totals;
-    int32_t* d_xy; int xy_cap;
-    int last_rays, last_valid;                              // of the last update (0 after a reset)
-    bool sets_valid;                                        // the stamps speak of update n (not after a reset or an upload)
-    bool updated, composed, staged;
-    hipEvent_t ev_stage, ev_ua, ev_ub, ev_ca, ev_cb;
-};
-
 extern "C" int bl_obslayer_create(bl_ctx* ctx, int width, int height, bl_obslayer** out)
 {
     BL_CHECK_ARG(ctx != nullptr && out != nullptr);
@@ -489,6 +468,20 @@ static int obs_count(bl_obslayer* ol, int totals[3])
     BL_HIP(hipGetLastError());
     BL_HIP(hipMemcpyAsync(totals, ol->d_totals, 3 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));
+    return BL_OK;
+}
+
+// the same two launches and the write pass, for a list that stays on the device (bl_obslayer_dev.h)
+int obs_live_list_enqueue(bl_obslayer* ol, int32_t* d_xy, int cap)
+{
+    bl_ctx* ctx = ol->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_obs_rowcount, dim3((unsigned int)ol->H), dim3(256), 0, ctx->stream, (const uint8_t*)ol->d_count, (const uint32_t*)ol->d_last,
+                       (const uint32_t*)ol->d_hit, (const uint32_t*)ol->d_clr, ol->W, obs_rule(ol), 0, ol->d_rows);   // the stamps are not read
+    hipLaunchKernelGGL(k_obs_rowscan, dim3(1), dim3(1024), 0, ctx->stream, ol->d_rows, ol->H, ol->d_totals);
+    hipLaunchKernelGGL(k_obs_livewrite, dim3((unsigned int)ol->H), dim3(256), 0, ctx->stream, (const uint8_t*)ol->d_count, (const uint32_t*)ol->d_last,
+                       ol->W, obs_rule(ol), (const int4*)ol->d_rows, d_xy, cap);
+    BL_HIP(hipGetLastError());
     return BL_OK;
 }
 

@@ -1243,6 +1243,115 @@ class ObstacleLayer:
             self.h = None
 
 
+class ObstacleTracker:
+    """Obstacle tracks (bl_obstracks_*, include/botlab_hip.h): the layer's live cells grouped into blobs, the blobs followed from
+    update to update, and a composed grid that also holds where the moving ones are heading.  update() once after each
+    layer.update(...); compose(grid, out, horizon, robot_cell) where layer.compose went.  Every parameter is an untuned knob."""
+
+    CONFIRMED, MOVING, MATCHED, BORN = 1, 2, 4, 8
+    MAX_TRACKS, MAX_BLOBS, MAX_CELLS = 256, 1024, 65536
+    PARAMS = ("min_cells", "max_cells", "gate_cells", "alpha", "beta", "confirm_hits", "max_missed", "min_speed")
+
+    def __init__(self, layer, min_cells=1, max_cells=65536, gate_cells=4, alpha=128, beta=64, confirm_hits=3, max_missed=3, min_speed=16):
+        self.layer = layer
+        self.ctx = layer.ctx
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_obstracks_create(self.ctx.h, layer.width, layer.height, C.byref(h)))
+        self.h = h
+        try:
+            self.setParams(min_cells, max_cells, gate_cells, alpha, beta, confirm_hits, max_missed, min_speed)
+        except _capi.BotlabHipError:
+            self.close()
+            raise
+
+    def setParams(self, min_cells, max_cells, gate_cells, alpha, beta, confirm_hits, max_missed, min_speed):
+        """Refused (BotlabHipError raised): the tracker keeps the parameters it had."""
+        p = _capi.ObsTracksParams(int(min_cells), int(max_cells), int(gate_cells), int(alpha), int(beta), int(confirm_hits), int(max_missed),
+                                  int(min_speed))
+        check(self.ctx.lib.bl_obstracks_set_params(self.h, C.byref(p)))
+        self.params = p
+
+    def update(self):
+        """One update from the layer's state as it stands (enqueued; nothing waits for the kernels).  Two refusals are found on the
+        device only -- more than MAX_CELLS live cells, a birth that would need id 2^32 - 1 -- and do not raise: the slots stay as they
+        were, there are no blobs, and stats()["refused"] is 1 or 2.  A caller that never reads stats() never learns of them."""
+        check(self.ctx.lib.bl_obstracks_update(self.h, self.layer.h))
+
+    def compose(self, grid, out=None, horizon=0, robot_cell=(0, 0), keep_clear=-1):
+        """layer.compose(grid, out), and 127 also where the confirmed moving tracks' cells will be within `horizon` updates, except
+        within keep_clear cells (Chebyshev) of robot_cell."""
+        if out is None:
+            out = OccupancyGrid(ctx=self.ctx, _raw=(grid.width, grid.height, grid.mpc, grid.cpm, grid.origin[0], grid.origin[1]))
+        c = _capi.ObsTracksCompose(int(horizon), int(robot_cell[0]), int(robot_cell[1]), int(keep_clear))
+        check(self.ctx.lib.bl_obstracks_compose(self.h, self.layer.h, grid.h, out.h, C.byref(c)))
+        out.mpc, out.cpm, out.origin = grid.mpc, grid.cpm, grid.origin
+        return out
+
+    def tracks(self):
+        """The occupied slots in slot order: a structured array (id, px, py, vx, vy, hits, missed, area, x0, y0, x1, y1, flags, slot)."""
+        out = np.zeros(self.MAX_TRACKS, _capi.OBSTRACK_DTYPE)
+        n = C.c_int()
+        check(self.ctx.lib.bl_obstracks_tracks(self.h, out.ctypes.data, self.MAX_TRACKS, C.byref(n)))
+        return out[:n.value]
+
+    def blobs(self):
+        """The kept blobs of the last update in rank order: a structured array (sum_x, sum_y, area, x0, y0, x1, y1, cx, cy, eligible,
+        track, rep)."""
+        out = np.zeros(self.MAX_BLOBS, _capi.OBSBLOB_DTYPE)
+        n = C.c_int()
+        check(self.ctx.lib.bl_obstracks_blobs(self.h, out.ctypes.data, self.MAX_BLOBS, C.byref(n)))
+        return out[:n.value]
+
+    def labels(self):
+        """int32 per live cell of the last update, in the order of layer.live_cells(): its blob's rank, -1 when dropped."""
+        n = C.c_int()
+        check(self.ctx.lib.bl_obstracks_labels(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.int32)
+        check(self.ctx.lib.bl_obstracks_labels(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
+
+    def stats(self):
+        s = _capi.ObsTracksStats()
+        check(self.ctx.lib.bl_obstracks_stats(self.h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in _capi.ObsTracksStats._fields_}
+
+    def download(self):
+        """(slots: all 256 as a structured array, dict(n, next_id, fresh))."""
+        out = np.zeros(self.MAX_TRACKS, _capi.OBSTRACK_DTYPE)
+        st = _capi.ObsTracksState()
+        check(self.ctx.lib.bl_obstracks_download(self.h, out.ctypes.data, C.byref(st)))
+        return out, dict(n=int(st.n), next_id=int(st.next_id), fresh=int(st.fresh))
+
+    def upload(self, slots, n, next_id, fresh):
+        """Replaces the state (tests, a restored tracker); the blobs of the last update are forgotten."""
+        slots = np.ascontiguousarray(slots, dtype=_capi.OBSTRACK_DTYPE)
+        assert slots.shape == (self.MAX_TRACKS,)
+        st = _capi.ObsTracksState(int(n), int(next_id), int(bool(fresh)), 0)
+        check(self.ctx.lib.bl_obstracks_upload(self.h, slots.ctypes.data, C.byref(st)))
+
+    def reset(self):
+        check(self.ctx.lib.bl_obstracks_reset(self.h))
+
+    def lastDeviceMs(self):
+        """(update_ms, compose_ms): device time of the last update and the last compose (waits for them)."""
+        u, c = C.c_float(), C.c_float()
+        check(self.ctx.lib.bl_obstracks_last_device_ms(self.h, C.byref(u), C.byref(c)))
+        return u.value, c.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_obstracks_destroy(self.h)
+            self.h = None
+
+
+def track_to_metric(track, grid, scan_period):
+    """(x, y, vx, vy) in metres and metres per second of one record of ObstacleTracker.tracks(), in the frame of `grid` (anything with
+    origin and mpc), one update taking scan_period seconds.  Double arithmetic on the host."""
+    mpc = float(grid.mpc)
+    return (float(grid.origin[0]) + int(track["px"]) / 256.0 * mpc, float(grid.origin[1]) + int(track["py"]) / 256.0 * mpc,
+            int(track["vx"]) / 256.0 * mpc / float(scan_period), int(track["vy"]) / 256.0 * mpc / float(scan_period))
+
+
 def nav_min_traversable_cells(distances, searchParams):
     """n_min: the smallest L1 distance (in cells) that is traversable under searchParams -- f[n] > minDistanceToObstacle * 1.000001
     with the distance grid's own table f[n] = f[n - 1] + 0.1f; None if no distance of this grid is."""
@@ -1710,6 +1819,21 @@ class MotionPlanner:
                 c.close()
             c = None
         self.composed_ = layer.compose(grid, c)
+        self.setMap(self.composed_)
+
+    def setMapWithTracks(self, grid, layer, tracker, horizon, robot_pose, keep_clear=2):
+        """setMapWithObstacles, with the cells that the tracker's confirmed moving tracks will cover within `horizon` updates occupied
+        too (ObstacleTracker.compose), except within keep_clear cells of the robot's own cell.  The caller's layer.update and
+        tracker.update come first."""
+        c = self.composed_
+        if c is None or c.h is None or (c.width, c.height) != (grid.width, grid.height):
+            if c is not None:
+                c.close()
+            c = None
+        assert tracker.layer is layer
+        rx = int(math.floor((float(robot_pose.x) - float(grid.origin[0])) * float(grid.cpm)))
+        ry = int(math.floor((float(robot_pose.y) - float(grid.origin[1])) * float(grid.cpm)))
+        self.composed_ = tracker.compose(grid, c, horizon=horizon, robot_cell=(rx, ry), keep_clear=keep_clear)
         self.setMap(self.composed_)
 
     def setMetricClearance(self, max_cells=64):

@@ -157,7 +157,20 @@ public:
         layer.compose(map, composed_);
         setMap(composed_);
     }
-    const OccupancyGrid& composedMap() const { return composed_; }          // of the last setMapWithObstacles
+    // (extension) setMapWithObstacles, with the cells that the confirmed moving tracks of an ObstacleTrackerT (obstacle_tracks.hpp) will
+    // cover within `horizon` updates occupied too, except within keepClear cells of the robot's own cell.  The caller's layer.update
+    // and tracker.update come first; `tracker` is the one that follows `layer` (anything else ends the program, as a failing call does).
+    template <class Layer, class Tracker>
+    void setMapWithTracks(const OccupancyGrid& map, Layer& layer, Tracker& tracker, int horizon, const Pose& robotPose, int keepClear = 2)
+    {
+        if (&tracker.layer() != &layer) { std::fprintf(stderr, "botlab_hip: setMapWithTracks: the tracker follows another layer\n"); std::abort(); }
+        const bl_pose_xyt_t p = pose_in(robotPose);
+        const int rx = static_cast<int>(std::floor((static_cast<double>(p.x) - map.originInGlobalFrame().x) * map.cellsPerMeter()));
+        const int ry = static_cast<int>(std::floor((static_cast<double>(p.y) - map.originInGlobalFrame().y) * map.cellsPerMeter()));
+        tracker.compose(map, composed_, horizon, rx, ry, keepClear);
+        setMap(composed_);
+    }
+    const OccupancyGrid& composedMap() const { return composed_; }          // of the last setMapWithObstacles / setMapWithTracks
     const SearchParams& searchParams() const { return searchParams_; }
     void setParams(const MotionPlannerParams&)                              // motion_planner.cpp:105-110 reads params_, not the argument
     {

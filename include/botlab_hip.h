@@ -1402,6 +1402,127 @@ int bl_obslayer_upload(bl_obslayer* layer, const uint8_t* count, const uint32_t*
 /* device time of the last update and of the last compose: HIP events around their launches (waits for them); either may be NULL */
 int bl_obslayer_last_device_ms(const bl_obslayer* layer, float* update_ms, float* compose_ms);
 
+/* ------------------------------------------------------------------ obstacle tracks (no reference counterpart)
+ * Velocities for what the obstacle layer sees.  The layer says where a thing that the map lacks IS; a planner that rolls out ahead
+ * over a grid frozen at the scan's instant avoids a walking person only once they stand in its way.  The tracks group the layer's
+ * live cells into blobs, follow the blobs from update to update and paint where the moving ones are heading.
+ * Integers throughout; tests/obstacle_tracks_model.py restates this comment.  Every parameter is an untuned knob.
+ *   bl_obstracks_update(tr, layer) is called once after each bl_obslayer_update and reads the layer's state on the device.
+ *   a. Blobs.  The live cells are the layer's live(c) at its current n.  A blob is a connected component of live cells under
+ *     8-connectivity; its representative is the live cell of least flat index y * W + x; the blob's rank is the row-major order of
+ *     the representatives.  Per blob: area A, sum_x, sum_y (int64), bounding box, centroid in 1/256 cell
+ *     cx = floor(256 * sum_x / A) + 128, cy likewise.  eligible = min_cells <= A <= max_cells.  The first
+ *     BL_OBSTRACKS_MAX_BLOBS blobs by rank are kept, the rest counted as dropped (their cells have label -1).
+ *   b. Tracks.  BL_OBSTRACKS_MAX_TRACKS slots; a slot is free when its id is 0.  Per track: id (from 1, never reused), position
+ *     (px, py) and velocity (vx, vy) in 1/256 cell, the velocity per update, hits and missed (both saturate at 65535), area and box
+ *     of the last matched blob.  pred = pos + vel.
+ *   c. Association: gated greedy nearest neighbour.  Candidates are (occupied slot i, eligible kept blob of rank j) with
+ *     |pred_i - c_j|^2 = d2 <= (256 * gate_cells)^2; they are taken in ascending order of the key (d2, i, j), a pair being accepted
+ *     when both ends are still free.
+ *   d. Transition, in this order.  Matched, with r = c - pred per component: pos = pred + floor(alpha * r / 256),
+ *     vel = clamp(vel + floor(beta * r / 256), -1023, 1023), hits + 1, missed = 0, box and area from the blob (floor rounds towards
+ *     minus infinity).  Unmatched track: pos = pred, missed + 1; the slot is freed when missed > max_missed.  Births: each unmatched
+ *     eligible kept blob, in rank order, takes the lowest free slot (one freed in this update included) with pos = its centroid,
+ *     vel = 0, hits = 1, missed = 0 and the next id; blobs left without a slot are counted (unborn).
+ *     Flags, set by every update for every occupied slot: BL_OBSTRACK_CONFIRMED hits >= confirm_hits, BL_OBSTRACK_MOVING
+ *     vx^2 + vy^2 >= min_speed^2, BL_OBSTRACK_MATCHED and BL_OBSTRACK_BORN by what this update did with the slot.
+ *   e. Order of calls.  The tracker remembers the layer's n.  An update is refused (BL_ERR_STATE) unless the layer's n is the
+ *     remembered value + 1 or the tracker is fresh (created, reset, or uploaded as fresh).  After bl_obslayer_reset or
+ *     bl_obslayer_upload the caller resets the tracker.
+ *   Two refusals depend on what only the device knows, and the update waits for nothing on the host: they are found on the device,
+ *     the update returns BL_OK, the tracks and the id counter stay as they were, there are no blobs (every label -1), and
+ *     bl_obstracks_stats reports refused = BL_OBSTRACKS_REFUSED_CELLS (more than BL_OBSTRACKS_MAX_CELLS live cells) or
+ *     BL_OBSTRACKS_REFUSED_IDS (a birth would need id 2^32 - 1; reached through upload, not by running).  The remembered n advances.
+ *   f. bl_obstracks_compose(tr, layer, map, out, c): bl_obslayer_compose(layer, map, out) itself -- out(c) = 127 where live(c), else
+ *     map(c), a new lineage, the mirror stale -- and then, for every live cell (x, y) of the last update whose blob was matched to or
+ *     born as a track that is CONFIRMED and MOVING, for s = 1 .. 4 * horizon: the cell
+ *     (x + floor((s * vx + 512) / 1024), y + floor((s * vy + 512) / 1024)) becomes 127 when it lies inside the grid and not
+ *     within Chebyshev distance keep_clear of (robot_x, robot_y) (keep_clear -1: nothing is skipped).  Live cells are painted
+ *     wherever they are.  Plain stores of one value.  horizon 0 is bl_obslayer_compose byte for byte.  With horizon > 0 the layer's n
+ *     must be the remembered one (BL_ERR_STATE); after a reset or an upload and before the next update nothing is stamped.
+ *   Refused with BL_ERR_ARG: parameters outside their ranges below (the handle keeps what it had); a layer of another shape or
+ *     ctx; by upload an occupied slot whose id is not below next_id or is shared, |vx| or |vy| > 1023, |px| or |py| > 2^30, hits
+ *     outside 1 .. 65535, missed outside 0 .. 255, next_id 0.  BL_ERR_STATE: update and compose before set_params on either handle,
+ *     the order of calls, last_device_ms for a call not yet made.
+ *   Calls are stream-ordered on the ctx stream; update and compose wait for nothing on the host; the readers synchronise. */
+#define BL_OBSTRACKS_MAX_BLOBS 1024
+#define BL_OBSTRACKS_MAX_CELLS 65536
+#define BL_OBSTRACKS_MAX_TRACKS 256
+#define BL_OBSTRACKS_MAX_HORIZON 64
+#define BL_OBSTRACKS_MAX_KEEP_CLEAR 64
+#define BL_OBSTRACKS_REFUSED_CELLS 1
+#define BL_OBSTRACKS_REFUSED_IDS 2
+#define BL_OBSTRACK_CONFIRMED 1
+#define BL_OBSTRACK_MOVING 2
+#define BL_OBSTRACK_MATCHED 4
+#define BL_OBSTRACK_BORN 8
+typedef struct bl_obstracks_params_t {
+    int32_t min_cells;                 /* 1 .. 65536 */
+    int32_t max_cells;                 /* min_cells .. 65536 */
+    int32_t gate_cells;                /* 1 .. 64 */
+    int32_t alpha;                     /* 0 .. 256: position gain in 1/256 */
+    int32_t beta;                      /* 0 .. 256: velocity gain in 1/256 */
+    int32_t confirm_hits;              /* 1 .. 255 */
+    int32_t max_missed;                /* 0 .. 255 */
+    int32_t min_speed;                 /* 0 .. 1023, 1/256 cell per update */
+} bl_obstracks_params_t;               /* 32 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28 */
+typedef struct bl_obstracks_compose_t {
+    int32_t horizon;                   /* 0 .. 64 updates ahead, four sub-steps each */
+    int32_t robot_x, robot_y;          /* the robot's cell (any value; read only when keep_clear >= 0) */
+    int32_t keep_clear;                /* -1 .. 64 */
+} bl_obstracks_compose_t;              /* 16 bytes: offsets 0, 4, 8, 12 */
+typedef struct bl_obstrack_t {
+    uint32_t id;                       /* 0: the slot is free */
+    int32_t px, py, vx, vy;            /* 1/256 cell; the velocity per update */
+    int32_t hits, missed;
+    int32_t area, x0, y0, x1, y1;      /* of the last matched blob (box inclusive) */
+    int32_t flags;                     /* BL_OBSTRACK_* */
+    int32_t slot;
+} bl_obstrack_t;                       /* 56 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52 */
+typedef struct bl_obsblob_t {
+    int64_t sum_x, sum_y;
+    int32_t area, x0, y0, x1, y1;      /* box inclusive */
+    int32_t cx, cy;                    /* 1/256 cell */
+    int32_t eligible;                  /* 0 or 1 */
+    int32_t track;                     /* the slot it was matched to or born as, else -1 */
+    int32_t rep;                       /* flat index of the representative */
+} bl_obsblob_t;                        /* 56 bytes: offsets 0, 8, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52 */
+typedef struct bl_obstracks_stats_t {
+    uint32_t n;                        /* the remembered layer counter */
+    uint32_t next_id;
+    int32_t live_cells;                /* of the last update */
+    int32_t blobs, eligible, dropped;  /* all blobs; eligible among the kept; beyond BL_OBSTRACKS_MAX_BLOBS */
+    int32_t matched, born, deleted, unborn;
+    int32_t tracks, confirmed;         /* occupied slots, and the confirmed among them */
+    int32_t refused;                   /* 0, or BL_OBSTRACKS_REFUSED_* of the last update */
+    int32_t rounds;                    /* mutual-best rounds of the last update that accepted a pair */
+} bl_obstracks_stats_t;                /* 56 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52 */
+typedef struct bl_obstracks_state_t {
+    uint32_t n;                        /* the remembered layer counter */
+    uint32_t next_id;                  /* >= 1 */
+    int32_t fresh;                     /* 1: the next update takes any n */
+    int32_t reserved;                  /* 0 */
+} bl_obstracks_state_t;                /* 16 bytes: offsets 0, 4, 8, 12 */
+typedef struct bl_obstracks bl_obstracks;
+int bl_obstracks_create(bl_ctx* ctx, int width, int height, bl_obstracks** out);
+void bl_obstracks_destroy(bl_obstracks* tr);
+int bl_obstracks_set_params(bl_obstracks* tr, const bl_obstracks_params_t* params);   /* refused: the handle keeps what it had */
+int bl_obstracks_reset(bl_obstracks* tr);                              /* no tracks, no blobs, ids from 1 again, fresh */
+int bl_obstracks_update(bl_obstracks* tr, bl_obslayer* layer);
+int bl_obstracks_compose(bl_obstracks* tr, bl_obslayer* layer, const bl_grid* map, bl_grid* out_grid, const bl_obstracks_compose_t* c);
+/* the occupied slots in slot order: *count = how many, the first min(cap, *count) to out */
+int bl_obstracks_tracks(bl_obstracks* tr, bl_obstrack_t* out, int cap, int* count);
+/* the kept blobs of the last update in rank order: *count = how many, the first min(cap, *count) to out */
+int bl_obstracks_blobs(bl_obstracks* tr, bl_obsblob_t* out, int cap, int* count);
+/* per live cell of the last update, in the layer's row-major list order: its blob's rank, -1 when the blob was dropped */
+int bl_obstracks_labels(bl_obstracks* tr, int32_t* out, int cap, int* count);
+int bl_obstracks_stats(bl_obstracks* tr, bl_obstracks_stats_t* out);
+/* the whole state: all BL_OBSTRACKS_MAX_TRACKS slots and the counters.  The blobs belong to an update: an upload forgets them. */
+int bl_obstracks_download(bl_obstracks* tr, bl_obstrack_t* slots, bl_obstracks_state_t* state);
+int bl_obstracks_upload(bl_obstracks* tr, const bl_obstrack_t* slots, const bl_obstracks_state_t* state);
+/* device time of the last update and of the last compose: HIP events around their launches (waits for them); either may be NULL */
+int bl_obstracks_last_device_ms(const bl_obstracks* tr, float* update_ms, float* compose_ms);
+
 #ifdef __cplusplus
 }
 #endif
