@@ -206,7 +206,13 @@ class LocalPlanResult(C.Structure):
                 f"cost={self.cost}, flags={self.flags})")
 
 
+class LocalPlanMoving(C.Structure):
+    """bl_localplan_moving_t: how the rollout's steps relate to the tracker's updates, and the margin around a moving box (16 bytes)."""
+    _fields_ = [("steps_per_update", C.c_int32), ("margin_cells", C.c_int32), ("lead_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
 assert C.sizeof(LocalPlanState) == 32 and C.sizeof(LocalPlanParams) == 56 and C.sizeof(LocalPlanResult) == 32
+assert C.sizeof(LocalPlanMoving) == 16
 
 
 class ShortcutParams(C.Structure):
@@ -483,6 +489,9 @@ SIGNATURES = {
     "bl_localplan_tables": (C.c_int, [_vp, _P(LocalPlanState), _vp, _vp]),
     "bl_localplan_debug_path": (C.c_int, [_vp]),
     "bl_localplan_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_localplan_commands_moving": (C.c_int, [_vp, _vp, _vp, _P(LocalPlanMoving), _vp, C.c_int, _vp]),
+    "bl_localplan_debug_costs_moving": (C.c_int, [_vp, _vp, _vp, _P(LocalPlanMoving), _P(LocalPlanState), _vp, _vp]),
+    "bl_localplan_debug_moving_path": (C.c_int, [_vp]),
     "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_shortcut_destroy": (None, [_vp]),
     "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),
@@ -516,6 +525,7 @@ SIGNATURES = {
     "bl_obstracks_reset": (C.c_int, [_vp]),
     "bl_obstracks_update": (C.c_int, [_vp, _vp]),
     "bl_obstracks_compose": (C.c_int, [_vp, _vp, _vp, _vp, _P(ObsTracksCompose)]),
+    "bl_obstracks_compose_static": (C.c_int, [_vp, _vp, _vp, _vp]),
     "bl_obstracks_tracks": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int)]),
     "bl_obstracks_blobs": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int)]),
     "bl_obstracks_labels": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int)]),

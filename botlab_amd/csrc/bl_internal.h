@@ -172,6 +172,11 @@ int bl_dist_view_host(const bl_dist* d, bl_dist_host_view* out);
 int bl_edt_transform(bl_ctx* ctx, const int8_t* cells, int W, int H, int R, uint8_t* g, unsigned int* has_source, uint16_t* codes);
 void bl_edt_table(int R, float mpc, std::vector<float>* out);
 
+// bl_obstracks.hip: what the local planner reads of a tracker (bl_localplan_commands_moving): its ctx, its shape, whether it has
+// parameters, and the BL_OBSTRACKS_MAX_TRACKS slots on the device
+struct bl_obstracks_view { bl_ctx* ctx; int W, H; bool have_params; const bl_obstrack_t* d_slots; };
+void bl_obstracks_view_host(const bl_obstracks* tr, bl_obstracks_view* out);
+
 // RAII-less helpers
 int bl_timer_begin(bl_ctx* ctx, int id, hipEvent_t* a, hipEvent_t* b);
 int bl_timer_end(bl_ctx* ctx, int id, hipEvent_t a, hipEvent_t b);

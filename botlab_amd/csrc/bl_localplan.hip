@@ -10,6 +10,9 @@
 //                      LDS broadcast; every visited cell's cost (-1 or the penalty) comes from the window staged in LDS (STAGED) or
 //                      from the grids; the end cell's field and the descent move from it are read from the grids, once
 //                 then the least (cost, c) key of the workgroup goes to its slot: no atomics, no floats in the reduction
+//                 MOVING (bl_localplan_commands_moving) adds a prologue -- a lane per tracker slot decides used and can-reach, the kept
+//                 slots go to LDS in slot order by ballot -- and, when they fit, a table of the kept boxes at every step beside
+//                 phase B; phase C then also tests every visited cell against the boxes of its step
 //   k_lp_finish   a thread per state: the flags of the pose's own cell, else the least key over the state's workgroups
 //   k_lp_poses    one thread: the poses of one candidate (bl_localplan_debug_rollout)
 #include <math.h>
@@ -23,8 +26,16 @@
 #define LP_RED_BYTES 64                // per wave: key cost (8), key c (4), admissible count (4)
 #define LP_LDS_FIXED (LP_TRIG_SLOTS * 8 + LP_RED_BYTES)
 #define LP_COST_NONE 0x7FFFFFFFFFFFFFFFll
+#define LP_MOV_POS_MAX (1 << 30)
+#define LP_MOV_KEPT_BYTES (BL_OBSTRACKS_MAX_TRACKS * 20)                  // lp_kept: five words per kept slot
+#define LP_MOV_BYTES (LP_MOV_KEPT_BYTES + BL_LOCALPLAN_MOVING_BYTES)
+static_assert(LP_THREADS == BL_OBSTRACKS_MAX_TRACKS, "the moving prologue has a lane per slot");
+// two workgroups with the largest window and the moving block fit a CU's 160 KiB
+static_assert(2 * (LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16 + LP_MOV_BYTES) <= 160 * 1024, "BL_LOCALPLAN_MOVING_BYTES too large");
 
 struct lp_partial { long long cost; int c; int n_adm; };
+
+struct lp_mov_div { int q; unsigned int magic; };     // steps_per_update and ceil(2^28 / q): lp_mov_offset
 
 struct lp_args {
     const uint32_t* field; const uint16_t* l1; const int32_t* table; int table_n;
@@ -40,7 +51,60 @@ struct lp_args {
     long long* costs;                             // bl_localplan_debug_costs: every candidate's cost (one state); else null
     float k_heading;                              // (float)(1024 / pi)
     float move_angle[8];
+    // MOVING only
+    const bl_obstrack_t* slots;                   // the tracker's BL_OBSTRACKS_MAX_TRACKS slots
+    lp_mov_div mq; int mmargin, mlead;            // bl_localplan_moving_t
+    int reach_r;                                  // R of the window rule, staged or not
+    int mov_off;                                  // where the moving block starts in the dynamic LDS
+    int* first_hit;                               // bl_localplan_debug_costs_moving: per candidate; else null
+    int* mpath;                                   // [state]: 0 table, 1 per step, 2 nothing kept, -1 not rolled out (the state's first workgroup writes it)
 };
+
+// a kept slot: its clamped box widened by the margin, and (vx, vy) as two int16
+struct lp_kept { int x0, y0, x1, y1, v; };
+
+// floor((t * v + 128 q) / (256 q)) without a division: floor(n / (256 q)) = floor((n >> 8) / q), and for 0 <= a < 2^20, q < 2^8,
+// floor(a / q) = (a * ceil(2^28 / q)) >> 28 (Granlund & Montgomery).  |t * v| <= 510 * 1023, so (n >> 8) + 2048 q lies in [9, 2^20).
+__device__ __forceinline__ int lp_mov_offset(int t, int v, lp_mov_div d)
+{
+    const unsigned int a = (unsigned int)(((t * v + 128 * d.q) >> 8) + 2048 * d.q);   // >> of a negative int: floor
+    return (int)(((unsigned long long)a * d.magic) >> 28) - 2048;
+}
+
+__device__ __forceinline__ int lp_mov_clamp(int v) { return v < -LP_MOV_POS_MAX ? -LP_MOV_POS_MAX : v > LP_MOV_POS_MAX ? LP_MOV_POS_MAX : v; }
+
+__device__ __forceinline__ bool lp_mov_used(const bl_obstrack_t& t)
+{
+    return t.id != 0u && (t.flags & (BL_OBSTRACK_CONFIRMED | BL_OBSTRACK_MOVING)) == (BL_OBSTRACK_CONFIRMED | BL_OBSTRACK_MOVING) &&
+           (t.flags & (BL_OBSTRACK_MATCHED | BL_OBSTRACK_BORN)) != 0;
+}
+
+__device__ __forceinline__ lp_kept lp_mov_record(const bl_obstrack_t& t, int margin)
+{
+    lp_kept r;
+    r.x0 = lp_mov_clamp(t.x0) - margin; r.y0 = lp_mov_clamp(t.y0) - margin;
+    r.x1 = lp_mov_clamp(t.x1) + margin; r.y1 = lp_mov_clamp(t.y1) + margin;
+    const int vx = min(max(t.vx, -1023), 1023), vy = min(max(t.vy, -1023), 1023);   // what every update and upload leaves; lp_mov_offset's domain
+    r.v = (vx & 0xffff) | (int)((unsigned int)vy << 16);
+    return r;
+}
+
+// is (ex, ey) inside the record's box at time t (rollout step + lead)
+__device__ __forceinline__ bool lp_mov_in_box(const lp_kept& r, int t, lp_mov_div q, int ex, int ey)
+{
+    const int ox = lp_mov_offset(t, (int)(short)(r.v & 0xffff), q), oy = lp_mov_offset(t, r.v >> 16, q);
+    return ex >= r.x0 + ox && ex <= r.x1 + ox && ey >= r.y0 + oy && ey <= r.y1 + oy;
+}
+
+// a visited cell outside the reach square (the bound is floating point): every used slot, straight from the tracker
+__device__ __noinline__ bool lp_mov_hit_all(const bl_obstrack_t* __restrict__ slots, int margin, int t, lp_mov_div q, int ex, int ey)
+{
+    for (int sl = 0; sl < BL_OBSTRACKS_MAX_TRACKS; ++sl) {
+        const bl_obstrack_t tr = slots[sl];
+        if (lp_mov_used(tr) && lp_mov_in_box(lp_mov_record(tr, margin), t, q, ex, ey)) return true;
+    }
+    return false;
+}
 
 // the flags of the pose's own cell; (cx, cy) its cell where it has one
 __device__ __forceinline__ int lp_start_flags(const lp_args& a, const bl_localplan_state_t& st, int* cx, int* cy)
@@ -55,7 +119,7 @@ __device__ __forceinline__ int lp_start_flags(const lp_args& a, const bl_localpl
 
 __device__ __forceinline__ bool lp_key_less(long long ca, int ia, long long cb, int ib) { return ca < cb || (ca == cb && ia < ib); }
 
-template <bool STAGED>
+template <bool STAGED, bool MOVING>
 __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -70,14 +134,45 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
     const bl_localplan_state_t st = a.states[state];
     int scx = 0, scy = 0;
     const int flags = lp_start_flags(a, st, &scx, &scy);
-    if (flags && !a.costs) return;                                   // nothing is rolled out (uniform over the workgroup)
+    if (flags && !a.costs) {                                         // nothing is rolled out (uniform over the workgroup)
+        if (MOVING && blk == 0 && tid == 0) a.mpath[state] = -1;
+        return;
+    }
     // the window's centre: the pose's cell, or (for the debug costs of a pose off the grid) the grid cell nearest to it
     const int side = 2 * a.win_r + 1;
     int wx0 = 0, wy0 = 0;
-    if (STAGED) {
+    int rx0 = 0, ry0 = 0;                                             // MOVING: the reach square's corner, its side 2 * reach_r + 1
+    if (STAGED || MOVING) {
         const double vx = ((double)st.pose.x - (double)a.frame.ox) * (double)a.frame.cpm, vy = ((double)st.pose.y - (double)a.frame.oy) * (double)a.frame.cpm;
         const int ccx = (int)fmin(fmax(vx, 0.0), (double)(W - 1)), ccy = (int)fmin(fmax(vy, 0.0), (double)(H - 1));
         wx0 = ccx - a.win_r; wy0 = ccy - a.win_r;
+        rx0 = ccx - a.reach_r; ry0 = ccy - a.reach_r;
+    }
+    // MOVING prologue, first half: a lane per slot decides used and can-reach; the waves' counts go where the reduction's will
+    lp_kept* s_kept = (lp_kept*)(s_raw + a.mov_off);
+    short4* s_box = (short4*)(s_raw + a.mov_off + LP_MOV_KEPT_BYTES);
+    const int rside = 2 * a.reach_r;
+    bool keep = false, used = false;
+    lp_kept rec;
+    unsigned long long keep_mask = 0ull;
+    if (MOVING) {
+        const bl_obstrack_t tr = a.slots[tid];
+        used = lp_mov_used(tr);
+        rec = lp_mov_record(tr, a.mmargin);
+        if (used) {
+            // the displacement is monotone in k per axis: the two ends bound the sweep
+            const int vx = (int)(short)(rec.v & 0xffff), vy = rec.v >> 16;
+            const int ox1 = lp_mov_offset(1 + a.mlead, vx, a.mq), oxn = lp_mov_offset(a.n_steps + a.mlead, vx, a.mq);
+            const int oy1 = lp_mov_offset(1 + a.mlead, vy, a.mq), oyn = lp_mov_offset(a.n_steps + a.mlead, vy, a.mq);
+            const long long lx = (long long)rec.x0 + min(ox1, oxn), hx = (long long)rec.x1 + max(ox1, oxn);
+            const long long ly = (long long)rec.y0 + min(oy1, oyn), hy = (long long)rec.y1 + max(oy1, oyn);
+            keep = hx >= (long long)rx0 && lx <= (long long)rx0 + rside && hy >= (long long)ry0 && ly <= (long long)ry0 + rside;
+        }
+        keep_mask = __ballot(keep);
+        const unsigned long long used_mask = __ballot(used);
+        if ((tid & 63) == 0) { s_n[tid >> 6] = __popcll(keep_mask); s_c[tid >> 6] = __popcll(used_mask); }
+    }
+    if (STAGED) {
         for (int idx = tid; idx < side * side; idx += LP_THREADS)
             s_win[idx] = (int16_t)nav_cost(a.l1, a.table, a.table_n, W, H, wx0 + idx % side, wy0 + idx / side);
     }
@@ -95,6 +190,19 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
         row[a.n_steps].x = theta;
     }
     __syncthreads();
+    // MOVING prologue, second half: the kept slots compacted in slot order
+    int kept = 0, n_used = 0;
+    bool boxed = false;
+    if (MOVING) {
+        int base = 0;
+        for (int w = 0; w < LP_THREADS / 64; ++w) {
+            if (w < (tid >> 6)) base += s_n[w];
+            kept += s_n[w]; n_used += s_c[w];
+        }
+        if (keep) s_kept[base + __popcll(keep_mask & ((1ull << (tid & 63)) - 1ull))] = rec;
+        boxed = kept > 0 && (long long)kept * a.n_steps * 8 <= (long long)BL_LOCALPLAN_MOVING_BYTES;
+        if (blk == 0 && tid == 0) a.mpath[state] = kept == 0 ? 2 : boxed ? 0 : 1;
+    }
     // B: their (cos, sin), in place
     for (int idx = tid; idx < a.jpb * stride; idx += LP_THREADS) {
         const int jl = idx / stride, k = idx - jl * stride;
@@ -104,6 +212,24 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
         s_trig[idx] = make_float2(cs, sn);
     }
     __syncthreads();
+    // MOVING, the table: every kept box at every step, clamped to the reach square and relative to its corner (an empty one is 1 > 0)
+    if (MOVING) {
+        if (boxed) {
+            for (int idx = tid; idx < kept * a.n_steps; idx += LP_THREADS) {
+                const int b = idx / a.n_steps, k = idx - b * a.n_steps;
+                const lp_kept r = s_kept[b];
+                const int t = k + 1 + a.mlead;
+                const int ox = lp_mov_offset(t, (int)(short)(r.v & 0xffff), a.mq), oy = lp_mov_offset(t, r.v >> 16, a.mq);
+                const long long lx = max((long long)r.x0 + ox, (long long)rx0) - rx0, hx = min((long long)r.x1 + ox, (long long)rx0 + rside) - rx0;
+                const long long ly = max((long long)r.y0 + oy, (long long)ry0) - ry0, hy = min((long long)r.y1 + oy, (long long)ry0 + rside) - ry0;
+                short4 bx;
+                if (lx > hx || ly > hy) { bx.x = 1; bx.y = 1; bx.z = 0; bx.w = 0; }
+                else { bx.x = (short)lx; bx.y = (short)ly; bx.z = (short)hx; bx.w = (short)hy; }
+                s_box[idx] = bx;
+            }
+        }
+        __syncthreads();
+    }
     // C: a thread per candidate
     const int i = tid & (a.nvp - 1), jl = tid / a.nvp, j = j0 + jl;
     const bool active = i < a.n_v && jl < a.jpb && j < a.n_w;
@@ -116,18 +242,37 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
         float x = st.pose.x, y = st.pose.y;
         int ex = 0, ey = 0, pen = 0;
         bool ok = true;
+        const bool all_steps = MOVING && a.first_hit != nullptr;      // the debug call looks at every step, rejected or not
+        int hit_k = 0;
         for (int k = 0; k < a.n_steps; ++k) {
             const float2 t = row[k];
             x = x + s * t.x;
             y = y + s * t.y;
-            if (!nav_pose_cell(a.frame, x, y, &ex, &ey)) { ok = false; break; }
+            if (!nav_pose_cell(a.frame, x, y, &ex, &ey)) { ok = false; if (all_steps) continue; break; }
+            if (MOVING && hit_k == 0 && n_used > 0) {
+                const int mx = ex - rx0, my = ey - ry0;
+                bool hit = false;
+                if ((unsigned)mx <= (unsigned)rside && (unsigned)my <= (unsigned)rside) {
+                    if (boxed) {
+                        for (int b = 0; b < kept; ++b) {
+                            const short4 bx = s_box[b * a.n_steps + k];  // one broadcast read per (box, step)
+                            hit = hit || (mx >= bx.x && mx <= bx.z && my >= bx.y && my <= bx.w);
+                        }
+                    } else {
+                        for (int b = 0; b < kept; ++b) hit = hit || lp_mov_in_box(s_kept[b], k + 1 + a.mlead, a.mq, ex, ey);
+                    }
+                } else hit = lp_mov_hit_all(a.slots, a.mmargin, k + 1 + a.mlead, a.mq, ex, ey);
+                if (hit) { hit_k = k + 1; ok = false; if (all_steps) continue; break; }
+            }
+            if (MOVING && !ok) continue;                              // (all_steps: only the moving test is still wanted)
             int q;
             const int ux = ex - wx0, uy = ey - wy0;
             if (STAGED && (unsigned)ux < (unsigned)side && (unsigned)uy < (unsigned)side) q = s_win[uy * side + ux];
             else q = nav_cost(a.l1, a.table, a.table_n, W, H, ex, ey);
-            if (q < 0) { ok = false; break; }
+            if (q < 0) { ok = false; if (all_steps) continue; break; }
             pen += q;
         }
+        if (all_steps) a.first_hit[c] = hit_k;
         uint32_t fe = NAV_UNREACHED;
         if (ok) fe = a.field[(size_t)ey * W + ex];
         if (fe != NAV_UNREACHED) {
@@ -226,6 +371,7 @@ struct bl_localplan {
     lp_partial* d_partial; size_t partial_cap;
     hipEvent_t ev0, ev1;
     int last_path; bool timed; float last_ms;
+    int last_mpath;                               // bl_localplan_debug_moving_path
 };
 
 static int lp_grow(void** p, size_t* cap, size_t want, bool host, bl_ctx* ctx)
@@ -247,6 +393,7 @@ extern "C" int bl_localplan_create(bl_ctx* ctx, bl_localplan** out)
     memset((void*)lp, 0, sizeof(*lp));
     lp->ctx = ctx;
     lp->last_path = -1;
+    lp->last_mpath = -1;
     hipError_t e = hipEventCreate(&lp->ev0);
     if (e == hipSuccess) e = hipEventCreate(&lp->ev1);
     if (e != hipSuccess) {
@@ -361,6 +508,7 @@ static int lp_prepare(bl_localplan* lp, bl_navfield* nf, const bl_localplan_stat
     const int R = (int)ceil(vabs * (double)p.dt_sim * p.n_steps * (double)nf->frame.cpm) + 2;
     *staged = (long long)(2 * R + 1) * (2 * R + 1) * 2 <= (long long)BL_LOCALPLAN_WINDOW_BYTES;
     a->win_r = *staged ? R : 0;
+    a->reach_r = R;
     a->k_heading = (float)(1024.0 / BL_PI);
     const double ang[8] = {0.0, BL_PI, BL_PI / 2, -BL_PI / 2, BL_PI / 4, 3 * BL_PI / 4, -BL_PI / 4, -3 * BL_PI / 4};
     for (int m = 0; m < 8; ++m) a->move_angle[m] = (float)ang[m];
@@ -388,16 +536,39 @@ static int lp_upload(bl_localplan* lp, const bl_localplan_state_t* states, int n
     return BL_OK;
 }
 
+// the window's share of the dynamic LDS
+static size_t lp_window_lds(const lp_args& a, bool staged)
+{
+    const int side = 2 * a.win_r + 1;
+    return staged ? (((size_t)side * side * 2 + 15) & ~(size_t)15) : 0;
+}
+
 static int lp_launch_rollout(bl_localplan* lp, const lp_args& a, int n, bool staged)
 {
     bl_ctx* ctx = lp->ctx;
-    const int side = 2 * a.win_r + 1;
-    const size_t lds = LP_LDS_FIXED + (staged ? (((size_t)side * side * 2 + 15) & ~(size_t)15) : 0);
+    const size_t lds = LP_LDS_FIXED + lp_window_lds(a, staged);
     if (staged) {
-        BL_DYN_LDS_ONCE_PER_DEVICE(k_lp_rollout<true>, LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16, ctx);
-        hipLaunchKernelGGL(k_lp_rollout<true>, dim3((unsigned int)(n * a.bps)), dim3(LP_THREADS), lds, ctx->stream, a);
+        BL_DYN_LDS_ONCE_PER_DEVICE((k_lp_rollout<true, false>), LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16, ctx);
+        hipLaunchKernelGGL((k_lp_rollout<true, false>), dim3((unsigned int)(n * a.bps)), dim3(LP_THREADS), lds, ctx->stream, a);
     } else {
-        hipLaunchKernelGGL(k_lp_rollout<false>, dim3((unsigned int)(n * a.bps)), dim3(LP_THREADS), lds, ctx->stream, a);
+        hipLaunchKernelGGL((k_lp_rollout<false, false>), dim3((unsigned int)(n * a.bps)), dim3(LP_THREADS), lds, ctx->stream, a);
+    }
+    BL_HIP(hipGetLastError());
+    lp->last_path = staged ? 0 : 1;
+    return BL_OK;
+}
+
+// a.mov_off is set here: the moving block lies behind the window
+static int lp_launch_rollout_moving(bl_localplan* lp, lp_args& a, int n, bool staged)
+{
+    bl_ctx* ctx = lp->ctx;
+    a.mov_off = (int)(LP_LDS_FIXED + lp_window_lds(a, staged));
+    const size_t lds = (size_t)a.mov_off + LP_MOV_BYTES;
+    if (staged) {
+        BL_DYN_LDS_ONCE_PER_DEVICE((k_lp_rollout<true, true>), LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16 + LP_MOV_BYTES, ctx);
+        hipLaunchKernelGGL((k_lp_rollout<true, true>), dim3((unsigned int)(n * a.bps)), dim3(LP_THREADS), lds, ctx->stream, a);
+    } else {
+        hipLaunchKernelGGL((k_lp_rollout<false, true>), dim3((unsigned int)(n * a.bps)), dim3(LP_THREADS), lds, ctx->stream, a);
     }
     BL_HIP(hipGetLastError());
     lp->last_path = staged ? 0 : 1;
@@ -478,6 +649,96 @@ extern "C" int bl_localplan_debug_rollout(bl_localplan* lp, bl_navfield* nf, con
     memcpy(out, lp->h_out, ob);
     return BL_OK;
 }
+
+// what the moving calls check beyond lp_prepare, and the tracker's share of the launch arguments
+static int lp_prepare_moving(bl_localplan* lp, bl_navfield* nf, bl_obstracks* tr, const bl_localplan_moving_t* m, const bl_localplan_state_t* states,
+                             int n, lp_args* a, bool* staged)
+{
+    BL_CHECK_ARG(tr != nullptr && m != nullptr);
+    BL_CHECK_ARG(m->steps_per_update >= 1 && m->steps_per_update <= 255);
+    BL_CHECK_ARG(m->margin_cells >= 0 && m->margin_cells <= BL_LOCALPLAN_MAX_MARGIN);
+    BL_CHECK_ARG(m->lead_steps >= 0 && m->lead_steps <= 255);
+    BL_CHECK_ARG(m->reserved == 0);
+    int rc = lp_prepare(lp, nf, states, n, a, staged);
+    if (rc) return rc;
+    bl_obstracks_view v;
+    bl_obstracks_view_host(tr, &v);
+    BL_CHECK_ARG(v.ctx == lp->ctx && v.W == nf->frame.width && v.H == nf->frame.height);
+    if (!v.have_params) { bl_set_error("obstacle tracks have no parameters (bl_obstracks_set_params first)"); return BL_ERR_STATE; }
+    a->slots = v.d_slots;
+    a->mq.q = m->steps_per_update; a->mq.magic = (unsigned int)(((1u << 28) + (unsigned int)m->steps_per_update - 1u) / (unsigned int)m->steps_per_update);
+    a->mmargin = m->margin_cells; a->mlead = m->lead_steps;
+    return BL_OK;
+}
+
+// the path of the first state that was rolled out; 2 when none was
+static int lp_mpath_of(const int* mpath, int n)
+{
+    for (int i = 0; i < n; ++i) if (mpath[i] >= 0) return mpath[i];
+    return 2;
+}
+
+extern "C" int bl_localplan_commands_moving(bl_localplan* lp, bl_navfield* nf, bl_obstracks* tr, const bl_localplan_moving_t* m,
+                                            const bl_localplan_state_t* states, int n, bl_localplan_result_t* results)
+{
+    lp_args a;
+    bool staged = false;
+    int rc = lp_prepare_moving(lp, nf, tr, m, states, n, &a, &staged);
+    if (rc) return rc;
+    BL_CHECK_ARG(n == 0 || results != nullptr);
+    if (n == 0) return BL_OK;
+    bl_ctx* ctx = lp->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    const size_t rb = (size_t)n * sizeof(bl_localplan_result_t), ob = rb + (size_t)n * 4;   // results | the states' moving paths
+    rc = lp_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = lp_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
+    if (!rc) rc = lp_upload(lp, states, n, &a);
+    if (rc) return rc;
+    a.mpath = (int*)((char*)lp->d_out + rb);
+    BL_HIP(hipEventRecord(lp->ev0, ctx->stream));
+    rc = lp_launch_rollout_moving(lp, a, n, staged);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_lp_finish, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, a, n, (bl_localplan_result_t*)lp->d_out);
+    BL_HIP(hipGetLastError());
+    BL_HIP(hipEventRecord(lp->ev1, ctx->stream));
+    BL_HIP(hipMemcpyAsync(lp->h_out, lp->d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
+    BL_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(results, lp->h_out, rb);
+    lp->last_mpath = lp_mpath_of((const int*)((const char*)lp->h_out + rb), n);
+    BL_HIP(hipEventElapsedTime(&lp->last_ms, lp->ev0, lp->ev1));
+    lp->timed = true;
+    return BL_OK;
+}
+
+extern "C" int bl_localplan_debug_costs_moving(bl_localplan* lp, bl_navfield* nf, bl_obstracks* tr, const bl_localplan_moving_t* m,
+                                               const bl_localplan_state_t* state, int64_t* costs, int32_t* first_hit)
+{
+    lp_args a;
+    bool staged = false;
+    BL_CHECK_ARG(state != nullptr);
+    int rc = lp_prepare_moving(lp, nf, tr, m, state, 1, &a, &staged);
+    if (rc) return rc;
+    bl_ctx* ctx = lp->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    const size_t nc = (size_t)a.n_v * a.n_w, ob = nc * 12 + 4;            // costs | first hits | the moving path
+    rc = lp_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = lp_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
+    if (!rc) rc = lp_upload(lp, state, 1, &a);
+    if (rc) return rc;
+    a.costs = (long long*)lp->d_out;
+    a.first_hit = (int*)((char*)lp->d_out + nc * 8);
+    a.mpath = a.first_hit + nc;
+    rc = lp_launch_rollout_moving(lp, a, 1, staged);
+    if (rc) return rc;
+    BL_HIP(hipMemcpyAsync(lp->h_out, lp->d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
+    BL_HIP(hipStreamSynchronize(ctx->stream));
+    if (costs) memcpy(costs, lp->h_out, nc * 8);
+    if (first_hit) memcpy(first_hit, (const char*)lp->h_out + nc * 8, nc * 4);
+    lp->last_mpath = *(const int*)((const char*)lp->h_out + nc * 12);
+    return BL_OK;
+}
+
+extern "C" int bl_localplan_debug_moving_path(const bl_localplan* lp) { return lp ? lp->last_mpath : -1; }
 
 extern "C" int bl_localplan_debug_path(const bl_localplan* lp) { return lp ? lp->last_path : -1; }
 

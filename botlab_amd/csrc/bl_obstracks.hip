@@ -18,6 +18,8 @@
 //                  copy of the slots in LDS, births in rank order by one wave, and only then -- unless the id limit refuses the
 //                  update -- the slots written back.
 //   k_obt_sweep    (compose, after the layer's own k_obs_compose) a thread per (live cell, sub-step), in strides: the cell's stamp.
+//   k_obt_static   (compose_static, after the layer's own k_obs_compose) a thread per live cell: a confirmed moving track's cell takes
+//                  the map's value back.
 // Integers only; no result depends on the launch shape or on the order in which anything arrives.
 #include <limits.h>
 #include <string.h>
@@ -406,6 +408,24 @@ __global__ __launch_bounds__(OBT_WG) void k_obt_sweep(const int* __restrict__ hd
     }
 }
 
+// (compose_static, after the layer's own k_obs_compose) a thread per live cell of the last update: where its blob is a confirmed moving
+// track's -- k_obt_sweep's predicate -- the cell takes the map's value back
+__global__ __launch_bounds__(OBT_WG) void k_obt_static(const int* __restrict__ hdr, const int32_t* __restrict__ xy, const int32_t* __restrict__ label,
+                                                       const bl_obsblob_t* __restrict__ blobs, const bl_obstrack_t* __restrict__ tracks,
+                                                       const int8_t* __restrict__ map, int8_t* __restrict__ out, int W)
+{
+    const int L = hdr[OBT_L];
+    const int i = (int)blockIdx.x * OBT_WG + (int)threadIdx.x;
+    if (hdr[OBT_KEPT] == 0 || L > BL_OBSTRACKS_MAX_CELLS || i >= L) return;
+    const int rk = label[i];
+    if (rk < 0) return;
+    const int slot = blobs[rk].track;
+    if (slot < 0) return;
+    if ((tracks[slot].flags & (BL_OBSTRACK_CONFIRMED | BL_OBSTRACK_MOVING)) != (BL_OBSTRACK_CONFIRMED | BL_OBSTRACK_MOVING)) return;
+    const size_t c = (size_t)xy[2 * i + 1] * W + xy[2 * i];
+    out[c] = map[c];
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
 struct bl_obstracks {
     bl_ctx* ctx;
@@ -579,6 +599,36 @@ extern "C" int bl_obstracks_compose(bl_obstracks* tr, bl_obslayer* ol, const bl_
     BL_HIP(hipEventRecord(tr->ev_cb, ctx->stream));
     tr->composed = true;
     return BL_OK;
+}
+
+extern "C" int bl_obstracks_compose_static(bl_obstracks* tr, bl_obslayer* ol, const bl_grid* map, bl_grid* out)
+{
+    BL_CHECK_ARG(tr != nullptr && ol != nullptr);
+    BL_CHECK_ARG(ol->ctx == tr->ctx && ol->W == tr->W && ol->H == tr->H);
+    int rc = obt_need_params(tr, ol);
+    if (rc) return rc;
+    if (!tr->fresh && ol->n != tr->last_n) {
+        bl_set_error("bl_obstracks_compose_static: the layer is at update %u, the tracks at %u", ol->n, tr->last_n);
+        return BL_ERR_STATE;
+    }
+    bl_ctx* ctx = tr->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    tr->composed = false;
+    BL_HIP(hipEventRecord(tr->ev_ca, ctx->stream));
+    rc = bl_obslayer_compose(ol, map, out);                             // the checks of map and out, the lineage, the mirror, the copy
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_obt_static, dim3(OBT_BLOCKS), dim3(OBT_WG), 0, ctx->stream, (const int*)tr->d_hdr, (const int32_t*)tr->d_xy,
+                       (const int32_t*)tr->d_label, (const bl_obsblob_t*)tr->d_blobs, (const bl_obstrack_t*)tr->d_tracks, (const int8_t*)map->cells,
+                       out->cells, tr->W);
+    BL_HIP(hipGetLastError());
+    BL_HIP(hipEventRecord(tr->ev_cb, ctx->stream));
+    tr->composed = true;
+    return BL_OK;
+}
+
+void bl_obstracks_view_host(const bl_obstracks* tr, bl_obstracks_view* out)
+{
+    out->ctx = tr->ctx; out->W = tr->W; out->H = tr->H; out->have_params = tr->have_params; out->d_slots = tr->d_tracks;
 }
 
 static int obt_hdr(bl_obstracks* tr, int hdr[OBT_HDR_WORDS])

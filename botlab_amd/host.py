@@ -989,9 +989,38 @@ class LocalPlanner:
         check(self.ctx.lib.bl_localplan_tables(self.h, C.byref(self._state(state)), v.ctypes.data, w.ctypes.data))
         return v, w
 
+    def commands_moving(self, field, tracker, states, steps_per_update, margin_cells=0, lead_steps=0):
+        """commands(field, states) with every rollout timed against the tracker's confirmed moving tracks: a candidate whose cell at
+        step k lies in a track's box at step k is refused.  steps_per_update rollout steps of dt_sim make one tracker update;
+        lead_steps of them have passed since the last one.  `field` is computed over tracker.composeStatic(...)."""
+        n = len(states)
+        s = (_capi.LocalPlanState * max(n, 1))(*[self._state(q) for q in states])
+        m = _capi.LocalPlanMoving(int(steps_per_update), int(margin_cells), int(lead_steps), 0)
+        out = np.zeros(max(n, 1), dtype=LOCALPLAN_RESULT_DTYPE)
+        check(self.ctx.lib.bl_localplan_commands_moving(self.h, field.h, tracker.h, C.byref(m), s, n, out.ctypes.data))
+        return out[:n]
+
+    def command_moving(self, field, tracker, pose, v, w, steps_per_update, margin_cells=0, lead_steps=0):
+        """(trans_v, angular_v, flags) for one state under the moving rule."""
+        r = self.commands_moving(field, tracker, [(pose, v, w)], steps_per_update, margin_cells, lead_steps)[0]
+        return float(r["trans_v"]), float(r["angular_v"]), int(r["flags"])
+
+    def costs_moving(self, field, tracker, state, steps_per_update, margin_cells=0, lead_steps=0):
+        """(int64 [n_w, n_v] costs under the moving rule, int32 [n_w, n_v] first_hit: the first step inside a moving box, 0: none)."""
+        n_v, n_w, _ = self._counts()
+        m = _capi.LocalPlanMoving(int(steps_per_update), int(margin_cells), int(lead_steps), 0)
+        costs, first = np.zeros((n_w, n_v), dtype=np.int64), np.zeros((n_w, n_v), dtype=np.int32)
+        check(self.ctx.lib.bl_localplan_debug_costs_moving(self.h, field.h, tracker.h, C.byref(m), C.byref(self._state(state)), costs.ctypes.data,
+                                                           first.ctypes.data))
+        return costs, first
+
     def debugPath(self):
         """0: the last launch staged the window in LDS; 1: it read the grids directly; -1 before the first."""
         return self.ctx.lib.bl_localplan_debug_path(self.h)
+
+    def debugMovingPath(self):
+        """Of the last moving call: 0 the boxes' table in LDS, 1 the boxes computed per step, 2 no used slot kept; -1 before the first."""
+        return self.ctx.lib.bl_localplan_debug_moving_path(self.h)
 
     def lastDeviceMs(self):
         ms = C.c_float()
@@ -1284,6 +1313,15 @@ class ObstacleTracker:
             out = OccupancyGrid(ctx=self.ctx, _raw=(grid.width, grid.height, grid.mpc, grid.cpm, grid.origin[0], grid.origin[1]))
         c = _capi.ObsTracksCompose(int(horizon), int(robot_cell[0]), int(robot_cell[1]), int(keep_clear))
         check(self.ctx.lib.bl_obstracks_compose(self.h, self.layer.h, grid.h, out.h, C.byref(c)))
+        out.mpc, out.cpm, out.origin = grid.mpc, grid.cpm, grid.origin
+        return out
+
+    def composeStatic(self, grid, out=None):
+        """layer.compose(grid, out) without the cells of the confirmed moving tracks' blobs, which keep the map's value: the grid for
+        the field of LocalPlanner.commands_moving, which meets the moving obstacles where they will be."""
+        if out is None:
+            out = OccupancyGrid(ctx=self.ctx, _raw=(grid.width, grid.height, grid.mpc, grid.cpm, grid.origin[0], grid.origin[1]))
+        check(self.ctx.lib.bl_obstracks_compose_static(self.h, self.layer.h, grid.h, out.h))
         out.mpc, out.cpm, out.origin = grid.mpc, grid.cpm, grid.origin
         return out
 
@@ -1834,6 +1872,18 @@ class MotionPlanner:
         rx = int(math.floor((float(robot_pose.x) - float(grid.origin[0])) * float(grid.cpm)))
         ry = int(math.floor((float(robot_pose.y) - float(grid.origin[1])) * float(grid.cpm)))
         self.composed_ = tracker.compose(grid, c, horizon=horizon, robot_cell=(rx, ry), keep_clear=keep_clear)
+        self.setMap(self.composed_)
+
+    def setMapWithStaticObstacles(self, grid, layer, tracker):
+        """setMapWithObstacles without the tracker's confirmed moving tracks (ObstacleTracker.composeStatic): the map for the field
+        under LocalPlanner.commands_moving.  The caller's layer.update and tracker.update come first."""
+        c = self.composed_
+        if c is None or c.h is None or (c.width, c.height) != (grid.width, grid.height):
+            if c is not None:
+                c.close()
+            c = None
+        assert tracker.layer is layer
+        self.composed_ = tracker.composeStatic(grid, c)
         self.setMap(self.composed_)
 
     def setMetricClearance(self, max_cells=64):

@@ -26,6 +26,15 @@ inline bl_localplan_params_t local_plan_params(float v_max = 0.5f, float w_max =
     return p;
 }
 
+// how the rollout's steps relate to a tracker's updates (commandMoving): stepsPerUpdate steps of dt_sim make one update, leadSteps of
+// them have passed since the last one, and a moving box is widened by marginCells
+inline bl_localplan_moving_t local_plan_moving(int stepsPerUpdate, int marginCells = 0, int leadSteps = 0)
+{
+    bl_localplan_moving_t m;
+    m.steps_per_update = stepsPerUpdate; m.margin_cells = marginCells; m.lead_steps = leadSteps; m.reserved = 0;
+    return m;
+}
+
 template <class Pose, class Path, class Command = motor_command_t>
 class LocalPlannerT {
 public:
@@ -65,6 +74,32 @@ public:
     {
         std::vector<bl_localplan_result_t> out(states.size());
         if (!states.empty()) check(bl_localplan_commands(h_, field.device(), states.data(), static_cast<int>(states.size()), out.data()), "bl_localplan_commands");
+        return out;
+    }
+    // command(), with every rollout timed against the confirmed moving tracks of an ObstacleTrackerT (obstacle_tracks.hpp): a candidate
+    // whose cell at step k lies in a track's box at step k is refused.  `field` is computed over the tracker's composeStatic
+    // (MotionPlannerT::setMapWithStaticObstacles).
+    template <class Tracker>
+    Command commandMoving(const Pose& pose, float v, float w, const NavigationField& field, const Tracker& tracker, const bl_localplan_moving_t& moving,
+                          bl_localplan_result_t* result = nullptr) const
+    {
+        bl_localplan_state_t s;
+        s.pose = pose_in(pose); s.v = v; s.w = w;
+        bl_localplan_result_t r;
+        check(bl_localplan_commands_moving(h_, field.device(), tracker.device(), &moving, &s, 1, &r), "bl_localplan_commands_moving");
+        if (result) *result = r;
+        Command c;
+        c.utime = pose.utime; c.trans_v = r.trans_v; c.angular_v = r.angular_v;
+        return c;
+    }
+    template <class Tracker>
+    std::vector<bl_localplan_result_t> commandsMoving(const std::vector<bl_localplan_state_t>& states, const NavigationField& field, const Tracker& tracker,
+                                                      const bl_localplan_moving_t& moving) const
+    {
+        std::vector<bl_localplan_result_t> out(states.size());
+        if (!states.empty())
+            check(bl_localplan_commands_moving(h_, field.device(), tracker.device(), &moving, states.data(), static_cast<int>(states.size()), out.data()),
+                  "bl_localplan_commands_moving");
         return out;
     }
     // what a GUI draws: the poses of candidate c

@@ -71,6 +71,17 @@ public:
         check(bl_obstracks_compose(h_, layer_.device(), map.device(), out.device(), &c), "bl_obstracks_compose");
         out.markDeviceWritten();
     }
+    // `out` = the layer's compose without the cells of the confirmed moving tracks' blobs, which keep the map's value: the grid for the
+    // field under LocalPlannerT::commandMoving (local_planner.hpp), which meets the moving obstacles where they will be.
+    void composeStatic(const OccupancyGrid& map, OccupancyGrid& out)
+    {
+        if (out.widthInCells() != map.widthInCells() || out.heightInCells() != map.heightInCells() || out.metersPerCell() != map.metersPerCell() ||
+            out.cellsPerMeter() != map.cellsPerMeter() || out.originInGlobalFrame().x != map.originInGlobalFrame().x ||
+            out.originInGlobalFrame().y != map.originInGlobalFrame().y)
+            out = map;
+        check(bl_obstracks_compose_static(h_, layer_.device(), map.device(), out.device()), "bl_obstracks_compose_static");
+        out.markDeviceWritten();
+    }
     void reset() { check(bl_obstracks_reset(h_), "bl_obstracks_reset"); }
 
     std::vector<bl_obstrack_t> tracks()                               // the occupied slots in slot order

@@ -170,7 +170,16 @@ public:
         tracker.compose(map, composed_, horizon, rx, ry, keepClear);
         setMap(composed_);
     }
-    const OccupancyGrid& composedMap() const { return composed_; }          // of the last setMapWithObstacles / setMapWithTracks
+    // (extension) setMapWithObstacles without the tracker's confirmed moving tracks (ObstacleTrackerT::composeStatic): the map for the
+    // field under LocalPlannerT::commandMoving, which times its rollouts against those tracks itself.
+    template <class Layer, class Tracker>
+    void setMapWithStaticObstacles(const OccupancyGrid& map, Layer& layer, Tracker& tracker)
+    {
+        if (&tracker.layer() != &layer) { std::fprintf(stderr, "botlab_hip: setMapWithStaticObstacles: the tracker follows another layer\n"); std::abort(); }
+        tracker.composeStatic(map, composed_);
+        setMap(composed_);
+    }
+    const OccupancyGrid& composedMap() const { return composed_; }          // of the last setMapWithObstacles / setMapWithTracks / setMapWithStaticObstacles
     const SearchParams& searchParams() const { return searchParams_; }
     void setParams(const MotionPlannerParams&)                              // motion_planner.cpp:105-110 reads params_, not the argument
     {

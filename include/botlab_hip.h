@@ -1510,6 +1510,13 @@ int bl_obstracks_set_params(bl_obstracks* tr, const bl_obstracks_params_t* param
 int bl_obstracks_reset(bl_obstracks* tr);                              /* no tracks, no blobs, ids from 1 again, fresh */
 int bl_obstracks_update(bl_obstracks* tr, bl_obslayer* layer);
 int bl_obstracks_compose(bl_obstracks* tr, bl_obslayer* layer, const bl_grid* map, bl_grid* out_grid, const bl_obstracks_compose_t* c);
+/* The composition that leaves the moving obstacles out (for bl_localplan_commands_moving below, which times them itself):
+ * out(c) = 127 where live(c), unless the cell's blob of the last update was matched to or born as a track that is CONFIRMED and
+ * MOVING -- bl_obstracks_compose's predicate: label, blob, slot, flags --; those cells, like every other cell, are map(c).  Lineage
+ * and mirror as bl_obslayer_compose.  The layer's n must be the remembered one (BL_ERR_STATE) unless the tracker is fresh; after a
+ * reset or an upload and before the next update there are no blobs and it is bl_obslayer_compose byte for byte.  The refusals are
+ * bl_obstracks_compose's; it waits for nothing on the host. */
+int bl_obstracks_compose_static(bl_obstracks* tr, bl_obslayer* layer, const bl_grid* map, bl_grid* out_grid);
 /* the occupied slots in slot order: *count = how many, the first min(cap, *count) to out */
 int bl_obstracks_tracks(bl_obstracks* tr, bl_obstrack_t* out, int cap, int* count);
 /* the kept blobs of the last update in rank order: *count = how many, the first min(cap, *count) to out */
@@ -1522,6 +1529,55 @@ int bl_obstracks_download(bl_obstracks* tr, bl_obstrack_t* slots, bl_obstracks_s
 int bl_obstracks_upload(bl_obstracks* tr, const bl_obstrack_t* slots, const bl_obstracks_state_t* state);
 /* device time of the last update and of the last compose: HIP events around their launches (waits for them); either may be NULL */
 int bl_obstracks_last_device_ms(const bl_obstracks* tr, float* update_ms, float* compose_ms);
+
+/* ------------------------------------------------------------------ local planner, moving obstacles (no reference counterpart)
+ * bl_localplan_commands with the rollout timed against the tracked moving obstacles: step k of a rollout is a time, and a candidate
+ * is refused when its cell at step k lies in a moving track's box AT step k.  bl_obstracks_compose stamps the whole
+ * sweep of a moving track into the grid as a wall that stands from the first step to the last; here the field is computed over
+ * bl_obstracks_compose_static, which leaves the moving obstacles out, and the rollout meets them where they will be.
+ * tests/local_plan_moving_model.py restates this comment.  Integers for everything compared.
+ *   The kernel reads the tracker's BL_OBSTRACKS_MAX_TRACKS slots on the device and nothing else of it: no blobs, no labels.  The
+ *     slots are those the last bl_obstracks_update or bl_obstracks_upload left, flags included.
+ *   A slot is used when id != 0, it is CONFIRMED and MOVING, and it is MATCHED or BORN (a coasting track's box is stale) -- the flags
+ *     as they stand in the slot.
+ *   The box of a used slot: x0, y0, x1, y1 each clamped to [-2^30, 2^30] first (so that no uploadable slot overflows), then with
+ *     q = steps_per_update, t = k + lead_steps for the rollout step k = 1 .. n_steps:
+ *       ox = floor((t * vx + 128 * q) / (256 * q)), oy likewise      (floor towards minus infinity; |t * vx| < 2^20)
+ *       [x0 + ox - margin_cells, x1 + ox + margin_cells] x [y0 + oy - margin_cells, y1 + oy + margin_cells]
+ *   A candidate is admissible when, in addition to bl_localplan_commands' rule, no visited cell cell_k lies in any used slot's box
+ *     at step k.  Everything else is the local planner's definition word for word: the tables, the float arc, the cost, the key
+ *     (cost, c), REACHED and OFF_FIELD decided on the pose's own cell alone before anything is rolled out (a box over the pose's cell
+ *     gives BLOCKED, not OFF_FIELD), BLOCKED, n_admissible, the refusals.  With no used slot the results are
+ *     bl_localplan_commands' byte for byte.
+ *   Refused with BL_ERR_ARG beyond bl_localplan_commands' refusals: steps_per_update outside 1 .. 255, margin_cells outside
+ *     0 .. 64, lead_steps outside 0 .. 255, reserved != 0, a tracker of another ctx or of another shape than the field's grid.
+ *     BL_ERR_STATE before the tracker's bl_obstracks_set_params.  n == 0 is fine.  One synchronisation, at the return.
+ *   bl_localplan_debug_costs_moving: costs as bl_localplan_debug_costs under the moving rule; first_hit[c] the least k whose visited
+ *     cell lies in a used box, 0 when there is none -- looked for at every k whose pose has a cell, whether or not another rule has
+ *     already refused the candidate.  Either pointer may be NULL.
+ * How it is computed (k_lp_rollout<STAGED, MOVING>): per workgroup a lane per slot decides used and can-reach -- the box swept over
+ * k = 1 .. n_steps (the offsets are monotone in k, so the two ends bound it) meets the square of half side R around the window's
+ * centre, R the window rule's --; the kept slots are compacted in slot order into LDS.  A visited cell outside that square (the
+ * bound on the reach is floating point) is tested against all used slots, so the cull decides speed only.  Box positions:
+ *   path 0 (table) iff kept * n_steps * 8 <= BL_LOCALPLAN_MOVING_BYTES: the kept boxes at every step, clamped to the square, as
+ *     4 x int16 in LDS, filled once per workgroup; a candidate's step reads one entry per box;
+ *   path 1 (per step) otherwise: the floor divisions are done per candidate, step and box;
+ *   path 2: no used slot was kept.
+ * bl_localplan_debug_moving_path: the path of the last moving call (of its first state that was rolled out; 2 when none was), -1
+ * before the first. */
+#define BL_LOCALPLAN_MOVING_BYTES (10 * 1024)
+#define BL_LOCALPLAN_MAX_MARGIN 64
+typedef struct bl_localplan_moving_t {
+    int32_t steps_per_update;          /* 1 .. 255: rollout steps of dt_sim in one tracker update */
+    int32_t margin_cells;              /* 0 .. 64 */
+    int32_t lead_steps;                /* 0 .. 255: rollout steps already elapsed since the tracker's last update */
+    int32_t reserved;                  /* 0 */
+} bl_localplan_moving_t;               /* 16 bytes: offsets 0, 4, 8, 12 */
+int bl_localplan_commands_moving(bl_localplan* lp, bl_navfield* nf, bl_obstracks* tr, const bl_localplan_moving_t* m,
+                                 const bl_localplan_state_t* states, int n, bl_localplan_result_t* results);
+int bl_localplan_debug_costs_moving(bl_localplan* lp, bl_navfield* nf, bl_obstracks* tr, const bl_localplan_moving_t* m,
+                                    const bl_localplan_state_t* state, int64_t* costs, int32_t* first_hit);
+int bl_localplan_debug_moving_path(const bl_localplan* lp);
 
 #ifdef __cplusplus
 }
