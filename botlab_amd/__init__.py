@@ -9,7 +9,7 @@ from .host import (AsyncExplorer, AsyncPlanner, Context, LidarScan, Mapping, Mot
                    OccupancyGrid, ParticleFilter, PARTICLE_DTYPE, POSE_DTYPE, default_context, make_pose,
                    search_for_path, search_for_path_begin, search_for_path_end, search_for_path_batch, Frontiers,
                    find_map_frontiers, plan_path_to_frontier, ExploringMap, ScanMatcher, NavigationField, nav_params,
-                   plan_path_to_frontier_by_cost, NAV_UNREACHED, ViewGain, plan_path_to_frontier_by_gain, RBSlam, LocalPlanner, LOCALPLAN_RESULT_DTYPE,
+                   plan_path_to_frontier_by_cost, NAV_UNREACHED, ViewGain, plan_path_to_frontier_by_gain, RBSlam, LocalPlanner, LOCALPLAN_RESULT_DTYPE, MppiPlanner, MPPI_RESULT_DTYPE, MPPI_FELL_BACK,
                    LOCALPLAN_REACHED, LOCALPLAN_OFF_FIELD, LOCALPLAN_BLOCKED, PathShortcut, LikelihoodField, ObstacleLayer, ObstacleTracker, track_to_metric,
                    prior_from_sigmas)
 
@@ -18,5 +18,5 @@ __all__ = ["AsyncExplorer", "AsyncPlanner", "BotlabHipError", "Lidar", "Particle
            "PARTICLE_DTYPE", "POSE_DTYPE", "default_context", "make_pose", "search_for_path", "search_for_path_begin",
            "search_for_path_end", "search_for_path_batch", "Frontiers", "find_map_frontiers", "plan_path_to_frontier", "ExploringMap", "ScanMatcher",
            "NavigationField", "nav_params", "plan_path_to_frontier_by_cost", "NAV_UNREACHED", "ViewGain",
-           "plan_path_to_frontier_by_gain", "RBSlam", "LocalPlanner", "LOCALPLAN_RESULT_DTYPE", "LOCALPLAN_REACHED", "LOCALPLAN_OFF_FIELD",
+           "plan_path_to_frontier_by_gain", "RBSlam", "LocalPlanner", "LOCALPLAN_RESULT_DTYPE", "MppiPlanner", "MPPI_RESULT_DTYPE", "MPPI_FELL_BACK", "LOCALPLAN_REACHED", "LOCALPLAN_OFF_FIELD",
            "LOCALPLAN_BLOCKED", "PathShortcut", "LikelihoodField", "ObstacleLayer", "ObstacleTracker", "track_to_metric", "prior_from_sigmas"]

@@ -215,6 +215,29 @@ assert C.sizeof(LocalPlanState) == 32 and C.sizeof(LocalPlanParams) == 56 and C.
 assert C.sizeof(LocalPlanMoving) == 16
 
 
+class MppiParams(C.Structure):
+    """bl_mppi_params_t: limits, noise, sample count, horizon, temperature, weights and seed of the sampling local planner (72 bytes)."""
+    _fields_ = [("v_min", C.c_float), ("v_max", C.c_float), ("w_max", C.c_float), ("acc_v", C.c_float), ("acc_w", C.c_float),
+                ("dt_sim", C.c_float), ("noise_v", C.c_float), ("noise_w", C.c_float), ("n_samples", C.c_int32), ("horizon", C.c_int32),
+                ("n_sub", C.c_int32), ("lam", C.c_int32), ("w_field", C.c_int32), ("w_heading", C.c_int32), ("w_clear", C.c_int32),
+                ("pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class MppiState(C.Structure):
+    """bl_mppi_state_t: a local planner state and the two Philox counter words of its draw (40 bytes)."""
+    _fields_ = [("s", LocalPlanState), ("tick", C.c_uint32), ("stream", C.c_uint32)]
+
+
+class MppiResult(C.Structure):
+    """bl_mppi_result_t: the command of one state, the best sample, the costs and the weight sums (56 bytes)."""
+    _fields_ = [("trans_v", C.c_float), ("angular_v", C.c_float), ("index_best", C.c_int32), ("n_admissible", C.c_int32),
+                ("cost_best", C.c_int64), ("cost_out", C.c_int64), ("weight_sum", C.c_uint64), ("weight_sq_sum", C.c_uint64),
+                ("flags", C.c_int32), ("pad", C.c_int32)]
+
+
+assert C.sizeof(MppiParams) == 72 and C.sizeof(MppiState) == 40 and C.sizeof(MppiResult) == 56
+
+
 class ShortcutParams(C.Structure):
     """bl_shortcut_params_t: clearance, longest span and the price of a waypoint of the path shortcutting (16 bytes)."""
     _fields_ = [("clearance", C.c_double), ("max_span", C.c_int32), ("waypoint_cost", C.c_int32)]
@@ -492,6 +515,15 @@ SIGNATURES = {
     "bl_localplan_commands_moving": (C.c_int, [_vp, _vp, _vp, _P(LocalPlanMoving), _vp, C.c_int, _vp]),
     "bl_localplan_debug_costs_moving": (C.c_int, [_vp, _vp, _vp, _P(LocalPlanMoving), _P(LocalPlanState), _vp, _vp]),
     "bl_localplan_debug_moving_path": (C.c_int, [_vp]),
+    "bl_mppi_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_mppi_destroy": (None, [_vp]),
+    "bl_mppi_set_params": (C.c_int, [_vp, _P(MppiParams)]),
+    "bl_mppi_plan": (C.c_int, [_vp, _vp, _vp, _P(LocalPlanMoving), _vp, C.c_int, _vp, _vp, _vp]),
+    "bl_mppi_debug_samples": (C.c_int, [_vp, _vp, _vp, _P(LocalPlanMoving), _P(MppiState), _vp, _vp, _vp, _vp]),
+    "bl_mppi_debug_rollout": (C.c_int, [_vp, _vp, _P(MppiState), _vp, _vp]),
+    "bl_mppi_weight_table": (None, [_vp]),
+    "bl_mppi_debug_path": (C.c_int, [_vp]),
+    "bl_mppi_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
     "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_shortcut_destroy": (None, [_vp]),
     "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),

@@ -20,13 +20,13 @@
 
 #include "bl_internal.h"
 #include "bl_navfield_dev.h"
+#include "bl_localplan_dev.h"
 
 #define LP_THREADS 256
 #define LP_TRIG_SLOTS 2048             // (cos, sin) pairs of a workgroup: jpb * (n_steps + 1) of them, the last of each j holds theta_end
 #define LP_RED_BYTES 64                // per wave: key cost (8), key c (4), admissible count (4)
 #define LP_LDS_FIXED (LP_TRIG_SLOTS * 8 + LP_RED_BYTES)
 #define LP_COST_NONE 0x7FFFFFFFFFFFFFFFll
-#define LP_MOV_POS_MAX (1 << 30)
 #define LP_MOV_KEPT_BYTES (BL_OBSTRACKS_MAX_TRACKS * 20)                  // lp_kept: five words per kept slot
 #define LP_MOV_BYTES (LP_MOV_KEPT_BYTES + BL_LOCALPLAN_MOVING_BYTES)
 static_assert(LP_THREADS == BL_OBSTRACKS_MAX_TRACKS, "the moving prologue has a lane per slot");
@@ -34,8 +34,6 @@ static_assert(LP_THREADS == BL_OBSTRACKS_MAX_TRACKS, "the moving prologue has a 
 static_assert(2 * (LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16 + LP_MOV_BYTES) <= 160 * 1024, "BL_LOCALPLAN_MOVING_BYTES too large");
 
 struct lp_partial { long long cost; int c; int n_adm; };
-
-struct lp_mov_div { int q; unsigned int magic; };     // steps_per_update and ceil(2^28 / q): lp_mov_offset
 
 struct lp_args {
     const uint32_t* field; const uint16_t* l1; const int32_t* table; int table_n;
@@ -60,52 +58,6 @@ struct lp_args {
     int* mpath;                                   // [state]: 0 table, 1 per step, 2 nothing kept, -1 not rolled out (the state's first workgroup writes it)
 };
 
-// a kept slot: its clamped box widened by the margin, and (vx, vy) as two int16
-struct lp_kept { int x0, y0, x1, y1, v; };
-
-// floor((t * v + 128 q) / (256 q)) without a division: floor(n / (256 q)) = floor((n >> 8) / q), and for 0 <= a < 2^20, q < 2^8,
-// floor(a / q) = (a * ceil(2^28 / q)) >> 28 (Granlund & Montgomery).  |t * v| <= 510 * 1023, so (n >> 8) + 2048 q lies in [9, 2^20).
-__device__ __forceinline__ int lp_mov_offset(int t, int v, lp_mov_div d)
-{
-    const unsigned int a = (unsigned int)(((t * v + 128 * d.q) >> 8) + 2048 * d.q);   // >> of a negative int: floor
-    return (int)(((unsigned long long)a * d.magic) >> 28) - 2048;
-}
-
-__device__ __forceinline__ int lp_mov_clamp(int v) { return v < -LP_MOV_POS_MAX ? -LP_MOV_POS_MAX : v > LP_MOV_POS_MAX ? LP_MOV_POS_MAX : v; }
-
-__device__ __forceinline__ bool lp_mov_used(const bl_obstrack_t& t)
-{
-    return t.id != 0u && (t.flags & (BL_OBSTRACK_CONFIRMED | BL_OBSTRACK_MOVING)) == (BL_OBSTRACK_CONFIRMED | BL_OBSTRACK_MOVING) &&
-           (t.flags & (BL_OBSTRACK_MATCHED | BL_OBSTRACK_BORN)) != 0;
-}
-
-__device__ __forceinline__ lp_kept lp_mov_record(const bl_obstrack_t& t, int margin)
-{
-    lp_kept r;
-    r.x0 = lp_mov_clamp(t.x0) - margin; r.y0 = lp_mov_clamp(t.y0) - margin;
-    r.x1 = lp_mov_clamp(t.x1) + margin; r.y1 = lp_mov_clamp(t.y1) + margin;
-    const int vx = min(max(t.vx, -1023), 1023), vy = min(max(t.vy, -1023), 1023);   // what every update and upload leaves; lp_mov_offset's domain
-    r.v = (vx & 0xffff) | (int)((unsigned int)vy << 16);
-    return r;
-}
-
-// is (ex, ey) inside the record's box at time t (rollout step + lead)
-__device__ __forceinline__ bool lp_mov_in_box(const lp_kept& r, int t, lp_mov_div q, int ex, int ey)
-{
-    const int ox = lp_mov_offset(t, (int)(short)(r.v & 0xffff), q), oy = lp_mov_offset(t, r.v >> 16, q);
-    return ex >= r.x0 + ox && ex <= r.x1 + ox && ey >= r.y0 + oy && ey <= r.y1 + oy;
-}
-
-// a visited cell outside the reach square (the bound is floating point): every used slot, straight from the tracker
-__device__ __noinline__ bool lp_mov_hit_all(const bl_obstrack_t* __restrict__ slots, int margin, int t, lp_mov_div q, int ex, int ey)
-{
-    for (int sl = 0; sl < BL_OBSTRACKS_MAX_TRACKS; ++sl) {
-        const bl_obstrack_t tr = slots[sl];
-        if (lp_mov_used(tr) && lp_mov_in_box(lp_mov_record(tr, margin), t, q, ex, ey)) return true;
-    }
-    return false;
-}
-
 // the flags of the pose's own cell; (cx, cy) its cell where it has one
 __device__ __forceinline__ int lp_start_flags(const lp_args& a, const bl_localplan_state_t& st, int* cx, int* cy)
 {
@@ -116,8 +68,6 @@ __device__ __forceinline__ int lp_start_flags(const lp_args& a, const bl_localpl
     if (f == NAV_UNREACHED) return BL_LOCALPLAN_OFF_FIELD;
     return f == 0 ? BL_LOCALPLAN_REACHED : 0;
 }
-
-__device__ __forceinline__ bool lp_key_less(long long ca, int ia, long long cb, int ib) { return ca < cb || (ca == cb && ia < ib); }
 
 template <bool STAGED, bool MOVING>
 __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)

@@ -1033,6 +1033,127 @@ class LocalPlanner:
             self.h = None
 
 
+MPPI_FELL_BACK = 8
+MPPI_RESULT_DTYPE = np.dtype([("trans_v", "<f4"), ("angular_v", "<f4"), ("index_best", "<i4"), ("n_admissible", "<i4"), ("cost_best", "<i8"),
+                              ("cost_out", "<i8"), ("weight_sum", "<u8"), ("weight_sq_sum", "<u8"), ("flags", "<i4"), ("pad", "<i4")])
+assert MPPI_RESULT_DTYPE.itemsize == 56
+
+
+class MppiPlanner:
+    """The sampling local planner (bl_mppi_*, include/botlab_hip.h): model-predictive path-integral control over a computed
+    NavigationField.  K perturbed control sequences of T periods are rolled out and their softmin-weighted average is the new
+    sequence; controls are int32 in units of 2^-16 (m/s, rad/s).  A state is (pose, v, w, tick, stream).  The planner holds one
+    warm-start sequence for command() / advance(); plan() takes and returns sequences explicitly.  K, T, lambda, the noises and the
+    weights are untuned knobs, and nothing here publishes the command."""
+
+    def __init__(self, ctx=None, **params):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_mppi_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        self.params = None
+        self.seq = None                                      # int32 [T, 2]: the held nominal sequence
+        self.tick = 0
+        self.last = None                                     # the record of the last command()
+        if params:
+            self.set_params(**params)
+
+    def set_params(self, v_min, v_max, w_max, acc_v, acc_w, dt_sim, noise_v, noise_w, n_samples, horizon, n_sub, lam, w_field=1, w_heading=0,
+                   w_clear=0, seed=0):
+        p = _capi.MppiParams(v_min, v_max, w_max, acc_v, acc_w, dt_sim, noise_v, noise_w, int(n_samples), int(horizon), int(n_sub), int(lam),
+                             int(w_field), int(w_heading), int(w_clear), 0, int(seed))
+        check(self.ctx.lib.bl_mppi_set_params(self.h, C.byref(p)))
+        self.params = p
+        self.seq = np.zeros((p.horizon, 2), np.int32)
+
+    @staticmethod
+    def _state(s):
+        pose, v, w = s[0], s[1], s[2]
+        tick, stream = (s[3], s[4]) if len(s) > 3 else (0, 0)
+        return _capi.MppiState(_capi.LocalPlanState(pose, float(np.float32(v)), float(np.float32(w))), int(tick), int(stream))
+
+    def _shape(self):
+        if self.params is None:
+            raise RuntimeError("MppiPlanner has no parameters (set_params first)")
+        return self.params.n_samples, self.params.horizon, self.params.n_sub
+
+    @staticmethod
+    def _moving(tracker, moving):
+        if tracker is None:
+            return None, None
+        steps_per_update, margin_cells, lead_steps = moving
+        return tracker.h, C.byref(_capi.LocalPlanMoving(int(steps_per_update), int(margin_cells), int(lead_steps), 0))
+
+    def plan(self, field, states, seq_in=None, tracker=None, moving=None):
+        """(MPPI_RESULT_DTYPE [n], seq_out int32 [n, T, 2]) for n states (pose, v, w, tick, stream); seq_in int32 [n, T, 2] or None
+        (zeros).  With a tracker, `moving` = (steps_per_update, margin_cells, lead_steps) times every rollout against its moving tracks."""
+        n = len(states)
+        T = self.params.horizon if self.params is not None else 1
+        s = (_capi.MppiState * max(n, 1))(*[self._state(q) for q in states])
+        out = np.zeros(max(n, 1), dtype=MPPI_RESULT_DTYPE)
+        seq_out = np.zeros((max(n, 1), T, 2), np.int32)
+        u = None
+        if seq_in is not None:
+            u = np.ascontiguousarray(seq_in, dtype=np.int32).reshape(n, T, 2)
+        th, m = self._moving(tracker, moving)
+        check(self.ctx.lib.bl_mppi_plan(self.h, field.h, th, m, s, n, u.ctypes.data if u is not None and n else None, seq_out.ctypes.data,
+                                        out.ctypes.data))
+        return out[:n], seq_out[:n]
+
+    def command(self, field, pose, v, w, stream=0, tracker=None, moving=None):
+        """(trans_v, angular_v, flags) for one state, warm-started from the held sequence; call advance() once the command is taken."""
+        r, so = self.plan(field, [(pose, v, w, self.tick, stream)], self.seq[None], tracker, moving)
+        self.last, self.seq = r[0], so[0].copy()
+        return float(r[0]["trans_v"]), float(r[0]["angular_v"]), int(r[0]["flags"])
+
+    def advance(self):
+        """The next tick: the held sequence shifted by one period, its last control repeated; zeros after any flag but FELL_BACK."""
+        flags = int(self.last["flags"]) if self.last is not None else 0
+        if flags & ~MPPI_FELL_BACK:
+            self.seq = np.zeros_like(self.seq)
+        else:
+            self.seq = np.concatenate([self.seq[1:], self.seq[-1:]], axis=0)
+        self.tick += 1
+
+    def debug_samples(self, field, state, seq_in=None, tracker=None, moving=None):
+        """(costs int64 [K], first_hit int32 [K], seqs int32 [K, T, 2]) of one state's samples, INT64_MAX where inadmissible."""
+        K, T, _ = self._shape()
+        costs, first, seqs = np.zeros(K, np.int64), np.zeros(K, np.int32), np.zeros((K, T, 2), np.int32)
+        u = np.ascontiguousarray(seq_in, dtype=np.int32).reshape(T, 2) if seq_in is not None else None
+        th, m = self._moving(tracker, moving)
+        check(self.ctx.lib.bl_mppi_debug_samples(self.h, field.h, th, m, C.byref(self._state(state)), u.ctypes.data if u is not None else None,
+                                                 costs.ctypes.data, first.ctypes.data, seqs.ctypes.data))
+        return costs, first, seqs
+
+    def rollout(self, field, state, seq=None):
+        """The T * n_sub poses of a sequence int32 [T, 2] (None: zeros), as a POSE_DTYPE array."""
+        _, T, n_sub = self._shape()
+        out = np.zeros(T * n_sub, dtype=POSE_DTYPE)
+        u = np.ascontiguousarray(seq, dtype=np.int32).reshape(T, 2) if seq is not None else None
+        check(self.ctx.lib.bl_mppi_debug_rollout(self.h, field.h, C.byref(self._state(state)), u.ctypes.data if u is not None else None,
+                                                 out.ctypes.data))
+        return out
+
+    def weightTable(self):
+        out = np.zeros(257, np.uint32)
+        self.ctx.lib.bl_mppi_weight_table(out.ctypes.data)
+        return out
+
+    def debugPath(self):
+        """0: the last rollout launch staged the window in LDS; 1: it read the grids directly; -1 before the first."""
+        return self.ctx.lib.bl_mppi_debug_path(self.h)
+
+    def lastDeviceMs(self):
+        ms = C.c_float()
+        check(self.ctx.lib.bl_mppi_last_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_mppi_destroy(self.h)
+            self.h = None
+
+
 class PathShortcut:
     """Path shortcutting (bl_shortcut_*, include/botlab_hip.h): any-angle waypoints from grid paths -- all-pairs line of sight over a
     path's cells and the cheapest chain of segments over the visibility graph, in exact integers."""

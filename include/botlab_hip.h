@@ -1579,6 +1579,104 @@ int bl_localplan_debug_costs_moving(bl_localplan* lp, bl_navfield* nf, bl_obstra
                                     const bl_localplan_state_t* state, int64_t* costs, int32_t* first_hit);
 int bl_localplan_debug_moving_path(const bl_localplan* lp);
 
+/* ------------------------------------------------------------------ sampling local planner (no reference counterpart)
+ * Model-predictive path-integral control (MPPI) over a navigation field: K perturbed control SEQUENCES of T periods are drawn around a
+ * nominal sequence, each is rolled out by the local planner's unicycle step, and the softmin-weighted average of the admissible ones
+ * is the new sequence, warm-started from the previous tick.  bl_localplan_commands scores constant (v, w) arcs; a
+ * sequence can turn on the spot and then drive, or slow down, let a tracked box cross and accelerate.  tests/mppi_model.py restates
+ * this comment.  Everything compared or summed is an integer: the result depends on no launch shape and no reduction order.
+ *   Fixed point: controls are int32 in units of 2^-16 (m/s, rad/s).  q16(x) = (int32)lrint((double)x * 65536.0), ties to even.
+ *   Derived once on the host: vmin_q, vmax_q, wmax_q, nv_q, nw_q by q16 of v_min, v_max, w_max, noise_v, noise_w;
+ *     av_q = (int32)lrint((double)acc_v * (double)dt_sim * n_sub * 65536.0), aw_q likewise from acc_w: the change a control period allows.
+ *   Refused with BL_ERR_ARG by bl_mppi_set_params: a non-finite value, v_min > v_max, w_max < 0, a noise < 0, an acc < 0, dt_sim <= 0,
+ *     any of the seven derived values with magnitude >= 2^21, n_samples outside 1 .. 16384, horizon outside 1 .. 64, n_sub outside
+ *     1 .. 16, horizon * n_sub > 255, lambda outside 1 .. 2^30, a weight outside 0 .. 65535; by the calls that see the field
+ *     (double)max(|v_min|, |v_max|) * (double)dt_sim > (double)meters_per_cell (a step may not skip a cell); a state the local planner
+ *     refuses, or one with |q16(v)| or |q16(w)| >= 2^21.  `pad` is not read.
+ *   Sequences, in and out, are int32 [n][T][2], channel 0 v and 1 w.  A NULL seq_in is all zeros.
+ *   Sample k = 0 .. K-1 of a state, control period t = 0 .. T-1:
+ *     (a0, a1, a2, a3) = bl_philox4x32 of counter (k, t, state.stream, state.tick) and key (seed low word, seed high word)
+ *     e_v = lo16(a0) + hi16(a0) + lo16(a1) + hi16(a1) - 131070, e_w the same of a2, a3: Irwin-Hall of four, -131070 .. 131070, so the
+ *       perturbation's standard deviation is about 0.2887 * noise
+ *     raw = u_in[t] + (((int64)e * noise_q) >> 17), the shift arithmetic (floor), raw an int64.  Sample 0 has e = 0 (the nominal);
+ *       when K >= 2, sample 1 has raw = 0 (brake).
+ *     the clamp chain, per channel, prev = q16(state.v) (or w) before t = 0: lo = max(limit_lo, prev - a_q), hi = min(limit_hi,
+ *       prev + a_q); if lo > hi both become prev clamped to the limits; q = min(max(raw, lo), hi); prev = q.  The limits are
+ *       vmin_q, vmax_q and -wmax_q, wmax_q.
+ *   Rollout of a sequence, the local planner's step word for word: theta = wrap_to_pi(pose.theta); per period v = (float)q_v * 2^-16f,
+ *     s = v * dt_sim, dth = (float)q_w * 2^-16f * dt_sim, then n_sub steps of (cs, sn) = cosf, sinf of theta; x = x + s * cs;
+ *     y = y + s * sn; theta = wrap_to_pi(theta + dth); the visited cell by global_position_to_grid_cell.  T * n_sub steps in all.
+ *   Admissible as in bl_localplan_commands: every visited cell inside and traversable, field(e) != UNREACHED at the last one.
+ *     cost = w_field * field(e) + w_heading * h + w_clear * (sum of penalties), int64, h the local planner's heading term.
+ *   Weights: (c_min, best) the least key (cost, k) over admissible samples; idx = min((cost_k - c_min) * 16 / lambda, 256);
+ *     W_k = table[idx], 0 for an inadmissible sample; table[0] = 2^24, table[i] = (table[i-1] * 4034748382) >> 32 for i <= 255
+ *     (the constant is floor(2^32 e^(-1/16)); the recurrence is the definition), table[256] = 0.  S = sum W and Q = sum W^2 in uint64;
+ *     per (t, channel) N = sum W_k q_k in int64; a = floor((2 N + S) / (2 S)), floor towards minus infinity.
+ *   Output: a through the clamp chain (raw = a) is the candidate sequence; it is rolled out; if admissible it is seq_out and cost_out
+ *     its cost; otherwise seq_out is sample best's sequence, cost_out = cost_best and flags = BL_MPPI_FELL_BACK.  (The average of two
+ *     ways round a pillar goes through the pillar.)  trans_v, angular_v = seq_out[0] * 2^-16.
+ *   REACHED, OFF_FIELD, BLOCKED: the local planner's rules and values, decided on the pose's own cell before anything is drawn
+ *     (BLOCKED: no admissible sample); each with the command (0, 0), a zero seq_out, index_best -1, zero weight sums; both costs 0
+ *     with REACHED and INT64_MAX with the other two; n_admissible 0.
+ *   Moving obstacles: tr and m are both NULL or both set (else BL_ERR_ARG).  Set: bl_localplan_commands_moving's admissibility rule
+ *     word for word -- used slots, the clamped box, ox / oy by floor division, the margin -- with k = 1 .. T * n_sub the integration
+ *     step, applied to the samples and to the candidate sequence's rollout; that call's refusals.  With no used slot the results are
+ *     the static call's byte for byte.
+ *   bl_mppi_debug_samples: the K costs of one state (INT64_MAX: inadmissible), rolled out whatever the state's flags would be;
+ *     first_hit[k] as bl_localplan_debug_costs_moving's (all 0 without a tracker); seqs the K sequences.  Either of the last two may
+ *     be NULL.  bl_mppi_debug_rollout: the T * n_sub poses of `seq` ([T][2], NULL: zeros; taken as given, no clamp chain; an entry
+ *     with magnitude >= 2^21 is refused).
+ * How it is computed (bl_mppi.hip): no sequence is stored; a sample's sequence is regenerated from Philox and the two prev registers
+ * wherever it is needed.  k_mppi_rollout<STAGED, MOVING>: a thread per sample, a workgroup per (state, 256 samples); the window of the
+ * rollouts' reach staged in LDS by the local planner's window rule with n_steps = T * n_sub (bl_mppi_debug_path: 0 staged, 1 grids);
+ * the used slots compacted into LDS in slot order; cost[k] and the least key per workgroup.  k_mppi_average: the weights and the
+ * 2 T + 2 integer sums per workgroup by wave shuffles, then LDS.  k_mppi_finish, a workgroup per state: the sums, the divisions, the
+ * clamp chain, the candidate's rollout and the fall-back.  No atomics.  One synchronisation, at the return. */
+#define BL_MPPI_MAX_SAMPLES 16384
+#define BL_MPPI_MAX_HORIZON 64
+#define BL_MPPI_MAX_SUB 16
+#define BL_MPPI_MAX_STEPS 255
+#define BL_MPPI_MAX_LAMBDA (1 << 30)
+#define BL_MPPI_MAX_Q (1 << 21)
+#define BL_MPPI_FELL_BACK 8
+typedef struct bl_mppi_params_t {
+    float v_min, v_max, w_max;         /* m/s, m/s, rad/s */
+    float acc_v, acc_w;                /* m/s^2, rad/s^2, >= 0 */
+    float dt_sim;                      /* s, > 0: the integration step; a control period is n_sub of them */
+    float noise_v, noise_w;            /* m/s, rad/s, >= 0: the perturbation's scale */
+    int32_t n_samples, horizon, n_sub; /* K 1 .. 16384, T 1 .. 64, 1 .. 16 with T * n_sub <= 255 */
+    int32_t lambda;                    /* 1 .. 2^30: the softmin's temperature in cost units */
+    int32_t w_field, w_heading, w_clear;   /* 0 .. 65535 each */
+    int32_t pad;
+    uint64_t seed;
+} bl_mppi_params_t;                    /* 72 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64 */
+typedef struct bl_mppi_state_t {
+    bl_localplan_state_t s;
+    uint32_t tick, stream;             /* Philox counter words: the control tick, and which robot or hypothesis draws */
+} bl_mppi_state_t;                     /* 40 bytes: offsets 0, 32, 36 */
+typedef struct bl_mppi_result_t {
+    float trans_v, angular_v;          /* seq_out[0] * 2^-16 */
+    int32_t index_best, n_admissible;
+    int64_t cost_best, cost_out;
+    uint64_t weight_sum, weight_sq_sum;    /* S and Q: S * S / Q is the effective sample size */
+    int32_t flags, pad;                /* BL_LOCALPLAN_REACHED / OFF_FIELD / BLOCKED, BL_MPPI_FELL_BACK */
+} bl_mppi_result_t;                    /* 56 bytes: offsets 0, 4, 8, 12, 16, 24, 32, 40, 48, 52 */
+typedef struct bl_mppi bl_mppi;
+int bl_mppi_create(bl_ctx* ctx, bl_mppi** out);                       /* buffers grow on demand */
+void bl_mppi_destroy(bl_mppi* mp);
+int bl_mppi_set_params(bl_mppi* mp, const bl_mppi_params_t* params);  /* refused: the handle keeps what it had */
+/* BL_ERR_STATE before set_params and for a field handle without a field; n == 0 is fine; seq_in may be NULL */
+int bl_mppi_plan(bl_mppi* mp, bl_navfield* nf, bl_obstracks* tr, const bl_localplan_moving_t* m, const bl_mppi_state_t* states, int n,
+                 const int32_t* seq_in, int32_t* seq_out, bl_mppi_result_t* results);
+int bl_mppi_debug_samples(bl_mppi* mp, bl_navfield* nf, bl_obstracks* tr, const bl_localplan_moving_t* m, const bl_mppi_state_t* state,
+                          const int32_t* seq_in, int64_t* costs, int32_t* first_hit, int32_t* seqs);
+int bl_mppi_debug_rollout(bl_mppi* mp, bl_navfield* nf, const bl_mppi_state_t* state, const int32_t* seq, bl_pose_xyt_t* out);
+void bl_mppi_weight_table(uint32_t out[257]);                         /* host arithmetic only */
+/* which path the last rollout launch took: 0 the window staged in LDS, 1 the grids read directly; -1 before the first */
+int bl_mppi_debug_path(const bl_mppi* mp);
+/* device time of the last bl_mppi_plan's kernels (HIP events around the launches); BL_ERR_STATE before the first */
+int bl_mppi_last_device_ms(const bl_mppi* mp, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
