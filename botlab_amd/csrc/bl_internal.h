@@ -98,6 +98,18 @@ struct bl_ctx {
     bl_scan_dev scan;
 };
 
+// a handle's scratch buffer (device, or pinned host) grown to `want` bytes; the contents are not kept
+static inline int bl_grow(void** p, size_t* cap, size_t want, bool host, bl_ctx* ctx)
+{
+    if (want <= *cap) return BL_OK;
+    BL_HIP(hipStreamSynchronize(ctx->stream));
+    if (*p) { if (host) BL_HIP(hipHostFree(*p)); else BL_HIP(hipFree(*p)); }
+    *p = nullptr; *cap = 0;
+    if (host) BL_HIP(hipHostMalloc(p, want, hipHostMallocDefault)); else BL_HIP(hipMalloc(p, want));
+    *cap = want;
+    return BL_OK;
+}
+
 // find_map_frontiers' result: frontier k = cells offsets[k]..offsets[k+1] of xy (x, y per cell, global metres)
 struct bl_frontiers {
     std::vector<int32_t> offsets;

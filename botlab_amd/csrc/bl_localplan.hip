@@ -15,6 +15,10 @@
 //                 phase B; phase C then also tests every visited cell against the boxes of its step
 //   k_lp_finish   a thread per state: the flags of the pose's own cell, else the least key over the state's workgroups
 //   k_lp_poses    one thread: the poses of one candidate (bl_localplan_debug_rollout)
+//
+// What the sampling planner (bl_mppi.hip) does by the same rule is in bl_localplan_dev.h: the start flags, the window (corner, staging,
+// a visited cell's cost), the end score, the unicycle step, the key reductions, the moving rule and its compaction, and on the host
+// the field's and the tracker's checks and launch arguments.  Here stay the (cos, sin) phases, the box table, w_speed and the tables.
 #include <math.h>
 #include <string.h>
 
@@ -22,52 +26,30 @@
 #include "bl_navfield_dev.h"
 #include "bl_localplan_dev.h"
 
-#define LP_THREADS 256
 #define LP_TRIG_SLOTS 2048             // (cos, sin) pairs of a workgroup: jpb * (n_steps + 1) of them, the last of each j holds theta_end
 #define LP_RED_BYTES 64                // per wave: key cost (8), key c (4), admissible count (4)
 #define LP_LDS_FIXED (LP_TRIG_SLOTS * 8 + LP_RED_BYTES)
-#define LP_COST_NONE 0x7FFFFFFFFFFFFFFFll
 #define LP_MOV_KEPT_BYTES (BL_OBSTRACKS_MAX_TRACKS * 20)                  // lp_kept: five words per kept slot
 #define LP_MOV_BYTES (LP_MOV_KEPT_BYTES + BL_LOCALPLAN_MOVING_BYTES)
-static_assert(LP_THREADS == BL_OBSTRACKS_MAX_TRACKS, "the moving prologue has a lane per slot");
 // two workgroups with the largest window and the moving block fit a CU's 160 KiB
 static_assert(2 * (LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16 + LP_MOV_BYTES) <= 160 * 1024, "BL_LOCALPLAN_MOVING_BYTES too large");
 
-struct lp_partial { long long cost; int c; int n_adm; };
-
 struct lp_args {
-    const uint32_t* field; const uint16_t* l1; const int32_t* table; int table_n;
-    bl_frame frame;
+    lp_field f;
     const bl_localplan_state_t* states;
     const float* v_tab; const float* w_tab;      // [state][n_v], [state][n_w]
     int n_v, n_w, n_steps;
     int nvp, jpb, bps;                            // lanes per heading (a power of two >= n_v), headings and workgroups per state
-    float dt_sim;
-    int w_field, w_heading, w_clear, w_speed;
-    int win_r;                                    // half side of the staged window
+    int w_speed;
     lp_partial* partial;                          // [state][bps]
     long long* costs;                             // bl_localplan_debug_costs: every candidate's cost (one state); else null
-    float k_heading;                              // (float)(1024 / pi)
-    float move_angle[8];
     // MOVING only
-    const bl_obstrack_t* slots;                   // the tracker's BL_OBSTRACKS_MAX_TRACKS slots
-    lp_mov_div mq; int mmargin, mlead;            // bl_localplan_moving_t
+    lp_moving m;
     int reach_r;                                  // R of the window rule, staged or not
     int mov_off;                                  // where the moving block starts in the dynamic LDS
     int* first_hit;                               // bl_localplan_debug_costs_moving: per candidate; else null
     int* mpath;                                   // [state]: 0 table, 1 per step, 2 nothing kept, -1 not rolled out (the state's first workgroup writes it)
 };
-
-// the flags of the pose's own cell; (cx, cy) its cell where it has one
-__device__ __forceinline__ int lp_start_flags(const lp_args& a, const bl_localplan_state_t& st, int* cx, int* cy)
-{
-    const int W = a.frame.width, H = a.frame.height;
-    if (!nav_pose_cell(a.frame, st.pose.x, st.pose.y, cx, cy)) return BL_LOCALPLAN_OFF_FIELD;
-    if (nav_cost(a.l1, a.table, a.table_n, W, H, *cx, *cy) < 0) return BL_LOCALPLAN_OFF_FIELD;
-    const uint32_t f = a.field[(size_t)*cy * W + *cx];
-    if (f == NAV_UNREACHED) return BL_LOCALPLAN_OFF_FIELD;
-    return f == 0 ? BL_LOCALPLAN_REACHED : 0;
-}
 
 template <bool STAGED, bool MOVING>
 __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
@@ -80,23 +62,18 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
     int16_t* s_win = (int16_t*)(s_raw + LP_LDS_FIXED);
     const int state = blockIdx.x / a.bps, blk = blockIdx.x % a.bps;
     const int tid = threadIdx.x;
-    const int W = a.frame.width, H = a.frame.height;
+    const int W = a.f.frame.width, H = a.f.frame.height;
     const bl_localplan_state_t st = a.states[state];
-    int scx = 0, scy = 0;
-    const int flags = lp_start_flags(a, st, &scx, &scy);
+    const int flags = lp_start_flags(a.f, st);
     if (flags && !a.costs) {                                         // nothing is rolled out (uniform over the workgroup)
         if (MOVING && blk == 0 && tid == 0) a.mpath[state] = -1;
         return;
     }
-    // the window's centre: the pose's cell, or (for the debug costs of a pose off the grid) the grid cell nearest to it
-    const int side = 2 * a.win_r + 1;
     int wx0 = 0, wy0 = 0;
     int rx0 = 0, ry0 = 0;                                             // MOVING: the reach square's corner, its side 2 * reach_r + 1
     if (STAGED || MOVING) {
-        const double vx = ((double)st.pose.x - (double)a.frame.ox) * (double)a.frame.cpm, vy = ((double)st.pose.y - (double)a.frame.oy) * (double)a.frame.cpm;
-        const int ccx = (int)fmin(fmax(vx, 0.0), (double)(W - 1)), ccy = (int)fmin(fmax(vy, 0.0), (double)(H - 1));
-        wx0 = ccx - a.win_r; wy0 = ccy - a.win_r;
-        rx0 = ccx - a.reach_r; ry0 = ccy - a.reach_r;
+        lp_window_corner(a.f.frame, st.pose, a.f.win_r, &wx0, &wy0);
+        lp_window_corner(a.f.frame, st.pose, a.reach_r, &rx0, &ry0);
     }
     // MOVING prologue, first half: a lane per slot decides used and can-reach; the waves' counts go where the reduction's will
     lp_kept* s_kept = (lp_kept*)(s_raw + a.mov_off);
@@ -106,14 +83,14 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
     lp_kept rec;
     unsigned long long keep_mask = 0ull;
     if (MOVING) {
-        const bl_obstrack_t tr = a.slots[tid];
+        const bl_obstrack_t tr = a.m.slots[tid];
         used = lp_mov_used(tr);
-        rec = lp_mov_record(tr, a.mmargin);
+        rec = lp_mov_record(tr, a.m.mmargin);
         if (used) {
             // the displacement is monotone in k per axis: the two ends bound the sweep
             const int vx = (int)(short)(rec.v & 0xffff), vy = rec.v >> 16;
-            const int ox1 = lp_mov_offset(1 + a.mlead, vx, a.mq), oxn = lp_mov_offset(a.n_steps + a.mlead, vx, a.mq);
-            const int oy1 = lp_mov_offset(1 + a.mlead, vy, a.mq), oyn = lp_mov_offset(a.n_steps + a.mlead, vy, a.mq);
+            const int ox1 = lp_mov_offset(1 + a.m.mlead, vx, a.m.mq), oxn = lp_mov_offset(a.n_steps + a.m.mlead, vx, a.m.mq);
+            const int oy1 = lp_mov_offset(1 + a.m.mlead, vy, a.m.mq), oyn = lp_mov_offset(a.n_steps + a.m.mlead, vy, a.m.mq);
             const long long lx = (long long)rec.x0 + min(ox1, oxn), hx = (long long)rec.x1 + max(ox1, oxn);
             const long long ly = (long long)rec.y0 + min(oy1, oyn), hy = (long long)rec.y1 + max(oy1, oyn);
             keep = hx >= (long long)rx0 && lx <= (long long)rx0 + rside && hy >= (long long)ry0 && ly <= (long long)ry0 + rside;
@@ -122,16 +99,13 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
         const unsigned long long used_mask = __ballot(used);
         if ((tid & 63) == 0) { s_n[tid >> 6] = __popcll(keep_mask); s_c[tid >> 6] = __popcll(used_mask); }
     }
-    if (STAGED) {
-        for (int idx = tid; idx < side * side; idx += LP_THREADS)
-            s_win[idx] = (int16_t)nav_cost(a.l1, a.table, a.table_n, W, H, wx0 + idx % side, wy0 + idx / side);
-    }
+    if (STAGED) lp_stage_window(a.f, s_win, wx0, wy0);
     // A: the headings of this workgroup's j
     const int stride = a.n_steps + 1;
     const int j0 = blk * a.jpb;
     if (tid < a.jpb && j0 + tid < a.n_w) {
         float theta = bl_wrap_to_pi(st.pose.theta);
-        const float dth = a.w_tab[(size_t)state * a.n_w + j0 + tid] * a.dt_sim;
+        const float dth = a.w_tab[(size_t)state * a.n_w + j0 + tid] * a.f.dt_sim;
         float2* row = s_trig + tid * stride;
         for (int k = 0; k < a.n_steps; ++k) {
             row[k].x = theta;
@@ -144,12 +118,8 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
     int kept = 0, n_used = 0;
     bool boxed = false;
     if (MOVING) {
-        int base = 0;
-        for (int w = 0; w < LP_THREADS / 64; ++w) {
-            if (w < (tid >> 6)) base += s_n[w];
-            kept += s_n[w]; n_used += s_c[w];
-        }
-        if (keep) s_kept[base + __popcll(keep_mask & ((1ull << (tid & 63)) - 1ull))] = rec;
+        for (int w = 0; w < LP_WAVES; ++w) n_used += s_c[w];
+        kept = lp_mov_compact(s_n, keep_mask, keep, rec, s_kept);
         boxed = kept > 0 && (long long)kept * a.n_steps * 8 <= (long long)BL_LOCALPLAN_MOVING_BYTES;
         if (blk == 0 && tid == 0) a.mpath[state] = kept == 0 ? 2 : boxed ? 0 : 1;
     }
@@ -168,8 +138,8 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
             for (int idx = tid; idx < kept * a.n_steps; idx += LP_THREADS) {
                 const int b = idx / a.n_steps, k = idx - b * a.n_steps;
                 const lp_kept r = s_kept[b];
-                const int t = k + 1 + a.mlead;
-                const int ox = lp_mov_offset(t, (int)(short)(r.v & 0xffff), a.mq), oy = lp_mov_offset(t, r.v >> 16, a.mq);
+                const int t = k + 1 + a.m.mlead;
+                const int ox = lp_mov_offset(t, (int)(short)(r.v & 0xffff), a.m.mq), oy = lp_mov_offset(t, r.v >> 16, a.m.mq);
                 const long long lx = max((long long)r.x0 + ox, (long long)rx0) - rx0, hx = min((long long)r.x1 + ox, (long long)rx0 + rside) - rx0;
                 const long long ly = max((long long)r.y0 + oy, (long long)ry0) - ry0, hy = min((long long)r.y1 + oy, (long long)ry0 + rside) - ry0;
                 short4 bx;
@@ -187,7 +157,7 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
     int c = 0x7FFFFFFF, adm = 0;
     if (active) {
         c = j * a.n_v + i;
-        const float s = a.v_tab[(size_t)state * a.n_v + i] * a.dt_sim;
+        const float s = a.v_tab[(size_t)state * a.n_v + i] * a.f.dt_sim;
         const float2* row = s_trig + jl * stride;
         float x = st.pose.x, y = st.pose.y;
         int ex = 0, ey = 0, pen = 0;
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
             const float2 t = row[k];
             x = x + s * t.x;
             y = y + s * t.y;
-            if (!nav_pose_cell(a.frame, x, y, &ex, &ey)) { ok = false; if (all_steps) continue; break; }
+            if (!nav_pose_cell(a.f.frame, x, y, &ex, &ey)) { ok = false; if (all_steps) continue; break; }
             if (MOVING && hit_k == 0 && n_used > 0) {
                 const int mx = ex - rx0, my = ey - ry0;
                 bool hit = false;
@@ -209,58 +179,26 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_rollout(lp_args a)
                             hit = hit || (mx >= bx.x && mx <= bx.z && my >= bx.y && my <= bx.w);
                         }
                     } else {
-                        for (int b = 0; b < kept; ++b) hit = hit || lp_mov_in_box(s_kept[b], k + 1 + a.mlead, a.mq, ex, ey);
+                        for (int b = 0; b < kept; ++b) hit = hit || lp_mov_in_box(s_kept[b], k + 1 + a.m.mlead, a.m.mq, ex, ey);
                     }
-                } else hit = lp_mov_hit_all(a.slots, a.mmargin, k + 1 + a.mlead, a.mq, ex, ey);
+                } else hit = lp_mov_hit_all(a.m.slots, a.m.mmargin, k + 1 + a.m.mlead, a.m.mq, ex, ey);
                 if (hit) { hit_k = k + 1; ok = false; if (all_steps) continue; break; }
             }
             if (MOVING && !ok) continue;                              // (all_steps: only the moving test is still wanted)
-            int q;
-            const int ux = ex - wx0, uy = ey - wy0;
-            if (STAGED && (unsigned)ux < (unsigned)side && (unsigned)uy < (unsigned)side) q = s_win[uy * side + ux];
-            else q = nav_cost(a.l1, a.table, a.table_n, W, H, ex, ey);
+            const int q = lp_cell_cost<STAGED>(a.f, s_win, wx0, wy0, ex, ey);
             if (q < 0) { ok = false; if (all_steps) continue; break; }
             pen += q;
         }
         if (all_steps) a.first_hit[c] = hit_k;
-        uint32_t fe = NAV_UNREACHED;
-        if (ok) fe = a.field[(size_t)ey * W + ex];
-        if (fe != NAV_UNREACHED) {
-            int h = 0;
-            if (fe != 0) {
-                uint32_t to_f;
-                const int bm = nav_descent_move(a.field, a.l1, a.table, a.table_n, W, H, ex, ey, &to_f);
-                if (bm < 0) h = 1024;
-                else {
-                    const float d = (float)bl_angle_diff((double)row[a.n_steps].x, (double)a.move_angle[bm]);
-                    h = (int)floorf(fabsf(d) * a.k_heading);
-                }
-            }
-            cost = (long long)a.w_field * (long long)fe + (long long)a.w_heading * h + (long long)a.w_clear * pen +
-                   (long long)a.w_speed * (a.n_v - 1 - i);
+        long long score;
+        if (lp_end_score(a.f, W, H, ok, ex, ey, row[a.n_steps].x, pen, &score)) {
+            cost = score + (long long)a.w_speed * (a.n_v - 1 - i);
             adm = 1;
         }
         if (a.costs) a.costs[c] = cost;
         if (!adm) c = 0x7FFFFFFF;
     }
-    // the least key of the workgroup
-    for (int off = 32; off > 0; off >>= 1) {
-        const long long oc = __shfl_xor(cost, off);
-        const int oi = __shfl_xor(c, off);
-        adm += __shfl_xor(adm, off);
-        if (lp_key_less(oc, oi, cost, c)) { cost = oc; c = oi; }
-    }
-    if ((tid & 63) == 0) { s_cost[tid >> 6] = cost; s_c[tid >> 6] = c; s_n[tid >> 6] = adm; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < LP_THREADS / 64; ++w) {
-            if (lp_key_less(s_cost[w], s_c[w], cost, c)) { cost = s_cost[w]; c = s_c[w]; }
-            adm += s_n[w];
-        }
-        lp_partial p;
-        p.cost = cost; p.c = c; p.n_adm = adm;
-        a.partial[blockIdx.x] = p;
-    }
+    lp_block_best(cost, c, adm, s_cost, s_c, s_n, a.partial + blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void k_lp_finish(lp_args a, int n_states, bl_localplan_result_t* __restrict__ out)
@@ -268,19 +206,14 @@ __global__ __launch_bounds__(64) void k_lp_finish(lp_args a, int n_states, bl_lo
     const int state = blockIdx.x * 64 + threadIdx.x;
     if (state >= n_states) return;
     const bl_localplan_state_t st = a.states[state];
-    int cx = 0, cy = 0;
     bl_localplan_result_t r;
     r.trans_v = 0.0f; r.angular_v = 0.0f; r.index = -1; r.n_admissible = 0; r.cost = LP_COST_NONE; r.pad = 0;
-    r.flags = lp_start_flags(a, st, &cx, &cy);
+    r.flags = lp_start_flags(a.f, st);
     if (r.flags == BL_LOCALPLAN_REACHED) r.cost = 0;
     if (!r.flags) {
-        long long cost = LP_COST_NONE;
-        int c = 0x7FFFFFFF, adm = 0;
-        const lp_partial* p = a.partial + (size_t)state * a.bps;
-        for (int b = 0; b < a.bps; ++b) {
-            if (lp_key_less(p[b].cost, p[b].c, cost, c)) { cost = p[b].cost; c = p[b].c; }
-            adm += p[b].n_adm;
-        }
+        long long cost;
+        int c, adm;
+        lp_state_best(a.partial + (size_t)state * a.bps, a.bps, &cost, &c, &adm);
         r.n_admissible = adm;
         if (adm == 0) r.flags = BL_LOCALPLAN_BLOCKED;
         else {
@@ -296,14 +229,10 @@ __global__ __launch_bounds__(64) void k_lp_poses(lp_args a, int c, bl_pose_xyt_t
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     const bl_localplan_state_t st = a.states[0];
-    const float s = a.v_tab[c % a.n_v] * a.dt_sim, dth = a.w_tab[c / a.n_v] * a.dt_sim;
+    const float s = a.v_tab[c % a.n_v] * a.f.dt_sim, dth = a.w_tab[c / a.n_v] * a.f.dt_sim;
     float x = st.pose.x, y = st.pose.y, theta = bl_wrap_to_pi(st.pose.theta);
     for (int k = 0; k < a.n_steps; ++k) {
-        float sn, cs;
-        bl_sincosf(theta, &sn, &cs);
-        x = x + s * cs;
-        y = y + s * sn;
-        theta = bl_wrap_to_pi(theta + dth);
+        lp_unicycle_step(x, y, theta, s, dth);
         bl_pose_xyt_t p;
         p.utime = st.pose.utime; p.x = x; p.y = y; p.theta = theta;
         out[k] = p;
@@ -323,17 +252,6 @@ struct bl_localplan {
     int last_path; bool timed; float last_ms;
     int last_mpath;                               // bl_localplan_debug_moving_path
 };
-
-static int lp_grow(void** p, size_t* cap, size_t want, bool host, bl_ctx* ctx)
-{
-    if (want <= *cap) return BL_OK;
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    if (*p) { if (host) BL_HIP(hipHostFree(*p)); else BL_HIP(hipFree(*p)); }
-    *p = nullptr; *cap = 0;
-    if (host) BL_HIP(hipHostMalloc(p, want, hipHostMallocDefault)); else BL_HIP(hipMalloc(p, want));
-    *cap = want;
-    return BL_OK;
-}
 
 extern "C" int bl_localplan_create(bl_ctx* ctx, bl_localplan** out)
 {
@@ -399,15 +317,6 @@ static void lp_tables_of(const bl_localplan_params_t& p, const bl_localplan_stat
     if (w) lp_table((double)st.w, -(double)p.w_max, (double)p.w_max, (double)p.acc_w, (double)p.dt_control, p.n_w, w);
 }
 
-static int lp_state_ok(const bl_localplan_state_t* s, int n)
-{
-    for (int i = 0; i < n; ++i) {
-        BL_CHECK_ARG(isfinite(s[i].pose.x) && isfinite(s[i].pose.y) && isfinite(s[i].pose.theta) && isfinite(s[i].v) && isfinite(s[i].w));
-        BL_CHECK_ARG(!(fabsf(s[i].pose.theta) > BL_LOCALPLAN_MAX_THETA));             // every accepted heading wraps within bl_wrap_to_pi's guard
-    }
-    return BL_OK;
-}
-
 extern "C" int bl_localplan_tables(bl_localplan* lp, const bl_localplan_state_t* state, float* v, float* w)
 {
     BL_CHECK_ARG(lp != nullptr && state != nullptr);
@@ -423,27 +332,12 @@ static int lp_prepare(bl_localplan* lp, bl_navfield* nf, const bl_localplan_stat
 {
     BL_CHECK_ARG(lp != nullptr && nf != nullptr);
     if (!lp->have_params) { bl_set_error("local planner has no parameters (bl_localplan_set_params first)"); return BL_ERR_STATE; }
-    if (!nf->valid) { bl_set_error("navigation field not computed (bl_navfield_compute first)"); return BL_ERR_STATE; }
-    BL_CHECK_ARG(nf->ctx == lp->ctx);
-    BL_CHECK_ARG(n >= 0 && (n == 0 || states != nullptr));
     const bl_localplan_params_t& p = lp->params;
-    bl_dist_host_view v;
-    int rc = bl_dist_view_host(nf->dist, &v);
-    if (rc) return rc;
-    if (v.l1 != nf->l1 || v.frame.width != nf->frame.width || v.frame.height != nf->frame.height || v.table_n != nf->table_n) {
-        bl_set_error("local planner: the distance grid was resized since the field was computed");
-        return BL_ERR_STATE;
-    }
-    const double vabs = fmax(fabs((double)p.v_min), fabs((double)p.v_max));
-    if (vabs * (double)p.dt_sim > (double)nf->frame.mpc) {
-        bl_set_error("local planner: a step of %g m can skip a cell of %g m", vabs * (double)p.dt_sim, (double)nf->frame.mpc);
-        return BL_ERR_ARG;
-    }
-    rc = lp_state_ok(states, n);
-    if (rc) return rc;
     memset((void*)a, 0, sizeof(*a));
-    a->field = nf->field; a->l1 = nf->l1; a->table = nf->table; a->table_n = nf->table_n;
-    a->frame = nf->frame;
+    int rc = lp_prepare_field("local planner", lp->ctx, nf, n, states != nullptr, p.v_min, p.v_max, p.dt_sim, p.n_steps, p.w_field, p.w_heading,
+                              p.w_clear, &a->f, &a->reach_r, staged);
+    if (!rc) rc = lp_state_ok(states, n);
+    if (rc) return rc;
     a->n_v = p.n_v; a->n_w = p.n_w; a->n_steps = p.n_steps;
     int nvp = 1;
     while (nvp < p.n_v) nvp *= 2;
@@ -453,15 +347,7 @@ static int lp_prepare(bl_localplan* lp, bl_navfield* nf, const bl_localplan_stat
     if (jpb > p.n_w) jpb = p.n_w;
     a->jpb = jpb;
     a->bps = (p.n_w + jpb - 1) / jpb;
-    a->dt_sim = p.dt_sim;
-    a->w_field = p.w_field; a->w_heading = p.w_heading; a->w_clear = p.w_clear; a->w_speed = p.w_speed;
-    const int R = (int)ceil(vabs * (double)p.dt_sim * p.n_steps * (double)nf->frame.cpm) + 2;
-    *staged = (long long)(2 * R + 1) * (2 * R + 1) * 2 <= (long long)BL_LOCALPLAN_WINDOW_BYTES;
-    a->win_r = *staged ? R : 0;
-    a->reach_r = R;
-    a->k_heading = (float)(1024.0 / BL_PI);
-    const double ang[8] = {0.0, BL_PI, BL_PI / 2, -BL_PI / 2, BL_PI / 4, 3 * BL_PI / 4, -BL_PI / 4, -3 * BL_PI / 4};
-    for (int m = 0; m < 8; ++m) a->move_angle[m] = (float)ang[m];
+    a->w_speed = p.w_speed;
     return BL_OK;
 }
 
@@ -471,9 +357,9 @@ static int lp_upload(bl_localplan* lp, const bl_localplan_state_t* states, int n
     bl_ctx* ctx = lp->ctx;
     const bl_localplan_params_t& p = lp->params;
     const size_t sb = (size_t)n * sizeof(bl_localplan_state_t), vb = (size_t)n * p.n_v * 4, wb = (size_t)n * p.n_w * 4;
-    int rc = lp_grow(&lp->d_in, &lp->d_in_cap, sb + vb + wb, false, ctx);
-    if (!rc) rc = lp_grow(&lp->h_in, &lp->h_in_cap, sb + vb + wb, true, ctx);
-    if (!rc) rc = lp_grow((void**)&lp->d_partial, &lp->partial_cap, (size_t)n * a->bps * sizeof(lp_partial), false, ctx);
+    int rc = bl_grow(&lp->d_in, &lp->d_in_cap, sb + vb + wb, false, ctx);
+    if (!rc) rc = bl_grow(&lp->h_in, &lp->h_in_cap, sb + vb + wb, true, ctx);
+    if (!rc) rc = bl_grow((void**)&lp->d_partial, &lp->partial_cap, (size_t)n * a->bps * sizeof(lp_partial), false, ctx);
     if (rc) return rc;
     char* h = (char*)lp->h_in;
     memcpy(h, states, sb);
@@ -486,17 +372,10 @@ static int lp_upload(bl_localplan* lp, const bl_localplan_state_t* states, int n
     return BL_OK;
 }
 
-// the window's share of the dynamic LDS
-static size_t lp_window_lds(const lp_args& a, bool staged)
-{
-    const int side = 2 * a.win_r + 1;
-    return staged ? (((size_t)side * side * 2 + 15) & ~(size_t)15) : 0;
-}
-
 static int lp_launch_rollout(bl_localplan* lp, const lp_args& a, int n, bool staged)
 {
     bl_ctx* ctx = lp->ctx;
-    const size_t lds = LP_LDS_FIXED + lp_window_lds(a, staged);
+    const size_t lds = LP_LDS_FIXED + lp_window_lds(a.f, staged);
     if (staged) {
         BL_DYN_LDS_ONCE_PER_DEVICE((k_lp_rollout<true, false>), LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16, ctx);
         hipLaunchKernelGGL((k_lp_rollout<true, false>), dim3((unsigned int)(n * a.bps)), dim3(LP_THREADS), lds, ctx->stream, a);
@@ -512,7 +391,7 @@ static int lp_launch_rollout(bl_localplan* lp, const lp_args& a, int n, bool sta
 static int lp_launch_rollout_moving(bl_localplan* lp, lp_args& a, int n, bool staged)
 {
     bl_ctx* ctx = lp->ctx;
-    a.mov_off = (int)(LP_LDS_FIXED + lp_window_lds(a, staged));
+    a.mov_off = (int)(LP_LDS_FIXED + lp_window_lds(a.f, staged));
     const size_t lds = (size_t)a.mov_off + LP_MOV_BYTES;
     if (staged) {
         BL_DYN_LDS_ONCE_PER_DEVICE((k_lp_rollout<true, true>), LP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16 + LP_MOV_BYTES, ctx);
@@ -536,8 +415,8 @@ extern "C" int bl_localplan_commands(bl_localplan* lp, bl_navfield* nf, const bl
     bl_ctx* ctx = lp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t ob = (size_t)n * sizeof(bl_localplan_result_t);
-    rc = lp_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
-    if (!rc) rc = lp_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
+    rc = bl_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = bl_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
     if (!rc) rc = lp_upload(lp, states, n, &a);
     if (rc) return rc;
     BL_HIP(hipEventRecord(lp->ev0, ctx->stream));
@@ -564,8 +443,8 @@ extern "C" int bl_localplan_debug_costs(bl_localplan* lp, bl_navfield* nf, const
     bl_ctx* ctx = lp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t ob = (size_t)a.n_v * a.n_w * 8;
-    rc = lp_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
-    if (!rc) rc = lp_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
+    rc = bl_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = bl_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
     if (!rc) rc = lp_upload(lp, state, 1, &a);
     if (rc) return rc;
     a.costs = (long long*)lp->d_out;
@@ -588,8 +467,8 @@ extern "C" int bl_localplan_debug_rollout(bl_localplan* lp, bl_navfield* nf, con
     bl_ctx* ctx = lp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t ob = (size_t)a.n_steps * sizeof(bl_pose_xyt_t);
-    rc = lp_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
-    if (!rc) rc = lp_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
+    rc = bl_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = bl_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
     if (!rc) rc = lp_upload(lp, state, 1, &a);
     if (rc) return rc;
     hipLaunchKernelGGL(k_lp_poses, dim3(1), dim3(64), 0, ctx->stream, a, c, (bl_pose_xyt_t*)lp->d_out);
@@ -605,20 +484,10 @@ static int lp_prepare_moving(bl_localplan* lp, bl_navfield* nf, bl_obstracks* tr
                              int n, lp_args* a, bool* staged)
 {
     BL_CHECK_ARG(tr != nullptr && m != nullptr);
-    BL_CHECK_ARG(m->steps_per_update >= 1 && m->steps_per_update <= 255);
-    BL_CHECK_ARG(m->margin_cells >= 0 && m->margin_cells <= BL_LOCALPLAN_MAX_MARGIN);
-    BL_CHECK_ARG(m->lead_steps >= 0 && m->lead_steps <= 255);
-    BL_CHECK_ARG(m->reserved == 0);
-    int rc = lp_prepare(lp, nf, states, n, a, staged);
-    if (rc) return rc;
-    bl_obstracks_view v;
-    bl_obstracks_view_host(tr, &v);
-    BL_CHECK_ARG(v.ctx == lp->ctx && v.W == nf->frame.width && v.H == nf->frame.height);
-    if (!v.have_params) { bl_set_error("obstacle tracks have no parameters (bl_obstracks_set_params first)"); return BL_ERR_STATE; }
-    a->slots = v.d_slots;
-    a->mq.q = m->steps_per_update; a->mq.magic = (unsigned int)(((1u << 28) + (unsigned int)m->steps_per_update - 1u) / (unsigned int)m->steps_per_update);
-    a->mmargin = m->margin_cells; a->mlead = m->lead_steps;
-    return BL_OK;
+    int rc = lp_moving_check(m);
+    if (!rc) rc = lp_prepare(lp, nf, states, n, a, staged);
+    if (!rc) rc = lp_prepare_tracks(lp->ctx, nf, tr, m, &a->m);
+    return rc;
 }
 
 // the path of the first state that was rolled out; 2 when none was
@@ -640,8 +509,8 @@ extern "C" int bl_localplan_commands_moving(bl_localplan* lp, bl_navfield* nf, b
     bl_ctx* ctx = lp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t rb = (size_t)n * sizeof(bl_localplan_result_t), ob = rb + (size_t)n * 4;   // results | the states' moving paths
-    rc = lp_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
-    if (!rc) rc = lp_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
+    rc = bl_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = bl_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
     if (!rc) rc = lp_upload(lp, states, n, &a);
     if (rc) return rc;
     a.mpath = (int*)((char*)lp->d_out + rb);
@@ -671,8 +540,8 @@ extern "C" int bl_localplan_debug_costs_moving(bl_localplan* lp, bl_navfield* nf
     bl_ctx* ctx = lp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t nc = (size_t)a.n_v * a.n_w, ob = nc * 12 + 4;            // costs | first hits | the moving path
-    rc = lp_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
-    if (!rc) rc = lp_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
+    rc = bl_grow(&lp->d_out, &lp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = bl_grow(&lp->h_out, &lp->h_out_cap, ob, true, ctx);
     if (!rc) rc = lp_upload(lp, state, 1, &a);
     if (rc) return rc;
     a.costs = (long long*)lp->d_out;

@@ -12,6 +12,10 @@
 //   k_mppi_finish   a workgroup per state: the slots summed, the floor divisions, the clamp chain, the candidate's rollout (one
 //                   thread, grids read directly) and the fall-back to the best sample
 //   k_mppi_poses    one thread: the poses of a given sequence (bl_mppi_debug_rollout)
+//
+// Every rule this planner has in common with the arc planner (bl_localplan.hip) is called from bl_localplan_dev.h and stated there
+// once.  Here stay the controls (Philox, the clamp chain, Q16), the rollout's loop over periods and sub-steps, the averaging, and
+// mp_keep_slots' two barriers around the shared compaction.
 #include <math.h>
 #include <string.h>
 
@@ -21,54 +25,31 @@
 
 #define MP_THREADS 256
 #define MP_WAVES (MP_THREADS / 64)
-#define MP_COST_NONE 0x7FFFFFFFFFFFFFFFll
 #define MP_RED_BYTES 64                // per wave: key cost (8), key k (4), count (4)
 #define MP_KEPT_BYTES (BL_OBSTRACKS_MAX_TRACKS * 20)
 #define MP_LDS_FIXED (MP_RED_BYTES + MP_KEPT_BYTES)
 #define MP_MAX_SUMS (2 * BL_MPPI_MAX_HORIZON + 2)
-static_assert(MP_THREADS == BL_OBSTRACKS_MAX_TRACKS, "the moving prologue has a lane per slot");
+static_assert(MP_THREADS == LP_THREADS, "the shared prologue, staging loop and reduction are written for LP_THREADS threads");
 static_assert(MP_LDS_FIXED % 16 == 0, "the window starts 16-byte aligned");
 static_assert(sizeof(lp_kept) == 20, "MP_KEPT_BYTES");
 static_assert(sizeof(bl_mppi_params_t) == 72 && sizeof(bl_mppi_state_t) == 40 && sizeof(bl_mppi_result_t) == 56, "botlab_hip.h states these sizes");
 
-struct mp_partial { long long cost; int k; int n_adm; };
-
 struct mp_args {
-    const uint32_t* field; const uint16_t* l1; const int32_t* table; int table_n;
-    bl_frame frame;
+    lp_field f;
     const bl_mppi_state_t* states;
     const int32_t* seq_in;                        // [state][T][2], or null: zeros
     int K, T, n_sub, bps;                         // bps: workgroups per state
     int lambda;
-    float dt_sim;
-    int w_field, w_heading, w_clear;
     int vmin_q, vmax_q, wmax_q, nv_q, nw_q, av_q, aw_q;
     uint32_t seed_lo, seed_hi;
-    int win_r;                                    // half side of the staged window
-    mp_partial* partial;                          // [state][bps]
+    lp_partial* partial;                          // [state][bps]
     long long* costs;                             // [state][K]
     long long* sums;                              // [state][bps][2 T + 2]: N of (t, channel), then S and Q
     const uint32_t* wtab;                         // the 257 weights
     int debug;                                    // bl_mppi_debug_samples: rolled out whatever the flags
     int* first_hit; int32_t* seqs;                // debug: per sample; either may be null
-    float k_heading;                              // (float)(1024 / pi)
-    float move_angle[8];
-    // MOVING only
-    const bl_obstrack_t* slots;
-    lp_mov_div mq; int mmargin, mlead;
+    lp_moving m;                                  // MOVING only
 };
-
-// the flags of the pose's own cell
-__device__ __forceinline__ int mp_start_flags(const mp_args& a, const bl_localplan_state_t& st)
-{
-    const int W = a.frame.width, H = a.frame.height;
-    int cx = 0, cy = 0;
-    if (!nav_pose_cell(a.frame, st.pose.x, st.pose.y, &cx, &cy)) return BL_LOCALPLAN_OFF_FIELD;
-    if (nav_cost(a.l1, a.table, a.table_n, W, H, cx, cy) < 0) return BL_LOCALPLAN_OFF_FIELD;
-    const uint32_t f = a.field[(size_t)cy * W + cx];
-    if (f == NAV_UNREACHED) return BL_LOCALPLAN_OFF_FIELD;
-    return f == 0 ? BL_LOCALPLAN_REACHED : 0;
-}
 
 // one link of the clamp chain
 __device__ __forceinline__ int mp_clamp(long long raw, int prev, int lim_lo, int lim_hi, int a_q)
@@ -106,14 +87,13 @@ __device__ __forceinline__ void mp_sample_ctrl(const mp_args& a, int state, cons
 
 __host__ __device__ __forceinline__ int mp_q16(float x) { return (int)lrint((double)x * 65536.0); }
 
-// The rollout of a sequence: ctrl(t, &qv, &qw) hands out the controls of period t, in order.  Returns the cost, MP_COST_NONE when
+// The rollout of a sequence: ctrl(t, &qv, &qw) hands out the controls of period t, in order.  Returns the cost, LP_COST_NONE when
 // inadmissible; *hit_k the first step inside a used box (0: none).  all_steps: every step is looked at for the moving rule.
 template <bool STAGED, bool MOVING, class Ctrl>
 __device__ __forceinline__ long long mp_rollout(const mp_args& a, const bl_localplan_state_t& st, const int16_t* s_win, int wx0, int wy0,
                                                 const lp_kept* s_kept, int kept, bool all_steps, int* hit_k_out, Ctrl ctrl)
 {
-    const int W = a.frame.width, H = a.frame.height;
-    const int side = 2 * a.win_r + 1;
+    const int W = a.f.frame.width, H = a.f.frame.height;
     float x = st.pose.x, y = st.pose.y, theta = bl_wrap_to_pi(st.pose.theta);
     int ex = 0, ey = 0, pen = 0, hit_k = 0, step = 0;
     bool ok = true, done = false;
@@ -121,44 +101,25 @@ __device__ __forceinline__ long long mp_rollout(const mp_args& a, const bl_local
         int qv, qw;
         ctrl(t, &qv, &qw);
         const float v = (float)qv * 0x1p-16f, w = (float)qw * 0x1p-16f;
-        const float s = v * a.dt_sim, dth = w * a.dt_sim;
+        const float s = v * a.f.dt_sim, dth = w * a.f.dt_sim;
         for (int i = 0; i < a.n_sub && !done; ++i) {
             ++step;
-            float sn, cs;
-            bl_sincosf(theta, &sn, &cs);
-            x = x + s * cs;
-            y = y + s * sn;
-            theta = bl_wrap_to_pi(theta + dth);
-            if (!nav_pose_cell(a.frame, x, y, &ex, &ey)) { ok = false; done = !all_steps; continue; }
+            lp_unicycle_step(x, y, theta, s, dth);
+            if (!nav_pose_cell(a.f.frame, x, y, &ex, &ey)) { ok = false; done = !all_steps; continue; }
             if (MOVING && hit_k == 0) {
                 bool hit = false;
-                for (int b = 0; b < kept; ++b) hit = hit || lp_mov_in_box(s_kept[b], step + a.mlead, a.mq, ex, ey);
+                for (int b = 0; b < kept; ++b) hit = hit || lp_mov_in_box(s_kept[b], step + a.m.mlead, a.m.mq, ex, ey);
                 if (hit) { hit_k = step; ok = false; done = !all_steps; continue; }
             }
             if (!ok) continue;                                       // (all_steps: only the moving test is still wanted)
-            int q;
-            const int ux = ex - wx0, uy = ey - wy0;
-            if (STAGED && (unsigned)ux < (unsigned)side && (unsigned)uy < (unsigned)side) q = s_win[uy * side + ux];
-            else q = nav_cost(a.l1, a.table, a.table_n, W, H, ex, ey);
+            const int q = lp_cell_cost<STAGED>(a.f, s_win, wx0, wy0, ex, ey);
             if (q < 0) { ok = false; done = !all_steps; continue; }
             pen += q;
         }
     }
     if (hit_k_out) *hit_k_out = hit_k;
-    if (!ok) return MP_COST_NONE;
-    const uint32_t fe = a.field[(size_t)ey * W + ex];
-    if (fe == NAV_UNREACHED) return MP_COST_NONE;
-    int h = 0;
-    if (fe != 0) {
-        uint32_t to_f;
-        const int bm = nav_descent_move(a.field, a.l1, a.table, a.table_n, W, H, ex, ey, &to_f);
-        if (bm < 0) h = 1024;
-        else {
-            const float d = (float)bl_angle_diff((double)theta, (double)a.move_angle[bm]);
-            h = (int)floorf(fabsf(d) * a.k_heading);
-        }
-    }
-    return (long long)a.w_field * (long long)fe + (long long)a.w_heading * h + (long long)a.w_clear * pen;
+    long long score;
+    return lp_end_score(a.f, W, H, ok, ex, ey, theta, pen, &score) ? score : LP_COST_NONE;
 }
 
 // MOVING: a lane per slot decides used; the used slots compacted in slot order into s_kept.  Returns how many.  All MP_THREADS
@@ -168,18 +129,13 @@ __device__ __forceinline__ int mp_keep_slots(const mp_args& a, lp_kept* s_kept, 
 {
     if (!MOVING) return 0;
     const int tid = threadIdx.x;
-    const bl_obstrack_t tr = a.slots[tid];
+    const bl_obstrack_t tr = a.m.slots[tid];
     const bool used = lp_mov_used(tr);
-    const lp_kept rec = lp_mov_record(tr, a.mmargin);
+    const lp_kept rec = lp_mov_record(tr, a.m.mmargin);
     const unsigned long long mask = __ballot(used);
     if ((tid & 63) == 0) s_cnt[tid >> 6] = __popcll(mask);
     __syncthreads();
-    int base = 0, kept = 0;
-    for (int w = 0; w < MP_WAVES; ++w) {
-        if (w < (tid >> 6)) base += s_cnt[w];
-        kept += s_cnt[w];
-    }
-    if (used) s_kept[base + __popcll(mask & ((1ull << (tid & 63)) - 1ull))] = rec;
+    const int kept = lp_mov_compact(s_cnt, mask, used, rec, s_kept);
     __syncthreads();
     return kept;
 }
@@ -195,23 +151,17 @@ __global__ __launch_bounds__(MP_THREADS) void k_mppi_rollout(mp_args a)
     int16_t* s_win = (int16_t*)(s_raw + MP_LDS_FIXED);
     const int state = blockIdx.x / a.bps, blk = blockIdx.x % a.bps;
     const int tid = threadIdx.x;
-    const int W = a.frame.width, H = a.frame.height;
     const bl_mppi_state_t st = a.states[state];
-    if (!a.debug && mp_start_flags(a, st.s)) return;                  // nothing is drawn (uniform over the workgroup)
-    // the window's centre: the pose's cell, or (for the debug call of a pose off the grid) the grid cell nearest to it
+    if (!a.debug && lp_start_flags(a.f, st.s)) return;                // nothing is drawn (uniform over the workgroup)
     int wx0 = 0, wy0 = 0;
     if (STAGED) {
-        const double vx = ((double)st.s.pose.x - (double)a.frame.ox) * (double)a.frame.cpm, vy = ((double)st.s.pose.y - (double)a.frame.oy) * (double)a.frame.cpm;
-        const int ccx = (int)fmin(fmax(vx, 0.0), (double)(W - 1)), ccy = (int)fmin(fmax(vy, 0.0), (double)(H - 1));
-        wx0 = ccx - a.win_r; wy0 = ccy - a.win_r;
-        const int side = 2 * a.win_r + 1;
-        for (int idx = tid; idx < side * side; idx += MP_THREADS)
-            s_win[idx] = (int16_t)nav_cost(a.l1, a.table, a.table_n, W, H, wx0 + idx % side, wy0 + idx / side);
+        lp_window_corner(a.f.frame, st.s.pose, a.f.win_r, &wx0, &wy0);
+        lp_stage_window(a.f, s_win, wx0, wy0);
     }
     const int kept = mp_keep_slots<MOVING>(a, s_kept, s_n);
     __syncthreads();
     const int k = blk * MP_THREADS + tid;
-    long long cost = MP_COST_NONE;
+    long long cost = LP_COST_NONE;
     int key = 0x7FFFFFFF, adm = 0;
     if (k < a.K) {
         const int pv0 = mp_q16(st.s.v), pw0 = mp_q16(st.s.w);
@@ -229,37 +179,9 @@ __global__ __launch_bounds__(MP_THREADS) void k_mppi_rollout(mp_args a)
                 a.seqs[((size_t)k * a.T + t) * 2 + 1] = pw;
             }
         }
-        if (cost != MP_COST_NONE) { key = k; adm = 1; }
+        if (cost != LP_COST_NONE) { key = k; adm = 1; }
     }
-    // the least key of the workgroup
-    for (int off = 32; off > 0; off >>= 1) {
-        const long long oc = __shfl_xor(cost, off);
-        const int oi = __shfl_xor(key, off);
-        adm += __shfl_xor(adm, off);
-        if (lp_key_less(oc, oi, cost, key)) { cost = oc; key = oi; }
-    }
-    if ((tid & 63) == 0) { s_cost[tid >> 6] = cost; s_k[tid >> 6] = key; s_n[tid >> 6] = adm; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < MP_WAVES; ++w) {
-            if (lp_key_less(s_cost[w], s_k[w], cost, key)) { cost = s_cost[w]; key = s_k[w]; }
-            adm += s_n[w];
-        }
-        mp_partial p;
-        p.cost = cost; p.k = key; p.n_adm = adm;
-        a.partial[blockIdx.x] = p;
-    }
-}
-
-// the least key and the admissible count of a state, over its workgroups' slots
-__device__ __forceinline__ void mp_state_best(const mp_args& a, int state, long long* cost, int* key, int* adm)
-{
-    *cost = MP_COST_NONE; *key = 0x7FFFFFFF; *adm = 0;
-    const mp_partial* p = a.partial + (size_t)state * a.bps;
-    for (int b = 0; b < a.bps; ++b) {
-        if (lp_key_less(p[b].cost, p[b].k, *cost, *key)) { *cost = p[b].cost; *key = p[b].k; }
-        *adm += p[b].n_adm;
-    }
+    lp_block_best(cost, key, adm, s_cost, s_k, s_n, a.partial + blockIdx.x);
 }
 
 __global__ __launch_bounds__(MP_THREADS) void k_mppi_average(mp_args a)
@@ -269,9 +191,9 @@ __global__ __launch_bounds__(MP_THREADS) void k_mppi_average(mp_args a)
     const int state = blockIdx.x / a.bps, blk = blockIdx.x % a.bps;
     const int tid = threadIdx.x, wave = tid >> 6;
     const bl_mppi_state_t st = a.states[state];
-    if (mp_start_flags(a, st.s)) return;
+    if (lp_start_flags(a.f, st.s)) return;
     long long c_min; int best, n_adm;
-    mp_state_best(a, state, &c_min, &best, &n_adm);
+    lp_state_best(a.partial + (size_t)state * a.bps, a.bps, &c_min, &best, &n_adm);
     if (n_adm == 0) return;                                            // BLOCKED: k_mppi_finish reads no sums
     s_tab[tid] = a.wtab[tid];
     if (tid == 0) s_tab[256] = a.wtab[256];
@@ -280,7 +202,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_mppi_average(mp_args a)
     long long wgt = 0;
     if (k < a.K) {
         const long long cost = a.costs[(size_t)state * a.K + k];
-        if (cost != MP_COST_NONE) {
+        if (cost != LP_COST_NONE) {
             const unsigned long long idx = ((unsigned long long)(cost - c_min) * 16ull) / (unsigned long long)a.lambda;
             wgt = (long long)s_tab[idx < 256ull ? (int)idx : 256];
         }
@@ -318,12 +240,12 @@ __global__ __launch_bounds__(MP_THREADS) void k_mppi_finish(mp_args a, int32_t* 
     const bl_mppi_state_t st = a.states[state];
     int32_t* so = seq_out + (size_t)state * a.T * 2;
     bl_mppi_result_t r;
-    r.trans_v = 0.0f; r.angular_v = 0.0f; r.index_best = -1; r.n_admissible = 0; r.cost_best = MP_COST_NONE; r.cost_out = MP_COST_NONE;
+    r.trans_v = 0.0f; r.angular_v = 0.0f; r.index_best = -1; r.n_admissible = 0; r.cost_best = LP_COST_NONE; r.cost_out = LP_COST_NONE;
     r.weight_sum = 0; r.weight_sq_sum = 0; r.pad = 0;
-    r.flags = mp_start_flags(a, st.s);
-    long long c_min = MP_COST_NONE; int best = 0x7FFFFFFF, n_adm = 0;
+    r.flags = lp_start_flags(a.f, st.s);
+    long long c_min = LP_COST_NONE; int best = 0x7FFFFFFF, n_adm = 0;
     if (!r.flags) {
-        mp_state_best(a, state, &c_min, &best, &n_adm);
+        lp_state_best(a.partial + (size_t)state * a.bps, a.bps, &c_min, &best, &n_adm);
         if (n_adm == 0) r.flags = BL_LOCALPLAN_BLOCKED;
     }
     if (r.flags) {                                                     // uniform over the workgroup
@@ -359,7 +281,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_mppi_finish(mp_args a, int32_t* 
                                                      [&](int t, int* qv, int* qw) { *qv = s_cand[2 * t]; *qw = s_cand[2 * t + 1]; });
     r.index_best = best; r.n_admissible = n_adm; r.cost_best = c_min;
     r.weight_sum = (unsigned long long)S; r.weight_sq_sum = (unsigned long long)s_sum[2 * a.T + 1];
-    if (cost != MP_COST_NONE) {
+    if (cost != LP_COST_NONE) {
         r.cost_out = cost;
         for (int i = 0; i < 2 * a.T; ++i) so[i] = s_cand[i];
         r.trans_v = (float)s_cand[0] * 0x1p-16f; r.angular_v = (float)s_cand[1] * 0x1p-16f;
@@ -383,13 +305,9 @@ __global__ __launch_bounds__(64) void k_mppi_poses(mp_args a, const int32_t* __r
     int step = 0;
     for (int t = 0; t < a.T; ++t) {
         const float v = (float)seq[2 * t] * 0x1p-16f, w = (float)seq[2 * t + 1] * 0x1p-16f;
-        const float s = v * a.dt_sim, dth = w * a.dt_sim;
+        const float s = v * a.f.dt_sim, dth = w * a.f.dt_sim;
         for (int i = 0; i < a.n_sub; ++i) {
-            float sn, cs;
-            bl_sincosf(theta, &sn, &cs);
-            x = x + s * cs;
-            y = y + s * sn;
-            theta = bl_wrap_to_pi(theta + dth);
+            lp_unicycle_step(x, y, theta, s, dth);
             bl_pose_xyt_t p;
             p.utime = st.pose.utime; p.x = x; p.y = y; p.theta = theta;
             out[step++] = p;
@@ -414,17 +332,6 @@ struct bl_mppi {
     hipEvent_t ev0, ev1;
     int last_path; bool timed; float last_ms;
 };
-
-static int mp_grow(void** p, size_t* cap, size_t want, bool host, bl_ctx* ctx)
-{
-    if (want <= *cap) return BL_OK;
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    if (*p) { if (host) BL_HIP(hipHostFree(*p)); else BL_HIP(hipFree(*p)); }
-    *p = nullptr; *cap = 0;
-    if (host) BL_HIP(hipHostMalloc(p, want, hipHostMallocDefault)); else BL_HIP(hipMalloc(p, want));
-    *cap = want;
-    return BL_OK;
-}
 
 extern "C" void bl_mppi_weight_table(uint32_t out[257])
 {
@@ -506,8 +413,8 @@ static int mp_state_ok(const bl_mppi_state_t* s, int n)
 {
     for (int i = 0; i < n; ++i) {
         const bl_localplan_state_t& l = s[i].s;
-        BL_CHECK_ARG(isfinite(l.pose.x) && isfinite(l.pose.y) && isfinite(l.pose.theta) && isfinite(l.v) && isfinite(l.w));
-        BL_CHECK_ARG(!(fabsf(l.pose.theta) > BL_LOCALPLAN_MAX_THETA));
+        const int rc = lp_state_ok(&l, 1);
+        if (rc) return rc;
         BL_CHECK_ARG(fabs((double)l.v * 65536.0) < 4.0 * BL_MPPI_MAX_Q && fabs((double)l.w * 65536.0) < 4.0 * BL_MPPI_MAX_Q);
         BL_CHECK_ARG(abs(mp_q16(l.v)) < BL_MPPI_MAX_Q && abs(mp_q16(l.w)) < BL_MPPI_MAX_Q);
     }
@@ -520,58 +427,24 @@ static int mp_prepare(bl_mppi* mp, bl_navfield* nf, bl_obstracks* tr, const bl_l
 {
     BL_CHECK_ARG(mp != nullptr && nf != nullptr);
     BL_CHECK_ARG((tr == nullptr) == (m == nullptr));
-    if (m) {
-        BL_CHECK_ARG(m->steps_per_update >= 1 && m->steps_per_update <= 255);
-        BL_CHECK_ARG(m->margin_cells >= 0 && m->margin_cells <= BL_LOCALPLAN_MAX_MARGIN);
-        BL_CHECK_ARG(m->lead_steps >= 0 && m->lead_steps <= 255);
-        BL_CHECK_ARG(m->reserved == 0);
-    }
+    int rc = m ? lp_moving_check(m) : BL_OK;
+    if (rc) return rc;
     if (!mp->have_params) { bl_set_error("sampling local planner has no parameters (bl_mppi_set_params first)"); return BL_ERR_STATE; }
-    if (!nf->valid) { bl_set_error("navigation field not computed (bl_navfield_compute first)"); return BL_ERR_STATE; }
-    BL_CHECK_ARG(nf->ctx == mp->ctx);
-    BL_CHECK_ARG(n >= 0 && (n == 0 || states != nullptr));
     const bl_mppi_params_t& p = mp->params;
-    bl_dist_host_view v;
-    int rc = bl_dist_view_host(nf->dist, &v);
-    if (rc) return rc;
-    if (v.l1 != nf->l1 || v.frame.width != nf->frame.width || v.frame.height != nf->frame.height || v.table_n != nf->table_n) {
-        bl_set_error("sampling local planner: the distance grid was resized since the field was computed");
-        return BL_ERR_STATE;
-    }
-    const double vabs = fmax(fabs((double)p.v_min), fabs((double)p.v_max));
-    if (vabs * (double)p.dt_sim > (double)nf->frame.mpc) {
-        bl_set_error("sampling local planner: a step of %g m can skip a cell of %g m", vabs * (double)p.dt_sim, (double)nf->frame.mpc);
-        return BL_ERR_ARG;
-    }
-    rc = mp_state_ok(states, n);
-    if (rc) return rc;
     memset((void*)a, 0, sizeof(*a));
-    if (tr) {
-        bl_obstracks_view tv;
-        bl_obstracks_view_host(tr, &tv);
-        BL_CHECK_ARG(tv.ctx == mp->ctx && tv.W == nf->frame.width && tv.H == nf->frame.height);
-        if (!tv.have_params) { bl_set_error("obstacle tracks have no parameters (bl_obstracks_set_params first)"); return BL_ERR_STATE; }
-        a->slots = tv.d_slots;
-        a->mq.q = m->steps_per_update; a->mq.magic = (unsigned int)(((1u << 28) + (unsigned int)m->steps_per_update - 1u) / (unsigned int)m->steps_per_update);
-        a->mmargin = m->margin_cells; a->mlead = m->lead_steps;
-    }
-    a->field = nf->field; a->l1 = nf->l1; a->table = nf->table; a->table_n = nf->table_n;
-    a->frame = nf->frame;
+    int reach_r;                                                       // (only the arc planner's moving prologue wants it)
+    rc = lp_prepare_field("sampling local planner", mp->ctx, nf, n, states != nullptr, p.v_min, p.v_max, p.dt_sim, p.horizon * p.n_sub, p.w_field,
+                          p.w_heading, p.w_clear, &a->f, &reach_r, staged);
+    if (!rc) rc = mp_state_ok(states, n);
+    if (!rc && tr) rc = lp_prepare_tracks(mp->ctx, nf, tr, m, &a->m);
+    if (rc) return rc;
     a->K = p.n_samples; a->T = p.horizon; a->n_sub = p.n_sub;
     a->bps = (p.n_samples + MP_THREADS - 1) / MP_THREADS;
     a->lambda = p.lambda;
-    a->dt_sim = p.dt_sim;
-    a->w_field = p.w_field; a->w_heading = p.w_heading; a->w_clear = p.w_clear;
     a->vmin_q = mp->q.vmin_q; a->vmax_q = mp->q.vmax_q; a->wmax_q = mp->q.wmax_q; a->nv_q = mp->q.nv_q; a->nw_q = mp->q.nw_q;
     a->av_q = mp->q.av_q; a->aw_q = mp->q.aw_q;
     a->seed_lo = (uint32_t)(p.seed & 0xFFFFFFFFull); a->seed_hi = (uint32_t)(p.seed >> 32);
-    const int R = (int)ceil(vabs * (double)p.dt_sim * (p.horizon * p.n_sub) * (double)nf->frame.cpm) + 2;
-    *staged = (long long)(2 * R + 1) * (2 * R + 1) * 2 <= (long long)BL_LOCALPLAN_WINDOW_BYTES;
-    a->win_r = *staged ? R : 0;
     a->wtab = mp->d_wtab;
-    a->k_heading = (float)(1024.0 / BL_PI);
-    const double ang[8] = {0.0, BL_PI, BL_PI / 2, -BL_PI / 2, BL_PI / 4, 3 * BL_PI / 4, -BL_PI / 4, -3 * BL_PI / 4};
-    for (int i = 0; i < 8; ++i) a->move_angle[i] = (float)ang[i];
     return BL_OK;
 }
 
@@ -580,11 +453,11 @@ static int mp_upload(bl_mppi* mp, const bl_mppi_state_t* states, int n, const in
 {
     bl_ctx* ctx = mp->ctx;
     const size_t sb = (size_t)n * sizeof(bl_mppi_state_t), qb = seq_in ? (size_t)n * a->T * 8 : 0;
-    int rc = mp_grow(&mp->d_in, &mp->d_in_cap, sb + qb, false, ctx);
-    if (!rc) rc = mp_grow(&mp->h_in, &mp->h_in_cap, sb + qb, true, ctx);
-    if (!rc) rc = mp_grow(&mp->d_partial, &mp->partial_cap, (size_t)n * a->bps * sizeof(mp_partial), false, ctx);
-    if (!rc) rc = mp_grow(&mp->d_costs, &mp->costs_cap, (size_t)n * a->K * 8, false, ctx);
-    if (!rc) rc = mp_grow(&mp->d_sums, &mp->sums_cap, (size_t)n * a->bps * (2 * a->T + 2) * 8, false, ctx);
+    int rc = bl_grow(&mp->d_in, &mp->d_in_cap, sb + qb, false, ctx);
+    if (!rc) rc = bl_grow(&mp->h_in, &mp->h_in_cap, sb + qb, true, ctx);
+    if (!rc) rc = bl_grow(&mp->d_partial, &mp->partial_cap, (size_t)n * a->bps * sizeof(lp_partial), false, ctx);
+    if (!rc) rc = bl_grow(&mp->d_costs, &mp->costs_cap, (size_t)n * a->K * 8, false, ctx);
+    if (!rc) rc = bl_grow(&mp->d_sums, &mp->sums_cap, (size_t)n * a->bps * (2 * a->T + 2) * 8, false, ctx);
     if (rc) return rc;
     char* h = (char*)mp->h_in;
     memcpy(h, states, sb);
@@ -592,7 +465,7 @@ static int mp_upload(bl_mppi* mp, const bl_mppi_state_t* states, int n, const in
     BL_HIP(hipMemcpyAsync(mp->d_in, mp->h_in, sb + qb, hipMemcpyHostToDevice, ctx->stream));
     a->states = (const bl_mppi_state_t*)mp->d_in;
     a->seq_in = seq_in ? (const int32_t*)((char*)mp->d_in + sb) : nullptr;
-    a->partial = (mp_partial*)mp->d_partial;
+    a->partial = (lp_partial*)mp->d_partial;
     a->costs = (long long*)mp->d_costs;
     a->sums = (long long*)mp->d_sums;
     return BL_OK;
@@ -601,8 +474,7 @@ static int mp_upload(bl_mppi* mp, const bl_mppi_state_t* states, int n, const in
 static int mp_launch_rollout(bl_mppi* mp, const mp_args& a, int n, bool staged, bool moving)
 {
     bl_ctx* ctx = mp->ctx;
-    const int side = 2 * a.win_r + 1;
-    const size_t lds = MP_LDS_FIXED + (staged ? (((size_t)side * side * 2 + 15) & ~(size_t)15) : 0);
+    const size_t lds = MP_LDS_FIXED + lp_window_lds(a.f, staged);
     const dim3 grid((unsigned int)(n * a.bps)), block(MP_THREADS);
     const size_t lds_max = MP_LDS_FIXED + BL_LOCALPLAN_WINDOW_BYTES + 16;
     if (staged && moving) {
@@ -633,8 +505,8 @@ extern "C" int bl_mppi_plan(bl_mppi* mp, bl_navfield* nf, bl_obstracks* tr, cons
     bl_ctx* ctx = mp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t rb = (size_t)n * sizeof(bl_mppi_result_t), qb = (size_t)n * a.T * 8;
-    rc = mp_grow(&mp->d_out, &mp->d_out_cap, rb + qb, false, ctx);
-    if (!rc) rc = mp_grow(&mp->h_out, &mp->h_out_cap, rb + qb, true, ctx);
+    rc = bl_grow(&mp->d_out, &mp->d_out_cap, rb + qb, false, ctx);
+    if (!rc) rc = bl_grow(&mp->h_out, &mp->h_out_cap, rb + qb, true, ctx);
     if (!rc) rc = mp_upload(mp, states, n, seq_in, &a);
     if (rc) return rc;
     BL_HIP(hipEventRecord(mp->ev0, ctx->stream));
@@ -668,8 +540,8 @@ extern "C" int bl_mppi_debug_samples(bl_mppi* mp, bl_navfield* nf, bl_obstracks*
     bl_ctx* ctx = mp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t K = (size_t)a.K, cb = K * 8, fb = K * 4, qb = K * a.T * 8, ob = cb + fb + qb;   // costs | first hits | sequences
-    rc = mp_grow(&mp->d_out, &mp->d_out_cap, ob, false, ctx);
-    if (!rc) rc = mp_grow(&mp->h_out, &mp->h_out_cap, ob, true, ctx);
+    rc = bl_grow(&mp->d_out, &mp->d_out_cap, ob, false, ctx);
+    if (!rc) rc = bl_grow(&mp->h_out, &mp->h_out_cap, ob, true, ctx);
     if (!rc) rc = mp_upload(mp, state, 1, seq_in, &a);
     if (rc) return rc;
     a.debug = 1;
@@ -697,8 +569,8 @@ extern "C" int bl_mppi_debug_rollout(bl_mppi* mp, bl_navfield* nf, const bl_mppi
     bl_ctx* ctx = mp->ctx;
     BL_HIP(hipSetDevice(ctx->device));
     const size_t pb = (size_t)a.T * a.n_sub * sizeof(bl_pose_xyt_t);
-    rc = mp_grow(&mp->d_out, &mp->d_out_cap, pb, false, ctx);
-    if (!rc) rc = mp_grow(&mp->h_out, &mp->h_out_cap, pb, true, ctx);
+    rc = bl_grow(&mp->d_out, &mp->d_out_cap, pb, false, ctx);
+    if (!rc) rc = bl_grow(&mp->h_out, &mp->h_out_cap, pb, true, ctx);
     std::vector<int32_t> zeros;
     if (!seq) { zeros.assign((size_t)2 * a.T, 0); seq = zeros.data(); }
     if (!rc) rc = mp_upload(mp, state, 1, seq, &a);

@@ -260,17 +260,6 @@ __global__ __launch_bounds__(64) void k_nav_paths(nav_path_args a)
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static int nav_grow(void** p, size_t* cap, size_t want, bool host, bl_ctx* ctx)
-{
-    if (want <= *cap) return BL_OK;
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    if (*p) { if (host) BL_HIP(hipHostFree(*p)); else BL_HIP(hipFree(*p)); }
-    *p = nullptr; *cap = 0;
-    if (host) BL_HIP(hipHostMalloc(p, want, hipHostMallocDefault)); else BL_HIP(hipMalloc(p, want));
-    *cap = want;
-    return BL_OK;
-}
-
 extern "C" int bl_navfield_create(bl_ctx* ctx, bl_navfield** out)
 {
     BL_CHECK_ARG(ctx != nullptr && out != nullptr);
@@ -483,8 +472,8 @@ extern "C" int bl_navfield_paths(bl_navfield* nf, const bl_pose_xyt_t* starts, i
     }
     const size_t tail = (size_t)n * 12;                                // lens, labels, costs
     const size_t out_bytes = (size_t)n * cap_each * sizeof(bl_pose_xyt_t) + tail;
-    rc = nav_grow(&nf->q_dev, &nf->q_cap, (size_t)n * sizeof(bl_pose_xyt_t), false, ctx);
-    if (!rc) rc = nav_grow(&nf->o_dev, &nf->o_cap, out_bytes, false, ctx);
+    rc = bl_grow(&nf->q_dev, &nf->q_cap, (size_t)n * sizeof(bl_pose_xyt_t), false, ctx);
+    if (!rc) rc = bl_grow(&nf->o_dev, &nf->o_cap, out_bytes, false, ctx);
     if (rc) return rc;
     BL_HIP(hipMemcpyAsync(nf->q_dev, starts, (size_t)n * sizeof(bl_pose_xyt_t), hipMemcpyHostToDevice, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));
@@ -524,8 +513,8 @@ extern "C" int bl_navfield_gather(bl_navfield* nf, const int32_t* xy_cells, int 
     if (n == 0) return BL_OK;
     bl_ctx* ctx = nf->ctx;
     BL_HIP(hipSetDevice(ctx->device));
-    rc = nav_grow(&nf->q_dev, &nf->q_cap, (size_t)n * 8, false, ctx);
-    if (!rc) rc = nav_grow(&nf->o_dev, &nf->o_cap, (size_t)n * 4, false, ctx);
+    rc = bl_grow(&nf->q_dev, &nf->q_cap, (size_t)n * 8, false, ctx);
+    if (!rc) rc = bl_grow(&nf->o_dev, &nf->o_cap, (size_t)n * 4, false, ctx);
     if (rc) return rc;
     BL_HIP(hipMemcpyAsync(nf->q_dev, xy_cells, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));

@@ -221,17 +221,6 @@ struct bl_shortcut {
     int last_path; bool timed; float last_ms, last_ms_visible;
 };
 
-static int sc_grow(void** p, size_t* cap, size_t want, bool host, bl_ctx* ctx)
-{
-    if (want <= *cap) return BL_OK;
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    if (*p) { if (host) BL_HIP(hipHostFree(*p)); else BL_HIP(hipFree(*p)); }
-    *p = nullptr; *cap = 0;
-    if (host) BL_HIP(hipHostMalloc(p, want, hipHostMallocDefault)); else BL_HIP(hipMalloc(p, want));
-    *cap = want;
-    return BL_OK;
-}
-
 static int sc_event(bl_shortcut* sc, int k, hipEvent_t* out)
 {
     while ((int)sc->ev->size() <= k) {
@@ -315,10 +304,10 @@ static int sc_run(bl_shortcut* sc, const bl_dist* dist, const int32_t* xy, const
     const size_t in_bytes = o_ok + (size_t)ln;
     const size_t o_counts = (size_t)P * 16, o_keep = o_counts + (((size_t)P * 4 + 7) & ~(size_t)7);
     const size_t out_bytes = o_keep + (size_t)N * 4;
-    rc = sc_grow(&sc->d_in, &sc->d_in_cap, in_bytes, false, ctx);
-    if (!rc) rc = sc_grow(&sc->h_in, &sc->h_in_cap, in_bytes, true, ctx);
-    if (!rc) rc = sc_grow(&sc->d_out, &sc->d_out_cap, out_bytes + 8, false, ctx);
-    if (!rc) rc = sc_grow(&sc->h_out, &sc->h_out_cap, out_bytes + 8, true, ctx);
+    rc = bl_grow(&sc->d_in, &sc->d_in_cap, in_bytes, false, ctx);
+    if (!rc) rc = bl_grow(&sc->h_in, &sc->h_in_cap, in_bytes, true, ctx);
+    if (!rc) rc = bl_grow(&sc->d_out, &sc->d_out_cap, out_bytes + 8, false, ctx);
+    if (!rc) rc = bl_grow(&sc->h_out, &sc->h_out_cap, out_bytes + 8, true, ctx);
     if (rc) return rc;
     char* h = (char*)sc->h_in;
     if (N) memcpy(h + o_xy, xy, (size_t)N * 8);
@@ -356,7 +345,7 @@ static int sc_run(bl_shortcut* sc, const bl_dist* dist, const int32_t* xy, const
         if (m * G > max_items) max_items = m * G;
     }
     batch_first.push_back(P);
-    rc = sc_grow(&sc->d_vis, &sc->d_vis_cap, (size_t)(max_words ? max_words : 1) * 8, false, ctx);
+    rc = bl_grow(&sc->d_vis, &sc->d_vis_cap, (size_t)(max_words ? max_words : 1) * 8, false, ctx);
     if (rc) return rc;
     BL_HIP(hipMemcpyAsync(sc->d_in, sc->h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
 

@@ -86,17 +86,6 @@ __global__ __launch_bounds__(VG_MAX_THREADS) void k_view_gain(vg_args a)
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static int vg_grow(void** p, size_t* cap, size_t want, bl_ctx* ctx)
-{
-    if (want <= *cap) return BL_OK;
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    if (*p) BL_HIP(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    BL_HIP(hipMalloc(p, want));
-    *cap = want;
-    return BL_OK;
-}
-
 extern "C" int bl_viewgain_create(bl_ctx* ctx, bl_viewgain** out)
 {
     BL_CHECK_ARG(ctx != nullptr && out != nullptr);
@@ -198,8 +187,8 @@ extern "C" int bl_viewgain_compute(bl_viewgain* vg, const bl_grid* map, const in
     if (n == 0) return BL_OK;
     bl_ctx* ctx = vg->ctx;
     BL_HIP(hipSetDevice(ctx->device));
-    rc = vg_grow(&vg->q_dev, &vg->q_cap, (size_t)n * 8, ctx);
-    if (!rc) rc = vg_grow(&vg->o_dev, &vg->o_cap, (size_t)n * 4, ctx);
+    rc = bl_grow(&vg->q_dev, &vg->q_cap, (size_t)n * 8, false, ctx);
+    if (!rc) rc = bl_grow(&vg->o_dev, &vg->o_cap, (size_t)n * 4, false, ctx);
     if (rc) return rc;
     BL_HIP(hipMemcpyAsync(vg->q_dev, xy_cells, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));                       // the caller's cells are pageable host memory
@@ -219,9 +208,9 @@ extern "C" int bl_viewgain_debug_seen(bl_viewgain* vg, const bl_grid* map, int x
     BL_HIP(hipSetDevice(ctx->device));
     const int side = 2 * vg->params.radius_cells + 1;
     const size_t words = (size_t)(side * side + 31) / 32;
-    rc = vg_grow(&vg->q_dev, &vg->q_cap, 8, ctx);
-    if (!rc) rc = vg_grow(&vg->o_dev, &vg->o_cap, 4, ctx);
-    if (!rc) rc = vg_grow((void**)&vg->bits_dev, &vg->bits_cap, words * 4, ctx);
+    rc = bl_grow(&vg->q_dev, &vg->q_cap, 8, false, ctx);
+    if (!rc) rc = bl_grow(&vg->o_dev, &vg->o_cap, 4, false, ctx);
+    if (!rc) rc = bl_grow((void**)&vg->bits_dev, &vg->bits_cap, words * 4, false, ctx);
     if (rc) return rc;
     const int32_t cell[2] = {x, y};
     BL_HIP(hipMemcpyAsync(vg->q_dev, cell, 8, hipMemcpyHostToDevice, ctx->stream));

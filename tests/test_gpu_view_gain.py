@@ -166,6 +166,27 @@ def test_new_params_on_one_handle(gpu_ctx, explored):
     g.close()
 
 
+def test_larger_calls_on_one_handle(gpu_ctx, explored):
+    """The handle's buffers are reallocated by a larger call: 5 candidates and then all 84 (candidates and gains), a 21 x 21 window
+    and then an 81 x 81 one (the bitmap of debugSeen), each against the model."""
+    cells, cands = explored["astar_maze"]
+    assert len(cands) > 5
+    g = _grid(cells, gpu_ctx)
+    vg = bl.ViewGain(10, 90, ctx=gpu_ctx)
+    try:
+        for r, k in [(10, 90), (40, 180)]:
+            vg.setParams(r, k)
+            p, ends = vm.Params(r, k), vg.rayEnds()
+            for part in (cands[:5], cands):
+                assert np.array_equal(vg.compute(g, part), vm.gains(cells, p, part, ends)), (r, k, len(part))
+            x, y = int(cands[7][0]), int(cands[7][1])
+            got = vg.debugSeen(g, x, y)
+            assert got.shape == (2 * r + 1, 2 * r + 1) and got.tobytes() == vm.seen_mask(cells, p, vm.walks(ends), x, y).tobytes(), (r, k)
+    finally:
+        vg.close()
+        g.close()
+
+
 def test_map_reuploaded_and_reshaped(gpu_ctx, explored, maps):
     vg = bl.ViewGain(60, 360, ctx=gpu_ctx)
     p = vm.Params(60, 360)
