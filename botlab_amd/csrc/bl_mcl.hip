@@ -1618,6 +1618,14 @@ __global__ void k_pf_init(float4* rec, float4* parent, int N, int lo, int n_loca
     if (j >= 0 && j < n_local) parent[j] = make_float4(x, y, th, 0.0f);
 }
 
+// The weight particles() hands out: units / S.  A set of equal weights the device knows (uni_seg: a fresh filter, an upload of equal
+// units -- 1 / N either way -- and the all-floor set a sensor update leaves) has the weight its cumulative was built from, c_0 = w:
+// for the all-floor set the reference's 0.001 / wSum of its N particles (pf_w_floor), a few ulps from 2 / S = 1 / N.
+__device__ __forceinline__ double pf_export_weight(const pf_state* state, float units)
+{
+    return state->uni_n > 0 ? state->uni[0].c0 : (double)__float_as_uint(units) / state->S;
+}
+
 __global__ void k_pf_export(const float4* rec, const float4* parent, const pf_state* state, int lo, int n_local,
                             int64_t pose_utime, int64_t parent_utime, bl_particle_t* out)
 {
@@ -1629,7 +1637,7 @@ __global__ void k_pf_export(const float4* rec, const float4* parent, const pf_st
     memset(&o, 0, sizeof(o));                                // the struct's padding bytes leave the device defined (zero)
     o.pose.utime = pose_utime; o.pose.x = r.x; o.pose.y = r.y; o.pose.theta = r.z;
     o.parent_pose.utime = parent_utime; o.parent_pose.x = p.x; o.parent_pose.y = p.y; o.parent_pose.theta = p.z;
-    o.weight = (double)__float_as_uint(r.w) / state->S;
+    o.weight = pf_export_weight(state, r.w);
     out[j] = o;
 }
 
@@ -1654,7 +1662,7 @@ __global__ __launch_bounds__(256) void k_pf_encode_lcm(const float4* __restrict_
         v = d == 5 ? (uint32_t)((uint64_t)parent_utime >> 32) : d == 6 ? (uint32_t)parent_utime
           : __float_as_uint(d == 7 ? p.x : (d == 8 ? p.y : p.z));
     } else {
-        const double w = (double)__float_as_uint(rec[lo + j].w) / state->S;     // the weight k_pf_export hands out
+        const double w = pf_export_weight(state, rec[lo + j].w);                // the weight k_pf_export hands out
         const uint64_t b = (uint64_t)__double_as_longlong(w);
         v = d == 10 ? (uint32_t)(b >> 32) : (uint32_t)b;
     }

@@ -308,11 +308,12 @@ BL_PF_HELPER int bl_pf_cluster_pose(const bl_pf_cluster_t* c, uint64_t units_sum
  *   Resampling: equal units (the host compares them) are resampled against the reference's own rounded cumulative of N weights 1 / N;
  *     any other upload by the integer rule, first i with (r + m / N) * S <= prefix[i], clamped to N - 1 (strict resampling: the
  *     reference's cumulative for every set).
- *   A total of 2 * num_particles units means "every particle at the likelihood floor" (weight 0.001 / wSum in resampling and in the
- *     pose estimate) ONLY for a record a sensor update wrote, where every unit is at least 2.  An upload with that total -- [1,3,1,3..],
+ *   A total of 2 * num_particles units means "every particle at the likelihood floor" (weight 0.001 / wSum in resampling, in the
+ *     pose estimate and in what bl_pf_get_particles hands out) ONLY for a record a sensor update wrote, where every unit is at least 2.  An upload with that total -- [1,3,1,3..],
  *     [0,4,0,4..], one unit of 2 N, every unit 2 -- is resampled and estimated with units / S like any other upload. */
 int bl_pf_set_particles(bl_pf* pf, const bl_particle_t* particles, const uint32_t* units);
-/* particles(): the local shard as lcm particle_t records (synchronises). */
+/* particles(): the local shard as lcm particle_t records (synchronises).  weight = units / S; the all-floor set a sensor update
+ * leaves has the reference's 0.001 / wSum of its particles (a few ulps from 1 / N), as in resampling and in the estimate. */
 int bl_pf_get_particles(bl_pf* pf, bl_particle_t* out_local);
 /* noise source of the action model: seed for the Philox stream used when update() gets noise == NULL */
 int bl_pf_set_noise_seed(bl_pf* pf, uint64_t seed);
