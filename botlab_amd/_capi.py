@@ -268,6 +268,16 @@ class ObsLayerStats(C.Structure):
 assert C.sizeof(ObsLayerParams) == 20 and C.sizeof(ObsLayerStats) == 40
 
 
+class BeamParams(C.Structure):
+    """bl_beam_params_t: the beam model's range cut, mixture, tables' shapes, tempering span and ray stride (56 bytes)."""
+    _fields_ = [("max_range", C.c_float), ("sigma_cells", C.c_float), ("z_hit", C.c_float), ("z_short", C.c_float), ("z_max", C.c_float),
+                ("z_rand", C.c_float), ("lam", C.c_float), ("blocked_factor", C.c_float), ("occ_min", C.c_int32), ("hit_cut", C.c_int32),
+                ("ray_stride", C.c_int32), ("pad", C.c_int32), ("span", C.c_int64)]
+
+
+assert C.sizeof(BeamParams) == 56 and BeamParams.span.offset == 48
+
+
 class ObsTracksParams(C.Structure):
     """bl_obstracks_params_t: blob area limits, the gate, the two filter gains, confirmation, coasting and the speed of "moving" (32 bytes)."""
     _fields_ = [("min_cells", C.c_int32), ("max_cells", C.c_int32), ("gate_cells", C.c_int32), ("alpha", C.c_int32), ("beta", C.c_int32),
@@ -524,6 +534,19 @@ SIGNATURES = {
     "bl_mppi_weight_table": (None, [_vp]),
     "bl_mppi_debug_path": (C.c_int, [_vp]),
     "bl_mppi_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_beam_create": (C.c_int, [_vp, _P(_vp)]),
+    "bl_beam_destroy": (None, [_vp]),
+    "bl_beam_set_params": (C.c_int, [_vp, _P(BeamParams)]),
+    "bl_beam_tables": (C.c_int, [_vp, C.c_float, _vp, _vp, _vp, _vp]),
+    "bl_beam_unit_table": (None, [_vp]),
+    "bl_beam_scores": (C.c_int, [_vp, _vp, _P(Lidar), _vp, C.c_int, _vp]),
+    "bl_beam_debug_cast": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _vp, _vp, _vp, _vp, _vp]),
+    "bl_beam_reweigh_pf": (C.c_int, [_vp, _vp, _vp, _P(Lidar), _P(Pose)]),
+    "bl_beam_units": (C.c_int, [_vp, _vp, C.c_int]),
+    "bl_beam_last_rays": (C.c_int, [_vp]),
+    "bl_beam_debug_set": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "bl_beam_debug_path": (C.c_int, [_vp]),
+    "bl_beam_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
     "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_shortcut_destroy": (None, [_vp]),
     "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),

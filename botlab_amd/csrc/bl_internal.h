@@ -201,4 +201,7 @@ void bl_scan_free(bl_ctx* ctx);
 // (begin, end), den = (double)(end - begin)
 __host__ __device__ inline double bl_interp_ratio(int64_t t, int64_t begin, double den) { return (double)(t - begin) / den; }
 
+// bl_mcl.hip: the in-place install of weight units computed on the device (the beam model's bl_beam_reweigh_pf), see there
+int bl_pf_install_units(bl_pf* pf, struct bl_ctx* ctx, int (*write)(void* user, float4* rec, int n), void* user, bl_pose_xyt_t* out_pose);
+
 #endif

@@ -168,6 +168,9 @@ struct bl_pf {
     // kidnapped-robot recovery (bl_pf_set_recovery): parameters, the eligible list of its own, the update counter u, the device
     // side; sensed: rec[cur] carries sensor-model weights (the fold's condition)
     bool rc_on, sensed;
+    // the weight total S of a sensed record whose units bl_pf_install_units has since replaced (the beam model): the tracker folds the
+    // sensor update's total, not the replaced units'.  rc_S: device, a pf_state of which only S is filled; valid while sensed is true
+    pf_state* rc_S; bool rc_S_saved;
     bl_pf_recovery_params_t rc_p;
     uint32_t* rc_list; size_t rc_list_cap;
     uint32_t rc_u;
@@ -1744,7 +1747,7 @@ extern "C" void bl_pf_destroy(bl_pf* pf)
     if (!pf->rec_external) { if (pf->rec[0]) (void)hipFree(pf->rec[0]); if (pf->rec[1]) (void)hipFree(pf->rec[1]); }
     void* ptrs[] = {pf->fin_wild, pf->tile_partials, pf->fin_recs, pf->fin_tabs, pf->fin_sync, pf->prefix, pf->parent, pf->state, pf->partials, pf->block_sums, pf->dbg_idx, pf->dbg_like,
                     pf->d_noise, pf->d_export, pf->sh_xchg, pf->sh_tab, pf->sh_fin, pf->sh_flags, pf->sh_peers_dev, pf->strict_recs, pf->strict_starts,
-                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out, pf->cl_mem, pf->rc_list, pf->rc_dev, pf->ad_table};
+                    pf->gl_tiles, pf->gl_list, pf->sp_parts, pf->sp_out, pf->cl_mem, pf->rc_list, pf->rc_dev, pf->rc_S, pf->ad_table};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (pf->ad_hcount) { (void)hipHostFree(pf->ad_hcount); (void)hipEventDestroy(pf->ad_ev); }
     delete pf->ad_wfloor;
@@ -2359,7 +2362,8 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     if (rec_mode) {
         const bl_pf_recovery_params_t& q = pf->rc_p;
         pf->rc_u += 1;
-        hipLaunchKernelGGL(k_pf_recovery_fold, dim3(1), dim3(64), 0, ctx->stream, (const pf_state*)pf->state, pf->rc_dev, pf->sensed ? 1 : 0,
+        const pf_state* folded = (pf->sensed && pf->rc_S_saved) ? pf->rc_S : pf->state;     // (the kernel reads S alone)
+        hipLaunchKernelGGL(k_pf_recovery_fold, dim3(1), dim3(64), 0, ctx->stream, folded, pf->rc_dev, pf->sensed ? 1 : 0,
                            pf->rc_u, pf->N, q.alpha_slow, q.alpha_fast, q.ratio, q.max_fraction);
         a.rc = pf->rc_dev;
     }
@@ -2451,6 +2455,7 @@ extern "C" int bl_pf_update_begin(bl_pf* pf, const bl_pose_xyt_t* odometry, cons
     // update after an initialisation or upload with utime != 0; pf_launch_main's a.interp): its scan is interpolated towards utime 0
     // (D3) and its weights are an order of magnitude below the steady ones
     pf->sensed = pf->pose_utime == 0;
+    pf->rc_S_saved = false;
     pf->pending_end = true;
     return BL_OK;
 }
@@ -3783,4 +3788,36 @@ extern "C" int bl_pf_adaptive_state(bl_pf* pf, bl_pf_adaptive_state_t* out)
     out->k_sat = pf->ad_on ? pf->ad_ksat : 0u;
     out->counts = pf->ad_counts;
     return BL_OK;
+}
+
+// The beam model's way into the filter (bl_beam.hip; botlab_hip.h, "beam model"): `write` enqueues on the ctx stream what replaces the
+// weight units of the current record's n active particles in place (poses untouched); the weights are then rescanned and the
+// posterior pose estimated as bl_pf_estimate_posterior_pose does.  The units count as an upload of unequal units (pf_uni_mode -1),
+// whatever their values.  Recovery: the tracker folds a sensor update's mean weight at the start of the NEXT moved update, from
+// state->S, which the rescan here overwrites.  With recovery on and a sensed record, S is therefore kept aside first (once per
+// record) and `sensed` stays: the tracker goes on as if the units had not been replaced.  Otherwise sensed = false, as for an upload.
+// write == nullptr: the checks alone.
+int bl_pf_install_units(bl_pf* pf, bl_ctx* ctx, int (*write)(void* user, float4* rec, int n), void* user, bl_pose_xyt_t* out_pose)
+{
+    BL_CHECK_ARG(pf != nullptr && pf->ctx == ctx);
+    if (!pf->initialized || pf->pending_end) { bl_set_error("filter not initialised or update pending"); return BL_ERR_STATE; }
+    if (pf->sh_world > 1) { bl_set_error("the beam model needs the whole record on this device (composed shard)"); return BL_ERR_STATE; }
+    if (!write) return BL_OK;
+    BL_HIP(hipSetDevice(ctx->device));
+    int rc = write(user, pf->rec[pf->cur], pf->N);
+    if (rc) return rc;
+    pf->uniform_now = false;
+    pf->updated_now = false;
+    if (pf->sensed && pf->rc_on) {
+        if (!pf->rc_S_saved) {
+            if (!pf->rc_S) BL_HIP(hipMalloc((void**)&pf->rc_S, sizeof(pf_state)));
+            BL_HIP(hipMemcpyAsync(&pf->rc_S->S, &pf->state->S, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+            pf->rc_S_saved = true;
+        }
+    } else {
+        pf->sensed = false;
+    }
+    rc = pf_scan(pf, pf->cur, 1, pf->pending_utime);
+    if (rc) return rc;
+    return out_pose ? bl_pf_pose_estimate(pf, out_pose) : BL_OK;
 }

@@ -440,6 +440,10 @@ class ParticleFilter:
         check(self.ctx.lib.bl_pf_estimate_posterior_pose(self.h, C.byref(out)))
         return out
 
+    def reweigh_beam(self, beam, grid, scan):
+        """The beam model's weights in place of the current ones (BeamModel.reweigh): the beam-weighted posterior pose."""
+        return beam.reweigh(self, grid, scan)
+
     def setStrictResampling(self, on=True):
         """Resample against the reference's own sequentially rounded cumulative weight (bl_pf_set_strict_resampling)."""
         check(self.ctx.lib.bl_pf_set_strict_resampling(self.h, 1 if on else 0))
@@ -1390,6 +1394,99 @@ class ObstacleLayer:
     def close(self):
         if self.h:
             self.ctx.lib.bl_obslayer_destroy(self.h)
+            self.h = None
+
+
+BEAM_OFF_GRID = -2 ** 63
+
+
+class BeamModel:
+    """Ray-cast (beam) sensor model (bl_beam_*, include/botlab_hip.h): every used ray of a scan cast against the map as far as
+    max_range and the measured range scored against the expected one, for many poses at once.  scores() for host poses; reweigh()
+    replaces a ParticleFilter's weight units in place and returns the beam-weighted posterior pose.  Every parameter is an untuned knob;
+    span (Q16 nats) is the score gap at which a particle reaches the floor."""
+
+    def __init__(self, max_range=5.0, occ_min=1, sigma_cells=1.0, z_hit=0.7, z_short=0.1, z_max=0.05, z_rand=0.15, lam=0.1,
+                 blocked_factor=0.1, hit_cut=64, span=1 << 22, ray_stride=1, ctx=None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_beam_create(self.ctx.h, C.byref(h)))
+        self.h = h
+        try:
+            self.setParams(max_range, occ_min, sigma_cells, z_hit, z_short, z_max, z_rand, lam, blocked_factor, hit_cut, span, ray_stride)
+        except _capi.BotlabHipError:
+            self.close()
+            raise
+
+    def setParams(self, max_range, occ_min, sigma_cells, z_hit, z_short, z_max, z_rand, lam, blocked_factor, hit_cut, span, ray_stride):
+        """Refused (BotlabHipError raised): the model keeps the parameters it had."""
+        p = _capi.BeamParams(max_range, sigma_cells, z_hit, z_short, z_max, z_rand, lam, blocked_factor, int(occ_min), int(hit_cut),
+                             int(ray_stride), 0, int(span))
+        check(self.ctx.lib.bl_beam_set_params(self.h, C.byref(p)))
+        self.params = p
+
+    def tables(self, cells_per_meter):
+        """dict: hit [1024], short [1024], lt [256] (uint32) and rand, max_free, max_blocked, ln2, reach for a map of cells_per_meter."""
+        hit, short, lt, sc = np.zeros(1024, np.uint32), np.zeros(1024, np.uint32), np.zeros(256, np.uint32), np.zeros(5, np.uint32)
+        check(self.ctx.lib.bl_beam_tables(self.h, C.c_float(cells_per_meter), hit.ctypes.data, short.ctypes.data, lt.ctypes.data, sc.ctypes.data))
+        return dict(hit=hit, short=short, lt=lt, rand=int(sc[0]), max_free=int(sc[1]), max_blocked=int(sc[2]), ln2=int(sc[3]), reach=int(sc[4]))
+
+    @staticmethod
+    def unitTable():
+        """U[0 .. 256] (host arithmetic only; needs no GPU)."""
+        out = np.zeros(257, np.uint32)
+        _capi.load().bl_beam_unit_table(out.ctypes.data)
+        return out
+
+    def scores(self, grid, scan, poses):
+        """int64 [n]: S of n poses, an [n][3] array of x, y, theta (BEAM_OFF_GRID for a pose that takes no part)."""
+        q = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        hp = np.zeros(len(q), POSE_DTYPE)
+        hp["x"], hp["y"], hp["theta"] = q[:, 0], q[:, 1], q[:, 2]
+        out = np.zeros(max(len(q), 1), np.int64)
+        ls = scan.as_c()
+        check(self.ctx.lib.bl_beam_scores(self.h, grid.h, C.byref(ls), hp.ctypes.data, len(q), out.ctypes.data))
+        return out[:len(q)]
+
+    def units(self, n):
+        """uint32 [n]: the units of the last scores() or reweigh() (n: that call's count)."""
+        out = np.zeros(max(int(n), 1), np.uint32)
+        check(self.ctx.lib.bl_beam_units(self.h, out.ctypes.data, int(n)))
+        return out[:int(n)]
+
+    def debug_cast(self, grid, scan, pose):
+        """dict of int64 arrays over the used rays of one pose (x, y, theta): first, K, z, zstar, p."""
+        ls = scan.as_c()
+        m = max(scan.num_ranges, 1)
+        a = [np.zeros(m, np.int32) for _ in range(4)] + [np.zeros(m, np.uint32)]
+        po = make_pose(*pose)
+        check(self.ctx.lib.bl_beam_debug_cast(self.h, grid.h, C.byref(ls), C.byref(po), *[v.ctypes.data for v in a]))
+        r = self.ctx.lib.bl_beam_last_rays(self.h)
+        return {k: v[:r].astype(np.int64) for k, v in zip(("first", "K", "z", "zstar", "p"), a)}
+
+    def reweigh(self, pf, grid, scan):
+        """bl_beam_reweigh_pf: the filter's weight units replaced in place; returns the beam-weighted posterior pose."""
+        ls = scan.as_c()
+        out = Pose()
+        check(self.ctx.lib.bl_beam_reweigh_pf(self.h, pf.h, grid.h, C.byref(ls), C.byref(out)))
+        return out
+
+    def debugSet(self, stage_windows=False, window_bytes=0):
+        """Stage the workgroups' windows in LDS when they fit window_bytes (0: 40960).  Off by default: the grid is read directly."""
+        check(self.ctx.lib.bl_beam_debug_set(self.h, 1 if stage_windows else 0, int(window_bytes)))
+
+    def debugPath(self):
+        """0 every workgroup staged its window in LDS, 1 every one read the grid, 2 some of each; -1 before the first launch."""
+        return self.ctx.lib.bl_beam_debug_path(self.h)
+
+    def lastDeviceMs(self):
+        ms = C.c_float()
+        check(self.ctx.lib.bl_beam_last_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_beam_destroy(self.h)
             self.h = None
 
 

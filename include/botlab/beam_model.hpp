@@ -1,0 +1,113 @@
+// beam_model.hpp -- the ray-cast (beam) sensor model over the C ABI (bl_beam_*, include/botlab_hip.h, "beam model"): every used ray of
+// a scan cast against the map as far as max_range and the measured range scored against the expected one, for many poses at once.
+// scores(map, scan, poses) for poses of the caller's; ParticleFilterT::reweighBeam(beam, map, scan) (botlab_dropin.hpp) replaces a
+// filter's weight units in place and returns the beam-weighted posterior pose; OccupancyGridSLAMT::setBeamModel (slam_driver.hpp) does
+// that behind every localisation update.
+//
+// Every parameter is an untuned knob.  span (Q16 nats) is the score gap at which a particle reaches the floor.  C++11.
+#ifndef BOTLAB_BEAM_MODEL_HPP
+#define BOTLAB_BEAM_MODEL_HPP
+
+#include <cstdint>
+#include <vector>
+
+#include "botlab_dropin.hpp"
+
+namespace botlab_hip {
+
+// 5 m of range, every cell with positive log-odds occupied, a hit term one cell wide cut at 16 cells, the usual mixture, a max reading
+// through a mapped wall a tenth as likely as a free one, the floor 64 nats below the best particle, every ray
+inline bl_beam_params_t default_beam_params()
+{
+    bl_beam_params_t p;
+    p.max_range = 5.0f; p.sigma_cells = 1.0f; p.z_hit = 0.7f; p.z_short = 0.1f; p.z_max = 0.05f; p.z_rand = 0.15f; p.lambda = 0.1f;
+    p.blocked_factor = 0.1f; p.occ_min = 1; p.hit_cut = 64; p.ray_stride = 1; p.pad = 0; p.span = static_cast<int64_t>(1) << 22;
+    return p;
+}
+
+struct BeamTables {
+    std::vector<uint32_t> hit, short_, lt;                            // 1024, 1024, 256
+    uint32_t rand, max_free, max_blocked, ln2, reach;
+};
+
+struct BeamCast { std::vector<int32_t> first, K, z, zstar; std::vector<uint32_t> p; };
+
+template <class Pose, class Lidar>
+class BeamModelT {
+public:
+    explicit BeamModelT(const bl_beam_params_t& params = default_beam_params()) : h_(nullptr)
+    {
+        check(bl_beam_create(default_ctx(), &h_), "bl_beam_create");
+        const int rc = bl_beam_set_params(h_, &params);
+        if (rc != BL_OK) { bl_beam_destroy(h_); h_ = nullptr; check(rc, "bl_beam_set_params"); }
+    }
+    ~BeamModelT() { bl_beam_destroy(h_); }
+    BeamModelT(const BeamModelT&) = delete;
+    BeamModelT& operator=(const BeamModelT&) = delete;
+
+    // false (and the model keeps the parameters it had) when the library refuses them
+    bool setParams(const bl_beam_params_t& params) { return bl_beam_set_params(h_, &params) == BL_OK; }
+
+    // S of every pose (BL_BEAM_OFF_GRID for one that takes no part)
+    std::vector<int64_t> scores(const OccupancyGrid& map, const Lidar& scan, const std::vector<Pose>& poses)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        std::vector<bl_pose_xyt_t> in(poses.size() ? poses.size() : 1);
+        for (std::size_t i = 0; i < poses.size(); ++i) in[i] = pose_in(poses[i]);
+        std::vector<int64_t> out(in.size());
+        check(bl_beam_scores(h_, map.device(), &v, in.data(), static_cast<int>(poses.size()), out.data()), "bl_beam_scores");
+        out.resize(poses.size());
+        return out;
+    }
+    // the units of the last scores() or reweighBeam(); n: that call's count
+    std::vector<uint32_t> units(int n)
+    {
+        std::vector<uint32_t> out(static_cast<std::size_t>(n > 0 ? n : 1));
+        check(bl_beam_units(h_, out.data(), n), "bl_beam_units");
+        out.resize(static_cast<std::size_t>(n > 0 ? n : 0));
+        return out;
+    }
+    // the per-ray values of one pose's used rays
+    BeamCast debugCast(const OccupancyGrid& map, const Lidar& scan, const Pose& pose)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        bl_pose_xyt_t p = pose_in(pose);
+        const std::size_t m = static_cast<std::size_t>(v.num_ranges > 0 ? v.num_ranges : 1);
+        BeamCast c;
+        c.first.resize(m); c.K.resize(m); c.z.resize(m); c.zstar.resize(m); c.p.resize(m);
+        check(bl_beam_debug_cast(h_, map.device(), &v, &p, c.first.data(), c.K.data(), c.z.data(), c.zstar.data(), c.p.data()), "bl_beam_debug_cast");
+        const std::size_t r = static_cast<std::size_t>(bl_beam_last_rays(h_));
+        c.first.resize(r); c.K.resize(r); c.z.resize(r); c.zstar.resize(r); c.p.resize(r);
+        return c;
+    }
+    BeamTables tables(float cellsPerMeter) const
+    {
+        BeamTables t;
+        t.hit.resize(1024); t.short_.resize(1024); t.lt.resize(256);
+        uint32_t s[5];
+        check(bl_beam_tables(h_, cellsPerMeter, t.hit.data(), t.short_.data(), t.lt.data(), s), "bl_beam_tables");
+        t.rand = s[0]; t.max_free = s[1]; t.max_blocked = s[2]; t.ln2 = s[3]; t.reach = s[4];
+        return t;
+    }
+    static std::vector<uint32_t> unitTable()
+    {
+        std::vector<uint32_t> u(257);
+        bl_beam_unit_table(u.data());
+        return u;
+    }
+    int debugPath() const { return bl_beam_debug_path(h_); }           // 0 staged, 1 direct, 2 both, -1 none yet
+    float lastDeviceMs() const
+    {
+        float ms = 0.0f;
+        check(bl_beam_last_device_ms(h_, &ms), "bl_beam_last_device_ms");
+        return ms;
+    }
+    bl_beam* device() const { return h_; }
+
+private:
+    bl_beam* h_;
+};
+
+}  // namespace botlab_hip
+
+#endif  // BOTLAB_BEAM_MODEL_HPP

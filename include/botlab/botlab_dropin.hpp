@@ -436,7 +436,17 @@ public:
     // (extension) resample against the reference's own sequentially rounded cumulative weight: identical source indices for
     // every rand() value, at the price of an extra launch per update (botlab_hip.h, bl_pf_set_strict_resampling)
     void setStrictResampling(bool on) { check(bl_pf_set_strict_resampling(h_, on ? 1 : 0), "bl_pf_set_strict_resampling"); }
-    bl_pf* device() const { return h_; }                                        // for the device-side extras (bl_pf_encode_particles_lcm ...)
+    // (extension) the beam model's weights in place of the current ones (BeamModelT, beam_model.hpp; bl_beam_reweigh_pf): poses and
+    // parents stay, the pose returned -- and poseEstimate() from then on -- is the beam-weighted mean
+    template <class Beam>
+    Pose reweighBeam(const Beam& beam, const OccupancyGrid& map, const Lidar& laser)
+    {
+        bl_lidar_t v = lidar_view(laser);
+        bl_pose_xyt_t out;
+        check(bl_beam_reweigh_pf(beam.device(), h_, map.device(), &v, &out), "bl_beam_reweigh_pf");
+        return pose_out<Pose>(out);
+    }
+    bl_pf* device() const { return h_; }                                      // for the device-side extras (bl_pf_encode_particles_lcm ...)
 private:
     bl_pf* h_;
     int n_;

@@ -25,6 +25,7 @@
 #include <utility>
 #include <vector>
 
+#include "beam_model.hpp"
 #include "botlab_dropin.hpp"
 #include "likelihood_field.hpp"
 #include "scan_matcher.hpp"
@@ -387,6 +388,14 @@ public:
     void setLikelihoodField(bool on, const bl_lfield_params_t& p) { lfieldOn_ = on; lfieldParams_ = p; }
     bool likelihoodFieldActive() const { return static_cast<bool>(lfield_); }
     const OccupancyGrid& sensorMap() const { return lfield_ ? lfield_->grid() : grid_; }     // what the filter's update reads
+    // (extension) Beam model (BeamModelT, beam_model.hpp): every localisation update -- the searching ones of global
+    // localization and the ones under recovery included, not the action-only mode -- is followed by bl_beam_reweigh_pf against the
+    // real map and the same scan, and the pose of the iteration is the beam-weighted one.  The filter's own update is unchanged; every
+    // iteration is then the call-by-call updateFilter.  The recovery tracker keeps folding the sensor update's mean weight, not the
+    // beam units (bl_beam_reweigh_pf).  Every parameter is an untuned knob.  Off by default, and with it off nothing the driver does
+    // changes; set before the first iteration.  beamModelActive(): the switch is on and an update has been reweighed.
+    void setBeamModel(bool on, const bl_beam_params_t& p = default_beam_params()) { beamOn_ = on; beamParams_ = p; }
+    bool beamModelActive() const { return beamOn_ && static_cast<bool>(beam_); }
     // (extension) The seed of the filter's first cloud, for runs that can be repeated (the reference, and the default here, take
     // it from the OS).  Set before the first iteration.
     void setFilterSeed(uint64_t seed) { seeded_ = true; seed_ = seed; }
@@ -413,7 +422,7 @@ public:
         if (scanMatching()) correctOdometry();
         if (globalSearching()) {                        // global localization, not converged yet: filter only, the map is left alone
             before_ = now_;
-            now_ = pf_.updateFilter(odomAtScan_, scan_, sensorMap());
+            now_ = sense(odomAtScan_);
             if (globalCluster_) { searchByCluster(); return; }
             announce();
             globalConverged_ = spreadConverged();
@@ -425,7 +434,7 @@ public:
         }
         if (kidnapOn_) {                                // recovery on: the map only from an update that did not inject
             before_ = now_;
-            now_ = pf_.updateFilter(filterOdometry(), scan_, sensorMap());
+            now_ = sense(filterOdometry());
             announce();
             if (pf_.recoveryState().p_inject > 0.0) ++heldMaps_;
             else extendMap(false);
@@ -500,6 +509,22 @@ private:
     std::unique_ptr<LikelihoodFieldT> lfield_;
     bool seeded_ = false;
     uint64_t seed_ = 0;
+    // beam model: switch and parameters; the model (made on first use)
+    bool beamOn_ = false;
+    bl_beam_params_t beamParams_ = default_beam_params();
+    std::unique_ptr<BeamModelT<Pose, Lidar> > beam_;
+
+    // the filter's update from `odometry` and, with the beam model on, its weights replaced by the beam model's
+    Pose sense(const Pose& odometry)
+    {
+        Pose p = pf_.updateFilter(odometry, scan_, sensorMap());
+        if (!beamOn_) return p;
+        if (!beam_) beam_.reset(new BeamModelT<Pose, Lidar>(beamParams_));
+        const int64_t t = p.utime;
+        p = pf_.reweighBeam(*beam_, grid_, scan_);
+        p.utime = t;
+        return p;
+    }
 
     bool scanMatching() const { return matching_ && !global_ && !how_.posesGiven; }
     const Pose& filterOdometry() const { return scanMatching() ? corrected_ : odomAtScan_; }
@@ -630,12 +655,12 @@ private:
     {
         if (how_.posesGiven || !how_.mapKnown) return false;
         before_ = now_;
-        if (!how_.odometryOnly && fused_ && !adaptiveOn_ && !scanMatching() && !lfield_) {
+        if (!how_.odometryOnly && fused_ && !adaptiveOn_ && !scanMatching() && !lfield_ && !beamOn_) {
             pf_.updateFilterBegin(odomAtScan_, scan_, grid_);
             if (!waiting_.empty()) prefetch_scan(waiting_.front());      // the next scan is already queued: it rides along
             return true;
         }
-        now_ = how_.odometryOnly ? pf_.updateFilterActionOnly(filterOdometry()) : pf_.updateFilter(filterOdometry(), scan_, sensorMap());
+        now_ = how_.odometryOnly ? pf_.updateFilterActionOnly(filterOdometry()) : sense(filterOdometry());
         announce();
         return false;
     }

@@ -1678,6 +1678,108 @@ int bl_mppi_debug_path(const bl_mppi* mp);
 /* device time of the last bl_mppi_plan's kernels (HIP events around the launches); BL_ERR_STATE before the first */
 int bl_mppi_last_device_ms(const bl_mppi* mp, float* ms);
 
+/* ------------------------------------------------------------------ beam model (no reference counterpart)
+ * A ray-cast sensor model for the particle filter.  The reference's endpoint rule and the likelihood field score a ray by the cell it
+ * ends in; a pose whose rays pass through a mapped wall and end on the next one scores as well as the true pose.  The beam model
+ * (Probabilistic Robotics 6.3) casts every ray against the map as far as the maximum range and scores the measured range against
+ * the expected one.  Off by default; nothing of the filter's update changes.  EVERY PARAMETER IS AN UNTUNED KNOB.
+ *   Rays.  For one pose (x, y, theta) and one scan, ray r is DROPPED when range <= 0.15f or not finite, a RETURN when
+ *     0.15f < range < max_range, a MAX READING when range >= max_range.  Of the non-dropped rays in scan order every ray_stride-th is
+ *     USED, starting with the first; more than 4096 used rays are refused.
+ *   Geometry.  The obstacle layer's step a: float32 with one rounding per operation, one pose for the whole scan,
+ *       (px, py) = ((float)(((double)x - origin_x) * cells_per_meter), likewise y);  a = wrap_to_pi(theta - theta_r)
+ *       start cell s = (trunc(px), trunc(py));  for a return the end cell e = (trunc(fx), trunc(fy)), fx = (range * cosf(a)) *
+ *       cells_per_meter + px, fy likewise with sinf;  for every used ray the far cell m, the same expression with max_range in place of
+ *       range.  has(f) = |fx| < 2^30 and |fy| < 2^30; a ray whose has is false for e (a return) or for m is dropped for this pose.
+ *     A pose takes part when its three members are finite, |px| < 2^30, |py| < 2^30 and s lies inside the grid.
+ *   Expected range.  The obstacle layer's walk (step b) from s to m, start included, end excluded, K = Chebyshev(s, m) cells.
+ *     first = the least k whose cell is inside the grid and has log-odds >= occ_min, else K.  When first < K the ray has an
+ *     EXPECTED HIT at walk cell c*.
+ *   Lengths, in quarter cells: q(a, b) = isqrt(16 * ((ax - bx)^2 + (ay - by)^2)), exact.  z = q(e, s) for a return, z* = q(c*, s) for
+ *     an expected hit.  reach = ceil((double)max_range * cells_per_meter) <= 4096 (else BL_ERR_ARG), so every value fits 32 bits.
+ *   Per-ray probability p, a uint32.  For a return: Hit[min(|z - z*|, hit_cut)] when there is an expected hit, plus
+ *     Short[min(z >> 2, 1023)] when there is no expected hit or z < z*, plus Rand.  For a max reading: MaxFree when there is no
+ *     expected hit, else MaxBlocked.  The tables, made on the host in double (lround: ties away from zero) from the float32 members:
+ *       Hit[d]   = lround(2^30 * z_hit * exp(-((d / 4) * (d / 4)) / (2 * sigma_cells * sigma_cells))),  d = 0 .. 1023
+ *       Short[c] = lround(2^30 * z_short * lambda * exp(-lambda * c)),                                  c = 0 .. 1023
+ *       Rand = max(1, lround(2^30 * z_rand / reach));  MaxFree = max(1, lround(2^30 * z_max));
+ *       MaxBlocked = max(1, lround(2^30 * z_max * blocked_factor)).
+ *     Rand depends on the map's cells_per_meter through reach; the others on the parameters alone (bl_beam_tables takes the
+ *     cells_per_meter for this reason).  bl_beam_set_params refuses a set for which some p could be 0 or exceed 2^31 - 1.  Because the
+ *     max(1, .) above would hide the first case, it is asked of the values before it: lround(2^30 * z_rand / 4096) (the largest legal
+ *     reach), lround(2^30 * z_max) and lround(2^30 * z_max * blocked_factor) must each be >= 1; and Hit[0] + Short[0] +
+ *     lround(2^30 * z_rand) (a reach of one cell), MaxFree and MaxBlocked must each be <= 2^31 - 1.
+ *   Integer logarithm.  e = 31 - clz(p);  mant = ((p << (31 - e)) >> 23) & 255 (uint32 arithmetic);  lg(p) = (e - 30) * LN2 + LT[mant],
+ *     LT[i] = lround(65536 * ln(1 + i / 256)), LN2 = lround(65536 * ln 2).
+ *   Score.  S(pose) = the sum over the used, not dropped rays of lg(p), an int64 in Q16 nats.  A pose that takes no part scores
+ *     BL_BEAM_OFF_GRID and is ignored by the maximum.  A scan without a used ray gives S = 0 for every pose that takes part.
+ *   Weights, over the poses that take part: Smax the largest S;  j = min(256, ((Smax - S) * 256) / span) in int64;  units = U[j],
+ *     U[j] = max(1, lround(2^20 * 2^(-20 j / 256))), so U[0] = 2^20 and U[256] = 1.  span is the score gap at which a particle reaches
+ *     the floor: the tempering knob (beam models are overconfident).  A pose that takes no part gets 1 unit.
+ *   bl_beam_reweigh_pf(beam, pf, map, scan, out_pose) scores the filter's posterior poses where they lie on the device (the active
+ *     particles of the current record), replaces their weight units in place -- poses and parents untouched -- rescans the weights and
+ *     ends with what bl_pf_estimate_posterior_pose does: poseEstimate() is then the beam-weighted mean.  The units count as an UPLOAD
+ *     of unequal units (bl_pf_set_particles): neither the equal-weight rule nor the all-floor rule of a sensor update applies to
+ *     them, whatever their values.  The recovery tracker (bl_pf_set_recovery) never folds them either: with recovery on, the weight
+ *     total of the sensor update that produced the record is kept aside before its units are replaced, and that total is what the
+ *     tracker folds at the start of the next moved update, as it would have without the call.  With recovery off the record counts as
+ *     an upload for the tracker too (nothing of it is folded, also when recovery is turned on before the next update).
+ *   Refused with BL_ERR_ARG: by bl_beam_set_params a member that is not finite, max_range <= 0.15, sigma_cells <= 0, a negative z_*,
+ *     lambda or blocked_factor, any of them with 2^30 * value > 2^31, occ_min outside 1 .. 127, hit_cut outside 1 .. 1023, span
+ *     outside 1 .. 2^40, ray_stride outside 1 .. 64, and the two conditions on p (the handle keeps what it had); by the calls that
+ *     take a map a map of another ctx, reach outside 1 .. 4096, more than 4096 used rays (nothing is enqueued).  BL_ERR_STATE: the
+ *     calls that take a map, and bl_beam_tables, before bl_beam_set_params; bl_beam_units and bl_beam_last_device_ms
+ *     before the first scores / reweigh_pf; bl_beam_reweigh_pf for a filter that is not initialised, has a pending
+ *     bl_pf_update_begin, or is sharded.
+ *   How it is computed (bl_beam.hip): k_beam_cast, a workgroup per 32 poses, a wave per 4 of them in turn, a lane per ray that walks
+ *     the reference's Bresenham loop and stops at its first occupied cell; the cells from the grid through L2 (bl_beam_debug_path 1, the
+ *     default: measured faster) or, under bl_beam_debug_set, from an LDS window when the bounding box of the workgroup's start cells
+ *     widened by reach + 2 fits 40 KB (0; 2: both in one launch);
+ *     k_beam_final, one workgroup, Smax from the workgroups' records; k_beam_units.  No atomics.  Calls are stream-ordered on the ctx
+ *     stream; bl_beam_scores makes one read-back, bl_beam_reweigh_pf only the pose's. */
+#define BL_BEAM_MAX_RAYS 4096
+#define BL_BEAM_MAX_REACH 4096         /* cells: ceil(max_range * cells_per_meter) */
+#define BL_BEAM_OFF_GRID INT64_MIN
+typedef struct bl_beam_params_t {
+    float max_range;                   /* metres, finite, > 0.15 */
+    float sigma_cells;                 /* cells, > 0: the hit term's standard deviation */
+    float z_hit, z_short, z_max, z_rand;   /* >= 0: the mixture's weights (they need not sum to 1) */
+    float lambda;                      /* per cell, >= 0: the short term's decay */
+    float blocked_factor;              /* >= 0: a max reading through a mapped wall is this much less likely than a free one */
+    int32_t occ_min;                   /* 1 .. 127: a static cell is occupied when its log-odds is >= occ_min */
+    int32_t hit_cut;                   /* 1 .. 1023 quarter cells: beyond it the hit term is Hit[hit_cut] */
+    int32_t ray_stride;                /* 1 .. 64 */
+    int32_t pad;
+    int64_t span;                      /* 1 .. 2^40, Q16 nats: the score gap at which a particle reaches the floor */
+} bl_beam_params_t;                    /* 56 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48 */
+typedef struct bl_beam bl_beam;
+int bl_beam_create(bl_ctx* ctx, bl_beam** out);                        /* buffers grow on demand */
+void bl_beam_destroy(bl_beam* beam);
+int bl_beam_set_params(bl_beam* beam, const bl_beam_params_t* params); /* refused: the handle keeps what it had */
+/* the tables of the parameters in force for a map of cells_per_meter: hit[1024], short_[1024], lt[256] and scalars = Rand, MaxFree,
+ * MaxBlocked, LN2, reach; any pointer may be NULL */
+int bl_beam_tables(const bl_beam* beam, float cells_per_meter, uint32_t* hit, uint32_t* short_, uint32_t* lt, uint32_t scalars[5]);
+void bl_beam_unit_table(uint32_t out[257]);                            /* host arithmetic only */
+/* n host poses in, n scores out; any n >= 0 */
+int bl_beam_scores(bl_beam* beam, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores);
+/* The intermediate values of one pose's used rays, by the same kernel: bl_beam_last_rays() entries each (room for the scan's
+ * num_ranges is always enough); any pointer may be NULL.  A ray dropped by `has`: first = K = z = z* = -1, p = 0; z = -1 for a max
+ * reading; z* = -1 without an expected hit.  A pose that takes no part: zeros.  The units and the count that bl_beam_units reads are
+ * left as they were; bl_beam_debug_path and bl_beam_last_device_ms speak of this launch afterwards. */
+int bl_beam_debug_cast(bl_beam* beam, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_first,
+                       int32_t* out_K, int32_t* out_z, int32_t* out_zstar, uint32_t* out_p);
+int bl_beam_reweigh_pf(bl_beam* beam, bl_pf* pf, const bl_grid* map, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose);
+/* the units of the last bl_beam_scores or bl_beam_reweigh_pf; n must be that call's count (the filter's active particles) */
+int bl_beam_units(bl_beam* beam, uint32_t* out_units, int n);
+int bl_beam_last_rays(const bl_beam* beam);                            /* used rays of the last scan taken; -1 before the first */
+/* tests and probes: stage_windows 1 stages a workgroup's window in LDS when it fits (0, the default: the grid is read everywhere);
+ * window_bytes 16 .. 40960 (0: the default, 40960) is what a staged window may take */
+int bl_beam_debug_set(bl_beam* beam, int stage_windows, int window_bytes);
+/* which path the workgroups of the last launch took: 0 staged, 1 direct, 2 some of each; -1 before the first (synchronises) */
+int bl_beam_debug_path(bl_beam* beam);
+/* device time of the last call's kernels (HIP events around the launches); BL_ERR_STATE before the first */
+int bl_beam_last_device_ms(const bl_beam* beam, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
