@@ -126,6 +126,18 @@ def pose_start(pose, origin, cpm, w, h):
     return (sx, sy) if 0 <= sx < w and 0 <= sy < h else None
 
 
+def window(box, reach, W, H):
+    """(x0, y0, w, h) of the window a workgroup stages: the bounding box (x0, y0, x1, y1) of its start cells widened by reach + 2 and
+    clipped to the W x H grid, the left edge rounded down and the width up to a multiple of 4 (the rows are copied as words when W is
+    one; a column at or beyond W holds 0).  It is staged when w * h <= window_bytes.  No result depends on it, only the path."""
+    pad = reach + 2
+    x0 = max(box[0] - pad, 0) & ~3
+    y0 = max(box[1] - pad, 0)
+    w = ((min(box[2] + pad, W - 1) - x0 + 1) + 3) & ~3
+    h = min(box[3] + pad, H - 1) - y0 + 1
+    return x0, y0, w, h
+
+
 def cast(cells, origin, cpm, rays, pose, p, t):
     """Per used ray of one pose: first, K, z, zstar, p (int64 each; -1, -1, -1, -1, 0 for a ray dropped by `has`; z = -1 for a max
     reading, zstar = -1 without an expected hit), or None for an off-grid pose.  rays = used_rays(...)."""
