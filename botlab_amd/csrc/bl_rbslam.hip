@@ -920,17 +920,9 @@ extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, co
     // scan matching: the valid rays, packed for the copy; too many are refused before the ActionModel latches the odometry
     int match_rays = 0; float match_reach = 0;
     if (rb->match_on) {
-        int valid = 0;
-        for (int i = 0; i < scan->num_ranges; ++i) valid += (scan->ranges[i] > RBM_MIN_RANGE && scan->ranges[i] < rb->match.max_range) ? 1 : 0;
+        const int valid = sm_valid_rays(scan, rb->match.max_range, nullptr, nullptr, nullptr);
         BL_CHECK_ARG(valid <= RBM_MAX_RAYS);
-        for (int i = 0; i < scan->num_ranges; ++i) {
-            const float r = scan->ranges[i];
-            if (r > RBM_MIN_RANGE && r < rb->match.max_range) {
-                rb->h_match_rays[match_rays] = r; rb->h_match_rays[RBM_MAX_RAYS + match_rays] = scan->thetas[i];
-                ++match_rays;
-                if (r > match_reach) match_reach = r;
-            }
-        }
+        match_rays = sm_valid_rays(scan, rb->match.max_range, rb->h_match_rays, rb->h_match_rays + RBM_MAX_RAYS, &match_reach);
     }
     const bool moved = rb_action_update(rb, *odometry);
     const int P = rb->P;

@@ -15,51 +15,23 @@
 #ifndef BL_RBSLAM_MATCH_H
 #define BL_RBSLAM_MATCH_H
 
+#include "bl_scanmatch_dev.h"                // the rules this match has in common with bl_scanmatch.hip's, each stated there once
+
 #define RBM_THREADS 512
 #define RBM_MAX_RAYS BL_RBSLAM_MATCH_MAX_RAYS
 #define RBM_MAX_SLICES 64
 #define RBM_WINDOW_BYTES BL_RBSLAM_MATCH_WINDOW_BYTES
 #define RBM_WHOLE (1 << 20)                  // a half window of this many cells or more: the window is the whole grid
 #define RBM_NONE (-(1 << 30))                // x of an endpoint without a cell: no shift brings it into a window
-#define RBM_MIN_RANGE 0.15f                  // moving_laser_scan.cpp:24
 
 struct rb_match_args {
-    int rays;                                // valid rays: 0.15f < range < max_range
+    int rays;                                // valid rays (sm_valid_rays)
     const float* ranges; const float* thetas;
     int nx, ny, ntheta; float dtheta; int min_score;
     int hx, hy;                              // half window in cells: reach + n + 1, or RBM_WHOLE
     int ends_bytes;                          // dynamic LDS: int2 ends[rays] | uint8 window[]
     int32_t* out;                            // di | dj | dk | score | score_centre | ties | accepted, P entries each
 };
-
-// The candidate order of the definition as one unsigned key (bl_scanmatch.hip's sm_key): score, then small di*di + dj*dj, small |dk|,
-// small dk, small dj, small di.  Given d2 and dj, di is known up to its sign, and given |dk|, dk likewise: one bit each.
-__device__ __forceinline__ unsigned long long rbm_key(int score, int di, int dj, int dk)
-{
-    const uint32_t d2 = (uint32_t)(di * di + dj * dj);                 // <= 128
-    const uint32_t adk = (uint32_t)(dk < 0 ? -dk : dk);                // <= 16
-    const uint32_t lo = ((16383u - d2) << 18) | ((255u - adk) << 10) | ((dk <= 0 ? 1u : 0u) << 9) | ((uint32_t)(64 - dj) << 1) |
-                        (di <= 0 ? 1u : 0u);
-    return ((unsigned long long)(uint32_t)score << 32) | lo;
-}
-__device__ __forceinline__ void rbm_key_decode(unsigned long long key, int* score, int* di, int* dj, int* dk)
-{
-    const uint32_t lo = (uint32_t)key;
-    const int d2 = 16383 - (int)(lo >> 18);
-    const int adk = 255 - (int)((lo >> 10) & 255u);
-    *dk = (lo & 512u) ? -adk : adk;
-    *dj = 64 - (int)((lo >> 1) & 255u);
-    int a = 0;
-    while ((a + 1) * (a + 1) <= d2 - *dj * *dj) ++a;                    // at most 8 steps, once per particle
-    *di = (lo & 1u) ? -a : a;
-    *score = (int)(uint32_t)(key >> 32);
-}
-
-__device__ __forceinline__ uint32_t rbm_positive_bytes(uint32_t v)     // max(0, b) of four signed bytes
-{
-    const uint32_t neg = (v >> 7) & 0x01010101u;
-    return v & ~(neg * 0xffu);
-}
 
 template <bool STAGED>
 __global__ __launch_bounds__(RBM_THREADS) void k_rb_match(rb_weigh_args a, rb_match_args q)
@@ -68,7 +40,7 @@ __global__ __launch_bounds__(RBM_THREADS) void k_rb_match(rb_weigh_args a, rb_ma
     __shared__ int s_part[RBM_THREADS];
     __shared__ unsigned long long s_key[RBM_THREADS / 64];
     __shared__ uint32_t s_ties[RBM_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = blockIdx.x;
+    const int tid = threadIdx.x, m = blockIdx.x;
     int2* s_ends = (int2*)s_raw;
     unsigned char* s_win = s_raw + q.ends_bytes;
     const bl_frame& f = a.frame;
@@ -83,33 +55,14 @@ __global__ __launch_bounds__(RBM_THREADS) void k_rb_match(rb_weigh_args a, rb_ma
     bl_global_to_grid(px, py, f, &sx, &sy);
     const bool near = __builtin_fabsf(sx) < 0x1p29f && __builtin_fabsf(sy) < 0x1p29f;      // false for NaN
     const int cx = near ? (int)sx : 0, cy = near ? (int)sy : 0;
-    int x0 = 0, y0 = 0, x1 = f.width - 1, y1 = f.height - 1;
+    int bx0 = 0, by0 = 0, bx1 = f.width - 1, by1 = f.height - 1;
     bool any = true;
-    if (q.hx < RBM_WHOLE) { any = near; x0 = max(cx - q.hx, 0); x1 = min(cx + q.hx, f.width - 1); }
-    if (q.hy < RBM_WHOLE) { any = any && near; y0 = max(cy - q.hy, 0); y1 = min(cy + q.hy, f.height - 1); }
-    const bool dwords = (f.width & 3) == 0;
-    if (dwords) x0 &= ~3;
-    any = any && x1 >= x0 && y1 >= y0;
-    const int w = any ? x1 - x0 + 1 : 0, h = any ? y1 - y0 + 1 : 0;
-    const int pitch = (w + 3) & ~3;
+    if (q.hx < RBM_WHOLE) { any = near; bx0 = cx - q.hx; bx1 = cx + q.hx; }
+    if (q.hy < RBM_WHOLE) { any = any && near; by0 = cy - q.hy; by1 = cy + q.hy; }
+    const sm_window win = sm_clip_window(bx0, by0, bx1, by1, any, f);
+    const int x0 = win.x0, y0 = win.y0, w = win.w, h = win.h, pitch = win.pitch;
     const int8_t* cells = a.maps + (size_t)a.slot[m] * a.stride;
-    if (STAGED) {
-        if (dwords) {
-            const int qw = pitch >> 2;                                  // x0 and the grid width are multiples of four: whole dwords lie inside the row
-            for (int i = tid; i < qw * h; i += RBM_THREADS) {
-                const int row = i / qw, c4 = i - row * qw;
-                const uint32_t v = *(const uint32_t*)(cells + (size_t)(y0 + row) * f.width + x0 + 4 * c4);
-                *(uint32_t*)(s_win + row * pitch + 4 * c4) = rbm_positive_bytes(v);
-            }
-        } else {
-            for (int i = tid; i < pitch * h; i += RBM_THREADS) {
-                const int row = i / pitch, col = i - row * pitch;
-                int v = 0;
-                if (col < w) v = cells[(size_t)(y0 + row) * f.width + x0 + col];
-                s_win[i] = (unsigned char)(v > 0 ? v : 0);
-            }
-        }
-    }
+    if (STAGED) sm_stage_window(cells, f.width, win, s_win, tid, RBM_THREADS);
 
     // ---- thread t: candidate t % ncand over the rays slice, slice + S, ...; thread c < ncand owns candidate c
     const int cw = 2 * q.nx + 1, ncand = cw * (2 * q.ny + 1);           // <= 289
@@ -123,15 +76,9 @@ __global__ __launch_bounds__(RBM_THREADS) void k_rb_match(rb_weigh_args a, rb_ma
     for (int dk = -q.ntheta; dk <= q.ntheta; ++dk) {
         const float theta_k = pth + (float)dk * q.dtheta;
         for (int r = tid; r < q.rays; r += RBM_THREADS) {
-            const float ang = bl_wrap_to_pi(theta_k - q.thetas[r]);   // moving_laser_scan.cpp:33
-            float sn, cs;
-            bl_sincosf_cells(ang, &sn, &cs);
-            const float range = q.ranges[r];
-            const float fx = range * cs * f.cpm + sx;                   // sensor_model.cpp:34-35
-            const float fy = range * sn * f.cpm + sy;
             int2 e = make_int2(RBM_NONE, RBM_NONE);
-            // beyond +-2^30 (or NaN) the endpoint is nowhere near a grid: it counts nothing, and the conversion is never asked for it
-            if (__builtin_fabsf(fx) < 0x1p30f && __builtin_fabsf(fy) < 0x1p30f) e = make_int2((int)fx - x0, (int)fy - y0);
+            int ix, iy;
+            if (sm_endpoint(q.ranges[r], q.thetas[r], theta_k, sx, sy, f, &ix, &iy)) e = make_int2(ix - x0, iy - y0);
             s_ends[r] = e;
         }
         __syncthreads();                                                // the endpoints (and, the first time, the window) are in LDS
@@ -156,38 +103,24 @@ __global__ __launch_bounds__(RBM_THREADS) void k_rb_match(rb_weigh_args a, rb_ma
             int acc = 0;
             for (int k = 0; k < S; ++k) acc += s_part[k * ncand + tid];
             if (dk == 0 && di == 0 && dj == 0) centre = acc;
-            const unsigned long long kc = rbm_key(acc, di, dj, dk);
+            const unsigned long long kc = sm_key(acc, di, dj, dk);
             key = kc > key ? kc : key;
             if (acc > top) { top = acc; ties = 1; } else if (acc == top) ++ties;
         }
     }
     // ---- the particle's best key, and how many candidates share its score
-    unsigned long long wkey = key;
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(wkey, off, 64); wkey = o > wkey ? o : wkey; }
-    if (lane == 0) s_key[wave] = wkey;
-    __syncthreads();
-    unsigned long long bkey = 0;
-    for (int k = 0; k < RBM_THREADS / 64; ++k) bkey = s_key[k] > bkey ? s_key[k] : bkey;
-    uint32_t n = (tid < ncand && (uint32_t)top == (uint32_t)(bkey >> 32)) ? ties : 0;
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    if (lane == 0) s_ties[wave] = n;
-    __syncthreads();
+    const sm_best wg = sm_block_best_key(key, (uint32_t)top, ties, RBM_THREADS / 64, s_key, s_ties);      // ties is 0 from ncand on
     if (tid == q.ny * cw + q.nx) q.out[4 * a.P + m] = centre;           // the thread that owns (0, 0)
     if (tid == 0) {
-        uint32_t total = 0;
-        for (int k = 0; k < RBM_THREADS / 64; ++k) total += s_ties[k];
         int score, bi, bj, bk;
-        rbm_key_decode(bkey, &score, &bi, &bj, &bk);
+        sm_key_decode(wg.key, &score, &bi, &bj, &bk);
         const int accepted = score >= q.min_score ? 1 : 0;
-        if (accepted && (bi != 0 || bj != 0 || bk != 0)) {
-            px = (float)((double)px + (double)bi * (double)f.mpc);
-            py = (float)((double)py + (double)bj * (double)f.mpc);
-            pth = bl_wrap_to_pi(pth + (float)bk * q.dtheta);
-        }
+        // a particle that stays where the action left it keeps that pose bit for bit (its heading is not wrapped again)
+        sm_result_pose(accepted && (bi != 0 || bj != 0 || bk != 0), px, py, pth, bi, bj, bk, f.mpc, q.dtheta, &px, &py, &pth);
         a.dst[m] = make_float4(px, py, pth, 0.0f);
         a.parent[m] = make_float4(s.x, s.y, s.z, 0.0f);
         q.out[m] = bi; q.out[a.P + m] = bj; q.out[2 * a.P + m] = bk; q.out[3 * a.P + m] = score;
-        q.out[5 * a.P + m] = (int32_t)total; q.out[6 * a.P + m] = accepted;
+        q.out[5 * a.P + m] = (int32_t)wg.ties; q.out[6 * a.P + m] = accepted;
     }
 }
 

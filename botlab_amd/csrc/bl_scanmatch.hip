@@ -18,20 +18,18 @@
 //                       weight of a candidate from one multiplication by a reciprocal of half_life and a 64-entry table in LDS;
 //                       64-bit integer sums, one record per workgroup, no atomics.
 //   k_sm_moments_final  one workgroup: the sum of the records, the sub-cell fractions from the winner's six neighbours.
+// The rules these kernels, the wide match's (below) and the per-particle matcher (bl_rbslam_match.h) have in common -- the key, the map
+// window, the endpoint of a ray, the lookup sum, a workgroup's best key, the pose of the winner, the valid rays -- are in
+// bl_scanmatch_dev.h.
 #include <string.h>
 
 #define BL_SM_HELPER                   // this translation unit defines the header's two helpers with external linkage (bindings call them)
 #include "bl_internal.h"
+#include "bl_scanmatch_dev.h"          // every rule the per-particle matcher (bl_rbslam_match.h) scores by as well
 
-#define SM_MAX_N 64
 #define SM_MAX_NTHETA 180
 #define SM_MAX_RAYS 4096
 #define SM_LDS_MAX (152 * 1024)        // dynamic LDS a workgroup of k_sm_score may ask for (a CU has 160 KiB)
-// x and y of an endpoint that no candidate can bring onto the grid.  2^31 + shift - origin, taken as unsigned, lies below a window's
-// or the grid's extent only for an origin within 64 + extent of 2^31 -- in both coordinates at once that would take a grid of 2^60
-// cells (bl_grid_create allows 2^31) -- so the scoring loops need no test for it.
-#define SM_NONE INT32_MIN
-#define SM_MIN_RANGE 0.15f             // moving_laser_scan.cpp:24
 
 // device header of a match: parameters in, bounding box and result out
 struct sm_head {
@@ -44,17 +42,28 @@ struct sm_head {
     bl_scan_match_result_t result;
 };
 
+// the wide match's (below): what k_sm_raster reads and writes is its base, and base.result is the result
+struct smw_head {
+    sm_head base;
+    int32_t hlog, nbx, nby, exhaustive;
+    long long candidates;
+    unsigned int kept; int32_t pad;
+    unsigned long long scored;
+};
+
 struct sm_block_best { unsigned long long key; uint32_t ties; uint32_t pad; };
 
+// Capacities are in bytes (bl_grow).  Every match ends in a stream synchronize, so no two are in flight on a handle and one header
+// and one set of ray buffers serve the plain, the prior and the wide match.
 struct bl_scanmatch {
     bl_ctx* ctx = nullptr;
-    sm_head* d_head = nullptr;
-    float* d_rays = nullptr;           // ranges[cap] | thetas[cap]
+    smw_head* d_head = nullptr;        // the plain match uses its base
+    float* d_rays = nullptr; size_t rays_bytes = 0;        // ranges[ray_cap] | thetas[ray_cap]
     int ray_cap = 0;
     int2* d_ends = nullptr; size_t ends_cap = 0;           // [heading][ray]
-    sm_block_best* d_best = nullptr; int best_cap = 0;     // one per workgroup of k_sm_score
+    sm_block_best* d_best = nullptr; size_t best_cap = 0;  // one per workgroup of k_sm_score
     int32_t* d_volume = nullptr; size_t volume_cap = 0;
-    void* staging = nullptr;           // pinned: sm_head | ranges | thetas
+    void* staging = nullptr;           // pinned: smw_head | ranges | thetas
     size_t staging_bytes = 0;
     bool volume_kept = false;
     int vol_nx = 0, vol_ny = 0, vol_nt = 0;
@@ -64,10 +73,7 @@ struct bl_scanmatch {
     bl_scan_match_moments_t* d_mom = nullptr;
     bl_scan_match_moments_t* h_mom = nullptr;
     struct sm_partial* d_partial = nullptr;
-    // the wide match (below): buffers of its own, so that bl_scanmatch_match's are as they were
-    struct smw_head* d_whead = nullptr;
-    void* wstaging = nullptr;          // pinned: smw_head | ranges | thetas
-    float* d_wrays = nullptr; int wray_cap = 0;
+    // the wide match (below)
     unsigned char* d_pool = nullptr; size_t pool_cap = 0;          // M_h, (W + B - 1) x (H + B - 1)
     unsigned char* d_pool_rows = nullptr; size_t pool_rows_cap = 0;
     int32_t* d_bounds = nullptr; size_t bounds_cap = 0;            // [heading][block row][block column]
@@ -77,38 +83,6 @@ struct bl_scanmatch {
     bool wide_ready = false, wide_matched = false;
     bl_scan_match_wide_stats_t wide_stats = bl_scan_match_wide_stats_t();
 };
-
-// The candidate order as one unsigned key: score, then small di*di + dj*dj, small |dk|, small dk, small dj, small di.  Given
-// d2 and dj, di is known up to its sign, and given |dk|, dk likewise: one bit each (set for the negative, i.e. smaller, value).
-__device__ __forceinline__ unsigned long long sm_key(int score, int di, int dj, int dk)
-{
-    const uint32_t d2 = (uint32_t)(di * di + dj * dj);                 // <= 8192
-    const uint32_t adk = (uint32_t)(dk < 0 ? -dk : dk);                // <= 180
-    const uint32_t lo = ((16383u - d2) << 18) | ((255u - adk) << 10) | ((dk <= 0 ? 1u : 0u) << 9) | ((uint32_t)(SM_MAX_N - dj) << 1) |
-                        (di <= 0 ? 1u : 0u);
-    return ((unsigned long long)(uint32_t)score << 32) | lo;
-}
-__device__ __forceinline__ void sm_key_decode(unsigned long long key, int* score, int* di, int* dj, int* dk)
-{
-    const uint32_t lo = (uint32_t)key;
-    const int d2 = 16383 - (int)(lo >> 18);
-    const int adk = 255 - (int)((lo >> 10) & 255u);
-    *dk = (lo & 512u) ? -adk : adk;
-    *dj = SM_MAX_N - (int)((lo >> 1) & 255u);
-    int a = 0;
-    while ((a + 1) * (a + 1) <= d2 - *dj * *dj) ++a;                    // at most 64 steps, once per match
-    *di = (lo & 1u) ? -a : a;
-    *score = (int)(uint32_t)(key >> 32);
-}
-
-__device__ __forceinline__ unsigned long long sm_wave_max(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- rasteriser
 __global__ __launch_bounds__(256) void k_sm_raster(sm_head* __restrict__ head, const float* __restrict__ ranges,
@@ -122,17 +96,12 @@ __global__ __launch_bounds__(256) void k_sm_raster(sm_head* __restrict__ head, c
     const int k = t / rp, r = t - k * rp;
     if (t < total && r < rays) {
         const float theta_k = head->ctheta + (float)(k - nt) * head->dtheta;
-        const float a = bl_wrap_to_pi(theta_k - thetas[r]);             // moving_laser_scan.cpp:33
-        float sn, cs, sx, sy;
-        bl_sincosf_cells(a, &sn, &cs);
+        float sx, sy;
+        int ix, iy;
         bl_global_to_grid(head->cx, head->cy, f, &sx, &sy);
-        const float range = ranges[r];
-        const float fx = range * cs * f.cpm + sx;                       // sensor_model.cpp:34-35
-        const float fy = range * sn * f.cpm + sy;
-        // beyond +-2^30 (or NaN) the endpoint is nowhere near a grid: it counts nothing, and the conversion is never asked for it
-        if (__builtin_fabsf(fx) < 0x1p30f && __builtin_fabsf(fy) < 0x1p30f) {
-            const int ix = (int)fx, iy = (int)fy;
-            if (ix >= -nx && ix < f.width + nx && iy >= -ny && iy < f.height + ny) { ex = ix; ey = iy; }
+        if (sm_endpoint(ranges[r], thetas[r], theta_k, sx, sy, f, &ix, &iy) && ix >= -nx && ix < f.width + nx && iy >= -ny &&
+            iy < f.height + ny) {
+            ex = ix; ey = iy;
         }
     }
     if (t < total) ends[t] = make_int2(ex, ey);
@@ -149,30 +118,11 @@ __global__ __launch_bounds__(256) void k_sm_raster(sm_head* __restrict__ head, c
 }
 
 // ---------------------------------------------------------------------------------------------------------------- scoring
-// the map window of a match: the endpoints' bounding box widened by the shifts, clipped to the grid; x0 a multiple of four when the
-// rows can be copied a dword at a time
-struct sm_window { int x0, y0, w, h, pitch; bool any, dwords; };
-
+// the map window of a match: the endpoints' bounding box widened by the shifts, clipped to the grid
 __device__ __forceinline__ sm_window sm_make_window(const sm_head* head, const bl_frame& f)
 {
-    sm_window win;
     const int bx0 = head->bbox[0], by0 = head->bbox[1], bx1 = head->bbox[2], by1 = head->bbox[3];
-    win.any = bx1 >= bx0;
-    win.dwords = (f.width & 3) == 0;
-    int x0 = max(bx0 - head->nx, 0), x1 = min(bx1 + head->nx, f.width - 1);
-    int y0 = max(by0 - head->ny, 0), y1 = min(by1 + head->ny, f.height - 1);
-    if (win.dwords) x0 &= ~3;
-    win.any = win.any && x1 >= x0 && y1 >= y0;
-    win.x0 = x0; win.y0 = y0;
-    win.w = win.any ? x1 - x0 + 1 : 0; win.h = win.any ? y1 - y0 + 1 : 0;
-    win.pitch = (win.w + 3) & ~3;
-    return win;
-}
-
-__device__ __forceinline__ uint32_t sm_positive_bytes(uint32_t v)       // max(0, b) of four signed bytes
-{
-    const uint32_t neg = (v >> 7) & 0x01010101u;
-    return v & ~(neg * 0xffu);
+    return sm_clip_window(bx0 - head->nx, by0 - head->ny, bx1 + head->nx, by1 + head->ny, bx1 >= bx0, f);
 }
 
 // The prior of bl_scanmatch_match_prior as the kernels take it, and the objective's offset in the key's high word.
@@ -201,27 +151,11 @@ __device__ __forceinline__ void sm_score_body(sm_head* __restrict__ head, const 
     unsigned char* s_win = s_raw;
     const int rp = (rays + 63) & ~63;                                   // a heading's row of endpoints, padded with sentinels
     const int2* __restrict__ k_ends = ends + (size_t)k * rp;
-    const int wave = tid >> 6, lane = tid & 63;
+    const int lane = tid & 63;
 
     const sm_window win = sm_make_window(head, f);
     const bool staged = (long long)win.pitch * win.h <= (long long)lds_window_bytes;          // uniform over the whole launch
-    if (staged && win.any) {
-        if (win.dwords) {
-            const int qw = win.pitch >> 2;                              // x0 and the grid width are multiples of four: whole dwords lie inside the row
-            for (int i = tid; i < qw * win.h; i += nthreads) {
-                const int row = i / qw, q = i - row * qw;
-                const uint32_t v = *(const uint32_t*)(cells + (size_t)(win.y0 + row) * f.width + win.x0 + 4 * q);
-                *(uint32_t*)(s_win + row * win.pitch + 4 * q) = sm_positive_bytes(v);
-            }
-        } else {
-            for (int i = tid; i < win.pitch * win.h; i += nthreads) {
-                const int row = i / win.pitch, col = i - row * win.pitch;
-                int v = 0;
-                if (col < win.w) v = cells[(size_t)(win.y0 + row) * f.width + win.x0 + col];
-                s_win[i] = (unsigned char)(v > 0 ? v : 0);
-            }
-        }
-    }
+    if (staged && win.any) sm_stage_window(cells, f.width, win, s_win, tid, nthreads);
     __syncthreads();
 
     const int cw = 2 * nx + 1, ncand = cw * (2 * ny + 1);
@@ -233,34 +167,10 @@ __device__ __forceinline__ void sm_score_body(sm_head* __restrict__ head, const 
         const int c = cb + lane;
         const int jrow = c / cw;
         const int di = c - jrow * cw - nx, dj = jrow - ny;
-        int acc = 0;
-        // 64 endpoints at a time, one per lane, the next 64 on their way; each is then broadcast through a scalar register pair
-        int2 mine = rp > 0 ? k_ends[lane] : make_int2(SM_NONE, SM_NONE);
-        for (int r0 = 0; r0 < rp; r0 += 64) {
-            int2 next = mine;
-            if (r0 + 64 < rp) next = k_ends[r0 + 64 + lane];
-            if (staged) {
-                const unsigned ox = (unsigned)(di - win.x0), oy = (unsigned)(dj - win.y0);
-#pragma unroll
-                for (int i = 0; i < 64; ++i) {
-                    const int ex = __builtin_amdgcn_readlane(mine.x, i), ey = __builtin_amdgcn_readlane(mine.y, i);
-                    const unsigned ux = (unsigned)ex + ox, uy = (unsigned)ey + oy;
-                    const bool in = ux < (unsigned)win.w && uy < (unsigned)win.h;      // never true for a sentinel (see SM_NONE)
-                    const int v = s_win[in ? uy * (unsigned)win.pitch + ux : 0u];      // no branch: the reads of a batch overlap
-                    acc += in ? v : 0;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 64; ++i) {
-                    const int ex = __builtin_amdgcn_readlane(mine.x, i), ey = __builtin_amdgcn_readlane(mine.y, i);
-                    const unsigned x = (unsigned)ex + (unsigned)di, y = (unsigned)ey + (unsigned)dj;
-                    const bool in = x < (unsigned)f.width && y < (unsigned)f.height;
-                    const int v = cells[in ? (size_t)y * f.width + x : (size_t)0];
-                    acc += (in && v > 0) ? v : 0;
-                }
-            }
-            mine = next;
-        }
+        int acc = staged ? sm_lookup_sum<false>(k_ends, rp, lane, (unsigned)(di - win.x0), (unsigned)(dj - win.y0), s_win, (unsigned)win.w,
+                                                (unsigned)win.h, (unsigned)win.pitch)
+                         : sm_lookup_sum<true>(k_ends, rp, lane, (unsigned)di, (unsigned)dj, (const unsigned char*)cells, (unsigned)f.width,
+                                               (unsigned)f.height, (unsigned)f.width);
         if (c >= c_end) continue;
         if (PRIOR) acc -= sm_pen(pr, di, dj, dk);                            // from here on the objective; the centre's pen is 0
         if (volume) volume[(size_t)k * ncand + c] = acc;
@@ -269,21 +179,10 @@ __device__ __forceinline__ void sm_score_body(sm_head* __restrict__ head, const 
         key = kc > key ? kc : key;
         if (acc > top) { top = acc; ties = 1; } else if (acc == top) ++ties;
     }
-    // the workgroup's best key, and how many of its candidates share that score
-    const unsigned long long wkey = sm_wave_max(key);
-    if (lane == 0) s_key[wave] = wkey;
-    __syncthreads();
-    unsigned long long bkey = 0;
-    for (int w = 0; w < (nthreads >> 6); ++w) bkey = s_key[w] > bkey ? s_key[w] : bkey;
-    uint32_t n = PRIOR ? ((ties != 0 && (uint32_t)(top + SM_OBJ_BIAS) == (uint32_t)(bkey >> 32)) ? ties : 0)
-                       : ((top >= 0 && (uint32_t)top == (uint32_t)(bkey >> 32)) ? ties : 0);
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
-    if (lane == 0) s_ties[wave] = n;
-    __syncthreads();
+    // a thread without candidates has ties 0, whatever its top
+    const sm_best wg = sm_block_best_key(key, (uint32_t)(PRIOR ? top + SM_OBJ_BIAS : top), ties, nthreads >> 6, s_key, s_ties);
     if (tid == 0) {
-        uint32_t total = 0;
-        for (int w = 0; w < (nthreads >> 6); ++w) total += s_ties[w];
-        sm_block_best b; b.key = bkey; b.ties = (c_end > c_begin) ? total : 0; b.pad = 0;
+        sm_block_best b; b.key = wg.key; b.ties = (c_end > c_begin) ? wg.ties : 0; b.pad = 0;
         best[blockIdx.y * gridDim.x + blockIdx.x] = b;
         if (blockIdx.x == 0 && blockIdx.y == 0) head->path = staged ? 0 : 1;
     }
@@ -304,6 +203,22 @@ __global__ __launch_bounds__(1024) void k_sm_score_prior(sm_head* __restrict__ h
 }
 
 // ---------------------------------------------------------------------------------------------------------------- result
+// the result struct of the plain, the prior and the wide match, from the winner and the header; one thread
+__device__ __forceinline__ void sm_write_result(sm_head* __restrict__ head, const bl_frame& f, int di, int dj, int dk, int score,
+                                                int32_t ties)
+{
+    bl_scan_match_result_t r;
+    r.di = di; r.dj = dj; r.dk = dk;
+    r.score = score;
+    r.score_centre = head->score_centre;
+    r.ties = ties;
+    r.rays_used = head->rays;
+    r.accepted = score >= head->min_score ? 1 : 0;
+    r.pose.utime = head->utime;
+    sm_result_pose(r.accepted != 0, head->cx, head->cy, head->ctheta, di, dj, dk, f.mpc, head->dtheta, &r.pose.x, &r.pose.y, &r.pose.theta);
+    head->result = r;
+}
+
 template <bool PRIOR>
 __device__ __forceinline__ void sm_final_body(sm_head* __restrict__ head, const sm_block_best* __restrict__ best, int nblocks,
                                               const bl_frame& f, const sm_prior_k& pr, bl_scan_match_moments_t* __restrict__ mom)
@@ -334,22 +249,7 @@ __device__ __forceinline__ void sm_final_body(sm_head* __restrict__ head, const 
             mom->best_obj = obj; mom->pen_best = pen;
             score = obj + pen;
         }
-        bl_scan_match_result_t r;
-        r.di = di; r.dj = dj; r.dk = dk;
-        r.score = score;
-        r.score_centre = head->score_centre;
-        r.ties = (int32_t)(s_ties[0] + s_ties[1] + s_ties[2] + s_ties[3]);
-        r.rays_used = head->rays;
-        r.accepted = score >= head->min_score ? 1 : 0;
-        r.pose.utime = head->utime;
-        if (r.accepted) {
-            r.pose.x = (float)((double)head->cx + (double)di * (double)f.mpc);
-            r.pose.y = (float)((double)head->cy + (double)dj * (double)f.mpc);
-            r.pose.theta = bl_wrap_to_pi(head->ctheta + (float)dk * head->dtheta);
-        } else {
-            r.pose.x = head->cx; r.pose.y = head->cy; r.pose.theta = head->ctheta;
-        }
-        head->result = r;
+        sm_write_result(head, f, di, dj, dk, score, (int32_t)(s_ties[0] + s_ties[1] + s_ties[2] + s_ties[3]));
     }
 }
 
@@ -510,7 +410,7 @@ extern "C" int bl_scanmatch_create(bl_ctx* ctx, bl_scanmatch** out)
     BL_HIP(hipFuncSetAttribute((const void*)k_sm_score_prior, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_MAX));
     bl_scanmatch* sm = new bl_scanmatch();
     sm->ctx = ctx;
-    hipError_t e = hipMalloc((void**)&sm->d_head, sizeof(sm_head));
+    hipError_t e = hipMalloc((void**)&sm->d_head, sizeof(smw_head));
     if (e != hipSuccess) { bl_set_error("hipMalloc failed: %s", hipGetErrorString(e)); delete sm; return BL_ERR_HIP; }
     *out = sm;
     return BL_OK;
@@ -524,19 +424,50 @@ extern "C" void bl_scanmatch_destroy(bl_scanmatch* sm)
     (void)hipFree(sm->d_mom); (void)hipFree(sm->d_partial);
     if (sm->h_mom) (void)hipHostFree(sm->h_mom);
     if (sm->staging) (void)hipHostFree(sm->staging);
-    (void)hipFree(sm->d_whead); (void)hipFree(sm->d_wrays); (void)hipFree(sm->d_pool); (void)hipFree(sm->d_pool_rows);
+    (void)hipFree(sm->d_pool); (void)hipFree(sm->d_pool_rows);
     (void)hipFree(sm->d_bounds); (void)hipFree(sm->d_list); (void)hipFree(sm->d_seeds); (void)hipFree(sm->d_rec);
-    if (sm->wstaging) (void)hipHostFree(sm->wstaging);
     delete sm;
 }
 
-template <typename T>
-static int sm_grow(T** p, size_t* cap, size_t need)
+// What every match begins with, behind its checks.  The ray buffers (device ranges | thetas, and the pinned block: the larger header,
+// then the same) and the endpoints for every heading of `rays` valid rays; then the pinned header zeroed and filled but for what is
+// the wide match's alone, and the valid rays packed behind it.  *reach: the largest valid range.
+static int sm_begin(bl_scanmatch* sm, const bl_lidar_t* scan, const bl_pose_xyt_t* centre, int nx, int ny, int ntheta, float dtheta,
+                    float max_range, int min_score, int rays, float* reach)
 {
-    if (need <= *cap) return BL_OK;
-    if (*p) { BL_HIP(hipFree(*p)); *p = nullptr; *cap = 0; }
-    BL_HIP(hipMalloc((void**)p, need * sizeof(T)));
-    *cap = need;
+    bl_ctx* ctx = sm->ctx;
+    const size_t want = (size_t)(((rays > 0 ? rays : 1) + 255) & ~255) * 2 * sizeof(float);
+    int rc = bl_grow((void**)&sm->d_rays, &sm->rays_bytes, want, false, ctx);
+    if (rc) return rc;
+    if ((rc = bl_grow(&sm->staging, &sm->staging_bytes, sizeof(smw_head) + sm->rays_bytes, true, ctx))) return rc;
+    sm->ray_cap = (int)(sm->rays_bytes / (2 * sizeof(float)));
+    const int rp = (rays + 63) & ~63;
+    if ((rc = bl_grow((void**)&sm->d_ends, &sm->ends_cap, (size_t)(2 * ntheta + 1) * (rp > 0 ? rp : 64) * sizeof(int2), false, ctx))) return rc;
+
+    smw_head* hd = (smw_head*)sm->staging;
+    float* h_ranges = (float*)(hd + 1);
+    memset(hd, 0, sizeof(smw_head));
+    sm_head* h = &hd->base;
+    h->cx = centre->x; h->cy = centre->y; h->ctheta = centre->theta; h->dtheta = dtheta;
+    h->utime = scan->utime;
+    h->nx = nx; h->ny = ny; h->ntheta = ntheta; h->rays = rays;
+    h->min_score = min_score;
+    h->bbox[0] = INT32_MAX; h->bbox[1] = INT32_MAX; h->bbox[2] = INT32_MIN; h->bbox[3] = INT32_MIN;
+    (void)sm_valid_rays(scan, max_range, h_ranges, h_ranges + sm->ray_cap, reach);
+    return BL_OK;
+}
+
+// head_bytes of the pinned header and the packed rays to the device, then the endpoints of every heading
+static int sm_upload_and_raster(bl_scanmatch* sm, size_t head_bytes, int nk, int rays, const bl_frame& f)
+{
+    bl_ctx* ctx = sm->ctx;
+    BL_HIP(hipMemcpyAsync(sm->d_head, sm->staging, head_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (rays > 0)
+        BL_HIP(hipMemcpyAsync(sm->d_rays, (char*)sm->staging + sizeof(smw_head), sm->rays_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const long long total = (long long)nk * ((rays + 63) & ~63);
+    if (total > 0)
+        hipLaunchKernelGGL(k_sm_raster, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, &sm->d_head->base, sm->d_rays,
+                           sm->d_rays + sm->ray_cap, f, sm->d_ends);
     return BL_OK;
 }
 
@@ -561,8 +492,7 @@ static int sm_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan
     BL_CHECK_ARG(params->ntheta >= 0 && params->ntheta <= SM_MAX_NTHETA);
     BL_CHECK_ARG(params->dtheta > 0.0f);
     BL_CHECK_ARG(scan->num_ranges >= 0 && (scan->num_ranges == 0 || (scan->ranges != nullptr && scan->thetas != nullptr)));
-    int rays = 0;
-    for (int i = 0; i < scan->num_ranges; ++i) rays += (scan->ranges[i] > SM_MIN_RANGE && scan->ranges[i] < params->max_range) ? 1 : 0;
+    const int rays = sm_valid_rays(scan, params->max_range, nullptr, nullptr, nullptr);
     BL_CHECK_ARG(rays <= SM_MAX_RAYS);
     const bool want_moments = prior != nullptr && prior->want_moments != 0;
     if (prior) {
@@ -574,22 +504,11 @@ static int sm_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan
     bl_ctx* ctx = sm->ctx;
     BL_HIP(hipSetDevice(ctx->device));
 
-    // ---- buffers
+    // ---- buffers; the header and the valid rays
     const int nk = 2 * params->ntheta + 1, cw = 2 * params->nx + 1, ch = 2 * params->ny + 1, ncand = cw * ch;
-    const int cap = rays > 0 ? rays : 1;
-    if (cap > sm->ray_cap) {
-        size_t c = 0;
-        BL_HIP(hipStreamSynchronize(ctx->stream));
-        if (sm->d_rays) { BL_HIP(hipFree(sm->d_rays)); sm->d_rays = nullptr; sm->ray_cap = 0; }
-        if (sm->staging) { BL_HIP(hipHostFree(sm->staging)); sm->staging = nullptr; }
-        c = (size_t)((cap + 255) & ~255);
-        BL_HIP(hipMalloc((void**)&sm->d_rays, 2 * c * sizeof(float)));
-        sm->staging_bytes = sizeof(sm_head) + 2 * c * sizeof(float);
-        BL_HIP(hipHostMalloc(&sm->staging, sm->staging_bytes, hipHostMallocDefault));
-        sm->ray_cap = (int)c;
-    }
-    const int rp = (rays + 63) & ~63;
-    int rc = sm_grow(&sm->d_ends, &sm->ends_cap, (size_t)nk * (rp > 0 ? rp : 64));
+    float rmax = 0;
+    int rc = sm_begin(sm, scan, centre, params->nx, params->ny, params->ntheta, params->dtheta, params->max_range, params->min_score, rays,
+                      &rmax);
     if (rc) return rc;
     // slices of a heading's candidates: enough workgroups to fill the device, none with less than a wave of candidates
     const int threads = ncand >= 4096 ? 1024 : 256;
@@ -598,8 +517,8 @@ static int sm_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan
     if (slices > max_slices) slices = max_slices;
     if (slices < 1) slices = 1;
     const int nblocks = slices * nk;
-    { size_t bc = (size_t)sm->best_cap; rc = sm_grow(&sm->d_best, &bc, (size_t)nblocks); sm->best_cap = (int)bc; if (rc) return rc; }
-    if (keep) { rc = sm_grow(&sm->d_volume, &sm->volume_cap, (size_t)nk * ncand); if (rc) return rc; }
+    if ((rc = bl_grow((void**)&sm->d_best, &sm->best_cap, (size_t)nblocks * sizeof(sm_block_best), false, ctx))) return rc;
+    if (keep && (rc = bl_grow((void**)&sm->d_volume, &sm->volume_cap, (size_t)nk * ncand * sizeof(int32_t), false, ctx))) return rc;
     // the moments pass: a wave per SM_MOM_BATCH rows of the volume, at most SM_MOM_MAX_GROUPS workgroups
     const int mom_rows = nk * ch;
     int mom_groups = (mom_rows + SM_MOM_BATCH * (SM_MOM_THREADS / 64) - 1) / (SM_MOM_BATCH * (SM_MOM_THREADS / 64));
@@ -609,25 +528,6 @@ static int sm_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan
         BL_HIP(hipMalloc((void**)&sm->d_partial, SM_MOM_MAX_GROUPS * sizeof(sm_partial)));
         BL_HIP(hipHostMalloc((void**)&sm->h_mom, sizeof(bl_scan_match_moments_t), hipHostMallocDefault));
     }
-
-    // ---- header and the valid rays, one copy
-    sm_head* h = (sm_head*)sm->staging;
-    float* h_ranges = (float*)((char*)sm->staging + sizeof(sm_head));
-    float* h_thetas = h_ranges + sm->ray_cap;
-    memset(h, 0, sizeof(sm_head));
-    h->cx = centre->x; h->cy = centre->y; h->ctheta = centre->theta; h->dtheta = params->dtheta;
-    h->utime = scan->utime;
-    h->nx = params->nx; h->ny = params->ny; h->ntheta = params->ntheta; h->rays = rays;
-    h->min_score = params->min_score;
-    h->bbox[0] = INT32_MAX; h->bbox[1] = INT32_MAX; h->bbox[2] = INT32_MIN; h->bbox[3] = INT32_MIN;
-    float rmax = 0;
-    for (int i = 0, j = 0; i < scan->num_ranges; ++i) {
-        const float r = scan->ranges[i];
-        if (r > SM_MIN_RANGE && r < params->max_range) { h_ranges[j] = r; h_thetas[j] = scan->thetas[i]; ++j; if (r > rmax) rmax = r; }
-    }
-    BL_HIP(hipMemcpyAsync(sm->d_head, h, sizeof(sm_head), hipMemcpyHostToDevice, ctx->stream));
-    if (rays > 0)
-        BL_HIP(hipMemcpyAsync(sm->d_rays, h_ranges, 2 * (size_t)sm->ray_cap * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
 
     // ---- LDS for the window: an upper bound of what the device will find (every endpoint lies within the longest range, a cell of
     // slack for each rounding, of the centre; the window is that box widened by the shifts, clipped to the grid).  The device
@@ -642,19 +542,18 @@ static int sm_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan
     if (win_bytes <= (size_t)SM_LDS_MAX) lds_window = (int)win_bytes;
     const size_t lds_bytes = (size_t)(lds_window > 16 ? lds_window : 16);   // never empty: a masked-out lookup reads byte 0
 
-    const int total = nk * rp;
-    if (total > 0)
-        hipLaunchKernelGGL(k_sm_raster, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, sm->d_head, sm->d_rays,
-                           sm->d_rays + sm->ray_cap, f, sm->d_ends);
+    sm_head* d_head = &sm->d_head->base;
+    sm_head* h = &((smw_head*)sm->staging)->base;
+    if ((rc = sm_upload_and_raster(sm, sizeof(sm_head), nk, rays, f))) return rc;
     if (!prior) {
-        hipLaunchKernelGGL(k_sm_score, dim3(slices, nk), dim3(threads), lds_bytes, ctx->stream, sm->d_head, map->cells, f, sm->d_ends,
+        hipLaunchKernelGGL(k_sm_score, dim3(slices, nk), dim3(threads), lds_bytes, ctx->stream, d_head, map->cells, f, sm->d_ends,
                            lds_window, sm->d_best, params->keep_volume ? sm->d_volume : (int32_t*)nullptr);
-        hipLaunchKernelGGL(k_sm_final, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_best, nblocks, f);
+        hipLaunchKernelGGL(k_sm_final, dim3(1), dim3(256), 0, ctx->stream, d_head, sm->d_best, nblocks, f);
     } else {
         sm_prior_k pr; pr.a_xx = prior->a_xx; pr.a_xy = prior->a_xy; pr.a_yy = prior->a_yy; pr.a_tt = prior->a_tt;
-        hipLaunchKernelGGL(k_sm_score_prior, dim3(slices, nk), dim3(threads), lds_bytes, ctx->stream, sm->d_head, map->cells, f,
+        hipLaunchKernelGGL(k_sm_score_prior, dim3(slices, nk), dim3(threads), lds_bytes, ctx->stream, d_head, map->cells, f,
                            sm->d_ends, lds_window, sm->d_best, keep ? sm->d_volume : (int32_t*)nullptr, pr);
-        hipLaunchKernelGGL(k_sm_final_prior, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_best, nblocks, f, pr, sm->d_mom);
+        hipLaunchKernelGGL(k_sm_final_prior, dim3(1), dim3(256), 0, ctx->stream, d_head, sm->d_best, nblocks, f, pr, sm->d_mom);
         if (want_moments) {
             // floor(64 d / half_life) as a multiplication (sm_weight): shift = 30 + L with 2^L >= half_life, magic = ceil(2^shift / half_life)
             int L = 0;
@@ -662,14 +561,14 @@ static int sm_match(bl_scanmatch* sm, const bl_grid* map, const bl_lidar_t* scan
             const int shift = 30 + L;
             const unsigned long long hl = (unsigned long long)prior->half_life;
             const uint32_t magic = (uint32_t)(((1ull << shift) + hl - 1) / hl);
-            hipLaunchKernelGGL(k_sm_moments, dim3(mom_groups), dim3(SM_MOM_THREADS), 0, ctx->stream, sm->d_head, sm->d_volume, sm->d_mom,
+            hipLaunchKernelGGL(k_sm_moments, dim3(mom_groups), dim3(SM_MOM_THREADS), 0, ctx->stream, d_head, sm->d_volume, sm->d_mom,
                                magic, shift, sm->d_partial);
-            hipLaunchKernelGGL(k_sm_moments_final, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_volume, sm->d_partial,
+            hipLaunchKernelGGL(k_sm_moments_final, dim3(1), dim3(256), 0, ctx->stream, d_head, sm->d_volume, sm->d_partial,
                                mom_groups, sm->d_mom);
         }
     }
     BL_HIP(hipGetLastError());
-    BL_HIP(hipMemcpyAsync(h, sm->d_head, sizeof(sm_head), hipMemcpyDeviceToHost, ctx->stream));
+    BL_HIP(hipMemcpyAsync(h, d_head, sizeof(sm_head), hipMemcpyDeviceToHost, ctx->stream));
     if (want_moments)
         BL_HIP(hipMemcpyAsync(sm->h_mom, sm->d_mom, sizeof(bl_scan_match_moments_t), hipMemcpyDeviceToHost, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));
@@ -768,13 +667,6 @@ __device__ __forceinline__ smw_key smw_wave_max(smw_key v)
     return v;
 }
 
-struct smw_head {
-    sm_head base;                      // what k_sm_raster reads and writes; base.result is the result
-    int32_t hlog, nbx, nby, exhaustive;
-    long long candidates;
-    unsigned int kept; int32_t pad;
-    unsigned long long scored;
-};
 struct smw_record { smw_key key; unsigned long long ties, scored; };
 
 __global__ __launch_bounds__(256) void k_smw_pool_rows(const int8_t* __restrict__ cells, int W, int H, int B, int mw,
@@ -805,31 +697,6 @@ __global__ __launch_bounds__(256) void k_smw_pool_cols(const unsigned char* __re
     pool[idx] = (unsigned char)m;
 }
 
-// sum over a heading's endpoints of bytes[(ey + oy) * pitch + ex + ox] where that lies inside w x h; all 64 lanes of the wave must
-// be here (the endpoints sit one per lane and are broadcast).  SIGNED: the bytes are int8 log-odds and only the positive count.
-template <bool SIGNED>
-__device__ __forceinline__ int smw_sum(const int2* __restrict__ k_ends, int rp, int lane, unsigned ox, unsigned oy,
-                                       const unsigned char* __restrict__ bytes, unsigned w, unsigned h, unsigned pitch)
-{
-    int acc = 0;
-    int2 mine = rp > 0 ? k_ends[lane] : make_int2(SM_NONE, SM_NONE);
-    for (int r0 = 0; r0 < rp; r0 += 64) {
-        int2 next = mine;
-        if (r0 + 64 < rp) next = k_ends[r0 + 64 + lane];
-#pragma unroll
-        for (int i = 0; i < 64; ++i) {
-            const int ex = __builtin_amdgcn_readlane(mine.x, i), ey = __builtin_amdgcn_readlane(mine.y, i);
-            const unsigned ux = (unsigned)ex + ox, uy = (unsigned)ey + oy;
-            const bool in = ux < w && uy < h;                               // never true for a sentinel (see SM_NONE; shifts <= 4096 + 63)
-            const unsigned char b = bytes[in ? (size_t)uy * pitch + ux : (size_t)0];
-            const int v = SIGNED ? (int)(signed char)b : (int)b;
-            acc += (in && v > 0) ? v : 0;
-        }
-        mine = next;
-    }
-    return acc;
-}
-
 __global__ __launch_bounds__(256) void k_smw_bounds(const smw_head* __restrict__ head, const unsigned char* __restrict__ pool, int mw,
                                                     int mh, const int2* __restrict__ ends, int32_t* __restrict__ bounds)
 {
@@ -842,7 +709,7 @@ __global__ __launch_bounds__(256) void k_smw_bounds(const smw_head* __restrict__
     const int rem = (int)(gw - (long long)k * nby * nchunk);
     const int bj = rem / nchunk, bi = (rem - bj * nchunk) * 64 + lane;
     const unsigned ox = (unsigned)(-head->base.nx + (bi << h) + B - 1), oy = (unsigned)(-head->base.ny + (bj << h) + B - 1);
-    const int acc = smw_sum<false>(ends + (size_t)k * rp, rp, lane, ox, oy, pool, (unsigned)mw, (unsigned)mh, (unsigned)mw);
+    const int acc = sm_lookup_sum<false>(ends + (size_t)k * rp, rp, lane, ox, oy, pool, (unsigned)mw, (unsigned)mh, (unsigned)mw);
     if (bi < nbx) bounds[((size_t)k * nby + bj) * nbx + bi] = acc;
 }
 
@@ -874,7 +741,7 @@ __global__ __launch_bounds__(256) void k_smw_seed(smw_head* __restrict__ head, c
     const bool any = bound > 0;                                              // a heading whose bounds are all 0 scores 0 everywhere: nothing to learn
     for (int cb = tid & ~63; any && cb < B * B; cb += 256) {                 // wave-uniform trip count
         const int c = cb + lane, di = i0 + (c & (B - 1)), dj = j0 + (c >> h);
-        const int acc = smw_sum<true>(k_ends, rp, lane, (unsigned)di, (unsigned)dj, (const unsigned char*)cells, (unsigned)f.width,
+        const int acc = sm_lookup_sum<true>(k_ends, rp, lane, (unsigned)di, (unsigned)dj, (const unsigned char*)cells, (unsigned)f.width,
                                       (unsigned)f.height, (unsigned)f.width);
         if (c < B * B && di <= nx && dj <= ny) top = max(top, acc);
     }
@@ -951,19 +818,8 @@ __global__ __launch_bounds__(SMW_THREADS) void k_smw_exact(smw_head* __restrict_
         if (tid == 0) { smw_record r; r.key.hi = 0; r.key.lo = 0; r.ties = 0; r.scored = 0; rec[blockIdx.x] = r; }
         return;
     }
-    if (STAGED) {
-        if ((f.width & 3) == 0) {
-            const int qw = f.width >> 2;
-            for (int i = tid; i < qw * f.height; i += SMW_THREADS)
-                ((uint32_t*)s_map)[i] = sm_positive_bytes(((const uint32_t*)cells)[i]);      // pitch == width here
-        } else {
-            for (int i = tid; i < pitch * f.height; i += SMW_THREADS) {
-                const int row = i / pitch, col = i - row * pitch;
-                int v = 0;
-                if (col < f.width) v = cells[(size_t)row * f.width + col];
-                s_map[i] = (unsigned char)(v > 0 ? v : 0);
-            }
-        }
+    if (STAGED) {                                                            // the window is the whole grid: its pitch is `pitch`
+        sm_stage_window(cells, f.width, sm_clip_window(0, 0, f.width - 1, f.height - 1, true, f), s_map, tid, SMW_THREADS);
         __syncthreads();
     }
     smw_key key; key.hi = 0; key.lo = 0;
@@ -977,9 +833,9 @@ __global__ __launch_bounds__(SMW_THREADS) void k_smw_exact(smw_head* __restrict_
         const int bj = rem / nbx, bi = rem - bj * nbx, dk = k - nt;
         const int c = chunk * 64 + lane;
         const int di = -nx + (bi << h) + (c & (B - 1)), dj = -ny + (bj << h) + (c >> h);
-        const int acc = STAGED ? smw_sum<false>(ends + (size_t)k * rp, rp, lane, (unsigned)di, (unsigned)dj, s_map, (unsigned)f.width,
+        const int acc = STAGED ? sm_lookup_sum<false>(ends + (size_t)k * rp, rp, lane, (unsigned)di, (unsigned)dj, s_map, (unsigned)f.width,
                                                 (unsigned)f.height, (unsigned)pitch)
-                               : smw_sum<true>(ends + (size_t)k * rp, rp, lane, (unsigned)di, (unsigned)dj, (const unsigned char*)cells,
+                               : sm_lookup_sum<true>(ends + (size_t)k * rp, rp, lane, (unsigned)di, (unsigned)dj, (const unsigned char*)cells,
                                                (unsigned)f.width, (unsigned)f.height, (unsigned)f.width);
         if (c >= B * B || di > nx || dj > ny) continue;                      // an edge block's shifts outside the window
         ++scored;
@@ -1037,22 +893,7 @@ __global__ __launch_bounds__(256) void k_smw_final(smw_head* __restrict__ head, 
         int dk = (key.lo & 0x80000000ull) ? -adk : adk;
         if (flat) { score = 0; di = 0; dj = 0; dk = 0; ties = (unsigned long long)head->candidates; }
         head->scored += s_scored[0] + s_scored[1] + s_scored[2] + s_scored[3];
-        bl_scan_match_result_t r;
-        r.di = di; r.dj = dj; r.dk = dk;
-        r.score = score;
-        r.score_centre = head->base.score_centre;
-        r.ties = ties > (unsigned long long)INT32_MAX ? INT32_MAX : (int32_t)ties;
-        r.rays_used = head->base.rays;
-        r.accepted = score >= head->base.min_score ? 1 : 0;
-        r.pose.utime = head->base.utime;
-        if (r.accepted) {
-            r.pose.x = (float)((double)head->base.cx + (double)di * (double)f.mpc);
-            r.pose.y = (float)((double)head->base.cy + (double)dj * (double)f.mpc);
-            r.pose.theta = bl_wrap_to_pi(head->base.ctheta + (float)dk * head->base.dtheta);
-        } else {
-            r.pose.x = head->base.cx; r.pose.y = head->base.cy; r.pose.theta = head->base.ctheta;
-        }
-        head->base.result = r;
+        sm_write_result(&head->base, f, di, dj, dk, score, ties > (unsigned long long)INT32_MAX ? INT32_MAX : (int32_t)ties);
     }
 }
 
@@ -1073,8 +914,7 @@ extern "C" int bl_scanmatch_match_wide(bl_scanmatch* sm, const bl_grid* map, con
     BL_CHECK_ARG(params->dtheta > 0.0f);
     BL_CHECK_ARG(params->block_log2 >= 0 && params->block_log2 <= 6);
     BL_CHECK_ARG(scan->num_ranges >= 0 && (scan->num_ranges == 0 || (scan->ranges != nullptr && scan->thetas != nullptr)));
-    int rays = 0;
-    for (int i = 0; i < scan->num_ranges; ++i) rays += (scan->ranges[i] > SM_MIN_RANGE && scan->ranges[i] < params->max_range) ? 1 : 0;
+    const int rays = sm_valid_rays(scan, params->max_range, nullptr, nullptr, nullptr);
     BL_CHECK_ARG(rays <= SM_MAX_RAYS);
     const int nk = 2 * params->ntheta + 1;
     const long long candidates = (long long)nk * (2 * params->nx + 1) * (2 * params->ny + 1);
@@ -1098,79 +938,47 @@ extern "C" int bl_scanmatch_match_wide(bl_scanmatch* sm, const bl_grid* map, con
     const bool staged = (long long)pitch * f.height <= (long long)SM_LDS_MAX;
     if (!sm->wide_ready) {
         BL_HIP(hipFuncSetAttribute((const void*)k_smw_exact<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SM_LDS_MAX));
-        BL_HIP(hipMalloc((void**)&sm->d_whead, sizeof(smw_head)));
         BL_HIP(hipMalloc((void**)&sm->d_rec, SMW_GROUPS * sizeof(smw_record)));
         sm->wide_ready = true;
     }
-    const int cap = rays > 0 ? rays : 1;
-    if (cap > sm->wray_cap) {
-        BL_HIP(hipStreamSynchronize(ctx->stream));
-        if (sm->d_wrays) { BL_HIP(hipFree(sm->d_wrays)); sm->d_wrays = nullptr; sm->wray_cap = 0; }
-        if (sm->wstaging) { BL_HIP(hipHostFree(sm->wstaging)); sm->wstaging = nullptr; }
-        const size_t c = (size_t)((cap + 255) & ~255);
-        BL_HIP(hipMalloc((void**)&sm->d_wrays, 2 * c * sizeof(float)));
-        BL_HIP(hipHostMalloc(&sm->wstaging, sizeof(smw_head) + 2 * c * sizeof(float), hipHostMallocDefault));
-        sm->wray_cap = (int)c;
-    }
-    const int rp = (rays + 63) & ~63;
-    int rc = sm_grow(&sm->d_ends, &sm->ends_cap, (size_t)nk * (rp > 0 ? rp : 64));
+    int rc = sm_begin(sm, scan, centre, params->nx, params->ny, params->ntheta, params->dtheta, params->max_range, params->min_score, rays,
+                      nullptr);
     if (rc) return rc;
     if (!exhaustive) {
-        if ((rc = sm_grow(&sm->d_pool, &sm->pool_cap, (size_t)mw * mh))) return rc;
-        if ((rc = sm_grow(&sm->d_pool_rows, &sm->pool_rows_cap, (size_t)mw * f.height))) return rc;
-        if ((rc = sm_grow(&sm->d_bounds, &sm->bounds_cap, (size_t)nblocks))) return rc;
-        if ((rc = sm_grow(&sm->d_list, &sm->list_cap, (size_t)nblocks))) return rc;
-        if ((rc = sm_grow(&sm->d_seeds, &sm->seeds_cap, (size_t)nk))) return rc;
+        if ((rc = bl_grow((void**)&sm->d_pool, &sm->pool_cap, (size_t)mw * mh, false, ctx))) return rc;
+        if ((rc = bl_grow((void**)&sm->d_pool_rows, &sm->pool_rows_cap, (size_t)mw * f.height, false, ctx))) return rc;
+        if ((rc = bl_grow((void**)&sm->d_bounds, &sm->bounds_cap, (size_t)nblocks * sizeof(int32_t), false, ctx))) return rc;
+        if ((rc = bl_grow((void**)&sm->d_list, &sm->list_cap, (size_t)nblocks * sizeof(uint32_t), false, ctx))) return rc;
+        if ((rc = bl_grow((void**)&sm->d_seeds, &sm->seeds_cap, (size_t)nk * sizeof(int2), false, ctx))) return rc;
     }
-
-    // ---- header and the valid rays
-    smw_head* hd = (smw_head*)sm->wstaging;
-    float* h_ranges = (float*)((char*)sm->wstaging + sizeof(smw_head));
-    float* h_thetas = h_ranges + sm->wray_cap;
-    memset(hd, 0, sizeof(smw_head));
-    hd->base.cx = centre->x; hd->base.cy = centre->y; hd->base.ctheta = centre->theta; hd->base.dtheta = params->dtheta;
-    hd->base.utime = scan->utime;
-    hd->base.nx = params->nx; hd->base.ny = params->ny; hd->base.ntheta = params->ntheta; hd->base.rays = rays;
-    hd->base.min_score = params->min_score;
-    hd->base.bbox[0] = INT32_MAX; hd->base.bbox[1] = INT32_MAX; hd->base.bbox[2] = INT32_MIN; hd->base.bbox[3] = INT32_MIN;
+    smw_head* hd = (smw_head*)sm->staging;
     hd->hlog = h; hd->nbx = nbx; hd->nby = nby; hd->exhaustive = exhaustive ? 1 : 0;
     hd->candidates = candidates;
-    for (int i = 0, j = 0; i < scan->num_ranges; ++i) {
-        const float r = scan->ranges[i];
-        if (r > SM_MIN_RANGE && r < params->max_range) { h_ranges[j] = r; h_thetas[j] = scan->thetas[i]; ++j; }
-    }
-    BL_HIP(hipMemcpyAsync(sm->d_whead, hd, sizeof(smw_head), hipMemcpyHostToDevice, ctx->stream));
-    if (rays > 0)
-        BL_HIP(hipMemcpyAsync(sm->d_wrays, h_ranges, 2 * (size_t)sm->wray_cap * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-
-    const long long total = (long long)nk * rp;
-    if (total > 0)
-        hipLaunchKernelGGL(k_sm_raster, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, &sm->d_whead->base, sm->d_wrays,
-                           sm->d_wrays + sm->wray_cap, f, sm->d_ends);
+    if ((rc = sm_upload_and_raster(sm, sizeof(smw_head), nk, rays, f))) return rc;
     if (!exhaustive) {
         hipLaunchKernelGGL(k_smw_pool_rows, dim3((unsigned)(((long long)mw * f.height + 255) / 256)), dim3(256), 0, ctx->stream,
                            map->cells, f.width, f.height, B, mw, sm->d_pool_rows);
         hipLaunchKernelGGL(k_smw_pool_cols, dim3((unsigned)(((long long)mw * mh + 255) / 256)), dim3(256), 0, ctx->stream,
                            sm->d_pool_rows, f.height, B, mw, mh, sm->d_pool);
         const long long waves = (long long)nk * nby * ((nbx + 63) >> 6);
-        hipLaunchKernelGGL(k_smw_bounds, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, ctx->stream, sm->d_whead, sm->d_pool, mw, mh,
+        hipLaunchKernelGGL(k_smw_bounds, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, ctx->stream, sm->d_head, sm->d_pool, mw, mh,
                            sm->d_ends, sm->d_bounds);
-        hipLaunchKernelGGL(k_smw_seed, dim3(nk), dim3(256), 0, ctx->stream, sm->d_whead, map->cells, f, sm->d_ends, sm->d_bounds,
+        hipLaunchKernelGGL(k_smw_seed, dim3(nk), dim3(256), 0, ctx->stream, sm->d_head, map->cells, f, sm->d_ends, sm->d_bounds,
                            sm->d_seeds);
-        hipLaunchKernelGGL(k_smw_compact, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, ctx->stream, sm->d_whead, sm->d_seeds,
+        hipLaunchKernelGGL(k_smw_compact, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, ctx->stream, sm->d_head, sm->d_seeds,
                            sm->d_bounds, nblocks, sm->d_list);
     }
     const uint32_t* list = exhaustive ? (const uint32_t*)nullptr : sm->d_list;
     if (staged)
-        hipLaunchKernelGGL(k_smw_exact<true>, dim3(SMW_GROUPS), dim3(SMW_THREADS), (size_t)pitch * f.height, ctx->stream, sm->d_whead,
+        hipLaunchKernelGGL(k_smw_exact<true>, dim3(SMW_GROUPS), dim3(SMW_THREADS), (size_t)pitch * f.height, ctx->stream, sm->d_head,
                            map->cells, f, sm->d_ends, list, nblocks, pitch, sm->d_rec);
     else
-        hipLaunchKernelGGL(k_smw_exact<false>, dim3(SMW_GROUPS), dim3(SMW_THREADS), 0, ctx->stream, sm->d_whead, map->cells, f,
+        hipLaunchKernelGGL(k_smw_exact<false>, dim3(SMW_GROUPS), dim3(SMW_THREADS), 0, ctx->stream, sm->d_head, map->cells, f,
                            sm->d_ends, list, nblocks, pitch, sm->d_rec);
-    hipLaunchKernelGGL(k_smw_final, dim3(1), dim3(256), 0, ctx->stream, sm->d_whead, sm->d_rec, SMW_GROUPS,
+    hipLaunchKernelGGL(k_smw_final, dim3(1), dim3(256), 0, ctx->stream, sm->d_head, sm->d_rec, SMW_GROUPS,
                        exhaustive ? (const int2*)nullptr : sm->d_seeds, f);
     BL_HIP(hipGetLastError());
-    BL_HIP(hipMemcpyAsync(hd, sm->d_whead, sizeof(smw_head), hipMemcpyDeviceToHost, ctx->stream));
+    BL_HIP(hipMemcpyAsync(hd, sm->d_head, sizeof(smw_head), hipMemcpyDeviceToHost, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));
     *result = hd->base.result;
     sm->wide_stats.candidates = candidates;

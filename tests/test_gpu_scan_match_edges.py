@@ -10,6 +10,8 @@ import pytest
 
 import botlab_amd as bl
 import scan_match_cases as smc
+import scan_match_model as sm
+import scan_match_prior_model as smp
 import scan_match_wide_model as smw
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +101,63 @@ def test_case_on_the_device(gpu_ctx, matcher, name):
         if "wide_path" in case.expect:
             assert st.path == case.expect["wide_path"]
     grid.close()
+
+
+def test_one_handle_across_the_three_matches(gpu_ctx):
+    """The plain, the prior and the wide match share a handle's header and ray buffers.  One handle, on a 20 x 19 grid (rows copied
+    as dwords) and again on a 21 x 19 one (as bytes): 1 valid ray plain; 300 wide (the buffers grow); 65 with a prior and the
+    moments; 0 plain; 64 wide exhaustive; 300 plain with the volume kept.  Every result, the kept volume and the moments equal the
+    model's, and every result is the one a fresh handle gives.  Each scan also has a ray at the 0.15 limit and one at max_range."""
+    rng = np.random.default_rng(20260227)
+    max_range, prior, half_life, dtheta = 0.55, (300, -40, 200, 90), 37, np.float32(np.radians(1.0))
+    centre = (0.52, 0.47, 0.3)
+    c = bl.make_pose(*centre, utime=7)
+
+    def scan_of(n):
+        r = np.concatenate([rng.uniform(0.16, 0.54, n), [0.15, max_range]]).astype(np.float32)
+        t = rng.uniform(-np.pi, np.pi, n + 2).astype(np.float32)
+        order = rng.permutation(n + 2)
+        return r[order], t[order]
+
+    # call, valid rays, window, what the call is given beyond the window
+    calls = [("plain", 1, (3, 3, 2), {}), ("wide", 300, (3, 2, 2), {}), ("prior", 65, (2, 3, 2), dict(prior=prior, half_life=half_life)),
+             ("plain", 0, (3, 3, 1), {}), ("wide", 64, (3, 3, 2), dict(exhaustive=True)), ("plain", 300, (3, 3, 2), dict(keep_volume=True))]
+
+    def run(m, grid, kind, scan, window, extra):
+        kw = dict(nx=window[0], ny=window[1], ntheta=window[2], dtheta=dtheta, max_range=max_range, min_score=1, **extra)
+        if kind == "plain":
+            return m.match(scan, c, grid, **kw), None
+        if kind == "wide":
+            return m.match_wide(scan, c, grid, **kw), None
+        return m.match_prior(scan, c, grid, **kw)
+
+    one = bl.ScanMatcher(ctx=gpu_ctx)
+    for width in (20, 21):
+        cells = rng.integers(-128, 128, (19, width)).astype(np.int8)
+        grid = bl.OccupancyGrid.from_cells(cells, (0.0, 0.0), smc.MPC, cellsPerMeter=smc.CPM, ctx=gpu_ctx)
+        for kind, n, window, extra in calls:
+            ranges, thetas = scan_of(n)
+            scan = bl.LidarScan(ranges, thetas, np.zeros(len(ranges), np.int64), utime=smc.UTIME)
+            model = (ranges, thetas, centre, *window, dtheta, max_range)
+            if kind == "prior":
+                ref = smp.match(cells, (0.0, 0.0), smc.MPC, smc.CPM, *model, prior=prior, half_life=half_life, min_score=1, utime=smc.UTIME)
+            else:
+                ref = sm.match(cells, (0.0, 0.0), smc.MPC, smc.CPM, *model, min_score=1, utime=smc.UTIME)
+            assert ref["rays_used"] == n
+            res, mom = run(one, grid, kind, scan, window, extra)
+            assert_same(res, ref, (width, kind, n))
+            if kind == "prior":
+                assert (mom.sums(), mom.best_obj, mom.pen_best, mom.fractions()) == (ref["sums"], ref["best_obj"], ref["pen_best"], ref["fractions"])
+            if kind == "prior" or extra.get("keep_volume"):
+                assert np.array_equal(one.volume(), ref["volume"]), (width, kind, n)
+            fresh = bl.ScanMatcher(ctx=gpu_ctx)
+            again, mom2 = run(fresh, grid, kind, scan, window, extra)
+            assert bytes(again) == bytes(res), (width, kind, n)
+            if kind == "prior":
+                assert (mom2.sums(), mom2.best_obj, mom2.pen_best, mom2.fractions()) == (mom.sums(), mom.best_obj, mom.pen_best, mom.fractions())
+            fresh.close()
+        grid.close()
+    one.close()
 
 
 def test_over_budget_block_sizes_are_refused(gpu_ctx, matcher):

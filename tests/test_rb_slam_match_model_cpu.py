@@ -16,6 +16,7 @@ from botlab_amd import synth
 from test_rb_slam_model_cpu import CPM, HIT, MAX_LASER, MISS, RAGGED_ORIGIN, RAGGED_SHAPE, make_run
 
 DTH = math.radians(0.5)
+HEADING_PI = math.pi - 0.004            # "heading_pi": the run's first heading, less than one step of DTH below pi
 CROP = 64
 BIG = 10 ** 9
 
@@ -51,10 +52,14 @@ def _case(maps, name):
     setScanMatching keywords or None, seed)."""
     c = dict(num=1, den=1, mpc=None, cpm=CPM, seed=17, spread=5)
     on = lambda **kw: dict(dict(nx=2, ny=2, ntheta=3, dtheta=DTH, max_range=8.0, min_score=0), **kw)
-    if name in ("main", "min_score", "p1", "p1000", "pause"):
-        P = {"main": 16, "min_score": 4, "p1": 1, "p1000": 1000, "pause": 4}[name]
-        steps = {"main": 6, "min_score": 3, "p1": 4, "p1000": 2, "pause": 5}[name]
+    if name in ("main", "min_score", "p1", "p1000", "pause", "heading_pi"):
+        P = {"main": 16, "min_score": 4, "p1": 1, "p1000": 1000, "pause": 4, "heading_pi": 16}[name]
+        steps = {"main": 6, "min_score": 3, "p1": 4, "p1000": 2, "pause": 5, "heading_pi": 3}[name]
         m, odoms, scans = _scans(maps, steps, rays=64 if name == "p1000" else synth.RAYS, pause_at=3 if name == "pause" else None)
+        if name == "heading_pi":
+            # the odometry's heading turned to just below pi (the maps then fit no scan: only the arithmetic is under test), so that a
+            # particle moved by dk > 0 crosses pi and its heading is wrapped
+            odoms = [(o[0], o[1], o[2] + HEADING_PI, o[3]) for o in odoms]
         cx, cy = _cell_of(m, odoms[0])
         x0, y0 = cx - CROP // 2, cy - CROP // 2
         rng = np.random.default_rng(3)
@@ -62,8 +67,9 @@ def _case(maps, name):
         init = np.stack([_crop(m, x0 + int(sh[p, 0]), y0 + int(sh[p, 1]), CROP, CROP) for p in range(P)])
         kw = on(max_range=2.0) if name == "main" else on(min_score=BIG) if name == "min_score" else on(nx=1, ny=1, ntheta=1) if name == "p1000" else on()
         c.update(P=P, shape=(CROP, CROP), origin=_origin_at(m, x0, y0), init_maps=init, match=[kw] * len(odoms))
-    elif name in ("zero_window", "off_on_off", "uniform", "all_zero", "rays720", "no_valid_rays", "all_beyond"):
-        steps = {"zero_window": 4, "off_on_off": 6, "uniform": 1, "all_zero": 2, "rays720": 2, "no_valid_rays": 2, "all_beyond": 2}[name]
+    elif name in ("zero_window", "off_on_off", "uniform", "uniform_81", "all_zero", "rays720", "no_valid_rays", "all_beyond"):
+        steps = {"zero_window": 4, "off_on_off": 6, "uniform": 1, "uniform_81": 1, "all_zero": 2, "rays720": 2, "no_valid_rays": 2,
+                 "all_beyond": 2}[name]
         m, odoms, scans = _scans(maps, steps, rays=720 if name == "rays720" else synth.RAYS)
         P = 4
         init = np.stack([m["cells"]] * P)
@@ -73,6 +79,13 @@ def _case(maps, name):
         if name == "uniform":
             init = np.full_like(init, 5)
             kw = on(ntheta=2)
+        if name == "uniform_81":
+            # 81 candidates a heading: the ties are counted in two waves of the kernel's workgroup; and a ray at the lower limit itself,
+            # which does not count (on this map every ray that counts adds 5 to every score)
+            init = np.full_like(init, 5)
+            kw = on(nx=4, ny=4, ntheta=1)
+            for s in scans:
+                s.ranges[0] = smm.MIN_RANGE
         if name == "all_zero":
             init = None
         if name == "no_valid_rays":
@@ -109,7 +122,7 @@ def _case(maps, name):
 
 
 CASES = ["main", "zero_window", "off_on_off", "direct", "ragged", "uniform", "min_score", "rays720", "no_valid_rays", "all_beyond", "pause",
-         "p1", "p1000"]
+         "p1", "p1000", "uniform_81", "heading_pi"]
 _records = {}
 
 
@@ -191,6 +204,16 @@ def test_inputs_reach_their_conditions(oracle, maps, name):
     if name == "uniform":                               # every candidate ties and the centre wins
         mt = snaps[1]["match"]
         assert np.all(mt["ties"] == 5 * 5 * 5) and not mt["di"].any() and not mt["dj"].any() and not mt["dk"].any() and np.all(mt["score"] > 0)
+    if name == "uniform_81":                            # 243 ties, 64 of a heading's 81 candidates in the workgroup's first wave
+        mt, sc = snaps[1]["match"], c["scans"][1]
+        counted = int(np.count_nonzero((sc.ranges > smm.MIN_RANGE) & (sc.ranges < np.float32(8.0))))
+        assert sc.ranges[0] == smm.MIN_RANGE and counted == int(np.count_nonzero(sc.ranges < np.float32(8.0))) - 1
+        assert np.all(mt["ties"] == 9 * 9 * 3) and np.all(mt["score"] == 5 * counted) and not (mt["di"] | mt["dj"] | mt["dk"]).any()
+    if name == "heading_pi":                            # a particle turned by dk > 0 whose heading came out below zero: wrapped
+        wrapped = sum(int(np.count_nonzero((s["match"]["dk"] > 0) & (s["match"]["accepted"] != 0) & (s["parts"]["theta"] < -3.0)))
+                      for s in snaps if s["matched"])
+        print("heading_pi: wrapped", wrapped)
+        assert wrapped > 0
     if name == "min_score":
         assert all(not s["match"]["accepted"].any() for s in snaps if s["matched"])
     if name in ("no_valid_rays", "all_beyond"):
