@@ -278,6 +278,21 @@ class BeamParams(C.Structure):
 assert C.sizeof(BeamParams) == 56 and BeamParams.span.offset == 48
 
 
+class ScanLogStats(C.Structure):
+    """bl_scanlog_stats_t: the launch shape and the device time of the last map rebuild (64 bytes)."""
+    _fields_ = [("tiles", C.c_int64), ("chunks", C.c_int64), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("chunk_scans", C.c_int32),
+                ("tile_cells", C.c_int32), ("scans", C.c_int32), ("pad", C.c_int32), ("ms_total", C.c_float), ("ms_geometry", C.c_float),
+                ("ms_fold", C.c_float), ("ms_apply", C.c_float)]
+
+    def __repr__(self):
+        return (f"ScanLogStats(tiles={self.tiles}, chunks={self.chunks}, pairs={self.pairs}, scratch_bytes={self.scratch_bytes}, "
+                f"chunk_scans={self.chunk_scans}, tile_cells={self.tile_cells}, scans={self.scans}, ms_total={self.ms_total:.4f}, "
+                f"ms_geometry={self.ms_geometry:.4f}, ms_fold={self.ms_fold:.4f}, ms_apply={self.ms_apply:.4f})")
+
+
+assert C.sizeof(ScanLogStats) == 64
+
+
 class ObsTracksParams(C.Structure):
     """bl_obstracks_params_t: blob area limits, the gate, the two filter gains, confirmation, coasting and the speed of "moving" (32 bytes)."""
     _fields_ = [("min_cells", C.c_int32), ("max_cells", C.c_int32), ("gate_cells", C.c_int32), ("alpha", C.c_int32), ("beta", C.c_int32),
@@ -547,6 +562,16 @@ SIGNATURES = {
     "bl_beam_debug_set": (C.c_int, [_vp, C.c_int, C.c_int]),
     "bl_beam_debug_path": (C.c_int, [_vp]),
     "bl_beam_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_scanlog_create": (C.c_int, [_vp, C.c_int, C.c_int, _P(_vp)]),
+    "bl_scanlog_destroy": (None, [_vp]),
+    "bl_scanlog_append": (C.c_int, [_vp, _P(Lidar), _P(Pose)]),
+    "bl_scanlog_append_dev_pose": (C.c_int, [_vp, _P(Lidar), _vp, C.c_int64]),
+    "bl_scanlog_size": (C.c_int, [_vp]),
+    "bl_scanlog_get_poses": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "bl_scanlog_set_poses": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "bl_scanlog_get_scan": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _P(C.c_int)]),
+    "bl_scanlog_rebuild": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _P(Pose), C.c_float, C.c_int8, C.c_int8, _vp, _vp]),
+    "bl_scanlog_last_stats": (C.c_int, [_vp, _P(ScanLogStats)]),
     "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_shortcut_destroy": (None, [_vp]),
     "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),

@@ -2187,3 +2187,77 @@ class MotionPlanner:
         out = np.zeros(len(path), np.float32)
         check(self.distances_.ctx.lib.bl_dist_gather(self.distances_.h, q.ctypes.data, len(path), out.ctypes.data))
         return bool(np.all(out > self.searchParams_.minDistanceToObstacle))
+
+
+class ScanHistory:
+    """Scan history and map rebuild (bl_scanlog_*, include/botlab_hip.h): the last `capacity` scans on the device -- kept rays,
+    kept count, pose -- and rebuild(): the map that sequential Mapping.updateMap calls over a window of them would leave, at the
+    recorded poses or at others, into any grid.  Index 0 is the oldest retained scan."""
+
+    def __init__(self, capacity, max_rays=8192, ctx=None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_scanlog_create(self.ctx.h, int(capacity), int(max_rays), C.byref(h)))
+        self.h = h
+        self.capacity, self.max_rays = int(capacity), int(max_rays)
+
+    def __len__(self):
+        return int(self.ctx.lib.bl_scanlog_size(self.h))
+
+    def append(self, scan, pose):
+        ls = scan.as_c()
+        check(self.ctx.lib.bl_scanlog_append(self.h, C.byref(ls), C.byref(pose)))
+
+    def append_device_pose(self, scan, d_pose_ptr, pose_utime):
+        """x, y, theta read from a bl_pose_xyt_t in device memory (e.g. ParticleFilter.poseDevicePtr()), stream-ordered; utime given."""
+        ls = scan.as_c()
+        check(self.ctx.lib.bl_scanlog_append_dev_pose(self.h, C.byref(ls), d_pose_ptr, int(pose_utime)))
+
+    def poses(self, first=0, count=None):
+        """POSE_DTYPE [count]: the recorded poses of entries first .. first + count - 1 (count None: to the end)."""
+        count = len(self) - first if count is None else int(count)
+        out = np.zeros(max(count, 0), POSE_DTYPE)
+        if count > 0:
+            check(self.ctx.lib.bl_scanlog_get_poses(self.h, int(first), count, out.ctypes.data))
+        return out
+
+    def set_poses(self, first, poses):
+        p = _pose_array(poses)
+        check(self.ctx.lib.bl_scanlog_set_poses(self.h, int(first), len(p), p.ctypes.data))
+
+    def scan(self, i):
+        """(ranges, thetas, times) of entry i: its kept rays."""
+        r, t, s = np.zeros(self.max_rays, np.float32), np.zeros(self.max_rays, np.float32), np.zeros(self.max_rays, np.int64)
+        n = C.c_int()
+        check(self.ctx.lib.bl_scanlog_get_scan(self.h, int(i), r.ctypes.data, t.ctypes.data, s.ctypes.data, C.byref(n)))
+        return r[:n.value].copy(), t[:n.value].copy(), s[:n.value].copy()
+
+    def rebuild(self, out, maxLaserDistance, hitOdds, missOdds, first=0, count=None, poses=None, prev_pose=None, base=None):
+        """`out` becomes base (None: zeros) after Mapping(maxLaserDistance, hitOdds, missOdds).updateMap of entries first ..
+        first + count - 1 in order, at `poses` (None: the recorded ones); prev_pose None: the first of them only latches its pose."""
+        count = len(self) - first if count is None else int(count)
+        p = None if poses is None else _pose_array(poses)
+        assert p is None or len(p) == count
+        check(self.ctx.lib.bl_scanlog_rebuild(self.h, int(first), count, None if p is None else p.ctypes.data,
+                                              None if prev_pose is None else C.byref(prev_pose), C.c_float(maxLaserDistance), int(hitOdds),
+                                              int(missOdds), None if base is None else base.h, out.h))
+
+    def stats(self):
+        s = _capi.ScanLogStats()
+        check(self.ctx.lib.bl_scanlog_last_stats(self.h, C.byref(s)))
+        return s
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_scanlog_destroy(self.h)
+            self.h = None
+
+
+def _pose_array(poses):
+    """POSE_DTYPE array of a POSE_DTYPE array or of a sequence of Pose."""
+    if isinstance(poses, np.ndarray) and poses.dtype == POSE_DTYPE:
+        return np.ascontiguousarray(poses)
+    out = np.zeros(len(poses), POSE_DTYPE)
+    for i, q in enumerate(poses):
+        out[i] = (int(q.utime), q.x, q.y, q.theta, 0.0)
+    return out

@@ -28,6 +28,7 @@
 #include "beam_model.hpp"
 #include "botlab_dropin.hpp"
 #include "likelihood_field.hpp"
+#include "map_rebuild.hpp"
 #include "scan_matcher.hpp"
 
 namespace botlab_hip {
@@ -249,7 +250,8 @@ public:
     OccupancyGridSLAMT(int numParticles, int8_t hitOddsIncrease, int8_t missOddsDecrease, const Publisher& pub,
                        bool waitForOptitrack, bool mappingOnlyMode = false, bool actionOnlyMode = false,
                        const std::string& localizationOnlyMap = std::string())
-        : pf_(numParticles), grid_(10.0f, 10.0f, 0.05f), mapping_(5.0f, hitOddsIncrease, missOddsDecrease), out_(pub)
+        : pf_(numParticles), grid_(10.0f, 10.0f, 0.05f), mapping_(mapRange(), hitOddsIncrease, missOddsDecrease), out_(pub),
+          mapHit_(hitOddsIncrease), mapMiss_(missOddsDecrease)
     {
         how_.posesGiven = mappingOnlyMode;
         how_.awaitingFrame = waitForOptitrack;
@@ -396,6 +398,22 @@ public:
     // changes; set before the first iteration.  beamModelActive(): the switch is on and an update has been reweighed.
     void setBeamModel(bool on, const bl_beam_params_t& p = default_beam_params()) { beamOn_ = on; beamParams_ = p; }
     bool beamModelActive() const { return beamOn_ && static_cast<bool>(beam_); }
+    // (extension) Scan history (ScanHistoryT, map_rebuild.hpp): every iteration that updates the map appends the same
+    // scan and the same pose bits to a history of the last `capacity` scans -- in the fused step the pose is read on the device, behind
+    // the map update that carries the filter's end.  rebuildMap() writes into the driver's map what sequential map updates of the
+    // recorded scans at the recorded poses give from an empty map -- the live map itself while the history still holds every scan --
+    // and rebuildMap(poses) the same at corrected poses, one per recorded scan.  Nothing here corrects a pose; the live mapper is
+    // neither read nor changed.  Off by default, and with it off nothing the driver does changes; set before the first iteration.
+    void setScanHistory(int capacity) { historyCapacity_ = capacity; }
+    ScanHistoryT<Pose, Lidar>* scanHistory() const { return history_.get(); }
+    void rebuildMap()
+    {
+        if (history_ && history_->size() > 0) history_->rebuild(grid_, mapRange(), mapHit_, mapMiss_, 0, history_->size());
+    }
+    void rebuildMap(const std::vector<Pose>& poses)
+    {
+        if (history_ && !poses.empty()) history_->rebuild(grid_, mapRange(), mapHit_, mapMiss_, 0, poses);
+    }
     // (extension) The seed of the filter's first cloud, for runs that can be repeated (the reference, and the default here, take
     // it from the OS).  Set before the first iteration.
     void setFilterSeed(uint64_t seed) { seeded_ = true; seed_ = seed; }
@@ -513,6 +531,11 @@ private:
     bool beamOn_ = false;
     bl_beam_params_t beamParams_ = default_beam_params();
     std::unique_ptr<BeamModelT<Pose, Lidar> > beam_;
+    // scan history: capacity (0: off); the history (made at the first map update); what the mapper was made with
+    int historyCapacity_ = 0;
+    std::unique_ptr<ScanHistoryT<Pose, Lidar> > history_;
+    int8_t mapHit_, mapMiss_;
+    static float mapRange() { return 5.0f; }               // slam.cpp:24
 
     // the filter's update from `odometry` and, with the beam model on, its weights replaced by the beam model's
     Pose sense(const Pose& odometry)
@@ -666,14 +689,22 @@ private:
     }
 
     // slam.cpp:274-294 (its mode test is always true: the map is extended in every mode); the map goes out with every fifth update.
+    bool recording()
+    {
+        if (historyCapacity_ > 0 && !history_) history_.reset(new ScanHistoryT<Pose, Lidar>(historyCapacity_));
+        return static_cast<bool>(history_);
+    }
+
     void extendMap(bool riding)
     {
         if (riding) {
             mapping_.updateMapFinishingFilter(scan_, pf_, odomAtScan_.utime, grid_);
+            if (recording()) history_->appendDevicePose(scan_, bl_pf_pose_device_ptr(pf_.device()), odomAtScan_.utime);
             now_ = pf_.poseEstimate();
             announce();
         } else {
             mapping_.updateMap(scan_, now_, grid_);
+            if (recording()) history_->append(scan_, now_);
         }
         if (lfield_ && !how_.mapFromFile) lfield_->compute(grid_);
         how_.mapKnown = true;

@@ -1780,6 +1780,58 @@ int bl_beam_debug_path(bl_beam* beam);
 /* device time of the last call's kernels (HIP events around the launches); BL_ERR_STATE before the first */
 int bl_beam_last_device_ms(const bl_beam* beam, float* ms);
 
+/* ------------------------------------------------------------------ scan history and map rebuild  
+ * A map is otherwise written once, at the pose held at that moment, and the scan is thrown away.  The log keeps the last
+ * `capacity_scans` scans on the device -- per scan the KEPT rays exactly as the mapper takes them (ranges, thetas, times; ranges
+ * <= 0.15 already dropped), the kept count and the pose (utime, x, y, theta) -- so that a map can be made again from any window of
+ * them, at any poses, in any grid.  Index 0 is the oldest retained scan.  All calls are stream-ordered on the ctx stream.
+ *
+ * bl_scanlog_rebuild(log, first, count, poses, prev_pose, max_laser, hit, miss, base, out).  The whole contract:
+ *   - Start from `base`'s cells.  `base` must have the same shape and frame as `out`, and may be `out` itself.  NULL means all zero.
+ *   - Take a fresh Mapping(max_laser, hit, miss).
+ *   - If `prev_pose` is given, the mapper is primed with it: initialized_ true, previousPose_ = *prev_pose.
+ *   - If `prev_pose` is NULL, scan `first` only latches its pose and changes no cell, as the first call of any Mapping does.
+ *   - Then updateMap(scan_k, pose_k, out) runs for k = first ... first + count - 1, in order.  pose_k is poses[k - first], or the
+ *     recorded pose when `poses` is NULL.
+ *   - `out` equals the result byte for byte.
+ *   Every rule of the map update's geometry holds: the range <= max_laser cut; per-ray pose interpolation between pose k-1 and
+ *   pose k by ray time; no interpolation when the two utimes are equal; float -> int truncation; the 2^24 coordinate limit; the end
+ *   cell gets the hit and is excluded from the walk; the start cell is included in the walk; off-grid cells are skipped; hits come
+ *   before misses within a scan.  The geometry uses `out`'s frame, so a rebuild into a grid of another resolution or origin is the
+ *   same call.  `out` is treated afterwards as bl_grid_upload treats its target (its mirror is stale, its cells start a new
+ *   lineage).  A live bl_mapping object is neither read nor changed.  The call makes one small read-back (it synchronises).
+ * Appending to a full ring drops the oldest scan.  A scan with more kept rays than max_rays_per_scan is refused and the log stays
+ * as it was.  The second append form reads x, y, theta from device memory, stream-ordered, with no host round trip; utime comes
+ * from the argument, as in bl_mapping_update_dev_pose.  bl_scanlog_set_poses overwrites recorded poses (a caller that corrected a
+ * trajectory keeps it); bl_scanlog_get_poses, bl_scanlog_get_scan synchronise.
+ * BL_ERR_ARG: capacity_scans < 1, max_rays_per_scan outside 1 .. 8192, more than 1 GiB of log (16 bytes a ray); a window outside
+ * 0 .. size or count < 1; negative odds; a grid of another ctx; a base of another shape or frame.  A refused call enqueues nothing
+ * and leaves `out` and the log untouched.  bl_scanlog_last_stats before the first rebuild: BL_ERR_STATE. */
+typedef struct bl_scanlog bl_scanlog;
+typedef struct bl_scanlog_stats_t {
+    int64_t tiles;                     /* tiles of `out` (tile_cells x tile_cells cells each) */
+    int64_t chunks;                    /* chunks of chunk_scans consecutive scans */
+    int64_t pairs;                     /* (tile, chunk) pairs whose boxes meet: workgroups of the fold */
+    int64_t scratch_bytes;             /* composed functions held between fold and apply: pairs * tile_cells^2 * 4 */
+    int32_t chunk_scans, tile_cells;
+    int32_t scans;                     /* scans that change cells: count, less the latching one without a prev_pose */
+    int32_t pad;
+    float ms_total, ms_geometry, ms_fold, ms_apply;   /* device time between events; geometry includes the read-back */
+} bl_scanlog_stats_t;                  /* 64 bytes */
+int bl_scanlog_create(bl_ctx* ctx, int capacity_scans, int max_rays_per_scan, bl_scanlog** out);
+void bl_scanlog_destroy(bl_scanlog* log);
+int bl_scanlog_append(bl_scanlog* log, const bl_lidar_t* scan, const bl_pose_xyt_t* pose);
+int bl_scanlog_append_dev_pose(bl_scanlog* log, const bl_lidar_t* scan, const void* d_pose /* bl_pose_xyt_t* */, int64_t pose_utime);
+int bl_scanlog_size(const bl_scanlog* log);                             /* scans held; 0 for NULL */
+int bl_scanlog_get_poses(bl_scanlog* log, int first, int count, bl_pose_xyt_t* out);
+int bl_scanlog_set_poses(bl_scanlog* log, int first, int count, const bl_pose_xyt_t* poses);
+/* the kept rays of entry i (room for max_rays_per_scan each; any pointer may be NULL) */
+int bl_scanlog_get_scan(bl_scanlog* log, int i, float* ranges, float* thetas, int64_t* times, int* kept);
+int bl_scanlog_rebuild(bl_scanlog* log, int first, int count, const bl_pose_xyt_t* poses /* NULL: recorded */,
+                       const bl_pose_xyt_t* prev_pose /* may be NULL */, float max_laser, int8_t hit, int8_t miss,
+                       const bl_grid* base /* may be NULL */, bl_grid* out);
+int bl_scanlog_last_stats(bl_scanlog* log, bl_scanlog_stats_t* stats);  /* of the last rebuild; waits for it */
+
 #ifdef __cplusplus
 }
 #endif
