@@ -427,6 +427,7 @@ SIGNATURES = {
     "bl_pf_pose_device_ptr": (_vp, [_vp]),
     "bl_pf_estimate_posterior_pose": (C.c_int, [_vp, _vp]),
     "bl_pf_debug_estimate_stats": (C.c_int, [_vp, _vp]),
+    "bl_pf_debug_lookahead": (C.c_int, [_vp, _vp]),
     "bl_pf_debug_set_finish_generation": (C.c_int, [_vp, C.c_uint32]),
     "bl_pf_set_strict_resampling": (C.c_int, [_vp, C.c_int]),
     "bl_pf_debug_resample": (C.c_int, [_vp, C.c_int, _vp]),
@@ -461,6 +462,7 @@ SIGNATURES = {
     "bl_planner_create_batched": (C.c_int, [_vp, C.c_int, C.c_int, _P(_vp)]),
     "bl_planner_destroy": (None, [_vp]),
     "bl_planner_submit": (C.c_int, [_vp, _vp, _vp, _P(Pose), _P(SearchParams)]),
+    "bl_planner_debug_snapshot": (C.c_int, [_vp, _vp, C.c_int64]),
     "bl_planner_fetch": (C.c_int, [_vp, _vp, C.c_int, _P(C.c_int), _P(C.c_int64)]),
     "bl_planner_flush": (C.c_int, [_vp]),
     "bl_planner_timing": (C.c_int, [_vp, C.c_int, _P(C.c_double), _P(C.c_double), _P(C.c_int64)]),

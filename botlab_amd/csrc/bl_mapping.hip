@@ -185,22 +185,42 @@ __global__ __launch_bounds__(MAP_THREADS) void k_map_update(map_args a)
 }
 
 // start cell and end cell of one ray (moving_laser_scan.cpp:22-37, mapping.cpp:45-49); x == 0x7fffffff: the ray takes no part
-__device__ __forceinline__ int4 map_ray_cells(const map_args& a, const bl_pose3& pb, const bl_pose3& pe, float range, float ray_theta, int64_t ray_time)
+// It comes in two parts.  What depends on the poses' THETA alone -- the interpolated theta does not depend on x or y --: the
+// ray's reach in cells along both axes (wrap, sine and cosine, two products each).  And what depends on their POSITION.  A map
+// update that ran ahead of the filter's exact x, y checks its cells with the second part alone: theta was final all along.
+struct map_ray_reach { float ex, ey; double ratio; bool on; };
+__device__ __forceinline__ map_ray_reach map_ray_angle(const map_args& a, const bl_pose3& pb, const bl_pose3& pe, float range, float ray_theta, int64_t ray_time)
+{
+    map_ray_reach d = {0.0f, 0.0f, 0.0, range <= a.max_laser};  // rays with range <= 0.15f were dropped on the host
+    if (d.on) {
+        if (a.interp) d.ratio = bl_interp_ratio(ray_time, a.t_begin, a.t_den);
+        const float rp_theta = a.interp ? bl_interpolate_pose(pb, pe, d.ratio).theta : pe.theta;
+        float theta = bl_wrap_to_pi(rp_theta - ray_theta);
+        float sn, cs;
+        bl_sincosf(theta, &sn, &cs);
+        d.ex = range * cs * a.frame.cpm;
+        d.ey = range * sn * a.frame.cpm;
+    }
+    return d;
+}
+__device__ __forceinline__ int4 map_ray_place(const map_args& a, const bl_pose3& pb, const bl_pose3& pe, const map_ray_reach& d)
 {
     int4 ray = make_int4(0x7fffffff, 0, 0, 0);
-    if (range <= a.max_laser) {                                 // rays with range <= 0.15f were dropped on the host
-        bl_pose3 rp = a.interp ? bl_interpolate_pose(pb, pe, bl_interp_ratio(ray_time, a.t_begin, a.t_den)) : pe;
-        float theta = bl_wrap_to_pi(rp.theta - ray_theta);
-        float sn, cs, sx, sy;
-        bl_sincosf(theta, &sn, &cs);
+    if (d.on) {
+        const bl_pose3 rp = a.interp ? bl_interpolate_pose(pb, pe, d.ratio) : pe;
+        float sx, sy;
         bl_global_to_grid(rp.x, rp.y, a.frame, &sx, &sy);
-        float fx = (range * cs * a.frame.cpm) + sx;
-        float fy = (range * sn * a.frame.cpm) + sy;
+        float fx = d.ex + sx;
+        float fy = d.ey + sy;
         const float lim = (float)MAP_CELL_LIMIT;
         if (fx > -lim && fx < lim && fy > -lim && fy < lim && sx > -lim && sx < lim && sy > -lim && sy < lim)
             ray = make_int4((int)sx, (int)sy, (int)fx, (int)fy);        // float -> int truncation at the bresenham() call
     }
     return ray;
+}
+__device__ __forceinline__ int4 map_ray_cells(const map_args& a, const bl_pose3& pb, const bl_pose3& pe, float range, float ray_theta, int64_t ray_time)
+{
+    return map_ray_place(a, pb, pe, map_ray_angle(a, pb, pe, range, ray_theta, ray_time));
 }
 
 // lds_pose: the pose of this update in shared memory (or null: a.cur_dev / a.cur_host).  provisional: its x, y are the map
@@ -254,10 +274,13 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
     // ---- phase A: ray geometry (moving_laser_scan.cpp:22-37, mapping.cpp:45-49)
     int bx_lo = 0x7fffffff, by_lo = 0x7fffffff, bx_hi = -0x7fffffff, by_hi = -0x7fffffff;
     int4 my_ray = make_int4(0x7fffffff, 0, 0, 0);
+    map_ray_reach my_reach = {0.0f, 0.0f, 0.0, false};          // of this thread's first ray (the one a look-ahead checks again)
     for (int r = tid; r < a.R; r += MAP_THREADS) {
         const bool first = r == tid;
-        const int4 ray = map_ray_cells(a, pb, pe, first ? pre_range : a.ranges[r], first ? pre_theta : a.thetas[r],
-                                       a.interp ? (first ? pre_time : a.times[r]) : 0);
+        const map_ray_reach reach = map_ray_angle(a, pb, pe, first ? pre_range : a.ranges[r], first ? pre_theta : a.thetas[r],
+                                                  a.interp ? (first ? pre_time : a.times[r]) : 0);
+        if (first) my_reach = reach;
+        const int4 ray = map_ray_place(a, pb, pe, reach);
         if (ray.x != 0x7fffffff) {
             bx_lo = min(bx_lo, min(ray.x, ray.z)); by_lo = min(by_lo, min(ray.y, ray.w));
             bx_hi = max(bx_hi, max(ray.x, ray.z)); by_hi = max(by_hi, max(ray.y, ray.w));
@@ -408,7 +431,7 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
                 XSTAMP(11);
                 const bl_pose3 pe2 = {lds_pose->x, lds_pose->y, pe.theta};
                 if (tid < a.R) {
-                    const int4 ray2 = map_ray_cells(a, pb, pe2, pre_range, pre_theta, pre_time);
+                    const int4 ray2 = map_ray_place(a, pb, pe2, my_reach);       // (pe2.theta == pe.theta: the angle part stands)
                     if (ray2.x != my_ray.x || ray2.y != my_ray.y || ray2.z != my_ray.z || ray2.w != my_ray.w) atomicOr(&s_redo, 1);
                 }
                 __syncthreads();

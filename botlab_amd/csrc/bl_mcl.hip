@@ -3122,6 +3122,16 @@ extern "C" int bl_pf_debug_estimate_stats(bl_pf* pf, uint32_t* out4)   /* eight 
     return BL_OK;
 }
 
+// Map updates that ran ahead of the exact pose since the filter was created, and those of them that had to run again
+extern "C" int bl_pf_debug_lookahead(bl_pf* pf, uint32_t* out2)
+{
+    BL_CHECK_ARG(pf != nullptr && out2 != nullptr && pf->state != nullptr);
+    BL_HIP(hipSetDevice(pf->ctx->device));
+    BL_HIP(hipStreamSynchronize(pf->ctx->stream));
+    BL_HIP(hipMemcpy(out2, pf->state->lookahead, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return BL_OK;
+}
+
 // The generation the NEXT finish launch's records are tagged with follows from this one (tests: the tag's wrap-around, where the
 // host skips the generations whose tag reads like zeroed slots)
 extern "C" int bl_pf_debug_set_finish_generation(bl_pf* pf, uint32_t generation)

@@ -233,6 +233,7 @@ struct mclf_smem {
     double bx[MCLF_MAXW], by[MCLF_MAXW];          // sums of the blocks before the group, per wave
     double wx[MCLF_MAXW], wy[MCLF_MAXW];          // sums of the sub-tiles' terms
     double red[MCLF_POSE_THREADS / 64][5];
+    double sred[MCLF_POSE_THREADS / 64];          // finisher: the units column alone, per wave (S ahead of the ordered sums)
     float xy[2], first[2];                        // the sums; the sums behind the finisher's own sub-tiles
     unsigned int stats[8];
     int tbase[2][BL_MAX_SHARDS + 1];              // per axis: first staged slot of every rank's tables (composed finish; one rank: {0, MCLF_TSLOTS})
@@ -251,11 +252,6 @@ struct mclf_smem {
 __device__ __forceinline__ double mclf_wave_sum(double v)
 {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double mclf_wave_sum_all(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
 
@@ -498,6 +494,40 @@ __device__ __forceinline__ int mclf_wave_max(int v)
 #undef MCLF_STEP
     return __builtin_amdgcn_readlane(v, 63);
 }
+// 64-bit values take the same steps as two dwords (old = 0 in both)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long mclf_dpp_u64(unsigned long long v)
+{
+    const int lo = mclf_dpp<CTRL, ROW_MASK>(0, (int)(unsigned int)v), hi = mclf_dpp<CTRL, ROW_MASK>(0, (int)(unsigned int)(v >> 32));
+    return ((unsigned long long)(unsigned int)hi << 32) | (unsigned long long)(unsigned int)lo;
+}
+// inclusive scan / sum over the wave (every lane gets the sum) of 64-bit integers: exact, whatever the order
+__device__ __forceinline__ unsigned long long mclf_scan_add_u64(unsigned long long v)
+{
+#define MCLF_STEP(C, R) v += mclf_dpp_u64<C, R>(v);
+    MCLF_DPP_STEPS(MCLF_STEP)
+#undef MCLF_STEP
+    return v;
+}
+__device__ __forceinline__ unsigned long long mclf_wave_sum_u64(unsigned long long v)
+{
+    return (unsigned long long)mclf_readlane_i64_((long long)mclf_scan_add_u64(v), 63);
+}
+// The same of doubles (a lane without a source lane adds +0.0).  The additions are NOT in the order of mclf_wave_sum, nor of
+// the shuffle butterfly these sums used before.  So: for exact integers below 2^53, and for PREDICTIONS only -- every use of a
+// prediction is checked against the true accumulator (ss_rec_fits, ssw_fits), and another rounding costs time, never a bit of
+// the result.  The ordered sums of the estimate (mclf_reduce_partials) stay on mclf_wave_sum.
+__device__ __forceinline__ double mclf_scan_add_f64(double v)
+{
+#define MCLF_STEP(C, R) v += __longlong_as_double((long long)mclf_dpp_u64<C, R>((unsigned long long)__double_as_longlong(v)));
+    MCLF_DPP_STEPS(MCLF_STEP)
+#undef MCLF_STEP
+    return v;
+}
+__device__ __forceinline__ double mclf_wave_sum_f64(double v)
+{
+    return __longlong_as_double(mclf_readlane_i64_(__double_as_longlong(mclf_scan_add_f64(v)), 63));
+}
 // inclusive scan of records by composition (lane l: records 0..l of the wave joined in order)
 __device__ __forceinline__ ss_rec mclf_scan_join(ss_rec r)
 {
@@ -552,6 +582,8 @@ __device__ __forceinline__ ss_wild mclf_wild_map(const double (&t)[MCLF_ITEMS], 
     const int k1 = cnt > 1 ? ss_key((float)P1) : k2;
     ss_wild w = cnt > 0 ? ssw_step(k0, k1, t[0]) : ssw_identity(k0);
     if (cnt > 1) w = ssw_join(w, ssw_step(k1, k2, t[1]));
+    // (this scan stays on shuffles: on DPP it moved the pre-chain's maps barrier by less than 0.1 us -- six ssw_join in a row are
+    // the time, not the twelve crossbar trips between them)
     for (int off = 1; off < 64; off <<= 1) {
         const ss_wild o = mclf_shfl_up_wild(w, off);
         if (lane >= off) w = ssw_join(o, w);
@@ -686,18 +718,15 @@ __device__ __forceinline__ void mclf_prefix_group(const mcl_finish_args& f, int 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (tid == 0 && g == f.groups / 2) f.state->xstamps[0] = MCLF_NOW();
 #endif
-    for (int off = 32; off > 0; off >>= 1) { before += __shfl_xor(before, off, 64); total += __shfl_xor(total, off, 64); }
-    bx = mclf_wave_sum_all(bx); by = mclf_wave_sum_all(by);
+    // (on DPP: before, total are exact integers; bx, by are predictions, checked where they are used -- mclf_scan_add_f64)
+    before = mclf_wave_sum_u64(before); total = mclf_wave_sum_u64(total);
+    bx = mclf_wave_sum_f64(bx); by = mclf_wave_sum_f64(by);
     if (lane == 0) { sm.off[wave] = before; sm.tot[wave] = total; sm.bx[wave] = bx; sm.by[wave] = by; }
     unsigned long long loc[MCLF_ITEMS];
     unsigned long long run = 0;
 #pragma unroll
     for (int k = 0; k < MCLF_ITEMS; ++k) { run += __float_as_uint(r[k].w); loc[k] = run; }
-    unsigned long long incl = run;
-    for (int off = 1; off < 64; off <<= 1) {
-        unsigned long long t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
+    const unsigned long long incl = mclf_scan_add_u64(run);
     if (lane == 63) sm.wave[wave] = incl;
     MCLF_GSTAMP(1);
     __syncthreads();
@@ -723,7 +752,7 @@ __device__ __forceinline__ void mclf_prefix_group(const mcl_finish_args& f, int 
         tx[k] = mclf_term(r[k], St, 0); ty[k] = mclf_term(r[k], St, 1);
         sx += tx[k]; sy += ty[k];
     }
-    sx = mclf_wave_sum_all(sx); sy = mclf_wave_sum_all(sy);
+    sx = mclf_wave_sum_f64(sx); sy = mclf_wave_sum_f64(sy);      // (predictions of where the later waves' sub-tiles start)
     if (lane == 0) { sm.wx[wave] = sx; sm.wy[wave] = sy; }
     MCLF_GSTAMP(4);
     __syncthreads();
@@ -1357,28 +1386,39 @@ __device__ __forceinline__ float mclf_chain(const mcl_finish_args& f, const mclf
 
 // The block sums in the fixed order of a 256-thread workgroup (thread-strided with a stride of 256, wave shuffles, waves in order)
 // into sm.red; the caller puts a barrier behind it and adds the four rows up (mclf_block_totals).
+// It comes in two parts, so that the finisher can take S out of the first before it pays for the second: the sums of thread
+// `vt` of those 256 (whichever thread of the workgroup plays it), then the wave sums of wave `vwave` of the four.
+__device__ __forceinline__ void mclf_partials_thread(const mcl_finish_args& f, int vt, double (&v)[5])
+{
+    for (int k = 0; k < 5; ++k) v[k] = 0.0;
+    // (four blocks per thread requested together -- a trip to memory each otherwise; the additions keep their order)
+    for (int b0 = vt; b0 < f.nblocks; b0 += 4 * MCLF_POSE_THREADS) {
+        double p[4][5];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int b = b0 + q * MCLF_POSE_THREADS;
+            const size_t at = (size_t)(b < f.nblocks ? b : 0) * 5;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) p[q][k] = f.partials[at + k];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (b0 + q * MCLF_POSE_THREADS < f.nblocks)
+                for (int k = 0; k < 5; ++k) v[k] += p[q][k];
+    }
+}
+__device__ __forceinline__ void mclf_partials_waves(mclf_smem& sm, double (&v)[5], int vwave, int lane)
+{
+    for (int k = 0; k < 5; ++k) v[k] = mclf_wave_sum(v[k]);
+    if (lane == 0) for (int k = 0; k < 5; ++k) sm.red[vwave][k] = v[k];
+}
 __device__ __forceinline__ void mclf_reduce_partials(const mcl_finish_args& f, mclf_smem& sm)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < MCLF_POSE_THREADS) {
-        double v[5] = {0, 0, 0, 0, 0};
-        // (four blocks per thread requested together -- a trip to memory each otherwise; the additions keep their order)
-        for (int b0 = tid; b0 < f.nblocks; b0 += 4 * MCLF_POSE_THREADS) {
-            double p[4][5];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int b = b0 + q * MCLF_POSE_THREADS;
-                const size_t at = (size_t)(b < f.nblocks ? b : 0) * 5;
-#pragma unroll
-                for (int k = 0; k < 5; ++k) p[q][k] = f.partials[at + k];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (b0 + q * MCLF_POSE_THREADS < f.nblocks)
-                    for (int k = 0; k < 5; ++k) v[k] += p[q][k];
-        }
-        for (int k = 0; k < 5; ++k) v[k] = mclf_wave_sum(v[k]);
-        if (lane == 0) for (int k = 0; k < 5; ++k) sm.red[wave][k] = v[k];
+        double v[5];
+        mclf_partials_thread(f, tid, v);
+        mclf_partials_waves(sm, v, wave, lane);
     }
 }
 __device__ __forceinline__ void mclf_block_totals(const mclf_smem& sm, double (&tot)[5])
@@ -1487,7 +1527,7 @@ __device__ __forceinline__ void mclf_pre_chain(const mcl_finish_args& f, mclf_sm
 #pragma unroll
             for (int q = 0; q < 4; ++q) if (b0 + q * MCLF_POSE_THREADS < f.nblocks) su += p[q];
         }
-        su = mclf_wave_sum_all(su);
+        su = mclf_wave_sum_f64(su);                                              // (exact integers: any order)
         if (lane == 0) sm.red[wave][0] = su;
     }
 #ifdef MCLF_STAMPS
@@ -1517,14 +1557,14 @@ __device__ __forceinline__ void mclf_pre_chain(const mcl_finish_args& f, mclf_sm
                 }
                 nstep = q * MCLF_SUB + cnt[q];                // (a short sub-tile can only be the last one)
             }
-            qs = mclf_wave_sum_all(qs);
+            qs = mclf_wave_sum_f64(qs);                       // (psum: the builders' predicted starts, checked by ssw_fits)
             if (lane == 0) sm.psum[axis][q] = qs;
         }
     } else if (builder) {
         double qs = 0.0;
 #pragma unroll
         for (int k = 0; k < MCLF_ITEMS; ++k) { bt[k] = k < bcnt ? mclf_term(br[k], S, axis) : 0.0; qs += bt[k]; }
-        qs = mclf_wave_sum_all(qs);
+        qs = mclf_wave_sum_f64(qs);
         if (lane == 0) sm.psum[axis][bq] = qs;
     }
 #ifdef MCLF_STAMPS
@@ -1609,7 +1649,17 @@ __device__ __forceinline__ void mclf_pose(const mcl_finish_args& f, mclf_smem& s
 #define MCLF_STAMP(i) do { } while (0)
 #endif
     const int nrec = f.groups * (f.gthreads >> 6), nbatch = (nrec + 63) >> 6;
-    mclf_reduce_partials(f, sm);
+    // The block sums: only S is needed now (the terms), the ordered sums at the exit (theta, state->S).  The LAST four waves play
+    // the 256 threads (they have one batch of records to take below, the first ten waves two; waves 0 and 1 run the chains): S
+    // goes out from their units column by one DPP sum, their five shuffle sums follow behind the barrier, beside the wait for
+    // the groups' records.
+    const int pt = tid - (MCLF_WG - MCLF_POSE_THREADS);
+    double pv[5] = {0, 0, 0, 0, 0};
+    if (pt >= 0) {
+        mclf_partials_thread(f, pt, pv);
+        const double su = mclf_wave_sum_f64(pv[0]);                              // exact integers below 2^53: any order gives S
+        if (lane == 0) sm.sred[pt >> 6] = su;
+    }
     const size_t per_axis = (mclf_stage_bytes(nbatch) + 15) & ~(size_t)15;
     const bool staged = scratch != nullptr && 2 * per_axis <= scratch_bytes;
 #define MCLF_STAGE(axis) mclf_stage_at(scratch + (size_t)(axis) * per_axis, nbatch)
@@ -1628,9 +1678,10 @@ __device__ __forceinline__ void mclf_pose(const mcl_finish_args& f, mclf_smem& s
     }
     __syncthreads();
     double S = 0.0;
-    for (int w = 0; w < MCLF_POSE_THREADS / 64; ++w) S += sm.red[w][0];          // exact integer below 2^53, any order gives it
+    for (int w = 0; w < MCLF_POSE_THREADS / 64; ++w) S += sm.sred[w];
     S = mclf_term_S(f, S);                                                       // (S feeds the terms only from here on)
     MCLF_STAMP(1);
+    if (pt >= 0) mclf_partials_waves(sm, pv, pt >> 6, lane);                     // (sm.red: read at the exit, barriers away)
     const int sh_world = mclf_world(f);
     {
         // ---- stage a: every wave takes batches of 64 records of both axes, four per round, as 16-byte loads through the L2 (sc1)
@@ -1807,7 +1858,14 @@ __device__ __forceinline__ void mclf_pose(const mcl_finish_args& f, mclf_smem& s
         const float first = __uint_as_float((unsigned int)fw);
         const mclf_stage mine = MCLF_STAGE(wave);
         const float v = mclf_chain(f, staged ? &mine : nullptr, wave ? ntab[1] : ntab[0], wave, S, first, lane, stats, trees[wave], &sm.pre[wave][0]);      // (sm.pre: the pre-chain workgroup's buffer, idle in this one)
-        if (lane == 0) { sm.xy[wave] = v; for (int k = 0; k < 4; ++k) sm.stats[4 * wave + k] = stats[k]; }
+        if (lane == 0) {
+            // another workgroup of this launch (the map update) is spinning on x and y: f.sync[3] / [4], each word its own flag,
+            // go out the moment their chains end (that workgroup has theta from its own reduction, and clears the two words;
+            // state->pose, the stats and the other sync words follow behind the barrier)
+            if (publish) mclf_store_u64(f.sync + 3 + wave, (unsigned long long)__float_as_uint(v) | (1ull << 32));
+            sm.xy[wave] = v;
+            for (int k = 0; k < 4; ++k) sm.stats[4 * wave + k] = stats[k];
+        }
     }
     __syncthreads();
     MCLF_STAMP(4);
@@ -1823,12 +1881,7 @@ __device__ __forceinline__ void mclf_pose(const mcl_finish_args& f, mclf_smem& s
         p.x = sm.xy[0];
         p.y = sm.xy[1];
         p.theta = (float)atan2(tot[3], tot[4]);
-        f.state->pose = p;
-        if (publish) {
-            // another workgroup of this launch (the map update) is waiting for x and y: f.sync[3] / [4], which that workgroup clears
-            mclf_store_u64(f.sync + 3, (unsigned long long)__float_as_uint(p.x) | (1ull << 32));
-            mclf_store_u64(f.sync + 4, (unsigned long long)__float_as_uint(p.y) | (1ull << 32));
-        }
+        f.state->pose = p;                                   // (x and y went to a waiting workgroup when their chains ended)
         for (int k = 0; k < 5; ++k) f.state->sums_used[k] = tot[k];
         for (int k = 0; k < 8; ++k) f.state->chain_stats[k] = sm.stats[k];
         uni_update(f.state, f.N, tot[0], f.uni_mode, f.w_floor);        // (behind the published pose: one compare and one store unless every particle is at the floor)

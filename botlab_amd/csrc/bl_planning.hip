@@ -3202,6 +3202,7 @@ struct bl_planner {
     int64_t submitted, fetched;
     std::deque<planner_ticket>* tickets;    // outstanding submissions, oldest first
     bool reserved;
+    bl_grid* last_snap;                 // the snapshot grid of the latest submission (bl_planner_debug_snapshot)
 };
 
 extern "C" int bl_planner_create_batched(bl_ctx* ctx, int lanes, int batch, bl_planner** out)
@@ -3352,6 +3353,7 @@ int bl_planner_reserve(bl_planner* p, const bl_grid* map, bl_planner_snap* out)
         BL_HIP(hipStreamWaitEvent(p->main->stream, L.slot_free[slot], 0));
     out->grid = snap;
     out->cells = snap->cells;
+    p->last_snap = snap;
     snap->mirror_valid = false;                              // (nobody localises on a snapshot, but its cells are about to change)
     out->pose = U.pose[slot];
     p->reserved = true;
@@ -3359,6 +3361,19 @@ int bl_planner_reserve(bl_planner* p, const bl_grid* map, bl_planner_snap* out)
 }
 
 void bl_planner_cancel(bl_planner* p) { if (p) p->reserved = false; }
+
+// The cells of the snapshot the latest submission searched (tests: the map kernel's mirrored stores against the map itself)
+extern "C" int bl_planner_debug_snapshot(bl_planner* p, int8_t* out_cells, int64_t n_cells)
+{
+    BL_CHECK_ARG(p != nullptr && out_cells != nullptr);
+    if (!p->last_snap) { bl_set_error("bl_planner_debug_snapshot: nothing has been submitted"); return BL_ERR_STATE; }
+    const bl_frame& f = p->last_snap->frame;
+    BL_CHECK_ARG(n_cells == (int64_t)f.width * f.height);
+    BL_HIP(hipSetDevice(p->main->device));
+    BL_HIP(hipStreamSynchronize(p->main->stream));
+    BL_HIP(hipMemcpy(out_cells, p->last_snap->cells, (size_t)n_cells, hipMemcpyDeviceToHost));
+    return BL_OK;
+}
 
 // Second half: the lane stream waits for the snapshot (an event) and runs setDistances on it; search_for_path goes
 // out with the lane's batch (at once when batch == 1).

@@ -466,6 +466,12 @@ class ParticleFilter:
         check(self.ctx.lib.bl_pf_debug_estimate_stats(self.h, out.ctypes.data))
         return [int(v) for v in out]
 
+    def debugLookahead(self):
+        """(map updates that ran ahead of the exact pose, those of them that ran again) since the filter was created."""
+        out = np.zeros(2, np.uint32)
+        check(self.ctx.lib.bl_pf_debug_lookahead(self.h, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
     def particles(self):
         """particles_t.particles of the local shard as a structured array."""
         out = np.zeros(self._counts()[0], dtype=PARTICLE_DTYPE)
@@ -2019,6 +2025,12 @@ class AsyncPlanner:
         check(self.ctx.lib.bl_planner_fetch(self.h, self._buf, 4097, C.byref(n), stats))
         path = [Pose(p.utime, p.x, p.y, p.theta) for p in self._buf[:min(n.value, 4097)]]
         return (path, (stats[0], stats[1])) if return_stats else path
+
+    def debugSnapshot(self, grid):
+        """The cells of the snapshot the latest submission searched, shaped like `grid` (bl_planner_debug_snapshot)."""
+        out = np.zeros((grid.height, grid.width), np.int8)
+        check(self.ctx.lib.bl_planner_debug_snapshot(self.h, out.ctypes.data, out.size))
+        return out
 
     def flush(self):
         """End of input: the batch every lane is still collecting goes out as it is (bl_planner_flush)."""

@@ -342,6 +342,9 @@ int bl_pf_estimate_posterior_pose(bl_pf* pf, bl_pose_xyt_t* out_pose);
 /* diagnostics of the last estimate, eight values: for the x sum, then for the y sum -- sub-tiles replayed generically, phases
  * of those replays, sub-tiles stepped through by their table, gaps walked the slow way (bl_serial_sum.h, bl_mcl_finish.h) */
 int bl_pf_debug_estimate_stats(bl_pf* pf, uint32_t* out8);
+/* map updates that ran ahead of the filter's exact pose (bl_mapping_update_finishing_filter) since the filter was created,
+ * and those of them that had to run again because a ray's cells differed under the exact pose */
+int bl_pf_debug_lookahead(bl_pf* pf, uint32_t out[2]);
 int bl_pf_debug_set_finish_generation(bl_pf* pf, uint32_t generation);   /* tests: the record tags of the finish launches wrap every 256 launches */
 /* Resampling rule.  The update's resampler compares U_m * S with an exact integer prefix of the weight units; the reference
  * (particle_filter.cpp:84-103) compares U_m with a sequentially rounded double sum of the normalised weights.  The two agree unless
@@ -679,6 +682,8 @@ void bl_planner_destroy(bl_planner* p);
 int bl_planner_submit(bl_planner* p, const bl_grid* map, const void* d_start_pose /* bl_pose_xyt_t* on the device */,
                       const bl_pose_xyt_t* goal, const bl_search_params_t* params);
 int bl_planner_fetch(bl_planner* p, bl_pose_xyt_t* out_path, int cap, int* out_len, int64_t* stats);
+/* tests: the cells of the snapshot the latest submission searched (n_cells = width * height of the submitted map) */
+int bl_planner_debug_snapshot(bl_planner* p, int8_t* out_cells, int64_t n_cells);
 /* End of input (the scan stream pauses, a run ends): sends off the batch every lane is still collecting, so that its work runs beside
  * whatever the SLAM stream still holds instead of behind the fetch that would have sent it.  Results are fetched as ever. */
 int bl_planner_flush(bl_planner* p);
