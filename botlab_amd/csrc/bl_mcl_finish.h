@@ -868,16 +868,31 @@ __device__ __forceinline__ float mclf_replay(const double (&t)[MCLF_ITEMS], int 
     return acc;
 }
 
+// The chain's accumulator between list entries (mclf_chain): the integer pair while it has a usable binade, the float when it has
+// none (a.key == 0: f is authoritative; otherwise f is stale).  Wave-uniform.
+struct mclf_acc { ss_acc a; float f; };
+__device__ __forceinline__ mclf_acc mclf_acc_of(float v)
+{
+    v = __uint_as_float((unsigned int)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v)));
+    mclf_acc c;
+    c.a = ss_acc_of(v); c.f = v;
+    return c;
+}
+__device__ __forceinline__ mclf_acc mclf_acc_make(int key, int M) { mclf_acc c; c.a.key = key; c.a.M = M; c.f = 0.0f; return c; }
+__device__ __forceinline__ float mclf_acc_float(const mclf_acc& c) { return c.a.key ? ss_acc_float(c.a) : c.f; }
+
 // A risky sub-tile by its table (this lane's two rows e[0], e[1]; tkey = the binade the table was made for): the usual case is
 // ONE step that leaves the binade upwards.  Returns through the generic replay whenever the sub-tile does something else.
-__device__ __forceinline__ float mclf_replay_table(const mclf_tab_elem (&e)[MCLF_ITEMS], int tkey, int n, int head, float acc, int lane,
-                                                   unsigned int* phases, unsigned int* by_table)
+// Every lane first settles, for its own two terms, whether one of them leaves and what the exact step would then need of it (the
+// magnitude in front of it, the term, its base in the second column); one ballot names the lane and the reads from it are
+// independent of each other -- they used to be six reads by lane, each indexed by what the one before had fetched.
+__device__ __forceinline__ mclf_acc mclf_replay_table(const mclf_tab_elem (&e)[MCLF_ITEMS], int tkey, int n, const mclf_acc& c, int lane,
+                                                      unsigned int* phases, unsigned int* by_table)
 {
+    static_assert(MCLF_ITEMS == 2, "two rows per lane");
     double t[MCLF_ITEMS] = {e[0].t, e[1].t};
-    const int key = __builtin_amdgcn_readfirstlane(ss_key(acc));
-    tkey = __builtin_amdgcn_readfirstlane(tkey); n = __builtin_amdgcn_readfirstlane(n); head = __builtin_amdgcn_readfirstlane(head);
-    if (key == 0 || key != tkey || head > 0) return mclf_replay(t, n, 0, head, acc, lane, phases);
-    const int M = ss_mag(acc);
+    const int key = c.a.key, M = c.a.M;
+    if (key == 0 || key != tkey) return mclf_acc_of(mclf_replay(t, n, 0, 0, mclf_acc_float(c), lane, phases));
     int Mi[MCLF_ITEMS];
     bool out[MCLF_ITEMS];
 #pragma unroll
@@ -886,21 +901,23 @@ __device__ __forceinline__ float mclf_replay_table(const mclf_tab_elem (&e)[MCLF
         Mi[k] = M + (e[k].se >> 1);
         out[k] = i < n && ((e[k].se & 1) || Mi[k] <= SS_MLO || Mi[k] >= SS_MHI);
     }
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(out[0] || out[1]);
+    const int Mprev = mclf_dpp<0x138, 0xf>(M, Mi[1]);            // wave_shr:1 -- the magnitude in front of this lane's first term (lane 0: M)
+    const int Mb_l = out[0] ? Mprev : Mi[0];
+    const double t_l = out[0] ? t[0] : t[1];
+    const int se1_l = out[0] ? e[0].se1 : e[1].se1;
+    const unsigned long long mask0 = __builtin_amdgcn_ballot_w64(out[0]), mask = mask0 | __builtin_amdgcn_ballot_w64(out[1]);
     *by_table += 1;
-    if (!mask) return ss_from(key, __builtin_amdgcn_readlane(Mi[MCLF_ITEMS - 1], 63));       // it stayed inside after all
+    if (!mask) return mclf_acc_make(key, __builtin_amdgcn_readlane(Mi[MCLF_ITEMS - 1], 63));       // it stayed inside after all
     const int fl = __ffsll((long long)mask) - 1;
-    const int ek = __builtin_amdgcn_readlane(out[0] ? 1 : 0, fl) ? 0 : 1;
-    const int j = fl * MCLF_ITEMS + ek;
-    int Mb = M;
-    if (j > 0) Mb = ek ? __builtin_amdgcn_readlane(Mi[0], fl) : __builtin_amdgcn_readlane(Mi[1], fl - 1);
-    const double tj = mclf_readlane_f64(ek ? t[1] : t[0], fl);
-    const float acc1 = ss_exact_step(ss_from(key, Mb), tj);
-    const int key1 = __builtin_amdgcn_readfirstlane(ss_key(acc1));
-    if (key1 != key + 1 || (key & 0xff) >= 254) return mclf_replay(t, n, j + 1, 0, acc1, lane, phases);
+    const int j = fl * MCLF_ITEMS + (((mask0 >> fl) & 1ull) ? 0 : 1);
+    const int Mb = __builtin_amdgcn_readlane(Mb_l, fl);
+    const double tj = mclf_readlane_f64(t_l, fl);
+    const int base1 = __builtin_amdgcn_readlane(se1_l, fl) >> 1;
+    const float acc1 = ss_exact_step(ss_acc_float(mclf_acc_make(key, Mb).a), tj);
+    const mclf_acc c1 = mclf_acc_of(acc1);
+    if (c1.a.key != key + 1 || (key & 0xff) >= 254) return mclf_acc_of(mclf_replay(t, n, j + 1, 0, acc1, lane, phases));
     // the rest of the sub-tile in the next binade: prefix differences of the table's second column
-    const int M1 = ss_mag(acc1);
-    const int base1 = (ek ? __builtin_amdgcn_readlane(e[1].se1, fl) : __builtin_amdgcn_readlane(e[0].se1, fl)) >> 1;
+    const int M1 = c1.a.M;
     bool out1 = false;
     int last1 = 0;
 #pragma unroll
@@ -910,9 +927,13 @@ __device__ __forceinline__ float mclf_replay_table(const mclf_tab_elem (&e)[MCLF
         out1 |= i > j && i < n && ((e[k].se1 & 1) || m <= SS_MLO || m >= SS_MHI);
         last1 = m;
     }
-    if (__builtin_amdgcn_ballot_w64(out1)) return mclf_replay(t, n, j + 1, 0, acc1, lane, phases);
-    return ss_from(key1, __builtin_amdgcn_readlane(last1, 63));
+    if (__builtin_amdgcn_ballot_w64(out1)) return mclf_acc_of(mclf_replay(t, n, j + 1, 0, acc1, lane, phases));
+    return mclf_acc_make(key + 1, __builtin_amdgcn_readlane(last1, 63));
 }
+
+// LDS by its own address space, 16 bytes at a time (mclf_chain)
+typedef int mclf_v4i __attribute__((ext_vector_type(4)));
+#define MCLF_LDS_PTR(T) const __attribute__((address_space(3))) T*
 
 __device__ __forceinline__ int mclf_plain_key(int key) { return key == SS_ID ? SS_ID : (key & MCLF_KEY_MASK); }
 
@@ -1332,23 +1353,44 @@ __device__ __forceinline__ float mclf_chain(const mcl_finish_args& f, const mclf
     if (st && trees) { const mclf_trees tr = mclf_trees_at(*st); return mclf_walk_trees(f, tr, axis, S, done, nrec, first, lane, &stats[0], &stats[1], lds_terms); }
     if (!st || *st->nent > MCLF_MAXENT) return mclf_walk(f, axis, S, done, nrec, first, lane, &stats[0], &stats[1]);
     const int nent = __builtin_amdgcn_readfirstlane(*st->nent);
-    float acc = first;                                           // the first sub-tiles are done (mclf_pose)
+    // The accumulator travels as (key, M) from entry to entry (mclf_acc); a float is formed for the exact step, for the slow paths
+    // and at the end.  What an entry reads from LDS does not depend on the accumulator, so it is read one entry ahead: entry k + 1's
+    // step and its two table rows are requested in front of entry k's arithmetic and waited for where they are first used.  The
+    // rows' address needs the entry's table slot, which is therefore read two entries ahead.  All of these reads are unconditional
+    // and clamped: an entry past the end reads slot `nent` again, a table slot outside [0, ntab) reads table 0 (and the rows are
+    // not used).
+    // The stage is LDS whenever there is one (mclf_pose's scratch); read through generic pointers these were flat loads, which
+    // the compiler must take for lane-dependent.  As LDS reads by a wave-uniform address the step's words are uniform values.
+    // (the stage's address hangs on the wave's number, which the compiler takes for lane-dependent too: readfirstlane says it is not)
+    ntab = __builtin_amdgcn_readfirstlane(ntab);
+    const unsigned int step_at = (unsigned int)__builtin_amdgcn_readfirstlane((int)(size_t)(MCLF_LDS_PTR(char))st->step);
+    const unsigned int tab_at = (unsigned int)__builtin_amdgcn_readfirstlane((int)(size_t)(MCLF_LDS_PTR(char))st->tab);
+    MCLF_LDS_PTR(mclf_v4i) const steps = (MCLF_LDS_PTR(mclf_v4i))(size_t)step_at;       // entry k: words 2k (the gap), 2k + 1 (s, tslot, tkey, lo_n)
+    MCLF_LDS_PTR(int) const tslots = (MCLF_LDS_PTR(int))(size_t)step_at + 5;            // entry k's tslot: 8k words on
+    MCLF_LDS_PTR(mclf_v4i) const rows = (MCLF_LDS_PTR(mclf_v4i))(size_t)tab_at + 2 * lane;      // this lane's two rows of table 0
+    static_assert(sizeof(mclf_step) == 32 && sizeof(mclf_tab_elem) == 16, "the chain reads steps and table rows as 16-byte words");
+    const auto rows_of = [&](int tslot) { return rows + ((tslot >= 0 && tslot < ntab) ? tslot : 0) * MCLF_SUB; };
+    mclf_v4i sg = steps[0], se = steps[1];
+    int tslot2 = tslots[8 * min(1, nent)];                       // table slot of entry k + 1
+    mclf_v4i r0 = rows_of(se.y)[0], r1 = rows_of(se.y)[1];
+    mclf_acc acc = mclf_acc_of(first);                           // the first sub-tiles are done (mclf_pose)
     int prev = done - 1;                                         // last sub-tile done
     for (int k = 0; k <= nent; ++k) {
 #ifdef MCLF_STAMPS
         if (axis == 0 && k < 16 && lane == 0) f.state->cstamps[k] = MCLF_NOW();
 #endif
-        mclf_step sp = st->step[k];                              // wave-uniform LDS reads
-        sp.gap.key = __builtin_amdgcn_readfirstlane(sp.gap.key); sp.gap.D = __builtin_amdgcn_readfirstlane(sp.gap.D);
-        sp.gap.lo = __builtin_amdgcn_readfirstlane(sp.gap.lo); sp.gap.hi = __builtin_amdgcn_readfirstlane(sp.gap.hi);
-        sp.s = __builtin_amdgcn_readfirstlane(sp.s); sp.tslot = __builtin_amdgcn_readfirstlane(sp.tslot);
-        sp.tkey = __builtin_amdgcn_readfirstlane(sp.tkey); sp.lo_n = __builtin_amdgcn_readfirstlane(sp.lo_n);
+        const int k1 = min(k + 1, nent);
+        const mclf_v4i nsg = steps[2 * k1], nse = steps[2 * k1 + 1];
+        const int ntslot2 = tslots[8 * min(k + 2, nent)];
+        MCLF_LDS_PTR(mclf_v4i) const nrow = rows_of(tslot2);
+        const mclf_v4i nr0 = nrow[0], nr1 = nrow[1];
+        asm volatile("" ::: "memory");                           // (the requests stay here, in front of the entry's arithmetic)
+        mclf_step sp;
+        sp.gap = ss_rec_make(sg.x, sg.y, sg.z, sg.w); sp.s = se.x; sp.tslot = se.y; sp.tkey = se.z; sp.lo_n = se.w;
         // the gap in front of entry k (behind the last one for k == nent)
         if (sp.gap.key != SS_ID) {
-            const int key = __builtin_amdgcn_readfirstlane(ss_key(acc));
-            const int M = ss_mag(acc);
-            if (key != 0 && ss_rec_fits(sp.gap, key, M)) acc = ss_from(key, M + sp.gap.D);
-            else { acc = mclf_walk(f, axis, S, prev + 1, sp.s, acc, lane, &stats[0], &stats[1]); stats[3] += 1; }
+            if (acc.a.key != 0 && ss_rec_fits(sp.gap, acc.a.key, acc.a.M)) acc.a.M += sp.gap.D;
+            else { acc = mclf_acc_of(mclf_walk(f, axis, S, prev + 1, sp.s, mclf_acc_float(acc), lane, &stats[0], &stats[1])); stats[3] += 1; }
         }
         if (k == nent) break;
         // the risky sub-tile itself
@@ -1356,32 +1398,39 @@ __device__ __forceinline__ float mclf_chain(const mcl_finish_args& f, const mclf
             const int lo = sp.lo_n >> 8, n = (sp.lo_n & 0xff) + 1;
             bool by_map = false;
             if (sp.tslot <= -2) {                                    // a wild sub-tile: its map, if the accumulator fits
-                ss_wild wn = st->wmap[-2 - sp.tslot];                // (wave-uniform LDS read)
+                ss_wild wn = st->wmap[-2 - sp.tslot];                // (wave-uniform LDS read, where it is used: read ahead like the step it cost every entry more than it saved these)
                 wn = mclf_readlane_wild(wn, 0);
-                const int key = __builtin_amdgcn_readfirstlane(ss_key(acc));
-                const long long m = ssw_signed(key, ss_mag(acc));
-                if (key != 0 && ssw_fits(wn, key, m)) {
+                const long long m = ssw_signed(acc.a.key, acc.a.M);
+                if (acc.a.key != 0 && ssw_fits(wn, acc.a.key, m)) {
                     const long long mo = ssw_apply(wn, m);
-                    acc = ss_from(wn.key_out, (int)(mo < 0 ? -mo : mo));
+                    acc = mclf_acc_make(wn.key_out, (int)(mo < 0 ? -mo : mo));
                     stats[2] += 1;
                     by_map = true;
                 }
             }
             if (by_map) { }
             else if (sp.tslot >= 0 && sp.tslot < ntab) {
-                const mclf_tab_elem* row = st->tab + sp.tslot * MCLF_SUB + 2 * lane;
-                mclf_tab_elem el[MCLF_ITEMS] = {row[0], row[1]};
-                acc = mclf_replay_table(el, sp.tkey, n, 0, acc, lane, &stats[1], &stats[2]);
+                mclf_tab_elem el[MCLF_ITEMS];
+                el[0].t = __hiloint2double(r0.y, r0.x); el[0].se = r0.z; el[0].se1 = r0.w;
+                el[1].t = __hiloint2double(r1.y, r1.x); el[1].se = r1.z; el[1].se1 = r1.w;
+                acc = mclf_replay_table(el, sp.tkey, n, acc, lane, &stats[1], &stats[2]);
             } else {
                 double t[MCLF_ITEMS];
                 mclf_load_terms(f, axis, S, lo, lo + n, lane, t);
-                acc = mclf_replay(t, n, 0, sp.tslot <= -2 ? n : 0, acc, lane, &stats[1], lds_terms);      // (a wild one that does not fit: stepped)
+                acc = mclf_acc_of(mclf_replay(t, n, 0, sp.tslot <= -2 ? n : 0, mclf_acc_float(acc), lane, &stats[1], lds_terms));      // (a wild one that does not fit: stepped)
                 stats[0] += 1;
             }
         }
         prev = sp.s;
+        // (scalar from here on, and not before: a scalar copy made where the read is requested would wait for it there)
+#define MCLF_RFL(v) __builtin_amdgcn_readfirstlane(v)
+        sg = mclf_v4i{MCLF_RFL(nsg.x), MCLF_RFL(nsg.y), MCLF_RFL(nsg.z), MCLF_RFL(nsg.w)};
+        se = mclf_v4i{MCLF_RFL(nse.x), MCLF_RFL(nse.y), MCLF_RFL(nse.z), MCLF_RFL(nse.w)};
+        tslot2 = MCLF_RFL(ntslot2);
+#undef MCLF_RFL
+        r0 = nr0; r1 = nr1;
     }
-    return acc;
+    return mclf_acc_float(acc);
 }
 
 // The block sums in the fixed order of a 256-thread workgroup (thread-strided with a stride of 256, wave shuffles, waves in order)

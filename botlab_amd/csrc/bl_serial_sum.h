@@ -69,6 +69,17 @@ SS_HD float ss_from(int key, int M)                // 2^23 <= M <= 2^24 (M = 2^2
     return (key & 0x200) ? -mag : mag;
 }
 
+// The accumulator as the integer pair it is inside a binade: key 0 = no usable binade (the float is authoritative), else
+// 2^23 <= M <= 2^24 as in ss_from.  ss_acc_float puts the float together from its bits -- sign, exponent field, the 23 low bits
+// of M -- and gives ss_from's value for every such pair: M = 2^24 carries into the exponent field (the next binade's first value,
+// fraction zero; from exponent field 254 the bits of infinity, as ldexpf rounds it).
+struct ss_acc { int key, M; };
+SS_HD ss_acc ss_acc_of(float v) { ss_acc a; a.key = ss_key(v); a.M = ss_mag(v); return a; }
+SS_HD float ss_acc_float(const ss_acc& a)
+{
+    return ss_u2f(((uint32_t)(a.key & 0x200) << 22) | ((((uint32_t)(a.key & 0xff)) << 23) + ((uint32_t)a.M - (uint32_t)SS_MLO)));
+}
+
 // What the in-binade step needs of the binade: computed once per key.
 struct ss_bin { double lim, C; int down; int neg; };
 SS_HD ss_bin ss_bin_of(int key)
