@@ -197,10 +197,6 @@ int bl_timer_commit(bl_ctx* ctx, int id, hipEvent_t a, hipEvent_t b);
 int bl_scan_upload(bl_ctx* ctx, const bl_lidar_t* scan, int* num_rays);
 void bl_scan_free(bl_ctx* ctx);
 
-// interpolateRatio of interpolate_pose_by_time (src/common/interpolation.hpp:35) for a ray stamped t and the pose pair
-// (begin, end), den = (double)(end - begin)
-__host__ __device__ inline double bl_interp_ratio(int64_t t, int64_t begin, double den) { return (double)(t - begin) / den; }
-
 // bl_mcl.hip: the in-place install of weight units computed on the device (the beam model's bl_beam_reweigh_pf), see there
 int bl_pf_install_units(bl_pf* pf, struct bl_ctx* ctx, int (*write)(void* user, float4* rec, int n), void* user, bl_pose_xyt_t* out_pose);
 

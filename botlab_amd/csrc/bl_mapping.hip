@@ -17,12 +17,12 @@
 #include <stdio.h>
 
 #include "bl_internal.h"
+#include "bl_mapray_dev.h"
 #include "bl_mcl_finish.h"
 
 #define MAP_THREADS 1024
 #define MAP_LDS_COUNTERS (72 * 1024)         // uint16 counters -> 144 KB of the 160 KB LDS
 #define MAP_MAX_RAYS 8192
-#define MAP_CELL_LIMIT (1 << 24)             // |cell coordinate| bound for a ray to be traced (rejects NaN/inf geometry)
 
 struct bl_mapping {
     bl_ctx* ctx;
@@ -88,15 +88,8 @@ __device__ __forceinline__ bool cell_in_grid(const bl_frame& f, int x, int y)
     return x >= 0 && x < f.width && y >= 0 && y < f.height;
 }
 
-// Cell k (k = 0 .. K-1, K = max(dx, dy); start cell included, end cell excluded) of the reference's Bresenham walk
-// (mapping.cpp:101-127: e2 = 2*err; if (e2 >= -dy) {err -= dy; x += sx;} if (e2 <= dx) {err += dx; y += sy;}) has a closed
-// form: the major axis advances k, the minor axis floor((2*k*dmin + dmaj) / (2*dmaj)).  Checked against the loop for every
-// dx, dy < 230 and all sign combinations (tests/tools/bresenham_closed_form.py), so the walk of one ray can be cut
-// into independent segments.
-#define MAP_SEG 16                            // cells per walk segment
+#define MAP_SEG 16                            // cells per walk segment (the walk from any step k0: bl_mapray_dev.h)
 #define MAP_SEG_RAYS 1024                     // rays whose segment table fits the static LDS array (more rays: serial walk per ray)
-
-__device__ __forceinline__ unsigned int half_of(unsigned int pair, int ci) { return (ci & 1) ? (pair >> 16) : (pair & 0xffffu); }
 
 // snap != nullptr: every store to the grid is mirrored into the replanner snapshot, whose bulk copy (the grid as it was when
 // the kernel started) the caller holds in sv[] and map_update_body stores once its first loads are under way.
@@ -184,45 +177,6 @@ __global__ __launch_bounds__(MAP_THREADS) void k_map_update(map_args a)
     }
 }
 
-// start cell and end cell of one ray (moving_laser_scan.cpp:22-37, mapping.cpp:45-49); x == 0x7fffffff: the ray takes no part
-// It comes in two parts.  What depends on the poses' THETA alone -- the interpolated theta does not depend on x or y --: the
-// ray's reach in cells along both axes (wrap, sine and cosine, two products each).  And what depends on their POSITION.  A map
-// update that ran ahead of the filter's exact x, y checks its cells with the second part alone: theta was final all along.
-struct map_ray_reach { float ex, ey; double ratio; bool on; };
-__device__ __forceinline__ map_ray_reach map_ray_angle(const map_args& a, const bl_pose3& pb, const bl_pose3& pe, float range, float ray_theta, int64_t ray_time)
-{
-    map_ray_reach d = {0.0f, 0.0f, 0.0, range <= a.max_laser};  // rays with range <= 0.15f were dropped on the host
-    if (d.on) {
-        if (a.interp) d.ratio = bl_interp_ratio(ray_time, a.t_begin, a.t_den);
-        const float rp_theta = a.interp ? bl_interpolate_pose(pb, pe, d.ratio).theta : pe.theta;
-        float theta = bl_wrap_to_pi(rp_theta - ray_theta);
-        float sn, cs;
-        bl_sincosf(theta, &sn, &cs);
-        d.ex = range * cs * a.frame.cpm;
-        d.ey = range * sn * a.frame.cpm;
-    }
-    return d;
-}
-__device__ __forceinline__ int4 map_ray_place(const map_args& a, const bl_pose3& pb, const bl_pose3& pe, const map_ray_reach& d)
-{
-    int4 ray = make_int4(0x7fffffff, 0, 0, 0);
-    if (d.on) {
-        const bl_pose3 rp = a.interp ? bl_interpolate_pose(pb, pe, d.ratio) : pe;
-        float sx, sy;
-        bl_global_to_grid(rp.x, rp.y, a.frame, &sx, &sy);
-        float fx = d.ex + sx;
-        float fy = d.ey + sy;
-        const float lim = (float)MAP_CELL_LIMIT;
-        if (fx > -lim && fx < lim && fy > -lim && fy < lim && sx > -lim && sx < lim && sy > -lim && sy < lim)
-            ray = make_int4((int)sx, (int)sy, (int)fx, (int)fy);        // float -> int truncation at the bresenham() call
-    }
-    return ray;
-}
-__device__ __forceinline__ int4 map_ray_cells(const map_args& a, const bl_pose3& pb, const bl_pose3& pe, float range, float ray_theta, int64_t ray_time)
-{
-    return map_ray_place(a, pb, pe, map_ray_angle(a, pb, pe, range, ray_theta, ray_time));
-}
-
 // lds_pose: the pose of this update in shared memory (or null: a.cur_dev / a.cur_host).  provisional: its x, y are the map
 // workgroup's own double reduction; the reference's x, y come from the finisher (mclf_wait_pose) -- everything up to the first
 // grid store runs with the provisional pose, then the rays' integer cells are recomputed with the exact one and compared.
@@ -259,7 +213,7 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
         bl_pose_xyt_t prev = a.apply ? *a.prev : cur;          // mapping.cpp:19-21: first call uses pose for both
         s_pose[0] = prev.x; s_pose[1] = prev.y; s_pose[2] = prev.theta;
         s_pose[3] = cur.x; s_pose[4] = cur.y; s_pose[5] = cur.theta;
-        s_box[0] = 0x7fffffff; s_box[1] = 0x7fffffff; s_box[2] = -0x7fffffff; s_box[3] = -0x7fffffff;
+        s_box[0] = BL_NO_RAY; s_box[1] = BL_NO_RAY; s_box[2] = -BL_NO_RAY; s_box[3] = -BL_NO_RAY;
         s_redo = 0;
         s_dirty[0] = 1; s_dirty[1] = 1; s_dirty[2] = 0; s_dirty[3] = 0;      // empty
     }
@@ -272,38 +226,23 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
 
     MSTAMP(1);
     // ---- phase A: ray geometry (moving_laser_scan.cpp:22-37, mapping.cpp:45-49)
-    int bx_lo = 0x7fffffff, by_lo = 0x7fffffff, bx_hi = -0x7fffffff, by_hi = -0x7fffffff;
-    int4 my_ray = make_int4(0x7fffffff, 0, 0, 0);
-    map_ray_reach my_reach = {0.0f, 0.0f, 0.0, false};          // of this thread's first ray (the one a look-ahead checks again)
+    bl_box box = bl_box_none();
+    int4 my_ray = make_int4(BL_NO_RAY, 0, 0, 0);
+    bl_ray_reach my_reach = {0.0f, 0.0f, 0.0, false};           // of this thread's first ray (the one a look-ahead checks again)
     for (int r = tid; r < a.R; r += MAP_THREADS) {
         const bool first = r == tid;
-        const map_ray_reach reach = map_ray_angle(a, pb, pe, first ? pre_range : a.ranges[r], first ? pre_theta : a.thetas[r],
-                                                  a.interp ? (first ? pre_time : a.times[r]) : 0);
+        const bl_ray_reach reach = bl_ray_angle(a.frame, a.max_laser, a.interp != 0, a.t_begin, a.t_den, pb, pe, first ? pre_range : a.ranges[r],
+                                                first ? pre_theta : a.thetas[r], a.interp ? (first ? pre_time : a.times[r]) : 0);
         if (first) my_reach = reach;
-        const int4 ray = map_ray_place(a, pb, pe, reach);
-        if (ray.x != 0x7fffffff) {
-            bx_lo = min(bx_lo, min(ray.x, ray.z)); by_lo = min(by_lo, min(ray.y, ray.w));
-            bx_hi = max(bx_hi, max(ray.x, ray.z)); by_hi = max(by_hi, max(ray.y, ray.w));
-        }
+        const int4 ray = bl_ray_place(a.frame, a.interp != 0, pb, pe, reach);
+        bl_box_add(box, ray);
         a.rays[r] = ray;
         my_ray = ray;
     }
-    // one LDS atomic per wave and bound (290 lanes hammering four words serialised this phase)
-    for (int off = 32; off > 0; off >>= 1) {
-        bx_lo = min(bx_lo, __shfl_xor(bx_lo, off, 64)); by_lo = min(by_lo, __shfl_xor(by_lo, off, 64));
-        bx_hi = max(bx_hi, __shfl_xor(bx_hi, off, 64)); by_hi = max(by_hi, __shfl_xor(by_hi, off, 64));
-    }
-    if ((tid & 63) == 0 && bx_lo != 0x7fffffff) {
-        atomicMin(&s_box[0], bx_lo); atomicMin(&s_box[1], by_lo);
-        atomicMax(&s_box[2], bx_hi); atomicMax(&s_box[3], by_hi);
-    }
+    bl_box_to_lds(box, s_box);
     // segment table: ray r contributes ceil(K / MAP_SEG) segments, K = max(dx, dy)
     if (seg_walk) {
-        int segs = 0;
-        if (tid < a.R && my_ray.x != 0x7fffffff) {
-            const int K = max(abs(my_ray.z - my_ray.x), abs(my_ray.w - my_ray.y));
-            segs = (K + MAP_SEG - 1) / MAP_SEG;
-        }
+        const int segs = bl_ray_segs(my_ray, MAP_SEG);          // (a thread without a ray holds BL_NO_RAY)
         int incl = segs;
         for (int off = 1; off < 64; off <<= 1) {
             int t = __shfl_up(incl, off, 64);
@@ -354,6 +293,9 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
     for (int sy0 = by0; sy0 <= by1; sy0 += rows_per_strip) {
         const int sy1 = min(sy0 + rows_per_strip - 1, by1);
         const int ncell = (sy1 - sy0 + 1) * ww;
+        auto count_miss = [&](int x, int y) {                   // M of a crossed cell (the window is already clipped to the grid)
+            if (x >= bx0 && x <= bx1 && y >= sy0 && y <= sy1) bl_cnt_add(s_cnt, (y - sy0) * ww + (x - bx0));
+        };
         for (int i = tid; i < (ncell + 1) / 2; i += MAP_THREADS) s_cnt[i] = 0;
         __syncthreads();
         // ---- phase B: endpoint pass (mapping.cpp:42-57).  H = rays ending in a cell; the ray whose increment found the
@@ -365,17 +307,16 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
             bool leader = false;
             if (r < a.R) {
                 const int4 me = seg_walk ? my_ray : a.rays[r];
-                if (me.x != 0x7fffffff && me.z >= bx0 && me.z <= bx1 && me.w >= sy0 && me.w <= sy1) {   // window = clipped grid
+                if (me.x != BL_NO_RAY && me.z >= bx0 && me.z <= bx1 && me.w >= sy0 && me.w <= sy1) {   // window = clipped grid
                     ci = (me.w - sy0) * ww + (me.z - bx0);
-                    const unsigned int old = atomicAdd(&s_cnt[ci >> 1], (ci & 1) ? 0x10000u : 1u);
-                    leader = half_of(old, ci) == 0u;
+                    leader = bl_cnt_half(bl_cnt_add(s_cnt, ci), ci) == 0u;
                 }
             }
             __syncthreads();
             int H = 0, idx_y = 0;
             size_t idx = 0;
             if (leader) {
-                H = (int)half_of(s_cnt[ci >> 1], ci);
+                H = bl_cnt_of(s_cnt, ci);
                 const int4 me = seg_walk ? my_ray : a.rays[r];
                 idx = (size_t)me.w * a.frame.width + me.z;
                 idx_y = me.w;
@@ -389,7 +330,7 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
                     a.cells[idx] = (int8_t)min(127, v + a.hit * H);
                     if (a.mirror) a.mirror[mirror_at(a, idx, idx_y)] = a.cells[idx];
                 }
-                if (ci >= 0) atomicAnd(&s_cnt[ci >> 1], (ci & 1) ? 0x0000ffffu : 0xffff0000u);
+                if (ci >= 0) bl_cnt_clear(s_cnt, ci);
                 __syncthreads();
                 continue;
             }
@@ -399,28 +340,9 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
             MSTAMP(4);
             const int nseg = s_segp[a.R];
             for (int sg = tid; sg < nseg; sg += MAP_THREADS) {
-                int lo = 0, hi = a.R - 1;                       // last ray whose prefix <= sg
-                while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_segp[mid] <= sg) lo = mid; else hi = mid - 1; }
-                const int4 ray = a.rays[lo];
-                const int k0 = (sg - s_segp[lo]) * MAP_SEG;
-                const int dx = abs(ray.z - ray.x), dy = abs(ray.w - ray.y);
-                const int sx = ray.x < ray.z ? 1 : -1, sy = ray.y < ray.w ? 1 : -1;
-                const int K = max(dx, dy), k1 = min(K, k0 + MAP_SEG);
-                const bool xmajor = dx >= dy;
-                const int dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
-                const long long num = 2ll * k0 * dmin + dmaj;
-                int n = (int)(num / (2ll * dmaj));
-                int rem = (int)(num - (long long)n * 2ll * dmaj);
-                for (int k = k0; k < k1; ++k) {
-                    const int x = xmajor ? ray.x + sx * k : ray.x + sx * n;
-                    const int y = xmajor ? ray.y + sy * n : ray.y + sy * k;
-                    if (x >= bx0 && x <= bx1 && y >= sy0 && y <= sy1) {   // window is already clipped to the grid
-                        const int c = (y - sy0) * ww + (x - bx0);
-                        atomicAdd(&s_cnt[c >> 1], (c & 1) ? 0x10000u : 1u);
-                    }
-                    rem += 2 * dmin;
-                    if (rem >= 2 * dmaj) { rem -= 2 * dmaj; n += 1; }
-                }
+                const int r = bl_seg_ray(s_segp, a.R, sg);
+                const int k0 = (sg - s_segp[r]) * MAP_SEG;
+                bl_walk_range(a.rays[r], k0, k0 + MAP_SEG, count_miss);
             }
             __syncthreads();
             MSTAMP(5);
@@ -431,7 +353,7 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
                 XSTAMP(11);
                 const bl_pose3 pe2 = {lds_pose->x, lds_pose->y, pe.theta};
                 if (tid < a.R) {
-                    const int4 ray2 = map_ray_place(a, pb, pe2, my_reach);       // (pe2.theta == pe.theta: the angle part stands)
+                    const int4 ray2 = bl_ray_place(a.frame, a.interp != 0, pb, pe2, my_reach);      // (pe2.theta == pe.theta: the angle part stands)
                     if (ray2.x != my_ray.x || ray2.y != my_ray.y || ray2.z != my_ray.z || ray2.w != my_ray.w) atomicOr(&s_redo, 1);
                 }
                 __syncthreads();
@@ -441,36 +363,21 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
             }
             // leaders finish their end cell: v' = max(-128, min(127, v + hit*H) - miss*M), then hide it from the window pass
             if (leader) {
-                const int M = (int)half_of(s_cnt[ci >> 1], ci);
+                const int M = bl_cnt_of(s_cnt, ci);
                 int v = a.cells[idx];
                 v = max(-128, min(127, v + a.hit * H) - a.miss * M);
                 a.cells[idx] = (int8_t)v;
                 if (snap) snap[idx] = (int8_t)v;
                 if (a.mirror) a.mirror[mirror_at(a, idx, idx_y)] = (int8_t)v;
-                atomicAnd(&s_cnt[ci >> 1], (ci & 1) ? 0x0000ffffu : 0xffff0000u);
+                bl_cnt_clear(s_cnt, ci);
             }
             __syncthreads();
         }
         if (a.R > MAP_THREADS) {
-            // serial walk per ray (the pre-segment form), all hits already applied
+            // serial walk per ray, all hits already applied
             for (int r = tid; r < a.R; r += MAP_THREADS) {
-                int4 ray = a.rays[r];
-                if (ray.x == 0x7fffffff) continue;
-                int x = ray.x, y = ray.y;
-                const int x2 = ray.z, y2 = ray.w;
-                const int dx = abs(x2 - x), dy = abs(y2 - y);
-                const int sx = x < x2 ? 1 : -1, sy = y < y2 ? 1 : -1;
-                int err = dx - dy;
-                int guard = dx + dy + 2;
-                while ((x != x2 || y != y2) && guard-- > 0) {
-                    if (x >= bx0 && x <= bx1 && y >= sy0 && y <= sy1) {
-                        int c = (y - sy0) * ww + (x - bx0);
-                        atomicAdd(&s_cnt[c >> 1], (c & 1) ? 0x10000u : 1u);
-                    }
-                    int e2 = 2 * err;
-                    if (e2 >= -dy) { err -= dy; x += sx; }
-                    if (e2 <= dx) { err += dx; y += sy; }
-                }
+                const int4 ray = a.rays[r];
+                if (ray.x != BL_NO_RAY) bl_walk_range(ray, 0, bl_ray_steps(ray), count_miss);
             }
             __syncthreads();
         }
@@ -504,13 +411,7 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
                     if (c[u]) {
-                        unsigned int nv = 0;
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) {
-                            const int M = (int)((c[u] >> (16 * b)) & 0xffffull);
-                            const int val = (int)(int8_t)(v[u] >> (8 * b));
-                            nv |= ((unsigned int)max(-128, val - a.miss * M) & 0xffu) << (8 * b);
-                        }
+                        const unsigned int nv = bl_apply4<false>(c[u], v[u], a.miss);
                         *(int*)(a.cells + gi[u]) = (int)nv;
                         if (snap) *(int*)(snap + gi[u]) = (int)nv;
                         if (a.mirror) *(int*)(a.mirror + mirror_at(a, gi[u], gy[u])) = (int)nv;
@@ -526,7 +427,7 @@ __device__ __forceinline__ void map_update_body(const map_args& a, int8_t* snap,
                     M[u] = 0;
                     if (ry < nrows) {
                         const int ci2 = ry * ww + cx;
-                        M[u] = (int)half_of(s_cnt[ci2 >> 1], ci2);
+                        M[u] = bl_cnt_of(s_cnt, ci2);
                     }
                 }
 #pragma unroll

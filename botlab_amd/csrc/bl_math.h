@@ -148,6 +148,10 @@ BL_HD bl_pose3 bl_interpolate_pose(bl_pose3 before, bl_pose3 after, double ratio
     return out;
 }
 
+// interpolateRatio of interpolate_pose_by_time (src/common/interpolation.hpp:35) for a ray stamped t and the pose pair
+// (begin, end), den = (double)(end - begin)
+BL_HD double bl_interp_ratio(int64_t t, int64_t begin, double den) { return (double)(t - begin) / den; }
+
 // ---------------------------------------------------------------- grid frame
 struct bl_frame { int width, height; float mpc, cpm, ox, oy; };
 

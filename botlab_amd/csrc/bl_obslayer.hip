@@ -4,7 +4,7 @@
 //
 //   k_obs_rays     a wave per ray of the scan.  The ray's geometry is the scan matcher's (k_sm_raster at heading step 0), formed by
 //                  every lane alike.  Phase 1: the lanes take the cells of the walk 64 at a time (closed form of the reference's
-//                  Bresenham variant, bl_mapping.hip) and a ballot finds `first`, the least occupied one; the tol box around the end
+//                  Bresenham variant, bl_mapray_dev.h) and a ballot finds `first`, the least occupied one; the tol box around the end
 //                  cell, clipped to the grid, is spread over the lanes the same way.  Phase 2, once the class is known: the cells
 //                  k < first get the update's number n stored into the clear stamps, the end cell of a NOVEL ray into the hit
 //                  stamps.  Plain stores of one value from any number of waves: a set without atomics and without a memset.
@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "bl_internal.h"
+#include "bl_mapray_dev.h"
 #include "bl_obslayer_dev.h"
 
 #define OBS_MIN_RANGE 0.15f               // moving_laser_scan.cpp:24, as the scan matcher
@@ -30,19 +31,6 @@
 #define OBS_NOVEL 2
 #define OBS_THROUGH 3
 #define OBS_OUTSIDE 4
-
-// cell k of the walk from (sx, sy) towards (ex, ey): bl_mapping.hip's closed form
-struct obs_walk { int sx, sy, stepx, stepy, dx, dy; };
-__device__ __forceinline__ void obs_walk_cell(const obs_walk& w, int k, int* x, int* y)
-{
-    if (w.dx >= w.dy) {
-        *x = w.sx + w.stepx * k;
-        *y = w.sy + w.stepy * (int)((2u * (unsigned int)k * (unsigned int)w.dy + (unsigned int)w.dx) / (2u * (unsigned int)w.dx));
-    } else {
-        *x = w.sx + w.stepx * (int)((2u * (unsigned int)k * (unsigned int)w.dx + (unsigned int)w.dy) / (2u * (unsigned int)w.dy));
-        *y = w.sy + w.stepy * k;
-    }
-}
 
 __global__ __launch_bounds__(64 * OBS_RAY_WAVES) void k_obs_rays(const int8_t* __restrict__ cells, bl_frame f, const float* __restrict__ ranges,
                                                                  const float* __restrict__ thetas, int R, float px, float py, float ptheta,
@@ -67,11 +55,8 @@ __global__ __launch_bounds__(64 * OBS_RAY_WAVES) void k_obs_rays(const int8_t* _
         if (__builtin_fabsf(fx) < 0x1p30f && __builtin_fabsf(fy) < 0x1p30f) {
             const int W = f.width, H = f.height;
             const int ex = (int)fx, ey = (int)fy;
-            obs_walk w;
-            w.sx = (int)fsx; w.sy = (int)fsy;
-            w.dx = abs(ex - w.sx); w.dy = abs(ey - w.sy);
-            w.stepx = w.sx < ex ? 1 : -1; w.stepy = w.sy < ey ? 1 : -1;
-            const int K = max(w.dx, w.dy);
+            const int4 ray = make_int4((int)fsx, (int)fsy, ex, ey);
+            const int K = bl_ray_steps(ray);
             // ---- phase 1: first, the least k whose cell is inside the grid and occupied
             int first = K;
             for (int base = 0; base < K; base += 64) {
@@ -79,7 +64,7 @@ __global__ __launch_bounds__(64 * OBS_RAY_WAVES) void k_obs_rays(const int8_t* _
                 bool occ = false;
                 if (k < K) {
                     int x, y;
-                    obs_walk_cell(w, k, &x, &y);
+                    bl_walk_cell(ray, k, &x, &y);
                     if (x >= 0 && x < W && y >= 0 && y < H) occ = cells[(size_t)y * W + x] >= occ_min;
                 }
                 const unsigned long long m = __ballot(occ);
@@ -106,7 +91,7 @@ __global__ __launch_bounds__(64 * OBS_RAY_WAVES) void k_obs_rays(const int8_t* _
             if (cls != OBS_THROUGH) {
                 for (int k = lane; k < first; k += 64) {
                     int x, y;
-                    obs_walk_cell(w, k, &x, &y);
+                    bl_walk_cell(ray, k, &x, &y);
                     if (x >= 0 && x < W && y >= 0 && y < H) clr[(size_t)y * W + x] = n;
                 }
             }

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "bl_internal.h"
+#include "bl_mapray_dev.h"
 
 #define RB_MAX_PARTICLES 4096
 #define RB_PLAN_THREADS 1024
@@ -28,7 +29,6 @@
 #define RB_MAP_SEG 16                        // cells per walk segment
 #define RB_MAP_SEG_RAYS 512                  // rays whose cells and segment table are kept in LDS (longer scans: a serial walk per ray)
 #define RB_MAP_MAX_RAYS 8192
-#define RB_CELL_LIMIT (1 << 24)              // |cell coordinate| bound for a ray to be traced (rejects NaN / inf geometry)
 #define RB_COPY_THREADS 256
 #define RB_COPY_VEC 4                        // int4 per thread and item: 16 KB per workgroup item
 #define RB_SCORE_SAT (1ll << 33)             // BL_RBSLAM_SCORE_MAX (botlab_hip.h)
@@ -441,48 +441,10 @@ struct rb_map_args {
     float max_laser; int hit, miss;
 };
 
-// start cell and end cell of one ray (moving_laser_scan.cpp:22-37, mapping.cpp:45-49); x == 0x7fffffff: the ray takes no part
-__device__ __forceinline__ int4 rb_ray_cells(const rb_map_args& a, const bl_pose3& pb, const bl_pose3& pe, int r)
+// start cell and end cell of ray r (bl_mapray_dev.h)
+__device__ __forceinline__ int4 rb_ray_of(const rb_map_args& a, const bl_pose3& pb, const bl_pose3& pe, int r)
 {
-    int4 ray = make_int4(0x7fffffff, 0, 0, 0);
-    const float range = a.ranges[r];
-    if (range <= a.max_laser) {
-        const bl_pose3 rp = a.interp ? bl_interpolate_pose(pb, pe, bl_interp_ratio(a.times[r], a.t_begin, a.t_den)) : pe;
-        const float theta = bl_wrap_to_pi(rp.theta - a.thetas[r]);
-        float sn, cs, sx, sy;
-        bl_sincosf(theta, &sn, &cs);
-        bl_global_to_grid(rp.x, rp.y, a.frame, &sx, &sy);
-        const float fx = (range * cs * a.frame.cpm) + sx;
-        const float fy = (range * sn * a.frame.cpm) + sy;
-        const float lim = (float)RB_CELL_LIMIT;
-        if (fx > -lim && fx < lim && fy > -lim && fy < lim && sx > -lim && sx < lim && sy > -lim && sy < lim)
-            ray = make_int4((int)sx, (int)sy, (int)fx, (int)fy);
-    }
-    return ray;
-}
-
-__device__ __forceinline__ void rb_count(unsigned int* s_cnt, int c) { atomicAdd(&s_cnt[c >> 1], (c & 1) ? 0x10000u : 1u); }
-__device__ __forceinline__ int rb_count_of(const unsigned int* s_cnt, int c) { const unsigned int w = s_cnt[c >> 1]; return (int)((c & 1) ? (w >> 16) : (w & 0xffffu)); }
-
-// cells k0 .. k1 - 1 of the reference's Bresenham walk of `ray` (start included, end excluded; the closed form of bl_mapping.hip:
-// the major axis advances k, the minor axis floor((2 k dmin + dmaj) / (2 dmaj))), counted where they fall into the tile
-__device__ __forceinline__ void rb_walk(unsigned int* s_cnt, const int4 ray, int k0, int k1, int tx0, int ty0, int tx1, int ty1, int tw)
-{
-    const int dx = abs(ray.z - ray.x), dy = abs(ray.w - ray.y);
-    const int sx = ray.x < ray.z ? 1 : -1, sy = ray.y < ray.w ? 1 : -1;
-    const bool xmajor = dx >= dy;
-    const int dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
-    if (dmaj == 0) return;
-    const long long num = 2ll * k0 * dmin + dmaj;
-    int n = (int)(num / (2ll * dmaj));
-    long long rem = num - (long long)n * 2ll * dmaj;
-    for (int k = k0; k < k1; ++k) {
-        const int x = xmajor ? ray.x + sx * k : ray.x + sx * n;
-        const int y = xmajor ? ray.y + sy * n : ray.y + sy * k;
-        if (x >= tx0 && x <= tx1 && y >= ty0 && y <= ty1) rb_count(s_cnt, (y - ty0) * tw + (x - tx0));
-        rem += 2ll * dmin;
-        if (rem >= 2ll * dmaj) { rem -= 2ll * dmaj; n += 1; }
-    }
+    return bl_ray_cells(a.frame, a.max_laser, a.interp != 0, a.t_begin, a.t_den, pb, pe, a.ranges[r], a.thetas[r], a.interp ? a.times[r] : 0);
 }
 
 // One owner thread per cell of the tile: v' = HIT ? min(127, v + k c) : max(-128, v - k c) where the count c is not zero.
@@ -497,20 +459,11 @@ __device__ __forceinline__ void rb_apply(int8_t* cells, int W, const unsigned in
             const unsigned long long c = *(const unsigned long long*)&s_cnt[(ry * tw + 4 * dq) >> 1];
             if (!c) continue;
             int* g = (int*)(cells + (size_t)(ty0 + ry) * W + tx0 + 4 * dq);
-            const int v = *g;
-            unsigned int nv = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int cnt = (int)((c >> (16 * b)) & 0xffffull);
-                const int val = (int)(int8_t)(v >> (8 * b));
-                const int r = HIT ? min(127, val + k * cnt) : max(-128, val - k * cnt);
-                nv |= ((unsigned int)r & 0xffu) << (8 * b);
-            }
-            *g = (int)nv;
+            *g = (int)bl_apply4<HIT>(c, *g, k);
         }
     } else {
         for (int it = tid; it < tw * th; it += RB_MAP_THREADS) {
-            const int cnt = rb_count_of(s_cnt, it);
+            const int cnt = bl_cnt_of(s_cnt, it);
             if (!cnt) continue;
             const int ry = it / tw, cx = it - ry * tw;
             int8_t* g = cells + (size_t)(ty0 + ry) * W + tx0 + cx;
@@ -531,35 +484,25 @@ __global__ __launch_bounds__(RB_MAP_THREADS) void k_rb_map(rb_map_args a)
     __shared__ int s_segp[RB_MAP_SEG_RAYS + 1];
     __shared__ int s_wsum[RB_MAP_THREADS / 64];
     __shared__ int s_box[4];
-    const int tid = threadIdx.x, lane = tid & 63, p = blockIdx.x;
+    const int tid = threadIdx.x, p = blockIdx.x;
     const bool seg_walk = a.R <= RB_MAP_SEG_RAYS;
     int8_t* cells = a.maps + (size_t)a.slot[p] * a.stride;
     const float4 b4 = a.begin[p], e4 = a.end[p];
     const bl_pose3 pb = {b4.x, b4.y, b4.z}, pe = {e4.x, e4.y, e4.z};
-    if (tid == 0) { s_box[0] = 0x7fffffff; s_box[1] = 0x7fffffff; s_box[2] = -0x7fffffff; s_box[3] = -0x7fffffff; }
+    if (tid == 0) { s_box[0] = BL_NO_RAY; s_box[1] = BL_NO_RAY; s_box[2] = -BL_NO_RAY; s_box[3] = -BL_NO_RAY; }
     __syncthreads();
     // ---- ray geometry, bounding box, segment table
-    int bx_lo = 0x7fffffff, by_lo = 0x7fffffff, bx_hi = -0x7fffffff, by_hi = -0x7fffffff;
+    bl_box box = bl_box_none();
     int segs = 0;
     for (int r = tid; r < a.R; r += RB_MAP_THREADS) {
-        const int4 ray = rb_ray_cells(a, pb, pe, r);
-        if (ray.x != 0x7fffffff) {
-            bx_lo = min(bx_lo, min(ray.x, ray.z)); by_lo = min(by_lo, min(ray.y, ray.w));
-            bx_hi = max(bx_hi, max(ray.x, ray.z)); by_hi = max(by_hi, max(ray.y, ray.w));
-        }
+        const int4 ray = rb_ray_of(a, pb, pe, r);
+        bl_box_add(box, ray);
         if (seg_walk) {
             s_rays[r] = ray;
-            if (ray.x != 0x7fffffff) segs = (max(abs(ray.z - ray.x), abs(ray.w - ray.y)) + RB_MAP_SEG - 1) / RB_MAP_SEG;
+            segs = bl_ray_segs(ray, RB_MAP_SEG);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        bx_lo = min(bx_lo, __shfl_xor(bx_lo, off, 64)); by_lo = min(by_lo, __shfl_xor(by_lo, off, 64));
-        bx_hi = max(bx_hi, __shfl_xor(bx_hi, off, 64)); by_hi = max(by_hi, __shfl_xor(by_hi, off, 64));
-    }
-    if (lane == 0 && bx_lo != 0x7fffffff) {
-        atomicMin(&s_box[0], bx_lo); atomicMin(&s_box[1], by_lo);
-        atomicMax(&s_box[2], bx_hi); atomicMax(&s_box[3], by_hi);
-    }
+    bl_box_to_lds(box, s_box);
     if (seg_walk) {                                             // thread r holds ray r's segment count (R <= 512 threads)
         int total;
         const int excl = rb_block_excl_scan(segs, s_wsum, &total);
@@ -586,10 +529,13 @@ __global__ __launch_bounds__(RB_MAP_THREADS) void k_rb_map(rb_map_args a)
         __syncthreads();
         for (int i = tid; i < nwords; i += RB_MAP_THREADS) s_cnt[i] = 0;
         __syncthreads();
+        auto count = [&](int x, int y) {                        // a cell of a ray, counted where it falls into the tile
+            if (x >= tx0 && x <= tx1 && y >= ty0 && y <= ty1) bl_cnt_add(s_cnt, (y - ty0) * tw + (x - tx0));
+        };
         // ---- endpoint pass (mapping.cpp:42-57): H = rays ending in a cell
         for (int r = tid; r < a.R; r += RB_MAP_THREADS) {
-            const int4 ray = seg_walk ? s_rays[r] : rb_ray_cells(a, pb, pe, r);
-            if (ray.x != 0x7fffffff && ray.z >= tx0 && ray.z <= tx1 && ray.w >= ty0 && ray.w <= ty1) rb_count(s_cnt, (ray.w - ty0) * tw + (ray.z - tx0));
+            const int4 ray = seg_walk ? s_rays[r] : rb_ray_of(a, pb, pe, r);
+            if (ray.x != BL_NO_RAY) count(ray.z, ray.w);
         }
         __syncthreads();
         rb_apply<true>(cells, W, s_cnt, tx0, ty0, tw, th, a.hit, dwords);
@@ -600,18 +546,14 @@ __global__ __launch_bounds__(RB_MAP_THREADS) void k_rb_map(rb_map_args a)
         if (seg_walk) {
             const int nseg = s_segp[a.R];
             for (int sg = tid; sg < nseg; sg += RB_MAP_THREADS) {
-                int lo = 0, hi = a.R - 1;                       // last ray whose prefix <= sg
-                while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_segp[mid] <= sg) lo = mid; else hi = mid - 1; }
-                const int4 ray = s_rays[lo];
-                const int K = max(abs(ray.z - ray.x), abs(ray.w - ray.y));
-                const int k0 = (sg - s_segp[lo]) * RB_MAP_SEG;
-                rb_walk(s_cnt, ray, k0, min(K, k0 + RB_MAP_SEG), tx0, ty0, tx1, ty1, tw);
+                const int r = bl_seg_ray(s_segp, a.R, sg);
+                const int k0 = (sg - s_segp[r]) * RB_MAP_SEG;
+                bl_walk_range(s_rays[r], k0, k0 + RB_MAP_SEG, count);
             }
         } else {
             for (int r = tid; r < a.R; r += RB_MAP_THREADS) {
-                const int4 ray = rb_ray_cells(a, pb, pe, r);
-                if (ray.x == 0x7fffffff) continue;
-                rb_walk(s_cnt, ray, 0, max(abs(ray.z - ray.x), abs(ray.w - ray.y)), tx0, ty0, tx1, ty1, tw);
+                const int4 ray = rb_ray_of(a, pb, pe, r);
+                if (ray.x != BL_NO_RAY) bl_walk_range(ray, 0, bl_ray_steps(ray), count);
             }
         }
         __syncthreads();

@@ -11,7 +11,7 @@
 //   functions to the base cell in chunk order gives the sequential result byte for byte.
 //
 //   phase 0  k_rl_poses, k_rl_rays: the pose table; one workgroup per scan writes the rays' start and end cells (the arithmetic of
-//            k_map_update, restated) and the scan's bounding box clipped to the grid.  k_rl_chunk_boxes, k_rl_count_fill
+//            k_map_update: bl_mapray_dev.h) and the scan's bounding box clipped to the grid.  k_rl_chunk_boxes, k_rl_count_fill
 //            (twice), k_rl_scan: the chunks' boxes and the list of (tile, chunk) pairs whose boxes meet, tile-major, chunks ascending.
 //   phase 1  k_rl_fold: one workgroup per pair; the tile's functions and two uint16 counters per cell in LDS (8 B per cell).
 //   phase 2  k_rl_apply: a thread per cell applies its tile's pairs' functions in order to the base cell.
@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "bl_internal.h"
+#include "bl_mapray_dev.h"
 
 #define RL_TILE 64
 #define RL_TILE_CELLS (RL_TILE * RL_TILE)
@@ -28,8 +29,6 @@
 #define RL_MAX_RAYS 8192                     // the mapper's own limit (MAP_MAX_RAYS)
 #define RL_MAX_BYTES (1ull << 30)
 #define RL_RAY_BYTES 16                      // int64 time + float range + float theta
-#define RL_CELL_LIMIT (1 << 24)              // |cell coordinate| bound for a ray to be traced (bl_mapping.hip)
-#define RL_NO_RAY 0x7fffffff
 
 struct bl_scanlog {
     bl_ctx* ctx;
@@ -221,27 +220,6 @@ __global__ void k_rl_poses(bl_pose_xyt_t* P, bl_pose_xyt_t prev, const bl_pose_x
     if (recorded && i < count) P[1 + i] = ring[(head + first + i) % capacity];
 }
 
-// start cell and end cell of one ray (moving_laser_scan.cpp:22-37, mapping.cpp:45-49; as map_ray_cells of bl_mapping.hip);
-// x == RL_NO_RAY: the ray takes no part
-__device__ __forceinline__ int4 rl_ray_cells(const bl_frame& f, float max_laser, bool interp, int64_t t_begin, double t_den, const bl_pose3& pb,
-                                             const bl_pose3& pe, float range, float ray_theta, int64_t ray_time)
-{
-    int4 ray = make_int4(RL_NO_RAY, 0, 0, 0);
-    if (range <= max_laser) {                                   // rays with range <= 0.15f were dropped when the scan was packed
-        const bl_pose3 rp = interp ? bl_interpolate_pose(pb, pe, bl_interp_ratio(ray_time, t_begin, t_den)) : pe;
-        const float theta = bl_wrap_to_pi(rp.theta - ray_theta);
-        float sn, cs, sx, sy;
-        bl_sincosf(theta, &sn, &cs);
-        bl_global_to_grid(rp.x, rp.y, f, &sx, &sy);
-        const float fx = (range * cs * f.cpm) + sx;
-        const float fy = (range * sn * f.cpm) + sy;
-        const float lim = (float)RL_CELL_LIMIT;
-        if (fx > -lim && fx < lim && fy > -lim && fy < lim && sx > -lim && sx < lim && sy > -lim && sy < lim)
-            ray = make_int4((int)sx, (int)sy, (int)fx, (int)fy);        // float -> int truncation at the bresenham() call
-    }
-    return ray;
-}
-
 __device__ __forceinline__ bool rl_box_empty(const int4 b) { return b.z < b.x || b.w < b.y; }
 
 // one workgroup per active scan: its rays' cells and the box of all of them, clipped to the grid (empty: z < x)
@@ -256,30 +234,20 @@ __global__ __launch_bounds__(RL_THREADS) void k_rl_rays(rl_args a)
     const bl_pose3 pb = {p0.x, p0.y, p0.theta}, pe = {p1.x, p1.y, p1.theta};
     const bool interp = p0.utime != p1.utime;                   // equal utimes: the pose itself (interpolation.hpp:27)
     const double t_den = interp ? (double)(p1.utime - p0.utime) : 1.0;
-    if (tid < 4) s_box[tid] = tid < 2 ? 0x7fffffff : -0x7fffffff;
+    if (tid < 4) s_box[tid] = tid < 2 ? BL_NO_RAY : -BL_NO_RAY;
     __syncthreads();
-    int x_lo = 0x7fffffff, y_lo = 0x7fffffff, x_hi = -0x7fffffff, y_hi = -0x7fffffff;
+    bl_box box = bl_box_none();
     int4* rays = a.rays + (size_t)i * a.stride;
     for (int r = tid; r < R; r += RL_THREADS) {
-        const int4 ray = rl_ray_cells(a.frame, a.max_laser, interp, p0.utime, t_den, pb, pe, s.ranges[r], s.thetas[r], interp ? s.times[r] : 0);
-        if (ray.x != RL_NO_RAY) {
-            x_lo = min(x_lo, min(ray.x, ray.z)); y_lo = min(y_lo, min(ray.y, ray.w));
-            x_hi = max(x_hi, max(ray.x, ray.z)); y_hi = max(y_hi, max(ray.y, ray.w));
-        }
+        const int4 ray = bl_ray_cells(a.frame, a.max_laser, interp, p0.utime, t_den, pb, pe, s.ranges[r], s.thetas[r], interp ? s.times[r] : 0);
+        bl_box_add(box, ray);
         rays[r] = ray;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        x_lo = min(x_lo, __shfl_xor(x_lo, off, 64)); y_lo = min(y_lo, __shfl_xor(y_lo, off, 64));
-        x_hi = max(x_hi, __shfl_xor(x_hi, off, 64)); y_hi = max(y_hi, __shfl_xor(y_hi, off, 64));
-    }
-    if ((tid & 63) == 0 && x_lo != 0x7fffffff) {
-        atomicMin(&s_box[0], x_lo); atomicMin(&s_box[1], y_lo);
-        atomicMax(&s_box[2], x_hi); atomicMax(&s_box[3], y_hi);
-    }
+    bl_box_to_lds(box, s_box);
     __syncthreads();
     if (tid == 0) {
         int4 b = make_int4(1, 1, 0, 0);
-        if (s_box[0] != 0x7fffffff) {
+        if (s_box[0] != BL_NO_RAY) {
             b = make_int4(max(s_box[0], 0), max(s_box[1], 0), min(s_box[2], a.frame.width - 1), min(s_box[3], a.frame.height - 1));
             if (rl_box_empty(b)) b = make_int4(1, 1, 0, 0);
         }
@@ -369,41 +337,23 @@ __device__ __forceinline__ unsigned int rl_compose_scan(unsigned int f, int H, i
 }
 
 // The cells of the reference's Bresenham walk of `ray` that fall into the tile, counted in the high halves of s_cnt (start cell
-// included, end cell excluded).  Cell k (k = 0 .. K - 1, K = max(dx, dy)) has the closed form of bl_mapping.hip: the major axis
-// advances k, the minor axis floor((2 k dmin + dmaj) / (2 dmaj)).  Only the k whose major coordinate lies in the tile are visited.
+// included, end cell excluded; the walk from any step: bl_mapray_dev.h).  Only the steps k whose major coordinate m0 + sm k lies in
+// the tile are visited.
 __device__ __forceinline__ void rl_walk(unsigned int* s_cnt, const int4 ray, int tx0, int ty0, int tx1, int ty1)
 {
-    const int dx = abs(ray.z - ray.x), dy = abs(ray.w - ray.y);
-    const int sx = ray.x < ray.z ? 1 : -1, sy = ray.y < ray.w ? 1 : -1;
-    const bool xmajor = dx >= dy;
-    const int dmaj = xmajor ? dx : dy, dmin = xmajor ? dy : dx;
-    if (dmaj == 0) return;
-    const int m0 = xmajor ? ray.x : ray.y, sm = xmajor ? sx : sy;
+    const int K = bl_ray_steps(ray);
+    if (K == 0) return;                                         // ahead of the clip: behind it k_rl_fold took 197 us for 182 (profiles/mapray_headline.json)
+    const bool xmajor = abs(ray.z - ray.x) >= abs(ray.w - ray.y);
+    const int m0 = xmajor ? ray.x : ray.y, m1 = xmajor ? ray.z : ray.w;
     const int ta = xmajor ? tx0 : ty0, tb = xmajor ? tx1 : ty1;
-    // m0 + sm k in [ta, tb]
-    long long k_lo = sm > 0 ? (long long)ta - m0 : (long long)m0 - tb;
-    long long k_hi = sm > 0 ? (long long)tb - m0 : (long long)m0 - ta;
+    long long k_lo = m0 < m1 ? (long long)ta - m0 : (long long)m0 - tb;
+    long long k_hi = m0 < m1 ? (long long)tb - m0 : (long long)m0 - ta;
     if (k_lo < 0) k_lo = 0;
-    if (k_hi > dmaj - 1) k_hi = dmaj - 1;
+    if (k_hi > K - 1) k_hi = K - 1;
     if (k_lo > k_hi) return;
-    const int k0 = (int)k_lo, k1 = (int)k_hi;
-    int n; long long rem;
-    if (dmaj < 32768) {                                         // 2 k dmin + dmaj < 2^31
-        const unsigned int num = 2u * (unsigned int)k0 * (unsigned int)dmin + (unsigned int)dmaj;
-        n = (int)(num / (2u * (unsigned int)dmaj));
-        rem = (long long)(num - (unsigned int)n * 2u * (unsigned int)dmaj);
-    } else {
-        const long long num = 2ll * k0 * dmin + dmaj;
-        n = (int)(num / (2ll * dmaj));
-        rem = num - (long long)n * 2ll * dmaj;
-    }
-    for (int k = k0; k <= k1; ++k) {
-        const int x = xmajor ? ray.x + sx * k : ray.x + sx * n;
-        const int y = xmajor ? ray.y + sy * n : ray.y + sy * k;
+    bl_walk_range(ray, (int)k_lo, (int)k_hi + 1, [&](int x, int y) {
         if (x >= tx0 && x <= tx1 && y >= ty0 && y <= ty1) atomicAdd(&s_cnt[(y - ty0) * RL_TILE + (x - tx0)], 0x10000u);
-        rem += 2ll * dmin;
-        if (rem >= 2ll * dmaj) { rem -= 2ll * dmaj; n += 1; }
-    }
+    });
 }
 
 __global__ __launch_bounds__(RL_THREADS) void k_rl_fold(rl_args a)
@@ -425,7 +375,7 @@ __global__ __launch_bounds__(RL_THREADS) void k_rl_fold(rl_args a)
         const int4* rays = a.rays + (size_t)i * a.stride;
         for (int r = tid; r < R; r += RL_THREADS) {
             const int4 ray = rays[r];
-            if (ray.x == RL_NO_RAY) continue;
+            if (ray.x == BL_NO_RAY) continue;
             if (min(ray.x, ray.z) > tx1 || max(ray.x, ray.z) < tx0 || min(ray.y, ray.w) > ty1 || max(ray.y, ray.w) < ty0) continue;
             if (ray.z >= tx0 && ray.z <= tx1 && ray.w >= ty0 && ray.w <= ty1) atomicAdd(&s_cnt[(ray.w - ty0) * RL_TILE + (ray.z - tx0)], 1u);
             rl_walk(s_cnt, ray, tx0, ty0, tx1, ty1);

@@ -357,6 +357,35 @@ def other_frame(orc):
     return Case("other_frame", W, H, 0.1, (-2.9, -2.2), base, src.entries, 5.0, 3, 1, condition, saturates=True)
 
 
+# ---- long and thin: walks that start behind dmaj = 32768
+LONG_DMAJ, LONG_DMIN = (32772, 32778), (0, 1, 3, 7)
+
+
+def long_thin(orc):
+    """A grid of 32 800 x 8 cells (513 tiles in a row) and two scans of eight rays from near one short edge, almost along the long axis,
+    ending inside the grid: every tile but the first takes up a walk with dmaj >= 32768 at k0 > 0, where the start's division takes
+    64 bits (bl_mapray_dev.h)."""
+    rng = np.random.default_rng(1800)
+    W, H = 32800, 8
+    o = (-820.0, -0.2)
+    base = rng.integers(-128, 128, (H, W)).astype(np.int8)
+    v = np.array([(a, b) for a in LONG_DMAJ for b in LONG_DMIN], np.float64)
+    path = [(o[0] + (10.5 + k) * 0.05, o[1] + 0.3 * 0.05, 0.0) for k in range(3)]
+    ent = [(_scan(np.hypot(v[:, 0], v[:, 1]) * 0.05, np.arctan2(v[:, 1], v[:, 0]), T0 + (k - 1) * DT, T0 + k * DT), (p[0], p[1], p[2], T0 + k * DT))
+           for k, p in enumerate(path)]
+
+    def condition(case, res):
+        assert res["info"]["scans"] == 2 and res["chunks"] == 1 and res["pairs"] == res["info"]["tiles"] == 513
+        for k in (1, 2):
+            c = mm.ray_cells(orc, ent[k][0], mm._opose(orc, ent[k - 1][1]), mm._opose(orc, ent[k][1]), case.origin, case.cpm, case.max_laser)
+            dx, dy = np.abs(c[:, 2] - c[:, 0]), np.abs(c[:, 3] - c[:, 1])
+            assert len(c) == len(v) and (dx >= 32768).all() and sorted(set(dy.tolist())) == list(LONG_DMIN)
+            assert (c >= 0).all() and (c[:, [0, 2]] < W).all() and (c[:, [1, 3]] < H).all()
+        assert (res["truth"] != case.base).sum() > 32768
+
+    return Case("long_thin", W, H, 0.05, o, base, ent[1:], 1700.0, 3, 1, condition, prev=ent[0][1])
+
+
 # ------------------------------------------------------------------ the list
 BUILDERS = {"count_one": count_one}
 for _n in COUNTS:
@@ -379,6 +408,7 @@ BUILDERS["other_poses"] = other_poses
 BUILDERS["ring_all"] = lambda orc: ring_all(orc)[0]
 BUILDERS["ring_window"] = lambda orc: ring_window(orc)[0]
 BUILDERS["other_frame"] = other_frame
+BUILDERS["long_thin"] = long_thin
 
 _cases = {}
 

@@ -541,6 +541,63 @@ def stamps(orc):
     return Case("stamps", 200, 200, 0.05, 5.0, 4, 1, start, updates, condition)
 
 
+# ---- 10: long and thin: a walk that starts behind dmaj = 32768
+LONG_DMAJ = (32768, 32780)
+LONG_DMIN = (0, 1, 3, 7)
+
+
+def long_thin(orc):
+    """A grid of 32 800 x 8 cells, eight rays from near one short edge almost along the long axis: the smallest shape in which a
+    segment starts at k0 > 0 of a walk with dmaj >= 32768, where the start's division takes 64 bits (bl_mapray_dev.h)."""
+    case = _fan_case(orc, "long_thin", 32800, 8, 0.05, 1700.0, (10, 0), [(a, b) for a in LONG_DMAJ for b in LONG_DMIN], 74)
+    fan_condition = case.condition
+
+    def condition(case, refs, geo):
+        fan_condition(case, refs, geo)                          # the rays have exactly these (dx, dy) and end inside the grid
+        for g in geo[1:]:
+            c = g["cells"]
+            assert (np.maximum(np.abs(c[:, 2] - c[:, 0]), np.abs(c[:, 3] - c[:, 1])) >= 32768).any() and g["kept"] <= SEG_RAYS
+
+    case.condition = condition
+    return case
+
+
+# ---- 11: a start far outside the grid: coordinates past 2^23, a start of the walk whose numerator passes 2^32
+FAR_CELL = (-8_500_000, -1_000_000)
+FAR_REACH = 200                              # every grid cell of a far ray lies within this many steps of its end
+
+
+def far_numerators(cells):
+    """2 k dmin + dmaj at k = dmaj - FAR_REACH for rays (n, 4): what the walk's first division takes in where the rays reach the grid."""
+    dx, dy = np.abs(cells[:, 2] - cells[:, 0]), np.abs(cells[:, 3] - cells[:, 1])
+    dmaj, dmin = np.maximum(dx, dy), np.minimum(dx, dy)
+    return 2 * (dmaj - FAR_REACH) * dmin + dmaj
+
+
+def far_start(orc):
+    """A standing robot 8.5 million cells from a grid of 64 x 64, eight rays that end in the grid.  Their start cells lie between 2^23
+    and 2^24 (BL_RAY_CELL_LIMIT is 2^24, not less), and where they reach the grid the numerator 2 k dmin + dmaj of the walk's start is
+    past 2^32 (the division must be the 64-bit one there)."""
+    rng = np.random.default_rng(1100)
+    W = H = 64
+    start = rng.integers(-128, 128, (H, W)).astype(np.int8)
+    case = Case("far_start", W, H, 0.05, 1.0e6, 4, 1, start, None, None)
+    x, y = case.centre_of(FAR_CELL[0] + 0.5, FAR_CELL[1] + 0.5)
+    v = np.array([(8.5 + 6 * i - FAR_CELL[0], 5.5 + 7 * i - FAR_CELL[1]) for i in range(8)], np.float64)
+    r, d = np.hypot(v[:, 0], v[:, 1]) * 0.05, np.arctan2(v[:, 1], v[:, 0])
+
+    def condition(case, refs, geo):
+        for g in geo[1:]:
+            c = g["cells"]
+            assert len(c) == 8 == g["kept"]
+            assert (np.abs(c[:, 0]) > 1 << 23).all() and (np.abs(c) < 1 << 24).all()
+            assert (c[:, 2:] > 64 - FAR_REACH).all() and (c[:, 2:] < FAR_REACH).all() and (far_numerators(c) >= 1 << 32).all()
+        assert (refs[-1] != refs[-2]).sum() > 100
+
+    case.updates, case.condition = _updates(lambda k, t0, t1: _scan(r, d, t0, t1), [(x, y, 0.0)] * 3), condition
+    return case
+
+
 # ------------------------------------------------------------------ the list
 RAY_COUNTS = [(1, 37), (64, 0), (65, 37), (1023, 0), (1024, 37), (1025, 0), (2048, 37), (2049, 0), (8192, 0)]
 
@@ -562,6 +619,8 @@ BUILDERS["fan_thin_right"] = lambda orc: fan_thin(orc, "right")
 BUILDERS["edges_inside"] = edges_inside
 BUILDERS["edges_outside"] = edges_outside
 BUILDERS["stamps"] = stamps
+BUILDERS["long_thin"] = long_thin
+BUILDERS["far_start"] = far_start
 
 _cases = {}
 

@@ -3,7 +3,7 @@ kernels of botlab_amd/csrc/bl_obslayer.hip must reproduce value for value: the c
 the stats, the list of live cells and the composed grid.
 
 The geometry is the scan matcher's at heading step 0 (scan_match_model.endpoints with dk = 0, grid_position); the walk is the
-reference's Bresenham variant in its closed form (tests/tools/bresenham_closed_form.py), start cell included, end cell excluded.
+reference's Bresenham variant in its closed form (tests/test_mapray_header_cpu.py), start cell included, end cell excluded.
 """
 import math
 

@@ -2,7 +2,7 @@
 its branches on a real SLAM sequence.
 
 The map workgroup traces the rays with its own double-precision weighted mean of x and y, and when the finisher's exact x, y -- the
-reference's serially rounded float sums -- arrive, places the rays again (map_ray_place: the angle part of a ray does not depend on
+reference's serially rounded float sums -- arrive, places the rays again (bl_ray_place: the angle part of a ray does not depend on
 x or y).  Equal cells: the counts stand and only the stores remain.  Any cell different: everything runs again with the exact pose.
 
 Which steps of the sequence must run again is worked out on the CPU from the oracle's particles (the double weighted mean, the

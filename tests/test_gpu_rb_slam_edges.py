@@ -2,7 +2,8 @@
 for: k_rb_map's serial walk of scans above 512 rays, its column tiles, its several tiles per workgroup after a pose jump, rb_apply's
 clamps and pass order in both code forms; k_rb_plan's exact due test at equality and one score beside it at 4096 particles near the
 largest score, its searches where every target falls on a partial sum, its slot table and copy list with maps that name their particle;
-k_rb_weigh's saturation, a scan without a kept ray, equal utimes; rb_walk's rays within one cell.  Every case compares what
+k_rb_weigh's saturation, a scan without a kept ray, equal utimes; rays within one cell; walks with dmaj >= 32768 on a long thin grid
+and from 8.5 million cells away.  Every case compares what
 tests/test_gpu_rb_slam.py compares, after every update: flags, indices, likelihoods, scores, units, S, Q, best, all poses and all P maps,
 byte for byte against tests/rb_slam_model.py."""
 import numpy as np
@@ -160,4 +161,44 @@ def test_coarse_grid(oracle, maps, gpu_ctx):
     c = E.coarse_case(maps)
     mdl, rb, flags = _go(oracle, gpu_ctx, c)
     assert np.count_nonzero(mdl.maps[0]) > 10
+    rb.close()
+
+
+# ---- 8. long and thin
+def test_long_thin_grid(oracle, maps, gpu_ctx):
+    """32 800 x 8 cells, two particles, eight rays with dmaj >= 32768: k_rb_map's segments start at k0 > 0 behind the point where the
+    walk's first division takes 64 bits.  The particles follow the odometry (no noise), so the rays end inside the grid."""
+    c = E.long_thin_case(maps)
+    mdl, rb = _pair(oracle, gpu_ctx, c.frame, c.P, c.num, c.den, c.odoms[0], spread=c.spread, cpm=c.cpm, max_laser=c.max_laser, hit=c.hit,
+                    miss=c.miss)
+    parts = E.long_thin_particles(mdl)
+    mdl.set_particles(parts)
+    rb.setParticles(parts)
+    rng = np.random.default_rng(c.noise_seed)
+    for k, o in enumerate(c.odoms):
+        noise = mdl.draw_noise(o, rng, stds=E.NO_NOISE)
+        r_m = mdl.update(o, c.scans[k], 4242 + k, noise)
+        r_g = rb.update(bl.make_pose(o[0], o[1], o[2], utime=o[3]), c.scans[k], rand_value=4242 + k, noise=noise)
+        _compare(mdl, rb, r_m, r_g, k)
+    assert np.count_nonzero(mdl.maps[0]) > 32768 and not np.array_equal(mdl.maps[0], mdl.maps[1])
+    rb.close()
+
+
+# ---- 9. a start far outside the grid
+def test_far_start(oracle, maps, gpu_ctx):
+    """Two particles 8.5 million cells from the grid: start cells between 2^23 and 2^24, and a walk whose first division takes in more
+    than 2^32 where the rays reach the grid."""
+    c = E.far_case(maps)
+    mdl, rb = _pair(oracle, gpu_ctx, c.frame, c.P, c.num, c.den, c.odoms[0], spread=c.spread, cpm=c.cpm, max_laser=c.max_laser, hit=c.hit,
+                    miss=c.miss)
+    parts = E.far_particles(mdl)
+    mdl.set_particles(parts)
+    rb.setParticles(parts)
+    rng = np.random.default_rng(c.noise_seed)
+    for k, o in enumerate(c.odoms):
+        noise = mdl.draw_noise(o, rng, stds=E.NO_NOISE)
+        r_m = mdl.update(o, c.scans[k], 4242 + k, noise)
+        r_g = rb.update(bl.make_pose(o[0], o[1], o[2], utime=o[3]), c.scans[k], rand_value=4242 + k, noise=noise)
+        _compare(mdl, rb, r_m, r_g, k)
+    assert np.count_nonzero(mdl.maps[0]) > 100 and not np.array_equal(mdl.maps[0], mdl.maps[1])
     rb.close()

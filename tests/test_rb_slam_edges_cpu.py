@@ -2,7 +2,8 @@
 the path of bl_rbslam.hip it is meant for -- scans of more than 512 kept rays, windows of several column and row tiles, a pose jump
 that leaves k_rb_map more tiles than workgroups, cells on both int8 rails with the order of the two passes visible, the exact
 "resampling is due" test at equality and beside it at the largest magnitudes, low-variance searches whose targets fall on partial sums,
-maps that name their particle, a scan without a kept ray, equal utimes, and rays that start and end in one cell.  The GPU file imports
+maps that name their particle, a scan without a kept ray, equal utimes, rays that start and end in one cell, walks with dmaj >= 32768 and
+walks from 8.5 million cells away.  The GPU file imports
 the constants and builders below and runs the same inputs on the device."""
 import types
 
@@ -540,3 +541,100 @@ def test_coarse_grid_has_rays_within_one_cell(oracle, maps):
     run_model(oracle, c, each)
     print("coarse: rays that start and end in one cell, of the rays traced:", n)
     assert all(a >= 10 and b - a >= 10 for a, b in n)
+
+
+# ---- 8. long and thin: walks that start behind dmaj = 32768
+LONG_THIN_SHAPE = (8, 32800)
+LONG_THIN_ORIGIN = (-820.0, -0.2)
+LONG_THIN_LASER = 1700.0
+LONG_THIN_DMAJ, LONG_THIN_DMIN = (32772, 32778), (0, 1, 3, 7)
+NO_NOISE = (0.0, 0.0, 0.0)                   # the particles follow the odometry: a heading off by 1e-3 would end these rays 32 rows away
+
+
+def long_thin_case(maps):
+    """A grid of 32 800 x 8 cells and two particles near one short edge, a fraction of a cell apart, moving along
+    the lower long edge; eight rays almost along the long axis whose end cells lie inside the grid: the smallest shape in which a segment of k_rb_map
+    starts at k0 > 0 of a walk with dmaj >= 32768, where the start's division takes 64 bits (bl_mapray_dev.h)."""
+    x0, y0 = LONG_THIN_ORIGIN[0] + 10.5 * 0.05, LONG_THIN_ORIGIN[1] + 0.3 * 0.05
+    odoms = [(x0 + 0.05 * k, y0, 0.0, 1000 + 100000 * k) for k in range(3)]
+    v = np.array([(a, b) for a in LONG_THIN_DMAJ for b in LONG_THIN_DMIN], np.float64)
+    n = len(v)
+    scans = [LidarScan(np.hypot(v[:, 0], v[:, 1]) * 0.05, -np.arctan2(v[:, 1], v[:, 0]), o[3] - 100000 + (np.arange(n, dtype=np.int64) + 1) * 100000 // n,
+                       utime=o[3]) for o in odoms]
+    return case("long_thin", LONG_THIN_SHAPE, LONG_THIN_ORIGIN, 2, odoms, scans, num=1, den=65535, max_laser=LONG_THIN_LASER, spread=None)       # (never resamples: the two maps stay two)
+
+
+def long_thin_particles(mdl):
+    """The case's two particles: the second 0.6 of a cell ahead of the first and 0.2 of a cell above it."""
+    p = mdl.parts.copy()
+    p["x"][1] += np.float32(0.03)
+    p["y"][1] += np.float32(0.01)
+    p["p_x"], p["p_y"] = p["x"], p["y"]
+    return p
+
+
+def test_long_thin_rays_pass_dmaj_32768_and_end_inside_the_grid(oracle, maps):
+    c = long_thin_case(maps)
+    mdl = model_of(oracle, c)
+    mdl.set_particles(long_thin_particles(mdl))
+    rng = np.random.default_rng(c.noise_seed)
+    H, W = c.shape
+    for k in range(len(c.odoms)):
+        before = mdl.maps.copy()
+        r = mdl.update(c.odoms[k], c.scans[k], 4242 + k, mdl.draw_noise(c.odoms[k], rng, stds=NO_NOISE))
+        assert r["moved"] == (k > 0) and not r["resampled"]
+        for p in range(c.P):
+            cells = rbm.ray_cells(oracle, c.scans[k], mdl._pose_of(p, parent=True), mdl._pose_of(p), c.origin, c.cpm, c.max_laser)
+            dx, dy = np.abs(cells[:, 2] - cells[:, 0]), np.abs(cells[:, 3] - cells[:, 1])
+            assert len(cells) == len(c.scans[k].ranges) <= SEG_RAYS and (dx >= 32768).all() and sorted(set(dy.tolist())) == list(LONG_THIN_DMIN)
+            assert (cells >= 0).all() and (cells[:, [0, 2]] < W).all() and (cells[:, [1, 3]] < H).all()
+            assert k == 0 or np.count_nonzero(mdl.maps[p] != before[p]) > 32768     # (update 0 only latches the pose)
+    assert not np.array_equal(mdl.maps[0], mdl.maps[1])
+
+
+# ---- 9. a start far outside the grid: coordinates past 2^23, a start of the walk whose numerator passes 2^32
+FAR_ORIGIN = (-1.6, -1.6)
+FAR_X, FAR_Y = -425000.0, -50000.0           # 8.5 and 1 million cells from the grid; floats are 0.03125 apart there
+FAR_STEP = 0.125                             # the odometry's step along x: four of those
+FAR_LASER = 1.0e6
+FAR_REACH = 200
+
+
+def far_case(maps):
+    """Two particles 8.5 million cells from a grid of 64 x 64, moving 2.5 cells an update, eight rays that end in the grid: start cells
+    between 2^23 and 2^24 (BL_RAY_CELL_LIMIT is 2^24, not less), and where the rays reach the grid the numerator 2 k dmin + dmaj of the
+    walk's start is past 2^32 (the division must be the 64-bit one there).  Every ray is stamped with its scan's utime: it leaves from
+    the pose itself."""
+    odoms = [(FAR_X + FAR_STEP * k, FAR_Y, 0.0, 1000 + 100000 * k) for k in range(3)]
+    scans = []
+    for o in odoms:
+        v = np.array([(FAR_ORIGIN[0] + (8.5 + 6 * i) * 0.05 - o[0], FAR_ORIGIN[1] + (5.5 + 7 * i) * 0.05 - o[1]) for i in range(8)], np.float64)
+        scans.append(LidarScan(np.hypot(v[:, 0], v[:, 1]), -np.arctan2(v[:, 1], v[:, 0]), np.full(8, o[3], np.int64), utime=o[3]))
+    return case("far", (64, 64), FAR_ORIGIN, 2, odoms, scans, num=1, den=65535, max_laser=FAR_LASER, spread=None)
+
+
+def far_particles(mdl):
+    """The case's two particles: the second two cells above the first."""
+    p = mdl.parts.copy()
+    p["y"][1] += np.float32(0.09375)
+    p["p_y"] = p["y"]
+    return p
+
+
+def test_far_rays_start_past_2_23_and_reach_the_grid_past_2_32(oracle, maps):
+    c = far_case(maps)
+    mdl = model_of(oracle, c)
+    mdl.set_particles(far_particles(mdl))
+    rng = np.random.default_rng(c.noise_seed)
+    for k in range(len(c.odoms)):
+        before = mdl.maps.copy()
+        r = mdl.update(c.odoms[k], c.scans[k], 4242 + k, mdl.draw_noise(c.odoms[k], rng, stds=NO_NOISE))
+        assert r["moved"] == (k > 0) and not r["resampled"]
+        for p in range(c.P):
+            cells = rbm.ray_cells(oracle, c.scans[k], mdl._pose_of(p, parent=True), mdl._pose_of(p), c.origin, c.cpm, c.max_laser)
+            dx, dy = np.abs(cells[:, 2] - cells[:, 0]), np.abs(cells[:, 3] - cells[:, 1])
+            assert len(cells) == 8 and (np.abs(cells[:, 0]) > 1 << 23).all() and (np.abs(cells) < 1 << 24).all()
+            assert (cells[:, 2:] > 64 - FAR_REACH).all() and (cells[:, 2:] < FAR_REACH).all()
+            assert (2 * (np.maximum(dx, dy) - FAR_REACH) * np.minimum(dx, dy) + np.maximum(dx, dy) >= 1 << 32).all()
+            assert k == 0 or np.count_nonzero(mdl.maps[p] != before[p]) > 100
+    assert not np.array_equal(mdl.maps[0], mdl.maps[1])
