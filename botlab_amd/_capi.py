@@ -293,6 +293,30 @@ class ScanLogStats(C.Structure):
 assert C.sizeof(ScanLogStats) == 64
 
 
+class PoseGraphEdge(C.Structure):
+    """bl_posegraph_edge_t: pose j seen from pose i is z, with information xx, xy, yy, xt, yt, tt (80 bytes)."""
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("z", C.c_double * 3), ("info", C.c_double * 6)]
+
+
+class PoseGraphParams(C.Structure):
+    """bl_posegraph_params_t: the held node, the caps on tries and on conjugate-gradient iterations, lambda and the tolerances (64 bytes)."""
+    _fields_ = [("fixed", C.c_int32), ("max_tries", C.c_int32), ("max_cg", C.c_int32), ("pad", C.c_int32), ("lambda0", C.c_double),
+                ("lambda_up", C.c_double), ("lambda_down", C.c_double), ("step_tol", C.c_double), ("rel_tol", C.c_double), ("cg_tol", C.c_double)]
+
+
+class PoseGraphResult(C.Structure):
+    """bl_posegraph_result_t: costs, lambda, counters and status of one subset's solve (40 bytes)."""
+    _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("final_lambda", C.c_double), ("tries", C.c_int32),
+                ("accepted", C.c_int32), ("cg_iterations", C.c_int32), ("status", C.c_int32)]
+
+    def __repr__(self):
+        return (f"PoseGraphResult(cost_before={self.cost_before!r}, cost_after={self.cost_after!r}, final_lambda={self.final_lambda!r}, "
+                f"tries={self.tries}, accepted={self.accepted}, cg_iterations={self.cg_iterations}, status={self.status})")
+
+
+assert C.sizeof(PoseGraphEdge) == 80 and C.sizeof(PoseGraphParams) == 64 and C.sizeof(PoseGraphResult) == 40
+
+
 class ObsTracksParams(C.Structure):
     """bl_obstracks_params_t: blob area limits, the gate, the two filter gains, confirmation, coasting and the speed of "moving" (32 bytes)."""
     _fields_ = [("min_cells", C.c_int32), ("max_cells", C.c_int32), ("gate_cells", C.c_int32), ("alpha", C.c_int32), ("beta", C.c_int32),
@@ -574,6 +598,19 @@ SIGNATURES = {
     "bl_scanlog_get_scan": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _P(C.c_int)]),
     "bl_scanlog_rebuild": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _P(Pose), C.c_float, C.c_int8, C.c_int8, _vp, _vp]),
     "bl_scanlog_last_stats": (C.c_int, [_vp, _P(ScanLogStats)]),
+    "bl_posegraph_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _P(_vp)]),
+    "bl_posegraph_destroy": (None, [_vp]),
+    "bl_posegraph_set_nodes": (C.c_int, [_vp, C.c_int, _vp]),
+    "bl_posegraph_set_nodes_from_log": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
+    "bl_posegraph_set_chain": (C.c_int, [_vp, _vp]),
+    "bl_posegraph_set_chain_from_nodes": (C.c_int, [_vp, _vp]),
+    "bl_posegraph_set_loops": (C.c_int, [_vp, C.c_int, _vp]),
+    "bl_posegraph_solve": (C.c_int, [_vp, _P(PoseGraphParams), C.c_int, _vp]),
+    "bl_posegraph_results": (C.c_int, [_vp, _vp]),
+    "bl_posegraph_poses": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "bl_posegraph_edge_chi2": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "bl_posegraph_poses_to_log": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
+    "bl_posegraph_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
     "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_shortcut_destroy": (None, [_vp]),
     "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),

@@ -189,6 +189,10 @@ void bl_edt_table(int R, float mpc, std::vector<float>* out);
 struct bl_obstracks_view { bl_ctx* ctx; int W, H; bool have_params; const bl_obstrack_t* d_slots; };
 void bl_obstracks_view_host(const bl_obstracks* tr, bl_obstracks_view* out);
 
+// bl_scanlog.hip: what the pose graph reads and writes of a scan log (bl_posegraph.hip): its ctx, its ring and the poses on the device
+struct bl_scanlog_view { bl_ctx* ctx; int capacity, head, size; bl_pose_xyt_t* d_poses; };
+void bl_scanlog_view_host(const bl_scanlog* log, bl_scanlog_view* out);
+
 // RAII-less helpers
 int bl_timer_begin(bl_ctx* ctx, int id, hipEvent_t* a, hipEvent_t* b);
 int bl_timer_end(bl_ctx* ctx, int id, hipEvent_t a, hipEvent_t b);

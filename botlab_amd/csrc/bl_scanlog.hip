@@ -141,6 +141,11 @@ extern "C" int bl_scanlog_append_dev_pose(bl_scanlog* l, const bl_lidar_t* scan,
 
 extern "C" int bl_scanlog_size(const bl_scanlog* l) { return l ? l->size : 0; }
 
+void bl_scanlog_view_host(const bl_scanlog* l, bl_scanlog_view* out)
+{
+    out->ctx = l->ctx; out->capacity = l->capacity; out->head = l->head; out->size = l->size; out->d_poses = l->d_poses;
+}
+
 // entries first .. first + count - 1 lie in at most two runs of slots
 template <class F>
 static int scanlog_runs(const bl_scanlog* l, int first, int count, F f)

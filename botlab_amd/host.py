@@ -2265,6 +2265,206 @@ class ScanHistory:
             self.h = None
 
 
+POSEGRAPH_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("z", "<f8", (3,)), ("info", "<f8", (6,))])
+POSEGRAPH_RESULT_DTYPE = np.dtype([("cost_before", "<f8"), ("cost_after", "<f8"), ("final_lambda", "<f8"), ("tries", "<i4"), ("accepted", "<i4"),
+                                   ("cg_iterations", "<i4"), ("status", "<i4")])
+POSEGRAPH_CONVERGED_STEP, POSEGRAPH_CONVERGED_DECREASE, POSEGRAPH_OUT_OF_TRIES, POSEGRAPH_CG_CAP = 1, 2, 3, 16
+
+
+def posegraph_params(fixed=0, max_tries=20, max_cg=500, lambda0=1e-6, lambda_up=10.0, lambda_down=0.1, step_tol=1e-6, rel_tol=1e-6, cg_tol=1e-8):
+    """bl_posegraph_params_t.  The defaults are untuned: they end the loop graphs of the tests in 3 - 4 accepted steps."""
+    return _capi.PoseGraphParams(int(fixed), int(max_tries), int(max_cg), 0, lambda0, lambda_up, lambda_down, step_tol, rel_tol, cg_tol)
+
+
+def posegraph_edges(i, j, z, info):
+    """POSEGRAPH_EDGE_DTYPE array of index arrays i, j, z (n, 3) and info (n, 6) or (6,): xx, xy, yy, xt, yt, tt."""
+    i = np.asarray(i, np.int32).reshape(-1)
+    e = np.zeros(len(i), POSEGRAPH_EDGE_DTYPE)
+    e["i"], e["j"] = i, np.asarray(j, np.int32).reshape(-1)
+    if len(i):
+        e["z"] = np.asarray(z, np.float64).reshape(-1, 3)
+        e["info"] = np.broadcast_to(np.asarray(info, np.float64), (len(i), 6))
+    return e
+
+
+class PoseGraph:
+    """Pose-graph back end (bl_posegraph_*, include/botlab_hip.h, "pose graph"): nodes, a chain of odometry edges, loop edges, and
+    solve(): one workgroup per subset of the loop edges, every subset in one launch.  The rules are the header's."""
+
+    def __init__(self, max_nodes, max_loop_edges=0, max_subsets=1, ctx=None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_posegraph_create(self.ctx.h, int(max_nodes), int(max_loop_edges), int(max_subsets), C.byref(h)))
+        self.h = h
+        self.n, self.n_loops, self.n_subsets = 0, 0, 0
+
+    def set_nodes(self, poses):
+        p = _pose_array(poses)
+        check(self.ctx.lib.bl_posegraph_set_nodes(self.h, len(p), p.ctypes.data))
+        self.n, self.n_loops = len(p), 0
+
+    def set_nodes_from_log(self, history, first=0, count=None):
+        count = len(history) - first if count is None else int(count)
+        check(self.ctx.lib.bl_posegraph_set_nodes_from_log(self.h, history.h, int(first), count))
+        self.n, self.n_loops = count, 0
+
+    def set_chain(self, edges):
+        e = np.ascontiguousarray(edges, POSEGRAPH_EDGE_DTYPE)
+        assert len(e) == self.n - 1
+        check(self.ctx.lib.bl_posegraph_set_chain(self.h, e.ctypes.data))
+
+    def set_chain_from_nodes(self, info6):
+        v = np.ascontiguousarray(info6, np.float64)
+        assert v.shape == (6,)
+        check(self.ctx.lib.bl_posegraph_set_chain_from_nodes(self.h, v.ctypes.data))
+
+    def set_loops(self, edges):
+        e = np.ascontiguousarray(edges, POSEGRAPH_EDGE_DTYPE)
+        check(self.ctx.lib.bl_posegraph_set_loops(self.h, len(e), e.ctypes.data if len(e) else None))
+        self.n_loops = len(e)
+
+    def solve(self, params=None, masks=None):
+        """masks: None (one subset, every loop edge on) or uint32 [n_subsets][(L + 31) // 32].  Enqueued; the readers wait."""
+        prm = params if params is not None else posegraph_params()
+        if masks is None:
+            check(self.ctx.lib.bl_posegraph_solve(self.h, C.byref(prm), 1, None))
+            self.n_subsets = 1
+            return
+        m = np.ascontiguousarray(masks, np.uint32)
+        words = (self.n_loops + 31) // 32
+        m = m.reshape(len(m), -1)[:, :words] if words else m.reshape(len(m), -1)[:, :0]
+        m = np.ascontiguousarray(m)
+        keep = m if m.size else np.zeros(1, np.uint32)
+        check(self.ctx.lib.bl_posegraph_solve(self.h, C.byref(prm), len(m), keep.ctypes.data))
+        self.n_subsets = len(m)
+
+    def results(self):
+        out = np.zeros(self.n_subsets, POSEGRAPH_RESULT_DTYPE)
+        check(self.ctx.lib.bl_posegraph_results(self.h, out.ctypes.data))
+        return out
+
+    def poses(self, subset=0, want_double=False):
+        """POSE_DTYPE [n] of a subset's result, narrowed once; with want_double also float64 [n][3]."""
+        out = np.zeros(self.n, POSE_DTYPE)
+        d = np.zeros((self.n, 3), np.float64) if want_double else None
+        check(self.ctx.lib.bl_posegraph_poses(self.h, int(subset), out.ctypes.data, None if d is None else d.ctypes.data))
+        return (out, d) if want_double else out
+
+    def edge_chi2(self, subset=0):
+        """(before, after): e' Omega e of every edge, chain first, at the nodes and at the subset's result."""
+        b, a = np.zeros(self.n - 1 + self.n_loops), np.zeros(self.n - 1 + self.n_loops)
+        check(self.ctx.lib.bl_posegraph_edge_chi2(self.h, int(subset), b.ctypes.data, a.ctypes.data))
+        return b, a
+
+    def poses_to_log(self, history, subset=0, first=0):
+        check(self.ctx.lib.bl_posegraph_poses_to_log(self.h, int(subset), history.h, int(first)))
+
+    def lastDeviceMs(self):
+        ms = C.c_float()
+        check(self.ctx.lib.bl_posegraph_last_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_posegraph_destroy(self.h)
+            self.h = None
+
+
+def find_loop_closures(history, matcher, like_grid, stride=4, min_gap=40, radius=1.0, w=5, submap_cells=200, nx=8, ny=8, ntheta=12,
+                       dtheta=math.radians(0.5), max_range=8.0, half_life=64, min_score=0, maxLaserDistance=5.0, hitOdds=3, missOdds=1):
+    """Loop-edge candidates from what is already here, for PoseGraph.set_loops / close_loops.  For every stride-th scan q of the
+    history: the older scans j < q - min_gap within `radius` metres of its recorded position, the nearest of them; the window
+    [j - w, j + w] rebuilt into a local grid of submap_cells x submap_cells cells of like_grid's resolution centred on pose j;
+    matcher.match_prior of scan q in it around its recorded pose, with moments.  A match is kept when it is accepted, has one best
+    candidate (ties == 1) and that candidate is off the window's edge.  Its edge (i = j, j = q): z is the sub-cell matched pose seen
+    from the recorded pose j; info is the inverse of the match's covariance (bl_scanmatch_covariance, turned into pose j's frame) plus
+    diag(mpc^2 / 12, mpc^2 / 12, dtheta^2 / 12), the variance of the matcher's own quantisation, which keeps the matrix invertible
+    when one candidate holds all the weight.  Returns a POSEGRAPH_EDGE_DTYPE array.
+
+    min_gap, radius, w, submap_cells, the match window (nx, ny, ntheta, dtheta), half_life and min_score are untuned knobs."""
+    n = len(history)
+    poses = history.poses()
+    mpc = float(like_grid.mpc)
+    px, py = poses["x"].astype(np.float64), poses["y"].astype(np.float64)
+    out = []
+    for q in range(0, n, max(int(stride), 1)):
+        last = q - int(min_gap) - 1                     # j < q - min_gap
+        if last < 0:
+            continue
+        d2 = (px[:last + 1] - px[q]) ** 2 + (py[:last + 1] - py[q]) ** 2
+        j = int(np.argmin(d2))
+        if d2[j] > radius * radius:
+            continue
+        first, end = max(j - int(w), 0), min(j + int(w), n - 1)
+        half = np.float32(submap_cells * mpc / 2.0)
+        sub = OccupancyGrid(ctx=history.ctx, _raw=(int(submap_cells), int(submap_cells), like_grid.mpc, like_grid.cpm,
+                                                   np.float32(poses["x"][j]) - half, np.float32(poses["y"][j]) - half))
+        try:
+            history.rebuild(sub, maxLaserDistance, hitOdds, missOdds, first=first, count=end - first + 1)
+            r, t, s = history.scan(q)
+            scan = LidarScan(r, t, s, utime=int(poses["utime"][q]))
+            centre = make_pose(poses["x"][q], poses["y"][q], poses["theta"][q], utime=int(poses["utime"][q]))
+            res, mom = matcher.match_prior(scan, centre, sub, half_life=half_life, nx=nx, ny=ny, ntheta=ntheta, dtheta=dtheta,
+                                           max_range=max_range, min_score=min_score)
+        finally:
+            sub.close()
+        if not (res.accepted and res.ties == 1 and abs(res.di) < nx and abs(res.dj) < ny and abs(res.dk) < ntheta):
+            continue
+        m = mom.refined_pose(res, centre, mpc, float(np.float32(dtheta)))
+        _, cov = mom.covariance(mpc, float(np.float32(dtheta)))
+        tj = float(poses["theta"][j])
+        c, sn = math.cos(tj), math.sin(tj)
+        dx, dy = float(m.x) - float(poses["x"][j]), float(m.y) - float(poses["y"][j])
+        dth = float(m.theta) - tj
+        z = (c * dx + sn * dy, -sn * dx + c * dy, math.atan2(math.sin(dth), math.cos(dth)))
+        S = np.array([[cov[0], cov[1], cov[3]], [cov[1], cov[2], cov[4]], [cov[3], cov[4], cov[5]]])
+        Rt = np.array([[c, sn, 0.0], [-sn, c, 0.0], [0.0, 0.0, 1.0]])
+        S = Rt @ S @ Rt.T + np.diag([mpc * mpc / 12.0, mpc * mpc / 12.0, float(np.float32(dtheta)) ** 2 / 12.0])
+        I = np.linalg.inv(S)
+        I = 0.5 * (I + I.T)
+        out.append((j, q, z, (I[0, 0], I[0, 1], I[1, 1], I[0, 2], I[1, 2], I[2, 2])))
+    return posegraph_edges([e[0] for e in out], [e[1] for e in out], [e[2] for e in out] or np.zeros((0, 3)),
+                           [e[3] for e in out] or np.zeros((0, 6)))
+
+
+def close_loops(history, graph, candidates, chain_info, gate=11.345, params=None):
+    """Gate loop-edge candidates and correct the history's poses.  The nodes are the history's recorded poses, the chain is made from
+    them with the information chain_info (xx, xy, yy, xt, yt, tt) on every edge.  One solve with L + 1 subsets: each candidate alone,
+    and all together (the graph needs max_subsets >= L + 1).  A candidate whose alone-cost -- its Mahalanobis distance under the
+    accumulated odometry -- exceeds `gate` is dropped (11.345: the 99 % point of chi2 with 3 degrees of freedom).  The survivors are
+    solved once more, those whose own chi2 in the joint solution exceeds the gate are dropped, and if any fell the rest is solved
+    again.  The poses are written to the history.  Returns (kept edges, results of the last solve, poses of it, alone costs).
+
+    chain_info and the gate are untuned knobs."""
+    cand = np.ascontiguousarray(candidates, POSEGRAPH_EDGE_DTYPE)
+    L, n = len(cand), len(history)
+    prm = params if params is not None else posegraph_params()
+    graph.set_nodes_from_log(history, 0, n)
+    graph.set_chain_from_nodes(chain_info)
+    alone = np.zeros(0)
+    kept = cand
+    if L:
+        graph.set_loops(cand)
+        words = (L + 31) // 32
+        masks = np.zeros((L + 1, words), np.uint32)
+        for l in range(L):
+            masks[l, l >> 5] = np.uint32(1) << np.uint32(l & 31)
+            masks[L, l >> 5] |= np.uint32(1) << np.uint32(l & 31)
+        graph.solve(prm, masks)
+        alone = graph.results()["cost_after"][:L].copy()
+        kept = cand[alone <= gate]
+    graph.set_loops(kept)
+    graph.solve(prm)
+    if len(kept):
+        own = graph.edge_chi2(0)[1][n - 1:]
+        if np.any(own > gate):
+            kept = kept[own <= gate]
+            graph.set_loops(kept)
+            graph.solve(prm)
+    graph.poses_to_log(history, 0, 0)
+    return kept, graph.results(), graph.poses(0), alone
+
+
 def _pose_array(poses):
     """POSE_DTYPE array of a POSE_DTYPE array or of a sequence of Pose."""
     if isinstance(poses, np.ndarray) and poses.dtype == POSE_DTYPE:

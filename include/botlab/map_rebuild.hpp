@@ -3,7 +3,7 @@
 // of them would leave, byte for byte -- at the recorded poses or at corrected ones, into the same grid or into one of another
 // resolution or origin.  OccupancyGridSLAMT::setScanHistory (slam_driver.hpp) records every scan the driver maps.
 //
-// Nothing here computes corrected poses.  C++11.
+// Corrected poses come from the pose graph (pose_graph.hpp).  C++11.
 #ifndef BOTLAB_MAP_REBUILD_HPP
 #define BOTLAB_MAP_REBUILD_HPP
 

@@ -29,6 +29,7 @@
 #include "botlab_dropin.hpp"
 #include "likelihood_field.hpp"
 #include "map_rebuild.hpp"
+#include "pose_graph.hpp"
 #include "scan_matcher.hpp"
 
 namespace botlab_hip {
@@ -402,8 +403,8 @@ public:
     // scan and the same pose bits to a history of the last `capacity` scans -- in the fused step the pose is read on the device, behind
     // the map update that carries the filter's end.  rebuildMap() writes into the driver's map what sequential map updates of the
     // recorded scans at the recorded poses give from an empty map -- the live map itself while the history still holds every scan --
-    // and rebuildMap(poses) the same at corrected poses, one per recorded scan.  Nothing here corrects a pose; the live mapper is
-    // neither read nor changed.  Off by default, and with it off nothing the driver does changes; set before the first iteration.
+    // and rebuildMap(poses) the same at corrected poses, one per recorded scan.  optimizeHistory below computes corrected poses
+    // (DESIGN.md 4.32); the live mapper is neither read nor changed.  Off by default, and with it off nothing the driver does changes; set before the first iteration.
     void setScanHistory(int capacity) { historyCapacity_ = capacity; }
     ScanHistoryT<Pose, Lidar>* scanHistory() const { return history_.get(); }
     void rebuildMap()
@@ -414,6 +415,27 @@ public:
     {
         if (history_ && !poses.empty()) history_->rebuild(grid_, mapRange(), mapHit_, mapMiss_, 0, poses);
     }
+    // (extension) Pose-graph back end on the history (PoseGraphT, pose_graph.hpp): the nodes are the recorded poses
+    // (device to device), the chain is made from the nodes with the information chainInfo (xx, xy, yy, xt, yt, tt) on every edge, the
+    // loop edges are the caller's (botlab_amd.find_loop_closures makes them on the Python side), all of them in force.  Solves, writes
+    // the poses back into the history and calls rebuildMap().  false, and nothing done, without a history of at least two scans.
+    // Nothing calls it by itself, and with it never called nothing the driver does changes.  lastPoseGraphResult(): of the last call.
+    bool optimizeHistory(const std::vector<bl_posegraph_edge_t>& loops, const double chainInfo[6],
+                         const bl_posegraph_params_t& params = poseGraphParams())
+    {
+        if (!history_ || history_->size() < 2) return false;
+        const int n = history_->size();
+        PoseGraphT<Pose> graph(n, static_cast<int>(loops.size()), 1);
+        graph.setNodesFromLog(history_->device(), 0, n);
+        graph.setChainFromNodes(chainInfo);
+        graph.setLoops(loops);
+        graph.solve(params);
+        poseGraphResult_ = graph.results()[0];
+        graph.posesToLog(0, history_->device(), 0);
+        rebuildMap();
+        return true;
+    }
+    const bl_posegraph_result_t& lastPoseGraphResult() const { return poseGraphResult_; }
     // (extension) The seed of the filter's first cloud, for runs that can be repeated (the reference, and the default here, take
     // it from the OS).  Set before the first iteration.
     void setFilterSeed(uint64_t seed) { seeded_ = true; seed_ = seed; }
@@ -534,6 +556,7 @@ private:
     // scan history: capacity (0: off); the history (made at the first map update); what the mapper was made with
     int historyCapacity_ = 0;
     std::unique_ptr<ScanHistoryT<Pose, Lidar> > history_;
+    bl_posegraph_result_t poseGraphResult_ = bl_posegraph_result_t();
     int8_t mapHit_, mapMiss_;
     static float mapRange() { return 5.0f; }               // slam.cpp:24
 

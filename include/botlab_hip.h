@@ -1837,6 +1837,80 @@ int bl_scanlog_rebuild(bl_scanlog* log, int first, int count, const bl_pose_xyt_
                        const bl_grid* base /* may be NULL */, bl_grid* out);
 int bl_scanlog_last_stats(bl_scanlog* log, bl_scanlog_stats_t* stats);  /* of the last rebuild; waits for it */
 
+/* ------------------------------------------------------------------ pose graph  
+ * The solver that turns "scan 900 saw the place scan 40 saw" into moved poses: what computes the corrected poses that the scan
+ * history rebuilds a map at.
+ *
+ * Problem.  Nodes x_k = (x, y, theta), 2 <= N <= 4096, theta within [-pi, pi].  An edge (i, j, z, info) says that pose j seen from
+ *   pose i is z; info holds xx, xy, yy, xt, yt, tt of a symmetric positive semi-definite 3 x 3 matrix Omega, in the order of the scan
+ *   matcher's covariance.  The cost is F = sum over the edges of e' Omega e,
+ *     e = ( R(theta_i)' (t_j - t_i) - z_xy , wrap(theta_j - theta_i - z_theta) ).
+ *   The first N - 1 edges are the chain (k, k + 1), in order: the odometry, which keeps the system connected.  Up to 1024 loop edges
+ *   follow, between any i != j; repeated pairs are allowed; a loop edge whose six information values are all zero behaves as an absent
+ *   one.  One node, params.fixed, is held.
+ * Method.  Gauss-Newton with Levenberg-Marquardt step control: H = sum J' Omega J + lambda I, H dx = -sum J' Omega e.  A try is accepted
+ *   only if F falls (then lambda *= lambda_down); otherwise lambda *= lambda_up and the try is repeated.  The solve stops at an
+ *   accepted step with max |dx| <= step_tol (status CONVERGED_STEP; a zero gradient counts as such a step and is not "accepted"), at
+ *   an accepted step with F_old - F_new <= rel_tol F_old (CONVERGED_DECREASE), or after max_tries tries (OUT_OF_TRIES).  The linear
+ *   step is conjugate gradients preconditioned by the block-tridiagonal part of H, which block cyclic reduction factors once per try;
+ *   it stops when r' T^-1 r <= cg_tol^2 times its first value, or after max_cg iterations (or when p' H p is not positive), and then
+ *   the status carries the flag CG_CAP and the step so far is tried.
+ * Arithmetic.  All state is double; every operation is one of + - * / rounded by itself; every sum has one order.
+ *   Sine and cosine of a heading are those of the heading narrowed to float, widened to double.  wrap is one comparison and one
+ *   +- 2 pi.  Results do not depend on the number of subsets, on their order or on any launch parameter.
+ * Subsets.  solve takes n_subsets bit masks over the loop edges, (L + 31) / 32 uint32 words each, bit l of a mask: loop edge l is in
+ *   force.  NULL means one subset with every edge on (n_subsets must be 1).  One workgroup solves one subset from start to finish,
+ *   all of them side by side in one launch.  A loop edge alone with the chain has as its optimal cost its Mahalanobis distance under
+ *   the accumulated odometry, so L + 1 subsets test every candidate at once.
+ * Calls.  set_nodes and set_nodes_from_log (device to device, entries first .. first + count - 1 of a log of the same ctx) replace the
+ *   nodes, and drop the chain and the loop edges.  set_chain takes N - 1 edges with i = k, j = k + 1; set_chain_from_nodes makes them
+ *   on the device, z_k the relative pose of the nodes k, k + 1 by the residual's own statements, so that with no loop edge the start
+ *   cost is exactly 0.  set_loops replaces the loop edges (n = 0: none).  solve is enqueued on the ctx stream and does not wait.
+ *   results, poses (x, y, theta in double, 3 a node, and/or narrowed once to float with the node's utime), edge_chi2 (N - 1 + L values
+ *   of e' Omega e at the start and at the end, edges out of force included) and last_device_ms wait for it.  poses_to_log writes a
+ *   subset's narrowed poses over the recorded poses of entries first .. first + N - 1, device to device, stream-ordered.
+ * BL_ERR_ARG: max_nodes outside 2 .. 4096, max_loop_edges outside 0 .. 1024, max_subsets < 1, more than 1 GiB in all; n outside
+ *   2 .. max_nodes; a chain edge that is not (k, k + 1); a loop edge with i = j or a node outside 0 .. N - 1; a z or info that is not
+ *   finite; n_subsets outside 1 .. max_subsets; fixed outside 0 .. N - 1; max_tries < 1; max_cg < 1; lambda0 < 0; lambda_up <= 1;
+ *   lambda_down outside (0, 1]; a negative or non-finite tolerance; a subset outside the last solve's; a log of another ctx or a
+ *   window outside it.  BL_ERR_STATE: chain or loops before nodes, solve before nodes and chain, a reader before the first solve.
+ *   A refused call enqueues nothing and changes nothing. */
+typedef struct bl_posegraph bl_posegraph;
+typedef struct bl_posegraph_edge_t {
+    int32_t i, j;
+    double z[3];                       /* x, y, theta of pose j in the frame of pose i */
+    double info[6];                    /* xx, xy, yy, xt, yt, tt */
+} bl_posegraph_edge_t;                 /* 80 bytes */
+typedef struct bl_posegraph_params_t {
+    int32_t fixed, max_tries, max_cg, pad;
+    double lambda0, lambda_up, lambda_down;
+    double step_tol, rel_tol, cg_tol;
+} bl_posegraph_params_t;               /* 64 bytes */
+#define BL_POSEGRAPH_CONVERGED_STEP 1
+#define BL_POSEGRAPH_CONVERGED_DECREASE 2
+#define BL_POSEGRAPH_OUT_OF_TRIES 3
+#define BL_POSEGRAPH_CG_CAP 16         /* flag, or-ed in: some try's conjugate gradients ended before their tolerance */
+typedef struct bl_posegraph_result_t {
+    double cost_before, cost_after;    /* F over the edges in force, at the nodes and at the result */
+    double final_lambda;
+    int32_t tries, accepted;
+    int32_t cg_iterations;             /* over all tries */
+    int32_t status;
+} bl_posegraph_result_t;               /* 40 bytes */
+int bl_posegraph_create(bl_ctx* ctx, int max_nodes, int max_loop_edges, int max_subsets, bl_posegraph** out);
+void bl_posegraph_destroy(bl_posegraph* pg);
+int bl_posegraph_set_nodes(bl_posegraph* pg, int n, const bl_pose_xyt_t* poses);
+int bl_posegraph_set_nodes_from_log(bl_posegraph* pg, bl_scanlog* log, int first, int count);
+int bl_posegraph_set_chain(bl_posegraph* pg, const bl_posegraph_edge_t* edges /* N - 1 */);
+int bl_posegraph_set_chain_from_nodes(bl_posegraph* pg, const double* info6);
+int bl_posegraph_set_loops(bl_posegraph* pg, int n, const bl_posegraph_edge_t* edges);
+int bl_posegraph_solve(bl_posegraph* pg, const bl_posegraph_params_t* params, int n_subsets, const uint32_t* masks /* may be NULL */);
+int bl_posegraph_results(bl_posegraph* pg, bl_posegraph_result_t* results /* n_subsets of the last solve */);
+int bl_posegraph_poses(bl_posegraph* pg, int subset, bl_pose_xyt_t* out_xyt /* may be NULL */, double* out_double /* may be NULL */);
+int bl_posegraph_edge_chi2(bl_posegraph* pg, int subset, double* before /* may be NULL */, double* after /* may be NULL */);
+int bl_posegraph_poses_to_log(bl_posegraph* pg, int subset, bl_scanlog* log, int first);
+int bl_posegraph_last_device_ms(bl_posegraph* pg, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
