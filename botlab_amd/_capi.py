@@ -317,6 +317,24 @@ class PoseGraphResult(C.Structure):
 assert C.sizeof(PoseGraphEdge) == 80 and C.sizeof(PoseGraphParams) == 64 and C.sizeof(PoseGraphResult) == 40
 
 
+class LoopCloseParams(C.Structure):
+    """bl_loopclose_params_t: the pair rule, the submap, the mapper's constants, the match window and its prior (84 bytes)."""
+    _fields_ = [("stride", C.c_int32), ("min_gap", C.c_int32), ("radius", C.c_float), ("w", C.c_int32), ("submap_cells", C.c_int32),
+                ("max_laser", C.c_float), ("hit", C.c_int32), ("miss", C.c_int32), ("match", ScanMatchParams), ("prior", ScanMatchPrior)]
+
+
+class LoopCloseCandidate(C.Structure):
+    """bl_loopclose_candidate_t: a candidate pair, its window, the gate's flags, the match and the edge (272 bytes)."""
+    _fields_ = [("q", C.c_int32), ("j", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("flags", C.c_uint32), ("pad", C.c_int32),
+                ("result", ScanMatchResult), ("moments", ScanMatchMoments), ("edge", PoseGraphEdge)]
+
+
+assert C.sizeof(LoopCloseParams) == 84 and LoopCloseParams.match.offset == 32 and LoopCloseParams.prior.offset == 60
+assert C.sizeof(LoopCloseCandidate) == 272 and LoopCloseCandidate.result.offset == 24 and LoopCloseCandidate.moments.offset == 80
+assert LoopCloseCandidate.edge.offset == 192
+LC_NOT_ACCEPTED, LC_TIED, LC_ON_EDGE, LC_TOO_MANY_RAYS = 1, 2, 4, 8
+
+
 class ObsTracksParams(C.Structure):
     """bl_obstracks_params_t: blob area limits, the gate, the two filter gains, confirmation, coasting and the speed of "moving" (32 bytes)."""
     _fields_ = [("min_cells", C.c_int32), ("max_cells", C.c_int32), ("gate_cells", C.c_int32), ("alpha", C.c_int32), ("beta", C.c_int32),
@@ -611,6 +629,13 @@ SIGNATURES = {
     "bl_posegraph_edge_chi2": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "bl_posegraph_poses_to_log": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "bl_posegraph_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_loopclose_create": (C.c_int, [_vp, C.c_int, _P(_vp)]),
+    "bl_loopclose_destroy": (None, [_vp]),
+    "bl_loopclose_find": (C.c_int, [_vp, _vp, _vp, _P(LoopCloseParams), _P(C.c_int)]),
+    "bl_loopclose_candidates": (C.c_int, [_vp, _vp]),
+    "bl_loopclose_edges": (C.c_int, [_vp, _P(C.c_int), _vp]),
+    "bl_loopclose_submap": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "bl_loopclose_last_device_ms": (C.c_int, [_vp, _P(C.c_float), _vp]),
     "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_shortcut_destroy": (None, [_vp]),
     "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),

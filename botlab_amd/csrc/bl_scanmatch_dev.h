@@ -185,13 +185,14 @@ __device__ __forceinline__ void sm_result_pose(bool moved, float cx, float cy, f
 // ---------------------------------------------------------------------------------------------------------------- host
 // The rays of a scan that count (min range < range < max_range), in scan order: how many, and the largest.  With `ranges` they are
 // packed there and their thetas into `thetas`; without, only counted.
+BL_HD bool sm_ray_valid(float range, float max_range) { return range > SM_MIN_RANGE && range < max_range; }
 static inline int sm_valid_rays(const bl_lidar_t* scan, float max_range, float* ranges, float* thetas, float* reach)
 {
     int n = 0;
     float longest = 0;
     for (int i = 0; i < scan->num_ranges; ++i) {
         const float r = scan->ranges[i];
-        if (!(r > SM_MIN_RANGE && r < max_range)) continue;
+        if (!sm_ray_valid(r, max_range)) continue;
         if (ranges) { ranges[n] = r; thetas[n] = scan->thetas[i]; }
         if (r > longest) longest = r;
         ++n;

@@ -2427,6 +2427,72 @@ def find_loop_closures(history, matcher, like_grid, stride=4, min_gap=40, radius
                            [e[3] for e in out] or np.zeros((0, 6)))
 
 
+SCAN_MATCH_RESULT_DTYPE = np.dtype([("pose", POSE_DTYPE), ("di", "<i4"), ("dj", "<i4"), ("dk", "<i4"), ("score", "<i4"), ("score_centre", "<i4"),
+                                    ("ties", "<i4"), ("rays_used", "<i4"), ("accepted", "<i4")])
+SCAN_MATCH_MOMENTS_DTYPE = np.dtype([(n, "<i8") for n in ("s0", "sx", "sy", "st", "sxx", "sxy", "syy", "sxt", "syt", "stt")] +
+                                    [("best_obj", "<i4"), ("pen_best", "<i4"), ("sub_num", "<i4", (3,)), ("sub_den", "<i4", (3,))])
+LOOPCLOSE_CANDIDATE_DTYPE = np.dtype([("q", "<i4"), ("j", "<i4"), ("first", "<i4"), ("count", "<i4"), ("flags", "<u4"), ("pad", "<i4"),
+                                      ("result", SCAN_MATCH_RESULT_DTYPE), ("moments", SCAN_MATCH_MOMENTS_DTYPE), ("edge", POSEGRAPH_EDGE_DTYPE)])
+assert SCAN_MATCH_RESULT_DTYPE.itemsize == 56 and SCAN_MATCH_MOMENTS_DTYPE.itemsize == 112 and LOOPCLOSE_CANDIDATE_DTYPE.itemsize == 272
+LC_NOT_ACCEPTED, LC_TIED, LC_ON_EDGE, LC_TOO_MANY_RAYS = _capi.LC_NOT_ACCEPTED, _capi.LC_TIED, _capi.LC_ON_EDGE, _capi.LC_TOO_MANY_RAYS
+
+
+class LoopCloser:
+    """Loop-closure front end on the device (bl_loopclose_*, include/botlab_hip.h, "loop closure"): find_loop_closures' pairs, submaps,
+    matches and gate for every candidate in one sequence of launches, and the edges by the header's stated arithmetic.  find() returns
+    the POSEGRAPH_EDGE_DTYPE array close_loops takes."""
+
+    def __init__(self, max_candidates, ctx=None):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_loopclose_create(self.ctx.h, int(max_candidates), C.byref(h)))
+        self.h = h
+        self.n_candidates, self.submap_cells = 0, 0
+
+    def find(self, history, like_grid, stride=4, min_gap=40, radius=1.0, w=5, submap_cells=200, nx=8, ny=8, ntheta=12,
+             dtheta=math.radians(0.5), max_range=8.0, half_life=64, min_score=0, maxLaserDistance=5.0, hitOdds=3, missOdds=1,
+             prior=(0, 0, 0, 0)):
+        """The keyword names are find_loop_closures'; prior: the match's motion prior (a_xx, a_xy, a_yy, a_tt)."""
+        match = _capi.ScanMatchParams(int(nx), int(ny), int(ntheta), float(np.float32(dtheta)), float(np.float32(max_range)), int(min_score), 0)
+        pr = _capi.ScanMatchPrior(int(prior[0]), int(prior[1]), int(prior[2]), int(prior[3]), int(half_life), 1)
+        prm = _capi.LoopCloseParams(int(stride), int(min_gap), float(np.float32(radius)), int(w), int(submap_cells),
+                                    float(np.float32(maxLaserDistance)), int(hitOdds), int(missOdds), match, pr)
+        m = C.c_int()
+        check(self.ctx.lib.bl_loopclose_find(self.h, history.h, like_grid.h, C.byref(prm), C.byref(m)))
+        self.n_candidates, self.submap_cells = m.value, int(submap_cells)
+        return self.edges()
+
+    def edges(self):
+        n = C.c_int()
+        out = np.zeros(max(self.n_candidates, 1), POSEGRAPH_EDGE_DTYPE)
+        check(self.ctx.lib.bl_loopclose_edges(self.h, C.byref(n), out.ctypes.data))
+        return out[:n.value].copy()
+
+    def candidates(self):
+        """LOOPCLOSE_CANDIDATE_DTYPE [M]: q, j, first, count, flags, result, moments, edge of every candidate of the last find."""
+        out = np.zeros(self.n_candidates, LOOPCLOSE_CANDIDATE_DTYPE)
+        check(self.ctx.lib.bl_loopclose_candidates(self.h, out.ctypes.data if len(out) else None))
+        return out
+
+    def submap(self, m):
+        """(cells int8 [S][S], origin float32 [2]) of candidate m's submap."""
+        cells = np.zeros((self.submap_cells, self.submap_cells), np.int8)
+        origin = np.zeros(2, np.float32)
+        check(self.ctx.lib.bl_loopclose_submap(self.h, int(m), cells.ctypes.data, origin.ctypes.data))
+        return cells, origin
+
+    def lastDeviceMs(self, split=False):
+        """Device time of the last find; with split also (pairs, rays + fold, match, records)."""
+        ms, ms4 = C.c_float(), (C.c_float * 4)()
+        check(self.ctx.lib.bl_loopclose_last_device_ms(self.h, C.byref(ms), ms4))
+        return (ms.value, tuple(ms4)) if split else ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_loopclose_destroy(self.h)
+            self.h = None
+
+
 def close_loops(history, graph, candidates, chain_info, gate=11.345, params=None):
     """Gate loop-edge candidates and correct the history's poses.  The nodes are the history's recorded poses, the chain is made from
     them with the information chain_info (xx, xy, yy, xt, yt, tt) on every edge.  One solve with L + 1 subsets: each candidate alone,

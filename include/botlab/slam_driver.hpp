@@ -28,6 +28,7 @@
 #include "beam_model.hpp"
 #include "botlab_dropin.hpp"
 #include "likelihood_field.hpp"
+#include "loop_closer.hpp"
 #include "map_rebuild.hpp"
 #include "pose_graph.hpp"
 #include "scan_matcher.hpp"
@@ -436,6 +437,26 @@ public:
         return true;
     }
     const bl_posegraph_result_t& lastPoseGraphResult() const { return poseGraphResult_; }
+    // (extension) Loop closure on the history (LoopCloserT, loop_closer.hpp): find -- every candidate pair, submap, match
+    // and edge of the history on the device, the submaps at the map's resolution -- then close -- the candidates gated through the pose
+    // graph's subsets (alone-cost, then own chi2, against `gate`), the corrected poses written back -- then rebuildMap().  Returns the
+    // number of kept edges; 0, and nothing done, without a history of at least two scans (at most 4096: the pose graph's limit).
+    // lastPoseGraphResult() is then the last solve's.  Nothing calls it by itself, and with it never called nothing the driver does
+    // changes.  Every parameter is an untuned knob.
+    int closeLoops(const bl_loopclose_params_t& params, const double chainInfo[6], double gate = 11.345,
+                   const bl_posegraph_params_t& graphParams = poseGraphParams())
+    {
+        if (!history_ || history_->size() < 2) return 0;
+        const int n = history_->size();
+        const int queries = params.stride >= 1 ? (n + params.stride - 1) / params.stride : 1;
+        LoopCloserT<Pose, Lidar> closer(queries < BL_LC_MAX_CANDIDATES ? queries : BL_LC_MAX_CANDIDATES);
+        const std::vector<bl_posegraph_edge_t> candidates = closer.find(*history_, grid_, params);
+        PoseGraphT<Pose> graph(n, static_cast<int>(candidates.size()), static_cast<int>(candidates.size()) + 1);
+        const LoopCloseOutcome outcome = LoopCloserT<Pose, Lidar>::close(*history_, graph, candidates, chainInfo, gate, graphParams);
+        poseGraphResult_ = outcome.result;
+        rebuildMap();
+        return static_cast<int>(outcome.kept.size());
+    }
     // (extension) The seed of the filter's first cloud, for runs that can be repeated (the reference, and the default here, take
     // it from the OS).  Set before the first iteration.
     void setFilterSeed(uint64_t seed) { seeded_ = true; seed_ = seed; }

@@ -1911,6 +1911,88 @@ int bl_posegraph_edge_chi2(bl_posegraph* pg, int subset, double* before /* may b
 int bl_posegraph_poses_to_log(bl_posegraph* pg, int subset, bl_scanlog* log, int first);
 int bl_posegraph_last_device_ms(bl_posegraph* pg, float* ms);
 
+/* ------------------------------------------------------------------ loop closure  
+ * The front end of the pose graph: from a scan log, the loop edges.  Every candidate pair is chosen, every submap rebuilt, every scan
+ * matched against its submap straight from the log and every edge formed in one sequence of launches whose length does not depend on
+ * the number of candidates.  The numpy restatement is tests/loop_closure_model.py.
+ *
+ * Inputs: a bl_scanlog with n entries; a grid `like`, of which only the two resolution floats mpc and cpm are read; the parameters
+ *   stride >= 1, min_gap >= 0, radius (float, > 0), w, 0 .. 31, submap_cells S, 16 .. 512, max_laser, hit, miss, a
+ *   bl_scan_match_params_t (its keep_volume must be 0) and a bl_scan_match_prior_t (its want_moments is taken as set; half_life is
+ *   checked as bl_scanmatch_match_prior checks it).
+ * Pairs.  For q = 0, stride, 2 stride, ... < n, let last = q - min_gap - 1.  If last < 0 there is no candidate.
+ *   d2(j) = (x_j - x_q)^2 + (y_j - y_q)^2 over j = 0 .. last.  The recorded float poses are widened to double and every operation is
+ *   rounded by itself.  j is the lowest index of the minimum.  There is no candidate if d2(j) > (double)radius * (double)radius.
+ *   Candidates are numbered in ascending q; m = 0 .. M - 1.
+ * Submap m.  Its window is first = max(j - w, 0) to end = min(j + w, n - 1).  The grid is S x S with like's mpc and cpm.  Its origin
+ *   is ((float)x_j - half, (float)y_j - half) with half = (float)((double)S * (double)mpc / 2.0).  Both subtractions are in float.
+ *   Its cells are, byte for byte, what bl_scanlog_rebuild(log, first, end - first + 1, NULL, NULL, max_laser, hit, miss, NULL, sub)
+ *   leaves.  So the window's first scan only latches its pose.  Every later one is traced from its predecessor's pose with the
+ *   per-ray time interpolation of the map update.
+ * Match m.  bl_scanmatch_match_prior's definition word for word.  The scan is the kept rays of entry q as they lie in the log,
+ *   filtered by the matcher's rule (range > 0.15f and range < max_range).  The centre is entry q's recorded pose; utime is that
+ *   pose's.  The map is submap m.  The caller's params and prior apply.  The result is a bl_scan_match_result_t and a
+ *   bl_scan_match_moments_t.  These equal, byte for byte, what the existing call returns for the same inputs.  A scan with more than
+ *   4096 valid rays is not matched: it carries the flag BL_LC_TOO_MANY_RAYS, and its result and moments are all zero.
+ * Gate.  A candidate is kept when all of these hold: accepted, ties == 1, |di| < nx, |dj| < ny, |dk| < ntheta.  Otherwise the flag
+ *   word says which failed: BL_LC_NOT_ACCEPTED, BL_LC_TIED, BL_LC_ON_EDGE.
+ * Edge of a kept candidate (i = j, j = q).  All arithmetic is plain double: each + - * / is rounded by itself and no operation is
+ *   fused.
+ *     p = bl_scanmatch_refined_pose(result, moments, centre, mpc, dtheta).
+ *     Sigma = bl_scanmatch_covariance(moments, mpc, dtheta).  Both are the helpers above, called as they are.
+ *     c and s are the cosine and sine of theta_j, formed as the pose graph forms them for a node: those of the float heading, widened.
+ *     dx = p.x - x_j, dy = p.y - y_j.
+ *     z = (c dx + s dy, c dy - s dx, wrap(p.theta - theta_j)), with the pose graph's wrap (one comparison, one +- 2 pi).
+ *     S = R' Sigma R + diag(mpc^2 / 12, mpc^2 / 12, dtheta^2 / 12), R' = ((c, s, 0), (-s, c, 0), (0, 0, 1)).  The two products are
+ *       taken left to right.  Every entry is (a0 b0 + a1 b1) + a2 b2.
+ *     info is the inverse of S by cofactors, each divided by the determinant (S00 C00 + S01 C01) + S02 C02, and symmetrised as
+ *       0.5 (I_ab + I_ba).  Its order is xx, xy, yy, xt, yt, tt.
+ *   A candidate that is not kept has an all-zero edge.
+ * Calls.  find is enqueued on the ctx stream and synchronises once to hand back M.  candidates returns the M records of the last
+ *   find, edges the kept candidates' edges in ascending q, ready for bl_posegraph_set_loops.  submap is diagnostic: submap m's S * S
+ *   bytes and its origin (either pointer may be NULL).  A log with fewer than two entries gives M = 0 and BL_OK.
+ * BL_ERR_ARG: a null pointer; max_candidates outside 1 .. 1024; a parameter outside the limits above; negative odds or odds above 127;
+ *   keep_volume != 0; a half life outside 1 .. 2^20; a window or a prior the matcher would refuse; a log of another ctx; radius not
+ *   positive or NaN; scratch (submaps, objective volumes, ray cells, endpoints) above 1 GiB; more queries with a partner than
+ *   max_candidates; m outside 0 .. M - 1.  Every refusal leaves the last results readable and unchanged; all but the count of partners
+ *   are found before any launch. */
+#define BL_LC_NOT_ACCEPTED 1
+#define BL_LC_TIED 2
+#define BL_LC_ON_EDGE 4
+#define BL_LC_TOO_MANY_RAYS 8
+#define BL_LC_MAX_CANDIDATES 1024
+#define BL_LC_MAX_W 31
+#define BL_LC_MIN_SUBMAP 16
+#define BL_LC_MAX_SUBMAP 512
+typedef struct bl_loopclose_params_t {
+    int32_t stride, min_gap;
+    float radius;
+    int32_t w, submap_cells;
+    float max_laser;
+    int32_t hit, miss;
+    bl_scan_match_params_t match;
+    bl_scan_match_prior_t prior;
+} bl_loopclose_params_t;               /* 84 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28, 32, 60 */
+typedef struct bl_loopclose_candidate_t {
+    int32_t q, j;                      /* the query scan and its partner */
+    int32_t first, count;              /* the submap's window of the log */
+    uint32_t flags;                    /* BL_LC_*; 0: kept */
+    int32_t pad;
+    bl_scan_match_result_t result;
+    bl_scan_match_moments_t moments;
+    bl_posegraph_edge_t edge;          /* i = j, j = q; all zero unless kept */
+} bl_loopclose_candidate_t;            /* 272 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 80, 192 */
+typedef struct bl_loopclose bl_loopclose;
+int bl_loopclose_create(bl_ctx* ctx, int max_candidates, bl_loopclose** out);
+void bl_loopclose_destroy(bl_loopclose* lc);
+int bl_loopclose_find(bl_loopclose* lc, bl_scanlog* log, const bl_grid* like, const bl_loopclose_params_t* params, int* n_candidates);
+int bl_loopclose_candidates(bl_loopclose* lc, bl_loopclose_candidate_t* out /* M of the last find */);
+int bl_loopclose_edges(bl_loopclose* lc, int* n, bl_posegraph_edge_t* out /* may be NULL: only the count; room for M */);
+int bl_loopclose_submap(bl_loopclose* lc, int m, int8_t* cells /* S * S */, float* origin_xy /* 2 */);
+/* device time of the last find between events: total, and pairs / rays + fold / match / records (ms4 may be NULL); BL_ERR_STATE
+ * before the first find that launched */
+int bl_loopclose_last_device_ms(bl_loopclose* lc, float* ms, float* ms4);
+
 #ifdef __cplusplus
 }
 #endif
