@@ -192,15 +192,79 @@ def cases():
     return _cases
 
 
+def _tie_history(partners):
+    """80 scans; q = 79 recorded at (0, 0) and every j of `partners` at 0.25 m from it along an axis: d2 = 0.0625 exactly for each, every
+    other older scan on the circle, about 0.5 m away."""
+    scans, poses = history(80, 16)
+    _set_pose(poses, 79, 0.0, 0.0)
+    for j, (x, y) in zip(partners, ((0.25, 0.0), (-0.25, 0.0), (0.0, 0.25))):
+        _set_pose(poses, j, x, y)
+    return scans, poses
+
+
+def _tie(partners):
+    """one candidate, the lowest of `partners`; they share the minimum of d2 exactly and every other j is farther"""
+    def reaches(m):
+        if len(m) != 1 or m[0]["q"] != 79 or len(m[0]["d2"]) < 71:
+            return False
+        d2 = m[0]["d2"]
+        low = min(d2)
+        return m[0]["j"] == min(partners) and low == 0.0625 and [j for j, v in enumerate(d2) if v == low] == sorted(partners)
+    return reaches
+
+
+LONG_N, LONG_LAP, LONG_RAYS, LONG_BIAS = 1100, 800, 24, 0.00002
+LONG_SAMPLE_KEPT = 16
+
+
+def _long_log(n, stride):
+    """more than 1024 queries and more than 256 candidates, on both sides of query index 1024 and of candidate 256, kept ones on both
+    sides; n scans and the stride are the case's own"""
+    def reaches(m):
+        queries = -(-n // stride)
+        qi = [c["q"] // stride for c in m]                     # the query's index: the thread of k_lc_number that numbers it
+        return (queries >= 1025 and len(m) >= 257 and any(v <= 1023 for v in qi) and any(v >= 1024 for v in qi) and
+                any(c["flags"] == 0 for c in m[:256]) and any(c["flags"] == 0 for c in m[256:]))
+    return reaches
+
+
+_edge_cases = None
+
+
+def edge_cases():
+    """The limits cases() does not reach: kept apart from cases(), whose GPU test compares every candidate with two
+    synchronous calls."""
+    global _edge_cases
+    if _edge_cases is not None:
+        return _edge_cases
+    out = []
+
+    def add(name, hist, params, reaches, **kw):
+        out.append(Case(name, list(hist[0]), list(hist[1]), params, reaches, **kw))
+
+    # a lap of 800 scans of 24 rays and a gap of 700: the queries from 734 on have a partner, the first of the lap before
+    long_params = dict(stride=1, min_gap=700, radius=0.25, w=1, submap_cells=64, nx=2, ny=2, ntheta=2)
+    long_hist = history(LONG_N, LONG_LAP, rays=LONG_RAYS, bias=LONG_BIAS)
+    add("long_log", long_hist, long_params, _long_log(len(long_hist[0]), long_params["stride"]), max_rays=LONG_RAYS)
+    tie = dict(stride=79, radius=0.375, submap_cells=65)
+    add("tie_same_lane", _tie_history((6, 70)), tie, _tie((6, 70)))                # one lane, two trips: the lane's own strict <
+    add("tie_lane_order", _tie_history((3, 64)), tie, _tie((3, 64)))               # lane 3 holds j = 3, lane 0 holds j = 64: the shuffle's oj < bj
+    add("tie_three", _tie_history((5, 64, 69)), tie, _tie((5, 64, 69)))
+    _edge_cases = {c.name: c for c in out}
+    assert not set(_edge_cases) & set(cases())
+    return _edge_cases
+
+
 # a second find on a handle that has just run a larger one, with other parameters
 SECOND_FIND = ("two_lap", "equal_d2")
+SECOND_FIND_LONG = ("long_log", "equal_d2")
 
 _models = {}
 
 
 def model(name):
     if name not in _models:
-        c = cases()[name]
+        c = cases()[name] if name in cases() else edge_cases()[name]
         scans, poses = c.retained()
         _models[name] = lcm.find(oracle_lib.load_oracle(), scans, poses, c.mpc, c.cpm, **c.params)
     return _models[name]

@@ -78,10 +78,15 @@ def cases():
         add("n%d_l%d" % (n, l), loop_graph(n, l, seed=n)[0], P._replace(fixed=(0, n - 1, n // 2)[n % 3]),
             condition=lambda r, n=n: _converged(r), why="%d levels of reduction, fixed %d" % (_levels(n), (0, n - 1, n // 2)[n % 3]))
     add("n64_l0", loop_graph(64, 0, seed=5)[0], condition=lambda r: r.accepted >= 1 and r.cg_per_try[0] == 1, why="no loop edge: the preconditioner is H, one iteration")
-    add("n64_fixed_last", loop_graph(64, 3, seed=6)[0], P._replace(fixed=63), why="fixed = N - 1")
-    add("n100_fixed_mid", loop_graph(100, 3, seed=7)[0], P._replace(fixed=50), why="fixed in the middle")
+    # the two converged statuses by name: _converged takes either
+    add("n64_fixed_last", loop_graph(64, 3, seed=6)[0], P._replace(fixed=63),
+        condition=lambda r: _converged(r) and (r.status & 15) == pgm.CONVERGED_STEP, why="fixed = N - 1; ends by the step rule after an accepted step")
+    add("n100_fixed_mid", loop_graph(100, 3, seed=7)[0], P._replace(fixed=50),
+        condition=lambda r: _converged(r) and (r.status & 15) == pgm.CONVERGED_DECREASE, why="fixed in the middle; ends by the relative-decrease rule")
     add("n64_repeated_pair", loop_graph(64, 0, seed=8, loops=[(3, 35), (3, 35), (35, 3)])[0], why="a pair three times, once reversed")
-    add("n64_loop_on_fixed", loop_graph(64, 0, seed=9, loops=[(0, 32), (40, 0)])[0], why="loop edges on the held node 0")
+    g_held = loop_graph(64, 0, seed=9, loops=[(0, 32), (40, 0)])[0]
+    add("n64_loop_on_fixed", g_held, condition=lambda r, g=g_held: _converged(r) and r.trial_wrapped and bool(np.all(np.abs(g.nodes[:, 2]) < pgm.PI)),
+        why="loop edges on the held node 0; a trial heading x + dx leaves [-pi, pi] though every node starts strictly inside")
     add("n64_adjacent_loop", loop_graph(64, 0, seed=10, loops=[(10, 11), (5, 37)])[0], why="a loop edge between chain neighbours")
     add("n64_across_pi", loop_graph(64, 2, seed=11, start_heading=math.pi - 0.05)[0], condition=lambda r: _converged(r) and r.wrapped,
         why="some |theta_j - theta_i - z_theta| > pi before the wrap")
@@ -96,6 +101,91 @@ def cases():
         condition=lambda r: (r.status & 15) == pgm.OUT_OF_TRIES and r.tries == 1, why="max_tries spent")
     add("n100_cg_cap", loop_graph(100, 8, seed=17)[0], P._replace(max_cg=3), condition=lambda r: bool(r.status & pgm.CG_CAP),
         why="the iteration cap ends the conjugate gradients")
+    return out
+
+
+HUB, HUB_EDGES = 7, 600
+F32_PI = float(np.float32(math.pi))             # 3.1415927410125732 > PG_PI: a float heading of pi lies outside [-PG_PI, PG_PI] in double
+
+
+def hub_loops(N=48, L=1024, seed=48):
+    """loop edges 0 .. HUB_EDGES - 1 touch node HUB, alternately as i and as j; the others are random pairs, repeats allowed"""
+    rng = np.random.default_rng(seed)
+    loops = []
+    for l in range(HUB_EDGES):
+        o = int(rng.integers(0, N - 1))
+        o = o + 1 if o >= HUB else o
+        loops.append((HUB, o) if l % 2 == 0 else (o, HUB))
+    for l in range(L - HUB_EDGES):
+        i, j = int(rng.integers(0, N)), int(rng.integers(0, N - 1))
+        loops.append((i, j + 1 if j >= i else j))
+    return loops
+
+
+def pi_headings_graph(seed=41):
+    """64 nodes, two loop edges; the two free nodes nearest +pi are set to exactly +float32(pi), the two nearest -pi to -float32(pi)
+    (none among the first eight: a node beside the held one hardly moves and would end within rounding of +-pi, where a heading and
+    its other representation differ by 2 pi), and the chain is made consistent with the nodes by the residual's own statements."""
+    g0, _ = loop_graph(64, 2, seed=seed, start_heading=math.pi - 0.05)
+    nodes = g0.nodes.copy()
+    k = np.arange(8, 64)
+    up = k[np.argsort(np.abs(nodes[k, 2] - math.pi))[:2]]
+    down = k[np.argsort(np.abs(nodes[k, 2] + math.pi))[:2]]
+    nodes[up, 2], nodes[down, 2] = F32_PI, -F32_PI
+    z = pgm.relative_pose(nodes[:-1], nodes[1:])
+    return pgm.Graph(nodes, g0.i, g0.j, np.concatenate([z, g0.z[63:]]), g0.info)
+
+
+def _power_of(final, lambda0, up, most):
+    lam = lambda0
+    for _ in range(most + 1):
+        if lam == final:
+            return True
+        lam = lam * up
+    return False
+
+
+_edge_cases = None
+
+
+def edge_cases():
+    """The limits cases() does not reach: loop edges past one trip of the workgroup and past two mask words, a long node list, float
+    headings of +-pi, and the accepted parameter values at the ends of their ranges."""
+    global _edge_cases
+    if _edge_cases is not None:
+        return _edge_cases
+    P = pgm.DEFAULT
+    out = []
+
+    def add(name, graph, params=P, condition=_converged, why="converges"):
+        out.append(Case(name, graph, params, None, condition, why))
+
+    hub = loop_graph(48, 0, seed=48, loops=hub_loops())[0]
+    add("n48_l1024_hub", hub,
+        condition=lambda r, g=hub: _converged(r) and g.L == 1024 and r.node_lists[HUB] >= pgm.PG_T + 1 and r.node_lists.sum() == 2 * 1024,
+        why="L = 1024: two trips of the set-up, 32 mask words, entries up to 2047, a node list of more than 512 entries, three loop terms a thread in the cost")
+    g600 = loop_graph(600, 513, seed=600)[0]
+    add("n600_l513", g600, condition=lambda r, g=g600: _converged(r) and g.N > pgm.PG_T and g.L == pgm.PG_T + 1, why="N and L one trip past PG_T")
+    g97 = loop_graph(64, 97, seed=97)[0]
+    add("n64_l97", g97, condition=lambda r, g=g97: _converged(r) and g.L == 97 and r.node_lists.sum() == 2 * 97, why="four mask words, the last holding one bit")
+    gpi = pi_headings_graph()
+    add("n64_pi_headings", gpi,
+        condition=lambda r, g=gpi: _converged(r) and r.trial_wrapped and g.nodes[0, 2] != F32_PI and
+        int(np.sum(g.nodes[1:, 2] == F32_PI)) >= 1 and int(np.sum(g.nodes[1:, 2] == -F32_PI)) >= 1 and F32_PI > pgm.PI,
+        why="free nodes at exactly +-float32(pi), outside +-PG_PI in double; a trial heading wraps")
+    # accepted parameter values at the ends of their ranges
+    g30, g31 = loop_graph(64, 3, seed=30)[0], loop_graph(64, 3, seed=31)[0]
+    add("n64_lambda0_zero", g30, P._replace(lambda0=0.0), condition=lambda r: r.final_lambda == 0.0 and r.accepted >= 1 and r.cost_after < r.cost_before,
+        why="lambda0 = 0: no damping, and lambda stays 0 whatever the tries do")
+    add("n64_lambda_down_one", g30, P._replace(lambda_down=1.0),
+        condition=lambda r: _converged(r) and r.tries > r.accepted and _power_of(r.final_lambda, P.lambda0, P.lambda_up, r.tries),
+        why="lambda_down = 1: lambda only ever rises, final_lambda = lambda0 times a power of lambda_up")
+    add("n64_max_cg_one", g30, P._replace(max_cg=1), condition=lambda r: all(n == 1 for n in r.cg_per_try) and bool(r.status & pgm.CG_CAP) and r.accepted >= 1,
+        why="max_cg = 1: every try is one iteration, ended by the cap")
+    add("n64_cg_tol_zero", g31, P._replace(cg_tol=0.0),
+        condition=lambda r: _converged(r) and not (r.status & pgm.CG_CAP) and all(end == "tol" and rz == 0.0 for end, rz in r.cg_ends),
+        why="cg_tol = 0: the iteration ends only at r' T^-1 r == 0 exactly")
+    _edge_cases = out
     return out
 
 

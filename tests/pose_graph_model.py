@@ -26,7 +26,7 @@ CONVERGED_STEP, CONVERGED_DECREASE, OUT_OF_TRIES, CG_CAP = 1, 2, 3, 16
 Params = namedtuple("Params", "fixed max_tries max_cg lambda0 lambda_up lambda_down step_tol rel_tol cg_tol")
 DEFAULT = Params(fixed=0, max_tries=20, max_cg=500, lambda0=1e-6, lambda_up=10.0, lambda_down=0.1, step_tol=1e-6, rel_tol=1e-6, cg_tol=1e-8)
 Result = namedtuple("Result", "cost_before cost_after tries accepted cg_iterations final_lambda status poses chi2_before chi2_after "
-                              "poses32 cg_per_try wrapped")
+                              "poses32 cg_per_try wrapped trial_wrapped node_lists cg_ends")
 
 _SYM = ((0, 0), (0, 1), (1, 1), (0, 2), (1, 2), (2, 2))        # xx, xy, yy, xt, yt, tt
 
@@ -287,6 +287,12 @@ def solve(g, prm=DEFAULT, mask=None):
     tries = accepted = cg_total = 0
     status, cap = OUT_OF_TRIES, 0
     cg_per_try = []
+    # what the cases' conditions read, beside the results: whether a trial heading left [-pi, pi] before its wrap, the length of every
+    # node's list of loop entries, and how each try's iteration ended -- ("tol" | "cap" | "php" | "none", the last r' T^-1 r)
+    trial_wrapped = False
+    ends = np.concatenate([g.i[loops_on], g.j[loops_on]]) if loops_on else np.zeros(0, np.int64)
+    node_lists = np.bincount(ends, minlength=N)
+    cg_ends = []
     free = np.arange(N) != prm.fixed
     while tries < prm.max_tries:
         tries += 1
@@ -306,10 +312,12 @@ def solve(g, prm=DEFAULT, mask=None):
         tol = (prm.cg_tol * prm.cg_tol) * rz0
         it = 0
         done = not (rz0 > 0.0)
+        end, last = "none" if done else "cap", rz0
         while not done and it < prm.max_cg:
             hp = _hp(g, Dl, AB, loops_on, p)
             php = dot(p, hp)
             if not (php > 0.0):
+                end = "php"
                 break
             al = rz / php
             dx = dx + al * p
@@ -317,12 +325,15 @@ def solve(g, prm=DEFAULT, mask=None):
             z = fac.solve(r)
             rz2 = dot(r, z)
             it += 1
+            last = rz2
             if rz2 <= tol:
                 done = True
+                end = "tol"
                 break
             beta = rz2 / rz
             p = z + beta * p
             rz = rz2
+        cg_ends.append((end, last))
         cg_total += it
         cg_per_try.append(it)
         if not done:
@@ -333,7 +344,9 @@ def solve(g, prm=DEFAULT, mask=None):
         xn = x.copy()
         xn[free, 0] = x[free, 0] + dx[free, 0]
         xn[free, 1] = x[free, 1] + dx[free, 1]
-        xn[free, 2] = wrap(x[free, 2] + dx[free, 2])
+        trial = x[free, 2] + dx[free, 2]
+        trial_wrapped = trial_wrapped or bool(np.any(np.abs(trial) > PI))
+        xn[free, 2] = wrap(trial)
         md = float(np.max(np.abs(dx[free]))) if np.any(free) else 0.0
         F2, _, _ = _edges(g, xn, on, prm.fixed, False)
         if F2 < F:
@@ -352,7 +365,8 @@ def solve(g, prm=DEFAULT, mask=None):
             lam = lam * prm.lambda_down
         else:
             lam = lam * prm.lambda_up
-    return Result(F0, F, tries, accepted, cg_total, lam, status | (CG_CAP if cap else 0), x, chi0, chi, x.astype(np.float32), cg_per_try, wrapped)
+    return Result(F0, F, tries, accepted, cg_total, lam, status | (CG_CAP if cap else 0), x, chi0, chi, x.astype(np.float32), cg_per_try, wrapped,
+                  trial_wrapped, node_lists, cg_ends)
 
 
 # ---------------------------------------------------------------- the independent dense solve

@@ -16,11 +16,12 @@ from botlab_amd import _capi
 pytestmark = pytest.mark.gpu
 BL_ERR_ARG, BL_ERR_STATE = 2, 4
 CASES = {c.name: c for c in pgc.cases()}
+EDGE_CASES = {c.name: c for c in pgc.edge_cases()}          # run by tests/test_gpu_pose_graph_edges.py, which shares _model
 
 
 @functools.lru_cache(maxsize=None)
 def _model(name, mask_key=None):
-    c = CASES[name] if name in CASES else pgc.large_case()
+    c = CASES[name] if name in CASES else EDGE_CASES[name] if name in EDGE_CASES else pgc.large_case()
     mask = None if mask_key is None else np.array(mask_key, np.uint32)
     return pgm.solve(c.graph, c.params, mask)
 

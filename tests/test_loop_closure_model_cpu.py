@@ -8,6 +8,8 @@ atan2(sin, cos), libm's double sine and cosine).
 Measured over the 128 kept edges of the case set: info differs by at most 1.44e-8 of the edge's largest information entry (the 1.25 cm
 case, whose quantisation term is the smallest; 4.2e-9 over the 127 edges at 5 cm), z by at most 2.5e-8 (the float sine and cosine of theta_j, relative error 6e-8, times offsets of up to 0.5 m).  The bounds are four times that, as
 DESIGN.md 4.32 did for its dense solve: a rounding difference between two formulations in double, not a tuning number."""
+import time
+
 import numpy as np
 import pytest
 
@@ -22,6 +24,39 @@ def test_case_reaches_its_path(name):
     case = lcc.cases()[name]
     assert lcm.check_params(case.params)
     assert case.reaches(lcc.model(name)), name
+
+
+assert list(lcc.edge_cases()) == ["long_log", "tie_same_lane", "tie_lane_order", "tie_three"]
+
+
+@pytest.mark.parametrize("name", list(lcc.edge_cases()))
+def test_edge_case_reaches_its_path(name):
+    case = lcc.edge_cases()[name]
+    assert lcm.check_params(case.params)
+    t = time.time()
+    m = lcc.model(name)
+    kept = sum(c["flags"] == 0 for c in m)
+    print(name, "model seconds %.2f" % (time.time() - t), "queries", -(-len(case.scans) // case.params["stride"]), "candidates", len(m), "kept", kept)
+    assert case.reaches(m), name
+
+
+def test_long_log_edges_against_the_python_formulation():
+    """the kept edges of long_log within the bounds the case set has"""
+    case = lcc.edge_cases()["long_log"]
+    _, poses = case.retained()
+    worst_info, worst_z, n = 0.0, 0.0, 0
+    for c in lcc.model("long_log"):
+        if c["flags"]:
+            continue
+        centre = tuple(np.float32(v) for v in poses[c["q"]][:3])
+        z, info = lcm.edge_reference(c["ref"], centre, poses[c["j"]], case.mpc, case.params["dtheta"])
+        info, z = np.array(info), np.array(z)
+        worst_info = max(worst_info, float(np.abs(info - np.array(c["info"])).max() / np.abs(info).max()))
+        worst_z = max(worst_z, float(np.abs(z - np.array(c["z"])).max()))
+        n += 1
+    print("long_log kept edges", n, "largest relative difference of info", worst_info, "largest absolute difference of z", worst_z)
+    assert n >= 2
+    assert worst_info <= INFO_REL_BOUND and worst_z <= Z_ABS_BOUND
 
 
 def test_case_set_is_not_vacuous():
