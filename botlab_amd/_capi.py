@@ -329,6 +329,19 @@ class LoopCloseCandidate(C.Structure):
                 ("result", ScanMatchResult), ("moments", ScanMatchMoments), ("edge", PoseGraphEdge)]
 
 
+class PlaceParams(C.Structure):
+    """bl_place_params_t: the descriptor's range bins and limit, the query's dilation, and the two thresholds (20 bytes)."""
+    _fields_ = [("bins_per_meter", C.c_float), ("max_range", C.c_float), ("dilate", C.c_int32), ("min_key", C.c_int32),
+                ("min_bits", C.c_int32)]
+
+
+class Place(C.Structure):
+    """bl_place_t: a query's best pair by the descriptors (32 bytes)."""
+    _fields_ = [(n, C.c_int32) for n in ("q", "j", "shift", "key", "overlap", "bits_q", "bits_j", "partner")]
+
+
+assert C.sizeof(PlaceParams) == 20 and C.sizeof(Place) == 32
+PLACE_SECTORS, PLACE_BINS = 64, 32
 assert C.sizeof(LoopCloseParams) == 84 and LoopCloseParams.match.offset == 32 and LoopCloseParams.prior.offset == 60
 assert C.sizeof(LoopCloseCandidate) == 272 and LoopCloseCandidate.result.offset == 24 and LoopCloseCandidate.moments.offset == 80
 assert LoopCloseCandidate.edge.offset == 192
@@ -636,6 +649,9 @@ SIGNATURES = {
     "bl_loopclose_edges": (C.c_int, [_vp, _P(C.c_int), _vp]),
     "bl_loopclose_submap": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "bl_loopclose_last_device_ms": (C.c_int, [_vp, _P(C.c_float), _vp]),
+    "bl_loopclose_find_places": (C.c_int, [_vp, _vp, _vp, _P(LoopCloseParams), _P(PlaceParams), _P(C.c_int)]),
+    "bl_loopclose_places": (C.c_int, [_vp, _P(C.c_int), _vp]),
+    "bl_loopclose_descriptors": (C.c_int, [_vp, _P(C.c_int), _vp, _vp]),
     "bl_shortcut_create": (C.c_int, [_vp, _P(_vp)]),
     "bl_shortcut_destroy": (None, [_vp]),
     "bl_shortcut_set_params": (C.c_int, [_vp, _P(ShortcutParams)]),

@@ -5,6 +5,8 @@
 // One stream-ordered sequence per find on the ctx stream, its length independent of the number of candidates; grids are sized by the
 // slots = min(queries, max_candidates), and a slot without a candidate leaves at once:
 //   k_lc_pairs          a wave per query: the nearest older scan by (d2, j), one 64 + 32 bit key, the lowest j of the minimum.
+//                       find_places puts k_pr_describe and k_pr_match (bl_place_dev.h) in its place: the partner by
+//                       the scans' descriptors, and k_lc_number then centres the match on the partner's pose turned by the shift.
 //   k_lc_number         one workgroup: the queries with a partner numbered in ascending q; M and whether it fits.  When it does not,
 //                       every later kernel leaves and the handle's results stay as they were.
 //   k_lc_prep           a workgroup per candidate: the match header; the valid rays of entry q compacted in scan order.
@@ -21,6 +23,7 @@
 #include "bl_internal.h"
 #include "bl_scanlog_dev.h"
 #include "bl_scanmatch_seq_dev.h"
+#include "bl_place_dev.h"
 
 #define LC_MAX_BYTES (1ull << 30)
 #define LC_PI 3.141592653589793
@@ -30,7 +33,7 @@ struct lc_cand {
     int32_t q, j, first, count;
     float ox, oy;                       // the submap's origin
     uint32_t flags; int32_t valid;      // BL_LC_TOO_MANY_RAYS or 0; the valid rays of entry q
-    bl_pose_xyt_t pq, pj;               // the recorded poses
+    bl_pose_xyt_t pq, pj;               // the centre of the match (pose mode: the recorded pose of q) and the recorded pose of j
 };
 struct lc_state { int32_t M, ok; };
 
@@ -45,6 +48,7 @@ struct lc_args {
     int nk, ncand, nblocks, mom_groups, rp_max, lds_window;
     char* scans; const int* kept; const bl_pose_xyt_t* ring;
     int* partner;                       // per query: j or -1
+    const bl_place_t* place;            // place mode: per query the best pair; NULL in pose mode
     lc_state* state; lc_cand* cand;
     int4* rays; int4* boxes; int8_t* sub;
     float* vr;                          // per slot: ranges[SM_MAX_RAYS] | thetas[SM_MAX_RAYS]
@@ -58,6 +62,10 @@ struct bl_loopclose {
     int maxc;
     lc_state* d_state; lc_cand* d_cand; sm_head* d_heads; bl_scan_match_moments_t* d_mom; bl_loopclose_candidate_t* d_rec;
     void* d_partner; size_t cap_partner;
+    void* d_desc; size_t cap_desc;      // place mode: the descriptors, their counts and the per-query records of the last
+    void* d_bits; size_t cap_bits;      // find_places that launched
+    void* d_place; size_t cap_place;
+    int place_n, place_Q; bool placed;
     void* d_rays; size_t cap_rays;
     void* d_boxes; size_t cap_boxes;
     void* d_sub; size_t cap_sub;
@@ -145,6 +153,11 @@ __global__ __launch_bounds__(1024) void k_lc_number(lc_args a)
             c.count = min(j + a.w, a.n - 1) - c.first + 1;
             c.pq = a.ring[(a.head + c.q) % a.capacity];
             c.pj = a.ring[(a.head + j) % a.capacity];
+            if (a.place) {                                      // the partner's pose turned by the shift; utime stays q's
+                const int s = a.place[t].shift, ss = s < 32 ? s : s - 64;
+                c.pq.x = c.pj.x; c.pq.y = c.pj.y;
+                c.pq.theta = __fadd_rn(c.pj.theta, __fmul_rn((float)ss, PR_STEP));
+            }
             c.ox = c.pj.x - a.half; c.oy = c.pj.y - a.half;
             c.flags = 0; c.valid = 0;
             a.cand[m] = c;
@@ -397,7 +410,7 @@ extern "C" void bl_loopclose_destroy(bl_loopclose* lc)
     if (!lc) return;
     (void)hipStreamSynchronize(lc->ctx->stream);
     void* bufs[] = {lc->d_state, lc->d_cand, lc->d_heads, lc->d_mom, lc->d_rec, lc->d_partner, lc->d_rays, lc->d_boxes, lc->d_sub,
-                    lc->d_vr, lc->d_ends, lc->d_best, lc->d_volume, lc->d_partial};
+                    lc->d_vr, lc->d_ends, lc->d_best, lc->d_volume, lc->d_partial, lc->d_desc, lc->d_bits, lc->d_place};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (lc->staging) (void)hipHostFree(lc->staging);
     for (int i = 0; i < 5; ++i) if (lc->ev[i]) (void)hipEventDestroy(lc->ev[i]);
@@ -420,12 +433,20 @@ static int lc_grow_keep(void** p, size_t* cap, size_t want, bl_ctx* ctx)
     return BL_OK;
 }
 
-extern "C" int bl_loopclose_find(bl_loopclose* lc, bl_scanlog* log, const bl_grid* like, const bl_loopclose_params_t* prm, int* n_candidates)
+// find (place == NULL: partners by the recorded poses) and find_places (partners by the descriptors)
+static int lc_find(bl_loopclose* lc, bl_scanlog* log, const bl_grid* like, const bl_loopclose_params_t* prm, const bl_place_params_t* place,
+                   int* n_candidates)
 {
-    BL_CHECK_ARG(lc != nullptr && log != nullptr && like != nullptr && prm != nullptr && n_candidates != nullptr);
     BL_CHECK_ARG(log->ctx == lc->ctx);
     BL_CHECK_ARG(prm->stride >= 1 && prm->min_gap >= 0);
-    BL_CHECK_ARG(prm->radius > 0.0f);                            // false for NaN
+    if (!place) BL_CHECK_ARG(prm->radius > 0.0f);                // false for NaN
+    if (place) {
+        BL_CHECK_ARG(place->bins_per_meter > 0.0f && place->bins_per_meter <= 1000.0f);       // false for NaN
+        BL_CHECK_ARG(place->max_range > SM_MIN_RANGE && place->max_range <= 1000.0f);
+        BL_CHECK_ARG(place->dilate == 0 || place->dilate == 1);
+        BL_CHECK_ARG(place->min_key >= 0 && place->min_key <= 65536);
+        BL_CHECK_ARG(place->min_bits >= 0 && place->min_bits <= PR_SECTORS * PR_BINS);
+    }
     BL_CHECK_ARG(prm->w >= 0 && prm->w <= BL_LC_MAX_W);
     BL_CHECK_ARG(prm->submap_cells >= BL_LC_MIN_SUBMAP && prm->submap_cells <= BL_LC_MAX_SUBMAP);
     BL_CHECK_ARG(prm->hit >= 0 && prm->hit <= 127 && prm->miss >= 0 && prm->miss <= 127);
@@ -484,6 +505,9 @@ extern "C" int bl_loopclose_find(bl_loopclose* lc, bl_scanlog* log, const bl_gri
     BL_CHECK_ARG(b_sub + b_vol + b_rays + b_ends <= LC_MAX_BYTES);
 
     int rc = bl_grow(&lc->d_partner, &lc->cap_partner, (size_t)a.Q * sizeof(int), false, ctx);
+    if (!rc && place) rc = bl_grow(&lc->d_desc, &lc->cap_desc, (size_t)n * PR_SECTORS * sizeof(uint32_t), false, ctx);
+    if (!rc && place) rc = bl_grow(&lc->d_bits, &lc->cap_bits, (size_t)n * sizeof(int32_t), false, ctx);
+    if (!rc && place) rc = bl_grow(&lc->d_place, &lc->cap_place, (size_t)a.Q * sizeof(bl_place_t), false, ctx);
     if (!rc) rc = bl_grow(&lc->d_rays, &lc->cap_rays, (size_t)b_rays, false, ctx);
     if (!rc) rc = bl_grow(&lc->d_boxes, &lc->cap_boxes, (size_t)(slots * (a.W2 > 0 ? a.W2 : 1)) * sizeof(int4), false, ctx);
     if (!rc) rc = lc_grow_keep(&lc->d_sub, &lc->cap_sub, (size_t)b_sub, ctx);
@@ -502,7 +526,22 @@ extern "C" int bl_loopclose_find(bl_loopclose* lc, bl_scanlog* log, const bl_gri
     hipStream_t st = ctx->stream;
     const unsigned ntiles = (unsigned)(((a.S + RL_TILE - 1) / RL_TILE) * ((a.S + RL_TILE - 1) / RL_TILE));
     BL_HIP(hipEventRecord(lc->ev[0], st));
-    hipLaunchKernelGGL(k_lc_pairs, dim3(a.Q), dim3(64), 0, st, a);
+    if (place) {
+        pr_args p;
+        memset(&p, 0, sizeof(p));
+        p.n = n; p.Q = a.Q; p.stride = a.stride; p.min_gap = a.min_gap;
+        p.head = a.head; p.capacity = a.capacity; p.max_rays = a.max_rays;
+        p.bins_per_meter = place->bins_per_meter; p.max_range = place->max_range;
+        p.dilate = place->dilate; p.min_key = place->min_key; p.min_bits = place->min_bits;
+        p.scans = a.scans; p.kept = a.kept;
+        p.desc = (uint32_t*)lc->d_desc; p.bits = (int32_t*)lc->d_bits; p.place = (bl_place_t*)lc->d_place; p.partner = a.partner;
+        a.place = p.place;
+        lc->place_n = n; lc->place_Q = a.Q; lc->placed = true;
+        hipLaunchKernelGGL(k_pr_describe, dim3(n), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(k_pr_match, dim3(a.Q), dim3(64 * PR_WAVES), 0, st, p);
+    } else {
+        hipLaunchKernelGGL(k_lc_pairs, dim3(a.Q), dim3(64), 0, st, a);
+    }
     hipLaunchKernelGGL(k_lc_number, dim3(1), dim3(1024), 0, st, a);
     BL_HIP(hipEventRecord(lc->ev[1], st));
     hipLaunchKernelGGL(k_lc_prep, dim3(a.slots), dim3(256), 0, st, a);
@@ -528,7 +567,7 @@ extern "C" int bl_loopclose_find(bl_loopclose* lc, bl_scanlog* log, const bl_gri
     BL_HIP(hipMemcpyAsync(h_rec, lc->d_rec, (size_t)a.slots * sizeof(bl_loopclose_candidate_t), hipMemcpyDeviceToHost, st));
     BL_HIP(hipStreamSynchronize(st));
     if (!h_state->ok) {
-        bl_set_error("bl_loopclose_find: %d queries have a partner, the handle holds %d", h_state->M, lc->maxc);
+        bl_set_error("%s: %d queries have a partner, the handle holds %d", place ? "bl_loopclose_find_places" : "bl_loopclose_find", h_state->M, lc->maxc);
         return BL_ERR_ARG;
     }
     const int M = h_state->M;
@@ -538,6 +577,46 @@ extern "C" int bl_loopclose_find(bl_loopclose* lc, bl_scanlog* log, const bl_gri
     for (int m = 0; m < M; ++m)
         if ((*lc->recs)[m].flags == 0) lc_edge(&(*lc->recs)[m], (*lc->cands)[m], (double)a.mpc, (double)a.dtheta);
     *n_candidates = M;
+    return BL_OK;
+}
+
+extern "C" int bl_loopclose_find(bl_loopclose* lc, bl_scanlog* log, const bl_grid* like, const bl_loopclose_params_t* prm, int* n_candidates)
+{
+    BL_CHECK_ARG(lc != nullptr && log != nullptr && like != nullptr && prm != nullptr && n_candidates != nullptr);
+    return lc_find(lc, log, like, prm, nullptr, n_candidates);
+}
+
+extern "C" int bl_loopclose_find_places(bl_loopclose* lc, bl_scanlog* log, const bl_grid* like, const bl_loopclose_params_t* prm,
+                                        const bl_place_params_t* place, int* n_candidates)
+{
+    BL_CHECK_ARG(lc != nullptr && log != nullptr && like != nullptr && prm != nullptr && place != nullptr && n_candidates != nullptr);
+    return lc_find(lc, log, like, prm, place, n_candidates);
+}
+
+// diagnostics of the last find_places that launched
+extern "C" int bl_loopclose_places(bl_loopclose* lc, int* n_queries, bl_place_t* out)
+{
+    BL_CHECK_ARG(lc != nullptr && n_queries != nullptr);
+    if (!lc->placed) { bl_set_error("bl_loopclose_places: no find_places yet"); return BL_ERR_STATE; }
+    if (out) {
+        BL_HIP(hipSetDevice(lc->ctx->device));
+        BL_HIP(hipMemcpyAsync(out, lc->d_place, (size_t)lc->place_Q * sizeof(bl_place_t), hipMemcpyDeviceToHost, lc->ctx->stream));
+        BL_HIP(hipStreamSynchronize(lc->ctx->stream));
+    }
+    *n_queries = lc->place_Q;
+    return BL_OK;
+}
+
+extern "C" int bl_loopclose_descriptors(bl_loopclose* lc, int* n_entries, uint32_t* words, int32_t* bits)
+{
+    BL_CHECK_ARG(lc != nullptr && n_entries != nullptr);
+    if (!lc->placed) { bl_set_error("bl_loopclose_descriptors: no find_places yet"); return BL_ERR_STATE; }
+    BL_HIP(hipSetDevice(lc->ctx->device));
+    const size_t n = (size_t)lc->place_n;
+    if (words) BL_HIP(hipMemcpyAsync(words, lc->d_desc, n * PR_SECTORS * sizeof(uint32_t), hipMemcpyDeviceToHost, lc->ctx->stream));
+    if (bits) BL_HIP(hipMemcpyAsync(bits, lc->d_bits, n * sizeof(int32_t), hipMemcpyDeviceToHost, lc->ctx->stream));
+    BL_HIP(hipStreamSynchronize(lc->ctx->stream));
+    *n_entries = lc->place_n;
     return BL_OK;
 }
 

@@ -2434,6 +2434,8 @@ SCAN_MATCH_MOMENTS_DTYPE = np.dtype([(n, "<i8") for n in ("s0", "sx", "sy", "st"
 LOOPCLOSE_CANDIDATE_DTYPE = np.dtype([("q", "<i4"), ("j", "<i4"), ("first", "<i4"), ("count", "<i4"), ("flags", "<u4"), ("pad", "<i4"),
                                       ("result", SCAN_MATCH_RESULT_DTYPE), ("moments", SCAN_MATCH_MOMENTS_DTYPE), ("edge", POSEGRAPH_EDGE_DTYPE)])
 assert SCAN_MATCH_RESULT_DTYPE.itemsize == 56 and SCAN_MATCH_MOMENTS_DTYPE.itemsize == 112 and LOOPCLOSE_CANDIDATE_DTYPE.itemsize == 272
+LOOPCLOSE_PLACE_DTYPE = np.dtype([(n, "<i4") for n in ("q", "j", "shift", "key", "overlap", "bits_q", "bits_j", "partner")])
+assert LOOPCLOSE_PLACE_DTYPE.itemsize == 32
 LC_NOT_ACCEPTED, LC_TIED, LC_ON_EDGE, LC_TOO_MANY_RAYS = _capi.LC_NOT_ACCEPTED, _capi.LC_TIED, _capi.LC_ON_EDGE, _capi.LC_TOO_MANY_RAYS
 
 
@@ -2461,6 +2463,43 @@ class LoopCloser:
         check(self.ctx.lib.bl_loopclose_find(self.h, history.h, like_grid.h, C.byref(prm), C.byref(m)))
         self.n_candidates, self.submap_cells = m.value, int(submap_cells)
         return self.edges()
+
+    def find_places(self, history, like_grid, bins_per_meter=4.0, place_max_range=8.0, dilate=1, min_key=16384, min_bits=8, stride=4,
+                    min_gap=40, w=5, submap_cells=200, nx=8, ny=8, ntheta=12, dtheta=math.radians(0.5), max_range=8.0, half_life=64,
+                    min_score=0, maxLaserDistance=5.0, hitOdds=3, missOdds=1, prior=(0, 0, 0, 0)):
+        """find with the partner chosen by what the scans look like, not by where odometry says they were taken
+        (bl_loopclose_find_places, include/botlab_hip.h, "loop closure by place recognition"): every scan's 64 x 32 bit descriptor,
+        per query the older scan and circular shift of greatest overlap, the match centred on that scan's pose turned by the shift.
+        The other keywords are find's; there is no radius.
+
+        bins_per_meter, dilate, min_key and min_bits are untuned knobs."""
+        match = _capi.ScanMatchParams(int(nx), int(ny), int(ntheta), float(np.float32(dtheta)), float(np.float32(max_range)), int(min_score), 0)
+        pr = _capi.ScanMatchPrior(int(prior[0]), int(prior[1]), int(prior[2]), int(prior[3]), int(half_life), 1)
+        prm = _capi.LoopCloseParams(int(stride), int(min_gap), 0.0, int(w), int(submap_cells), float(np.float32(maxLaserDistance)),
+                                    int(hitOdds), int(missOdds), match, pr)
+        pl = _capi.PlaceParams(float(np.float32(bins_per_meter)), float(np.float32(place_max_range)), int(dilate), int(min_key), int(min_bits))
+        m = C.c_int()
+        check(self.ctx.lib.bl_loopclose_find_places(self.h, history.h, like_grid.h, C.byref(prm), C.byref(pl), C.byref(m)))
+        self.n_candidates, self.submap_cells = m.value, int(submap_cells)
+        return self.edges()
+
+    def places(self):
+        """LOOPCLOSE_PLACE_DTYPE [queries]: q, j, shift, key, overlap, bits_q, bits_j, partner of the last find_places that launched."""
+        n = C.c_int()
+        check(self.ctx.lib.bl_loopclose_places(self.h, C.byref(n), None))
+        out = np.zeros(n.value, LOOPCLOSE_PLACE_DTYPE)
+        if n.value:
+            check(self.ctx.lib.bl_loopclose_places(self.h, C.byref(n), out.ctypes.data))
+        return out
+
+    def descriptors(self):
+        """(words uint32 [n][64], bits int32 [n]) of the n log entries of the last find_places that launched."""
+        n = C.c_int()
+        check(self.ctx.lib.bl_loopclose_descriptors(self.h, C.byref(n), None, None))
+        words, bits = np.zeros((n.value, _capi.PLACE_SECTORS), np.uint32), np.zeros(n.value, np.int32)
+        if n.value:
+            check(self.ctx.lib.bl_loopclose_descriptors(self.h, C.byref(n), words.ctypes.data, bits.ctypes.data))
+        return words, bits
 
     def edges(self):
         n = C.c_int()

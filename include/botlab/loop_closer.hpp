@@ -2,6 +2,8 @@
 // find() makes the loop edges of a ScanHistoryT (map_rebuild.hpp) -- every candidate pair, submap, match and edge in one sequence of
 // launches -- and close() gates them through a PoseGraphT (pose_graph.hpp) and writes the corrected poses back into the history.
 // OccupancyGridSLAMT::closeLoops (slam_driver.hpp) is find, close and rebuildMap on the driver's history.
+// findPlaces() is find() with the partner chosen by the scans' descriptors instead of the recorded poses ("loop closure by place
+// recognition"), for a drift larger than the radius; closeLoopsByPlace is the driver's call with it.
 //
 // Every rule is the C header's.  C++11.
 #ifndef BOTLAB_LOOP_CLOSER_HPP
@@ -25,6 +27,14 @@ inline bl_loopclose_params_t loopCloseParams()
     p.match.nx = 8; p.match.ny = 8; p.match.ntheta = 12; p.match.dtheta = 0.00872664625997164788f; p.match.max_range = 8.0f;
     p.match.min_score = 0; p.match.keep_volume = 0;
     p.prior.a_xx = 0; p.prior.a_xy = 0; p.prior.a_yy = 0; p.prior.a_tt = 0; p.prior.half_life = 64; p.prior.want_moments = 1;
+    return p;
+}
+
+// botlab_amd.LoopCloser.find_places' defaults; bins_per_meter, dilate, min_key and min_bits are untuned knobs
+inline bl_place_params_t placeParams()
+{
+    bl_place_params_t p;
+    p.bins_per_meter = 4.0f; p.max_range = 8.0f; p.dilate = 1; p.min_key = 16384; p.min_bits = 8;
     return p;
 }
 
@@ -58,6 +68,30 @@ public:
         check(bl_loopclose_find(h_, log, like, &params, &m), "bl_loopclose_find");
         m_ = m; cells_ = params.submap_cells;
         return edges();
+    }
+    // find with the partners by place recognition: params.radius is not read
+    std::vector<bl_posegraph_edge_t> findPlaces(const ScanHistoryT<Pose, Lidar>& history, OccupancyGrid& like, const bl_loopclose_params_t& params,
+                                                const bl_place_params_t& place)
+    {
+        return findPlaces(history.device(), like.device(), params, place);
+    }
+    std::vector<bl_posegraph_edge_t> findPlaces(bl_scanlog* log, const bl_grid* like, const bl_loopclose_params_t& params,
+                                                const bl_place_params_t& place)
+    {
+        int m = 0;
+        check(bl_loopclose_find_places(h_, log, like, &params, &place, &m), "bl_loopclose_find_places");
+        m_ = m; cells_ = params.submap_cells;
+        return edges();
+    }
+    // every query's best pair of the last findPlaces that launched
+    std::vector<bl_place_t> places() const
+    {
+        int n = 0;
+        check(bl_loopclose_places(h_, &n, nullptr), "bl_loopclose_places");
+        std::vector<bl_place_t> p(static_cast<std::size_t>(n > 0 ? n : 1));
+        check(bl_loopclose_places(h_, &n, p.data()), "bl_loopclose_places");
+        p.resize(static_cast<std::size_t>(n));
+        return p;
     }
     std::vector<bl_posegraph_edge_t> edges() const
     {

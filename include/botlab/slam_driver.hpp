@@ -447,15 +447,18 @@ public:
                    const bl_posegraph_params_t& graphParams = poseGraphParams())
     {
         if (!history_ || history_->size() < 2) return 0;
-        const int n = history_->size();
-        const int queries = params.stride >= 1 ? (n + params.stride - 1) / params.stride : 1;
-        LoopCloserT<Pose, Lidar> closer(queries < BL_LC_MAX_CANDIDATES ? queries : BL_LC_MAX_CANDIDATES);
-        const std::vector<bl_posegraph_edge_t> candidates = closer.find(*history_, grid_, params);
-        PoseGraphT<Pose> graph(n, static_cast<int>(candidates.size()), static_cast<int>(candidates.size()) + 1);
-        const LoopCloseOutcome outcome = LoopCloserT<Pose, Lidar>::close(*history_, graph, candidates, chainInfo, gate, graphParams);
-        poseGraphResult_ = outcome.result;
-        rebuildMap();
-        return static_cast<int>(outcome.kept.size());
+        LoopCloserT<Pose, Lidar> closer(loopCloserSlots(params));
+        return closeCandidates(closer.find(*history_, grid_, params), chainInfo, gate, graphParams);
+    }
+    // (extension) closeLoops with the partners chosen by place recognition (LoopCloserT::findPlaces), for a history
+    // whose drift is beyond any radius: find by place, close, rebuildMap().  params.radius is not read.  Off unless called; the place
+    // parameters are untuned knobs too.
+    int closeLoopsByPlace(const bl_loopclose_params_t& params, const bl_place_params_t& place, const double chainInfo[6], double gate = 11.345,
+                          const bl_posegraph_params_t& graphParams = poseGraphParams())
+    {
+        if (!history_ || history_->size() < 2) return 0;
+        LoopCloserT<Pose, Lidar> closer(loopCloserSlots(params));
+        return closeCandidates(closer.findPlaces(*history_, grid_, params, place), chainInfo, gate, graphParams);
     }
     // (extension) The seed of the filter's first cloud, for runs that can be repeated (the reference, and the default here, take
     // it from the OS).  Set before the first iteration.
@@ -514,6 +517,23 @@ public:
 
 private:
     enum { kDroppedBeforeNotice = 10, kFewestRanges = 100, kMapEvery = 5 };
+
+    // what closeLoops and closeLoopsByPlace share: a handle with a slot per query, and close + rebuildMap on the candidates found
+    int loopCloserSlots(const bl_loopclose_params_t& params) const
+    {
+        const int n = history_->size();
+        const int queries = params.stride >= 1 ? (n + params.stride - 1) / params.stride : 1;
+        return queries < BL_LC_MAX_CANDIDATES ? queries : BL_LC_MAX_CANDIDATES;
+    }
+    int closeCandidates(const std::vector<bl_posegraph_edge_t>& candidates, const double chainInfo[6], double gate,
+                        const bl_posegraph_params_t& graphParams)
+    {
+        PoseGraphT<Pose> graph(history_->size(), static_cast<int>(candidates.size()), static_cast<int>(candidates.size()) + 1);
+        const LoopCloseOutcome outcome = LoopCloserT<Pose, Lidar>::close(*history_, graph, candidates, chainInfo, gate, graphParams);
+        poseGraphResult_ = outcome.result;
+        rebuildMap();
+        return static_cast<int>(outcome.kept.size());
+    }
 
     // What the four modes of slam.hpp:72-78 differ in:  mapping-only = posesGiven;  localization-only = mapKnown from a file;
     // action-only = that + odometryOnly;  full SLAM = none of them (mapKnown turns true with the first map update).

@@ -1993,6 +1993,53 @@ int bl_loopclose_submap(bl_loopclose* lc, int m, int8_t* cells /* S * S */, floa
  * before the first find that launched */
 int bl_loopclose_last_device_ms(bl_loopclose* lc, float* ms, float* ms4);
 
+/* ------------------------------------------------------------------ loop closure by place recognition  
+ * The pair rule above finds a partner only while the drift of the recorded poses is smaller than `radius`.  find_places chooses the
+ * partner by what the scans look like instead: every logged scan gets a descriptor, a query's partner is the older scan whose
+ * descriptor it resembles most at the best circular shift, and the match is centred on the partner's pose turned by that shift.
+ * Everything is integer work on the bits of the logged floats; the numpy restatement is tests/place_model.py.
+ *
+ * Constants.  BL_PLACE_SECTORS = 64, BL_PLACE_BINS = 32, K = 10.185916f (the float nearest 32 / pi), STEP = 0.09817477f (the float
+ *   nearest 2 pi / 64).
+ * Parameters (bl_place_params_t).  bins_per_meter in (0, 1000]; max_range in (0.15, 1000]; dilate 0 or 1; min_key 0 .. 65536;
+ *   min_bits 0 .. 2048.  bins_per_meter, dilate, min_key and min_bits are untuned knobs.
+ * Descriptor of entry e: 64 words of 32 bits, all zero at first.  Ray r counts for every r < min(kept, max_rays) when the matcher's
+ *   own rule holds (range > 0.15f and range < max_range, with this struct's max_range) and fabsf(theta) <= 1024.0f (false for NaN).
+ *   Sector a = (int)floorf(theta * K) & 63, one float multiply.  Bin b = min((int)(range * bins_per_meter), 31), one float multiply,
+ *   truncated.  Bit b of word a is set.  bits[e] is the number of set bits.  The rays' times and the robot's motion during the scan
+ *   are ignored: the descriptor is that of the scan as it lies in the log.
+ * Query side.  D'q[a] = Dq[a] when dilate == 0, else Dq[a] | Dq[a] << 1 | Dq[a] >> 1 in uint32 (bits fall off both ends);
+ *   bits'q is the number of set bits of D'q.
+ * Score of (q, j, s), s = 0 .. 63.  ov = sum over a of popcount(D'q[(a + s) & 63] & Dj[a]); den = bits'q + bits[j] - ov;
+ *   key = den == 0 ? 0 : (ov * 65536) / den in unsigned integers (ov <= 2048).
+ * Best.  Queries are q = 0, stride, 2 stride, ... < n with last = q - min_gap - 1, as the pair search counts them.  j is eligible when
+ *   0 <= j <= last and bits[j] >= min_bits.  If bits[q] < min_bits or no j is eligible the query has no best: j = -1, partner = -1,
+ *   every other field but q and bits_q is 0.  Otherwise the best is the greatest key over the eligible j and all s; among equal keys
+ *   the lowest j wins, then the lowest s.  partner = j when key >= min_key, else -1; the best is recorded either way.
+ * Candidates.  The queries with a partner, numbered in ascending q.  first, count, origin and submap are those of the section above.
+ *   The centre of the match is (x_j, y_j, theta_c, utime_q) with theta_c = theta_j + (float)ss * STEP, ss = s < 32 ? s : s - 64; the
+ *   product and the sum are each rounded to float by itself, there is no fused operation and no wrap.  Match, gate, flags, record and
+ *   edge are the section above's word for word with this centre where the recorded pose of q stood.  params.radius is not read.
+ * Sign.  Ray i of a scan is cast at pose.theta - scan.theta, so two scans from one spot with headings theta_q and theta_j line up at
+ *   s near (theta_q - theta_j) * 64 / (2 pi), modulo 64.
+ * Calls.  find_places runs as find does and refuses what find refuses, the radius test left out and the limits above added; every
+ *   refusal leaves the last results readable and unchanged.  places returns the per-query records, descriptors the n x 64 words and
+ *   the n counts (either pointer may be NULL; n itself is handed back), both of the last find_places that launched; BL_ERR_STATE before one.  A plain find
+ *   leaves them as they were.  The first slot of last_device_ms's split then holds descriptors + best pairs. */
+#define BL_PLACE_SECTORS 64
+#define BL_PLACE_BINS 32
+typedef struct bl_place_params_t {
+    float bins_per_meter, max_range;
+    int32_t dilate, min_key, min_bits;
+} bl_place_params_t;                   /* 20 bytes: offsets 0, 4, 8, 12, 16 */
+typedef struct bl_place_t {
+    int32_t q, j, shift, key, overlap, bits_q, bits_j, partner;
+} bl_place_t;                          /* 32 bytes: offsets 0, 4, 8, 12, 16, 20, 24, 28 */
+int bl_loopclose_find_places(bl_loopclose* lc, bl_scanlog* log, const bl_grid* like, const bl_loopclose_params_t* params,
+                             const bl_place_params_t* place, int* n_candidates);
+int bl_loopclose_places(bl_loopclose* lc, int* n_queries, bl_place_t* out /* may be NULL: only the count */);
+int bl_loopclose_descriptors(bl_loopclose* lc, int* n, uint32_t* words /* n * 64, may be NULL */, int32_t* bits /* n, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
