@@ -33,6 +33,7 @@
 #define BL_PF_HELPER                   // this translation unit defines the header's bl_pf_cluster_pose with external linkage (bindings call it)
 #include "bl_internal.h"
 #include "bl_mcl_finish.h"
+#include "bl_pfmodel.h"
 
 #define MCL_LDS_RAYS 384                      // rays whose (range, theta, cos theta, sin theta) table is staged in LDS at a time (longer scans: several passes)
 #define MCL_BLOCK 512                         // threads of a k_mcl_main workgroup: within 3 % of the best of 256 / 512 / 1024 at 100k and 1M particles, 200x200
@@ -125,10 +126,7 @@ struct bl_pf {
     bl_particle_t* d_export;  // n_local
     // uniform utimes of the particle set (every particle carries the same pair; DESIGN.md "Particle utimes")
     int64_t pose_utime, parent_utime;
-    // ActionModel state (action_model.hpp:60-78)
-    bl_pose_xyt_t prev_odom;
-    bool action_initialized, moved;
-    double rot1, trans, rot2, rot1Std, transStd, rot2Std;
+    bl_action_state action;   // ActionModel::updateAction (bl_pfmodel.h)
     uint64_t noise_seed;
     uint32_t step;
     bool initialized;
@@ -217,8 +215,7 @@ __device__ __forceinline__ int clamp_from_m1(int x, int hi)
 
 // MAP_MODE: 0 = gathers from HBM/L2 only; 1 = the whole grid is staged in LDS; 2 = an LDS window of the zero-framed copy,
 // cells outside it gathered from that copy through L2 (packed scoring only).
-// Branch-free in modes 0 and 1: an off-grid cell reads a dummy slot and is masked to 0 (OccupancyGrid::logOdds,
-// occupancy_grid.cpp:63-71).
+// Branch-free in modes 0 and 1: an off-grid cell reads a dummy slot and is masked to 0 (bl_grid_odds, bl_pfmodel.h).
 template <int MAP_MODE>
 __device__ __forceinline__ int grid_odds(const int8_t* __restrict__ cells, const lds_i8_t* s_map, const map_window& win,
                                          const bl_frame& f, int x, int y)
@@ -233,33 +230,7 @@ __device__ __forceinline__ int grid_odds(const int8_t* __restrict__ cells, const
         return s_map[__mul24(cy, win.stride) + cx];
     }
     // modes 0 and 2 (lanes of the window mode that cannot take the packed path): bounds test + gather through L2
-    const bool in = (unsigned int)x < (unsigned int)f.width && (unsigned int)y < (unsigned int)f.height;
-    const int v = cells[in ? (size_t)y * f.width + x : (size_t)0];
-    return in ? v : 0;
-}
-
-// SensorModel::scoreRay (sensor_model.cpp:28-59) in half-units: returns 2*odds, o1 or o2 (score = that / 2).
-// The two neighbour cells are gathered unconditionally: within a 64-lane wave some ray always needs them, so the
-// early-out of the reference would only add divergence.
-template <int MAP_MODE>
-__device__ __forceinline__ int score_ray_half_units(const int8_t* __restrict__ cells, const lds_i8_t* s_map,
-                                                     const map_window& win, const bl_frame& f, float sx, float sy,
-                                                     int isx, int isy, float range, float cs, float sn)
-{
-    const float tx = range * cs * f.cpm, ty = range * sn * f.cpm;
-    const int ex = (int)(tx + sx);
-    const int ey = (int)(ty + sy);
-    // (2 * range * cos) * cpm == 2 * ((range * cos) * cpm) bit for bit: scaling by two is exact and commutes with
-    // rounding for normal floats (range > 0.15 and |cos| >= 4e-8 keep every product far from the subnormal range)
-    const int xx = (int)((2.0f * tx) + sx);
-    const int xy = (int)((2.0f * ty) + sy);
-    int ax, ay, bx, by;
-    bl_bresenham_first_step(ex, ey, isx, isy, &ax, &ay);
-    bl_bresenham_first_step(ex, ey, xx, xy, &bx, &by);
-    const int odds = grid_odds<MAP_MODE>(cells, s_map, win, f, ex, ey);
-    const int o1 = grid_odds<MAP_MODE>(cells, s_map, win, f, ax, ay);
-    const int o2 = grid_odds<MAP_MODE>(cells, s_map, win, f, bx, by);
-    return odds > 0 ? 2 * odds : (o1 > 0 ? o1 : (o2 > 0 ? o2 : 0));
+    return bl_grid_odds(cells, f, x, y);
 }
 
 // ---- packed 16-bit form of the scoring arithmetic (whole-grid LDS mode, no pose interpolation) ----------------------------
@@ -343,7 +314,7 @@ __device__ __forceinline__ int pk_pos(const pk_map_global& pm, short2_t c) { ret
 __device__ __forceinline__ int pk_at(const pk_map&, int pos) { return *(const lds_i8_t*)(size_t)(unsigned int)pos; }
 __device__ __forceinline__ int pk_at(const pk_map_global& pm, int pos) { return pm.base[pos]; }
 
-// SensorModel::scoreRay in half-units (see score_ray_half_units), packed form.  The float endpoint arithmetic is written on
+// SensorModel::scoreRay in half-units (see bl_score_ray_half_units, bl_pfmodel.h), packed form.  The float endpoint arithmetic is written on
 // (x, y) pairs as well (v_pk_mul_f32 / v_pk_add_f32): each lane-wise operation is the reference's own IEEE operation
 // (2.0f * t == t + t exactly).
 typedef float float2_t __attribute__((ext_vector_type(2)));
@@ -646,22 +617,6 @@ struct mcl_prefix_view {              // what the resampling search reads the cu
     __device__ __forceinline__ unsigned long long operator[](int i) const { return sh ? sh->prefix[i / sh->block][i] : flat[i]; }
 };
 
-__device__ __forceinline__ void philox_normals3(uint32_t m, uint32_t step, uint32_t k0, uint32_t k1, float z[3])
-{
-    uint32_t o[4];
-    bl_philox4x32(m, step, 0x6d636c31u, 0, k0, k1, o);
-    // (0,1] uniforms; Box-Muller
-    float u1 = ((float)(o[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    float u2 = ((float)(o[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    float u3 = ((float)(o[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    float u4 = ((float)(o[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
-    float s2, c2, c4;
-    sincosf(6.2831853071795864769f * u2, &s2, &c2);
-    c4 = cosf(6.2831853071795864769f * u4);
-    z[0] = ra * c2; z[1] = ra * s2; z[2] = rb * c4;
-}
-
 // The packed ray loops: lane `sub` of a particle's group takes rays sub, sub + split, ...  All lanes of a wave run the same
 // number of whole rounds (a scalar loop counter; the ray index only lives on as the LDS address of the table entry), and the
 // lanes with one more ray take it in a masked round behind the loop.
@@ -722,7 +677,7 @@ __device__ __forceinline__ int kary_pos(int lo, int hi, int step, int k) { retur
 // mode -- the reference's own sequentially rounded double cumulative c_i (k_pf_cumulative_strict; compared with T = U).
 __device__ __forceinline__ bool resample_reaches(double T, unsigned long long v, bool strict)
 {
-    return strict ? T <= __longlong_as_double((long long)v) : T <= (double)v;
+    return strict ? T <= __longlong_as_double((long long)v) : bl_resample_reaches(T, v);
 }
 
 // Q probes per lane and search in a round: 64 Q probes narrow a range by that factor per dependent round trip.  Measured at 100 000
@@ -1047,7 +1002,7 @@ __global__ __launch_bounds__(MCL_BLOCK) void k_mcl_main(mcl_args a)
     // cumulative, no prefix (uni_seg, bl_mcl_finish.h).  The same value in every lane of the launch.
     const int uni_n = a.resample ? a.state->uni_n : 0;
     if (a.resample && (!shared_pro || wave < pw)) {                  // whole waves: the narrowing is cooperative
-        if (pro_active) { rs_T = a.r + mp * a.M_inv; if (!a.strict && uni_n <= 0) rs_T *= a.state->S; }      // U (particle_filter.cpp:95), or U * S
+        if (pro_active) { rs_T = bl_resample_u(a.r, mp, a.M_inv); if (!a.strict && uni_n <= 0) rs_T = bl_resample_target(a.r, mp, a.M_inv, a.state->S); }   // U (particle_filter.cpp:95), or U * S
         if (uni_n > 0) { }
         else if (a.sh) resample_bracket(pview, a.N, rs_T, pro_active, lane, &rs_lo, &rs_hi, a.strict != 0);
         else resample_bracket<MCL_BRACKET_Q>(a.prefix, a.N, rs_T, pro_active, lane, &rs_lo, &rs_hi, a.strict != 0, pro_active ? mp : -1);
@@ -1077,22 +1032,19 @@ __global__ __launch_bounds__(MCL_BLOCK) void k_mcl_main(mcl_args a)
         }
         if (!injected)
         s = mcl_src_at(a, i);
-        // ---- ActionModel::applyAction (action_model.cpp:78-103)
-        float n1, n2, n3;
-        if (a.noise) {
-            n1 = a.noise[3 * jp]; n2 = a.noise[3 * jp + 1]; n3 = a.noise[3 * jp + 2];
-        } else {
-            float z[3];
-            philox_normals3((uint32_t)mp, a.step, a.seed_lo, a.seed_hi, z);
-            n1 = (float)(a.rot1 + a.rot1Std * (double)z[0]);
-            n2 = (float)(a.trans + a.transStd * (double)z[1]);
-            n3 = (float)(a.rot2 + a.rot2Std * (double)z[2]);
+        // ---- ActionModel::applyAction, written out: bl_pf_apply_action(a, mp, jp, s, px, py, pth) (bl_pfmodel.h) is its definition and
+        // these lines stay its twin.  As a call the prologue is scheduled differently around the double sincos and the headline lay 1.2 %
+        // below the parent's in five of five rounds (profiles/pfmodel_headline.json); test_gpu_rb_slam.py holds the two together.
+        float n1, n2, n3, z[3];
+        if (a.noise) { n1 = a.noise[3 * jp]; n2 = a.noise[3 * jp + 1]; n3 = a.noise[3 * jp + 2]; }
+        else {
+            bl_pf_normals3((uint32_t)mp, a.step, a.seed_lo, a.seed_hi, z);
+            n1 = (float)(a.rot1 + a.rot1Std * (double)z[0]); n2 = (float)(a.trans + a.transStd * (double)z[1]); n3 = (float)(a.rot2 + a.rot2Std * (double)z[2]);
         }
         const float head = s.z + n1;                        // float sum, then double libm cos/sin of it
         double hs, hc;
         sincos((double)head, &hs, &hc);                     // one argument reduction for both
-        px = (float)((double)s.x + (double)n2 * hc);
-        py = (float)((double)s.y + (double)n2 * hs);
+        px = (float)((double)s.x + (double)n2 * hc); py = (float)((double)s.y + (double)n2 * hs);
         pth = bl_wrap_to_pi(s.z + n1 + n3);
         if (a.cells) bl_global_to_grid(px, py, a.frame, &sx0, &sy0);
         bl_sincosf(pth, &pth_sin, &pth_cos);                 // (the estimate's partial sums need them anyway: particle_filter.cpp:151-152)
@@ -1171,20 +1123,16 @@ __global__ __launch_bounds__(MCL_BLOCK) void k_mcl_main(mcl_args a)
                 const bl_pose3 pe = {px, py, pth};
                 for (int n = sub; n < cnt; n += split) {    // the host uploads only rays with range > 0.15f (moving_laser_scan.cpp:24)
                     const float4 rt = s_ray[n];
-                    float theta, sx, sy;
-                    int isx, isy;
+                    float sx, sy, sn, cs; int isx, isy;
                     if (INTERP) {
                         bl_pose3 rp = bl_interpolate_pose(pb, pe, bl_interp_ratio(a.times[base + n], a.t_begin, a.t_den));
-                        theta = bl_wrap_to_pi(rp.theta - rt.y);
-                        bl_global_to_grid(rp.x, rp.y, a.frame, &sx, &sy);
-                        isx = (int)sx; isy = (int)sy;
-                    } else {
-                        theta = bl_wrap_to_pi(pth_r - rt.y);
+                        bl_ray_setup(a.frame, rp, rt.y, &sx, &sy, &isx, &isy, &sn, &cs);
+                    } else {                                // every ray leaves the pose itself, whose start the prologue left
                         sx = r_sx0; sy = r_sy0; isx = isx0; isy = isy0;
+                        bl_sincosf(bl_ray_theta(pth_r, rt.y), &sn, &cs);
                     }
-                    float sn, cs;
-                    bl_sincosf(theta, &sn, &cs);
-                    acc += score_ray_half_units<MAP_MODE>(a.cells, s_map, win, a.frame, sx, sy, isx, isy, rt.x, cs, sn);
+                    acc += bl_score_ray_half_units(a.frame.cpm, sx, sy, isx, isy, rt.x, cs, sn,
+                                                   [&](int x, int y) { return grid_odds<MAP_MODE>(a.cells, s_map, win, a.frame, x, y); });
                 }
             }
         }
@@ -1199,7 +1147,7 @@ __global__ __launch_bounds__(MCL_BLOCK) void k_mcl_main(mcl_args a)
     }
     if (shared_pro ? pro_active : (active && sub == 0)) {
         // ---- computeNormalizedPosterior (particle_filter.cpp:116-141): w = max(likelihood, 0.001) in units of 0.0005
-        const uint32_t units = a.cells ? (acc > 0 ? (uint32_t)acc * 1000u : 2u) : __float_as_uint(s.w);
+        const uint32_t units = a.cells ? (uint32_t)bl_score_units(acc) : __float_as_uint(s.w);
         a.dst[mp] = make_float4(px, py, pth, __uint_as_float(units));
         a.parent[jp] = make_float4(s.x, s.y, s.z, 0.0f);
         if (a.dbg_idx) { a.dbg_idx[jp] = i; a.dbg_like[jp] = acc; }
@@ -1350,7 +1298,7 @@ __global__ __launch_bounds__(256) void k_pf_resample_only(const unsigned long lo
 {
     const int m = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const bool on = m < N;
-    double T = on ? r + m * M_inv : 0.0;
+    double T = on ? bl_resample_u(r, m, M_inv) : 0.0;
     const int uni_n = state->uni_n;                                 // equal weights: the runs of the reference's cumulative (uni_seg)
     if (uni_n > 0) { if (on) out[m] = uni_search(state, uni_n, T, N); return; }
     if (!strict) T *= state->S;
@@ -1365,7 +1313,7 @@ __global__ __launch_bounds__(256) void k_pf_resample_next(const unsigned long lo
 {
     const int m = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
     const bool on = m < M;
-    double T = on ? r + m * M_inv : 0.0;
+    double T = on ? bl_resample_u(r, m, M_inv) : 0.0;
     const int uni_n = state->uni_n;
     if (uni_n > 0) { if (on) out[m] = uni_search(state, uni_n, T, N); return; }
     if (!strict) T *= state->S;
@@ -1610,12 +1558,8 @@ __global__ void k_pf_init(float4* rec, float4* parent, int N, int lo, int n_loca
     // initializeFilterAtPose (particle_filter.cpp:16-34): every rank fills the WHOLE record (it is replicated)
     int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= N) return;
-    float z[3];
-    philox_normals3((uint32_t)m, 0xffffffffu, k0, k1, z);
-    float x = (float)((double)pose.x + 0.01 * (double)z[0]);
-    float y = (float)((double)pose.y + 0.01 * (double)z[1]);
-    float th = bl_wrap_to_pi((float)((double)pose.theta + 0.01 * (double)z[2]));
-    if (m == N - 1) { x = pose.x; y = pose.y; th = pose.theta; }     // posterior_.back().pose = pose
+    float th, y, x;                                          // (in this order: the compiler's selects follow it, as they did inline)
+    bl_pf_init_draw(pose.x, pose.y, pose.theta, m, N, k0, k1, x, y, th);
     rec[m] = make_float4(x, y, th, __uint_as_float(1u));
     int j = m - lo;
     if (j >= 0 && j < n_local) parent[j] = make_float4(x, y, th, 0.0f);
@@ -1636,10 +1580,7 @@ __global__ void k_pf_export(const float4* rec, const float4* parent, const pf_st
     if (j >= n_local) return;
     float4 r = rec[lo + j];
     float4 p = parent[j];
-    bl_particle_t o;
-    memset(&o, 0, sizeof(o));                                // the struct's padding bytes leave the device defined (zero)
-    o.pose.utime = pose_utime; o.pose.x = r.x; o.pose.y = r.y; o.pose.theta = r.z;
-    o.parent_pose.utime = parent_utime; o.parent_pose.x = p.x; o.parent_pose.y = p.y; o.parent_pose.theta = p.z;
+    bl_particle_t o; bl_particle_fill(&o, r, pose_utime, p, parent_utime);       // the struct's padding bytes leave the device defined (zero)
     o.weight = pf_export_weight(state, r.w);
     out[j] = o;
 }
@@ -1888,8 +1829,7 @@ static int pf_scan(bl_pf* pf, int which, int write_pose, int64_t utime)
 
 static void pf_reset_action(bl_pf* pf)
 {
-    pf->action_initialized = false; pf->moved = false;
-    pf->rot1 = pf->trans = pf->rot2 = 0;
+    bl_action_reset(pf->action);
     pf->step = 0;
     pf->pending_end = false;
 }
@@ -2004,27 +1944,6 @@ extern "C" int bl_pf_set_noise_seed(bl_pf* pf, uint64_t seed)
     BL_CHECK_ARG(pf != nullptr);
     pf->noise_seed = seed;
     return BL_OK;
-}
-
-// ActionModel::updateAction (action_model.cpp:22-75) -- host scalars, same libm calls as the reference
-static bool action_update(bl_pf* pf, const bl_pose_xyt_t& odometry)
-{
-    if (!pf->action_initialized) { pf->prev_odom = odometry; pf->action_initialized = true; }
-    float deltaX = odometry.x - pf->prev_odom.x;
-    float deltaY = odometry.y - pf->prev_odom.y;
-    float deltaTheta = (float)bl_angle_diff(odometry.theta, pf->prev_odom.theta);
-    float dir = 1.0;
-    pf->rot1 = bl_angle_diff(atan2f(deltaY, deltaX), pf->prev_odom.theta);
-    pf->trans = sqrtf(deltaX * deltaX + deltaY * deltaY);
-    if (fabs(pf->trans) < 0.0001) { pf->rot1 = 0.0f; }
-    else if (fabs(pf->rot1) > BL_PI / 2.0) { pf->rot1 = -bl_angle_diff(BL_PI, pf->rot1); dir = -1.0; }
-    // (the reference's third branch, |rot1| < -pi/2, can never be taken: action_model.cpp:44-47)
-    pf->trans *= dir;
-    pf->rot2 = bl_angle_diff(deltaTheta, pf->rot1);
-    pf->moved = !((fabs(pf->trans) + fabs(pf->rot2)) < 0.00001f);
-    pf->rot1Std = 0.05; pf->transStd = 0.005; pf->rot2Std = 0.05;
-    pf->prev_odom = odometry;
-    return pf->moved;
 }
 
 // parity mode: 3 * n floats for the n output particles of the update (n_local, or next in adaptive mode)
@@ -2227,9 +2146,9 @@ static int pf_launch_main(bl_pf* pf, const bl_grid* map, int R, int rand_value, 
     a.R = R;
     a.N = pf->N; a.lo = pf->lo; a.n_local = n_out;                  // (adaptive: N active records searched, n_out = next drawn)
     a.M_inv = 1.0 / (resize ? n_out : pf->N);                        // particle_filter.cpp:89
-    a.r = (((double)rand_value) / (double)RAND_MAX) * a.M_inv;       // particle_filter.cpp:92
-    a.rot1 = pf->rot1; a.trans = pf->trans; a.rot2 = pf->rot2;
-    a.rot1Std = pf->rot1Std; a.transStd = pf->transStd; a.rot2Std = pf->rot2Std;
+    a.r = bl_resample_offset(rand_value, a.M_inv);
+    a.rot1 = pf->action.rot1; a.trans = pf->action.trans; a.rot2 = pf->action.rot2;
+    a.rot1Std = pf->action.rot1Std; a.transStd = pf->action.transStd; a.rot2Std = pf->action.rot2Std;
     a.noise = noise ? pf->d_noise : nullptr;
     a.seed_lo = (uint32_t)pf->noise_seed; a.seed_hi = (uint32_t)(pf->noise_seed >> 32);
     a.step = pf->step;
@@ -2434,7 +2353,7 @@ extern "C" int bl_pf_update_begin(bl_pf* pf, const bl_pose_xyt_t* odometry, cons
     if (pf->pending_end) { bl_set_error("bl_pf_update_begin called twice without bl_pf_update_end"); return BL_ERR_STATE; }
     if (pf->sh_broken) { bl_set_error("the shard exchange of this particle set gave up earlier: set the shards up again or re-initialise the filter"); return BL_ERR_STATE; }
     BL_HIP(hipSetDevice(pf->ctx->device));
-    bool mv = action_update(pf, *odometry);
+    bool mv = bl_action_update(pf->action, *odometry);
     if (moved) *moved = mv ? 1 : 0;
     pf->pending_utime = odometry->utime;
     if (!mv) {
@@ -3019,7 +2938,7 @@ extern "C" int bl_pf_update_action_only(bl_pf* pf, const bl_pose_xyt_t* odometry
     if (!pf->initialized || pf->pending_end) { bl_set_error("filter not initialised or update pending"); return BL_ERR_STATE; }
     if (pf->n_local != pf->N) { bl_set_error("updateFilterActionOnly needs the whole particle set on one device"); return BL_ERR_ARG; }
     BL_HIP(hipSetDevice(pf->ctx->device));
-    bool mv = action_update(pf, *odometry);
+    bool mv = bl_action_update(pf->action, *odometry);
     if (mv) {
         int rc = pf_launch_main(pf, nullptr, 0, 0, noise, 0);     // proposal = applyAction(posterior_) (particle_filter.cpp:60-61)
         if (rc) return rc;
@@ -3163,7 +3082,7 @@ extern "C" int bl_pf_debug_resample(bl_pf* pf, int rand_value, int32_t* out_idx)
     int M = pf->N;
     if (pf->ad_on || pf->N != pf->cap) { int rc = pf_adaptive_resolve(pf); if (rc) return rc; M = pf->ad_next; }
     const double M_inv = 1.0 / M;                                                  // particle_filter.cpp:89
-    const double r = (((double)rand_value) / (double)RAND_MAX) * M_inv;            // particle_filter.cpp:92
+    const double r = bl_resample_offset(rand_value, M_inv);
     if (M == pf->N)
         hipLaunchKernelGGL(k_pf_resample_only, dim3((pf->N + 255) / 256), dim3(256), 0, pf->ctx->stream, pf->prefix, pf->state, pf->N, r, M_inv,
                            pf->prefix_is_strict ? 1 : 0, pf->dbg_idx);

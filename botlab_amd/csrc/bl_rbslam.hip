@@ -12,12 +12,14 @@
 //   (k_rb_match  only with scan matching on, and then k_rb_weigh in its form without the action: bl_rbslam_match.h)
 //   k_rb_map     Mapping::updateMap of all P maps: a workgroup per (particle, window tile), hit and miss counts of the tile in an
 //                LDS window of uint16 counters, one owner thread per cell
-// The sensor model's and the mapper's arithmetic is restated here from bl_mcl.hip / bl_mapping.hip with bl_math.h's bit-exact pieces.
+// The motion and sensor model, the initial draw and the low-variance draw are bl_pfmodel.h's, which the filter (bl_mcl.hip) shares; the
+// mapper's ray cells and walk are bl_mapray_dev.h's.
 #include <stdio.h>
 #include <string.h>
 
 #include "bl_internal.h"
 #include "bl_mapray_dev.h"
+#include "bl_pfmodel.h"
 
 #define RB_MAX_PARTICLES 4096
 #define RB_PLAN_THREADS 1024
@@ -58,9 +60,7 @@ struct bl_rbslam {
     rb_state* h_state;                       // pinned
     bl_particle_t* d_export;
     int64_t pose_utime, parent_utime;
-    bl_pose_xyt_t prev_odom;
-    bool action_initialized;
-    double rot1, trans, rot2;
+    bl_action_state action;                  // ActionModel::updateAction (bl_pfmodel.h)
     uint64_t noise_seed; uint32_t step;
     bool initialized, map_latched;
     // scan matching (step 3b, bl_rbslam_match.h); the buffers exist once it has been switched on
@@ -73,22 +73,6 @@ struct bl_rbslam {
 };
 
 // ---------------------------------------------------------------- device helpers
-// ActionModel noise and initializeFilterAtPose draw exactly as bl_mcl.hip's filter does (same counters, same arithmetic)
-__device__ __forceinline__ void rb_philox_normals3(uint32_t m, uint32_t step, uint32_t k0, uint32_t k1, float z[3])
-{
-    uint32_t o[4];
-    bl_philox4x32(m, step, 0x6d636c31u, 0, k0, k1, o);
-    float u1 = ((float)(o[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    float u2 = ((float)(o[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    float u3 = ((float)(o[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    float u4 = ((float)(o[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    float ra = sqrtf(-2.0f * logf(u1)), rb = sqrtf(-2.0f * logf(u3));
-    float s2, c2, c4;
-    sincosf(6.2831853071795864769f * u2, &s2, &c2);
-    c4 = cosf(6.2831853071795864769f * u4);
-    z[0] = ra * c2; z[1] = ra * s2; z[2] = rb * c4;
-}
-
 template <class T>
 __device__ __forceinline__ T rb_wave_incl_scan(T v, int lane)
 {
@@ -192,7 +176,7 @@ __global__ __launch_bounds__(RB_PLAN_THREADS) void k_rb_plan(rb_plan_args a)
         for (int k = 0; k < RB_PLAN_ITEMS; ++k) if (i0 + k < P) a.idx[i0 + k] = i0 + k;
         return;
     }
-    // ---- low-variance search by the integer-prefix rule: T_m = (r + m / M) S, first i with T_m <= prefix_i, clamped to P - 1
+    // ---- low-variance search by the integer-prefix rule (bl_pfmodel.h): the first i whose prefix reaches T_m, clamped to P - 1
     const double Sd = (double)S;
     int src[RB_PLAN_ITEMS];
 #pragma unroll
@@ -200,9 +184,9 @@ __global__ __launch_bounds__(RB_PLAN_THREADS) void k_rb_plan(rb_plan_args a)
         const int m = i0 + k;
         src[k] = 0;
         if (m < P) {
-            const double T = (a.r + m * a.M_inv) * Sd;
+            const double T = bl_resample_target(a.r, m, a.M_inv, Sd);
             int lo = 0, hi = P - 1;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (T <= (double)s_pre[mid]) hi = mid; else lo = mid + 1; }
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (bl_resample_reaches(T, s_pre[mid])) hi = mid; else lo = mid + 1; }
             src[k] = lo;
             s_idx[m] = (unsigned short)lo;
         }
@@ -310,48 +294,6 @@ struct rb_weigh_args {
     long long* cum; unsigned long long* units; int32_t* like;
 };
 
-__device__ __forceinline__ int rb_grid_odds(const int8_t* __restrict__ cells, const bl_frame& f, int x, int y)
-{
-    const bool in = (unsigned int)x < (unsigned int)f.width && (unsigned int)y < (unsigned int)f.height;
-    const int v = cells[in ? (size_t)y * f.width + x : (size_t)0];
-    return in ? v : 0;                                          // OccupancyGrid::logOdds (occupancy_grid.cpp:63-71)
-}
-
-// SensorModel::scoreRay (sensor_model.cpp:28-59) in half-units: 2 * odds, o1 or o2
-__device__ __forceinline__ int rb_score_ray(const int8_t* __restrict__ cells, const bl_frame& f, float sx, float sy, float range, float cs, float sn)
-{
-    const float tx = range * cs * f.cpm, ty = range * sn * f.cpm;
-    const int ex = (int)(tx + sx), ey = (int)(ty + sy);
-    const int xx = (int)((2.0f * tx) + sx), xy = (int)((2.0f * ty) + sy);      // (2 range cos) cpm == 2 ((range cos) cpm) bit for bit
-    int ax, ay, bx, by;
-    bl_bresenham_first_step(ex, ey, (int)sx, (int)sy, &ax, &ay);
-    bl_bresenham_first_step(ex, ey, xx, xy, &bx, &by);
-    const int odds = rb_grid_odds(cells, f, ex, ey);
-    const int o1 = rb_grid_odds(cells, f, ax, ay);
-    const int o2 = rb_grid_odds(cells, f, bx, by);
-    return odds > 0 ? 2 * odds : (o1 > 0 ? o1 : (o2 > 0 ? o2 : 0));
-}
-
-// ActionModel::applyAction (action_model.cpp:78-103) of particle m from its source pose s
-__device__ __forceinline__ void rb_action(const rb_weigh_args& a, int m, const float4 s, float* px, float* py, float* pth)
-{
-    float n1, n2, n3;
-    if (a.noise) { n1 = a.noise[3 * m]; n2 = a.noise[3 * m + 1]; n3 = a.noise[3 * m + 2]; }
-    else {
-        float z[3];
-        rb_philox_normals3((uint32_t)m, a.step, a.seed_lo, a.seed_hi, z);
-        n1 = (float)(a.rot1 + a.rot1Std * (double)z[0]);
-        n2 = (float)(a.trans + a.transStd * (double)z[1]);
-        n3 = (float)(a.rot2 + a.rot2Std * (double)z[2]);
-    }
-    const float head = s.z + n1;
-    double hs, hc;
-    sincos((double)head, &hs, &hc);
-    *px = (float)((double)s.x + (double)n2 * hc);
-    *py = (float)((double)s.y + (double)n2 * hs);
-    *pth = bl_wrap_to_pi(s.z + n1 + n3);
-}
-
 // ACTION: step 3 and step 4 of particle m in one wave (the form every update without scan matching launches).  !ACTION: step 4
 // alone, on the pose and parent pose that k_rb_match (bl_rbslam_match.h) has left in dst and parent.
 template <bool ACTION>
@@ -364,7 +306,7 @@ __device__ __forceinline__ void rb_weigh_wave(const rb_weigh_args& a)
     float px, py, pth;
     if (ACTION) {
         s = a.src[a.idx[m]];
-        rb_action(a, m, s, &px, &py, &pth);                     // the same in every lane of the wave
+        bl_pf_apply_action(a, m, m, s, px, py, pth);            // the same in every lane of the wave
         if (lane == 0) { a.dst[m] = make_float4(px, py, pth, 0.0f); a.parent[m] = make_float4(s.x, s.y, s.z, 0.0f); }
     } else {
         s = a.parent[m];
@@ -376,12 +318,11 @@ __device__ __forceinline__ void rb_weigh_wave(const rb_weigh_args& a)
     const bl_pose3 pb = {s.x, s.y, s.z}, pe = {px, py, pth};
     int acc = 0;
     for (int n = lane; n < a.R; n += 64) {                      // the host keeps only rays with range > 0.15f (moving_laser_scan.cpp:24)
-        const bl_pose3 rp = a.interp ? bl_interpolate_pose(pb, pe, bl_interp_ratio(a.times[n], a.t_begin, a.t_den)) : pe;
-        const float theta = bl_wrap_to_pi(rp.theta - a.thetas[n]);
-        float sx, sy, sn, cs;
-        bl_global_to_grid(rp.x, rp.y, a.frame, &sx, &sy);
-        bl_sincosf(theta, &sn, &cs);
-        acc += rb_score_ray(cells, a.frame, sx, sy, a.ranges[n], cs, sn);
+        float sx, sy, sn, cs; int isx, isy;
+        const bl_pose3 rp = bl_ray_pose(a.interp != 0, pb, pe, a.times, n, a.t_begin, a.t_den);
+        bl_ray_setup(a.frame, rp, a.thetas[n], &sx, &sy, &isx, &isy, &sn, &cs);
+        acc += bl_score_ray_half_units(a.frame.cpm, sx, sy, isx, isy, a.ranges[n], cs, sn,
+                                       [&](int x, int y) { return bl_grid_odds(cells, a.frame, x, y); });
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if (lane == 0) {
@@ -389,7 +330,7 @@ __device__ __forceinline__ void rb_weigh_wave(const rb_weigh_args& a)
         if (c > RB_SCORE_SAT) c = RB_SCORE_SAT;
         a.cum[m] = c;
         a.like[m] = acc;
-        a.units[m] = c > 0 ? (unsigned long long)c * 1000ull : 2ull;
+        a.units[m] = bl_score_units(c);
     }
 }
 
@@ -565,15 +506,10 @@ __global__ __launch_bounds__(RB_MAP_THREADS) void k_rb_map(rb_map_args a)
 __global__ void k_rb_init(int P, bl_pose_xyt_t pose, uint32_t k0, uint32_t k1, float4* rec, float4* parent, long long* cum,
                           unsigned long long* units, int32_t* like, int32_t* idx, int32_t* slot)
 {
-    // initializeFilterAtPose (particle_filter.cpp:16-34), drawn as bl_pf_init_at_pose draws
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= P) return;
-    float z[3];
-    rb_philox_normals3((uint32_t)m, 0xffffffffu, k0, k1, z);
-    float x = (float)((double)pose.x + 0.01 * (double)z[0]);
-    float y = (float)((double)pose.y + 0.01 * (double)z[1]);
-    float th = bl_wrap_to_pi((float)((double)pose.theta + 0.01 * (double)z[2]));
-    if (m == P - 1) { x = pose.x; y = pose.y; th = pose.theta; }
+    float th, y, x;                                             // (in k_pf_init's order: the compiler's selects follow it)
+    bl_pf_init_draw(pose.x, pose.y, pose.theta, m, P, k0, k1, x, y, th);     // the filter's own draw (bl_pfmodel.h)
     rec[m] = make_float4(x, y, th, 0.0f);
     parent[m] = make_float4(x, y, th, 0.0f);
     cum[m] = 0; units[m] = 2ull; like[m] = 0; idx[m] = m; slot[m] = m;
@@ -585,10 +521,7 @@ __global__ void k_rb_export(int P, const float4* rec, const float4* parent, cons
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= P) return;
     const float4 r = rec[m], q = parent[m];
-    bl_particle_t o;
-    memset(&o, 0, sizeof(o));
-    o.pose.utime = pose_utime; o.pose.x = r.x; o.pose.y = r.y; o.pose.theta = r.z;
-    o.parent_pose.utime = parent_utime; o.parent_pose.x = q.x; o.parent_pose.y = q.y; o.parent_pose.theta = q.z;
+    bl_particle_t o; bl_particle_fill(&o, r, pose_utime, q, parent_utime);
     o.weight = (double)units[m] / (double)state->S;
     out[m] = o;
 }
@@ -721,8 +654,7 @@ static void rb_reset_run(bl_rbslam* rb, int64_t pose_utime, int64_t parent_utime
 {
     rb->cur = 0;
     rb->pose_utime = pose_utime; rb->parent_utime = parent_utime;
-    rb->action_initialized = false;
-    rb->rot1 = rb->trans = rb->rot2 = 0;
+    bl_action_reset(rb->action);
     rb->step = 0;
     rb->map_latched = false;
     rb->match_done = false; rb->match_path = -1;
@@ -758,7 +690,7 @@ extern "C" int bl_rbslam_set_particles(bl_rbslam* rb, const bl_particle_t* parti
         rec[m] = make_float4(particles[m].pose.x, particles[m].pose.y, particles[m].pose.theta, 0.0f);
         par[m] = make_float4(particles[m].parent_pose.x, particles[m].parent_pose.y, particles[m].parent_pose.theta, 0.0f);
         cum[m] = cum_scores ? cum_scores[m] : 0;
-        units[m] = cum[m] > 0 ? (unsigned long long)cum[m] * 1000ull : 2ull;
+        units[m] = bl_score_units(cum[m]);
     }
     rb->cur = 0;
     rb->pose_utime = particles[0].pose.utime; rb->parent_utime = particles[0].parent_pose.utime;
@@ -789,25 +721,6 @@ extern "C" int bl_rbslam_get_particles(bl_rbslam* rb, bl_particle_t* out, int64_
     if (units) BL_HIP(hipMemcpyAsync(units, rb->units, P * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     BL_HIP(hipStreamSynchronize(st));
     return BL_OK;
-}
-
-// ActionModel::updateAction (action_model.cpp:22-75) -- host scalars, as bl_pf_update's
-static bool rb_action_update(bl_rbslam* rb, const bl_pose_xyt_t& odometry)
-{
-    if (!rb->action_initialized) { rb->prev_odom = odometry; rb->action_initialized = true; }
-    float deltaX = odometry.x - rb->prev_odom.x;
-    float deltaY = odometry.y - rb->prev_odom.y;
-    float deltaTheta = (float)bl_angle_diff(odometry.theta, rb->prev_odom.theta);
-    float dir = 1.0;
-    rb->rot1 = bl_angle_diff(atan2f(deltaY, deltaX), rb->prev_odom.theta);
-    rb->trans = sqrtf(deltaX * deltaX + deltaY * deltaY);
-    if (fabs(rb->trans) < 0.0001) { rb->rot1 = 0.0f; }
-    else if (fabs(rb->rot1) > BL_PI / 2.0) { rb->rot1 = -bl_angle_diff(BL_PI, rb->rot1); dir = -1.0; }
-    rb->trans *= dir;
-    rb->rot2 = bl_angle_diff(deltaTheta, rb->rot1);
-    const bool moved = !((fabs(rb->trans) + fabs(rb->rot2)) < 0.00001f);
-    rb->prev_odom = odometry;
-    return moved;
 }
 
 // step 3b: the action and the match of every particle against its own map, one launch (bl_rbslam_match.h)
@@ -866,7 +779,7 @@ extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, co
         BL_CHECK_ARG(valid <= RBM_MAX_RAYS);
         match_rays = sm_valid_rays(scan, rb->match.max_range, rb->h_match_rays, rb->h_match_rays + RBM_MAX_RAYS, &match_reach);
     }
-    const bool moved = rb_action_update(rb, *odometry);
+    const bool moved = bl_action_update(rb->action, *odometry);
     const int P = rb->P;
     if (moved) {
         if (noise) {
@@ -876,7 +789,7 @@ extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, co
         rb_plan_args pa;
         pa.P = P; pa.units = rb->units; pa.state = rb->state; pa.idx = rb->idx; pa.slot = rb->slot; pa.copies = rb->copies; pa.cum = rb->cum;
         pa.M_inv = 1.0 / P;
-        pa.r = (((double)rand_value) / (double)RAND_MAX) * pa.M_inv;
+        pa.r = bl_resample_offset(rand_value, pa.M_inv);
         pa.num = rb->num; pa.den = rb->den;
         hipLaunchKernelGGL(k_rb_plan, dim3(1), dim3(RB_PLAN_THREADS), 0, st, pa);
         const int chunks = (int)((rb->stride / 16 + RB_COPY_THREADS * RB_COPY_VEC - 1) / (RB_COPY_THREADS * RB_COPY_VEC));
@@ -895,7 +808,7 @@ extern "C" int bl_rbslam_update(bl_rbslam* rb, const bl_pose_xyt_t* odometry, co
         wa.interp = rb->pose_utime != odometry->utime ? 1 : 0;
         wa.t_den = wa.interp ? (double)(odometry->utime - rb->pose_utime) : 1.0;
         wa.noise = noise ? rb->d_noise : nullptr;
-        wa.rot1 = rb->rot1; wa.trans = rb->trans; wa.rot2 = rb->rot2; wa.rot1Std = 0.05; wa.transStd = 0.005; wa.rot2Std = 0.05;
+        wa.rot1 = rb->action.rot1; wa.trans = rb->action.trans; wa.rot2 = rb->action.rot2; wa.rot1Std = rb->action.rot1Std; wa.transStd = rb->action.transStd; wa.rot2Std = rb->action.rot2Std;
         wa.seed_lo = (uint32_t)rb->noise_seed; wa.seed_hi = (uint32_t)(rb->noise_seed >> 32); wa.step = rb->step;
         wa.cum = rb->cum; wa.units = rb->units; wa.like = rb->like;
         if (!rb->match_on) {

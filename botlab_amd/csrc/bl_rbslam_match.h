@@ -1,6 +1,6 @@
 // bl_rbslam_match.h -- step 3b of a moved bl_rbslam_update with scan matching on: every particle matches the scan against ITS OWN map in
 // a small window around the pose the action left, and moves to the best pose there.  Included by bl_rbslam.hip (the object's struct is
-// private to that file), after rb_weigh_args and rb_action.  The definition is botlab_hip.h's "correlative scan matching" word for
+// private to that file), after rb_weigh_args.  The definition is botlab_hip.h's "correlative scan matching" word for
 // word, one match per particle; tests/rb_slam_match_model.py is the same over tests/scan_match_model.py.
 //
 // k_rb_match: ONE launch, a workgroup per particle, no atomics, no host round trip.
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(RBM_THREADS) void k_rb_match(rb_weigh_args a, rb_ma
     // ---- step 3, the same in every thread
     const float4 s = a.src[a.idx[m]];
     float px, py, pth;
-    rb_action(a, m, s, &px, &py, &pth);
+    bl_pf_apply_action(a, m, m, s, px, py, pth);
 
     // ---- the window of this particle
     float sx, sy;

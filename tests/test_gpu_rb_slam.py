@@ -217,3 +217,44 @@ def test_philox_mode_is_repeatable_and_seeded(maps, gpu_ctx):
     assert a == b
     assert a[0] != c[0] and a[1] != c[1]
     assert np.frombuffer(a[1], np.int8).any()
+
+
+def test_filter_and_rb_slam_share_the_devices_own_noise(gpu_ctx):
+    """The yardstick the Philox path has: bl_pfmodel.h's initial draw and applyAction run in k_pf_init / k_mcl_main and in k_rb_init /
+    k_rb_weigh.  One ParticleFilter and one RBSlam, P = 300 (two 256-thread blocks of the init kernels, 75 workgroups of k_rb_weigh),
+    the same init pose and seed and the same noise seed: bit-identical (x, y, theta) of every particle after initialisation, and of
+    every pose and parent pose after each of two moved steps -- the filter through updateFilterActionOnly, RB-SLAM through update on
+    a 40 x 40 map with an 8-ray scan and a resampling threshold that no weight set reaches (1 / 65535 < 1 / P <= Q / S^2)."""
+    P, W, H = 300, 40, 40
+    start = bl.make_pose(0.3, -0.2, 3.1, utime=1000)
+    pf = bl.ParticleFilter(P, ctx=gpu_ctx)
+    rb = bl.RBSlam(P, W, H, 0.05, CPM, (-1.0, -1.0), MAX_LASER, HIT, MISS, ctx=gpu_ctx)
+    rb.setResampling(1, 65535)
+    pf.setNoiseSeed(0x123456789abcdef)
+    rb.setNoiseSeed(0x123456789abcdef)
+    pf.initializeFilterAtPose(start, seed=77)
+    rb.initializeAtPose(start, seed=77)
+    fields = ["x", "y", "theta", "p_x", "p_y", "p_theta"]
+
+    def same(k):
+        a, b = pf.particles(), rb.particles()[0]
+        for f in fields:
+            assert a[f].tobytes() == b[f].tobytes(), (k, f)
+        return a
+
+    a0 = same("init")
+    assert len(np.unique(a0["x"])) > P // 2 and (a0["x"][-1], a0["y"][-1], a0["theta"][-1]) == (start.x, start.y, start.theta)
+    thetas = np.linspace(0.0, 5.5, 8).astype(np.float32)
+    prev = a0
+    for k, o in enumerate([(0.3, -0.2, 3.1, 1000), (0.25, -0.19, -3.12, 101000), (0.2, -0.21, -3.0, 201000)]):
+        scan = bl.LidarScan(np.full(8, 0.6, np.float32), thetas, np.linspace(o[3] - 90000, o[3], 8).astype(np.int64), utime=o[3])
+        odom = bl.make_pose(o[0], o[1], o[2], utime=o[3])
+        pf.updateFilterActionOnly(odom)
+        r = rb.update(odom, scan, rand_value=99 + k)
+        assert r["moved"] == (k > 0) and not r["resampled"], k
+        cur = same(k)
+        if k > 0:
+            assert cur["p_x"].tobytes() == prev["x"].tobytes() and cur["p_theta"].tobytes() == prev["theta"].tobytes(), k
+            assert np.count_nonzero(cur["x"] != prev["x"]) > P - 5, k
+        prev = cur
+    pf.close(); rb.close()
