@@ -278,6 +278,15 @@ class BeamParams(C.Structure):
 assert C.sizeof(BeamParams) == 56 and BeamParams.span.offset == 48
 
 
+class RangeTableInfo(C.Structure):
+    """bl_rangetable_info_t: the shape, headings, reach, occ_min and device bytes of a range table (32 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("headings", C.c_int32), ("reach", C.c_int32), ("occ_min", C.c_int32),
+                ("built", C.c_int32), ("bytes", C.c_int64)]
+
+
+assert C.sizeof(RangeTableInfo) == 32 and RangeTableInfo.bytes.offset == 24
+
+
 class ScanLogStats(C.Structure):
     """bl_scanlog_stats_t: the launch shape and the device time of the last map rebuild (64 bytes)."""
     _fields_ = [("tiles", C.c_int64), ("chunks", C.c_int64), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("chunk_scans", C.c_int32),
@@ -619,6 +628,17 @@ SIGNATURES = {
     "bl_beam_debug_set": (C.c_int, [_vp, C.c_int, C.c_int]),
     "bl_beam_debug_path": (C.c_int, [_vp]),
     "bl_beam_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_rangetable_create": (C.c_int, [_vp, C.c_int, _P(_vp)]),
+    "bl_rangetable_destroy": (None, [_vp]),
+    "bl_rangetable_build": (C.c_int, [_vp, _vp, _vp]),
+    "bl_rangetable_update": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bl_rangetable_read": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "bl_rangetable_directions": (C.c_int, [_vp, _vp]),
+    "bl_rangetable_info": (C.c_int, [_vp, _P(RangeTableInfo)]),
+    "bl_rangetable_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_rangetable_scores": (C.c_int, [_vp, _vp, _P(Lidar), _vp, C.c_int, _vp]),
+    "bl_rangetable_reweigh_pf": (C.c_int, [_vp, _vp, _vp, _P(Lidar), _P(Pose)]),
+    "bl_rangetable_debug_lookup": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _vp, _vp, _vp, _vp]),
     "bl_scanlog_create": (C.c_int, [_vp, C.c_int, C.c_int, _P(_vp)]),
     "bl_scanlog_destroy": (None, [_vp]),
     "bl_scanlog_append": (C.c_int, [_vp, _P(Lidar), _P(Pose)]),

@@ -14,6 +14,9 @@
 //                 of the grid outside a staged window (there is none by construction) would still be read from the grid.  The
 //                 three tables live in LDS.  Per pose a wave sum of the rays' integer logarithms (int64); per workgroup the largest score
 //                 and the path taken.
+//   k_beam_lookup the second scoring form ("range table" in the header): the same launch shape and records, but the expected range of a
+//                 ray is one uint16 of a range table (bl_rangetable.hip) -- the row of the pose's start cell at the ray's quantised
+//                 heading -- and the measured one the range in quarter cells: no sine, no walk.  Off unless called.
 //   k_beam_final  one workgroup: Smax over the workgroups' records, and how many workgroups took which path.
 //   k_beam_units  a thread per pose: the units, to the handle's array and, for a filter, into the record's weight word in place.
 //
@@ -22,16 +25,12 @@
 #include <math.h>
 #include <string.h>
 
-#include "bl_internal.h"
+#include "bl_beam_dev.h"
 
 #define BEAM_MIN_RANGE 0.15f              // moving_laser_scan.cpp:24, as the obstacle layer
 #define BEAM_THREADS 512
 #define BEAM_WAVE_POSES 4
 #define BEAM_WG_POSES ((BEAM_THREADS / 64) * BEAM_WAVE_POSES)
-#define BEAM_HIT 0                        // the tables' places in the block of BEAM_TABLE_WORDS words
-#define BEAM_SHORT 1024
-#define BEAM_LT 2048
-#define BEAM_TABLE_WORDS 2304
 #define BEAM_WINDOW_BYTES 40960           // a 200 x 200 grid whole; with the tables 50 176 bytes of LDS: three workgroups per CU
 #define BEAM_OFF INT64_MIN
 
@@ -57,16 +56,6 @@ __device__ __forceinline__ bool beam_start(const float4& p, const bl_frame& f, f
     if (!(__builtin_fabsf(*px) < 0x1p30f && __builtin_fabsf(*py) < 0x1p30f)) return false;
     *sx = (int)*px; *sy = (int)*py;
     return *sx >= 0 && *sx < f.width && *sy >= 0 && *sy < f.height;
-}
-
-__device__ __forceinline__ int beam_quarter(int ax, int ay, int bx, int by)
-{
-    const int dx = ax - bx, dy = ay - by;
-    const uint32_t v = 16u * (uint32_t)(dx * dx + dy * dy);            // below 2^31: the cells lie within reach + 2 <= 4098 of each other
-    uint32_t r = (uint32_t)__builtin_sqrtf((float)v);
-    while (r * r > v) --r;
-    while ((r + 1u) * (r + 1u) <= v) ++r;
-    return (int)r;
 }
 
 struct beam_window { int x0, y0, w, h; };
@@ -200,6 +189,73 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_cast(beam_args a)
         for (int k = 1; k < BEAM_THREADS / 64; ++k) best = s_max[k] > best ? s_max[k] : best;
         a.wg_max[blockIdx.x] = best;
         a.wg_path[blockIdx.x] = staged ? 0 : 1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- scoring by table
+struct beam_lookup_args {
+    const uint16_t* table; bl_frame f; int Hn;            // the range table and the frame it was built on
+    const float* ranges; const float* thetas; int R;
+    const float4* poses; int n;
+    float max_range, kf, q; int hit_cut;                  // kf = (float)(Hn / (2 pi)); q = 4.0f * cells_per_meter
+    uint32_t rnd, max_free, max_blocked; int ln2;
+    const uint32_t* tables;
+    long long* scores; long long* wg_max; uint8_t* wg_path;
+    int32_t* dbg;                                         // null, or [4][R] of pose 0: h, z, zstar, p
+};
+
+// k_beam_cast's launch shape and records; z* of a ray is one uint16 of the row of its pose's start cell
+__global__ __launch_bounds__(BEAM_THREADS) void k_beam_lookup(beam_lookup_args a)
+{
+    __shared__ uint32_t s_tab[BEAM_TABLE_WORDS];
+    __shared__ long long s_max[BEAM_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p0 = blockIdx.x * BEAM_WG_POSES;
+    for (int i = tid; i < BEAM_TABLE_WORDS; i += BEAM_THREADS) s_tab[i] = a.tables[i];
+    __syncthreads();
+    long long best = BEAM_OFF;
+    for (int q = 0; q < BEAM_WAVE_POSES; ++q) {
+        const int pi = p0 + wave * BEAM_WAVE_POSES + q;
+        if (pi >= a.n) break;                                           // (uniform over the wave)
+        const float4 pose = a.poses[pi];
+        float px, py; int sx, sy;
+        long long s = BEAM_OFF;
+        int32_t* dbg = (a.dbg && pi == 0) ? a.dbg : nullptr;
+        if (beam_start(pose, a.f, &px, &py, &sx, &sy)) {
+            const uint16_t* row = a.table + ((size_t)sy * a.f.width + sx) * a.Hn;
+            s = 0;
+            for (int r = lane; r < a.R; r += 64) {
+                const float range = a.ranges[r];
+                const float ang = bl_wrap_to_pi(pose.z - a.thetas[r]);
+                int h = -1, z = -1, zstar = -1, lgp = 0;
+                uint32_t p = 0;
+                if (__builtin_fabsf(ang) < __builtin_inff()) {
+                    h = (int)__builtin_floorf(ang * a.kf + 0.5f) & (a.Hn - 1);
+                    const int t = row[h];
+                    const bool expect = t != BL_RANGETABLE_NONE;
+                    if (expect) zstar = t;
+                    if (range >= a.max_range) {
+                        p = expect ? a.max_blocked : a.max_free;
+                    } else {
+                        z = (int)(range * a.q);
+                        p = beam_return_p(s_tab, a.rnd, a.hit_cut, expect, z, zstar);
+                    }
+                    lgp = beam_lg(s_tab, p, a.ln2);
+                }
+                if (dbg) { dbg[r] = h; dbg[a.R + r] = z; dbg[2 * a.R + r] = zstar; dbg[3 * a.R + r] = (int32_t)p; }
+                s += lgp;
+            }
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            best = s > best ? s : best;
+        }
+        if (lane == 0) a.scores[pi] = s;
+    }
+    if (lane == 0) s_max[wave] = best;
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < BEAM_THREADS / 64; ++k) best = s_max[k] > best ? s_max[k] : best;
+        a.wg_max[blockIdx.x] = best;
+        a.wg_path[blockIdx.x] = 1;                                      // nothing is staged: k_beam_final counts it with the direct ones
     }
 }
 
@@ -423,14 +479,39 @@ static int beam_stage_rays(bl_beam* b, const bl_lidar_t* scan, int* R_out)
     return BL_OK;
 }
 
+// what the scoring kernel of either form writes: n scores, n units, the workgroups' records
+static int beam_grow_outputs(bl_beam* b, int n, int blocks)
+{
+    bl_ctx* ctx = b->ctx;
+    int rc = bl_grow(&b->d_scores, &b->d_scores_cap, (size_t)n * 8, false, ctx);
+    if (!rc) rc = bl_grow(&b->d_units, &b->d_units_cap, (size_t)n * 4, false, ctx);
+    if (!rc) rc = bl_grow(&b->d_wg, &b->d_wg_cap, (size_t)blocks * 9, false, ctx);
+    return rc;
+}
+
+// behind the scoring kernel of either form: k_beam_final, k_beam_units (not for a debug launch: it leaves the last call's units and
+// count alone) and the closing event
+static int beam_launch_rest(bl_beam* b, int blocks, int n, float4* rec, bool debug)
+{
+    bl_ctx* ctx = b->ctx;
+    hipLaunchKernelGGL(k_beam_final, dim3(1), dim3(1024), 0, ctx->stream, (const long long*)b->d_wg, (const uint8_t*)b->d_wg + (size_t)blocks * 8, blocks,
+                       b->d_state);
+    if (!debug)
+        hipLaunchKernelGGL(k_beam_units, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const long long*)b->d_scores, n,
+                           (const beam_state*)b->d_state, (long long)b->params.span, (const uint32_t*)b->d_U, (uint32_t*)b->d_units, rec);
+    BL_HIP(hipGetLastError());
+    BL_HIP(hipEventRecord(b->ev_b, ctx->stream));
+    b->staged = true; b->timed = true;
+    if (!debug) b->last_n = n;
+    return BL_OK;
+}
+
 // the three launches for n poses at `poses` (device); rec: the filter's record for k_beam_units, or null
 static int beam_launch(bl_beam* b, const bl_grid* map, int reach, int R, const float4* poses, int n, float4* rec, int32_t* dbg)
 {
     bl_ctx* ctx = b->ctx;
     const int blocks = (n + BEAM_WG_POSES - 1) / BEAM_WG_POSES;
-    int rc = bl_grow(&b->d_scores, &b->d_scores_cap, (size_t)n * 8, false, ctx);
-    if (!rc) rc = bl_grow(&b->d_units, &b->d_units_cap, (size_t)n * 4, false, ctx);
-    if (!rc) rc = bl_grow(&b->d_wg, &b->d_wg_cap, (size_t)blocks * 9, false, ctx);
+    int rc = beam_grow_outputs(b, n, blocks);
     if (rc) return rc;
     const bl_beam_params_t& p = b->params;
     beam_args a;
@@ -448,15 +529,31 @@ static int beam_launch(bl_beam* b, const bl_grid* map, int reach, int R, const f
     BL_HIP(hipEventRecord(b->ev_a, ctx->stream));
     hipLaunchKernelGGL(k_beam_cast, dim3((unsigned int)blocks), dim3(BEAM_THREADS), BEAM_TABLE_WORDS * sizeof(uint32_t) + (b->stage ? (size_t)b->window_bytes : 0),
                        ctx->stream, a);
-    hipLaunchKernelGGL(k_beam_final, dim3(1), dim3(1024), 0, ctx->stream, (const long long*)a.wg_max, (const uint8_t*)a.wg_path, blocks, b->d_state);
-    if (!dbg)                                                           // (the debug cast leaves the last call's units and count alone)
-        hipLaunchKernelGGL(k_beam_units, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const long long*)a.scores, n,
-                           (const beam_state*)b->d_state, (long long)p.span, (const uint32_t*)b->d_U, (uint32_t*)b->d_units, rec);
-    BL_HIP(hipGetLastError());
-    BL_HIP(hipEventRecord(b->ev_b, ctx->stream));
-    b->staged = true; b->timed = true;
-    if (!dbg) b->last_n = n;
-    return BL_OK;
+    return beam_launch_rest(b, blocks, n, rec, dbg != nullptr);
+}
+
+// the same for the scoring by table: v is the table's view, checked by beam_check_table; dbg: [4][R] of pose 0, or null
+static int beam_launch_table(bl_beam* b, const bl_rangetable_view& v, int R, const float4* poses, int n, float4* rec, int32_t* dbg)
+{
+    bl_ctx* ctx = b->ctx;
+    const int blocks = (n + BEAM_WG_POSES - 1) / BEAM_WG_POSES;
+    int rc = beam_grow_outputs(b, n, blocks);
+    if (rc) return rc;
+    const bl_beam_params_t& p = b->params;
+    beam_lookup_args a;
+    a.table = v.d_table; a.f = v.frame; a.Hn = v.headings;
+    a.ranges = (const float*)b->d_rays; a.thetas = (const float*)b->d_rays + R; a.R = R;
+    a.poses = poses; a.n = n;
+    a.max_range = p.max_range; a.kf = (float)((double)v.headings / (2.0 * BL_PI)); a.q = 4.0f * v.frame.cpm; a.hit_cut = p.hit_cut;
+    a.rnd = beam_rand(p, v.reach); a.max_free = beam_max_free(p); a.max_blocked = beam_max_blocked(p);
+    a.ln2 = (int)beam_round(65536.0 * log(2.0));
+    a.tables = b->d_tab;
+    a.scores = (long long*)b->d_scores; a.wg_max = (long long*)b->d_wg; a.wg_path = (uint8_t*)b->d_wg + (size_t)blocks * 8;
+    a.dbg = dbg;
+    BL_HIP(hipEventRecord(b->ev_stage, ctx->stream));
+    BL_HIP(hipEventRecord(b->ev_a, ctx->stream));
+    hipLaunchKernelGGL(k_beam_lookup, dim3((unsigned int)blocks), dim3(BEAM_THREADS), 0, ctx->stream, a);
+    return beam_launch_rest(b, blocks, n, rec, dbg != nullptr);
 }
 
 static int beam_check_map(const bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, int* reach)
@@ -548,6 +645,104 @@ extern "C" int bl_beam_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_grid* map, con
     rc = beam_stage_rays(b, scan, &q.R);
     if (rc) return rc;
     return bl_pf_install_units(pf, b->ctx, beam_write_units, &q, out_pose);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- by table (host)
+void bl_beam_view_host(const bl_beam* b, bl_beam_view* out)
+{
+    out->ctx = b->ctx; out->have_params = b->have_params; out->max_range = b->params.max_range; out->occ_min = b->params.occ_min;
+}
+
+// the table's view, once it is known to be built on this ctx with the reach and occ_min the parameters in force give
+static int beam_check_table(const bl_beam* b, const bl_rangetable* rt, const bl_lidar_t* scan, bl_rangetable_view* v)
+{
+    BL_CHECK_ARG(rt != nullptr && scan != nullptr);
+    bl_rangetable_view_host(rt, v);
+    BL_CHECK_ARG(v->ctx == b->ctx);
+    if (!v->built) { bl_set_error("range table not built (bl_rangetable_build first)"); return BL_ERR_STATE; }
+    if (b->params.occ_min != v->occ_min) {
+        bl_set_error("range table built with occ_min %d, the beam model has %d", v->occ_min, b->params.occ_min);
+        return BL_ERR_STATE;
+    }
+    if (ceil((double)b->params.max_range * (double)v->frame.cpm) != (double)v->reach) {
+        bl_set_error("range table built with a reach of %d cells, the beam model's is another", v->reach);
+        return BL_ERR_STATE;
+    }
+    return BL_OK;
+}
+
+extern "C" int bl_rangetable_scores(bl_beam* b, const bl_rangetable* rt, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores)
+{
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    bl_rangetable_view v;
+    int R = 0;
+    rc = beam_check_table(b, rt, scan, &v);
+    if (rc) return rc;
+    BL_CHECK_ARG(n >= 0 && (n == 0 || (poses != nullptr && out_scores != nullptr)));
+    bl_ctx* ctx = b->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    rc = beam_stage_rays(b, scan, &R);
+    if (rc) return rc;
+    if (n == 0) { b->last_n = 0; return BL_OK; }
+    rc = beam_stage_poses(b, poses, n);
+    if (!rc) rc = beam_launch_table(b, v, R, (const float4*)b->d_poses, n, nullptr, nullptr);
+    if (rc) return rc;
+    BL_HIP(hipMemcpyAsync(out_scores, b->d_scores, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    BL_HIP(hipStreamSynchronize(ctx->stream));
+    return BL_OK;
+}
+
+extern "C" int bl_rangetable_debug_lookup(bl_beam* b, const bl_rangetable* rt, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_h,
+                                    int32_t* out_z, int32_t* out_zstar, uint32_t* out_p)
+{
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    bl_rangetable_view v;
+    int R = 0;
+    rc = beam_check_table(b, rt, scan, &v);
+    if (rc) return rc;
+    BL_CHECK_ARG(pose != nullptr);
+    bl_ctx* ctx = b->ctx;
+    BL_HIP(hipSetDevice(ctx->device));
+    rc = beam_stage_rays(b, scan, &R);
+    if (rc) return rc;
+    if (R == 0) return BL_OK;
+    rc = bl_grow(&b->d_dbg, &b->d_dbg_cap, 4 * (size_t)R * 4, false, ctx);
+    if (!rc) rc = beam_stage_poses(b, pose, 1);
+    if (rc) return rc;
+    BL_HIP(hipMemsetAsync(b->d_dbg, 0, 4 * (size_t)R * 4, ctx->stream));   // (an off-grid pose writes nothing)
+    rc = beam_launch_table(b, v, R, (const float4*)b->d_poses, 1, nullptr, (int32_t*)b->d_dbg);
+    if (rc) return rc;
+    void* outs[4] = {out_h, out_z, out_zstar, out_p};
+    for (int k = 0; k < 4; ++k)
+        if (outs[k]) BL_HIP(hipMemcpyAsync(outs[k], (const int32_t*)b->d_dbg + (size_t)k * R, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BL_HIP(hipStreamSynchronize(ctx->stream));
+    return BL_OK;
+}
+
+struct beam_install_table { bl_beam* b; bl_rangetable_view v; int R; };
+static int beam_write_units_table(void* user, float4* rec, int n)
+{
+    const beam_install_table* q = (const beam_install_table*)user;
+    return beam_launch_table(q->b, q->v, q->R, rec, n, rec, nullptr);
+}
+
+extern "C" int bl_rangetable_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_rangetable* rt, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose)
+{
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    beam_install_table q;
+    q.b = b;
+    rc = beam_check_table(b, rt, scan, &q.v);
+    if (rc) return rc;
+    BL_CHECK_ARG(pf != nullptr);
+    rc = bl_pf_install_units(pf, b->ctx, nullptr, nullptr, nullptr);   // the filter's state and ctx, before anything is enqueued
+    if (rc) return rc;
+    BL_HIP(hipSetDevice(b->ctx->device));
+    rc = beam_stage_rays(b, scan, &q.R);
+    if (rc) return rc;
+    return bl_pf_install_units(pf, b->ctx, beam_write_units_table, &q, out_pose);
 }
 
 extern "C" int bl_beam_units(bl_beam* b, uint32_t* out_units, int n)

@@ -193,6 +193,13 @@ void bl_obstracks_view_host(const bl_obstracks* tr, bl_obstracks_view* out);
 struct bl_scanlog_view { bl_ctx* ctx; int capacity, head, size; bl_pose_xyt_t* d_poses; };
 void bl_scanlog_view_host(const bl_scanlog* log, bl_scanlog_view* out);
 
+// bl_beam.hip: what the range table reads of a beam model when it is built (bl_rangetable.hip)
+struct bl_beam_view { bl_ctx* ctx; bool have_params; float max_range; int occ_min; };
+void bl_beam_view_host(const bl_beam* b, bl_beam_view* out);
+// bl_rangetable.hip: what the beam model's scoring by table reads of a range table (bl_beam.hip); d_table is null until the first build
+struct bl_rangetable_view { bl_ctx* ctx; bool built; bl_frame frame; int headings, reach, occ_min; const uint16_t* d_table; };
+void bl_rangetable_view_host(const bl_rangetable* rt, bl_rangetable_view* out);
+
 // RAII-less helpers
 int bl_timer_begin(bl_ctx* ctx, int id, hipEvent_t* a, hipEvent_t* b);
 int bl_timer_end(bl_ctx* ctx, int id, hipEvent_t a, hipEvent_t b);

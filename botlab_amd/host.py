@@ -444,6 +444,10 @@ class ParticleFilter:
         """The beam model's weights in place of the current ones (BeamModel.reweigh): the beam-weighted posterior pose."""
         return beam.reweigh(self, grid, scan)
 
+    def reweigh_beam_table(self, beam, table, scan):
+        """The same with the expected ranges looked up in a built RangeTable (BeamModel.reweigh_table)."""
+        return beam.reweigh_table(self, table, scan)
+
     def setStrictResampling(self, on=True):
         """Resample against the reference's own sequentially rounded cumulative weight (bl_pf_set_strict_resampling)."""
         check(self.ctx.lib.bl_pf_set_strict_resampling(self.h, 1 if on else 0))
@@ -1477,6 +1481,34 @@ class BeamModel:
         check(self.ctx.lib.bl_beam_reweigh_pf(self.h, pf.h, grid.h, C.byref(ls), C.byref(out)))
         return out
 
+    def scores_table(self, table, scan, poses):
+        """bl_rangetable_scores: scores() with the expected ranges looked up in a built RangeTable instead of cast against the map.
+        The table is not checked against the live map."""
+        q = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        hp = np.zeros(len(q), POSE_DTYPE)
+        hp["x"], hp["y"], hp["theta"] = q[:, 0], q[:, 1], q[:, 2]
+        out = np.zeros(max(len(q), 1), np.int64)
+        ls = scan.as_c()
+        check(self.ctx.lib.bl_rangetable_scores(self.h, table.h, C.byref(ls), hp.ctypes.data, len(q), out.ctypes.data))
+        return out[:len(q)]
+
+    def debug_lookup(self, table, scan, pose):
+        """dict of int64 arrays over the used rays of one pose (x, y, theta): h, z, zstar, p."""
+        ls = scan.as_c()
+        m = max(scan.num_ranges, 1)
+        a = [np.zeros(m, np.int32) for _ in range(3)] + [np.zeros(m, np.uint32)]
+        po = make_pose(*pose)
+        check(self.ctx.lib.bl_rangetable_debug_lookup(self.h, table.h, C.byref(ls), C.byref(po), *[v.ctypes.data for v in a]))
+        r = self.ctx.lib.bl_beam_last_rays(self.h)
+        return {k: v[:r].astype(np.int64) for k, v in zip(("h", "z", "zstar", "p"), a)}
+
+    def reweigh_table(self, pf, table, scan):
+        """bl_rangetable_reweigh_pf: reweigh() with the table behind it."""
+        ls = scan.as_c()
+        out = Pose()
+        check(self.ctx.lib.bl_rangetable_reweigh_pf(self.h, pf.h, table.h, C.byref(ls), C.byref(out)))
+        return out
+
     def debugSet(self, stage_windows=False, window_bytes=0):
         """Stage the workgroups' windows in LDS when they fit window_bytes (0: 40960).  Off by default: the grid is read directly."""
         check(self.ctx.lib.bl_beam_debug_set(self.h, 1 if stage_windows else 0, int(window_bytes)))
@@ -1493,6 +1525,58 @@ class BeamModel:
     def close(self):
         if self.h:
             self.ctx.lib.bl_beam_destroy(self.h)
+            self.h = None
+
+
+class RangeTable:
+    """Range table (bl_rangetable_*, include/botlab_hip.h): the beam model's expected range of every (cell, heading) of a map that does
+    not change, built once on the device and read by BeamModel.scores_table / reweigh_table.  build(beam, grid) takes reach and occ_min
+    from the beam model; update(grid, x0, y0, x1, y1) after the cells of that box (inclusive) changed.  The table is never checked
+    against the live map: keeping it current is the caller's job."""
+
+    NONE = 0xFFFF
+
+    def __init__(self, ctx=None, headings=256):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_rangetable_create(self.ctx.h, int(headings), C.byref(h)))
+        self.h = h
+
+    def build(self, beam, grid):
+        check(self.ctx.lib.bl_rangetable_build(self.h, beam.h, grid.h))
+
+    def update(self, grid, x0, y0, x1, y1):
+        check(self.ctx.lib.bl_rangetable_update(self.h, grid.h, int(x0), int(y0), int(x1), int(y1)))
+
+    def info(self):
+        """dict: width, height, headings, reach, occ_min, built, bytes."""
+        i = _capi.RangeTableInfo()
+        check(self.ctx.lib.bl_rangetable_info(self.h, C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in _capi.RangeTableInfo._fields_}
+
+    def read(self, x0=0, y0=0, w=None, h=None):
+        """uint16 [h][w][headings]: the entries of a rectangle of cells (default: from (x0, y0) to the far corner)."""
+        i = self.info()
+        w = i["width"] - x0 if w is None else w
+        h = i["height"] - y0 if h is None else h
+        out = np.zeros((max(h, 1), max(w, 1), i["headings"]), np.uint16)
+        check(self.ctx.lib.bl_rangetable_read(self.h, int(x0), int(y0), int(w), int(h), out.ctypes.data))
+        return out
+
+    def directions(self):
+        """int32 [headings][2]: D[h] of the built table."""
+        out = np.zeros((self.info()["headings"], 2), np.int32)
+        check(self.ctx.lib.bl_rangetable_directions(self.h, out.ctypes.data))
+        return out
+
+    def lastDeviceMs(self):
+        ms = C.c_float()
+        check(self.ctx.lib.bl_rangetable_last_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_rangetable_destroy(self.h)
             self.h = None
 
 

@@ -80,6 +80,42 @@ public:
         c.first.resize(r); c.K.resize(r); c.z.resize(r); c.zstar.resize(r); c.p.resize(r);
         return c;
     }
+    // scores() with the expected ranges looked up in a built range table (RangeTableT, range_table.hpp) instead of cast against the
+    // map.  The table is not checked against the live map.
+    template <class Table>
+    std::vector<int64_t> scoresTable(const Table& table, const Lidar& scan, const std::vector<Pose>& poses)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        std::vector<bl_pose_xyt_t> in(poses.size() ? poses.size() : 1);
+        for (std::size_t i = 0; i < poses.size(); ++i) in[i] = pose_in(poses[i]);
+        std::vector<int64_t> out(in.size());
+        check(bl_rangetable_scores(h_, table.device(), &v, in.data(), static_cast<int>(poses.size()), out.data()), "bl_rangetable_scores");
+        out.resize(poses.size());
+        return out;
+    }
+    // a filter's weight units replaced in place by the scoring by table (Filter: ParticleFilterT); the beam-weighted posterior pose
+    template <class Filter, class Table>
+    Pose reweighTable(Filter& pf, const Table& table, const Lidar& scan)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        bl_pose_xyt_t out;
+        check(bl_rangetable_reweigh_pf(h_, pf.device(), table.device(), &v, &out), "bl_rangetable_reweigh_pf");
+        return pose_out<Pose>(out);
+    }
+    // the per-ray values of one pose's used rays by table (first and K stay empty; h: the heading looked up)
+    template <class Table>
+    BeamCast debugLookup(const Table& table, const Lidar& scan, const Pose& pose, std::vector<int32_t>* h)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        bl_pose_xyt_t p = pose_in(pose);
+        const std::size_t m = static_cast<std::size_t>(v.num_ranges > 0 ? v.num_ranges : 1);
+        BeamCast c;
+        h->resize(m); c.z.resize(m); c.zstar.resize(m); c.p.resize(m);
+        check(bl_rangetable_debug_lookup(h_, table.device(), &v, &p, h->data(), c.z.data(), c.zstar.data(), c.p.data()), "bl_rangetable_debug_lookup");
+        const std::size_t r = static_cast<std::size_t>(bl_beam_last_rays(h_));
+        h->resize(r); c.z.resize(r); c.zstar.resize(r); c.p.resize(r);
+        return c;
+    }
     BeamTables tables(float cellsPerMeter) const
     {
         BeamTables t;

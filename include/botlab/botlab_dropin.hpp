@@ -446,6 +446,16 @@ public:
         check(bl_beam_reweigh_pf(beam.device(), h_, map.device(), &v, &out), "bl_beam_reweigh_pf");
         return pose_out<Pose>(out);
     }
+    // (extension) the same with the expected ranges looked up in a built range table (RangeTableT, range_table.hpp;
+    // bl_rangetable_reweigh_pf); the table is not checked against the live map
+    template <class Beam, class Table>
+    Pose reweighBeamTable(const Beam& beam, const Table& table, const Lidar& laser)
+    {
+        bl_lidar_t v = lidar_view(laser);
+        bl_pose_xyt_t out;
+        check(bl_rangetable_reweigh_pf(beam.device(), h_, table.device(), &v, &out), "bl_rangetable_reweigh_pf");
+        return pose_out<Pose>(out);
+    }
     bl_pf* device() const { return h_; }                                      // for the device-side extras (bl_pf_encode_particles_lcm ...)
 private:
     bl_pf* h_;

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "beam_model.hpp"
+#include "range_table.hpp"
 #include "botlab_dropin.hpp"
 #include "likelihood_field.hpp"
 #include "loop_closer.hpp"
@@ -400,6 +401,18 @@ public:
     // changes; set before the first iteration.  beamModelActive(): the switch is on and an update has been reweighed.
     void setBeamModel(bool on, const bl_beam_params_t& p = default_beam_params()) { beamOn_ = on; beamParams_ = p; }
     bool beamModelActive() const { return beamOn_ && static_cast<bool>(beam_); }
+    // (extension) Range table (RangeTableT, range_table.hpp): with the beam model on and a map from a file
+    // (localizationOnlyMap), the reweigh looks the expected ranges up in a table of `headings` headings, built from the map before the
+    // first reweigh, instead of casting -- AS LONG AS THE DRIVER HAS NOT UPDATED THE MAP SINCE THE TABLE WAS BUILT.  The driver extends
+    // its map in every mode (slam.cpp's mode test is always true), so that holds for the iterations that leave the map alone: all of
+    // a global search until it converges, the ones recovery holds back, and the first one otherwise.  From the first map update on the
+    // switch is ignored and the cast is used: bringing the table up to date after every scan would cost more than the casts it saves,
+    // and a stale table is never read.  In every other mode (no map file, poses given, action only) the switch is ignored altogether.
+    // Off by default, and with it off nothing the driver does changes; set before the first iteration.  beamRangeTableBuilds() and
+    // beamRangeTableReweighs(): tables built (0 or 1) and reweighs that read one.
+    void setBeamRangeTable(bool on, int headings = 256) { beamTableOn_ = on; beamTableHeadings_ = headings; }
+    int beamRangeTableBuilds() const { return beamTableBuilds_; }
+    int beamRangeTableReweighs() const { return beamTableReweighs_; }
     // (extension) Scan history (ScanHistoryT, map_rebuild.hpp): every iteration that updates the map appends the same
     // scan and the same pose bits to a history of the last `capacity` scans -- in the fused step the pose is read on the device, behind
     // the map update that carries the filter's end.  rebuildMap() writes into the driver's map what sequential map updates of the
@@ -594,6 +607,11 @@ private:
     bool beamOn_ = false;
     bl_beam_params_t beamParams_ = default_beam_params();
     std::unique_ptr<BeamModelT<Pose, Lidar> > beam_;
+    // range table: switch and headings; the table (built on first use); the two counters
+    bool beamTableOn_ = false;
+    int beamTableHeadings_ = 256;
+    std::unique_ptr<RangeTableT<Pose, Lidar> > beamTable_;
+    int beamTableBuilds_ = 0, beamTableReweighs_ = 0;
     // scan history: capacity (0: off); the history (made at the first map update); what the mapper was made with
     int historyCapacity_ = 0;
     std::unique_ptr<ScanHistoryT<Pose, Lidar> > history_;
@@ -608,9 +626,23 @@ private:
         if (!beamOn_) return p;
         if (!beam_) beam_.reset(new BeamModelT<Pose, Lidar>(beamParams_));
         const int64_t t = p.utime;
-        p = pf_.reweighBeam(*beam_, grid_, scan_);
+        if (beamTableCurrent()) { p = pf_.reweighBeamTable(*beam_, *beamTable_, scan_); ++beamTableReweighs_; }
+        else p = pf_.reweighBeam(*beam_, grid_, scan_);
         p.utime = t;
         return p;
+    }
+
+    // true when the reweigh may read the range table: the switch is on, the map came from a file and the driver has not updated it
+    // yet (mapsMade_ counts every update, and rebuildMap needs a history that only they fill); the table is built here, once
+    bool beamTableCurrent()
+    {
+        if (!beamTableOn_ || !how_.mapFromFile || mapsMade_ != 0) return false;
+        if (!beamTable_) {
+            beamTable_.reset(new RangeTableT<Pose, Lidar>(beamTableHeadings_));
+            beamTable_->build(*beam_, grid_);
+            ++beamTableBuilds_;
+        }
+        return true;
     }
 
     bool scanMatching() const { return matching_ && !global_ && !how_.posesGiven; }

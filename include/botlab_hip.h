@@ -1785,6 +1785,78 @@ int bl_beam_debug_path(bl_beam* beam);
 /* device time of the last call's kernels (HIP events around the launches); BL_ERR_STATE before the first */
 int bl_beam_last_device_ms(const bl_beam* beam, float* ms);
 
+/* ------------------------------------------------------------------ range table (no reference counterpart)
+ * On a map that does not change, the expected range of a ray depends only on its start cell and its direction.  The table holds it
+ * for every cell and Hn headings, so that the beam model can look it up instead of walking the map (range_libc's LUT).  Off unless
+ * called: bl_beam_scores, bl_beam_reweigh_pf and the filter's update are untouched.
+ *   Handle.  bl_rangetable_create(ctx, headings, &rt): headings = Hn, a power of two in 64 .. 1024, else BL_ERR_ARG.
+ *   Directions.  reach = ceil((double)max_range * cells_per_meter), as in bl_beam_tables.  For h = 0 .. Hn - 1
+ *       D[h] = (lround(reach * cos(2 pi h / Hn)), lround(reach * sin(2 pi h / Hn))), made on the host in double, int32 pairs.
+ *   Entries.  uint16, T[(y * W + x) * Hn + h].  The ray starts at cell s = (x, y) and ends at the far cell m = s + D[h]; the walk is
+ *     the beam model's (start cell k = 0 included, far cell k = K excluded, K = Chebyshev(s, m)).  first = the least k whose cell lies
+ *     inside the grid and has log-odds >= occ_min; the entry is q(c*, s) of that cell, the beam model's exact integer length in quarter
+ *     cells, and BL_RANGETABLE_NONE when there is no such k.  An occupied start cell holds 0 in all Hn entries.  The largest real
+ *     entry is 23 170 (reach <= 4096), so the sentinel cannot collide with a value.
+ *   bl_rangetable_build(rt, beam, map) takes reach and occ_min from the beam model's parameters and the size, origin and
+ *     cells_per_meter from the map, stores them in the handle and fills the whole table.  More than 2^31 entries (W * H * Hn) are
+ *     refused with BL_ERR_ARG before anything is allocated, and the handle keeps the table it had.  A handle may be built again with
+ *     other parameters or another map.
+ *   bl_rangetable_update(rt, map, x0, y0, x1, y1) is called after the cells of the box x0 .. x1, y0 .. y1 (inclusive) changed: the
+ *     entries of every cell of the box widened by reach on each side and clipped to the grid are computed again (a cell's entries
+ *     depend on no cell farther away), by the same kernel.  The table then equals byte for byte what build gives on the new map.  A box
+ *     with x1 < x0 or y1 < y0, or one that lies wholly outside the grid, changes nothing.  A map of another shape than the built one:
+ *     BL_ERR_ARG, the table stays as it was.  Before the first build: BL_ERR_STATE.
+ *   bl_rangetable_read(rt, x0, y0, w, h, out) downloads the entries of the cells x0 .. x0 + w - 1, y0 .. y0 + h - 1 (inside the
+ *     grid, else BL_ERR_ARG) as out[((y - y0) * w + (x - x0)) * Hn + hd].  bl_rangetable_directions(rt, out): 2 * Hn int32 (x, y per
+ *     heading) of the built table.  Both BL_ERR_STATE before the first build.  bl_rangetable_info works at any time.
+ *   Scoring by table, bl_rangetable_scores(beam, rt, scan, poses, n, out_scores).  The used rays, the start cell s of a pose and the
+ *     poses that take no part are exactly the beam model's, with the frame the table was built on.  Per used ray
+ *       a = wrap_to_pi(theta - theta_r) in float32 (the angle of the beam model's geometry); a ray whose a is not finite is dropped;
+ *       hd = (int)floorf(a * kf + 0.5f) & (Hn - 1), kf = (float)(Hn / (2 pi)): one multiply and one add, each rounded to float;
+ *       z* = T[s, hd]: an expected hit unless it is BL_RANGETABLE_NONE;
+ *       for a return z = (int)(range * q), q = 4.0f * cells_per_meter: no sine, no cosine, no end cell.
+ *     The rest is the beam model's with the handle's own tables: Hit[min(|z - z*|, hit_cut)] with an expected hit, plus
+ *     Short[min(z >> 2, 1023)] without one or when z < z*, plus Rand; MaxBlocked / MaxFree for a max reading; lg, the int64 sum, Smax,
+ *     the units.  BL_ERR_STATE: the table is not built; the beam model's occ_min differs from the one the table was built with; the
+ *     beam model's reach at the table's cells_per_meter differs from the built one.  THE TABLE IS NOT CHECKED AGAINST THE LIVE MAP:
+ *     keeping it current is the caller's job (bl_rangetable_update).
+ *   bl_rangetable_reweigh_pf(beam, pf, rt, scan, out_pose) is bl_beam_reweigh_pf with the table behind it: the same install of the
+ *     units, the same state rules, the same behaviour under recovery; sharded filters are refused.  bl_rangetable_debug_lookup returns one
+ *     pose's hd, z, z*, p per used ray (z = -1 for a max reading, z* = -1 without an expected hit, hd = z = z* = -1 and p = 0 for a
+ *     dropped ray, zeros for a pose that takes no part), as bl_beam_debug_cast does for the cast.  bl_beam_units and
+ *     bl_beam_last_device_ms work after either form; bl_beam_debug_path answers 1 after a scoring by table.
+ *   How it is computed.  k_rt_build (bl_rangetable.hip): a wave per cell, a lane per heading in rounds of 64; the lane walks the
+ *     Bresenham loop from s and stops at its first occupied cell or when it leaves the grid; an occupied start cell is settled without
+ *     a walk; D[] in LDS; a cell's entries are stored as one row, 128 bytes per 64 lanes; the map bytes come from the grid through
+ *     L2.  k_beam_lookup (bl_beam.hip): k_beam_cast's launch shape, the three score tables in LDS, a pose's rays read one row of
+ *     2 * Hn bytes; k_beam_final and k_beam_units as they stand.  No atomics; no workgroup waits for another. */
+#define BL_RANGETABLE_NONE 0xFFFF
+typedef struct bl_rangetable bl_rangetable;
+typedef struct bl_rangetable_info_t {
+    int32_t width, height;             /* of the map built on; 0 before the first build */
+    int32_t headings;
+    int32_t reach, occ_min;            /* 0 before the first build */
+    int32_t built;                     /* 0 or 1 */
+    int64_t bytes;                     /* of the table on the device: 2 * width * height * headings */
+} bl_rangetable_info_t;                /* 32 bytes: offsets 0, 4, 8, 12, 16, 20, 24 */
+int bl_rangetable_create(bl_ctx* ctx, int headings, bl_rangetable** out);
+void bl_rangetable_destroy(bl_rangetable* rt);
+int bl_rangetable_build(bl_rangetable* rt, const bl_beam* beam, const bl_grid* map);
+int bl_rangetable_update(bl_rangetable* rt, const bl_grid* map, int x0, int y0, int x1, int y1);
+int bl_rangetable_read(bl_rangetable* rt, int x0, int y0, int w, int h, uint16_t* out);
+int bl_rangetable_directions(const bl_rangetable* rt, int32_t* out);
+int bl_rangetable_info(const bl_rangetable* rt, bl_rangetable_info_t* out);
+/* device time of the last build's or update's kernel (HIP events around the launch); BL_ERR_STATE before the first */
+int bl_rangetable_last_device_ms(const bl_rangetable* rt, float* ms);
+/* The beam model scored through the table.  (Named after the handle they need beside the beam model: the bl_beam_ names are the
+ * cast's.)  n host poses in, n scores out; any n >= 0 */
+int bl_rangetable_scores(bl_beam* beam, const bl_rangetable* rt, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores);
+int bl_rangetable_reweigh_pf(bl_beam* beam, bl_pf* pf, const bl_rangetable* rt, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose);
+/* bl_beam_last_rays() entries each (room for the scan's num_ranges is always enough); any pointer may be NULL.  The units and the
+ * count that bl_beam_units reads are left as they were. */
+int bl_rangetable_debug_lookup(bl_beam* beam, const bl_rangetable* rt, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_h,
+                               int32_t* out_z, int32_t* out_zstar, uint32_t* out_p);
+
 /* ------------------------------------------------------------------ scan history and map rebuild  
  * A map is otherwise written once, at the pose held at that moment, and the scan is thrown away.  The log keeps the last
  * `capacity_scans` scans on the device -- per scan the KEPT rays exactly as the mapper takes them (ranges, thetas, times; ranges
