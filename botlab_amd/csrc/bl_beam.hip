@@ -20,6 +20,11 @@
 //   k_beam_final  one workgroup: Smax over the workgroups' records, and how many workgroups took which path.
 //   k_beam_units  a thread per pose: the units, to the handle's array and, for a filter, into the record's weight word in place.
 //
+// The two scoring kernels are their prologue (tables to LDS; the cast's box and window) round one frame, beam_score_poses, with the
+// form's per-ray body; the rules of a ray -- start cell, walk, lengths, p, lg, heading index -- are bl_beam_dev.h's.  On the host
+// a beam_form says where the expected ranges come from, and the launcher, "scores", "debug" and "reweigh" exist once for both; the
+// six entry points check their form (beam_check_map, beam_check_table) and call them.
+//
 // Integers only behind the end cells; no atomics; no workgroup waits for another; no result depends on the launch shape.
 #include <limits.h>
 #include <math.h>
@@ -48,16 +53,6 @@ struct beam_args {
     int32_t* dbg;                                         // null, or [5][R] of pose 0: first, K, z, zstar, p
 };
 
-// the start cell of a pose; false for a pose that takes no part
-__device__ __forceinline__ bool beam_start(const float4& p, const bl_frame& f, float* px, float* py, int* sx, int* sy)
-{
-    if (!(__builtin_fabsf(p.x) < __builtin_inff() && __builtin_fabsf(p.y) < __builtin_inff() && __builtin_fabsf(p.z) < __builtin_inff())) return false;
-    bl_global_to_grid(p.x, p.y, f, px, py);
-    if (!(__builtin_fabsf(*px) < 0x1p30f && __builtin_fabsf(*py) < 0x1p30f)) return false;
-    *sx = (int)*px; *sy = (int)*py;
-    return *sx >= 0 && *sx < f.width && *sy >= 0 && *sy < f.height;
-}
-
 struct beam_window { int x0, y0, w, h; };
 
 // lg(p) of one used ray of one pose (0 with p = 0 for a ray that `has` drops); dbg as in beam_args
@@ -78,40 +73,62 @@ __device__ __forceinline__ int beam_ray(const beam_args& a, const uint32_t* s_ta
     int first = -1, K = -1, z = -1, zstar = -1, lgp = 0;
     uint32_t p = 0;
     if (has) {
-        const int mx = (int)fmx, my = (int)fmy;
-        const int dx = abs(mx - sx), dy = abs(my - sy);
-        const int stepx = sx < mx ? 1 : -1, stepy = sy < my ? 1 : -1;
-        K = max(dx, dy);
-        first = K;
-        int err = dx - dy, x = sx, y = sy, cx = 0, cy = 0;
-        for (int k = 0; k < K; ++k) {                                   // mapping.cpp:101-127, end cell excluded
+        // a cell outside the grid is free and the walk goes on: the far cell may lie anywhere
+        const beam_hit hit = beam_first_hit(sx, sy, (int)fmx, (int)fmy, [&](int x, int y) {
             bool occ = false;
             if ((unsigned int)x < (unsigned int)W && (unsigned int)y < (unsigned int)H) {
                 const int lx = x - win.x0, ly = y - win.y0;
                 if (STAGED && (unsigned int)lx < (unsigned int)win.w && (unsigned int)ly < (unsigned int)win.h) occ = s_win[ly * win.w + lx] >= a.occ_min;
                 else occ = a.cells[(size_t)y * W + x] >= a.occ_min;
             }
-            if (occ) { first = k; cx = x; cy = y; break; }
-            const int e2 = 2 * err;
-            if (e2 >= -dy) { err -= dy; x += stepx; }
-            if (e2 <= dx) { err += dx; y += stepy; }
-        }
+            return occ;
+        });
+        first = hit.first; K = hit.K;
         const bool expect = first < K;
-        if (expect) zstar = beam_quarter(cx, cy, sx, sy);
+        if (expect) zstar = beam_quarter(hit.x, hit.y, sx, sy);
         if (is_max) {
             p = expect ? a.max_blocked : a.max_free;
         } else {
             z = beam_quarter((int)fex, (int)fey, sx, sy);
-            p = a.rnd;
-            if (expect) p += s_tab[BEAM_HIT + min(abs(z - zstar), a.hit_cut)];
-            if (!expect || z < zstar) p += s_tab[BEAM_SHORT + min(z >> 2, 1023)];
+            p = beam_return_p(s_tab, a.rnd, a.hit_cut, expect, z, zstar);
         }
-        const int e = 31 - __clz((int)p);                               // p >= 1: bl_beam_set_params
-        const uint32_t mant = ((p << (31 - e)) >> 23) & 255u;
-        lgp = (e - 30) * a.ln2 + (int)s_tab[BEAM_LT + mant];
+        lgp = beam_lg(s_tab, p, a.ln2);
     }
     if (dbg) { dbg[r] = first; dbg[a.R + r] = K; dbg[2 * a.R + r] = z; dbg[3 * a.R + r] = zstar; dbg[4 * a.R + r] = (int32_t)p; }
     return lgp;
+}
+
+// The scoring frame of both forms: the workgroup's BEAM_WG_POSES poses, a wave per BEAM_WAVE_POSES of them one after the other, a lane
+// per ray through ray(pose, px, py, sx, sy, r, dbg) -> lg(p); per pose the wave's int64 sum, per workgroup the largest score and
+// `path` (k_beam_final counts the workgroups with path 1).  Every thread of the workgroup calls it.
+template <class Args, class Ray>
+__device__ __forceinline__ void beam_score_poses(const Args& a, long long* s_max, int path, Ray ray)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p0 = blockIdx.x * BEAM_WG_POSES;
+    long long best = BEAM_OFF;
+    for (int q = 0; q < BEAM_WAVE_POSES; ++q) {
+        const int pi = p0 + wave * BEAM_WAVE_POSES + q;
+        if (pi >= a.n) break;                                           // (uniform over the wave)
+        const float4 pose = a.poses[pi];
+        float px, py; int sx, sy;
+        long long s = BEAM_OFF;
+        int32_t* dbg = (a.dbg && pi == 0) ? a.dbg : nullptr;
+        if (beam_start(pose, a.f, &px, &py, &sx, &sy)) {
+            s = 0;
+            for (int r = lane; r < a.R; r += 64) s += ray(pose, px, py, sx, sy, r, dbg);
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+            best = s > best ? s : best;
+        }
+        if (lane == 0) a.scores[pi] = s;
+    }
+    if (lane == 0) s_max[wave] = best;
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < BEAM_THREADS / 64; ++k) best = s_max[k] > best ? s_max[k] : best;
+        a.wg_max[blockIdx.x] = best;
+        a.wg_path[blockIdx.x] = (uint8_t)path;
+    }
 }
 
 __global__ __launch_bounds__(BEAM_THREADS) void k_beam_cast(beam_args a)
@@ -165,31 +182,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_cast(beam_args a)
         }
     }
     __syncthreads();
-    long long best = BEAM_OFF;
-    for (int q = 0; q < BEAM_WAVE_POSES; ++q) {
-        const int pi = p0 + wave * BEAM_WAVE_POSES + q;
-        if (pi >= a.n) break;                                           // (uniform over the wave)
-        const float4 pose = a.poses[pi];
-        float px, py; int sx, sy;
-        long long s = BEAM_OFF;
-        int32_t* dbg = (a.dbg && pi == 0) ? a.dbg : nullptr;
-        if (beam_start(pose, a.f, &px, &py, &sx, &sy)) {
-            s = 0;
-            for (int r = lane; r < a.R; r += 64)
-                s += staged ? beam_ray<true>(a, s_tab, s_win, win, px, py, sx, sy, pose.z, r, dbg)
-                            : beam_ray<false>(a, s_tab, s_win, win, px, py, sx, sy, pose.z, r, dbg);
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            best = s > best ? s : best;
-        }
-        if (lane == 0) a.scores[pi] = s;
-    }
-    if (lane == 0) s_max[wave] = best;
-    __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < BEAM_THREADS / 64; ++k) best = s_max[k] > best ? s_max[k] : best;
-        a.wg_max[blockIdx.x] = best;
-        a.wg_path[blockIdx.x] = staged ? 0 : 1;
-    }
+    beam_score_poses(a, s_max, staged ? 0 : 1, [&](const float4& pose, float px, float py, int sx, int sy, int r, int32_t* dbg) {
+        return staged ? beam_ray<true>(a, s_tab, s_win, win, px, py, sx, sy, pose.z, r, dbg)
+                      : beam_ray<false>(a, s_tab, s_win, win, px, py, sx, sy, pose.z, r, dbg);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- scoring by table
@@ -209,54 +205,31 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_lookup(beam_lookup_args a
 {
     __shared__ uint32_t s_tab[BEAM_TABLE_WORDS];
     __shared__ long long s_max[BEAM_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int p0 = blockIdx.x * BEAM_WG_POSES;
-    for (int i = tid; i < BEAM_TABLE_WORDS; i += BEAM_THREADS) s_tab[i] = a.tables[i];
+    for (int i = threadIdx.x; i < BEAM_TABLE_WORDS; i += BEAM_THREADS) s_tab[i] = a.tables[i];
     __syncthreads();
-    long long best = BEAM_OFF;
-    for (int q = 0; q < BEAM_WAVE_POSES; ++q) {
-        const int pi = p0 + wave * BEAM_WAVE_POSES + q;
-        if (pi >= a.n) break;                                           // (uniform over the wave)
-        const float4 pose = a.poses[pi];
-        float px, py; int sx, sy;
-        long long s = BEAM_OFF;
-        int32_t* dbg = (a.dbg && pi == 0) ? a.dbg : nullptr;
-        if (beam_start(pose, a.f, &px, &py, &sx, &sy)) {
-            const uint16_t* row = a.table + ((size_t)sy * a.f.width + sx) * a.Hn;
-            s = 0;
-            for (int r = lane; r < a.R; r += 64) {
-                const float range = a.ranges[r];
-                const float ang = bl_wrap_to_pi(pose.z - a.thetas[r]);
-                int h = -1, z = -1, zstar = -1, lgp = 0;
-                uint32_t p = 0;
-                if (__builtin_fabsf(ang) < __builtin_inff()) {
-                    h = (int)__builtin_floorf(ang * a.kf + 0.5f) & (a.Hn - 1);
-                    const int t = row[h];
-                    const bool expect = t != BL_RANGETABLE_NONE;
-                    if (expect) zstar = t;
-                    if (range >= a.max_range) {
-                        p = expect ? a.max_blocked : a.max_free;
-                    } else {
-                        z = (int)(range * a.q);
-                        p = beam_return_p(s_tab, a.rnd, a.hit_cut, expect, z, zstar);
-                    }
-                    lgp = beam_lg(s_tab, p, a.ln2);
-                }
-                if (dbg) { dbg[r] = h; dbg[a.R + r] = z; dbg[2 * a.R + r] = zstar; dbg[3 * a.R + r] = (int32_t)p; }
-                s += lgp;
+    // path 1: nothing is staged, k_beam_final counts the workgroup with the direct ones
+    beam_score_poses(a, s_max, 1, [&](const float4& pose, float, float, int sx, int sy, int r, int32_t* dbg) {
+        const uint16_t* row = a.table + ((size_t)sy * a.f.width + sx) * a.Hn;
+        const float range = a.ranges[r];
+        const float ang = bl_wrap_to_pi(pose.z - a.thetas[r]);
+        int h = -1, z = -1, zstar = -1, lgp = 0;
+        uint32_t p = 0;
+        if (__builtin_fabsf(ang) < __builtin_inff()) {
+            h = beam_heading_index(ang, a.kf, a.Hn);
+            const int t = row[h];
+            const bool expect = t != BL_RANGETABLE_NONE;
+            if (expect) zstar = t;
+            if (range >= a.max_range) {
+                p = expect ? a.max_blocked : a.max_free;
+            } else {
+                z = (int)(range * a.q);
+                p = beam_return_p(s_tab, a.rnd, a.hit_cut, expect, z, zstar);
             }
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            best = s > best ? s : best;
+            lgp = beam_lg(s_tab, p, a.ln2);
         }
-        if (lane == 0) a.scores[pi] = s;
-    }
-    if (lane == 0) s_max[wave] = best;
-    __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < BEAM_THREADS / 64; ++k) best = s_max[k] > best ? s_max[k] : best;
-        a.wg_max[blockIdx.x] = best;
-        a.wg_path[blockIdx.x] = 1;                                      // nothing is staged: k_beam_final counts it with the direct ones
-    }
+        if (dbg) { dbg[r] = h; dbg[a.R + r] = z; dbg[2 * a.R + r] = zstar; dbg[3 * a.R + r] = (int32_t)p; }
+        return lgp;
+    });
 }
 
 __global__ __launch_bounds__(1024) void k_beam_final(const long long* __restrict__ wg_max, const uint8_t* __restrict__ wg_path, int blocks, beam_state* st)
@@ -414,27 +387,21 @@ static int beam_need_params(const bl_beam* b)
     return BL_OK;
 }
 
-static int beam_reach(const bl_beam* b, float cpm, int* reach)
-{
-    const double r = ceil((double)b->params.max_range * (double)cpm);
-    BL_CHECK_ARG(r >= 1.0 && r <= (double)BL_BEAM_MAX_REACH);           // (false for NaN too)
-    *reach = (int)r;
-    return BL_OK;
-}
+static int beam_ln2() { return (int)beam_round(65536.0 * log(2.0)); }
 
 extern "C" int bl_beam_tables(const bl_beam* b, float cells_per_meter, uint32_t* hit, uint32_t* short_, uint32_t* lt, uint32_t scalars[5])
 {
     int rc = beam_need_params(b);
     if (rc) return rc;
     int reach = 0;
-    rc = beam_reach(b, cells_per_meter, &reach);
+    rc = beam_reach(b->params.max_range, cells_per_meter, &reach);
     if (rc) return rc;
     if (hit) memcpy(hit, b->h_tab + BEAM_HIT, 1024 * sizeof(uint32_t));
     if (short_) memcpy(short_, b->h_tab + BEAM_SHORT, 1024 * sizeof(uint32_t));
     if (lt) memcpy(lt, b->h_tab + BEAM_LT, 256 * sizeof(uint32_t));
     if (scalars) {
         scalars[0] = beam_rand(b->params, reach); scalars[1] = beam_max_free(b->params); scalars[2] = beam_max_blocked(b->params);
-        scalars[3] = (uint32_t)beam_round(65536.0 * log(2.0)); scalars[4] = (uint32_t)reach;
+        scalars[3] = (uint32_t)beam_ln2(); scalars[4] = (uint32_t)reach;
     }
     return BL_OK;
 }
@@ -479,87 +446,95 @@ static int beam_stage_rays(bl_beam* b, const bl_lidar_t* scan, int* R_out)
     return BL_OK;
 }
 
-// what the scoring kernel of either form writes: n scores, n units, the workgroups' records
-static int beam_grow_outputs(bl_beam* b, int n, int blocks)
+// where the expected ranges come from: cast against `map`, or (map null) looked up in the table `v`; reach: the beam model's in cells
+// on that map's or table's frame (a table's own is checked to equal it)
+struct beam_form { const bl_grid* map; int reach; bl_rangetable_view v; };
+
+// the fields the two kernels' argument structs share, for a map or table of `reach` cells
+template <class Args>
+static void beam_fill_args(Args& a, const bl_beam* b, int reach, int R, const float4* poses, int n, int blocks, int32_t* dbg)
+{
+    const bl_beam_params_t& p = b->params;
+    a.ranges = (const float*)b->d_rays; a.thetas = (const float*)b->d_rays + R; a.R = R;
+    a.poses = poses; a.n = n;
+    a.max_range = p.max_range; a.hit_cut = p.hit_cut;
+    a.rnd = beam_rand(p, reach); a.max_free = beam_max_free(p); a.max_blocked = beam_max_blocked(p);
+    a.ln2 = beam_ln2();
+    a.tables = b->d_tab;
+    a.scores = (long long*)b->d_scores; a.wg_max = (long long*)b->d_wg; a.wg_path = (uint8_t*)b->d_wg + (size_t)blocks * 8;
+    a.dbg = dbg;
+}
+
+// The launches for n poses at `poses` (device): the form's scoring kernel, k_beam_final and -- not for a debug launch, which leaves
+// the last call's units and count alone -- k_beam_units, then the closing event.  rec: the filter's record for k_beam_units, or
+// null; dbg: the form's planes ([5][R] cast, [4][R] table) of pose 0, or null
+static int beam_launch(bl_beam* b, const beam_form& fm, int R, const float4* poses, int n, float4* rec, int32_t* dbg)
 {
     bl_ctx* ctx = b->ctx;
+    const int blocks = (n + BEAM_WG_POSES - 1) / BEAM_WG_POSES;
     int rc = bl_grow(&b->d_scores, &b->d_scores_cap, (size_t)n * 8, false, ctx);
     if (!rc) rc = bl_grow(&b->d_units, &b->d_units_cap, (size_t)n * 4, false, ctx);
     if (!rc) rc = bl_grow(&b->d_wg, &b->d_wg_cap, (size_t)blocks * 9, false, ctx);
-    return rc;
-}
-
-// behind the scoring kernel of either form: k_beam_final, k_beam_units (not for a debug launch: it leaves the last call's units and
-// count alone) and the closing event
-static int beam_launch_rest(bl_beam* b, int blocks, int n, float4* rec, bool debug)
-{
-    bl_ctx* ctx = b->ctx;
+    if (rc) return rc;
+    BL_HIP(hipEventRecord(b->ev_stage, ctx->stream));                   // the pinned blocks have left once this is reached
+    BL_HIP(hipEventRecord(b->ev_a, ctx->stream));
+    if (fm.map) {
+        beam_args a;
+        beam_fill_args(a, b, fm.reach, R, poses, n, blocks, dbg);
+        a.cells = fm.map->cells; a.f = fm.map->frame;
+        a.occ_min = b->params.occ_min; a.reach = fm.reach;
+        a.window_bytes = b->window_bytes; a.stage = b->stage;
+        hipLaunchKernelGGL(k_beam_cast, dim3((unsigned int)blocks), dim3(BEAM_THREADS),
+                           BEAM_TABLE_WORDS * sizeof(uint32_t) + (b->stage ? (size_t)b->window_bytes : 0), ctx->stream, a);
+    } else {
+        beam_lookup_args a;
+        beam_fill_args(a, b, fm.reach, R, poses, n, blocks, dbg);
+        a.table = fm.v.d_table; a.f = fm.v.frame; a.Hn = fm.v.headings;
+        a.kf = (float)((double)fm.v.headings / (2.0 * BL_PI)); a.q = 4.0f * fm.v.frame.cpm;
+        hipLaunchKernelGGL(k_beam_lookup, dim3((unsigned int)blocks), dim3(BEAM_THREADS), 0, ctx->stream, a);
+    }
     hipLaunchKernelGGL(k_beam_final, dim3(1), dim3(1024), 0, ctx->stream, (const long long*)b->d_wg, (const uint8_t*)b->d_wg + (size_t)blocks * 8, blocks,
                        b->d_state);
-    if (!debug)
+    if (!dbg)
         hipLaunchKernelGGL(k_beam_units, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const long long*)b->d_scores, n,
                            (const beam_state*)b->d_state, (long long)b->params.span, (const uint32_t*)b->d_U, (uint32_t*)b->d_units, rec);
     BL_HIP(hipGetLastError());
     BL_HIP(hipEventRecord(b->ev_b, ctx->stream));
     b->staged = true; b->timed = true;
-    if (!debug) b->last_n = n;
+    if (!dbg) b->last_n = n;
     return BL_OK;
 }
 
-// the three launches for n poses at `poses` (device); rec: the filter's record for k_beam_units, or null
-static int beam_launch(bl_beam* b, const bl_grid* map, int reach, int R, const float4* poses, int n, float4* rec, int32_t* dbg)
-{
-    bl_ctx* ctx = b->ctx;
-    const int blocks = (n + BEAM_WG_POSES - 1) / BEAM_WG_POSES;
-    int rc = beam_grow_outputs(b, n, blocks);
-    if (rc) return rc;
-    const bl_beam_params_t& p = b->params;
-    beam_args a;
-    a.cells = map->cells; a.f = map->frame;
-    a.ranges = (const float*)b->d_rays; a.thetas = (const float*)b->d_rays + R; a.R = R;
-    a.poses = poses; a.n = n;
-    a.max_range = p.max_range; a.occ_min = p.occ_min; a.hit_cut = p.hit_cut; a.reach = reach;
-    a.rnd = beam_rand(p, reach); a.max_free = beam_max_free(p); a.max_blocked = beam_max_blocked(p);
-    a.ln2 = (int)beam_round(65536.0 * log(2.0));
-    a.tables = b->d_tab;
-    a.window_bytes = b->window_bytes; a.stage = b->stage;
-    a.scores = (long long*)b->d_scores; a.wg_max = (long long*)b->d_wg; a.wg_path = (uint8_t*)b->d_wg + (size_t)blocks * 8;
-    a.dbg = dbg;
-    BL_HIP(hipEventRecord(b->ev_stage, ctx->stream));                   // the pinned blocks have left once this is reached
-    BL_HIP(hipEventRecord(b->ev_a, ctx->stream));
-    hipLaunchKernelGGL(k_beam_cast, dim3((unsigned int)blocks), dim3(BEAM_THREADS), BEAM_TABLE_WORDS * sizeof(uint32_t) + (b->stage ? (size_t)b->window_bytes : 0),
-                       ctx->stream, a);
-    return beam_launch_rest(b, blocks, n, rec, dbg != nullptr);
-}
-
-// the same for the scoring by table: v is the table's view, checked by beam_check_table; dbg: [4][R] of pose 0, or null
-static int beam_launch_table(bl_beam* b, const bl_rangetable_view& v, int R, const float4* poses, int n, float4* rec, int32_t* dbg)
-{
-    bl_ctx* ctx = b->ctx;
-    const int blocks = (n + BEAM_WG_POSES - 1) / BEAM_WG_POSES;
-    int rc = beam_grow_outputs(b, n, blocks);
-    if (rc) return rc;
-    const bl_beam_params_t& p = b->params;
-    beam_lookup_args a;
-    a.table = v.d_table; a.f = v.frame; a.Hn = v.headings;
-    a.ranges = (const float*)b->d_rays; a.thetas = (const float*)b->d_rays + R; a.R = R;
-    a.poses = poses; a.n = n;
-    a.max_range = p.max_range; a.kf = (float)((double)v.headings / (2.0 * BL_PI)); a.q = 4.0f * v.frame.cpm; a.hit_cut = p.hit_cut;
-    a.rnd = beam_rand(p, v.reach); a.max_free = beam_max_free(p); a.max_blocked = beam_max_blocked(p);
-    a.ln2 = (int)beam_round(65536.0 * log(2.0));
-    a.tables = b->d_tab;
-    a.scores = (long long*)b->d_scores; a.wg_max = (long long*)b->d_wg; a.wg_path = (uint8_t*)b->d_wg + (size_t)blocks * 8;
-    a.dbg = dbg;
-    BL_HIP(hipEventRecord(b->ev_stage, ctx->stream));
-    BL_HIP(hipEventRecord(b->ev_a, ctx->stream));
-    hipLaunchKernelGGL(k_beam_lookup, dim3((unsigned int)blocks), dim3(BEAM_THREADS), 0, ctx->stream, a);
-    return beam_launch_rest(b, blocks, n, rec, dbg != nullptr);
-}
-
-static int beam_check_map(const bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, int* reach)
+static int beam_check_map(const bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, beam_form* fm)
 {
     BL_CHECK_ARG(map != nullptr && scan != nullptr && map->ctx == b->ctx);
-    return beam_reach(b, map->frame.cpm, reach);
+    fm->map = map;
+    return beam_reach(b->params.max_range, map->frame.cpm, &fm->reach);
+}
+
+void bl_beam_view_host(const bl_beam* b, bl_beam_view* out)
+{
+    out->ctx = b->ctx; out->have_params = b->have_params; out->max_range = b->params.max_range; out->occ_min = b->params.occ_min;
+}
+
+// the table's view, once it is known to be built on this ctx with the reach and occ_min the parameters in force give
+static int beam_check_table(const bl_beam* b, const bl_rangetable* rt, const bl_lidar_t* scan, beam_form* fm)
+{
+    BL_CHECK_ARG(rt != nullptr && scan != nullptr);
+    bl_rangetable_view* v = &fm->v;
+    fm->map = nullptr;
+    bl_rangetable_view_host(rt, v);
+    BL_CHECK_ARG(v->ctx == b->ctx);
+    if (!v->built) { bl_set_error("range table not built (bl_rangetable_build first)"); return BL_ERR_STATE; }
+    if (b->params.occ_min != v->occ_min) {
+        bl_set_error("range table built with occ_min %d, the beam model has %d", v->occ_min, b->params.occ_min);
+        return BL_ERR_STATE;
+    }
+    if (beam_reach(b->params.max_range, v->frame.cpm, &fm->reach) != BL_OK || fm->reach != v->reach) {
+        bl_set_error("range table built with a reach of %d cells, the beam model's is another", v->reach);
+        return BL_ERR_STATE;
+    }
+    return BL_OK;
 }
 
 // n host poses staged as the kernels read them
@@ -575,71 +550,60 @@ static int beam_stage_poses(bl_beam* b, const bl_pose_xyt_t* poses, int n)
     return BL_OK;
 }
 
-extern "C" int bl_beam_scores(bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores)
+// The three calls of either form, behind beam_need_params and the form's check.
+static int beam_scores(bl_beam* b, const beam_form& fm, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores)
 {
-    int rc = beam_need_params(b);
-    if (rc) return rc;
-    int reach = 0, R = 0;
-    rc = beam_check_map(b, map, scan, &reach);
-    if (rc) return rc;
     BL_CHECK_ARG(n >= 0 && (n == 0 || (poses != nullptr && out_scores != nullptr)));
     bl_ctx* ctx = b->ctx;
     BL_HIP(hipSetDevice(ctx->device));
-    rc = beam_stage_rays(b, scan, &R);
+    int R = 0;
+    int rc = beam_stage_rays(b, scan, &R);
     if (rc) return rc;
     if (n == 0) { b->last_n = 0; return BL_OK; }
     rc = beam_stage_poses(b, poses, n);
-    if (!rc) rc = beam_launch(b, map, reach, R, (const float4*)b->d_poses, n, nullptr, nullptr);
+    if (!rc) rc = beam_launch(b, fm, R, (const float4*)b->d_poses, n, nullptr, nullptr);
     if (rc) return rc;
     BL_HIP(hipMemcpyAsync(out_scores, b->d_scores, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));   // the one read-back
     BL_HIP(hipStreamSynchronize(ctx->stream));
     return BL_OK;
 }
 
-extern "C" int bl_beam_debug_cast(bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_first,
-                                  int32_t* out_K, int32_t* out_z, int32_t* out_zstar, uint32_t* out_p)
+// outs: the form's `planes` planes of R words each (5 cast, 4 table), any of them null
+static int beam_debug(bl_beam* b, const beam_form& fm, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, void* const* outs, int planes)
 {
-    int rc = beam_need_params(b);
-    if (rc) return rc;
-    int reach = 0, R = 0;
-    rc = beam_check_map(b, map, scan, &reach);
-    if (rc) return rc;
     BL_CHECK_ARG(pose != nullptr);
     bl_ctx* ctx = b->ctx;
     BL_HIP(hipSetDevice(ctx->device));
-    rc = beam_stage_rays(b, scan, &R);
+    int R = 0;
+    int rc = beam_stage_rays(b, scan, &R);
     if (rc) return rc;
     if (R == 0) return BL_OK;
-    rc = bl_grow(&b->d_dbg, &b->d_dbg_cap, 5 * (size_t)R * 4, false, ctx);
+    const size_t bytes = (size_t)planes * R * 4;
+    rc = bl_grow(&b->d_dbg, &b->d_dbg_cap, bytes, false, ctx);
     if (!rc) rc = beam_stage_poses(b, pose, 1);
     if (rc) return rc;
-    BL_HIP(hipMemsetAsync(b->d_dbg, 0, 5 * (size_t)R * 4, ctx->stream));   // (an off-grid pose writes nothing)
-    rc = beam_launch(b, map, reach, R, (const float4*)b->d_poses, 1, nullptr, (int32_t*)b->d_dbg);
+    BL_HIP(hipMemsetAsync(b->d_dbg, 0, bytes, ctx->stream));            // (an off-grid pose writes nothing)
+    rc = beam_launch(b, fm, R, (const float4*)b->d_poses, 1, nullptr, (int32_t*)b->d_dbg);
     if (rc) return rc;
-    void* outs[5] = {out_first, out_K, out_z, out_zstar, out_p};
-    for (int k = 0; k < 5; ++k)
+    for (int k = 0; k < planes; ++k)
         if (outs[k]) BL_HIP(hipMemcpyAsync(outs[k], (const int32_t*)b->d_dbg + (size_t)k * R, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->stream));
     BL_HIP(hipStreamSynchronize(ctx->stream));
     return BL_OK;
 }
 
-struct beam_install { bl_beam* b; const bl_grid* map; int reach, R; };
+struct beam_install { bl_beam* b; beam_form fm; int R; };
 static int beam_write_units(void* user, float4* rec, int n)
 {
     const beam_install* q = (const beam_install*)user;
-    return beam_launch(q->b, q->map, q->reach, q->R, rec, n, rec, nullptr);
+    return beam_launch(q->b, q->fm, q->R, rec, n, rec, nullptr);
 }
 
-extern "C" int bl_beam_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_grid* map, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose)
+// q: b and the checked form
+static int beam_reweigh(beam_install& q, bl_pf* pf, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose)
 {
-    int rc = beam_need_params(b);
-    if (rc) return rc;
-    beam_install q;
-    q.b = b; q.map = map;
-    rc = beam_check_map(b, map, scan, &q.reach);
-    if (rc) return rc;
+    bl_beam* b = q.b;
     BL_CHECK_ARG(pf != nullptr);
-    rc = bl_pf_install_units(pf, b->ctx, nullptr, nullptr, nullptr);   // the filter's state and ctx, before anything is enqueued
+    int rc = bl_pf_install_units(pf, b->ctx, nullptr, nullptr, nullptr);   // the filter's state and ctx, before anything is enqueued
     if (rc) return rc;
     BL_HIP(hipSetDevice(b->ctx->device));
     rc = beam_stage_rays(b, scan, &q.R);
@@ -647,50 +611,33 @@ extern "C" int bl_beam_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_grid* map, con
     return bl_pf_install_units(pf, b->ctx, beam_write_units, &q, out_pose);
 }
 
-// ---------------------------------------------------------------------------------------------------------------- by table (host)
-void bl_beam_view_host(const bl_beam* b, bl_beam_view* out)
+extern "C" int bl_beam_scores(bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores)
 {
-    out->ctx = b->ctx; out->have_params = b->have_params; out->max_range = b->params.max_range; out->occ_min = b->params.occ_min;
-}
-
-// the table's view, once it is known to be built on this ctx with the reach and occ_min the parameters in force give
-static int beam_check_table(const bl_beam* b, const bl_rangetable* rt, const bl_lidar_t* scan, bl_rangetable_view* v)
-{
-    BL_CHECK_ARG(rt != nullptr && scan != nullptr);
-    bl_rangetable_view_host(rt, v);
-    BL_CHECK_ARG(v->ctx == b->ctx);
-    if (!v->built) { bl_set_error("range table not built (bl_rangetable_build first)"); return BL_ERR_STATE; }
-    if (b->params.occ_min != v->occ_min) {
-        bl_set_error("range table built with occ_min %d, the beam model has %d", v->occ_min, b->params.occ_min);
-        return BL_ERR_STATE;
-    }
-    if (ceil((double)b->params.max_range * (double)v->frame.cpm) != (double)v->reach) {
-        bl_set_error("range table built with a reach of %d cells, the beam model's is another", v->reach);
-        return BL_ERR_STATE;
-    }
-    return BL_OK;
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    beam_form fm;
+    rc = beam_check_map(b, map, scan, &fm);
+    return rc ? rc : beam_scores(b, fm, scan, poses, n, out_scores);
 }
 
 extern "C" int bl_rangetable_scores(bl_beam* b, const bl_rangetable* rt, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores)
 {
     int rc = beam_need_params(b);
     if (rc) return rc;
-    bl_rangetable_view v;
-    int R = 0;
-    rc = beam_check_table(b, rt, scan, &v);
+    beam_form fm;
+    rc = beam_check_table(b, rt, scan, &fm);
+    return rc ? rc : beam_scores(b, fm, scan, poses, n, out_scores);
+}
+
+extern "C" int bl_beam_debug_cast(bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_first,
+                                  int32_t* out_K, int32_t* out_z, int32_t* out_zstar, uint32_t* out_p)
+{
+    int rc = beam_need_params(b);
     if (rc) return rc;
-    BL_CHECK_ARG(n >= 0 && (n == 0 || (poses != nullptr && out_scores != nullptr)));
-    bl_ctx* ctx = b->ctx;
-    BL_HIP(hipSetDevice(ctx->device));
-    rc = beam_stage_rays(b, scan, &R);
-    if (rc) return rc;
-    if (n == 0) { b->last_n = 0; return BL_OK; }
-    rc = beam_stage_poses(b, poses, n);
-    if (!rc) rc = beam_launch_table(b, v, R, (const float4*)b->d_poses, n, nullptr, nullptr);
-    if (rc) return rc;
-    BL_HIP(hipMemcpyAsync(out_scores, b->d_scores, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    return BL_OK;
+    beam_form fm;
+    rc = beam_check_map(b, map, scan, &fm);
+    void* const outs[5] = {out_first, out_K, out_z, out_zstar, out_p};
+    return rc ? rc : beam_debug(b, fm, scan, pose, outs, 5);
 }
 
 extern "C" int bl_rangetable_debug_lookup(bl_beam* b, const bl_rangetable* rt, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_h,
@@ -698,51 +645,30 @@ extern "C" int bl_rangetable_debug_lookup(bl_beam* b, const bl_rangetable* rt, c
 {
     int rc = beam_need_params(b);
     if (rc) return rc;
-    bl_rangetable_view v;
-    int R = 0;
-    rc = beam_check_table(b, rt, scan, &v);
-    if (rc) return rc;
-    BL_CHECK_ARG(pose != nullptr);
-    bl_ctx* ctx = b->ctx;
-    BL_HIP(hipSetDevice(ctx->device));
-    rc = beam_stage_rays(b, scan, &R);
-    if (rc) return rc;
-    if (R == 0) return BL_OK;
-    rc = bl_grow(&b->d_dbg, &b->d_dbg_cap, 4 * (size_t)R * 4, false, ctx);
-    if (!rc) rc = beam_stage_poses(b, pose, 1);
-    if (rc) return rc;
-    BL_HIP(hipMemsetAsync(b->d_dbg, 0, 4 * (size_t)R * 4, ctx->stream));   // (an off-grid pose writes nothing)
-    rc = beam_launch_table(b, v, R, (const float4*)b->d_poses, 1, nullptr, (int32_t*)b->d_dbg);
-    if (rc) return rc;
-    void* outs[4] = {out_h, out_z, out_zstar, out_p};
-    for (int k = 0; k < 4; ++k)
-        if (outs[k]) BL_HIP(hipMemcpyAsync(outs[k], (const int32_t*)b->d_dbg + (size_t)k * R, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->stream));
-    BL_HIP(hipStreamSynchronize(ctx->stream));
-    return BL_OK;
+    beam_form fm;
+    rc = beam_check_table(b, rt, scan, &fm);
+    void* const outs[4] = {out_h, out_z, out_zstar, out_p};
+    return rc ? rc : beam_debug(b, fm, scan, pose, outs, 4);
 }
 
-struct beam_install_table { bl_beam* b; bl_rangetable_view v; int R; };
-static int beam_write_units_table(void* user, float4* rec, int n)
+extern "C" int bl_beam_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_grid* map, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose)
 {
-    const beam_install_table* q = (const beam_install_table*)user;
-    return beam_launch_table(q->b, q->v, q->R, rec, n, rec, nullptr);
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    beam_install q;
+    q.b = b;
+    rc = beam_check_map(b, map, scan, &q.fm);
+    return rc ? rc : beam_reweigh(q, pf, scan, out_pose);
 }
 
 extern "C" int bl_rangetable_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_rangetable* rt, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose)
 {
     int rc = beam_need_params(b);
     if (rc) return rc;
-    beam_install_table q;
+    beam_install q;
     q.b = b;
-    rc = beam_check_table(b, rt, scan, &q.v);
-    if (rc) return rc;
-    BL_CHECK_ARG(pf != nullptr);
-    rc = bl_pf_install_units(pf, b->ctx, nullptr, nullptr, nullptr);   // the filter's state and ctx, before anything is enqueued
-    if (rc) return rc;
-    BL_HIP(hipSetDevice(b->ctx->device));
-    rc = beam_stage_rays(b, scan, &q.R);
-    if (rc) return rc;
-    return bl_pf_install_units(pf, b->ctx, beam_write_units_table, &q, out_pose);
+    rc = beam_check_table(b, rt, scan, &q.fm);
+    return rc ? rc : beam_reweigh(q, pf, scan, out_pose);
 }
 
 extern "C" int bl_beam_units(bl_beam* b, uint32_t* out_units, int n)

@@ -5,8 +5,8 @@
 //
 //   k_rt_build    over a box of cells (the whole grid for a build, the changed box widened by reach for an update): a workgroup per
 //                 RT_WG_CELLS cells of the box in row order, a wave per RT_WAVE_CELLS of them one after the other, a LANE PER HEADING
-//                 in rounds of 64.  The lane walks the reference's Bresenham loop from the cell towards cell + D[h] and stops at the
-//                 first occupied cell, or when it leaves the grid (a walk that starts inside never comes back).  An occupied start cell
+//                 in rounds of 64.  The lane's walk from the cell towards cell + D[h] is the cast's own (beam_first_hit, bl_beam_dev.h),
+//                 ended where it leaves the grid, and the entry the cast's length of the hit cell (beam_quarter).  An occupied start cell
 //                 is settled without a walk.  D[] lives in LDS.  A round stores 64 consecutive uint16 of the cell's row: 128 bytes.
 //                 The map bytes come from the grid through L2; the other form -- the workgroup's tile of cells widened by reach staged
 //                 in LDS -- was not built and is not measured.
@@ -51,19 +51,10 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_build(rt_args a)
         }
         for (int h = lane; h < a.Hn; h += 64) {
             const int2 d = s_dir[h];
-            const int dx = abs(d.x), dy = abs(d.y);
-            const int stepx = d.x > 0 ? 1 : -1, stepy = d.y > 0 ? 1 : -1;
-            const int K = max(dx, dy);
-            int err = dx - dy, x = sx, y = sy;
-            uint32_t v = BL_RANGETABLE_NONE;
-            for (int k = 0; k < K; ++k) {                               // mapping.cpp:101-127, end cell excluded
-                if (!((unsigned int)x < (unsigned int)W && (unsigned int)y < (unsigned int)H)) break;
-                if (a.cells[(size_t)y * W + x] >= a.occ_min) { v = (uint32_t)beam_quarter(x, y, sx, sy); break; }
-                const int e2 = 2 * err;
-                if (e2 >= -dy) { err -= dy; x += stepx; }
-                if (e2 <= dx) { err += dx; y += stepy; }
-            }
-            row[h] = (uint16_t)v;
+            const beam_hit hit = beam_first_hit(sx, sy, sx + d.x, sy + d.y,
+                [&](int x, int y) { return a.cells[(size_t)y * W + x] >= a.occ_min; },
+                [&](int x, int y) { return !((unsigned int)x < (unsigned int)W && (unsigned int)y < (unsigned int)H); });
+            row[h] = (uint16_t)(hit.first < hit.K ? (uint32_t)beam_quarter(hit.x, hit.y, sx, sy) : (uint32_t)BL_RANGETABLE_NONE);
         }
     }
 }
@@ -143,9 +134,10 @@ extern "C" int bl_rangetable_build(bl_rangetable* rt, const bl_beam* beam, const
     bl_beam_view_host(beam, &bv);
     BL_CHECK_ARG(bv.ctx == rt->ctx && map->ctx == rt->ctx);
     if (!bv.have_params) { bl_set_error("beam model has no parameters (bl_beam_set_params first)"); return BL_ERR_STATE; }
-    const double r = ceil((double)bv.max_range * (double)map->frame.cpm);
-    BL_CHECK_ARG(r >= 1.0 && r <= (double)BL_BEAM_MAX_REACH);           // (false for NaN too)
-    const int W = map->frame.width, H = map->frame.height, Hn = rt->headings, reach = (int)r;
+    int reach = 0;
+    const int rr = beam_reach(bv.max_range, map->frame.cpm, &reach);
+    if (rr) return rr;
+    const int W = map->frame.width, H = map->frame.height, Hn = rt->headings;
     BL_CHECK_ARG(W >= 1 && H >= 1);
     const long long entries = (long long)W * H * Hn;
     BL_CHECK_ARG(entries <= RT_MAX_ENTRIES);                            // before anything is allocated

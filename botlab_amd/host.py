@@ -1448,15 +1448,35 @@ class BeamModel:
         _capi.load().bl_beam_unit_table(out.ctypes.data)
         return out
 
-    def scores(self, grid, scan, poses):
-        """int64 [n]: S of n poses, an [n][3] array of x, y, theta (BEAM_OFF_GRID for a pose that takes no part)."""
+    def _scores(self, fn, source, scan, poses):
+        """Poses in, scores out through bl_beam_scores or bl_rangetable_scores; source: the grid or the table."""
         q = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
         hp = np.zeros(len(q), POSE_DTYPE)
         hp["x"], hp["y"], hp["theta"] = q[:, 0], q[:, 1], q[:, 2]
         out = np.zeros(max(len(q), 1), np.int64)
         ls = scan.as_c()
-        check(self.ctx.lib.bl_beam_scores(self.h, grid.h, C.byref(ls), hp.ctypes.data, len(q), out.ctypes.data))
+        check(fn(self.h, source.h, C.byref(ls), hp.ctypes.data, len(q), out.ctypes.data))
         return out[:len(q)]
+
+    def _debug(self, fn, source, scan, pose, names):
+        """The debug planes of one pose, int32 each but the last (p, uint32), cut to the used rays."""
+        ls = scan.as_c()
+        m = max(scan.num_ranges, 1)
+        a = [np.zeros(m, np.int32) for _ in names[:-1]] + [np.zeros(m, np.uint32)]
+        po = make_pose(*pose)
+        check(fn(self.h, source.h, C.byref(ls), C.byref(po), *[v.ctypes.data for v in a]))
+        r = self.ctx.lib.bl_beam_last_rays(self.h)
+        return {k: v[:r].astype(np.int64) for k, v in zip(names, a)}
+
+    def _reweigh(self, fn, pf, source, scan):
+        ls = scan.as_c()
+        out = Pose()
+        check(fn(self.h, pf.h, source.h, C.byref(ls), C.byref(out)))
+        return out
+
+    def scores(self, grid, scan, poses):
+        """int64 [n]: S of n poses, an [n][3] array of x, y, theta (BEAM_OFF_GRID for a pose that takes no part)."""
+        return self._scores(self.ctx.lib.bl_beam_scores, grid, scan, poses)
 
     def units(self, n):
         """uint32 [n]: the units of the last scores() or reweigh() (n: that call's count)."""
@@ -1466,48 +1486,24 @@ class BeamModel:
 
     def debug_cast(self, grid, scan, pose):
         """dict of int64 arrays over the used rays of one pose (x, y, theta): first, K, z, zstar, p."""
-        ls = scan.as_c()
-        m = max(scan.num_ranges, 1)
-        a = [np.zeros(m, np.int32) for _ in range(4)] + [np.zeros(m, np.uint32)]
-        po = make_pose(*pose)
-        check(self.ctx.lib.bl_beam_debug_cast(self.h, grid.h, C.byref(ls), C.byref(po), *[v.ctypes.data for v in a]))
-        r = self.ctx.lib.bl_beam_last_rays(self.h)
-        return {k: v[:r].astype(np.int64) for k, v in zip(("first", "K", "z", "zstar", "p"), a)}
+        return self._debug(self.ctx.lib.bl_beam_debug_cast, grid, scan, pose, ("first", "K", "z", "zstar", "p"))
 
     def reweigh(self, pf, grid, scan):
         """bl_beam_reweigh_pf: the filter's weight units replaced in place; returns the beam-weighted posterior pose."""
-        ls = scan.as_c()
-        out = Pose()
-        check(self.ctx.lib.bl_beam_reweigh_pf(self.h, pf.h, grid.h, C.byref(ls), C.byref(out)))
-        return out
+        return self._reweigh(self.ctx.lib.bl_beam_reweigh_pf, pf, grid, scan)
 
     def scores_table(self, table, scan, poses):
         """bl_rangetable_scores: scores() with the expected ranges looked up in a built RangeTable instead of cast against the map.
         The table is not checked against the live map."""
-        q = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
-        hp = np.zeros(len(q), POSE_DTYPE)
-        hp["x"], hp["y"], hp["theta"] = q[:, 0], q[:, 1], q[:, 2]
-        out = np.zeros(max(len(q), 1), np.int64)
-        ls = scan.as_c()
-        check(self.ctx.lib.bl_rangetable_scores(self.h, table.h, C.byref(ls), hp.ctypes.data, len(q), out.ctypes.data))
-        return out[:len(q)]
+        return self._scores(self.ctx.lib.bl_rangetable_scores, table, scan, poses)
 
     def debug_lookup(self, table, scan, pose):
         """dict of int64 arrays over the used rays of one pose (x, y, theta): h, z, zstar, p."""
-        ls = scan.as_c()
-        m = max(scan.num_ranges, 1)
-        a = [np.zeros(m, np.int32) for _ in range(3)] + [np.zeros(m, np.uint32)]
-        po = make_pose(*pose)
-        check(self.ctx.lib.bl_rangetable_debug_lookup(self.h, table.h, C.byref(ls), C.byref(po), *[v.ctypes.data for v in a]))
-        r = self.ctx.lib.bl_beam_last_rays(self.h)
-        return {k: v[:r].astype(np.int64) for k, v in zip(("h", "z", "zstar", "p"), a)}
+        return self._debug(self.ctx.lib.bl_rangetable_debug_lookup, table, scan, pose, ("h", "z", "zstar", "p"))
 
     def reweigh_table(self, pf, table, scan):
         """bl_rangetable_reweigh_pf: reweigh() with the table behind it."""
-        ls = scan.as_c()
-        out = Pose()
-        check(self.ctx.lib.bl_rangetable_reweigh_pf(self.h, pf.h, table.h, C.byref(ls), C.byref(out)))
-        return out
+        return self._reweigh(self.ctx.lib.bl_rangetable_reweigh_pf, pf, table, scan)
 
     def debugSet(self, stage_windows=False, window_bytes=0):
         """Stage the workgroups' windows in LDS when they fit window_bytes (0: 40960).  Off by default: the grid is read directly."""

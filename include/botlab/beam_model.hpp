@@ -51,13 +51,7 @@ public:
     // S of every pose (BL_BEAM_OFF_GRID for one that takes no part)
     std::vector<int64_t> scores(const OccupancyGrid& map, const Lidar& scan, const std::vector<Pose>& poses)
     {
-        bl_lidar_t v = lidar_view(scan);
-        std::vector<bl_pose_xyt_t> in(poses.size() ? poses.size() : 1);
-        for (std::size_t i = 0; i < poses.size(); ++i) in[i] = pose_in(poses[i]);
-        std::vector<int64_t> out(in.size());
-        check(bl_beam_scores(h_, map.device(), &v, in.data(), static_cast<int>(poses.size()), out.data()), "bl_beam_scores");
-        out.resize(poses.size());
-        return out;
+        return scoresBy(bl_beam_scores, map.device(), "bl_beam_scores", scan, poses);
     }
     // the units of the last scores() or reweighBeam(); n: that call's count
     std::vector<uint32_t> units(int n)
@@ -70,14 +64,8 @@ public:
     // the per-ray values of one pose's used rays
     BeamCast debugCast(const OccupancyGrid& map, const Lidar& scan, const Pose& pose)
     {
-        bl_lidar_t v = lidar_view(scan);
-        bl_pose_xyt_t p = pose_in(pose);
-        const std::size_t m = static_cast<std::size_t>(v.num_ranges > 0 ? v.num_ranges : 1);
         BeamCast c;
-        c.first.resize(m); c.K.resize(m); c.z.resize(m); c.zstar.resize(m); c.p.resize(m);
-        check(bl_beam_debug_cast(h_, map.device(), &v, &p, c.first.data(), c.K.data(), c.z.data(), c.zstar.data(), c.p.data()), "bl_beam_debug_cast");
-        const std::size_t r = static_cast<std::size_t>(bl_beam_last_rays(h_));
-        c.first.resize(r); c.K.resize(r); c.z.resize(r); c.zstar.resize(r); c.p.resize(r);
+        debugPlanes(bl_beam_debug_cast, map.device(), "bl_beam_debug_cast", scan, pose, c.first, c.K, c.z, c.zstar, c.p);
         return c;
     }
     // scores() with the expected ranges looked up in a built range table (RangeTableT, range_table.hpp) instead of cast against the
@@ -85,13 +73,7 @@ public:
     template <class Table>
     std::vector<int64_t> scoresTable(const Table& table, const Lidar& scan, const std::vector<Pose>& poses)
     {
-        bl_lidar_t v = lidar_view(scan);
-        std::vector<bl_pose_xyt_t> in(poses.size() ? poses.size() : 1);
-        for (std::size_t i = 0; i < poses.size(); ++i) in[i] = pose_in(poses[i]);
-        std::vector<int64_t> out(in.size());
-        check(bl_rangetable_scores(h_, table.device(), &v, in.data(), static_cast<int>(poses.size()), out.data()), "bl_rangetable_scores");
-        out.resize(poses.size());
-        return out;
+        return scoresBy(bl_rangetable_scores, table.device(), "bl_rangetable_scores", scan, poses);
     }
     // a filter's weight units replaced in place by the scoring by table (Filter: ParticleFilterT); the beam-weighted posterior pose
     template <class Filter, class Table>
@@ -106,14 +88,8 @@ public:
     template <class Table>
     BeamCast debugLookup(const Table& table, const Lidar& scan, const Pose& pose, std::vector<int32_t>* h)
     {
-        bl_lidar_t v = lidar_view(scan);
-        bl_pose_xyt_t p = pose_in(pose);
-        const std::size_t m = static_cast<std::size_t>(v.num_ranges > 0 ? v.num_ranges : 1);
         BeamCast c;
-        h->resize(m); c.z.resize(m); c.zstar.resize(m); c.p.resize(m);
-        check(bl_rangetable_debug_lookup(h_, table.device(), &v, &p, h->data(), c.z.data(), c.zstar.data(), c.p.data()), "bl_rangetable_debug_lookup");
-        const std::size_t r = static_cast<std::size_t>(bl_beam_last_rays(h_));
-        h->resize(r); c.z.resize(r); c.zstar.resize(r); c.p.resize(r);
+        debugPlanes(bl_rangetable_debug_lookup, table.device(), "bl_rangetable_debug_lookup", scan, pose, *h, c.z, c.zstar, c.p);
         return c;
     }
     BeamTables tables(float cellsPerMeter) const
@@ -141,6 +117,31 @@ public:
     bl_beam* device() const { return h_; }
 
 private:
+    // poses in, scores out through fn (bl_beam_scores or bl_rangetable_scores) on its map or table
+    template <class Fn, class Source>
+    std::vector<int64_t> scoresBy(Fn fn, const Source* source, const char* what, const Lidar& scan, const std::vector<Pose>& poses)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        std::vector<bl_pose_xyt_t> in(poses.size() ? poses.size() : 1);
+        for (std::size_t i = 0; i < poses.size(); ++i) in[i] = pose_in(poses[i]);
+        std::vector<int64_t> out(in.size());
+        check(fn(h_, source, &v, in.data(), static_cast<int>(poses.size()), out.data()), what);
+        out.resize(poses.size());
+        return out;
+    }
+    // the debug planes of one pose through fn (bl_beam_debug_cast or bl_rangetable_debug_lookup): sized for the whole scan, filled,
+    // cut to the used rays
+    template <class Fn, class Source, class... Planes>
+    void debugPlanes(Fn fn, const Source* source, const char* what, const Lidar& scan, const Pose& pose, Planes&... planes)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        bl_pose_xyt_t p = pose_in(pose);
+        const int sized[] = {(planes.resize(static_cast<std::size_t>(v.num_ranges > 0 ? v.num_ranges : 1)), 0)...};
+        check(fn(h_, source, &v, &p, planes.data()...), what);
+        const int cut[] = {(planes.resize(static_cast<std::size_t>(bl_beam_last_rays(h_))), 0)...};
+        (void)sized; (void)cut;
+    }
+
     bl_beam* h_;
 };
 

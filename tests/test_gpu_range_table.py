@@ -391,3 +391,72 @@ def test_state_refusals(gpu_ctx):
         rt.close()
         beam.close()
         grid.close()
+
+
+def test_cast_and_table_alternate_on_one_handle(gpu_ctx):
+    """Both scoring forms through one handle's buffers, closing launches and state, turn and turn about: 1 pose, 33 (two workgroups,
+    the second with one pose) and none; 65 used rays (a lane takes two) and none; a debug call of either form between two scoring
+    calls.  After every call the scores and units are the model's, a wrong count is refused and the device time answers."""
+    cells = bc.room(16, 12)
+    cells[3:9, 6] = 100
+    cells[8, 9:13] = 100
+    cells[2, 11] = 1
+    rg, th = bc.octant_scan(65, r0=0.16, dr=0.04)
+    rng = np.random.default_rng(11)
+    poses = np.stack([rng.uniform(-0.05, 16 * rc.MPC + 0.05, 33), rng.uniform(-0.05, 12 * rc.MPC + 0.05, 33), rng.uniform(-3.1, 3.1, 33)], axis=1)
+    poses[0], poses[32] = bc.centre(3, 4, 0.4), bc.centre(12, 3, -2.0)
+    c = bc.case(cells, rg, th, poses, max_range=0.5)
+    none = dict(c, ranges=np.array([0.1, float("nan"), 0.0], np.float32), thetas=np.zeros(3, np.float32))
+    assert len(bm.used_rays(c["ranges"], c["thetas"], c["params"])[0]) == 65 and len(bm.used_rays(none["ranges"], none["thetas"], c["params"])[0]) == 0
+    beam, grid, rt = beam_of(gpu_ctx, c), grid_of(gpu_ctx, c), bl.RangeTable(gpu_ctx, 64)
+    try:
+        rt.build(beam, grid)
+        t = beam.tables(c["cpm"])
+        table = rm.build(c["cells"], rt.directions().astype(np.int64), c["params"]["occ_min"])
+        U = bl.BeamModel.unitTable()
+
+        def units_answer(exp, n):
+            assert np.array_equal(beam.units(n), bm.units(exp, c["params"]["span"], U))
+            with pytest.raises(bl.BotlabHipError, match="status 2"):
+                beam.units(n + 1)
+            assert beam.lastDeviceMs() > 0
+
+        def score(form, d, n):
+            p = d["poses"][:n]
+            if form == "cast":
+                got = beam.scores(grid, scan_of(d), p)
+                exp = bm.scores(d["cells"], d["origin"], d["cpm"], d["ranges"], d["thetas"], p, d["params"], t)
+            else:
+                got = beam.scores_table(rt, scan_of(d), p)
+                exp = rm.scores(table, d["origin"], d["cpm"], d["ranges"], d["thetas"], p, d["params"], t)
+            assert got.tolist() == exp.tolist(), (form, n)
+            units_answer(exp, n)
+            return exp
+
+        rays = bm.used_rays(c["ranges"], c["thetas"], c["params"])
+        s33 = score("cast", c, 33)
+        assert (s33 == bm.OFF_GRID).any() and (s33 != bm.OFF_GRID).sum() > 20 and s33[32] != bm.OFF_GRID
+        s1 = score("table", c, 1)
+        g = beam.debug_cast(grid, scan_of(c), c["poses"][32])                 # a debug call of the other form in between
+        e = bm.cast(c["cells"], c["origin"], c["cpm"], rays, c["poses"][32], c["params"], t)
+        assert all(np.array_equal(g[k], e[k]) for k in ("first", "K", "z", "zstar", "p")) and (e["first"] < e["K"]).any()
+        units_answer(s1, 1)                                                   # ... leaves the scoring call before it standing
+        score("cast", c, 0)
+        st = score("table", c, 33)
+        g = beam.debug_lookup(rt, scan_of(c), c["poses"][0])
+        e = rm.lookup(table, c["origin"], c["cpm"], rays, c["poses"][0], c["params"], t)
+        assert all(np.array_equal(g[k], e[k]) for k in ("h", "z", "zstar", "p")) and (e["zstar"] >= 0).any()
+        units_answer(st, 33)
+        assert score("cast", none, 1).tolist() == [0]
+        sn = score("table", none, 33)
+        assert set(sn.tolist()) == {0, bm.OFF_GRID}
+        assert beam.debug_cast(grid, scan_of(none), c["poses"][0])["p"].tolist() == []
+        units_answer(sn, 33)
+        score("table", c, 0)
+        assert score("cast", c, 33).tolist() == s33.tolist()
+        assert score("cast", c, 1).tolist() == s33[:1].tolist()
+        assert score("table", c, 33).tolist() == st.tolist()
+    finally:
+        rt.close()
+        beam.close()
+        grid.close()
