@@ -1202,6 +1202,14 @@ void bl_frontier_scratch_free(bl_ctx* ctx)
     ctx->frontier = nullptr;
 }
 
+// Entries of the frontier table of a scratch of `cells` cells: the most frontiers ANY grid of that many cells can hold, whatever its
+// shape (the scratch outlives the grid it was sized for: a later grid of another shape runs on it as long as its cells fit).
+// Frontiers are 8-separated components, so a W x H grid holds at most one per 2 x 2 block, ceil(W/2) * ceil(H/2) of them (a lattice
+// of single cells reaches that), which is at most (W + 1)(H + 1) / 4 = (WH + W + H + 1) / 4; with W, H >= 1 and WH <= cells,
+// W + H <= cells + 1, hence at most cells / 2 + 1 / 2.  (cells / 4 + 4, the blocks of a grid with EVEN sides, was one short for a
+// 9 x 9 lattice: 25 frontiers, 24 entries.)
+static int frontier_table_entries(size_t cells) { return (int)(cells / 2 + 1); }
+
 // The kernels of one find_map_frontiers on ctx's stream, the robot pose from the host or read on the device; nothing waits.
 static int frontiers_launch(bl_ctx* ctx, const bl_grid* map, const bl_pose_xyt_t* robot_pose, const bl_pose_xyt_t* d_pose)
 {
@@ -1217,7 +1225,7 @@ static int frontiers_launch(bl_ctx* ctx, const bl_grid* map, const bl_pose_xyt_t
         for (void* q : dev) if (q) BL_HIP(hipFree(q));
         s->cls = nullptr; s->claim = nullptr; s->fclaim = nullptr; s->queue = nullptr; s->out_cells = nullptr; s->out_offsets = nullptr; s->nb = nullptr;
         s->cells = 0;
-        s->cap_frontiers = (int)(n / 4 + 4);               // components are 8-separated: at most one per 2x2 block
+        s->cap_frontiers = frontier_table_entries(n);
         BL_HIP(hipMalloc((void**)&s->cls, n));
         BL_HIP(hipMalloc((void**)&s->nb, n));
         BL_HIP(hipMalloc((void**)&s->claim, n * 4));
