@@ -287,6 +287,15 @@ class RangeTableInfo(C.Structure):
 assert C.sizeof(RangeTableInfo) == 32 and RangeTableInfo.bytes.offset == 24
 
 
+class ClearanceInfo(C.Structure):
+    """bl_clearance_info_t: the shape, cap, occ_min and device bytes of a clearance grid (32 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("cap", C.c_int32), ("occ_min", C.c_int32), ("built", C.c_int32),
+                ("pad", C.c_int32), ("bytes", C.c_int64)]
+
+
+assert C.sizeof(ClearanceInfo) == 32 and ClearanceInfo.bytes.offset == 24
+
+
 class ScanLogStats(C.Structure):
     """bl_scanlog_stats_t: the launch shape and the device time of the last map rebuild (64 bytes)."""
     _fields_ = [("tiles", C.c_int64), ("chunks", C.c_int64), ("pairs", C.c_int64), ("scratch_bytes", C.c_int64), ("chunk_scans", C.c_int32),
@@ -639,6 +648,16 @@ SIGNATURES = {
     "bl_rangetable_scores": (C.c_int, [_vp, _vp, _P(Lidar), _vp, C.c_int, _vp]),
     "bl_rangetable_reweigh_pf": (C.c_int, [_vp, _vp, _vp, _P(Lidar), _P(Pose)]),
     "bl_rangetable_debug_lookup": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _vp, _vp, _vp, _vp]),
+    "bl_clearance_create": (C.c_int, [_vp, C.c_int, _P(_vp)]),
+    "bl_clearance_destroy": (None, [_vp]),
+    "bl_clearance_build": (C.c_int, [_vp, _vp, C.c_int]),
+    "bl_clearance_update": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bl_clearance_read": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "bl_clearance_info": (C.c_int, [_vp, _P(ClearanceInfo)]),
+    "bl_clearance_last_device_ms": (C.c_int, [_vp, _P(C.c_float)]),
+    "bl_clearance_scores": (C.c_int, [_vp, _vp, _P(Lidar), _vp, C.c_int, _vp]),
+    "bl_clearance_reweigh_pf": (C.c_int, [_vp, _vp, _vp, _P(Lidar), _P(Pose)]),
+    "bl_clearance_debug_cast": (C.c_int, [_vp, _vp, _P(Lidar), _P(Pose), _vp, _vp, _vp, _vp, _vp, _vp]),
     "bl_scanlog_create": (C.c_int, [_vp, C.c_int, C.c_int, _P(_vp)]),
     "bl_scanlog_destroy": (None, [_vp]),
     "bl_scanlog_append": (C.c_int, [_vp, _P(Lidar), _P(Pose)]),

@@ -17,13 +17,17 @@
 //   k_beam_lookup the second scoring form ("range table" in the header): the same launch shape and records, but the expected range of a
 //                 ray is one uint16 of a range table (bl_rangetable.hip) -- the row of the pose's start cell at the ray's quantised
 //                 heading -- and the measured one the range in quarter cells: no sine, no walk.  Off unless called.
+//   k_beam_leap   the third scoring form ("clearance grid" in the header): k_beam_cast's launch shape, records and per-ray values, but
+//                 the lane reads a clearance grid (bl_clearance.hip) instead of the map and leaps as far as each entry allows
+//                 (beam_first_hit_leap): a few dependent loads through L2 with one 32-bit division each, where the loop reads every
+//                 cell.  first, K, the hit cell and everything behind them equal the cast's.  Off unless called.
 //   k_beam_final  one workgroup: Smax over the workgroups' records, and how many workgroups took which path.
 //   k_beam_units  a thread per pose: the units, to the handle's array and, for a filter, into the record's weight word in place.
 //
-// The two scoring kernels are their prologue (tables to LDS; the cast's box and window) round one frame, beam_score_poses, with the
+// The three scoring kernels are their prologue (tables to LDS; the cast's box and window) round one frame, beam_score_poses, with the
 // form's per-ray body; the rules of a ray -- start cell, walk, lengths, p, lg, heading index -- are bl_beam_dev.h's.  On the host
-// a beam_form says where the expected ranges come from, and the launcher, "scores", "debug" and "reweigh" exist once for both; the
-// six entry points check their form (beam_check_map, beam_check_table) and call them.
+// a beam_form says where the expected ranges come from, and the launcher, "scores", "debug" and "reweigh" exist once for all; the
+// nine entry points check their form (beam_check_map, beam_check_table, beam_check_clearance) and call them.
 //
 // Integers only behind the end cells; no atomics; no workgroup waits for another; no result depends on the launch shape.
 #include <limits.h>
@@ -228,6 +232,62 @@ __global__ __launch_bounds__(BEAM_THREADS) void k_beam_lookup(beam_lookup_args a
             lgp = beam_lg(s_tab, p, a.ln2);
         }
         if (dbg) { dbg[r] = h; dbg[a.R + r] = z; dbg[2 * a.R + r] = zstar; dbg[3 * a.R + r] = (int32_t)p; }
+        return lgp;
+    });
+}
+
+// ---------------------------------------------------------------------------------------------------------------- scoring by leaps
+struct beam_leap_args {
+    const uint8_t* clear; bl_frame f;                     // the clearance grid and the frame it was built on
+    const float* ranges; const float* thetas; int R;
+    const float4* poses; int n;
+    float max_range; int hit_cut;
+    uint32_t rnd, max_free, max_blocked; int ln2;
+    const uint32_t* tables;
+    long long* scores; long long* wg_max; uint8_t* wg_path;
+    int32_t* dbg;                                         // null, or [6][R] of pose 0: first, K, z, zstar, p, rounds
+};
+
+// k_beam_cast's launch shape and records; a ray's geometry, `has`, z, z*, p and lg are beam_ray's line for line (k_beam_cast is not
+// edited for this form), and only the walk differs: entries of the clearance grid through L2, one per leap
+__global__ __launch_bounds__(BEAM_THREADS) void k_beam_leap(beam_leap_args a)
+{
+    __shared__ uint32_t s_tab[BEAM_TABLE_WORDS];
+    __shared__ long long s_max[BEAM_THREADS / 64];
+    for (int i = threadIdx.x; i < BEAM_TABLE_WORDS; i += BEAM_THREADS) s_tab[i] = a.tables[i];
+    __syncthreads();
+    const int W = a.f.width, H = a.f.height;
+    // path 1: nothing is staged, k_beam_final counts the workgroup with the direct ones
+    beam_score_poses(a, s_max, 1, [&](const float4& pose, float px, float py, int sx, int sy, int r, int32_t* dbg) {
+        const float range = a.ranges[r];
+        const bool is_max = range >= a.max_range;
+        const float ang = bl_wrap_to_pi(pose.z - a.thetas[r]);
+        float sn, cs;
+        bl_sincosf_cells(ang, &sn, &cs);
+        const float fmx = a.max_range * cs * a.f.cpm + px, fmy = a.max_range * sn * a.f.cpm + py;
+        const float fex = range * cs * a.f.cpm + px, fey = range * sn * a.f.cpm + py;
+        bool has = __builtin_fabsf(fmx) < 0x1p30f && __builtin_fabsf(fmy) < 0x1p30f;
+        if (!is_max) has = has && __builtin_fabsf(fex) < 0x1p30f && __builtin_fabsf(fey) < 0x1p30f;
+        int first = -1, K = -1, z = -1, zstar = -1, rounds = -1, lgp = 0;
+        uint32_t p = 0;
+        if (has) {
+            const beam_leap_hit hit = beam_first_hit_leap(sx, sy, (int)fmx, (int)fmy,
+                [&](int x, int y) { return (int)a.clear[(size_t)y * W + x]; },
+                [&](int x, int y) { return !((unsigned int)x < (unsigned int)W && (unsigned int)y < (unsigned int)H); });
+            first = hit.first; K = hit.K; rounds = hit.rounds;
+            const bool expect = first < K;
+            if (expect) zstar = beam_quarter(hit.x, hit.y, sx, sy);
+            if (is_max) {
+                p = expect ? a.max_blocked : a.max_free;
+            } else {
+                z = beam_quarter((int)fex, (int)fey, sx, sy);
+                p = beam_return_p(s_tab, a.rnd, a.hit_cut, expect, z, zstar);
+            }
+            lgp = beam_lg(s_tab, p, a.ln2);
+        }
+        if (dbg) {
+            dbg[r] = first; dbg[a.R + r] = K; dbg[2 * a.R + r] = z; dbg[3 * a.R + r] = zstar; dbg[4 * a.R + r] = (int32_t)p; dbg[5 * a.R + r] = rounds;
+        }
         return lgp;
     });
 }
@@ -446,11 +506,11 @@ static int beam_stage_rays(bl_beam* b, const bl_lidar_t* scan, int* R_out)
     return BL_OK;
 }
 
-// where the expected ranges come from: cast against `map`, or (map null) looked up in the table `v`; reach: the beam model's in cells
-// on that map's or table's frame (a table's own is checked to equal it)
-struct beam_form { const bl_grid* map; int reach; bl_rangetable_view v; };
+// where the expected ranges come from: cast against `map`, or (map null) looked up in the table `v`, or (leap) found by leaps over the
+// clearance grid `c`; reach: the beam model's in cells on that map's, table's or grid's frame (a table's own is checked to equal it)
+struct beam_form { const bl_grid* map; int reach; bl_rangetable_view v; bool leap; bl_clearance_view c; };
 
-// the fields the two kernels' argument structs share, for a map or table of `reach` cells
+// the fields the three kernels' argument structs share, for a map or table of `reach` cells
 template <class Args>
 static void beam_fill_args(Args& a, const bl_beam* b, int reach, int R, const float4* poses, int n, int blocks, int32_t* dbg)
 {
@@ -467,7 +527,7 @@ static void beam_fill_args(Args& a, const bl_beam* b, int reach, int R, const fl
 
 // The launches for n poses at `poses` (device): the form's scoring kernel, k_beam_final and -- not for a debug launch, which leaves
 // the last call's units and count alone -- k_beam_units, then the closing event.  rec: the filter's record for k_beam_units, or
-// null; dbg: the form's planes ([5][R] cast, [4][R] table) of pose 0, or null
+// null; dbg: the form's planes ([5][R] cast, [4][R] table, [6][R] leaps) of pose 0, or null
 static int beam_launch(bl_beam* b, const beam_form& fm, int R, const float4* poses, int n, float4* rec, int32_t* dbg)
 {
     bl_ctx* ctx = b->ctx;
@@ -478,7 +538,12 @@ static int beam_launch(bl_beam* b, const beam_form& fm, int R, const float4* pos
     if (rc) return rc;
     BL_HIP(hipEventRecord(b->ev_stage, ctx->stream));                   // the pinned blocks have left once this is reached
     BL_HIP(hipEventRecord(b->ev_a, ctx->stream));
-    if (fm.map) {
+    if (fm.leap) {
+        beam_leap_args a;
+        beam_fill_args(a, b, fm.reach, R, poses, n, blocks, dbg);
+        a.clear = fm.c.d_grid; a.f = fm.c.frame;
+        hipLaunchKernelGGL(k_beam_leap, dim3((unsigned int)blocks), dim3(BEAM_THREADS), 0, ctx->stream, a);
+    } else if (fm.map) {
         beam_args a;
         beam_fill_args(a, b, fm.reach, R, poses, n, blocks, dbg);
         a.cells = fm.map->cells; a.f = fm.map->frame;
@@ -508,7 +573,7 @@ static int beam_launch(bl_beam* b, const beam_form& fm, int R, const float4* pos
 static int beam_check_map(const bl_beam* b, const bl_grid* map, const bl_lidar_t* scan, beam_form* fm)
 {
     BL_CHECK_ARG(map != nullptr && scan != nullptr && map->ctx == b->ctx);
-    fm->map = map;
+    fm->map = map; fm->leap = false;
     return beam_reach(b->params.max_range, map->frame.cpm, &fm->reach);
 }
 
@@ -522,7 +587,7 @@ static int beam_check_table(const bl_beam* b, const bl_rangetable* rt, const bl_
 {
     BL_CHECK_ARG(rt != nullptr && scan != nullptr);
     bl_rangetable_view* v = &fm->v;
-    fm->map = nullptr;
+    fm->map = nullptr; fm->leap = false;
     bl_rangetable_view_host(rt, v);
     BL_CHECK_ARG(v->ctx == b->ctx);
     if (!v->built) { bl_set_error("range table not built (bl_rangetable_build first)"); return BL_ERR_STATE; }
@@ -535,6 +600,22 @@ static int beam_check_table(const bl_beam* b, const bl_rangetable* rt, const bl_
         return BL_ERR_STATE;
     }
     return BL_OK;
+}
+
+// the grid's view, once it is known to be built on this ctx with the occ_min the parameters in force give
+static int beam_check_clearance(const bl_beam* b, const bl_clearance* cl, const bl_lidar_t* scan, beam_form* fm)
+{
+    BL_CHECK_ARG(cl != nullptr && scan != nullptr);
+    bl_clearance_view* c = &fm->c;
+    fm->map = nullptr; fm->leap = true;
+    bl_clearance_view_host(cl, c);
+    BL_CHECK_ARG(c->ctx == b->ctx);
+    if (!c->built) { bl_set_error("clearance grid not built (bl_clearance_build first)"); return BL_ERR_STATE; }
+    if (b->params.occ_min != c->occ_min) {
+        bl_set_error("clearance grid built with occ_min %d, the beam model has %d", c->occ_min, b->params.occ_min);
+        return BL_ERR_STATE;
+    }
+    return beam_reach(b->params.max_range, c->frame.cpm, &fm->reach);
 }
 
 // n host poses staged as the kernels read them
@@ -568,7 +649,7 @@ static int beam_scores(bl_beam* b, const beam_form& fm, const bl_lidar_t* scan, 
     return BL_OK;
 }
 
-// outs: the form's `planes` planes of R words each (5 cast, 4 table), any of them null
+// outs: the form's `planes` planes of R words each (5 cast, 4 table, 6 leaps), any of them null
 static int beam_debug(bl_beam* b, const beam_form& fm, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, void* const* outs, int planes)
 {
     BL_CHECK_ARG(pose != nullptr);
@@ -668,6 +749,36 @@ extern "C" int bl_rangetable_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_rangetab
     beam_install q;
     q.b = b;
     rc = beam_check_table(b, rt, scan, &q.fm);
+    return rc ? rc : beam_reweigh(q, pf, scan, out_pose);
+}
+
+extern "C" int bl_clearance_scores(bl_beam* b, const bl_clearance* cl, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores)
+{
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    beam_form fm;
+    rc = beam_check_clearance(b, cl, scan, &fm);
+    return rc ? rc : beam_scores(b, fm, scan, poses, n, out_scores);
+}
+
+extern "C" int bl_clearance_debug_cast(bl_beam* b, const bl_clearance* cl, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_first,
+                                       int32_t* out_K, int32_t* out_z, int32_t* out_zstar, uint32_t* out_p, int32_t* out_rounds)
+{
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    beam_form fm;
+    rc = beam_check_clearance(b, cl, scan, &fm);
+    void* const outs[6] = {out_first, out_K, out_z, out_zstar, out_p, out_rounds};
+    return rc ? rc : beam_debug(b, fm, scan, pose, outs, 6);
+}
+
+extern "C" int bl_clearance_reweigh_pf(bl_beam* b, bl_pf* pf, const bl_clearance* cl, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose)
+{
+    int rc = beam_need_params(b);
+    if (rc) return rc;
+    beam_install q;
+    q.b = b;
+    rc = beam_check_clearance(b, cl, scan, &q.fm);
     return rc ? rc : beam_reweigh(q, pf, scan, out_pose);
 }
 

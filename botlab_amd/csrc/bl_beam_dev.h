@@ -2,6 +2,7 @@
 // start cell, the first-hit walk, the tables' places, the length in quarter cells, a return's probability, the integer logarithm,
 // the look-up's heading index and the reach in cells.  k_beam_cast and k_beam_lookup (bl_beam.hip) score with them and k_rt_build
 // (bl_rangetable.hip) fills its entries with the same walk and length, so a table entry equals the cast's z* by construction.
+// k_beam_leap (bl_beam.hip) takes the same walk in leaps over a clearance grid (beam_first_hit_leap).
 //   host and device  everything but beam_reach
 //   host             beam_reach, with the library's error text
 // What differs stays with its kernel: where a cell is read from (the grid through L2 or a staged window), what leaving the grid
@@ -23,6 +24,7 @@ struct float4 { float x, y, z, w; };
 inline int min(int a, int b) { return a < b ? a : b; }
 inline int max(int a, int b) { return a > b ? a : b; }
 #endif
+#include "bl_mapray_dev.h"
 
 #define BEAM_HIT 0                        // the tables' places in the block of BEAM_TABLE_WORDS words
 #define BEAM_SHORT 1024
@@ -63,6 +65,31 @@ BL_HD beam_hit beam_first_hit(int sx, int sy, int tx, int ty, Occupied occupied,
         if (e2 <= dx) { err += dx; y += stepy; }
     }
     const beam_hit h = {k, K, x, y};
+    return h;
+}
+
+// The same walk in leaps ("clearance grid" in the header): clearance(x, y) of a cell inside the grid is a lower bound, 0 only for an
+// occupied cell, on the Chebyshev distance to the nearest occupied cell.  Consecutive cells of the walk are Chebyshev neighbours, so
+// from cell k with clearance d > 0 the cells k + 1 .. k + d - 1 are free and the walk goes on at cell k + d, placed by the closed form
+// of bl_mapray_dev.h: one division (K <= BL_BEAM_MAX_REACH + 1, so bl_walk_begin takes its 32-bit branch).  left(x, y): the cell lies
+// outside the grid, which ends the walk as it ends k_rt_build's; clearance is not asked about it.  first, K and the hit cell are
+// beam_first_hit's; rounds counts the calls of clearance.
+struct beam_leap_hit { int first, K, x, y, rounds; };
+template <class Clearance, class Left>
+BL_HD beam_leap_hit beam_first_hit_leap(int sx, int sy, int tx, int ty, Clearance clearance, Left left)
+{
+    const int4 ray = make_int4(sx, sy, tx, ty);
+    const int K = bl_ray_steps(ray);
+    int k = 0, rounds = 0, x = sx, y = sy;
+    while (k < K) {
+        bl_walk_cell(ray, k, &x, &y);
+        if (left(x, y)) { k = K; break; }
+        ++rounds;
+        const int d = clearance(x, y);
+        if (d == 0) break;
+        k += d;
+    }
+    const beam_leap_hit h = {k < K ? k : K, K, x, y, rounds};
     return h;
 }
 

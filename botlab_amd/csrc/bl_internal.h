@@ -199,6 +199,9 @@ void bl_beam_view_host(const bl_beam* b, bl_beam_view* out);
 // bl_rangetable.hip: what the beam model's scoring by table reads of a range table (bl_beam.hip); d_table is null until the first build
 struct bl_rangetable_view { bl_ctx* ctx; bool built; bl_frame frame; int headings, reach, occ_min; const uint16_t* d_table; };
 void bl_rangetable_view_host(const bl_rangetable* rt, bl_rangetable_view* out);
+// bl_clearance.hip: what the beam model's scoring by leaps reads of a clearance grid (bl_beam.hip); d_grid is null until the first build
+struct bl_clearance_view { bl_ctx* ctx; bool built; bl_frame frame; int cap, occ_min; const uint8_t* d_grid; };
+void bl_clearance_view_host(const bl_clearance* cl, bl_clearance_view* out);
 
 // RAII-less helpers
 int bl_timer_begin(bl_ctx* ctx, int id, hipEvent_t* a, hipEvent_t* b);

@@ -448,6 +448,10 @@ class ParticleFilter:
         """The same with the expected ranges looked up in a built RangeTable (BeamModel.reweigh_table)."""
         return beam.reweigh_table(self, table, scan)
 
+    def reweigh_beam_leap(self, beam, clearance, scan):
+        """The same with the expected ranges found by leaps over a built ClearanceGrid (BeamModel.reweigh_leap)."""
+        return beam.reweigh_leap(self, clearance, scan)
+
     def setStrictResampling(self, on=True):
         """Resample against the reference's own sequentially rounded cumulative weight (bl_pf_set_strict_resampling)."""
         check(self.ctx.lib.bl_pf_set_strict_resampling(self.h, 1 if on else 0))
@@ -1449,7 +1453,8 @@ class BeamModel:
         return out
 
     def _scores(self, fn, source, scan, poses):
-        """Poses in, scores out through bl_beam_scores or bl_rangetable_scores; source: the grid or the table."""
+        """Poses in, scores out through bl_beam_scores, bl_rangetable_scores or bl_clearance_scores; source: the grid, the table or the
+        clearance grid."""
         q = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
         hp = np.zeros(len(q), POSE_DTYPE)
         hp["x"], hp["y"], hp["theta"] = q[:, 0], q[:, 1], q[:, 2]
@@ -1459,10 +1464,10 @@ class BeamModel:
         return out[:len(q)]
 
     def _debug(self, fn, source, scan, pose, names):
-        """The debug planes of one pose, int32 each but the last (p, uint32), cut to the used rays."""
+        """The debug planes of one pose, int32 each but p (uint32), cut to the used rays."""
         ls = scan.as_c()
         m = max(scan.num_ranges, 1)
-        a = [np.zeros(m, np.int32) for _ in names[:-1]] + [np.zeros(m, np.uint32)]
+        a = [np.zeros(m, np.uint32 if k == "p" else np.int32) for k in names]
         po = make_pose(*pose)
         check(fn(self.h, source.h, C.byref(ls), C.byref(po), *[v.ctypes.data for v in a]))
         r = self.ctx.lib.bl_beam_last_rays(self.h)
@@ -1504,6 +1509,20 @@ class BeamModel:
     def reweigh_table(self, pf, table, scan):
         """bl_rangetable_reweigh_pf: reweigh() with the table behind it."""
         return self._reweigh(self.ctx.lib.bl_rangetable_reweigh_pf, pf, table, scan)
+
+    def scores_leap(self, clearance, scan, poses):
+        """bl_clearance_scores: scores() with the expected ranges found by leaps over a built ClearanceGrid; value for value the
+        cast's on the map the grid was built on.  The grid is not checked against the live map."""
+        return self._scores(self.ctx.lib.bl_clearance_scores, clearance, scan, poses)
+
+    def debug_leap(self, clearance, scan, pose):
+        """dict of int64 arrays over the used rays of one pose (x, y, theta): first, K, z, zstar, p as debug_cast, and rounds (the
+        entries of the clearance grid the ray read; -1 for a dropped ray)."""
+        return self._debug(self.ctx.lib.bl_clearance_debug_cast, clearance, scan, pose, ("first", "K", "z", "zstar", "p", "rounds"))
+
+    def reweigh_leap(self, pf, clearance, scan):
+        """bl_clearance_reweigh_pf: reweigh() with the leaps behind it."""
+        return self._reweigh(self.ctx.lib.bl_clearance_reweigh_pf, pf, clearance, scan)
 
     def debugSet(self, stage_windows=False, window_bytes=0):
         """Stage the workgroups' windows in LDS when they fit window_bytes (0: 40960).  Off by default: the grid is read directly."""
@@ -1573,6 +1592,50 @@ class RangeTable:
     def close(self):
         if self.h:
             self.ctx.lib.bl_rangetable_destroy(self.h)
+            self.h = None
+
+
+class ClearanceGrid:
+    """Clearance grid (bl_clearance_*, include/botlab_hip.h): per cell the Chebyshev distance to the nearest occupied cell, capped at
+    cap, one uint8, read by BeamModel.scores_leap / reweigh_leap to leap over empty space.  build(grid, occ_min) fills it;
+    update(grid, x0, y0, x1, y1) after the cells of that box (inclusive) changed redoes the box widened by cap.  The grid is never
+    checked against the live map: keeping it current is the caller's job.  cap is an untuned knob."""
+
+    def __init__(self, ctx=None, cap=64):
+        self.ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(self.ctx.lib.bl_clearance_create(self.ctx.h, int(cap), C.byref(h)))
+        self.h = h
+
+    def build(self, grid, occ_min=1):
+        check(self.ctx.lib.bl_clearance_build(self.h, grid.h, int(occ_min)))
+
+    def update(self, grid, x0, y0, x1, y1):
+        check(self.ctx.lib.bl_clearance_update(self.h, grid.h, int(x0), int(y0), int(x1), int(y1)))
+
+    def info(self):
+        """dict: width, height, cap, occ_min, built, bytes."""
+        i = _capi.ClearanceInfo()
+        check(self.ctx.lib.bl_clearance_info(self.h, C.byref(i)))
+        return {k: int(getattr(i, k)) for k, _ in _capi.ClearanceInfo._fields_ if k != "pad"}
+
+    def read(self, x0=0, y0=0, w=None, h=None):
+        """uint8 [h][w]: the entries of a rectangle of cells (default: from (x0, y0) to the far corner)."""
+        i = self.info()
+        w = i["width"] - x0 if w is None else w
+        h = i["height"] - y0 if h is None else h
+        out = np.zeros((max(h, 1), max(w, 1)), np.uint8)
+        check(self.ctx.lib.bl_clearance_read(self.h, int(x0), int(y0), int(w), int(h), out.ctypes.data))
+        return out
+
+    def lastDeviceMs(self):
+        ms = C.c_float()
+        check(self.ctx.lib.bl_clearance_last_device_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.bl_clearance_destroy(self.h)
             self.h = None
 
 

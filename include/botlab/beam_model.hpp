@@ -92,6 +92,30 @@ public:
         debugPlanes(bl_rangetable_debug_lookup, table.device(), "bl_rangetable_debug_lookup", scan, pose, *h, c.z, c.zstar, c.p);
         return c;
     }
+    // scores() with the expected ranges found by leaps over a built clearance grid (ClearanceGridT, clearance_grid.hpp): value for
+    // value the cast's on the map the grid was built on.  The grid is not checked against the live map.
+    template <class Clearance>
+    std::vector<int64_t> scoresLeap(const Clearance& clearance, const Lidar& scan, const std::vector<Pose>& poses)
+    {
+        return scoresBy(bl_clearance_scores, clearance.device(), "bl_clearance_scores", scan, poses);
+    }
+    // a filter's weight units replaced in place by the scoring by leaps (Filter: ParticleFilterT); the beam-weighted posterior pose
+    template <class Filter, class Clearance>
+    Pose reweighLeap(Filter& pf, const Clearance& clearance, const Lidar& scan)
+    {
+        bl_lidar_t v = lidar_view(scan);
+        bl_pose_xyt_t out;
+        check(bl_clearance_reweigh_pf(h_, pf.device(), clearance.device(), &v, &out), "bl_clearance_reweigh_pf");
+        return pose_out<Pose>(out);
+    }
+    // debugCast's columns by leaps; rounds: the entries of the clearance grid each ray read (-1 for a dropped ray)
+    template <class Clearance>
+    BeamCast debugLeap(const Clearance& clearance, const Lidar& scan, const Pose& pose, std::vector<int32_t>* rounds)
+    {
+        BeamCast c;
+        debugPlanes(bl_clearance_debug_cast, clearance.device(), "bl_clearance_debug_cast", scan, pose, c.first, c.K, c.z, c.zstar, c.p, *rounds);
+        return c;
+    }
     BeamTables tables(float cellsPerMeter) const
     {
         BeamTables t;

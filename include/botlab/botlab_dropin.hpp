@@ -456,6 +456,16 @@ public:
         check(bl_rangetable_reweigh_pf(beam.device(), h_, table.device(), &v, &out), "bl_rangetable_reweigh_pf");
         return pose_out<Pose>(out);
     }
+    // (extension) the same with the expected ranges found by leaps over a built clearance grid (ClearanceGridT, clearance_grid.hpp;
+    // bl_clearance_reweigh_pf); the grid is not checked against the live map
+    template <class Beam, class Clearance>
+    Pose reweighBeamLeap(const Beam& beam, const Clearance& clearance, const Lidar& laser)
+    {
+        bl_lidar_t v = lidar_view(laser);
+        bl_pose_xyt_t out;
+        check(bl_clearance_reweigh_pf(beam.device(), h_, clearance.device(), &v, &out), "bl_clearance_reweigh_pf");
+        return pose_out<Pose>(out);
+    }
     bl_pf* device() const { return h_; }                                      // for the device-side extras (bl_pf_encode_particles_lcm ...)
 private:
     bl_pf* h_;

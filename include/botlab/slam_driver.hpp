@@ -27,6 +27,7 @@
 
 #include "beam_model.hpp"
 #include "range_table.hpp"
+#include "clearance_grid.hpp"
 #include "botlab_dropin.hpp"
 #include "likelihood_field.hpp"
 #include "loop_closer.hpp"
@@ -406,13 +407,27 @@ public:
     // first reweigh, instead of casting -- AS LONG AS THE DRIVER HAS NOT UPDATED THE MAP SINCE THE TABLE WAS BUILT.  The driver extends
     // its map in every mode (slam.cpp's mode test is always true), so that holds for the iterations that leave the map alone: all of
     // a global search until it converges, the ones recovery holds back, and the first one otherwise.  From the first map update on the
-    // switch is ignored and the cast is used: bringing the table up to date after every scan would cost more than the casts it saves,
-    // and a stale table is never read.  In every other mode (no map file, poses given, action only) the switch is ignored altogether.
+    // switch is ignored and the reweigh casts (by leaps with setBeamLeapCast, cell by cell without): bringing the table up to date
+    // after every scan would cost more than the casts it saves, and a stale table is never read.  In every other mode (no map file, poses given, action only) the switch is ignored altogether.
     // Off by default, and with it off nothing the driver does changes; set before the first iteration.  beamRangeTableBuilds() and
     // beamRangeTableReweighs(): tables built (0 or 1) and reweighs that read one.
     void setBeamRangeTable(bool on, int headings = 256) { beamTableOn_ = on; beamTableHeadings_ = headings; }
     int beamRangeTableBuilds() const { return beamTableBuilds_; }
     int beamRangeTableReweighs() const { return beamTableReweighs_; }
+    // (extension) Leap cast (ClearanceGridT, clearance_grid.hpp): with the beam model on, the reweigh that would have
+    // cast against the map leaps over a clearance grid of cap `cap` instead, with the cast's results value for value -- on a map that
+    // changes with every scan, where the range table cannot serve.  A current range table keeps precedence while it is current.  The
+    // grid is built from the map before the first leap reweigh; after every map update from then on it is brought up to date in a
+    // box -- the bounding box of the cells of the poses of the last and of this map update (every ray starts between the two),
+    // widened by ceil(maxLaserDistance * cellsPerMeter) + 2 -- and whatever else writes the map (rebuildMap, optimizeHistory,
+    // closeLoops, closeLoopsByPlace) marks it for a whole build before the next reweigh.  THE CAP IS AN UNTUNED KNOB.  Off by
+    // default, and with it off nothing the driver does changes; set before the first iteration.  beamLeapBuilds(),
+    // beamLeapUpdates() and beamLeapReweighs(): whole builds, boxed updates and reweighs by leaps; beamLeapGrid(): the grid, or null.
+    void setBeamLeapCast(bool on, int cap = 64) { beamLeapOn_ = on; beamLeapCap_ = cap; }
+    int beamLeapBuilds() const { return beamLeapBuilds_; }
+    int beamLeapUpdates() const { return beamLeapUpdates_; }
+    int beamLeapReweighs() const { return beamLeapReweighs_; }
+    const ClearanceGridT<Pose, Lidar>* beamLeapGrid() const { return beamLeap_.get(); }
     // (extension) Scan history (ScanHistoryT, map_rebuild.hpp): every iteration that updates the map appends the same
     // scan and the same pose bits to a history of the last `capacity` scans -- in the fused step the pose is read on the device, behind
     // the map update that carries the filter's end.  rebuildMap() writes into the driver's map what sequential map updates of the
@@ -423,11 +438,11 @@ public:
     ScanHistoryT<Pose, Lidar>* scanHistory() const { return history_.get(); }
     void rebuildMap()
     {
-        if (history_ && history_->size() > 0) history_->rebuild(grid_, mapRange(), mapHit_, mapMiss_, 0, history_->size());
+        if (history_ && history_->size() > 0) { history_->rebuild(grid_, mapRange(), mapHit_, mapMiss_, 0, history_->size()); beamLeapStale_ = true; }
     }
     void rebuildMap(const std::vector<Pose>& poses)
     {
-        if (history_ && !poses.empty()) history_->rebuild(grid_, mapRange(), mapHit_, mapMiss_, 0, poses);
+        if (history_ && !poses.empty()) { history_->rebuild(grid_, mapRange(), mapHit_, mapMiss_, 0, poses); beamLeapStale_ = true; }
     }
     // (extension) Pose-graph back end on the history (PoseGraphT, pose_graph.hpp): the nodes are the recorded poses
     // (device to device), the chain is made from the nodes with the information chainInfo (xx, xy, yy, xt, yt, tt) on every edge, the
@@ -612,6 +627,13 @@ private:
     int beamTableHeadings_ = 256;
     std::unique_ptr<RangeTableT<Pose, Lidar> > beamTable_;
     int beamTableBuilds_ = 0, beamTableReweighs_ = 0;
+    // leap cast: switch and cap; the grid (made on first use); stale: a whole build is due before the next reweigh; the pose of the
+    // last map update; the three counters
+    bool beamLeapOn_ = false, beamLeapStale_ = true, beamLeapPoseSet_ = false;
+    int beamLeapCap_ = 64;
+    std::unique_ptr<ClearanceGridT<Pose, Lidar> > beamLeap_;
+    Pose beamLeapPose_;
+    int beamLeapBuilds_ = 0, beamLeapUpdates_ = 0, beamLeapReweighs_ = 0;
     // scan history: capacity (0: off); the history (made at the first map update); what the mapper was made with
     int historyCapacity_ = 0;
     std::unique_ptr<ScanHistoryT<Pose, Lidar> > history_;
@@ -627,9 +649,42 @@ private:
         if (!beam_) beam_.reset(new BeamModelT<Pose, Lidar>(beamParams_));
         const int64_t t = p.utime;
         if (beamTableCurrent()) { p = pf_.reweighBeamTable(*beam_, *beamTable_, scan_); ++beamTableReweighs_; }
+        else if (beamLeapCurrent()) { p = pf_.reweighBeamLeap(*beam_, *beamLeap_, scan_); ++beamLeapReweighs_; }
         else p = pf_.reweighBeam(*beam_, grid_, scan_);
         p.utime = t;
         return p;
+    }
+
+    // true when the reweigh leaps: the switch is on; the grid is made here and built whenever a whole build is due
+    bool beamLeapCurrent()
+    {
+        if (!beamLeapOn_) return false;
+        if (!beamLeap_) beamLeap_.reset(new ClearanceGridT<Pose, Lidar>(beamLeapCap_));
+        if (beamLeapStale_) {
+            beamLeap_->build(grid_, beamParams_.occ_min);
+            ++beamLeapBuilds_;
+            beamLeapStale_ = false;
+        }
+        return true;
+    }
+
+    // after the map update at now_: the built grid brought up to date in the box of the cells the update can have written
+    void beamLeapFollow()
+    {
+        if (!beamLeapOn_) return;
+        const Pose last = beamLeapPoseSet_ ? beamLeapPose_ : now_;
+        beamLeapPose_ = now_;
+        beamLeapPoseSet_ = true;
+        if (!beamLeap_ || beamLeapStale_) return;
+        const double cpm = grid_.cellsPerMeter(), ox = grid_.originInGlobalFrame().x, oy = grid_.originInGlobalFrame().y;
+        const double ax = std::floor((last.x - ox) * cpm), ay = std::floor((last.y - oy) * cpm);
+        const double bx = std::floor((now_.x - ox) * cpm), by = std::floor((now_.y - oy) * cpm);
+        const double lim = 1073741824.0;
+        if (!(std::fabs(ax) < lim && std::fabs(ay) < lim && std::fabs(bx) < lim && std::fabs(by) < lim)) { beamLeapStale_ = true; return; }
+        const int pad = static_cast<int>(std::ceil(static_cast<double>(mapRange()) * cpm)) + 2;
+        beamLeap_->update(grid_, static_cast<int>(ax < bx ? ax : bx) - pad, static_cast<int>(ay < by ? ay : by) - pad,
+                          static_cast<int>(ax > bx ? ax : bx) + pad, static_cast<int>(ay > by ? ay : by) + pad);
+        ++beamLeapUpdates_;
     }
 
     // true when the reweigh may read the range table: the switch is on, the map came from a file and the driver has not updated it
@@ -801,6 +856,7 @@ private:
         } else {
             mapping_.updateMap(scan_, now_, grid_);
             if (recording()) history_->append(scan_, now_);
+            beamLeapFollow();
         }
         if (lfield_ && !how_.mapFromFile) lfield_->compute(grid_);
         how_.mapKnown = true;

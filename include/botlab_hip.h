@@ -1857,6 +1857,72 @@ int bl_rangetable_reweigh_pf(bl_beam* beam, bl_pf* pf, const bl_rangetable* rt, 
 int bl_rangetable_debug_lookup(bl_beam* beam, const bl_rangetable* rt, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_h,
                                int32_t* out_z, int32_t* out_zstar, uint32_t* out_p);
 
+/* ------------------------------------------------------------------ clearance grid (no reference counterpart)
+ * The beam model's cast reads every cell of a ray's walk, and nearly all of them are empty.  The clearance grid holds, per cell, how
+ * far the nearest occupied cell is, so that the walk can leap over the empty stretch: one byte per cell, redone in a box after a map
+ * update, for maps that change (the range table is for maps that do not).  Off unless called: bl_beam_*, bl_rangetable_* and the
+ * filter's update are untouched.
+ *   Handle.  bl_clearance_create(ctx, cap, &cl): cap = C in 1 .. 255, else BL_ERR_ARG.  C IS AN UNTUNED KNOB.
+ *   Entries.  uint8, D[y * W + x] = min(C, the least max(|x - ox|, |y - oy|) over the cells (ox, oy) inside the grid whose log-odds is
+ *     >= occ_min): the Chebyshev distance to the nearest occupied cell, capped.  An occupied cell holds 0; a map without an occupied
+ *     cell holds C everywhere; cells outside the grid are never occupied.
+ *   bl_clearance_build(cl, map, occ_min) (occ_min in 1 .. 127, else BL_ERR_ARG) stores the map's size, origin and cells_per_meter and
+ *     occ_min in the handle and fills the whole grid.  A handle may be built again on another shape or occ_min.  More than 2^30 cells
+ *     are refused with BL_ERR_ARG before anything is allocated.
+ *   bl_clearance_update(cl, map, x0, y0, x1, y1) is called after the cells of the box x0 .. x1, y0 .. y1 (inclusive) changed: every
+ *     entry of the box widened by C on each side and clipped to the grid is computed again (an entry depends on no cell farther
+ *     away), by the same kernels.  The grid then equals byte for byte what build gives on the new map.  A box with x1 < x0 or
+ *     y1 < y0, or one that lies wholly outside the grid, changes nothing.  A map of another shape than the built one: BL_ERR_ARG,
+ *     the grid stays as it was.  Before the first build: BL_ERR_STATE.
+ *   bl_clearance_read(cl, x0, y0, w, h, out) downloads the entries of the cells x0 .. x0 + w - 1, y0 .. y0 + h - 1 (inside the
+ *     grid, else BL_ERR_ARG) as out[(y - y0) * w + (x - x0)]; BL_ERR_STATE before the first build.  bl_clearance_info works at any
+ *     time.  A NULL handle and a map of another ctx are BL_ERR_ARG.
+ *   The leap walk.  Consecutive cells of the beam model's walk are Chebyshev neighbours, so from walk cell k with D = d > 0 the cells
+ *     k + 1 .. k + d - 1 are not occupied and the walk may go on at cell k + d, whose place the walk's closed form gives (one 32-bit
+ *     division).  From k = 0: a cell outside the grid ends the walk with first = K (a walk that has left never comes back); d = 0
+ *     ends it with first = k; otherwise k += d; k >= K ends it with first = K.  first, K and the hit cell equal the cast's for
+ *     every ray; `rounds` counts the entries read.
+ *   Scoring by leaps, bl_clearance_scores(beam, cl, scan, poses, n, out_scores): bl_beam_scores in the frame the grid was built on,
+ *     with the expected range found by the leap walk: the used rays, the geometry, the dropped rays, z, z*, p, lg, the int64 sum, Smax
+ *     and the units equal the cast's value for value.  BL_ERR_STATE: the grid is not built; the beam model's occ_min differs from the
+ *     one the grid was built with; before bl_beam_set_params.  THE GRID IS NOT CHECKED AGAINST THE LIVE MAP: keeping it current is
+ *     the caller's job (bl_clearance_update).
+ *   bl_clearance_reweigh_pf(beam, pf, cl, scan, out_pose) is bl_beam_reweigh_pf with the leaps behind it: the same install of the
+ *     units, the same state rules, the same behaviour under recovery; sharded filters are refused.  bl_clearance_debug_cast returns
+ *     bl_beam_debug_cast's five columns with its conventions and the rounds (-1 for a dropped ray, 0 for a pose that takes no
+ *     part).  bl_beam_units, bl_beam_last_rays and bl_beam_last_device_ms work after this form too; bl_beam_debug_path answers 1.
+ *   How it is computed (bl_clearance.hip), two passes.  k_clr_rows: a wave per 64 cells of a row; the occupancy of these and of as
+ *     many neighbouring 64-cell words as C reaches, each as one ballot; a lane's distance along the row to the nearest set bit by
+ *     count-trailing and count-leading zeros, capped, a uint8 of the intermediate.  k_clr_cols: a thread per cell, threads along x;
+ *     D = min over dy of max(|dy|, row[y + dy]) taken outward from dy = 0 and stopped when |dy| reaches the best so far.
+ *     k_beam_leap (bl_beam.hip): k_beam_cast's launch shape and frame, D read through L2.  No atomics; no workgroup waits for
+ *     another; no result depends on the launch shape.  The intermediate takes as many bytes on the device as the grid. */
+typedef struct bl_clearance bl_clearance;
+typedef struct bl_clearance_info_t {
+    int32_t width, height;             /* of the map built on; 0 before the first build */
+    int32_t cap;
+    int32_t occ_min;                   /* 0 before the first build */
+    int32_t built;                     /* 0 or 1 */
+    int32_t pad;
+    int64_t bytes;                     /* of the grid on the device: width * height */
+} bl_clearance_info_t;                 /* 32 bytes: offsets 0, 4, 8, 12, 16, 20, 24 */
+int bl_clearance_create(bl_ctx* ctx, int cap, bl_clearance** out);
+void bl_clearance_destroy(bl_clearance* cl);
+int bl_clearance_build(bl_clearance* cl, const bl_grid* map, int occ_min);
+int bl_clearance_update(bl_clearance* cl, const bl_grid* map, int x0, int y0, int x1, int y1);
+int bl_clearance_read(bl_clearance* cl, int x0, int y0, int w, int h, uint8_t* out);
+int bl_clearance_info(const bl_clearance* cl, bl_clearance_info_t* out);
+/* device time of the last build's or update's kernels (HIP events around the launches); BL_ERR_STATE before the first */
+int bl_clearance_last_device_ms(const bl_clearance* cl, float* ms);
+/* The beam model scored by leaps.  (Named after the handle they need beside the beam model: the bl_beam_ names are the cast's.)
+ * n host poses in, n scores out; any n >= 0 */
+int bl_clearance_scores(bl_beam* beam, const bl_clearance* cl, const bl_lidar_t* scan, const bl_pose_xyt_t* poses, int n, int64_t* out_scores);
+int bl_clearance_reweigh_pf(bl_beam* beam, bl_pf* pf, const bl_clearance* cl, const bl_lidar_t* scan, bl_pose_xyt_t* out_pose);
+/* bl_beam_last_rays() entries each (room for the scan's num_ranges is always enough); any pointer may be NULL.  The units and the
+ * count that bl_beam_units reads are left as they were. */
+int bl_clearance_debug_cast(bl_beam* beam, const bl_clearance* cl, const bl_lidar_t* scan, const bl_pose_xyt_t* pose, int32_t* out_first,
+                            int32_t* out_K, int32_t* out_z, int32_t* out_zstar, uint32_t* out_p, int32_t* out_rounds);
+
 /* ------------------------------------------------------------------ scan history and map rebuild  
  * A map is otherwise written once, at the pose held at that moment, and the scan is thrown away.  The log keeps the last
  * `capacity_scans` scans on the device -- per scan the KEPT rays exactly as the mapper takes them (ranges, thetas, times; ranges
